@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- the headline benchmark of the MI355X-native SIFT extraction path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 (the first form with N > 1 starts the second one itself, as a child process, before anything touches a GPU)
+
+A plain run sets up, runs the set-up check and the fixed pre-flight as warm-up, times the W + K steps of `value`,
+writes the last timed step's SiftData if --dump-outputs is given, and prints the line.  --full adds every extra figure:
+the literal W + K region below and every leg listed at the end of this text (the same as --legs with all of them);
+--legs selects some of them.
 
 Workload (BASELINE.json configs[2]/[3]): a batch of 64 synthetic 1920x1080 8-bit-valued images per GPU
 (seeded `tile` images pre-blurred to sigma 1.0), 5 octaves, initBlur=1.0, thresh=3.0, edge=10.
@@ -18,13 +23,13 @@ Consecutive steps rotate over --streams HIP streams (default 4, one extractor ea
 batch overlap the kernels of the others; every step is still one complete pass over one batch, and the timed region is
 bracketed by barrier + device-wide synchronisation on both sides.
 
-Measurement protocol (bench_legs/timed.py; fixed, identical on every rank): set-up check -> W warm-up + K timed steps
-exactly as the contract words them (`value_no_preflight_mpix_per_s`) -> --preflight rounds of untimed load (28 steps)
--> W warm-up + K timed steps at the device's steady clocks (`value`).  --preflight 0: the W + K steps alone.
+Measurement protocol (bench_legs/timed.py; fixed, identical on every rank): set-up check -> [with --full or --legs
+only: W warm-up + K timed steps with nothing added, `value_no_preflight_mpix_per_s`] -> --preflight rounds of untimed
+load (28 steps) -> W warm-up + K timed steps at the device's steady clocks (`value`).  --preflight 0: the W + K steps
+alone.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task description).  `value` comes from the timed
-region only.  Everything else on the line is measured in separate, labelled legs after it (bench_legs/*.py, same inputs
-unless the leg says otherwise); `--legs` selects them:
+Prints ONE JSON line on rank 0.  `value` comes from the timed region only.  With --full (or --legs), everything else on
+the line is measured in separate, labelled legs after it (bench_legs/*.py, same inputs unless the leg says otherwise):
   single     the same steps on ONE stream with HIP events per launch: per-stage ms (kernel spans do not overlap)
   two_stage  the reference's LaplaceMulti -> DoG in HBM -> FindPointsMulti pipeline: `roofline` (blur+DoG kernel,
              algorithmic bytes / HIP-event time vs 8 TB/s, the north-star gate)
@@ -83,9 +88,14 @@ def parse_args(argv=None):
     ap.add_argument("--thresh", type=float, default=3.0)
     ap.add_argument("--max-pts", type=int, default=32768)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--legs", default=",".join(ALL_LEGS),
-                    help="comma-separated extra legs after the timed region (%s); 'none' = only the timed region"
-                         % ", ".join(ALL_LEGS))
+    ap.add_argument("--full", action="store_true",
+                    help="run every extra leg after the timed region (the full line); off: the timed region alone")
+    ap.add_argument("--legs", default=None,
+                    help="comma-separated extra legs after the timed region (%s); 'none' = only the timed region.  "
+                         "Default: all of them with --full, none without" % ", ".join(ALL_LEGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the SiftData of the last timed step (rank 0's images) as DIR/<name>.npy: "
+                         "bench_legs/dump.py says what each file holds")
     ap.add_argument("--two-stage", action="store_true",
                     help="time the reference's two-stage pipeline (DoG planes in HBM) instead of the fused detection")
     ap.add_argument("--streams", type=int, default=0,
@@ -141,6 +151,8 @@ def main():
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
     if args.dry_launch:
         raise SystemExit(dry_launch(args))
+    if args.legs is None:
+        args.legs = ",".join(ALL_LEGS) if args.full else "none"
     legs = set() if args.legs in ("none", "") else set(x for x in args.legs.split(",") if x)
     unknown = legs - set(ALL_LEGS)
     if unknown:
@@ -151,7 +163,7 @@ def main():
     import torch
     import torch.distributed as dist
 
-    from bench_legs import configs, content, cpu, host, match, repeat, single, timed, two_stage
+    from bench_legs import configs, content, cpu, dump, host, match, repeat, single, timed, two_stage
     from cusift_amd import capi, synth
 
     # Rank 0 prints exactly ONE line on stdout.  Libraries write there too (RCCL prints a version banner on
@@ -189,16 +201,20 @@ def main():
 
     timed.setup(R)
     timed.run(R)  # `value`; R.out exists on rank 0 from here on
+    if R.captured is not None:
+        dump.write(args.dump_outputs, R.captured)
+        R.captured = None
 
     # ================================================================================================================
-    # Extra legs (rank 0's GPU only; not part of `value`).  With N > 1 the other ranks wait at the final barrier.
+    # Extra legs (--full or --legs; rank 0's GPU only; not part of `value`).  With N > 1 the other ranks wait at the
+    # final barrier.
     # ================================================================================================================
-    R.blur_b, R.down_b, R.find_b = algorithmic_bytes(R.w, R.h, args.octaves, R.B)
-    R.traffic = load_profile_json("traffic.json")
-    R.valu = load_profile_json("valu.json")
-    R.isa_mix = load_profile_json("isa_mix.json")
     out, ex, E = R.out, R.ex, R.E
     if rank == 0 and legs:
+        R.blur_b, R.down_b, R.find_b = algorithmic_bytes(R.w, R.h, args.octaves, R.B)
+        R.traffic = load_profile_json("traffic.json")
+        R.valu = load_profile_json("valu.json")
+        R.isa_mix = load_profile_json("isa_mix.json")
         torch.cuda.synchronize()
         if "repeat" in legs and not R.use_dist:
             repeat.run(R)

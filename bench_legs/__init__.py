@@ -5,6 +5,7 @@ object (bench_legs.common) and adds its keys to `run.out`, the ONE JSON line ran
   launch   spawn_ranks / dry_launch: `python bench.py --gpus N` as a plain command, and its CPU rehearsal over gloo
   models   gather_model / tiled_model: committed PREDICTIONS of the multi-GPU steps (no multi-GPU node was reachable)
   timed    inputs, the exchange, pre-flight, the W + K steps of `value`
+  dump     --dump-outputs: the last timed step's SiftData as .npy files
   repeat   the timed region again (spread, from idle, the pyramid policy A/B)
   single   one stream with HIP events per launch: stage table, VALU rooflines of the two kernels that own the step
   two_stage  the reference's LaplaceMulti -> DoG in HBM -> FindPointsMulti pipeline: `roofline` (the north-star gate)

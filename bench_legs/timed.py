@@ -2,10 +2,11 @@
 
 Protocol (identical on every rank, nothing in it adapts to what it measures):
   1. set-up check    every extractor runs the batch once per output slot; all must report identical keypoint counts
-  2. literal region  W warm-up steps, barrier + synchronize, K timed steps, barrier + synchronize -- the driver contract's
-                     wording with nothing added: `value_no_preflight_mpix_per_s`.  On a device that idled through the
-                     process's start-up the first ~20 ms of load run 5-12 % slow (tools/probe_rampup.py), so with the driver's
-                     W = 5 (5 ms) this region measures the clock ramp as much as the kernels.
+  2. literal region  (--full or --legs only: a figure of its own, not part of `value`) W warm-up steps, barrier +
+                     synchronize, K timed steps, barrier + synchronize -- the W + K steps with nothing added:
+                     `value_no_preflight_mpix_per_s`.  On a device that idled through the process's start-up the first
+                     ~20 ms of load run 5-12 % slow (tools/probe_rampup.py), so with W = 5 (5 ms) this region measures the
+                     clock ramp as much as the kernels.
   3. pre-flight      --preflight rounds (default 7) of one batch per extractor output slot: a FIXED number of untimed steps
                      (28 with four streams) that keep the device loaded; config.preflight_steps says how many ran.
   4. timed region    W warm-up steps, barrier + synchronize, K timed steps, barrier + synchronize: `value` -- the same K
@@ -17,6 +18,7 @@ import time
 
 import numpy as np
 
+from . import dump
 from .common import METRIC
 from .models import gather_model
 
@@ -123,6 +125,7 @@ def run(R):
         e = pipe.submitted % E
         key = (e, (pipe.submitted // E) % pipe.n_slots)
         pts, cnt, ev = pipe.submit(d_imgs, ready=slot_free.pop(key, None))
+        state["last"] = (pts, cnt)
         if use_dist:
             ticket = None
             with torch.cuda.stream(side_stream):
@@ -181,8 +184,9 @@ def run(R):
             for _, cnt_t in x.slots:
                 if not torch.equal(cnt_t, ref_counts):
                     raise SystemExit("bench.py: set-up check: extractors disagree on the keypoint counts of the same batch")
-        # 2. the contract's wording with nothing added
-        elapsed_literal = region(K)
+        # 2. the W + K steps with nothing added: an extra figure, measured only when extra legs run
+        if R.legs:
+            elapsed_literal = region(K)
         # 3. a fixed number of untimed steps, the same on every rank; nothing but enqueueing between here and the
         #    timed region's fence
         R.preflight_steps = preflight * E * n_slots
@@ -192,6 +196,9 @@ def run(R):
     forks_before = sum(x.ctx.forks() for x in exs)
     elapsed = region(K)
     R.forks_timed = sum(x.ctx.forks() for x in exs) - forks_before
+    R.captured = None
+    if args.dump_outputs and rank == 0:  # the last timed step's SiftData, before any later step reuses its slot
+        R.captured = dump.capture(capi, *state["last"], ex.max_pts)
     gathered = state["gathered"]
     R.gather_waits = (comm.host_waits(), comm.host_wait_ms()) if comm is not None else None
     if R.legs and not use_dist:
@@ -210,10 +217,11 @@ def run(R):
                 k: (R.stage_overlapped[k][0] + t[k][0], R.stage_overlapped[k][1] + t[k][1]) for k in t}
             x.ctx.timing_enable(False)
 
-    # N > 1: the same K steps WITHOUT the exchange, right behind the timed region -- what gather_model needs as the
-    # extraction's own time, so that "measured - predicted" means something (max over ranks, like the timed region)
+    # N > 1 with extra legs: the same K steps WITHOUT the exchange, right behind the timed region -- what gather_model
+    # needs as the extraction's own time, so that "measured - predicted" means something (max over ranks, like the
+    # timed region)
     extraction_only_ms = None
-    if use_dist:
+    if use_dist and R.legs:
         drain()
         torch.cuda.synchronize()
         if world > 1:
@@ -280,8 +288,8 @@ def run(R):
             "timed_region_forks": int(R.forks_timed),
             "preflight_steps": R.preflight_steps,
             "preflight_note": "protocol (bench_legs/timed.py), identical on every rank: set-up check (all extractors must "
-                              "report identical keypoint counts) -> W + K steps exactly as the contract words it "
-                              "(value_no_preflight_mpix_per_s) -> a FIXED number of untimed steps (preflight_steps) -> W "
+                              "report identical keypoint counts) -> [--full: W + K steps with nothing added, "
+                              "value_no_preflight_mpix_per_s] -> a FIXED number of untimed steps (preflight_steps) -> W "
                               "warm-up + K timed steps at steady clocks (`value`); --preflight 0 runs the W + K steps alone",
             "pyramid_in_detect": ex.ctx.get_policy(capi.POLICY_PYRAMID_IN_DETECT),
             "pyramid_in_detect_note": "-1 = the library's default (include/cusift_amd.h): a pipelining caller's call of >= 2 "
@@ -289,21 +297,23 @@ def run(R):
                                       "writes the next octave's image (ScaleDown's arithmetic, bit for bit) -- no "
                                       "ScaleDown launch, no memset",
         },
-        # the contract's W + K steps with nothing before them but the set-up check (the like-for-like figure of rounds 1-4)
-        "value_no_preflight_mpix_per_s": round(R.total_pix / (elapsed_literal / K) / 1e6, 2),
-        "ms_per_step_no_preflight": round(elapsed_literal / K * 1e3, 4),
         "keypoints_per_s_in_hbm": round(total_kp / (elapsed / K), 1),
         "keypoints_per_step": total_kp,
     }
-    # (N = 1: the prediction is for the wire format an N > 1 run of this command line would use)
+    if R.legs:
+        # the W + K steps with nothing before them but the set-up check (the like-for-like figure of rounds 1-4)
+        out["value_no_preflight_mpix_per_s"] = round(R.total_pix / (elapsed_literal / K) / 1e6, 2)
+        out["ms_per_step_no_preflight"] = round(elapsed_literal / K * 1e3, 4)
+    # an extra of --full (N = 1: the prediction is for the wire format an N > 1 run of this command line would use)
     rec_b = gatherer.record_bytes if gatherer is not None else (
         160 if args.gather_compact else (588 if args.gather_exact else 540))
-    out["gather_model"] = gather_model(local_kp, rec_b, extraction_only_ms if use_dist else R.ms_per_step,
-                                       R.LAG if use_dist else E)
-    if use_dist:
-        out["gather_model"]["extraction_ms_per_step_source"] = (
-            "the same K steps run without the exchange right behind the timed region (max over ranks)")
-    out["gather_model"]["step_of_this_run_includes_an_exchange"] = bool(use_dist)
+    if R.legs:
+        out["gather_model"] = gather_model(local_kp, rec_b, extraction_only_ms if use_dist else R.ms_per_step,
+                                           R.LAG if use_dist else E)
+        if use_dist:
+            out["gather_model"]["extraction_ms_per_step_source"] = (
+                "the same K steps run without the exchange right behind the timed region (max over ranks)")
+        out["gather_model"]["step_of_this_run_includes_an_exchange"] = bool(use_dist)
     if use_dist:
         out["config"]["gather_impl"] = R.gather_impl
         out["config"]["rccl_library"] = capi.Comm.library()
@@ -319,7 +329,8 @@ def run(R):
         out["config"]["rccl_ranks"] = info.get("lib_ranks")
         out["config"]["rccl_version"] = info.get("lib_version")
         out["config"]["ms_per_step_by_rank"] = [round(float(t) / K * 1e3, 4) for t in per_rank_elapsed]
-        ex_ms = out["gather_model"]["ranks"].get(str(world), {}).get("eff_1.0", {}).get("ms_per_step_overlapped")
+        ex_ms = out["gather_model"]["ranks"].get(str(world), {}).get("eff_1.0", {}).get(
+            "ms_per_step_overlapped") if "gather_model" in out else None
         if ex_ms:
             out["gather_model"]["measured_minus_predicted_ms_at_link_peak"] = round(R.ms_per_step - ex_ms, 4)
         if R.gather_waits is not None:

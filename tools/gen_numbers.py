@@ -7,8 +7,8 @@ README.md that was MEASURED is typed by hand.
     python tools/gen_numbers.py --check    # exit 1 if a block differs from what the records give (tests/test_docs_numbers.py)
 
 Records (all written on an MI355X box by the commands named in profiles/README.md):
-  bench_steps20_warmup5.json   python bench.py --steps 20 --warmup 5      (the driver's command)
-  bench_default.json           python bench.py
+  bench_steps20_warmup5.json   python bench.py --full --steps 20 --warmup 5   (the driver's steps, every leg)
+  bench_default.json           python bench.py --full
   cpp_threads.txt              tests/cpp/threads_dropin + pipeline_dropin
   golden_shares.json           tools/golden_shares.py (CPU: the oracle against both golden files)
   gpu_tests_tail.txt, fuzz_parity.txt, fuzz_tiled.txt, fuzz_match.txt
@@ -55,8 +55,8 @@ def numbers_block():
     dfl = load("bench_default.json")
     L = []
     a = L.append
-    a("Records: `profiles/r06/bench_steps20_warmup5.json` (the driver's command, `python bench.py --steps 20 --warmup 5`) and")
-    a("`profiles/r06/bench_default.json` (`python bench.py`: 50 steps) — one MI355X each, the builder's boxes; rates differ by")
+    a("Records: `profiles/r06/bench_steps20_warmup5.json` (the driver's steps, `python bench.py --full --steps 20 --warmup 5`)")
+    a("and `profiles/r06/bench_default.json` (`python bench.py --full`: 50 steps) — one MI355X each, the builder's boxes; rates differ by")
     a("3–7 % from box to box. Gpix/s = 1e9 base pixels per second; one step = 64 × 1920 × 1080 = 132.7 Mpix.")
     a("")
     a("| the step (64 × 1080p, SiftData left in HBM) | driver's form | default form |")
