@@ -1,7 +1,6 @@
 # Python-free build of libcusift_amd.so (the HIP kernels + the C ABI of include/cusift_amd.h) for gfx950.
 #
 #   make                 cusift_amd/libcusift_amd.so  (one object per .hip under build/obj, then one link)
-#   make lab             cusift_amd/libcusift_amd_lab.so     (-DCUSIFT_LAB: the tuning overrides of the A/B tools)
 #   make stamps          cusift_amd/libcusift_amd_stamps.so  (-DCUSIFT_STAMPS: phase stamps in describe_all_kernel)
 #   make oracle          the CPU parity oracle (test infrastructure; never linked by the product)
 #   make cpp-tests       the reference's own test programs re-written against include/cuSIFT.h, plain g++
@@ -28,12 +27,10 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vec
             -Wno-unused-function
 
 LIB        := $(ROOT)/cusift_amd/libcusift_amd.so
-LIB_LAB    := $(ROOT)/cusift_amd/libcusift_amd_lab.so
 LIB_STAMPS := $(ROOT)/cusift_amd/libcusift_amd_stamps.so
 
-.PHONY: all lab stamps ab oracle cpp-tests check install clean
+.PHONY: all stamps oracle cpp-tests check install clean
 all: $(LIB)
-lab: $(LIB_LAB)
 stamps: $(LIB_STAMPS)
 
 # $(call variant,<name>,<extra flags>,<library>)
@@ -46,15 +43,7 @@ $(3): $(addprefix $(OBJROOT)/$(1)/,$(addsuffix .o,$(SOURCES)))
 	mv -f $$@.tmp $$@
 endef
 $(eval $(call variant,product,,$(LIB)))
-$(eval $(call variant,lab,-DCUSIFT_LAB,$(LIB_LAB)))
 $(eval $(call variant,stamps,-DCUSIFT_STAMPS,$(LIB_STAMPS)))
-
-# an experiment's build for a same-box A/B (tools/ab_libs.sh): make ab NAME=x DEFS="-DCUSIFT_SOMETHING" -> tools/ab/x.so
-NAME ?= variant
-$(eval $(call variant,ab_$(NAME),$(DEFS),$(ROOT)/tools/ab/$(NAME).so))
-ab:
-	@mkdir -p $(ROOT)/tools/ab
-	$(MAKE) -f $(lastword $(MAKEFILE_LIST)) $(ROOT)/tools/ab/$(NAME).so NAME=$(NAME) DEFS="$(DEFS)"
 
 oracle:
 	$(MAKE) -C $(ROOT)/oracle
@@ -72,4 +61,4 @@ install: $(LIB)
 	install -m 0644 $(ROOT)/cmake/cusift_amdConfig.cmake $(DESTDIR)$(PREFIX)/lib/cmake/cusift_amd/
 
 clean:
-	rm -rf $(ROOT)/build/obj $(LIB) $(LIB_LAB) $(LIB_STAMPS)
+	rm -rf $(ROOT)/build/obj $(LIB) $(LIB_STAMPS)

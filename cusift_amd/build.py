@@ -1,11 +1,7 @@
 """Builds libcusift_amd.so (HIP kernels + C ABI) for gfx950 in-tree with hipcc -- by running the top-level Makefile, the
 one recipe of this repository (a C++ caller needs no Python: `make`, or the CMakeLists.txt next to it).
 
-    python -m cusift_amd.build [--force] [--lab] [--stamps]
-
---lab builds libcusift_amd_lab.so with -DCUSIFT_LAB: the same kernels, plus the tuning overrides the A/B scripts under
-tools/ read from the environment (CUSIFT_*_ROWS_*, CUSIFT_DETECT_WAVES, ...; select it with CUSIFT_AMD_LIB=<path>).  The
-product library reads none of them.
+    python -m cusift_amd.build [--force] [--stamps]
 
 --stamps builds libcusift_amd_stamps.so with -DCUSIFT_STAMPS: describe_all_kernel with shader-clock stamps at its phase
 boundaries (tools/describe_stamps.py).
@@ -49,7 +45,6 @@ def find_hipcc():
 
 
 ROOT = os.path.dirname(HERE)
-LAB_LIB = os.path.join(HERE, "libcusift_amd_lab.so")
 STAMPS_LIB = os.path.join(HERE, "libcusift_amd_stamps.so")  # --stamps: -DCUSIFT_STAMPS, for tools/describe_stamps.py
 
 
@@ -59,7 +54,7 @@ def is_stale():
                            stderr=subprocess.DEVNULL) != 0
 
 
-def build(force=False, verbose=False, lab=False, stamps=False):
+def build(force=False, verbose=False, stamps=False):
     """Compile the HIP extension for gfx950 if missing or older than its sources (make decides). Returns the path.
     One object per translation unit under build/obj, compiled in parallel; the link goes to a temporary file that is
     renamed onto the library, so a process that LOADS the library never sees a half-written shared object.  Builders are
@@ -68,7 +63,7 @@ def build(force=False, verbose=False, lab=False, stamps=False):
     second builder then finds everything up to date)."""
     import fcntl
 
-    target, lib = ("stamps", STAMPS_LIB) if stamps else (("lab", LAB_LIB) if lab else ("all", LIB))
+    target, lib = ("stamps", STAMPS_LIB) if stamps else ("all", LIB)
     cmd = ["make", "-C", ROOT, "-j%d" % max(1, min(8, os.cpu_count() or 1)), target, "HIPCC=" + find_hipcc()]
     if force:
         cmd.insert(1, "-B")
@@ -85,4 +80,4 @@ def build(force=False, verbose=False, lab=False, stamps=False):
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True, lab="--lab" in sys.argv, stamps="--stamps" in sys.argv))
+    print(build(force="--force" in sys.argv, verbose=True, stamps="--stamps" in sys.argv))

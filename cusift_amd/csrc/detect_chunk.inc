@@ -24,8 +24,8 @@
     return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin, edge.voff, yc * pitch * 4, 0));
   };
   // Only the waves whose 256 columns reach the image's left or right border replace anything (two strips of eight at
-  // 1080p): a wave-uniform branch around the seven selects of the fix-up (round 5, same-box A/B tools/ab_libs.sh base
-  // edgeu: 64 x 1080p 1.154 -> 1.133 ms for a lone caller, 0.955 -> 0.944 on four streams; profiles/r05/ab_edge_uniform.txt)
+  // 1080p): a wave-uniform branch around the seven selects of the fix-up (round 5, same-box A/B:
+  // 64 x 1080p 1.154 -> 1.133 ms for a lone caller, 0.955 -> 0.944 on four streams; profiles/r05/ab_edge_uniform.txt)
   const bool edge_wave = bx == 0 || bx * kDetStrip - kDetHaloLanes * kBlurCols + 64 * kBlurCols > w;
   auto fix = [&](f4 v) -> f4 { return edge_wave ? edge(v) : v; };
 

@@ -18,42 +18,6 @@ int cusift_fail(int code, const char *fmt, ...) {
   return code;
 }
 
-Knobs read_knobs() {
-  Knobs k;
-  // (the product build reads NO environment variable here: CUSIFT_OCTAVE_OVERLAP, the one it read until round 5 for
-  // unchanged callers of the C++ shim, is now read by that shim -- include/cuSIFT.h -- and set through cusift_ctx_set_policy)
-#ifdef CUSIFT_LAB
-  if (const char *e = getenv("CUSIFT_OCTAVE_OVERLAP")) k.octave_overlap = std::max(0, std::min(3, atoi(e)));
-  auto text = [](const char *name) -> const char * { return getenv(name); };
-  auto num = [&](const char *name, int unset) { const char *e = text(name); return e ? atoi(e) : unset; };
-  k.rows_per_wave = num("CUSIFT_ROWS_PER_WAVE", 0);
-  static const char *const stage[kKnobStages] = {"SCALEDOWN", "LAPLACE", "FINDPOINTS", "DETECT"};
-  for (int i = 0; i < kKnobStages; ++i) {
-    char name[64];
-    snprintf(name, sizeof(name), "CUSIFT_%s_ROWS_LO", stage[i]);
-    k.rows_lo[i] = num(name, 0);
-    snprintf(name, sizeof(name), "CUSIFT_%s_ROWS_HI", stage[i]);
-    k.rows_hi[i] = num(name, 0);
-  }
-  if (const char *e = text("CUSIFT_DETECT_ROWS_COEF")) k.detect_rows_coef = atof(e);
-  k.detect_waves = num("CUSIFT_DETECT_WAVES", 0);
-  k.laplace_waves = num("CUSIFT_LAPLACE_WAVES", 0);
-  k.laplace_aux = num("CUSIFT_LAPLACE_AUX", -1);
-  k.no_ident = text("CUSIFT_NO_IDENT") != nullptr;
-  k.side_debug = text("CUSIFT_SIDE_DEBUG") != nullptr;
-  k.stage_all_mb = num("CUSIFT_STAGE_ALL_MB", 0);
-  k.small_pyramid = num("CUSIFT_SMALL_PYRAMID", -1);
-  // the policy keys as well, for the A/B scripts that drive bench.py from the shell
-  k.force_generic = text("CUSIFT_FORCE_GENERIC") != nullptr;
-  k.match_splits = num("CUSIFT_MATCH_SPLITS", 0);
-  k.stage_all = num("CUSIFT_STAGE_ALL", -1);
-  k.no_multi = text("CUSIFT_NO_MULTI") != nullptr;
-  k.pyramid_in_detect = num("CUSIFT_PYRAMID_IN_DETECT", -1);
-  k.unordered_coarse = text("CUSIFT_UNORDERED_COARSE") != nullptr;
-#endif
-  return k;
-}
-
 int fold_spans(cusift_ctx *ctx) {
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (auto &s : ctx->spans) {
@@ -69,7 +33,7 @@ int fold_spans(cusift_ctx *ctx) {
 }
 
 int make_plan(Plan &pl, int n_images, int w, int h, int pitch, const cusift_params *prm, bool fork,
-              bool stage_all, size_t stage_all_limit) {
+              bool stage_all) {
   if (!prm) return fail(CUSIFT_ERR_INVALID, "params is NULL");
   if (n_images < 1 || w < 1 || h < 1 || pitch < w)
     return fail(CUSIFT_ERR_INVALID, "bad geometry n=%d w=%d h=%d pitch=%d", n_images, w, h, pitch);
@@ -106,7 +70,7 @@ int make_plan(Plan &pl, int n_images, int w, int h, int pitch, const cusift_para
   off = align_up_sz(off + (size_t)n_images * kMaxOctaves * sizeof(unsigned int), 256);
   const size_t per_octave = (size_t)n_images * prm->max_pts * kStagedRecBytes;
   pl.fork = fork && pl.n_oct >= 2 && per_octave <= kMaxStagedBytes;
-  pl.staged_octaves = (stage_all && pl.n_oct >= 2 && per_octave * pl.n_oct <= stage_all_limit) ? pl.n_oct : (pl.fork ? 1 : 0);
+  pl.staged_octaves = (stage_all && pl.n_oct >= 2 && per_octave * pl.n_oct <= kMaxStagedAllBytes) ? pl.n_oct : (pl.fork ? 1 : 0);
   if (pl.staged_octaves) {
     pl.staged_off = off;
     off = align_up_sz(off + per_octave * pl.staged_octaves, 256);
@@ -144,20 +108,12 @@ int ensure_arena(cusift_ctx *ctx, size_t bytes) {
 
 // rows each wave marches: as large as possible (less halo re-read) while the launch still has
 // >= ~2 waves per SIMD on 256 CUs.
-int pick_rows(const cusift_ctx *ctx, int h, int strips, int n_images, int lo, int hi) {
-  if (ctx->knobs.rows_per_wave > 0) return ctx->knobs.rows_per_wave;  // tuning/experiments only
+int pick_rows(int h, int strips, int n_images, int lo, int hi) {
   const long target_waves = 256L * 4 * 2 * 2;
   long r = (long)h * strips * n_images / target_waves;
   if (r < lo) r = lo;
   if (r > hi) r = hi;
   return (int)r;
-}
-
-// [lo, hi] of pick_rows for a stage, overridable for tuning experiments (Knobs)
-void rows_bounds(const cusift_ctx *ctx, int stage, int &lo, int &hi) {
-  if (ctx->knobs.rows_hi[stage] > 0) hi = ctx->knobs.rows_hi[stage];
-  if (ctx->knobs.rows_lo[stage] > 0) lo = ctx->knobs.rows_lo[stage];
-  lo = std::min(lo, hi);
 }
 
 void scale_down_taps(ScaleDownTaps &T, float variance) {
@@ -274,9 +230,9 @@ extern "C" int cusift_init(int device) {
 // to a staging list in the arena, the ScaleDown chain and the coarser detections run on the context's stream as
 // before, the streams join, and describe_all_kernel moves the staged keypoints behind the coarser ones while it
 // describes them -- so SiftData comes out coarsest octave first, and saturates coarsest first, exactly as before.
-// Measured on MI355X (tools/probe_octave_overlap.py, one stream, back to back): 64 x 1080p 1.527 -> 1.356 ms, 16: 0.478 ->
-// 0.429, 4: 0.213 -> 0.200 -- but ONE frame 0.132 -> 0.138 ms, and its recorded graph 0.148 -> 0.187: the two
-// cross-stream waits cost more than a frame's tails.  So the fork is taken from kSideStreamMinPixels up (three 1080p
+// Measured on MI355X (one stream, back to back; a later run: profiles/r03/octave_overlap.txt): 64 x 1080p 1.527 ->
+// 1.356 ms, 16: 0.478 -> 0.429, 4: 0.213 -> 0.200 -- but ONE frame 0.132 -> 0.138 ms, and its recorded graph 0.148 ->
+// 0.187: the two cross-stream waits cost more than a frame's tails.  So the fork is taken from kSideStreamMinPixels up (three 1080p
 // frames), never inside a recording, never with the stage timers on (they bracket launches on one stream).
 constexpr size_t kSideStreamMinPixels = 6u << 20;
 bool wants_side_stream(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h) {
@@ -297,9 +253,6 @@ bool wants_side_stream(const cusift_ctx *ctx, const cusift_params *prm, int n_im
 // instantiation).  So: a lone caller whenever the lists fit, a pipelining caller up to eight 1080p frames' worth of
 // pixels per call.  Not with the per-octave stage sequence, the generic kernels or the stage timers on.
 constexpr size_t kListsMaxPixelsPipelined = 16u << 20;
-size_t stage_all_limit(const cusift_ctx *ctx) {
-  return ctx->knobs.stage_all_mb > 0 ? (size_t)ctx->knobs.stage_all_mb << 20 : kMaxStagedAllBytes;
-}
 bool wants_stage_all(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h) {
   if (ctx->knobs.stage_all == 0 || ctx->knobs.force_generic) return false;
   if (!prm || !prm->fused_detect || n_images < 1 || n_images > kMaxFlatImages) return false;
@@ -314,8 +267,8 @@ bool wants_stage_all(const cusift_ctx *ctx, const cusift_params *prm, int n_imag
 // re-reading per 64 x 1080p, a fifth of a lone caller's step -- disappear for ~5 % more vector instructions in the
 // detection, and the octaves are searched finest first (lists per octave).  What it costs is the one-launch detection
 // of the coarser octaves: a chain of dependent launches has a tail per octave, which a caller with several batches in
-// flight fills with the other batches' kernels and a lone caller does not.  Measured on MI355X (tools/ab_pyramid.py,
-// profiles/r05/ab_pyramid_by_size.txt; 1080p frames per call, ms per call, ScaleDown chain first -> every octave):
+// flight fills with the other batches' kernels and a lone caller does not.  Measured on MI355X
+// (profiles/r05/ab_pyramid_by_size.txt; 1080p frames per call, ms per call, ScaleDown chain first -> every octave):
 //   four calls in flight  1: 0.0409 -> 0.0390   3: 0.0776 -> 0.0725   8: 0.1645 -> 0.1450   16: 0.288 -> 0.267   64: 1.033 -> 0.976
 //   a lone caller         1: 0.0649 -> 0.0973  16: 0.342 -> 0.392    32: 0.645 -> 0.662    48: 0.941 -> 0.932   64: 1.241 -> 1.153
 // A lone caller's middle ground is "octave 0 only" (1): octave 0's detection hands octave 1 over -- the large ScaleDown is
@@ -424,9 +377,6 @@ int ensure_side_stream(cusift_ctx *ctx) {
       break;
     }
     const bool beside = beside_ms < 1.25f * std::max(alone, 0.08f);
-    if (ctx->knobs.side_debug)
-      fprintf(stderr, "cusift: side stream candidate %d: probe chain alone %.1f us, beside the candidate %.1f us -> %s\n",
-              attempt, alone * 1e3f, beside_ms * 1e3f, beside ? "kept" : "rejected");
     if (beside) {
       ctx->side = cand;
       ctx->side_probed = true;
@@ -468,7 +418,6 @@ int ctx_create_impl(cusift_ctx **out, int device, void *hip_stream, bool borrow)
   HIP_TRY(hipSetDevice(device));
   cusift_ctx *ctx = new cusift_ctx();
   ctx->device = device;
-  ctx->knobs = read_knobs();
   (void)hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device);
   if (ctx->num_cus < 1) ctx->num_cus = 256;
   if (borrow) {
@@ -558,7 +507,7 @@ extern "C" int cusift_ctx_reserve(cusift_ctx *ctx, int n_images, int w, int h, c
   TRY(enter(ctx));
   Plan pl;
   TRY(make_plan(pl, n_images, w, h, ialign_up(w, 128), p, wants_side_stream(ctx, p, n_images, w, h),
-                wants_stage_all(ctx, p, n_images, w, h), stage_all_limit(ctx)));
+                wants_stage_all(ctx, p, n_images, w, h)));
   // + one pitched upload image for cusift_extract_host
   return ensure_arena(ctx, pl.total + align_up_sz((size_t)h * ialign_up(w, 128) * sizeof(float), 256));
 }
@@ -706,7 +655,7 @@ extern "C" int cusift_kernel_occupancy(const char *kernel, int *blocks_per_cu, i
   if (k == "detect_fused")  // single-wave workgroups, a 10.5 KB candidate list each
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, detect_fused_kernel<false, (int)sizeof(cusift_point), false>, t = 64,
                                                      kDetectWaveLdsFloats * sizeof(float));
-  else if (k == "laplace_multi") e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, laplace_multi_fast_kernel<0>, t, 0);
+  else if (k == "laplace_multi") e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, laplace_multi_fast_kernel<2>, t, 0);
   else if (k == "find_points") e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, find_points_fast_kernel, t, 0);
   else if (k == "scale_down") e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, scale_down_fast_kernel, t, 0);
   else if (k == "describe_all") e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, describe_all_kernel, t = 64, 0);

@@ -101,15 +101,11 @@ struct TimedSpan {
   int stage;
 };
 
-// Launch policy of a context.  The PRODUCT build reads no environment variable for it (CUSIFT_OCTAVE_OVERLAP, for an
-// unchanged caller of the C++ shim, is read by the shim: include/cuSIFT.h); everything a test needs to force a driver path is
-// set per context through cusift_ctx_set_policy; the tuning overrides of the A/B tools (rows per wave, waves per
-// workgroup, cache policy of the DoG stores, ...) exist only in a -DCUSIFT_LAB build, which reads them from the
-// environment ONCE, when a context is created -- nothing on a launch path looks at the environment in either build.
+// Launch policy of a context, set per context through cusift_ctx_set_policy; a context starts with the defaults
+// below.  Nothing here comes from the environment (CUSIFT_OCTAVE_OVERLAP, for an unchanged caller of the C++ shim, is
+// read by the shim: include/cuSIFT.h), and nothing on a launch path looks at the environment.
 // 0 / negative = "not set".
-enum { kKnobScaleDown = 0, kKnobLaplace, kKnobFindPoints, kKnobDetect, kKnobStages };
 struct Knobs {
-  // ---- policy (cusift_ctx_set_policy) ----
   int octave_overlap = 0;                            // CUSIFT_POLICY_SIDE_STREAM: 0 never (default), 1 eligible calls, 2 eligible calls
                                                      // after the concurrency probe, 3 every call (tests)
   int stage_all = -1;                                // CUSIFT_POLICY_OCTAVE_LISTS: -1 by size (default), 0 never, 1 whenever it fits
@@ -118,18 +114,6 @@ struct Knobs {
   int match_splits = 0;                              // CUSIFT_POLICY_MATCH_SPLITS
   bool tiled_per_octave = false;                     // CUSIFT_POLICY_TILED_PER_OCTAVE (read by cusift_tiled_create)
   int pyramid_in_detect = -1;                        // CUSIFT_POLICY_PYRAMID_IN_DETECT: -1 by size, 0 never, 1 octave 0, 2 every octave
-  // ---- tuning (CUSIFT_LAB builds only) ----
-  int rows_per_wave = 0;                             // CUSIFT_ROWS_PER_WAVE: every stencil stage
-  int rows_lo[kKnobStages] = {0}, rows_hi[kKnobStages] = {0};  // CUSIFT_<STAGE>_ROWS_LO / _HI
-  double detect_rows_coef = 0.0;                     // CUSIFT_DETECT_ROWS_COEF
-  int detect_waves = 0, laplace_waves = 0;           // CUSIFT_DETECT_WAVES, CUSIFT_LAPLACE_WAVES (waves per workgroup)
-  int laplace_aux = -1;                              // CUSIFT_LAPLACE_AUX: cache policy of the DoG stores
-  bool no_ident = false;                             // CUSIFT_NO_IDENT
-  bool side_debug = false;                           // CUSIFT_SIDE_DEBUG: print the side stream's concurrency probe
-  int stage_all_mb = 0;                              // CUSIFT_STAGE_ALL_MB: largest staging for all octaves (0: default)
-  int small_pyramid = -1;                            // CUSIFT_SMALL_PYRAMID: 0 never, 1 always, default by size
-  bool unordered_coarse = false;                     // CUSIFT_UNORDERED_COARSE: a TIMING experiment, results are wrong unless
-                                                     // the same batch is extracted over and over (sift_driver.hip)
 };
 
 struct cusift_ctx {
@@ -242,11 +226,10 @@ struct MultiOctave {
 // defined in sift_context.hip / sift_stages.hip / sift_driver.hip
 int fold_spans(cusift_ctx *ctx);
 int make_plan(Plan &pl, int n_images, int w, int h, int pitch, const cusift_params *prm, bool fork = false,
-              bool stage_all = false, size_t stage_all_limit = kMaxStagedAllBytes);
+              bool stage_all = false);
 int ensure_dog(cusift_ctx *ctx, size_t bytes);
 int ensure_arena(cusift_ctx *ctx, size_t bytes);
-int pick_rows(const cusift_ctx *ctx, int h, int strips, int n_images, int lo, int hi);
-void rows_bounds(const cusift_ctx *ctx, int stage, int &lo, int &hi);
+int pick_rows(int h, int strips, int n_images, int lo, int hi);
 void scale_down_taps(ScaleDownTaps &T, float variance);
 void laplace_taps_table(float init_blur, float taps[8 * 16]);
 void find_params(FindParams &P, float peak_thresh, float edge_thresh, float subsampling);
@@ -254,7 +237,6 @@ void frac_consts(int frac_bits, float &q, float &inv_q);
 int enter(cusift_ctx *ctx);
 int check_launch(const char *what);
 bool wants_side_stream(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h);
-size_t stage_all_limit(const cusift_ctx *ctx);
 bool wants_stage_all(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h);
 int wants_pyramid_in_detect(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h);
 int ensure_side_stream(cusift_ctx *ctx);

@@ -67,7 +67,7 @@ __device__ __forceinline__ void stage_patch(const float *__restrict__ img, int w
   // row, lane = column, written by the memory pipeline straight into LDS (`buffer_load_dword ... lds`: LDS address =
   // M0 + 4 * lane, lanes at or beyond the patch width masked off): no staging registers, so ALL rows of the patch are
   // in flight at once and nothing but one vmcnt(0) stands between the last load and the first tap.
-  // History (phase stamps, tools/exp_describe_stamps.sh; 64 x 1080p, cycles per keypoint in this function):
+  // History (phase stamps, profiles/r02_ab/describe_all_stamps_and_sensitivity.txt; 64 x 1080p, cycles per keypoint in this function):
   //   row arithmetic on the scalar unit, 8 loads in flight, register staging + ds_write   5,450
   //   row offsets by lane + v_readlane, 16 in flight                                      4,380
   //   LDS-DMA                                                                             3,580   (wide patches: 9,700 -> 4,300)
@@ -542,11 +542,7 @@ __device__ __forceinline__ float kp_orientation(SH &S, const TEX &tex, const Ori
 #pragma unroll
   for (int rep = 0; rep < kReps; ++rep) {
     bool near;
-#ifdef CUSIFT_AB_ORI_FORMULA  // (an A/B build: the reference's formula for every sample, as rounds 1-5)
-    near = true;
-#else
     sbin[rep] = ori_bin_shortcut(dy[rep], dx[rep], near);  // the bin without an angle (see ori_bin_shortcut)
-#endif
     near_edge = near_edge || near;
     const float grad = sqrtf(dx[rep] * dx[rep] + dy[rep] * dy[rep]);
     swgt[rep] = grad * S.gauss[xd[rep]] * S.gauss[yd[rep]];
@@ -1222,7 +1218,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
     wave_sync();
     STAMP(S, 2);
     // the patch loads have been waited for, so has the atomic issued before them: the next item's index is here.
-    // (Tried on top of this and dropped, tools/exp_describe_stamps.sh: forming the next keypoint's geometry between the
+    // (Tried on top of this and dropped, by the phase stamps: forming the next keypoint's geometry between the
     // stages -- the ~600 cycles it saves here come back, and more, in the descriptor stage; touching the next patch's
     // lines with two LDS-DMA loads so that they are in L2 by the time they are staged -- no gain.)
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(raw) : : "memory");  // (already satisfied after stage_patch)

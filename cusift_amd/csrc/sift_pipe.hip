@@ -161,7 +161,7 @@ extern "C" int cusift_pipe_create(cusift_pipe **out, int device, int n_images, i
   // FOUR streams in all -- two extraction streams (consecutive batches alternate; a batch's records are packed on its own
   // extraction stream), the upload stream and the copy stream: HIP maps streams onto four hardware queues, and a fifth
   // or sixth busy stream shares a queue with one of these -- an upload then waits behind another batch's kernels.
-  // Measured, 64 x 1080p 8-bit frames, a fresh process each (tools/probe_pipe_depth.py): three extraction streams + a pack
+  // Measured, 64 x 1080p 8-bit frames, a fresh process each: three extraction streams + a pack
   // stream 2.64 ms per batch at depth 4 (3.02 at depth 3), two + a pack stream 2.55, two with the pack on the extraction
   // stream 2.51 (2.49 at depth 3) -- 0.93 of the upload's own time; the link-bound pipeline has no use for a third batch
   // in extraction (1.1 ms of GPU time per 2.3 ms of upload).

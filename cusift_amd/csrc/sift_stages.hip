@@ -82,17 +82,15 @@ int scale_down_impl(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_str
   StageTimer t(ctx, CUSIFT_STAGE_SCALEDOWN);
   if (fast) {
     const int strips = idiv_up(ow, 124);  // kDownStrip
-    // measured (tools/probe_rows.py, 64 images): 1920x1080 -> 960x540 streams from HBM and likes short chunks
+    // measured (64 images): 1920x1080 -> 960x540 streams from HBM and likes short chunks
     // (r = 4: 0.137 ms, r = 32: 0.150 ms); the smaller levels are served by the Infinity Cache and like tall ones
-    int rlo = 4, rhi = (long)oh * strips * n_images > 200000 ? 4 : 32;
-    rows_bounds(ctx, kKnobScaleDown, rlo, rhi);
-    const int rows = pick_rows(ctx, oh, strips, n_images, rlo, rhi);
+    const int rows = pick_rows(oh, strips, n_images, 4, (long)oh * strips * n_images > 200000 ? 4 : 32);
     dim3 grid(idiv_up(strips, kWavesPerBlock), idiv_up(oh, rows), n_images);
     hipLaunchKernelGGL(scale_down_fast_kernel, grid, dim3(256), 0, ctx->stream, d_dst, dst_pitch, (long)dst_stride,
                        d_src, w, h, src_pitch, (long)src_stride, rows, T, src_rw, dst_row0, r_begin, r_end);
   } else {
     const int strips = idiv_up(ow, 64);
-    const int rows = pick_rows(ctx, oh, strips, n_images, 4, 16);
+    const int rows = pick_rows(oh, strips, n_images, 4, 16);
     dim3 grid(strips, idiv_up(idiv_up(oh, rows), kWavesPerBlock), n_images);
     hipLaunchKernelGGL(scale_down_kernel, grid, dim3(256), 0, ctx->stream, d_dst, dst_pitch, (long)dst_stride, d_src,
                        w, h, src_pitch, (long)src_stride, rows, T);
@@ -106,9 +104,7 @@ int scale_down_impl(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_str
 // count one ScaleDown per octave).
 constexpr size_t kPyramidSmallPixels = (size_t)5 << 19;  // 2.6 Mpixel
 bool wants_small_pyramid(const cusift_ctx *ctx, int n_images, int w, int h) {
-  if (ctx->knobs.small_pyramid == 0 || ctx->knobs.force_generic) return false;
-  if (ctx->knobs.small_pyramid > 0) return true;
-  return !ctx->timing && (size_t)n_images * (size_t)w * (size_t)h <= kPyramidSmallPixels;
+  return !ctx->knobs.force_generic && !ctx->timing && (size_t)n_images * (size_t)w * (size_t)h <= kPyramidSmallPixels;
 }
 
 // describe_all_kernel may form the lists' running sums itself (no join_counts_kernel: a small call saves the dispatch) --
@@ -215,11 +211,10 @@ extern "C" int cusift_laplace_multi(cusift_ctx *ctx, const float *d_img, int w, 
                      (img_stride % 4 == 0) && (dog_stride % 4 == 0) && (((size_t)h * pitch) % 4 == 0);
   const int strips = idiv_up(w, kBlurStrip);
   // short chunks: the halo rows they re-read come from L2, and the chip sustains a visibly higher store rate when
-  // many short waves write than when few long ones do (tools/ab_laplace_rows.sh with non-temporal stores, 64x1080p, all
-  // octaves at one r: r = 3 0.263 ms per launch, 6: 0.242, 8: 0.234, 12: 0.239, 16: 0.243, 32: 0.270)
-  int rlo = 3, rhi = 8;
-  rows_bounds(ctx, kKnobLaplace, rlo, rhi);
-  const int rows = pick_rows(ctx, h, strips, n_images, rlo, rhi);
+  // many short waves write than when few long ones do (profiles/r02_ab/laplace_rows_and_nt_stores.txt: non-temporal
+  // stores, 64x1080p, all octaves at one r: r = 3 0.263 ms per launch, 6: 0.242, 8: 0.234, 12: 0.239, 16: 0.243,
+  // 32: 0.270)
+  const int rows = pick_rows(h, strips, n_images, 3, 8);
   dim3 grid(strips, idiv_up(idiv_up(h, rows), kWavesPerBlock), n_images);
   // fast path: 16-byte aligned rows (any width >= 4), 32-bit buffer offsets
   const bool fast = vec_ok && w >= 4 && ((size_t)h * pitch * sizeof(float) < (1ull << 31)) && !ctx->knobs.force_generic;
@@ -231,21 +226,12 @@ extern "C" int cusift_laplace_multi(cusift_ctx *ctx, const float *d_img, int w, 
         TP.k[q][j].x = taps[16 * (2 * q) + j];
         TP.k[q][j].y = taps[16 * (2 * q + 1) + j];
       }
-    int wpb = kWavesPerBlock;
-    if (ctx->knobs.laplace_waves > 0) wpb = std::min(4, ctx->knobs.laplace_waves);  // experiments only
-    dim3 fgrid(strips, idiv_up(idiv_up(h, rows), wpb), n_images);
     // DoG planes are written once and read much later (by FindPointsMulti): non-temporal stores keep them from
-    // displacing the source rows' halo in L2 -- measured on one box (tools/ab_laplace_aux.sh): 4.35 -> 4.63 TB/s for
-    // this kernel and 3.87 -> 4.18 TB/s for the FindPointsMulti that follows
-    const int aux = ctx->knobs.laplace_aux >= 0 ? ctx->knobs.laplace_aux : 2;  // experiments: cache policy of the stores
-#define LAUNCH_LAPLACE(A)                                                                                         \
-  hipLaunchKernelGGL(laplace_multi_fast_kernel<A>, fgrid, dim3(64 * wpb), 0, ctx->stream, d_img, d_dog, w, h, pitch, \
-                     (long)img_stride, (long)dog_stride, rows, TP)
-    if (aux == 2) LAUNCH_LAPLACE(2);
-    else if (aux == 16) LAUNCH_LAPLACE(16);
-    else if (aux == 18) LAUNCH_LAPLACE(18);
-    else LAUNCH_LAPLACE(0);
-#undef LAUNCH_LAPLACE
+    // displacing the source rows' halo in L2 -- measured on one box: 4.35 -> 4.63 TB/s for this kernel and 3.87 ->
+    // 4.18 TB/s for the FindPointsMulti that follows (profiles/r02_ab/laplace_rows_and_nt_stores.txt: the same A/B at
+    // every chunk height)
+    hipLaunchKernelGGL(laplace_multi_fast_kernel<2>, grid, dim3(256), 0, ctx->stream, d_img, d_dog, w, h, pitch,
+                       (long)img_stride, (long)dog_stride, rows, TP);
   } else {
     hipLaunchKernelGGL(laplace_multi_kernel, grid, dim3(256), 0, ctx->stream, d_img, d_dog, w, h, pitch,
                        (long)img_stride, (long)dog_stride, rows, vec_ok, T);
@@ -266,9 +252,7 @@ extern "C" int cusift_find_points_multi(cusift_ctx *ctx, const float *d_dog, int
   const int vec_ok = (pitch % 2 == 0) && (((uintptr_t)d_dog % 8) == 0) && (dog_stride % 2 == 0) &&
                      (((size_t)h * pitch) % 2 == 0);
   const int strips = idiv_up(w, kFindStrip);
-  int rlo = 4, rhi = 16;  // tools/probe_rows.py, 64x1080p: r = 16 0.770 ms, r = 32 0.803 ms
-  rows_bounds(ctx, kKnobFindPoints, rlo, rhi);
-  const int rows = pick_rows(ctx, h, strips, n_images, rlo, rhi);
+  const int rows = pick_rows(h, strips, n_images, 4, 16);  // 64x1080p: r = 16 0.770 ms, r = 32 0.803 ms
   dim3 grid(strips, idiv_up(idiv_up(h, rows), kWavesPerBlock), n_images);
   const bool fast = vec_ok && w >= 2 &&
                     ((size_t)kNumDog * h * pitch * sizeof(float) < (1ull << 31)) && !ctx->knobs.force_generic;
@@ -291,25 +275,22 @@ bool detect_fused_ok(const float *d_img, int w, int h, int pitch, size_t img_str
 
 // Chunk height of the fused detection: centre rows per wave (see the comment in detect_impl).
 int detect_rows(const cusift_ctx *ctx, int rows_total, int strips, int n_images, int concurrent) {
-  int rows_lo = 2, rows_hi = concurrent >= 3 ? 240 : (concurrent >= 2 ? 112 : 64);
-  rows_bounds(ctx, kKnobDetect, rows_lo, rows_hi);
+  const int rows_lo = 2, rows_hi = concurrent >= 3 ? 240 : (concurrent >= 2 ? 112 : 64);
   const double wave_rows = (double)rows_total * strips * n_images;
-  double coef = concurrent >= 2 ? 0.09 : 0.05;
-  if (ctx->knobs.detect_rows_coef > 0.0) coef = ctx->knobs.detect_rows_coef;  // tuning experiments only
-  double r = coef * sqrt(wave_rows);
+  double r = (concurrent >= 2 ? 0.09 : 0.05) * sqrt(wave_rows);
   // Three or more batches in flight (round 5, the detections of one batch are a chain of launches now): the other batches'
   // kernels fill whatever a launch leaves idle, so a LARGE launch is best cut into about as many chunks as the chip holds
   // waves at once -- 1.17 x (CUs x 4 SIMDs x 2 waves) = 2400 on MI355X -- i.e. chunk height proportional to the work, not
   // to its square root: the window fill and the two extra rows of a chunk are then paid ~5 times per strip instead of ~16.
-  // tools/ab_pyramid.py with the lab build's CUSIFT_DETECT_ROWS_COEF / _HI, four streams, ms per call, rows of octave 0:
+  // profiles/r05/ab_detect_rows.txt; four streams, ms per call, rows of octave 0:
   // 64 frames 67: 0.977, 119: 0.955, 164: 0.947, 223: 0.945, 298: 0.952, 446: 1.000;  32 frames 47: 0.505, 105: 0.489,
   // 158: 0.489;  16 frames 33: 0.274, 74: 0.271, 111: 0.287;  8 frames 24: 0.154, 79: 0.182;  three streams, 64 frames
   // 67: 0.982, 134: 0.960, 186: 0.959;  two streams 67: 1.018, 119: 1.059, 223: 1.103 (stays on the square-root rule).
-  if (concurrent >= 3 && ctx->knobs.detect_rows_coef <= 0.0) r = std::max(r, wave_rows / (1.17 * ctx->num_cus * 8.0));
+  if (concurrent >= 3) r = std::max(r, wave_rows / (1.17 * ctx->num_cus * 8.0));
   int rows = std::max(rows_lo, std::min(rows_hi, (int)lround(r)));
   // equal chunks: 1080 rows at 37 per chunk are 29 x 37 + 7 -- thirty chunks of 36 end together (a lone caller's
   // 64 x 1080p 1.108 -> 1.102 ms, three interleaved runs each; four streams: unchanged)
-  if (ctx->knobs.detect_rows_coef <= 0.0) rows = std::max(rows_lo, idiv_up(rows_total, idiv_up(rows_total, rows)));
+  rows = std::max(rows_lo, idiv_up(rows_total, idiv_up(rows_total, rows)));
   return rows;
 }
 
@@ -341,7 +322,7 @@ int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, si
   // Chunk height.  A chunk of r centre rows costs r + 2 blurred rows (+ an 8-row window fill), so tall chunks waste
   // the least arithmetic -- but the launch ends with a tail in which the last chunks run on a part-empty chip, and
   // that tail grows with r.  Minimising (r + c)/r * work + k * r gives r ~ sqrt(work): r = coef * sqrt(rows * strips *
-  // images).  Measured on MI355X, 64 x 1080p (tools/ab_detect_rows.sh, profiles/r02_ab/): a launch that has the GPU to
+  // images).  Measured on MI355X, 64 x 1080p (profiles/r02_ab/detect_chunk_height_*.txt): a launch that has the GPU to
   // itself was fastest at coef 0.022-0.035 with the round-1 kernel and is at 0.05 since the candidates are refined in
   // batches (0.03: 0.873 ms, 0.04: 0.862, 0.05: 0.850, 0.07: 0.883; a chunk's fill and its two extra rows weigh more
   // now that a row with a candidate no longer costs 3,300 cycles); with consecutive batches on
@@ -357,25 +338,22 @@ int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, si
   }
   // Single-wave workgroups: a workgroup's wave slots and LDS are released only when its slowest wave ends, and the
   // threshold pre-test makes the waves' run times uneven -- measured 64x1080p, r = 16: 4 waves per workgroup 0.693 ms,
-  // 2: 0.645 ms, 1: 0.630 ms (tools/probe_rows.py with CUSIFT_DETECT_WAVES).
-  int wpb = 1;
-  if (ctx->knobs.detect_waves > 0) wpb = std::min(4, ctx->knobs.detect_waves);  // experiments only
-  dim3 grid(strips, idiv_up(idiv_up(rows_total, rows), wpb), n_images);
-  const size_t cube_bytes = (size_t)wpb * kDetectWaveLdsFloats * sizeof(float);  // the wave's candidate list
+  // 2: 0.645 ms, 1: 0.630 ms.
+  dim3 grid(strips, idiv_up(rows_total, rows), n_images);
+  const size_t cube_bytes = kDetectWaveLdsFloats * sizeof(float);  // the wave's candidate list
   // levels 0 and 1 both identity (initBlur >= their sigma)?  then the kernel passes them through
-  bool ident0 = true;
+  bool ident = true;
   for (int lv = 0; lv < 2; ++lv)
-    for (int j = 0; j < 9; ++j) ident0 = ident0 && (taps[16 * lv + j] == (j == kBlurRadius ? 1.0f : 0.0f));
+    for (int j = 0; j < 9; ++j) ident = ident && (taps[16 * lv + j] == (j == kBlurRadius ? 1.0f : 0.0f));
   StageTimer t(ctx, CUSIFT_STAGE_DETECT);
   constexpr int kWhole = (int)sizeof(cusift_point);
-  const bool ident = ident0 && !ctx->knobs.no_ident;
   auto kernel = down ? (ident ? detect_fused_kernel<true, kStagedRecBytes, true> : detect_fused_kernel<false, kStagedRecBytes, true>)
               : heads ? (ident ? detect_fused_kernel<true, kStagedRecBytes, false> : detect_fused_kernel<false, kStagedRecBytes, false>)
                       : (ident ? detect_fused_kernel<true, kWhole, false> : detect_fused_kernel<false, kWhole, false>);
   DownOut dn;
   memset(&dn, 0, sizeof(dn));
   if (down) dn = *down;
-  hipLaunchKernelGGL(kernel, grid, dim3(64 * wpb), cube_bytes, side ? ctx->side : ctx->stream, d_img, w, h, pitch,
+  hipLaunchKernelGGL(kernel, grid, dim3(64), cube_bytes, side ? ctx->side : ctx->stream, d_img, w, h, pitch,
                      (long)img_stride, d_points, max_pts, d_counters, rows, TP, P, rw, cy_begin, cy_end, dn);
   return check_launch("detect_multi");
 }
@@ -403,7 +381,7 @@ int detect_multi_impl(cusift_ctx *ctx, const MultiOctave *octaves, int n_octaves
         o.T.k[q][j].x = taps[16 * (2 * q) + j];
         o.T.k[q][j].y = taps[16 * (2 * q + 1) + j];
       }
-    bool ident0 = !ctx->knobs.no_ident;  // levels 0 and 1 both identity (initBlur >= their sigma)?
+    bool ident0 = true;  // levels 0 and 1 both identity (initBlur >= their sigma)?
     for (int lv = 0; lv < 2; ++lv)
       for (int j = 0; j < 9; ++j) ident0 = ident0 && (taps[16 * lv + j] == (j == kBlurRadius ? 1.0f : 0.0f));
     o.ident = ident0 ? 1 : 0;

@@ -183,24 +183,8 @@ __global__ void __launch_bounds__(256) laplace_multi_kernel(const float *__restr
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
 __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-#ifdef CUSIFT_BLUR_BPERMUTE
-// experiment (tools/ab_libs.sh): the blur's neighbour exchange on the LDS crossbar (ds_bpermute_b32: no VALU issue slot)
-// instead of DPP moves (slow-class VALU instructions, 18 % of the blur's)
-__device__ __forceinline__ float bperm(int addr, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ f2 dpp_prev2(f2 v) {
-  const int a = (((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) - 1) & 63) * 4;
-  return f2{bperm(a, v.x), bperm(a, v.y)};
-}
-__device__ __forceinline__ f2 dpp_next2(f2 v) {
-  const int a = (((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) + 1) & 63) * 4;
-  return f2{bperm(a, v.x), bperm(a, v.y)};
-}
-#else
 __device__ __forceinline__ f2 dpp_prev2(f2 v) { return f2{from_prev_lane(v.x), from_prev_lane(v.y)}; }
 __device__ __forceinline__ f2 dpp_next2(f2 v) { return f2{from_next_lane(v.x), from_next_lane(v.y)}; }
-#endif
 
 template <int kStoreAux>
 __global__ void __launch_bounds__(256) laplace_multi_fast_kernel(const float *__restrict__ img,
@@ -296,10 +280,8 @@ __global__ void __launch_bounds__(256) laplace_multi_fast_kernel(const float *__
     win[8] = nxt;
   }
 }
-template __global__ void laplace_multi_fast_kernel<0>(const float *, float *, int, int, int, long, long, int, LaplaceTapsPk);
+// kStoreAux: cache policy of the DoG stores; the library launches only 2, non-temporal (cusift_laplace_multi)
 template __global__ void laplace_multi_fast_kernel<2>(const float *, float *, int, int, int, long, long, int, LaplaceTapsPk);
-template __global__ void laplace_multi_fast_kernel<16>(const float *, float *, int, int, int, long, long, int, LaplaceTapsPk);
-template __global__ void laplace_multi_fast_kernel<18>(const float *, float *, int, int, int, long, long, int, LaplaceTapsPk);
 
 // ------------------------------------------------------------------------------------------------
 // ScaleDown, fast path (16-byte aligned source rows, any w >= 4, 8-byte aligned destination rows).
@@ -645,7 +627,7 @@ __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf
 // FindPointsMulti, fast path (8-byte aligned DoG rows: pitch % 2 == 0, any w >= 2, block < 2 GiB): the same test and the
 // same refinement as find_points_kernel, with buffer_load_dwordx2 on a wave-uniform row base, the next
 // row of all 7 planes requested one iteration ahead, and v_min3/v_max3 trees.  (Non-temporal loads were tried and
-// lose: 4.2 -> 3.6 TB/s, tools/ab_findpoints.sh -- the 3-row window's re-reads want the L2.)
+// lose: 4.2 -> 3.6 TB/s -- the 3-row window's re-reads want the L2.)
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) find_points_fast_kernel(const float *__restrict__ dog, int w, int h, int pitch,
                                                               long dog_stride, cusift_point *__restrict__ points,
@@ -825,7 +807,7 @@ __device__ __forceinline__ void blur_dog_row(const f4 (&win)[9], const LaplaceTa
   }
 }
 
-// Per-wave list of CANDIDATES in LDS, refined 64 at a time.  Measured (tools/exp_detect_parts.sh, 64 x 1080p): refining
+// Per-wave list of CANDIDATES in LDS, refined 64 at a time.  Measured (profiles/r02_ab/detect_stamps_and_parts.txt, 64 x 1080p): refining
 // each candidate where it is found -- one or two active lanes walking ~150 dependent instructions with three IEEE
 // divisions and an exp2, ~0.25 times per wave-row -- cost 21 % of the fused kernel although it is 1 % of its
 // arithmetic.  Now the detecting lane only copies the 19 DoG values its refinement reads (from the wave's cube) and its

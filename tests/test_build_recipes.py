@@ -2,6 +2,7 @@
 drive it); an installed tree is found by find_package(cusift_amd) and a consumer links the reference's detector test
 against it with its ordinary C++ compiler (the reference is a CMake project: CMakeLists.txt:45-72)."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -21,6 +22,35 @@ def test_python_build_is_the_makefile():
         assert flag in text
     for flag in b.HIPCC_FLAGS:  # the tools' copy of the flags says what the Makefile says
         assert flag in ("-shared",) or flag.replace("gfx950", "$(ARCH)") in text, flag
+
+
+def test_one_product_build_and_no_dangling_tool_paths():
+    """The product sources compile one way: their only preprocessor conditionals are the phase stamps (CUSIFT_STAMPS),
+    sift_math.h's header guard and its host/device switch -- no experiment switch grows back.  And every tools/ path that
+    the product and its documents cite exists."""
+    csrc = os.path.join(ROOT, "cusift_amd", "csrc")
+    allowed = {"#ifdef CUSIFT_STAMPS": None,  # (any file)
+               "#ifndef CUSIFT_SIFT_MATH_H": "sift_math.h", "#if defined(__HIPCC__) || defined(__HIP__)": "sift_math.h"}
+    stray = []
+    for name in sorted(os.listdir(csrc)):
+        for n, line in enumerate(open(os.path.join(csrc, name), errors="replace"), 1):
+            text = " ".join(line.split("//")[0].replace("# ", "#").split())
+            if re.match(r"#(if|ifdef|ifndef|elif)\b", text) and allowed.get(text, "") not in (None, name):
+                stray.append("%s:%d: %s" % (name, n, text))
+    assert not stray, stray
+
+    cited = {}
+    paths = [os.path.join(ROOT, f) for f in ("README.md", "DESIGN.md", "INTEGRATION.md", "BASELINE.md", "bench.py")]
+    for d in ("cusift_amd", "include", "bench_legs"):
+        for dirpath, dirnames, files in os.walk(os.path.join(ROOT, d)):
+            dirnames[:] = [x for x in dirnames if x != "__pycache__"]
+            paths += [os.path.join(dirpath, f) for f in files if not f.endswith((".so", ".o", ".pyc"))]
+    for path in paths:
+        for ref in re.findall(r"(?<![\w/.])tools/[\w./-]*\w", open(path, errors="replace").read()):
+            cited.setdefault(ref, os.path.relpath(path, ROOT))
+    assert cited  # the pattern finds what the documents cite
+    missing = {ref: where for ref, where in cited.items() if not os.path.exists(os.path.join(ROOT, ref))}
+    assert not missing, missing
 
 
 @pytest.mark.skipif(shutil.which("cmake") is None, reason="cmake not installed")

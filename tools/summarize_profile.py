@@ -204,7 +204,7 @@ def main():
             entry["valu_wave_insts_per_launch"] = insts
             entry["launches_profiled"] = len(sv["SQ_INSTS_VALU"])
             entry["counted_in"] = "the one-stream pass (--streams 1 --pyramid-in-detect 2 --legs single)"
-        if "SQ_LDS_IDX_ACTIVE" in pk and "GRBM_GUI_ACTIVE" in pk:  # only when tools/pmc_lds.sh passes are present
+        if "SQ_LDS_IDX_ACTIVE" in pk and "GRBM_GUI_ACTIVE" in pk:  # only when a pmc pass collected both counters
             gui = sum(pk["GRBM_GUI_ACTIVE"]) / len(pk["GRBM_GUI_ACTIVE"])
             entry["lds_busy"] = round(sum(pk["SQ_LDS_IDX_ACTIVE"]) / len(pk["SQ_LDS_IDX_ACTIVE"]) / (256.0 * gui / 8.0), 4)
         if "SQ_WAVES" in pk:
