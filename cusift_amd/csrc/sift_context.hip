@@ -18,7 +18,7 @@ int cusift_fail(int code, const char *fmt, ...) {
   return code;
 }
 
-int fold_spans(cusift_ctx *ctx) {
+static int fold_spans(cusift_ctx *ctx) {
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (auto &s : ctx->spans) {
     float t = 0.f;
@@ -32,88 +32,14 @@ int fold_spans(cusift_ctx *ctx) {
   return CUSIFT_OK;
 }
 
-int make_plan(Plan &pl, int n_images, int w, int h, int pitch, const cusift_params *prm, bool fork,
-              bool stage_all) {
-  if (!prm) return fail(CUSIFT_ERR_INVALID, "params is NULL");
-  if (n_images < 1 || w < 1 || h < 1 || pitch < w)
-    return fail(CUSIFT_ERR_INVALID, "bad geometry n=%d w=%d h=%d pitch=%d", n_images, w, h, pitch);
-  if (n_images > 65535) return fail(CUSIFT_ERR_INVALID, "at most 65535 images per batch (grid.z), got %d", n_images);
-  if (prm->max_pts < 1) return fail(CUSIFT_ERR_INVALID, "max_pts must be >= 1");
-  int n = std::max(1, std::min(prm->num_octaves, kMaxOctaves));
-  pl.w[0] = w;
-  pl.h[0] = h;
-  pl.p[0] = pitch;
-  pl.blur[0] = prm->init_blur;
-  pl.sub[0] = prm->subsampling;
-  pl.n_oct = 1;
-  for (int o = 1; o < n; ++o) {
-    int ww = pl.w[o - 1] / 2, hh = pl.h[o - 1] / 2;  // integer division, cuSIFT.cu:182
-    if (ww < 1 || hh < 1) break;
-    pl.w[o] = ww;
-    pl.h[o] = hh;
-    pl.p[o] = ialign_up(ww, 128);  // cuSIFT.cu:183
-    // cuSIFT.cu:188: float totInitBlur = (float)sqrt(initBlur*initBlur + 0.5f*0.5f) / 2.0f;
-    float tot = (float)sqrt(pl.blur[o - 1] * pl.blur[o - 1] + 0.5f * 0.5f) / 2.0f;
-    pl.blur[o] = tot;
-    pl.sub[o] = pl.sub[o - 1] * 2.0f;
-    pl.n_oct = o + 1;
-  }
-  size_t off = 0;
-  pl.base_off[0] = 0;
-  for (int o = 1; o < pl.n_oct; ++o) {
-    pl.base_off[o] = off;
-    off = align_up_sz(off + (size_t)n_images * pl.h[o] * pl.p[o] * sizeof(float), 256);
-  }
-  pl.first_off = off;  // per-octave snapshots of the counters (fstPts), or the segments' counters
-  off = align_up_sz(off + (size_t)n_images * kMaxOctaves * sizeof(unsigned int), 256);
-  pl.seg_end_off = off;  // join_counts_kernel's running sums, [image][segment]
-  off = align_up_sz(off + (size_t)n_images * kMaxOctaves * sizeof(unsigned int), 256);
-  const size_t per_octave = (size_t)n_images * prm->max_pts * kStagedRecBytes;
-  pl.fork = fork && pl.n_oct >= 2 && per_octave <= kMaxStagedBytes;
-  pl.staged_octaves = (stage_all && pl.n_oct >= 2 && per_octave * pl.n_oct <= kMaxStagedAllBytes) ? pl.n_oct : (pl.fork ? 1 : 0);
-  if (pl.staged_octaves) {
-    pl.staged_off = off;
-    off = align_up_sz(off + per_octave * pl.staged_octaves, 256);
-  }
-  pl.total = off;
-  return CUSIFT_OK;
-}
-
-int ensure_dog(cusift_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->dog_bytes) return CUSIFT_OK;
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  ctx->scratch_gen++;
-  if (ctx->dog) HIP_TRY(hipFree(ctx->dog));
-  ctx->dog = nullptr;
-  ctx->dog_bytes = 0;
-  hipError_t e = hipMalloc((void **)&ctx->dog, bytes);
-  if (e != hipSuccess) return fail(CUSIFT_ERR_NOMEM, "DoG hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  ctx->dog_bytes = bytes;
-  return CUSIFT_OK;
-}
-
+// Arena offsets (Plan) are multiples of 256 and hipMalloc returns memory aligned to at least that, so whatever lives in
+// the arena is 256-byte aligned: the octave driver decides its kernels without looking at an arena address.
 int ensure_arena(cusift_ctx *ctx, size_t bytes) {
   if (bytes <= ctx->arena_bytes) return CUSIFT_OK;
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  ctx->scratch_gen++;
   ctx->seg_clean_ptr = nullptr;
-  if (ctx->arena) HIP_TRY(hipFree(ctx->arena));
-  ctx->arena = nullptr;
-  ctx->arena_bytes = 0;
-  hipError_t e = hipMalloc((void **)&ctx->arena, bytes);
-  if (e != hipSuccess) return fail(CUSIFT_ERR_NOMEM, "arena hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  ctx->arena_bytes = bytes;
+  TRY(grow_scratch(ctx, ctx->arena, ctx->arena_bytes, bytes, "arena ", true));
+  if ((uintptr_t)ctx->arena % 256) return fail(CUSIFT_ERR_HIP, "hipMalloc returned an arena that is not 256-byte aligned");
   return CUSIFT_OK;
-}
-
-// rows each wave marches: as large as possible (less halo re-read) while the launch still has
-// >= ~2 waves per SIMD on 256 CUs.
-int pick_rows(int h, int strips, int n_images, int lo, int hi) {
-  const long target_waves = 256L * 4 * 2 * 2;
-  long r = (long)h * strips * n_images / target_waves;
-  if (r < lo) r = lo;
-  if (r > hi) r = hi;
-  return (int)r;
 }
 
 void scale_down_taps(ScaleDownTaps &T, float variance) {
@@ -127,49 +53,6 @@ void scale_down_taps(ScaleDownTaps &T, float variance) {
   T.k[0] = k[0];
   T.k[1] = k[1];
   T.k[2] = k[2];
-}
-
-void laplace_taps_table(float init_blur, float taps[8 * 16]) {
-  // cuSIFT.cu:239-240,400-412.  Rule of this build: var <= 1e-6 => identity (the reference produces
-  // NaN taps at var == 0 and an inverted kernel at var < 0; see DESIGN.md "degenerate initBlur").
-  const float baseBlur = powf(2.0f, -1.0f / kNumScales);
-  const float diffScale = powf(2.0f, 1.0f / kNumScales);
-  float scale = baseBlur;
-  memset(taps, 0, sizeof(float) * 8 * 16);
-  for (int i = 0; i < kNumLevels; i++) {
-    float kernelSum = 0.0f;
-    float var = scale * scale - init_blur * init_blur;
-    float *k = taps + 16 * i;
-    if (var <= 1e-6f) {
-      k[kBlurRadius] = 1.0f;
-    } else {
-      for (int j = -kBlurRadius; j <= kBlurRadius; j++) {
-        k[j + kBlurRadius] = (float)expf(-(double)j * j / 2.0 / var);
-        kernelSum += k[j + kBlurRadius];
-      }
-      for (int j = -kBlurRadius; j <= kBlurRadius; j++) k[j + kBlurRadius] /= kernelSum;
-    }
-    scale *= diffScale;
-  }
-}
-
-void find_params(FindParams &P, float peak_thresh, float edge_thresh, float subsampling) {
-  // cuSIFT.cu:239-247 (sigma = baseBlur*diffScale, factor = 1/NUM_SCALES), cuSIFT.cu:432-444
-  const float baseBlur = powf(2.0f, -1.0f / kNumScales);
-  const float diffScale0 = powf(2.0f, 1.0f / kNumScales);
-  const double sigma = baseBlur * diffScale0;
-  const float factor = 1.0f / kNumScales;
-  float scale = (float)sigma;
-  const float diffScale = powf(2.0f, factor);
-  for (int i = 0; i < kNumScales; i++) {
-    P.scales[i] = scale;
-    scale *= diffScale;
-  }
-  P.thr_pos = peak_thresh;
-  P.thr_neg = -peak_thresh;
-  P.edge_limit = edge_thresh;
-  P.factor = factor;
-  P.subsampling = subsampling;
 }
 
 void frac_consts(int frac_bits, float &q, float &inv_q) {
@@ -220,75 +103,6 @@ extern "C" int cusift_init(int device) {
   device = std::max(0, std::min(n - 1, device));
   HIP_TRY(hipSetDevice(device));
   return CUSIFT_OK;
-}
-
-// Octave 0 beside the coarser octaves.  One extraction on one stream is a chain of launches of very different sizes:
-// octave 0's detection (3/4 of the pixels), then four ScaleDowns and four detections that each fill the chip for a few
-// microseconds and end in a tail.  A caller that keeps several batches in flight (cusift_params.concurrent_batches >= 2)
-// covers those tails with the other batches' kernels; a lone caller -- ExtractSift as the reference calls it -- cannot.
-// For it the driver forks: octave 0's detection goes to a second stream of the context and appends HEADS (64 bytes)
-// to a staging list in the arena, the ScaleDown chain and the coarser detections run on the context's stream as
-// before, the streams join, and describe_all_kernel moves the staged keypoints behind the coarser ones while it
-// describes them -- so SiftData comes out coarsest octave first, and saturates coarsest first, exactly as before.
-// Measured on MI355X (one stream, back to back; a later run: profiles/r03/octave_overlap.txt): 64 x 1080p 1.527 ->
-// 1.356 ms, 16: 0.478 -> 0.429, 4: 0.213 -> 0.200 -- but ONE frame 0.132 -> 0.138 ms, and its recorded graph 0.148 ->
-// 0.187: the two cross-stream waits cost more than a frame's tails.  So the fork is taken from kSideStreamMinPixels up (three 1080p
-// frames), never inside a recording, never with the stage timers on (they bracket launches on one stream).
-constexpr size_t kSideStreamMinPixels = 6u << 20;
-bool wants_side_stream(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h) {
-  const int mode = ctx->knobs.octave_overlap;  // 0 (default): the context has not been asked to fork
-  if (mode == 0 || ctx->timing || ctx->knobs.force_generic || ctx->side_failed) return false;
-  if (!prm || !prm->fused_detect || n_images < 1 || n_images > kMaxFlatImages) return false;
-  if (mode == 3) return true;  // tests: whatever the size, also inside a recording
-  if (ctx->recording) return false;
-  return prm->concurrent_batches < 2 && (size_t)n_images * (size_t)w * (size_t)h >= kSideStreamMinPixels;
-}
-
-// Every octave's keypoints to staging lists, joined by describe_all_kernel: detections no longer have to run, or end, in
-// list order -- ALL octaves are searched by ONE launch (detect_multi_impl; two with octave 0 on the side stream), the
-// large octave's workgroups first and the small ones in its tail.  What it buys is dispatches and tails (MI355X,
-// 1080p, ms per call back to back on one stream: 1 frame 0.130 -> 0.082, 4: 0.210 -> 0.145, 16: 0.476 -> 0.389,
-// 64: 1.52 -> 1.41; with four calls in flight: 1 frame 0.062 -> 0.043, 4: 0.111 -> 0.106, 16: 0.338 -> 0.343,
-// 64: 1.165 -> 1.20 -- there the other batches fill the tails already and octave 0 is better off in its own, tuned
-// instantiation).  So: a lone caller whenever the lists fit, a pipelining caller up to eight 1080p frames' worth of
-// pixels per call.  Not with the per-octave stage sequence, the generic kernels or the stage timers on.
-constexpr size_t kListsMaxPixelsPipelined = 16u << 20;
-bool wants_stage_all(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h) {
-  if (ctx->knobs.stage_all == 0 || ctx->knobs.force_generic) return false;
-  if (!prm || !prm->fused_detect || n_images < 1 || n_images > kMaxFlatImages) return false;
-  if (ctx->knobs.stage_all > 0) return true;  // tests: whenever the lists fit
-  if (wants_pyramid_in_detect(ctx, prm, n_images, w, h) > 0) return true;  // finest first needs a list per octave
-  if (ctx->timing) return false;  // the stage timers bracket the reference's launch-per-octave sequence
-  return prm->concurrent_batches < 2 || (size_t)n_images * (size_t)w * (size_t)h <= kListsMaxPixelsPipelined;
-}
-
-// The pyramid as a by-product of the detection (CUSIFT_POLICY_PYRAMID_IN_DETECT; detect_fused_kernel<.., kDown>): octave
-// o's detection writes octave o + 1's image from its own row window, so the ScaleDown launches -- 0.2 ms of HBM-bound
-// re-reading per 64 x 1080p, a fifth of a lone caller's step -- disappear for ~5 % more vector instructions in the
-// detection, and the octaves are searched finest first (lists per octave).  What it costs is the one-launch detection
-// of the coarser octaves: a chain of dependent launches has a tail per octave, which a caller with several batches in
-// flight fills with the other batches' kernels and a lone caller does not.  Measured on MI355X
-// (profiles/r05/ab_pyramid_by_size.txt; 1080p frames per call, ms per call, ScaleDown chain first -> every octave):
-//   four calls in flight  1: 0.0409 -> 0.0390   3: 0.0776 -> 0.0725   8: 0.1645 -> 0.1450   16: 0.288 -> 0.267   64: 1.033 -> 0.976
-//   a lone caller         1: 0.0649 -> 0.0973  16: 0.342 -> 0.392    32: 0.645 -> 0.662    48: 0.941 -> 0.932   64: 1.241 -> 1.153
-// A lone caller's middle ground is "octave 0 only" (1): octave 0's detection hands octave 1 over -- the large ScaleDown is
-// the one worth saving -- and the coarser octaves keep their short ScaleDown chain and their ONE launch: 32 frames
-// 0.645 -> 0.640, 48: 0.941 -> 0.910 (every octave: 0.932), 64: 1.241 -> 1.152 (every octave: 1.154); 24: 0.496 -> 0.505.
-// So by default: a pipelining caller (concurrent_batches >= 2) every octave from one 1080p frame's worth of pixels up
-// (2,000,000: a single 1920 x 1080 frame, 2,073,600 pixels, qualifies -- until round 6 the limit was 2 << 20 = 2,097,152
-// and it did not), a lone caller octave 0 only from 64,000,000 pixels per call (31 frames of 1080p).  0: never; 1: octave 0
-// only; 2: every octave.
-constexpr size_t kPyramidInDetectMinPixelsPipelined = 2000000, kPyramidInDetectMinPixelsLone = 64000000;
-int wants_pyramid_in_detect(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h) {
-  const int mode = ctx->knobs.pyramid_in_detect;
-  if (mode == 0 || ctx->knobs.force_generic || ctx->knobs.stage_all == 0) return 0;
-  if (!prm || !prm->fused_detect || prm->num_octaves < 2 || n_images < 1 || n_images > kMaxFlatImages) return 0;
-  // (the stage timers do not change this: every launch of the finest-first sequence is a detection launch and is
-  // bracketed as one -- the ScaleDown stage then simply reports no launches)
-  if (mode > 0) return std::min(mode, 2);
-  const size_t px = (size_t)n_images * (size_t)w * (size_t)h;
-  if (prm->concurrent_batches >= 2) return px >= kPyramidInDetectMinPixelsPipelined ? 2 : 0;
-  return px >= kPyramidInDetectMinPixelsLone ? 1 : 0;
 }
 
 // OPT-IN since round 4 (cusift_ctx_set_policy(ctx, CUSIFT_POLICY_SIDE_STREAM, 1 | 2), or CUSIFT_OCTAVE_OVERLAP=1 | 2 in the
@@ -409,7 +223,7 @@ extern "C" void cusift_default_params(cusift_params *p) {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-int ctx_create_impl(cusift_ctx **out, int device, void *hip_stream, bool borrow) {
+static int ctx_create_impl(cusift_ctx **out, int device, void *hip_stream, bool borrow) {
   if (!out) return fail(CUSIFT_ERR_INVALID, "out is NULL");
   *out = nullptr;
   int n = 0;
@@ -501,15 +315,6 @@ extern "C" int cusift_ctx_wait(cusift_ctx *ctx, cusift_ctx *other) {
   (void)hipEventDestroy(ev);  // destruction is deferred until the event has completed
   if (e != hipSuccess) return fail(CUSIFT_ERR_HIP, "cusift_ctx_wait: %s", hipGetErrorString(e));
   return CUSIFT_OK;
-}
-
-extern "C" int cusift_ctx_reserve(cusift_ctx *ctx, int n_images, int w, int h, const cusift_params *p) {
-  TRY(enter(ctx));
-  Plan pl;
-  TRY(make_plan(pl, n_images, w, h, ialign_up(w, 128), p, wants_side_stream(ctx, p, n_images, w, h),
-                wants_stage_all(ctx, p, n_images, w, h)));
-  // + one pitched upload image for cusift_extract_host
-  return ensure_arena(ctx, pl.total + align_up_sz((size_t)h * ialign_up(w, 128) * sizeof(float), 256));
 }
 
 // scratch of cusift_extract_bands: [counters of the bands | running sums | a list of heads per band]

@@ -3,7 +3,8 @@
 //   sift_context.hip  errors, context + arena + policy + stage timers, memory helpers
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, matcher, homography, packing)
-//   sift_driver.hip   the octave driver (cusift_extract_batch), its recorded graph, the single-image entry points
+//   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
+//                     recorded graph, the single-image entry points, cusift_ctx_reserve
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -191,9 +192,24 @@ struct StageTimer {
   }
 };
 
-// Octave geometry of one extraction (cuSIFT.cu:76-91,175-190).
+// How cusift_extract_batch detects one octave's keypoints.
+enum Detect : unsigned char {
+  kNotSearched,  // below cusift_params.lowest_scale (cuSIFT.cu:194)
+  kTwoStage,     // LaplaceMulti + FindPointsMulti: the fused kernel does not apply (a 2x1 octave, a caller's odd pitch)
+  kFused,        // the fused detection, appending in place to SiftData
+  kStaged,       // the fused detection, heads to the octave's own list
+  kSide,         // kStaged on the context's side stream (octave 0 of a forked call)
+  kChain,        // kStaged, and it writes the next octave's image (the pyramid as a by-product of the detection)
+  kOneLaunch,    // a member of the one multi-octave launch (heads to the octave's own list)
+};
+// Who zeroes the lists' counters: kByMemset is skipped when the previous extraction's join left these very counters zero.
+enum SegClear : unsigned char { kNoLists, kByPyramid, kByMemset };
+
+// One extraction, decided: the octave geometry (cuSIFT.cu:76-91,175-190), the arena layout and the launch sequence.  A pure
+// function of the context's policy and flags (timing, recording, side_failed), cusift_params, the batch geometry and the
+// alignment of the caller's images (resolve_plan, sift_driver.hip); cusift_extract_batch enqueues what it says.
 struct Plan {
-  int n_oct = 0;
+  int n_images = 0, n_oct = 0;
   int w[kMaxOctaves], h[kMaxOctaves], p[kMaxOctaves];
   double blur[kMaxOctaves];
   float sub[kMaxOctaves];
@@ -204,13 +220,25 @@ struct Plan {
   // staged_octaves == 0: none; 1: octave 0's (searched on the side stream); n_oct: every octave's
   size_t staged_off = 0, seg_end_off = 0;
   int staged_octaves = 0;
-  bool fork = false;  // octave 0's detection on the context's side stream
+  bool fork = false;     // the layout has octave 0's list for the side stream (stays set when no side stream is found)
+  size_t dog_bytes = 0;  // DoG planes of the largest kTwoStage octave (0: none)
+  // the launch sequence
+  Detect detect[kMaxOctaves];
+  bool flat = false;       // the keypoint stages run once, over all octaves (describe_all_kernel); else per octave
+  bool stage_all = false;  // every searched octave to a list of its own, joined behind the detections
+  bool forked = false;     // octave 0 on the side stream (wanted: cusift_extract_batch drops it if it finds no stream)
+  int chain_end = 0;       // octaves [0, chain_end) are kChain: images 1 .. chain_end come from detections
+  int small_levels = 0;    // levels 1 .. small_levels from ONE ScaleDown launch (pyramid_small_kernel); 0: none
+  int concurrent = 1;      // what the detections are told about other batches in flight
+  bool self_join = false;  // describe_all_kernel joins the lists itself (no join_counts_kernel)
+  bool join_clears = false;  // join_counts_kernel leaves the lists' counters zero for the next extraction
+  SegClear clear = kNoLists;
+  size_t n_seg_counts = 0, seg_bytes = 0;  // the lists' counters: how many, and the bytes a memset clears
 };
 
 // Largest staging a context allocates: for octave 0 alone (the side stream), for all octaves (one detection launch; a
 // batch beyond it keeps the in-place lists)
 constexpr size_t kMaxStagedBytes = (size_t)1 << 30, kMaxStagedAllBytes = (size_t)1 << 30;
-
 
 struct MultiOctave {
   const float *img;
@@ -223,34 +251,40 @@ struct MultiOctave {
   int row0 = 0, hg = -1, cy_begin = 0, cy_end = 0;
 };
 
-// defined in sift_context.hip / sift_stages.hip / sift_driver.hip
-int fold_spans(cusift_ctx *ctx);
-int make_plan(Plan &pl, int n_images, int w, int h, int pitch, const cusift_params *prm, bool fork = false,
-              bool stage_all = false);
-int ensure_dog(cusift_ctx *ctx, size_t bytes);
-int ensure_arena(cusift_ctx *ctx, size_t bytes);
-int pick_rows(int h, int strips, int n_images, int lo, int hi);
-void scale_down_taps(ScaleDownTaps &T, float variance);
-void laplace_taps_table(float init_blur, float taps[8 * 16]);
-void find_params(FindParams &P, float peak_thresh, float edge_thresh, float subsampling);
-void frac_consts(int frac_bits, float &q, float &inv_q);
+// Grows one of the context's device scratch blocks (never shrinks): waits for the stream, frees the old block, allocates.
+// `recorded`: recorded graphs refer to the block, so its re-allocation invalidates them (scratch_gen).
+template <class T>
+static int grow_scratch(cusift_ctx *ctx, T *&ptr, size_t &have, size_t bytes, const char *what, bool recorded) {
+  if (bytes <= have) return CUSIFT_OK;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (recorded) ctx->scratch_gen++;
+  if (ptr) HIP_TRY(hipFree(ptr));
+  ptr = nullptr;
+  have = 0;
+  hipError_t e = hipMalloc((void **)&ptr, bytes);
+  if (e != hipSuccess) return fail(CUSIFT_ERR_NOMEM, "%shipMalloc(%zu) failed: %s", what, bytes, hipGetErrorString(e));
+  have = bytes;
+  return CUSIFT_OK;
+}
+
+// shared between sift_context.hip, sift_stages.hip and sift_driver.hip
 int enter(cusift_ctx *ctx);
 int check_launch(const char *what);
-bool wants_side_stream(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h);
-bool wants_stage_all(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h);
-int wants_pyramid_in_detect(const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h);
+int ensure_arena(cusift_ctx *ctx, size_t bytes);
 int ensure_side_stream(cusift_ctx *ctx);
-int ctx_create_impl(cusift_ctx **out, int device, void *hip_stream, bool borrow);
 size_t bands_arena_bytes(int n_bands, int max_pts);
-int scale_down_impl(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_stride, const float *d_src, int w, int h, int src_pitch, size_t src_stride, int n_images, float variance, RowWindow src_rw, int dst_row0, int r_begin, int r_end, bool band);
-bool wants_small_pyramid(const cusift_ctx *ctx, int n_images, int w, int h);
-bool wants_self_join(const cusift_ctx *ctx, int n_images, int w, int h);
-int pyramid_small_impl(cusift_ctx *ctx, const float *const *base, const int *w, const int *h, const int *pitch, const size_t *stride, int n_levels, int n_images, float variance, unsigned int *d_zero, int n_zero);
+void scale_down_taps(ScaleDownTaps &T, float variance);
+void frac_consts(int frac_bits, float &q, float &inv_q);
 bool detect_fused_ok(const float *d_img, int w, int h, int pitch, size_t img_stride);
-int detect_rows(const cusift_ctx *ctx, int rows_total, int strips, int n_images, int concurrent);
-int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride, float init_blur, float peak_thresh, float edge_thresh, float subsampling, cusift_point *d_points, int max_pts, unsigned int *d_counters, int n_images, RowWindow rw, int cy_begin, int cy_end, int concurrent = 1, bool heads = false, bool side = false, const DownOut *down = nullptr);
-int detect_multi_impl(cusift_ctx *ctx, const MultiOctave *octaves, int n_octaves, float peak_thresh, float edge_thresh, int max_pts, int n_images, int concurrent, unsigned int *d_queue);
-int keypoint_grid_x(int max_pts, int n_images);
-int orientations_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride, cusift_point *d_points, int max_pts, const unsigned int *d_first, const unsigned int *d_counters, int tex_frac_bits, int n_images, RowWindow rw);
-int descriptors_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride, cusift_point *d_points, int max_pts, const unsigned int *d_first, const unsigned int *d_counters, float subsampling, int tex_frac_bits, int n_images, RowWindow rw, int root_sift = 0, unsigned int *d_flags = nullptr);
-size_t two_stage_dog_bytes(const cusift_ctx *ctx, const Plan &pl, const cusift_params *prm, const float *d_imgs, size_t image_stride, const char *arena_base, int n_images);
+int pyramid_small_impl(cusift_ctx *ctx, const float *const *base, const int *w, const int *h, const int *pitch,
+                       const size_t *stride, int n_levels, int n_images, float variance, unsigned int *d_zero, int n_zero);
+int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride, float init_blur,
+                float peak_thresh, float edge_thresh, float subsampling, cusift_point *d_points, int max_pts,
+                unsigned int *d_counters, int n_images, RowWindow rw, int cy_begin, int cy_end, int concurrent = 1,
+                bool heads = false, bool side = false, const DownOut *down = nullptr);
+int detect_multi_impl(cusift_ctx *ctx, const MultiOctave *octaves, int n_octaves, float peak_thresh, float edge_thresh,
+                      int max_pts, int n_images, int concurrent, unsigned int *d_queue);
+int descriptors_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride,
+                     cusift_point *d_points, int max_pts, const unsigned int *d_first, const unsigned int *d_counters,
+                     float subsampling, int tex_frac_bits, int n_images, RowWindow rw, int root_sift = 0,
+                     unsigned int *d_flags = nullptr);

@@ -27,15 +27,7 @@ extern "C" int cusift_image_u8_h2d(cusift_ctx *ctx, float *d_dst, int dst_pitch,
   TRY(enter(ctx));
   const size_t spitch = align_up_sz((size_t)w, 4);
   const size_t bytes = spitch * h;
-  if (bytes > ctx->u8_stage_bytes) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->u8_stage) HIP_TRY(hipFree(ctx->u8_stage));
-    ctx->u8_stage = nullptr;
-    ctx->u8_stage_bytes = 0;
-    hipError_t e = hipMalloc((void **)&ctx->u8_stage, bytes);
-    if (e != hipSuccess) return fail(CUSIFT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    ctx->u8_stage_bytes = bytes;
-  }
+  TRY(grow_scratch(ctx, ctx->u8_stage, ctx->u8_stage_bytes, bytes, "", false));
   HIP_TRY(hipMemcpy2DAsync(ctx->u8_stage, spitch, h_src, (size_t)w, (size_t)w, h, hipMemcpyHostToDevice, ctx->stream));
   TRY(cusift_u8_to_f32(ctx, d_dst, dst_pitch, (size_t)dst_pitch * h, ctx->u8_stage, w, h, (int)spitch, bytes, 1));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -62,7 +54,87 @@ extern "C" int cusift_gaussian3x3(cusift_ctx *ctx, float *d_dst, int dst_pitch, 
 // ------------------------------------------------------------------------------------------------
 // stage entry points
 // ------------------------------------------------------------------------------------------------
-int scale_down_impl(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_stride, const float *d_src, int w,
+// rows each wave marches: as large as possible (less halo re-read) while the launch still has
+// >= ~2 waves per SIMD on 256 CUs.
+static int pick_rows(int h, int strips, int n_images, int lo, int hi) {
+  const long target_waves = 256L * 4 * 2 * 2;
+  long r = (long)h * strips * n_images / target_waves;
+  if (r < lo) r = lo;
+  if (r > hi) r = hi;
+  return (int)r;
+}
+
+static void laplace_taps_table(float init_blur, float taps[8 * 16]) {
+  // cuSIFT.cu:239-240,400-412.  Rule of this build: var <= 1e-6 => identity (the reference produces
+  // NaN taps at var == 0 and an inverted kernel at var < 0; see DESIGN.md "degenerate initBlur").
+  const float baseBlur = powf(2.0f, -1.0f / kNumScales);
+  const float diffScale = powf(2.0f, 1.0f / kNumScales);
+  float scale = baseBlur;
+  memset(taps, 0, sizeof(float) * 8 * 16);
+  for (int i = 0; i < kNumLevels; i++) {
+    float kernelSum = 0.0f;
+    float var = scale * scale - init_blur * init_blur;
+    float *k = taps + 16 * i;
+    if (var <= 1e-6f) {
+      k[kBlurRadius] = 1.0f;
+    } else {
+      for (int j = -kBlurRadius; j <= kBlurRadius; j++) {
+        k[j + kBlurRadius] = (float)expf(-(double)j * j / 2.0 / var);
+        kernelSum += k[j + kBlurRadius];
+      }
+      for (int j = -kBlurRadius; j <= kBlurRadius; j++) k[j + kBlurRadius] /= kernelSum;
+    }
+    scale *= diffScale;
+  }
+}
+
+static void find_params(FindParams &P, float peak_thresh, float edge_thresh, float subsampling) {
+  // cuSIFT.cu:239-247 (sigma = baseBlur*diffScale, factor = 1/NUM_SCALES), cuSIFT.cu:432-444
+  const float baseBlur = powf(2.0f, -1.0f / kNumScales);
+  const float diffScale0 = powf(2.0f, 1.0f / kNumScales);
+  const double sigma = baseBlur * diffScale0;
+  const float factor = 1.0f / kNumScales;
+  float scale = (float)sigma;
+  const float diffScale = powf(2.0f, factor);
+  for (int i = 0; i < kNumScales; i++) {
+    P.scales[i] = scale;
+    scale *= diffScale;
+  }
+  P.thr_pos = peak_thresh;
+  P.thr_neg = -peak_thresh;
+  P.edge_limit = edge_thresh;
+  P.factor = factor;
+  P.subsampling = subsampling;
+}
+
+// the tap table as the fast kernels take it: two levels per register pair
+static void pack_taps(const float taps[8 * 16], LaplaceTapsPk &TP) {
+  for (int q = 0; q < kNumLevels / 2; ++q)
+    for (int j = 0; j < 5; ++j) {
+      TP.k[q][j].x = taps[16 * (2 * q) + j];
+      TP.k[q][j].y = taps[16 * (2 * q + 1) + j];
+    }
+}
+
+// levels 0 and 1 both identity (initBlur >= their sigma)?  then the fused kernels pass them through
+static bool taps_ident01(const float taps[8 * 16]) {
+  bool ident = true;
+  for (int lv = 0; lv < 2; ++lv)
+    for (int j = 0; j < 9; ++j) ident = ident && (taps[16 * lv + j] == (j == kBlurRadius ? 1.0f : 0.0f));
+  return ident;
+}
+
+// What is wrong with a band's rows (NULL: nothing).  Centres need 4 blur rows + 1 extremum row of true data on either
+// side, unless the band ends at the image border.
+static const char *band_rows_error(int row0, int h, int h_global, int cy_begin, int cy_end) {
+  if (row0 < 0 || h < 1 || row0 + h > h_global || cy_begin < row0 || cy_end > row0 + h || cy_end <= cy_begin)
+    return "bad row geometry";
+  if ((row0 > 0 && cy_begin - row0 < 5) || (row0 + h < h_global && row0 + h - cy_end < 5))
+    return "the centres need 5 halo rows inside the band";
+  return nullptr;
+}
+
+static int scale_down_impl(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_stride, const float *d_src, int w,
                            int h, int src_pitch, size_t src_stride, int n_images, float variance, RowWindow src_rw,
                            int dst_row0, int r_begin, int r_end, bool band) {
   TRY(enter(ctx));
@@ -96,23 +168,6 @@ int scale_down_impl(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_str
                        w, h, src_pitch, (long)src_stride, rows, T);
   }
   return check_launch("scale_down");
-}
-
-// The ScaleDown chain of a small call -- levels 1 .. n from level 0 -- in ONE launch (pyramid_small_kernel).
-// A call takes it up to kPyramidSmallPixels source pixels (one 1080p frame: four launches of 6-10 us become one of
-// ~10); beyond that the 2.9x re-reads of the source cost more than the dispatches.  Not with the stage timers on (they
-// count one ScaleDown per octave).
-constexpr size_t kPyramidSmallPixels = (size_t)5 << 19;  // 2.6 Mpixel
-bool wants_small_pyramid(const cusift_ctx *ctx, int n_images, int w, int h) {
-  return !ctx->knobs.force_generic && !ctx->timing && (size_t)n_images * (size_t)w * (size_t)h <= kPyramidSmallPixels;
-}
-
-// describe_all_kernel may form the lists' running sums itself (no join_counts_kernel: a small call saves the dispatch) --
-// but it then finds every keypoint's list by a walk over the lists' counters, which a large call pays per keypoint
-// (64 x 1080p of `blobs`, 581 k keypoints, one stream: 2.066 ms with the self-join against 1.99 with the 5-us join kernel and
-// its precomputed ends).  So: small calls only.
-bool wants_self_join(const cusift_ctx *, int n_images, int w, int h) {
-  return (size_t)n_images * (size_t)w * (size_t)h <= kPyramidSmallPixels;
 }
 
 int pyramid_small_impl(cusift_ctx *ctx, const float *const *base, const int *w, const int *h, const int *pitch,
@@ -221,11 +276,7 @@ extern "C" int cusift_laplace_multi(cusift_ctx *ctx, const float *d_img, int w, 
   StageTimer t(ctx, CUSIFT_STAGE_LAPLACE);
   if (fast) {
     LaplaceTapsPk TP;
-    for (int q = 0; q < kNumLevels / 2; ++q)
-      for (int j = 0; j < 5; ++j) {
-        TP.k[q][j].x = taps[16 * (2 * q) + j];
-        TP.k[q][j].y = taps[16 * (2 * q + 1) + j];
-      }
+    pack_taps(taps, TP);
     // DoG planes are written once and read much later (by FindPointsMulti): non-temporal stores keep them from
     // displacing the source rows' halo in L2 -- measured on one box: 4.35 -> 4.63 TB/s for this kernel and 3.87 ->
     // 4.18 TB/s for the FindPointsMulti that follows (profiles/r02_ab/laplace_rows_and_nt_stores.txt: the same A/B at
@@ -274,7 +325,7 @@ bool detect_fused_ok(const float *d_img, int w, int h, int pitch, size_t img_str
 }
 
 // Chunk height of the fused detection: centre rows per wave (see the comment in detect_impl).
-int detect_rows(const cusift_ctx *ctx, int rows_total, int strips, int n_images, int concurrent) {
+static int detect_rows(const cusift_ctx *ctx, int rows_total, int strips, int n_images, int concurrent) {
   const int rows_lo = 2, rows_hi = concurrent >= 3 ? 240 : (concurrent >= 2 ? 112 : 64);
   const double wave_rows = (double)rows_total * strips * n_images;
   double r = (concurrent >= 2 ? 0.09 : 0.05) * sqrt(wave_rows);
@@ -310,11 +361,7 @@ int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, si
   float taps[8 * 16];
   laplace_taps_table(init_blur, taps);
   LaplaceTapsPk TP;
-  for (int q = 0; q < kNumLevels / 2; ++q)
-    for (int j = 0; j < 5; ++j) {
-      TP.k[q][j].x = taps[16 * (2 * q) + j];
-      TP.k[q][j].y = taps[16 * (2 * q + 1) + j];
-    }
+  pack_taps(taps, TP);
   FindParams P;
   find_params(P, peak_thresh, edge_thresh, subsampling);
   const int rows_total = cy_end - cy_begin;
@@ -341,10 +388,7 @@ int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, si
   // 2: 0.645 ms, 1: 0.630 ms.
   dim3 grid(strips, idiv_up(rows_total, rows), n_images);
   const size_t cube_bytes = kDetectWaveLdsFloats * sizeof(float);  // the wave's candidate list
-  // levels 0 and 1 both identity (initBlur >= their sigma)?  then the kernel passes them through
-  bool ident = true;
-  for (int lv = 0; lv < 2; ++lv)
-    for (int j = 0; j < 9; ++j) ident = ident && (taps[16 * lv + j] == (j == kBlurRadius ? 1.0f : 0.0f));
+  const bool ident = taps_ident01(taps);
   StageTimer t(ctx, CUSIFT_STAGE_DETECT);
   constexpr int kWhole = (int)sizeof(cusift_point);
   auto kernel = down ? (ident ? detect_fused_kernel<true, kStagedRecBytes, true> : detect_fused_kernel<false, kStagedRecBytes, true>)
@@ -376,15 +420,8 @@ int detect_multi_impl(cusift_ctx *ctx, const MultiOctave *octaves, int n_octaves
     DetectOctave &o = tab.o[k];
     float taps[8 * 16];
     laplace_taps_table(m.init_blur, taps);
-    for (int q = 0; q < kNumLevels / 2; ++q)
-      for (int j = 0; j < 5; ++j) {
-        o.T.k[q][j].x = taps[16 * (2 * q) + j];
-        o.T.k[q][j].y = taps[16 * (2 * q + 1) + j];
-      }
-    bool ident0 = true;  // levels 0 and 1 both identity (initBlur >= their sigma)?
-    for (int lv = 0; lv < 2; ++lv)
-      for (int j = 0; j < 9; ++j) ident0 = ident0 && (taps[16 * lv + j] == (j == kBlurRadius ? 1.0f : 0.0f));
-    o.ident = ident0 ? 1 : 0;
+    pack_taps(taps, o.T);
+    o.ident = taps_ident01(taps) ? 1 : 0;
     find_params(o.P, peak_thresh, edge_thresh, m.subsampling);
     o.img = m.img;
     o.img_stride = (long)m.img_stride;
@@ -439,23 +476,19 @@ extern "C" int cusift_detect_multi_down(cusift_ctx *ctx, const float *d_img, int
 extern "C" int cusift_detect_band(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, int row0, int h_global,
                                   int cy_begin, int cy_end, float init_blur, float peak_thresh, float edge_thresh,
                                   float subsampling, cusift_point *d_points, int max_pts, unsigned int *d_counter) {
-  if (row0 < 0 || h < 1 || row0 + h > h_global || cy_begin < row0 || cy_end > row0 + h || cy_end <= cy_begin)
-    return fail(CUSIFT_ERR_INVALID, "Detect (band): bad row geometry");
-  // centres need 4 blur rows + 1 extremum row of true data on either side, unless the band ends at the image border
-  if ((row0 > 0 && cy_begin - row0 < 5) || (row0 + h < h_global && row0 + h - cy_end < 5))
-    return fail(CUSIFT_ERR_INVALID, "Detect (band): centres [%d,%d) need 5 halo rows inside the band [%d,%d)", cy_begin,
-                cy_end, row0, row0 + h);
+  if (const char *why = band_rows_error(row0, h, h_global, cy_begin, cy_end))
+    return fail(CUSIFT_ERR_INVALID, "Detect (band): %s (centres [%d,%d), band [%d,%d))", why, cy_begin, cy_end, row0, row0 + h);
   return detect_impl(ctx, d_img, w, h, pitch, (size_t)h * pitch, init_blur, peak_thresh, edge_thresh, subsampling,
                      d_points, max_pts, d_counter, 1, RowWindow{row0, h_global}, cy_begin, cy_end);
 }
 
-int keypoint_grid_x(int max_pts, int n_images) {
+static int keypoint_grid_x(int max_pts, int n_images) {
   // persistent grid: enough waves to fill 256 CUs x 32 wave slots, never more than max_pts per image
   int per_image = std::max(1, (256 * 32 * 2) / std::max(1, n_images));
   return std::max(1, std::min(max_pts, std::min(per_image, 4096)));
 }
 
-int orientations_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride,
+static int orientations_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride,
                              cusift_point *d_points, int max_pts, const unsigned int *d_first,
                              const unsigned int *d_counters, int tex_frac_bits, int n_images, RowWindow rw) {
   TRY(enter(ctx));
@@ -530,12 +563,8 @@ extern "C" int cusift_extract_bands(cusift_ctx *ctx, const cusift_band *bands, i
     return fail(CUSIFT_ERR_INVALID, "ExtractBands: 1..%d bands", kMaxMultiOctaves);
   for (int k = 0; k < n_bands; ++k) {
     const cusift_band &b = bands[k];
-    if (!b.d_img || b.row0 < 0 || b.h < 1 || b.row0 + b.h > b.h_global || b.cy_begin < b.row0 || b.cy_end > b.row0 + b.h ||
-        b.cy_end <= b.cy_begin)
-      return fail(CUSIFT_ERR_INVALID, "ExtractBands: band %d has bad row geometry", k);
-    // centres need 4 blur rows + 1 extremum row of true data on either side, unless the band ends at the image border
-    if ((b.row0 > 0 && b.cy_begin - b.row0 < 5) || (b.row0 + b.h < b.h_global && b.row0 + b.h - b.cy_end < 5))
-      return fail(CUSIFT_ERR_INVALID, "ExtractBands: band %d: centres [%d,%d) need 5 halo rows inside [%d,%d)", k, b.cy_begin,
+    if (const char *why = !b.d_img ? "bad row geometry" : band_rows_error(b.row0, b.h, b.h_global, b.cy_begin, b.cy_end))
+      return fail(CUSIFT_ERR_INVALID, "ExtractBands: band %d: %s (centres [%d,%d), band [%d,%d))", k, why, b.cy_begin,
                   b.cy_end, b.row0, b.row0 + b.h);
     if (k > 0 && !(b.subsampling == 2.0f * bands[k - 1].subsampling))
       return fail(CUSIFT_ERR_INVALID, "ExtractBands: band %d is not the next octave of band %d", k, k - 1);
@@ -634,16 +663,7 @@ extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1
   MatchPartial *partials = nullptr;
   if (splits > 1) {
     const size_t bytes = sizeof(MatchPartial) * (size_t)splits * n1_pad;
-    if (bytes > ctx->match_scratch_bytes) {
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      ctx->scratch_gen++;
-      if (ctx->match_scratch) HIP_TRY(hipFree(ctx->match_scratch));
-      ctx->match_scratch = nullptr;
-      ctx->match_scratch_bytes = 0;
-      hipError_t e = hipMalloc((void **)&ctx->match_scratch, bytes);
-      if (e != hipSuccess) return fail(CUSIFT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-      ctx->match_scratch_bytes = bytes;
-    }
+    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
     partials = ctx->match_scratch;
   }
   if (distance)
@@ -679,15 +699,7 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
   const size_t homo_b = align_up_sz(sizeof(float) * 8 * (size_t)num_loops, 256);
   const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
   const size_t bytes = coord_b + rand_b + homo_b + cnt_b;
-  if (bytes > ctx->homo_scratch_bytes) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->homo_scratch) HIP_TRY(hipFree(ctx->homo_scratch));
-    ctx->homo_scratch = nullptr;
-    ctx->homo_scratch_bytes = 0;
-    hipError_t e = hipMalloc((void **)&ctx->homo_scratch, bytes);
-    if (e != hipSuccess) return fail(CUSIFT_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    ctx->homo_scratch_bytes = bytes;
-  }
+  TRY(grow_scratch(ctx, ctx->homo_scratch, ctx->homo_scratch_bytes, bytes, "", false));
   float *d_coord = (float *)ctx->homo_scratch;
   int *d_rand = (int *)(ctx->homo_scratch + coord_b);
   float *d_homo = (float *)(ctx->homo_scratch + coord_b + rand_b);
