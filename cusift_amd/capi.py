@@ -176,6 +176,8 @@ SIGNATURES = {
     "cusift_match": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "cusift_memcpy2d_d2h": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
     "cusift_find_homography": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, C.POINTER(_i), _vp, _vp]),
+    "cusift_estimate_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp,
+                                   _vp, _vp]),
     "cusift_pack_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_compact": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_trimmed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -269,6 +271,45 @@ def ialign_up(a, b):
 # cusift_ctx_set_policy keys (include/cusift_amd.h)
 POLICY_SIDE_STREAM, POLICY_OCTAVE_LISTS, POLICY_GENERIC_KERNELS, POLICY_LAUNCH_PER_OCTAVE, POLICY_MATCH_SPLITS, \
     POLICY_TILED_PER_OCTAVE, POLICY_PYRAMID_IN_DETECT = range(7)
+
+
+RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
+
+
+def check_rigid_args(coord, indices=None, loops=None, thresh2=0.0025, kind="3d"):
+    """What Context.estimate_rigid checks before it calls the library (needs no device): returns (coord float32 [N, 6],
+    indices int32 [L, 3] or None, L, type).  ValueError for anything cusift_estimate_rigid would refuse."""
+    if kind not in RIGID_KINDS:
+        raise ValueError("kind must be '2d' or '3d', not %r" % (kind,))
+    coord = np.asarray(coord)
+    if coord.dtype != np.float32:
+        raise ValueError("coord must be float32, not %s" % coord.dtype)
+    if coord.ndim != 2 or coord.shape[1] != 6:
+        raise ValueError("coord must be [num_pts, 6] (reference xyz, moving xyz), not %s" % (coord.shape,))
+    coord = np.ascontiguousarray(coord)
+    num_pts = coord.shape[0]
+    if not (float(thresh2) > 0.0):
+        raise ValueError("thresh2 must be > 0")
+    used = 3 if kind == "3d" else 2
+    if indices is None:
+        if loops is None or int(loops) < 1:
+            raise ValueError("without indices, loops >= 1 says how many hypotheses to draw")
+        if num_pts < 3:
+            raise ValueError("drawing needs num_pts >= 3, got %d" % num_pts)
+        return coord, None, int(loops), RIGID_KINDS[kind]
+    indices = np.asarray(indices)
+    if indices.dtype != np.int32:
+        raise ValueError("indices must be int32, not %s" % indices.dtype)
+    if indices.ndim != 2 or indices.shape[1] != 3 or indices.shape[0] < 1:
+        raise ValueError("indices must be [num_loops >= 1, 3], not %s" % (indices.shape,))
+    if loops is not None and int(loops) != indices.shape[0]:
+        raise ValueError("loops = %d but indices has %d rows" % (int(loops), indices.shape[0]))
+    if num_pts < used:
+        raise ValueError("the %s estimate needs num_pts >= %d, got %d" % (kind, used, num_pts))
+    read = indices[:, :used]
+    if read.min() < 0 or read.max() >= num_pts:
+        raise ValueError("sample index out of range [0, %d)" % num_pts)
+    return coord, np.ascontiguousarray(indices), indices.shape[0], RIGID_KINDS[kind]
 
 
 class Context:
@@ -509,6 +550,29 @@ class Context:
                                            hom.ctypes.data, C.byref(n), all_h.ctypes.data if want_all else None,
                                            all_c.ctypes.data if want_all else None))
         return (hom, n.value, all_h, all_c) if want_all else (hom, n.value)
+
+    def estimate_rigid(self, coord, indices=None, loops=None, thresh2=0.0025, kind="3d", seed=0, want_all=False):
+        """cusift_estimate_rigid: RANSAC rigid transform x ~ R y + t from coord float32 [N, 6] (reference xyz, moving
+        xyz).  indices int32 [L, 3]: the samples of every hypothesis; None: `loops` hypotheses drawn on the device from
+        `seed`.  kind "3d" (three-point Horn estimate, refitted over the winner's inliers) or "2d" (rotation about y
+        from two points, no refit).  Returns (Rt [3, 4], num_inliers, best_loop, inlier flags bool [N]) and, with
+        want_all, also (all Rt [L, 3, 4], all counts [L], the samples used [L, 3])."""
+        coord, indices, loops, rtype = check_rigid_args(coord, indices, loops, thresh2, kind)
+        n_pts = coord.shape[0]
+        rt = np.zeros((3, 4), dtype=np.float32)
+        n, best = C.c_int(0), C.c_int(-1)
+        flags = np.zeros(n_pts, dtype=np.int8)
+        all_rt = np.zeros((loops, 3, 4), dtype=np.float32) if want_all else None
+        all_c = np.zeros(loops, dtype=np.int32) if want_all else None
+        drawn = np.zeros((loops, 3), dtype=np.int32) if want_all else None
+        check(lib().cusift_estimate_rigid(self.handle, coord.ctypes.data, n_pts,
+                                          indices.ctypes.data if indices is not None else None, loops, float(thresh2),
+                                          rtype, int(seed) & 0xFFFFFFFFFFFFFFFF, rt.ctypes.data, C.byref(n),
+                                          C.byref(best), flags.ctypes.data, all_rt.ctypes.data if want_all else None,
+                                          all_c.ctypes.data if want_all else None,
+                                          drawn.ctypes.data if want_all else None))
+        out = (rt, n.value, best.value, flags.astype(bool))
+        return out + (all_rt, all_c, drawn) if want_all else out
 
     # ---- drivers ----
     def extract_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):

@@ -2,7 +2,8 @@
 // the context object, the octave plan and the helpers of the launch wrappers.
 //   sift_context.hip  errors, context + arena + policy + stage timers, memory helpers
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
-//                     FindPointsMulti, fused detection, orientation, descriptors, bands, matcher, homography, packing)
+//                     FindPointsMulti, fused detection, orientation, descriptors, bands, matcher, homography, rigid
+//                     transform, packing)
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 #pragma once
@@ -57,6 +58,11 @@ __global__ void match_merge_kernel(cusift_point *, int, const cusift_point *, in
 __global__ void homography_gather_kernel(const cusift_point *, int, float *);
 __global__ void homography_solve_kernel(const float *, int, const int *, int, float *);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
+template <bool k3D>
+__global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *);
+__global__ void rigid_score_kernel(const float *, int, int, const float *, int, float, int *);
+template <bool k3D>
+__global__ void rigid_select_kernel(const float *, int, const float *, const int *, int, float, float *, char *);
 __global__ void u8_to_f32_kernel(float *, int, long, const unsigned char *, int, int, int, long, int);
 __global__ void gaussian3x3_kernel(float *, int, long, const float *, int, int, int, long, float, float);
 __global__ void math_eval_kernel(int, const float *, const float *, float *, float *, long);
@@ -135,6 +141,9 @@ struct cusift_ctx {
   // coordinates / samples / hypotheses / counts of cusift_find_homography
   char *homo_scratch = nullptr;
   size_t homo_scratch_bytes = 0;
+  // result head / flags / hypotheses / counts / samples / coordinates of cusift_estimate_rigid
+  char *rigid_scratch = nullptr;
+  size_t rigid_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;

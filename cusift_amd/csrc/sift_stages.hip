@@ -731,6 +731,88 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
   return CUSIFT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// RANSAC rigid transform (sift_rigid.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int num_pts, const int *h_indices,
+                                     int num_loops, float thresh2, int type, uint64_t seed, float h_rt[12],
+                                     int *num_inliers, int *best_loop, char *h_inliers, float *h_all_rt,
+                                     int *h_all_counts, int *h_drawn) {
+  TRY(enter(ctx));
+  if (!h_rt || !num_inliers) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: NULL output");
+  if (!h_coord) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: missing data");
+  if (type != 0 && type != 1) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: type must be 0 (2D) or 1 (3D)");
+  const int used = type == 1 ? 3 : 2;  // the 2-D estimate never reads a hypothesis' third sample
+  const int min_pts = h_indices ? used : 3;  // drawing takes three distinct points for either type
+  if (num_pts < min_pts || num_pts > (1 << 26))
+    return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: num_pts %d outside [%d, 2^26]", num_pts, min_pts);
+  if (num_loops < 1 || num_loops > (1 << 24))
+    return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: num_loops %d outside [1, 2^24]", num_loops);
+  if (!(thresh2 > 0.0f)) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: thresh2 must be > 0");
+  if (h_indices)
+    for (int l = 0; l < num_loops; ++l)
+      for (int i = 0; i < used; ++i) {
+        const int v = h_indices[3 * (size_t)l + i];
+        if (v < 0 || v >= num_pts)
+          return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: sample index %d out of range [0, %d)", v, num_pts);
+      }
+  // [head | flags | hypotheses | counts | samples] is what travels back, in one copy; the coordinates come last
+  const size_t head_b = 256;
+  const size_t flag_b = align_up_sz((size_t)num_pts, 256);
+  const size_t rt_b = align_up_sz(sizeof(float) * 12 * (size_t)num_loops, 256);
+  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
+  const size_t idx_b = align_up_sz(sizeof(int) * 3 * (size_t)num_loops, 256);
+  const size_t coord_b = align_up_sz(sizeof(float) * 6 * (size_t)num_pts, 256);
+  const size_t rt_off = head_b + flag_b, cnt_off = rt_off + rt_b, idx_off = cnt_off + cnt_b, coord_off = idx_off + idx_b;
+  TRY(grow_scratch(ctx, ctx->rigid_scratch, ctx->rigid_scratch_bytes, coord_off + coord_b, "", false));
+  char *base = ctx->rigid_scratch;
+  float *d_head = (float *)base, *d_rt = (float *)(base + rt_off), *d_coord = (float *)(base + coord_off);
+  char *d_flags = base + head_b;
+  int *d_counts = (int *)(base + cnt_off), *d_idx = (int *)(base + idx_off);
+  HIP_TRY(hipMemcpyAsync(d_coord, h_coord, sizeof(float) * 6 * (size_t)num_pts, hipMemcpyHostToDevice, ctx->stream));
+  if (h_indices)
+    HIP_TRY(hipMemcpyAsync(d_idx, h_indices, sizeof(int) * 3 * (size_t)num_loops, hipMemcpyHostToDevice, ctx->stream));
+  // scoring: 256 hypotheses per workgroup; split the points until the launch has ~4 workgroups per CU, but keep
+  // at least one 256-point tile per split
+  const int loop_blocks = idiv_up(num_loops, 256);
+  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks), idiv_up(num_pts, 256)));
+  splits = std::min(splits, 65535);
+  const int pts_per_split = idiv_up(num_pts, splits);
+  splits = idiv_up(num_pts, pts_per_split);
+  const int draw = h_indices ? 0 : 1;
+  if (type == 1) {
+    hipLaunchKernelGGL(rigid_solve_kernel<true>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
+                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts);
+    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
+                       pts_per_split, d_rt, num_loops, thresh2, d_counts);
+    hipLaunchKernelGGL(rigid_select_kernel<true>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt, d_counts,
+                       num_loops, thresh2, d_head, d_flags);
+  } else {
+    hipLaunchKernelGGL(rigid_solve_kernel<false>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
+                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts);
+    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
+                       pts_per_split, d_rt, num_loops, thresh2, d_counts);
+    hipLaunchKernelGGL(rigid_select_kernel<false>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
+                       d_counts, num_loops, thresh2, d_head, d_flags);
+  }
+  TRY(check_launch("estimate_rigid"));
+  // the one blocking read-back
+  const bool all = h_all_rt || h_all_counts || h_drawn;
+  std::vector<char> back(all ? coord_off : head_b + (h_inliers ? flag_b : 0));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  memcpy(h_rt, back.data(), sizeof(float) * 12);
+  int tail[2];
+  memcpy(tail, back.data() + sizeof(float) * 12, sizeof(tail));
+  *num_inliers = tail[0];
+  if (best_loop) *best_loop = tail[1];
+  if (h_inliers) memcpy(h_inliers, back.data() + head_b, (size_t)num_pts);
+  if (h_all_rt) memcpy(h_all_rt, back.data() + rt_off, sizeof(float) * 12 * (size_t)num_loops);
+  if (h_all_counts) memcpy(h_all_counts, back.data() + cnt_off, sizeof(int) * (size_t)num_loops);
+  if (h_drawn) memcpy(h_drawn, back.data() + idx_off, sizeof(int) * 3 * (size_t)num_loops);
+  return CUSIFT_OK;
+}
+
 extern "C" int cusift_memcpy2d_d2h(cusift_ctx *ctx, void *h_dst, size_t dst_pitch, const void *d_src,
                                    size_t src_pitch, size_t width_bytes, size_t rows) {
   if (!ctx || !h_dst || !d_src) return fail(CUSIFT_ERR_INVALID, "NULL argument");

@@ -1,9 +1,12 @@
 /*
- * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher and the RANSAC homography.
+ * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography and
+ * the RANSAC rigid transform.
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
 #define CUSIFT_AMD_EXTRAS_H
+
+#include <stdint.h>
 
 #include "cusift_amd.h"
 
@@ -36,6 +39,34 @@ int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sift, int num_
                            int num_loops, float thresh, float h_homography[9], int *num_matches, float *h_all_homo,
                            int *h_all_counts);
 
+/* ---- RANSAC rigid transform from matched 3-D points -------------------------- */
+/* EstimateRigidTransformH(h_coord, Rt, numInliers, numLoops, numPts, thresh2, type, h_indices, h_inliers),
+ * extras/rigidTransform.cu:388-520.  h_coord[i] = reference-frame xyz, then moving-frame xyz of match i (coords3D of
+ * SiftMatch::pt1 and ::pt2); the result maps the moving frame into the reference frame, x ~ R y + t, as h_rt = [R | t]
+ * row-major 3x4.  Every hypothesis l is estimated from the samples h_indices[3 l .. 3 l + 2] -- type 1 (3D): Horn's
+ * quaternion estimate from three pairs (:15-209); type 0 (2D): a rotation about y and an x-z translation from the
+ * first two (:222-290; coincident samples give a NaN hypothesis that counts no inlier) -- and scored by the number of
+ * points with |R y + t - x|^2 < thresh2 (:292-329).  The winner is the hypothesis with the most inliers, among equals
+ * the LAST one (the reference's `>=`, :450): *num_inliers is its count, *best_loop its index, h_inliers[i] = 1 for its
+ * inliers.  For type 1 h_rt is the same estimate over all the winner's inliers (:477-479) -- unless it has fewer than
+ * three, then h_rt is the winner itself; for type 0 h_rt is the winner itself (:472-475).
+ * h_indices == NULL: the samples are drawn on the device, three distinct indices per hypothesis, from `seed`:
+ *     draw k of loop l:  u = mix(seed ^ mix((l << 32) | k)),  index = (u >> 32) mod num_pts
+ *     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)              (64-bit unsigned, wrapping)
+ *     p1, p2, p3 = draws 0, 1, 2; then with k = 3, 4, ...: while p2 == p1 redraw p2; while p3 is p1 or p2 redraw p3;
+ *     a slot redrawn 64 times takes the lowest index not taken yet.
+ * The same seed gives the same samples and the same bits in every output.  h_drawn receives the samples that were
+ * used (drawn or given).  h_all_rt [num_loops][12], h_all_counts [num_loops]: every hypothesis and its count.
+ * CUSIFT_ERR_INVALID: num_pts < 3 (< 2 for type 0 with h_indices), num_loops < 1, thresh2 not > 0, a sample that is
+ * read out of [0, num_pts), a NULL h_coord / h_rt / num_inliers.  Nothing of the caller's is written except the
+ * outputs.  Blocking: one read-back at the end, no host round trip between the stages. */
+int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord /* [num_pts][6] */, int num_pts,
+                          const int *h_indices /* [num_loops][3], or NULL */, int num_loops, float thresh2,
+                          int type /* 0 = 2D (x-z), 1 = 3D */, uint64_t seed, float h_rt[12], int *num_inliers,
+                          int *best_loop /* may be NULL */, char *h_inliers /* [num_pts], may be NULL */,
+                          float *h_all_rt /* may be NULL */, int *h_all_counts /* may be NULL */,
+                          int *h_drawn /* [num_loops][3], may be NULL */);
 
 #ifdef __cplusplus
 }

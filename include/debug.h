@@ -1,6 +1,6 @@
 // debug.h -- drop-in for the parts of the reference's extras/debug.h that move SiftData around (no OpenCV):
 // AddSiftData (append with doubling), the VLFeat dump format (reader as in the reference, plus a writer so that
-// extracted / gathered SiftData has a wire format), the MATLAB match-index reader and the print helpers.
+// extracted / gathered SiftData has a wire format), the MATLAB match-index and RANSAC readers and the print helpers.
 // Plain C++ over the C ABI (cusift_amd.h); the cv::Mat helpers of the reference (writeMatToFile, PrintMatchData,
 // ReadMATLABMatchData ...) stay out: OpenCV is a caller-side dependency.
 //
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cuSIFT.h"
+#include "matching.h"
 
 // extras/debug.cpp:413-454: append `numPts` host records to `data` (host and device copies), doubling the capacity
 // until they fit.  Deviation: a SiftData without any buffer gets host + device buffers first -- in the reference
@@ -120,6 +121,45 @@ inline int ReadMATLABMatchIndices(const char *indices_filename, uint32_t *indice
     ok = std::fread(indices_i, sizeof(uint32_t), n, fp) == n && std::fread(indices_j, sizeof(uint32_t), n, fp) == n;
   std::fclose(fp);
   return ok ? (int)n : -1;
+}
+
+// extras/debug.cpp:318-371, the dump of the reference authors' DEBUG_ransactfitRt.m:
+//   uint32 numMatches, numLoops; float32 coords3D_i[numMatches][3]; float32 coords3D_j[numMatches][3];
+//   int32 indices[numLoops][3] (1-based); float32 Rt[12]
+// Returns one SiftMatch per match with freshly allocated pt1 / pt2 that carry only coords3D (the caller deletes all
+// three, like in the reference); `indices` receives the 0-based samples, Rt MATLAB's result.  An unreadable or
+// truncated file gives an empty vector (the reference does not check).
+inline std::vector<SiftMatch *> ReadMATLABRANSAC(const char *filename, std::vector<int> &indices, float *Rt) {
+  std::fprintf(stderr, "Reading MATLAB RANSAC data produced using DEBUG_ransactfitRt.m from %s\n", filename);
+  std::vector<SiftMatch *> matches;
+  FILE *fp = std::fopen(filename, "rb");
+  if (!fp) return matches;
+  uint32_t numMatches = 0, numLoops = 0;
+  bool ok = std::fread(&numMatches, sizeof(uint32_t), 1, fp) == 1 && std::fread(&numLoops, sizeof(uint32_t), 1, fp) == 1;
+  std::vector<float> ci, cj;
+  std::vector<int32_t> raw;
+  if (ok) {
+    ci.resize(3 * (size_t)numMatches);
+    cj.resize(3 * (size_t)numMatches);
+    raw.resize(3 * (size_t)numLoops);
+    ok = std::fread(ci.data(), sizeof(float), ci.size(), fp) == ci.size() &&
+         std::fread(cj.data(), sizeof(float), cj.size(), fp) == cj.size() &&
+         std::fread(raw.data(), sizeof(int32_t), raw.size(), fp) == raw.size() &&
+         std::fread(Rt, sizeof(float), 12, fp) == 12;
+  }
+  std::fclose(fp);
+  if (!ok) return matches;
+  std::fprintf(stderr, "Read %d matches and %d loop indices\n", (int)numMatches, (int)numLoops);
+  for (uint32_t i = 0; i < numMatches; ++i) {
+    SiftMatch *match = new SiftMatch();
+    match->pt1 = new SiftPoint();
+    match->pt2 = new SiftPoint();
+    std::memcpy(match->pt1->coords3D, &ci[3 * (size_t)i], sizeof(float) * 3);
+    std::memcpy(match->pt2->coords3D, &cj[3 * (size_t)i], sizeof(float) * 3);
+    matches.push_back(match);
+  }
+  for (size_t i = 0; i < raw.size(); ++i) indices.push_back((int)raw[i] - 1);
+  return matches;
 }
 
 // extras/debug.cpp:26-73: one block of text per keypoint; a SiftData without host records gets them first.
