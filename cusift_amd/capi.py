@@ -71,6 +71,24 @@ class Params(C.Structure):
     ]
 
 
+class Camera(C.Structure):
+    """cusift_camera (include/cusift_amd_extras.h): pinhole intrinsics and the encoding of a 16-bit depth image.
+    origin 1 = MATLAB 1-based cx / cy; encoding 1 = SUN3D PNG samples (the depth rotated left by 3 bits)."""
+
+    _fields_ = [
+        ("fx", C.c_float),
+        ("fy", C.c_float),
+        ("cx", C.c_float),
+        ("cy", C.c_float),
+        ("origin", C.c_float),
+        ("units_per_metre", C.c_float),
+        ("encoding", C.c_int),
+    ]
+
+    def __init__(self, fx, fy, cx, cy, origin=0.0, units_per_metre=1000.0, encoding=0):
+        super().__init__(fx, fy, cx, cy, origin, units_per_metre, encoding)
+
+
 class CusiftError(RuntimeError):
     pass
 
@@ -178,6 +196,10 @@ SIGNATURES = {
     "cusift_find_homography": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, C.POINTER(_i), _vp, _vp]),
     "cusift_estimate_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp,
                                    _vp, _vp]),
+    "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
+    "cusift_select_matches": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
+    "cusift_register_rgbd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(Camera), _i, _f, _f, _i, _f, _i,
+                                  C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
     "cusift_pack_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_compact": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_trimmed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -573,6 +595,42 @@ class Context:
                                           drawn.ctypes.data if want_all else None))
         out = (rt, n.value, best.value, flags.astype(bool))
         return out + (all_rt, all_c, drawn) if want_all else out
+
+    # ---- RGB-D registration ----
+    def lift_depth(self, d_points, max_pts, d_depth, w, h, camera, pitch=None, n_images=1, d_counters=None,
+                   image_stride=None):
+        """cusift_lift_depth: coords3D of d_points[n_images][max_pts] from coords2D, the 16-bit depth image of each
+        frame (device pointer; rows `pitch` samples apart, frames `image_stride` samples apart) and `camera`.
+        d_counters None: every frame has max_pts records.  Asynchronous."""
+        pitch = w if pitch is None else pitch
+        image_stride = h * pitch if image_stride is None else image_stride
+        check(lib().cusift_lift_depth(self.handle, d_points, d_counters, n_images, max_pts, d_depth, w, h, pitch,
+                                      image_stride, C.byref(camera)))
+
+    def select_matches(self, d_sift1, n1, d_sift2, n2, d_pairs, d_coord, d_count, score_threshold=999.0,
+                       ambiguity_threshold=1.0, kind="3d"):
+        """cusift_select_matches: MatchSiftData's threshold filter on the device, after match().  d_pairs int32 [n1, 2],
+        d_coord float32 [n1, 6] and d_count int32 [1] are device pointers; rows come in ascending record order.
+        kind "3d" also asks for a depth on both sides.  Asynchronous."""
+        check(lib().cusift_select_matches(self.handle, d_sift1, n1, d_sift2, n2, score_threshold, ambiguity_threshold,
+                                          RIGID_KINDS[kind], d_pairs, d_coord, d_count))
+
+    def register_rgbd(self, d_sift1, n1, d_depth1, d_sift2, n2, d_depth2, w, h, camera, pitch=None, distance=1,
+                      score_threshold=999.0, ambiguity_threshold=1.0, loops=1024, thresh2=0.0025, kind="3d", seed=0):
+        """cusift_register_rgbd: lift both frames, match, select (3-D), RANSAC + refit -- one synchronisation, at the
+        read-back.  Returns (Rt [3, 4] with x1 ~ R x2 + t, pairs int32 [num_matches, 2], inlier flags bool
+        [num_matches], num_inliers)."""
+        pitch = w if pitch is None else pitch
+        rt = np.zeros((3, 4), dtype=np.float32)
+        n_match, n_in = C.c_int(0), C.c_int(0)
+        pairs = np.zeros((max(n1, 1), 2), dtype=np.int32)
+        flags = np.zeros(max(n1, 1), dtype=np.int8)
+        check(lib().cusift_register_rgbd(self.handle, d_sift1, n1, d_depth1, d_sift2, n2, d_depth2, w, h, pitch,
+                                         C.byref(camera), distance, score_threshold, ambiguity_threshold, int(loops),
+                                         float(thresh2), RIGID_KINDS[kind], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                         rt.ctypes.data, C.byref(n_match), C.byref(n_in), pairs.ctypes.data,
+                                         flags.ctypes.data))
+        return rt, pairs[:n_match.value].copy(), flags[:n_match.value].astype(bool), n_in.value
 
     # ---- drivers ----
     def extract_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):

@@ -3,7 +3,7 @@
 //   sift_context.hip  errors, context + arena + policy + stage timers, memory helpers
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, matcher, homography, rigid
-//                     transform, packing)
+//                     transform, RGB-D registration, packing)
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 #pragma once
@@ -59,10 +59,16 @@ __global__ void homography_gather_kernel(const cusift_point *, int, float *);
 __global__ void homography_solve_kernel(const float *, int, const int *, int, float *);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
 template <bool k3D>
-__global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *);
-__global__ void rigid_score_kernel(const float *, int, int, const float *, int, float, int *);
+__global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *);
+__global__ void rigid_score_kernel(const float *, int, int, const float *, int, float, int *, const int *);
 template <bool k3D>
-__global__ void rigid_select_kernel(const float *, int, const float *, const int *, int, float, float *, char *);
+__global__ void rigid_select_kernel(const float *, int, const float *, const int *, int, float, float *, char *,
+                                    const int *);
+__global__ void rgbd_lift_kernel(cusift_point *, const unsigned int *, int, const unsigned short *, int, int, int, size_t,
+                                 cusift_camera);
+__global__ void match_select_count_kernel(const cusift_point *, int, const cusift_point *, int, float, float, int, int *);
+__global__ void match_select_write_kernel(const cusift_point *, int, const cusift_point *, int, float, float, int,
+                                          const int *, int *, float *, int *);
 __global__ void u8_to_f32_kernel(float *, int, long, const unsigned char *, int, int, int, long, int);
 __global__ void gaussian3x3_kernel(float *, int, long, const float *, int, int, int, long, float, float);
 __global__ void math_eval_kernel(int, const float *, const float *, float *, float *, long);
@@ -144,6 +150,9 @@ struct cusift_ctx {
   // result head / flags / hypotheses / counts / samples / coordinates of cusift_estimate_rigid
   char *rigid_scratch = nullptr;
   size_t rigid_scratch_bytes = 0;
+  // per-workgroup keep counts of cusift_select_matches
+  int *select_scratch = nullptr;
+  size_t select_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;

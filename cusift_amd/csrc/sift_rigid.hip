@@ -157,13 +157,23 @@ __device__ __forceinline__ void rigid_solve_2d(const float *__restrict__ a, cons
   rt[11] = (float)((szw - sn * sxc - cs * szc) / 2.0);
 }
 
+// The number of points when only the device knows it (the matches cusift_register_rgbd selected): *count, never more
+// than the capacity the grids were sized by.  count == NULL: the host's num_pts, as cusift_estimate_rigid passes it.
+__device__ __forceinline__ int rigid_num_pts(const int *__restrict__ count, int capacity) {
+  return count ? min(max(*count, 0), capacity) : capacity;
+}
+
 template <bool k3D>
 __global__ void __launch_bounds__(64) rigid_solve_kernel(const float *__restrict__ coord, int num_pts,
                                                          int *__restrict__ indices, int num_loops, int draw,
                                                          unsigned long long seed, float *__restrict__ rt_all,
-                                                         int *__restrict__ counts) {
+                                                         int *__restrict__ counts, const int *__restrict__ count) {
   const int loop = blockIdx.x * 64 + threadIdx.x;
   if (loop >= num_loops) return;
+  if (count) {  // the point count is on the device (see rigid_num_pts); too few: rigid_select_kernel answers alone
+    num_pts = rigid_num_pts(count, num_pts);
+    if (num_pts < (k3D ? 3 : 2)) return;
+  }
   int p[3];
   if (draw) {
     unsigned int k = 3;
@@ -231,8 +241,10 @@ __device__ __forceinline__ bool rigid_inlier(const float (&rt)[12], float x0, fl
 __global__ void __launch_bounds__(kRigidThreads) rigid_score_kernel(const float *__restrict__ coord, int num_pts,
                                                                     int pts_per_split,
                                                                     const float *__restrict__ rt_all, int num_loops,
-                                                                    float thresh2, int *__restrict__ counts) {
+                                                                    float thresh2, int *__restrict__ counts,
+                                                                    const int *__restrict__ count) {
   __shared__ float s_pt[6][kRigidTile + 1];
+  num_pts = rigid_num_pts(count, num_pts);
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kRigidThreads + tx;
   const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
@@ -268,16 +280,28 @@ __device__ __forceinline__ double rigid_block_sum(double v, double *s_red) {
   return s_red[0];
 }
 
-// head: Rt[12] as float, then count and winning loop as int (16 words).
+// head: Rt[12] as float, then count and winning loop as int and, with a device-side point count, that count
+// (16 words).
 template <bool k3D>
 __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float *__restrict__ coord, int num_pts,
                                                                      const float *__restrict__ rt_all,
                                                                      const int *__restrict__ counts, int num_loops,
                                                                      float thresh2, float *__restrict__ head,
-                                                                     char *__restrict__ flags) {
+                                                                     char *__restrict__ flags,
+                                                                     const int *__restrict__ count) {
   __shared__ unsigned long long s_key[kRigidThreads];
   __shared__ double s_red[kRigidThreads];
   const int tx = threadIdx.x;
+  if (count) {
+    num_pts = rigid_num_pts(count, num_pts);
+    if (tx == 0) ((int *)head)[14] = num_pts;
+    if (num_pts < (k3D ? 3 : 2)) {  // uniform; nothing was solved: the identity, no inlier
+      for (int i = tx; i < num_pts; i += kRigidThreads) flags[i] = 0;
+      if (tx < 12) head[tx] = (tx % 5 == 0) ? 1.0f : 0.0f;
+      if (tx == 0) ((int *)head)[12] = 0, ((int *)head)[13] = 0;
+      return;
+    }
+  }
   unsigned long long key = 0;
   for (int l = tx; l < num_loops; l += kRigidThreads) {
     const unsigned long long k = ((unsigned long long)(unsigned int)counts[l] << 32) | (unsigned int)l;
@@ -336,12 +360,12 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float
 }
 
 template __global__ void rigid_solve_kernel<false>(const float *, int, int *, int, int, unsigned long long, float *,
-                                                   int *);
+                                                   int *, const int *);
 template __global__ void rigid_solve_kernel<true>(const float *, int, int *, int, int, unsigned long long, float *,
-                                                  int *);
+                                                  int *, const int *);
 template __global__ void rigid_select_kernel<false>(const float *, int, const float *, const int *, int, float,
-                                                    float *, char *);
+                                                    float *, char *, const int *);
 template __global__ void rigid_select_kernel<true>(const float *, int, const float *, const int *, int, float, float *,
-                                                   char *);
+                                                   char *, const int *);
 
 }  // namespace cusift

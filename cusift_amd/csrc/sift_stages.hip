@@ -734,6 +734,35 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
 // ------------------------------------------------------------------------------------------------
 // RANSAC rigid transform (sift_rigid.hip)
 // ------------------------------------------------------------------------------------------------
+// The three launches of sift_rigid.hip over d_coord[num_pts][6].  d_count == NULL: num_pts is the number of points;
+// otherwise it is their capacity (the grids are sized by it) and the kernels read the number from *d_count.
+static void rigid_launch(cusift_ctx *ctx, const float *d_coord, int num_pts, const int *d_count, int *d_idx,
+                         int num_loops, int draw, float thresh2, int type, uint64_t seed, float *d_rt, int *d_counts,
+                         float *d_head, char *d_flags) {
+  // scoring: 256 hypotheses per workgroup; split the points until the launch has ~4 workgroups per CU, but keep
+  // at least one 256-point tile per split
+  const int loop_blocks = idiv_up(num_loops, 256);
+  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks), idiv_up(num_pts, 256)));
+  splits = std::min(splits, 65535);
+  const int pts_per_split = idiv_up(num_pts, splits);
+  splits = idiv_up(num_pts, pts_per_split);
+  if (type == 1) {
+    hipLaunchKernelGGL(rigid_solve_kernel<true>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
+                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count);
+    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
+                       pts_per_split, d_rt, num_loops, thresh2, d_counts, d_count);
+    hipLaunchKernelGGL(rigid_select_kernel<true>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt, d_counts,
+                       num_loops, thresh2, d_head, d_flags, d_count);
+  } else {
+    hipLaunchKernelGGL(rigid_solve_kernel<false>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
+                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count);
+    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
+                       pts_per_split, d_rt, num_loops, thresh2, d_counts, d_count);
+    hipLaunchKernelGGL(rigid_select_kernel<false>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
+                       d_counts, num_loops, thresh2, d_head, d_flags, d_count);
+  }
+}
+
 extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int num_pts, const int *h_indices,
                                      int num_loops, float thresh2, int type, uint64_t seed, float h_rt[12],
                                      int *num_inliers, int *best_loop, char *h_inliers, float *h_all_rt,
@@ -772,29 +801,8 @@ extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int 
   HIP_TRY(hipMemcpyAsync(d_coord, h_coord, sizeof(float) * 6 * (size_t)num_pts, hipMemcpyHostToDevice, ctx->stream));
   if (h_indices)
     HIP_TRY(hipMemcpyAsync(d_idx, h_indices, sizeof(int) * 3 * (size_t)num_loops, hipMemcpyHostToDevice, ctx->stream));
-  // scoring: 256 hypotheses per workgroup; split the points until the launch has ~4 workgroups per CU, but keep
-  // at least one 256-point tile per split
-  const int loop_blocks = idiv_up(num_loops, 256);
-  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks), idiv_up(num_pts, 256)));
-  splits = std::min(splits, 65535);
-  const int pts_per_split = idiv_up(num_pts, splits);
-  splits = idiv_up(num_pts, pts_per_split);
-  const int draw = h_indices ? 0 : 1;
-  if (type == 1) {
-    hipLaunchKernelGGL(rigid_solve_kernel<true>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
-                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts);
-    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
-                       pts_per_split, d_rt, num_loops, thresh2, d_counts);
-    hipLaunchKernelGGL(rigid_select_kernel<true>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt, d_counts,
-                       num_loops, thresh2, d_head, d_flags);
-  } else {
-    hipLaunchKernelGGL(rigid_solve_kernel<false>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
-                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts);
-    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
-                       pts_per_split, d_rt, num_loops, thresh2, d_counts);
-    hipLaunchKernelGGL(rigid_select_kernel<false>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
-                       d_counts, num_loops, thresh2, d_head, d_flags);
-  }
+  rigid_launch(ctx, d_coord, num_pts, nullptr, d_idx, num_loops, h_indices ? 0 : 1, thresh2, type, seed, d_rt, d_counts,
+               d_head, d_flags);
   TRY(check_launch("estimate_rigid"));
   // the one blocking read-back
   const bool all = h_all_rt || h_all_counts || h_drawn;
@@ -810,6 +818,156 @@ extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int 
   if (h_all_rt) memcpy(h_all_rt, back.data() + rt_off, sizeof(float) * 12 * (size_t)num_loops);
   if (h_all_counts) memcpy(h_all_counts, back.data() + cnt_off, sizeof(int) * (size_t)num_loops);
   if (h_drawn) memcpy(h_drawn, back.data() + idx_off, sizeof(int) * 3 * (size_t)num_loops);
+  return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// RGB-D registration (sift_rgbd.hip): depth lift, match selection, the fused frame-pair call
+// ------------------------------------------------------------------------------------------------
+static int check_camera(const cusift_camera *cam, const char *who) {
+  if (!cam) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
+  if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || cam->fx == 0.0f || cam->fy == 0.0f ||
+      !std::isfinite(cam->cx) || !std::isfinite(cam->cy) || !std::isfinite(cam->origin))
+    return fail(CUSIFT_ERR_INVALID, "%s: fx and fy must be finite and not 0, cx / cy / origin finite", who);
+  if (!(cam->units_per_metre > 0.0f) || !std::isfinite(cam->units_per_metre))
+    return fail(CUSIFT_ERR_INVALID, "%s: units_per_metre must be > 0", who);
+  if (cam->encoding != 0 && cam->encoding != 1)
+    return fail(CUSIFT_ERR_INVALID, "%s: encoding must be 0 (plain) or 1 (rotated by 3 bits)", who);
+  return CUSIFT_OK;
+}
+
+static int check_depth_geometry(int w, int h, int pitch, size_t image_stride, int n_images, const char *who) {
+  if (w < 1 || h < 1 || w > (1 << 24) || h > (1 << 24) || pitch < w)
+    return fail(CUSIFT_ERR_INVALID, "%s: depth image %d x %d, pitch %d", who, w, h, pitch);
+  if (n_images > 1 && image_stride < (size_t)(h - 1) * (size_t)pitch + (size_t)w)
+    return fail(CUSIFT_ERR_INVALID, "%s: image stride %zu is smaller than one image", who, image_stride);
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_lift_depth(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters, int n_images,
+                                 int max_pts, const uint16_t *d_depth, int width, int height, int pitch_elems,
+                                 size_t image_stride_elems, const cusift_camera *camera) {
+  TRY(enter(ctx));
+  TRY(check_camera(camera, "LiftDepth"));
+  if (n_images < 0 || n_images > 65535 || max_pts < 0)
+    return fail(CUSIFT_ERR_INVALID, "LiftDepth: n_images %d outside [0, 65535] or max_pts %d < 0", n_images, max_pts);
+  if (n_images == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_points || !d_depth) return fail(CUSIFT_ERR_INVALID, "LiftDepth: missing data");
+  TRY(check_depth_geometry(width, height, pitch_elems, image_stride_elems, n_images, "LiftDepth"));
+  hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(max_pts, 256), n_images), dim3(256), 0, ctx->stream, d_points,
+                     d_counters, max_pts, (const unsigned short *)d_depth, width, height, pitch_elems,
+                     image_stride_elems, *camera);
+  return check_launch("lift_depth");
+}
+
+// the two launches of the selection; d_blocks: idiv_up(n1, 256) ints.  n1 >= 1.
+static void select_launch(cusift_ctx *ctx, const cusift_point *d_sift1, int n1, const cusift_point *d_sift2, int n2,
+                          float score_thresh, float ambiguity_thresh, int type, int *d_blocks, int *d_pairs,
+                          float *d_coord, int *d_count) {
+  const float s2 = score_thresh * score_thresh, a2 = ambiguity_thresh * ambiguity_thresh;  // include/matching.h:43-44
+  const int blocks = idiv_up(n1, 256);
+  hipLaunchKernelGGL(match_select_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_sift1, n1, d_sift2, n2, s2,
+                     a2, type, d_blocks);
+  hipLaunchKernelGGL(match_select_write_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_sift1, n1, d_sift2, n2, s2,
+                     a2, type, d_blocks, d_pairs, d_coord, d_count);
+}
+
+extern "C" int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1,
+                                     const cusift_point *d_sift2, int num_pts2, float score_thresh,
+                                     float ambiguity_thresh, int type, int *d_pairs, float *d_coord, int *d_count) {
+  TRY(enter(ctx));
+  if (!d_count) return fail(CUSIFT_ERR_INVALID, "SelectMatches: NULL d_count");
+  if (type != 0 && type != 1) return fail(CUSIFT_ERR_INVALID, "SelectMatches: type must be 0 (2D) or 1 (3D)");
+  if (num_pts1 < 0 || num_pts2 < 0 || num_pts1 > (1 << 26))
+    return fail(CUSIFT_ERR_INVALID, "SelectMatches: num_pts1 %d outside [0, 2^26] or num_pts2 %d < 0", num_pts1, num_pts2);
+  if (std::isnan(score_thresh) || std::isnan(ambiguity_thresh))
+    return fail(CUSIFT_ERR_INVALID, "SelectMatches: a threshold is NaN");
+  if (num_pts1 == 0) {
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
+    return CUSIFT_OK;
+  }
+  if (!d_sift1 || (!d_sift2 && num_pts2 > 0) || !d_pairs || !d_coord)
+    return fail(CUSIFT_ERR_INVALID, "SelectMatches: missing data");
+  TRY(grow_scratch(ctx, ctx->select_scratch, ctx->select_scratch_bytes, sizeof(int) * (size_t)idiv_up(num_pts1, 256), "",
+                   false));
+  select_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, type, ctx->select_scratch,
+                d_pairs, d_coord, d_count);
+  return check_launch("select_matches");
+}
+
+extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const uint16_t *d_depth1,
+                                    cusift_point *d_sift2, int num_pts2, const uint16_t *d_depth2, int width,
+                                    int height, int pitch_elems, const cusift_camera *camera, int distance,
+                                    float score_thresh, float ambiguity_thresh, int num_loops, float thresh2,
+                                    int rigid_type, uint64_t seed, float h_rt[12], int *num_matches, int *num_inliers,
+                                    int *h_pairs, char *h_inliers) {
+  TRY(enter(ctx));
+  if (!h_rt || !num_matches || !num_inliers) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: NULL output");
+  TRY(check_camera(camera, "RegisterRGBD"));
+  if (rigid_type != 0 && rigid_type != 1) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: rigid_type must be 0 (2D) or 1 (3D)");
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: distance must be 0 or 1");
+  if (num_pts1 < 0 || num_pts2 < 0 || num_pts1 > (1 << 26))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: num_pts1 %d outside [0, 2^26] or num_pts2 %d < 0", num_pts1, num_pts2);
+  if (num_loops < 1 || num_loops > (1 << 24))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: num_loops %d outside [1, 2^24]", num_loops);
+  if (!(thresh2 > 0.0f)) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: thresh2 must be > 0");
+  if (std::isnan(score_thresh) || std::isnan(ambiguity_thresh))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: a threshold is NaN");
+  if ((num_pts1 > 0 && (!d_sift1 || !d_depth1)) || (num_pts2 > 0 && (!d_sift2 || !d_depth2)))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: missing data");
+  TRY(check_depth_geometry(width, height, pitch_elems, 0, 1, "RegisterRGBD"));
+  const int n1 = num_pts1;
+  // [head | flags | pairs] is what travels back, in one copy; behind it what stays on the device
+  const size_t head_b = 256;
+  const size_t flag_b = align_up_sz((size_t)std::max(n1, 1), 256);
+  const size_t pair_b = align_up_sz(sizeof(int) * 2 * (size_t)n1, 256);
+  const size_t rt_b = align_up_sz(sizeof(float) * 12 * (size_t)num_loops, 256);
+  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
+  const size_t idx_b = align_up_sz(sizeof(int) * 3 * (size_t)num_loops, 256);
+  const size_t coord_b = align_up_sz(sizeof(float) * 6 * (size_t)n1, 256);
+  const size_t block_b = align_up_sz(sizeof(int) * (size_t)idiv_up(std::max(n1, 1), 256), 256);
+  const size_t pair_off = head_b + flag_b, rt_off = pair_off + pair_b, cnt_off = rt_off + rt_b;
+  const size_t idx_off = cnt_off + cnt_b, coord_off = idx_off + idx_b, block_off = coord_off + coord_b;
+  const size_t count_off = block_off + block_b;
+  TRY(grow_scratch(ctx, ctx->rigid_scratch, ctx->rigid_scratch_bytes, count_off + 256, "", false));
+  char *base = ctx->rigid_scratch;
+  float *d_head = (float *)base, *d_rt = (float *)(base + rt_off), *d_coord = (float *)(base + coord_off);
+  char *d_flags = base + head_b;
+  int *d_pairs = (int *)(base + pair_off), *d_counts = (int *)(base + cnt_off), *d_idx = (int *)(base + idx_off);
+  int *d_blocks = (int *)(base + block_off), *d_count = (int *)(base + count_off);
+  if (n1 > 0)
+    hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(n1, 256), 1), dim3(256), 0, ctx->stream, d_sift1, nullptr, n1,
+                       (const unsigned short *)d_depth1, width, height, pitch_elems, (size_t)0, *camera);
+  if (num_pts2 > 0)
+    hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(num_pts2, 256), 1), dim3(256), 0, ctx->stream, d_sift2, nullptr,
+                       num_pts2, (const unsigned short *)d_depth2, width, height, pitch_elems, (size_t)0, *camera);
+  TRY(check_launch("register_rgbd lift"));
+  static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  if (n1 == 0 || num_pts2 == 0) {  // nothing to match (extras/matching.cu:241-242); known from the arguments alone
+    memcpy(h_rt, ident, sizeof(ident));
+    *num_matches = 0;
+    *num_inliers = 0;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // blocking like the full route: the depth images may be freed
+    return CUSIFT_OK;
+  }
+  TRY(cusift_match(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
+  select_launch(ctx, d_sift1, n1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, 1, d_blocks, d_pairs, d_coord,
+                d_count);
+  rigid_launch(ctx, d_coord, n1, d_count, d_idx, num_loops, 1, thresh2, rigid_type, seed, d_rt, d_counts, d_head,
+               d_flags);
+  TRY(check_launch("register_rgbd"));
+  // the one blocking read-back
+  std::vector<char> back(h_pairs ? rt_off : (h_inliers ? pair_off : head_b));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  int tail[3];
+  memcpy(tail, back.data() + sizeof(float) * 12, sizeof(tail));
+  const int n = std::min(std::max(tail[2], 0), n1);
+  memcpy(h_rt, back.data(), sizeof(float) * 12);
+  *num_inliers = tail[0];
+  *num_matches = n;
+  if (h_inliers) memcpy(h_inliers, back.data() + head_b, (size_t)n);
+  if (h_pairs) memcpy(h_pairs, back.data() + pair_off, sizeof(int) * 2 * (size_t)n);
   return CUSIFT_OK;
 }
 

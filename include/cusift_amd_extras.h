@@ -1,6 +1,6 @@
 /*
- * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography and
- * the RANSAC rigid transform.
+ * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography, the
+ * RANSAC rigid transform and the RGB-D registration built on them (depth lift, match selection, the fused call).
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
@@ -67,6 +67,62 @@ int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord /* [num_pts][6] 
                           int *best_loop /* may be NULL */, char *h_inliers /* [num_pts], may be NULL */,
                           float *h_all_rt /* may be NULL */, int *h_all_counts /* may be NULL */,
                           int *h_drawn /* [num_loops][3], may be NULL */);
+
+/* ---- RGB-D registration: depth lift, match selection on the device, the fused frame-pair call (sift_rgbd.hip) --- */
+/* A pinhole camera and the encoding of its 16-bit depth image.  The reference ships the inputs of this step
+ * (test/data/depth1.png, depth2.png, INTRINSICS, match/match1_2) but no code for it; the convention is the one that
+ * reproduces match/match1_2 from the VLFeat keypoints: SUN3D frames, MATLAB (1-based) intrinsics. */
+typedef struct cusift_camera {
+  float fx, fy, cx, cy;  /* focal lengths and principal point in pixels */
+  float origin;          /* pixel-centre convention of cx / cy: 0 = 0-based, 1 = MATLAB 1-based (the fixture) */
+  float units_per_metre; /* depth samples per metre: 1000 for millimetres */
+  int encoding;          /* 0: the sample is the depth; 1: SUN3D PNG, the depth rotated left by 3 bits */
+} cusift_camera;
+
+/* Writes coords3D of every record from its coords2D = (x, y) (0-based pixels at base-image scale) and the depth image
+ * of its frame, all in fp32:
+ *     u = roundf(x), v = roundf(y);  not finite or outside [0, width) x [0, height)  ->  (0, 0, 0)
+ *     r = depth[v][u];  encoding 1: r = (r >> 3) | (r << 13) in 16 bits;  r == 0  ->  (0, 0, 0)
+ *     z = (float)r / units_per_metre;  X = ((u + origin) - cx) * z / fx;  Y = ((v + origin) - cy) * z / fy
+ * z == 0 is the "no depth" mark that MatchSiftData(..., MatchType3D) and cusift_select_matches test.  The batch is laid
+ * out like the output of cusift_extract_batch: d_points[n_images][max_pts], frame k's depth image at d_depth +
+ * k * image_stride_elems, rows pitch_elems samples apart.  d_counters (may be NULL: every frame has max_pts records)
+ * gives the records per frame; records past the count and every byte of a record other than coords3D are untouched.
+ * Asynchronous on the context's stream. */
+int cusift_lift_depth(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters /* or NULL */, int n_images,
+                      int max_pts, const uint16_t *d_depth, int width, int height, int pitch_elems,
+                      size_t image_stride_elems, const cusift_camera *camera);
+
+/* The threshold filter of MatchSiftData (extras/matching.cu:318-349) on the device, after cusift_match: record i of
+ * d_sift1 is kept iff score < score_thresh^2, ambiguity < ambiguity_thresh^2, 0 <= match < num_pts2 and, for type 1
+ * (MatchType3D), coords3D[2] != 0 in the record and in its partner d_sift2[match].  In ASCENDING i (the order of the
+ * reference's host loop): d_pairs[k] = (i, match), d_coord[k] = coords3D of record i, then of its partner -- the
+ * [n][6] rows cusift_estimate_rigid takes -- and *d_count = the number kept.  d_pairs [num_pts1][2], d_coord
+ * [num_pts1][6] and d_count are device memory; rows past the count are not written.  No atomics: the same input gives
+ * the same output.  Asynchronous on the context's stream. */
+int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                          int num_pts2, float score_thresh, float ambiguity_thresh, int type /* 0 = 2D, 1 = 3D */,
+                          int *d_pairs, float *d_coord, int *d_count);
+
+/* Frame-to-frame registration of an RGB-D pair, device-resident from SiftData + depth to [R | t]: cusift_lift_depth
+ * of both frames (one width x height image each, rows pitch_elems apart), cusift_match(distance), the 3-D selection
+ * above and the RANSAC + refit of cusift_estimate_rigid over the selected pairs, drawn from `seed` -- sampling, tie
+ * rule and refit exactly as documented there, reading the points and their number from device memory.  The result
+ * maps frame 2 into frame 1: x1 ~ R x2 + t.  The same bits as the staged route (lift, match, select, read back,
+ * cusift_estimate_rigid with the same seed).  *num_matches = selected pairs, *num_inliers = the winner's count,
+ * h_pairs [num_matches][2] (capacity num_pts1) and h_inliers [num_matches] (capacity num_pts1) may be NULL.  Fewer
+ * than 3 selected pairs (2 for rigid_type 0): h_rt = identity, *num_inliers = 0, CUSIFT_OK.  The match fields and
+ * coords3D of d_sift1 and coords3D of d_sift2 are written as by the staged calls.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing of the caller's written): NULL h_rt / num_matches / num_inliers /
+ * camera, fx or fy 0 or not finite, units_per_metre not > 0, an unknown encoding / distance / rigid_type, num_loops
+ * < 1, thresh2 not > 0, a NaN threshold, missing buffers, pitch_elems < width.
+ * Blocking: ONE stream synchronisation, at the final read-back; no host decision between the stages. */
+int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const uint16_t *d_depth1,
+                         cusift_point *d_sift2, int num_pts2, const uint16_t *d_depth2, int width, int height,
+                         int pitch_elems, const cusift_camera *camera, int distance, float score_thresh,
+                         float ambiguity_thresh, int num_loops, float thresh2, int rigid_type /* 0 = 2D, 1 = 3D */,
+                         uint64_t seed, float h_rt[12], int *num_matches, int *num_inliers,
+                         int *h_pairs /* may be NULL */, char *h_inliers /* may be NULL */);
 
 #ifdef __cplusplus
 }
