@@ -87,6 +87,24 @@ class BatchExtractor:
 
         return packer
 
+    def register_sequence(self, d_depth, camera, pairs=None, slot=0, **ransac):
+        """Registers the frames of the last extract() into `slot` against each other: cusift_register_rgbd_batch over
+        this extractor's own device records and raw counters -- no count is read back, the frame counts never reach
+        the host.  d_depth: int16 / uint16 device tensor [n, h, w'] (contiguous; w' >= w is the row pitch), one depth
+        image per frame at base-image scale.  pairs: (frame 1, frame 2) rows; None: (i, i + 1) for every consecutive
+        frame.  **ransac goes to capi.Context.register_rgbd_batch (loops, thresh2, kind, seed, distance, score_threshold,
+        ambiguity_threshold).  Returns its tuple: (rt [P, 3, 4], num_matches [P], num_inliers [P], pairs list, flags
+        list); capi.chain_poses(rt) turns the default pair list's result into per-frame poses.  Blocking."""
+        assert d_depth.is_cuda and d_depth.element_size() == 2 and d_depth.is_contiguous()
+        assert d_depth.dim() == 3 and d_depth.shape[0] == self.n and d_depth.shape[1] == self.h, tuple(d_depth.shape)
+        assert d_depth.shape[2] >= self.w, tuple(d_depth.shape)
+        if pairs is None:
+            pairs = [(i, i + 1) for i in range(self.n - 1)]
+        points, counts = self.slots[slot]
+        return self.ctx.register_rgbd_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
+                                            d_depth.data_ptr(), self.w, self.h, camera, pairs,
+                                            pitch=d_depth.shape[2], image_stride=self.h * d_depth.shape[2], **ransac)
+
     def valid_counts(self):
         return torch.clamp(self.counts, max=self.max_pts)
 

@@ -50,6 +50,12 @@ TRIMMED_POINT_DTYPE = np.dtype([("coords2D", "<f4", (2,)), ("scale", "<f4"), ("s
                                 ("orientation", "<f4"), ("subsampling", "<f4"), ("data", "<f4", (128,))])
 TRIMMED_POINT_BYTES = 540
 assert TRIMMED_POINT_DTYPE.itemsize == TRIMMED_POINT_BYTES
+# cusift_match_row (cusift_amd_extras.h): one row of cusift_match_batch
+MATCH_ROW_DTYPE = np.dtype([("score", "<f4"), ("ambiguity", "<f4"), ("match", "<i4"), ("reserved", "<i4")])
+MatchRow = MATCH_ROW_DTYPE
+MATCH_ROW_BYTES = 16
+assert MATCH_ROW_DTYPE.itemsize == MATCH_ROW_BYTES
+
 WIRE_FORMATS = {"exact": (0, SIFT_POINT_BYTES), "compact": (1, COMPACT_POINT_BYTES), "trimmed": (2, TRIMMED_POINT_BYTES)}
 
 
@@ -200,6 +206,9 @@ SIGNATURES = {
     "cusift_select_matches": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
     "cusift_register_rgbd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(Camera), _i, _f, _f, _i, _f, _i,
                                   C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
+    "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
+                                        _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_pack_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_compact": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_trimmed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -332,6 +341,32 @@ def check_rigid_args(coord, indices=None, loops=None, thresh2=0.0025, kind="3d")
     if read.min() < 0 or read.max() >= num_pts:
         raise ValueError("sample index out of range [0, %d)" % num_pts)
     return coord, np.ascontiguousarray(indices), indices.shape[0], RIGID_KINDS[kind]
+
+
+def pair_list(pairs):
+    """A pair list as the C ABI takes it: contiguous int32 [P, 2] of (frame 1, frame 2)."""
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    return pairs
+
+
+def chain_poses(rts, pairs=None):
+    """Poses of the frames of a sequence in frame 0's coordinates, float64 [n_images, 4, 4], from the transforms of
+    consecutive pairs: rts[i] = [R | t] with x_i ~ R x_{i+1} + t (what register_rgbd_batch returns for pair (i, i + 1)),
+    so pose[0] = I and pose[i + 1] = pose[i] @ [[R, t], [0, 1]].  pairs (optional) must be (0, 1), (1, 2), ...:
+    anything else is a ValueError -- composing a graph of loop closures is a pose-graph problem, not this helper's."""
+    rts = np.asarray(rts, dtype=np.float64).reshape(-1, 3, 4)
+    if pairs is not None:
+        pairs = np.asarray(pairs).reshape(-1, 2)
+        want = np.stack([np.arange(len(rts)), np.arange(len(rts)) + 1], axis=1)
+        if pairs.shape != want.shape or not np.array_equal(pairs, want):
+            raise ValueError("chain_poses composes consecutive pairs (i, i + 1) only")
+    poses = np.zeros((len(rts) + 1, 4, 4), dtype=np.float64)
+    poses[0] = np.eye(4)
+    for i, rt in enumerate(rts):
+        step = np.eye(4)
+        step[:3, :] = rt
+        poses[i + 1] = poses[i] @ step
+    return poses
 
 
 class Context:
@@ -631,6 +666,40 @@ class Context:
                                          rt.ctypes.data, C.byref(n_match), C.byref(n_in), pairs.ctypes.data,
                                          flags.ctypes.data))
         return rt, pairs[:n_match.value].copy(), flags[:n_match.value].astype(bool), n_in.value
+
+    # ---- RGB-D registration of a sequence: a batch of frames and a pair list ----
+    def match_batch(self, d_points, d_counters, n_images, max_pts, pairs, d_rows, distance=1):
+        """cusift_match_batch: cusift_match for every (frame 1, frame 2) of `pairs` (int32 [P, 2]) over
+        d_points[n_images][max_pts] + d_counters[n_images] (None: max_pts each), into d_rows[P][max_pts] of MatchRow
+        (device pointer).  The records are not written.  Asynchronous."""
+        pairs = pair_list(pairs)
+        check(lib().cusift_match_batch(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
+                                       len(pairs), distance, d_rows))
+
+    def register_rgbd_batch(self, d_points, d_counters, n_images, max_pts, d_depth, w, h, camera, pairs, pitch=None,
+                            image_stride=None, distance=1, score_threshold=999.0, ambiguity_threshold=1.0, loops=1024,
+                            thresh2=0.0025, kind="3d", seed=0):
+        """cusift_register_rgbd_batch: one lift of all frames, then match, 3-D selection and RANSAC + refit of every
+        pair of `pairs` (int32 [P, 2]) in a fixed number of launches and one synchronisation.  Pair p = (a, b) maps
+        frame b into frame a and draws from seed + p.  Returns (rt float32 [P, 3, 4], num_matches int32 [P],
+        num_inliers int32 [P], a list of P int32 [num_matches, 2] arrays of selected (record in a, record in b), a list
+        of P bool [num_matches] inlier flags)."""
+        pairs = pair_list(pairs)
+        n_pairs = len(pairs)
+        pitch = w if pitch is None else pitch
+        image_stride = h * pitch if image_stride is None else image_stride
+        rt = np.zeros((n_pairs, 3, 4), dtype=np.float32)
+        n_match, n_in = np.zeros(n_pairs, dtype=np.int32), np.zeros(n_pairs, dtype=np.int32)
+        sel = np.zeros((n_pairs, max(max_pts, 1), 2), dtype=np.int32)
+        flags = np.zeros((n_pairs, max(max_pts, 1)), dtype=np.int8)
+        check(lib().cusift_register_rgbd_batch(self.handle, d_points, d_counters, n_images, max_pts, d_depth, w, h,
+                                               pitch, image_stride, C.byref(camera), pairs.ctypes.data, n_pairs,
+                                               distance, score_threshold, ambiguity_threshold, int(loops),
+                                               float(thresh2), RIGID_KINDS[kind], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               rt.ctypes.data, n_match.ctypes.data, n_in.ctypes.data, sel.ctypes.data,
+                                               flags.ctypes.data))
+        return (rt, n_match, n_in, [sel[p, :n_match[p]].copy() for p in range(n_pairs)],
+                [flags[p, :n_match[p]].astype(bool) for p in range(n_pairs)])
 
     # ---- drivers ----
     def extract_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):

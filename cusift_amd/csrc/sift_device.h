@@ -27,6 +27,12 @@ __device__ __forceinline__ int local_row(int y_global, int h_local, RowWindow rw
   return clampi(clampi(y_global, 0, rw.hg - 1) - rw.row0, 0, h_local - 1);
 }
 
+// records of one frame of a batch (d_points[n_images][max_pts] + d_counters[n_images], the output of
+// cusift_extract_batch): the raw counter may exceed max_pts; no counters: every frame is full
+__device__ __forceinline__ int frame_count(const unsigned int *__restrict__ counters, int frame, int max_pts) {
+  return counters ? (int)min(counters[frame], (unsigned int)max_pts) : max_pts;
+}
+
 // lane i receives the value of lane i-1 (lane 0 receives 0): DPP wave_shr:1.  bound_ctrl makes the hardware
 // write 0 for the lane without a source, so no "old" value has to be materialised in front of every DPP move.
 __device__ __forceinline__ float from_prev_lane(float v) {

@@ -55,15 +55,23 @@ __global__ void rootsift_kernel(cusift_point *, int);
 template <bool kL2>
 __global__ void match_kernel(cusift_point *, int, const cusift_point *, int, int, MatchPartial *, int);
 __global__ void match_merge_kernel(cusift_point *, int, const cusift_point *, int, int, const MatchPartial *, int, int);
+template <bool kL2>
+__global__ void match_batch_kernel(const cusift_point *, const unsigned int *, int, const int *, int, MatchPartial *, int,
+                                   cusift_match_row *);
+__global__ void match_batch_merge_kernel(const unsigned int *, int, const int *, int, int, const MatchPartial *, int, int,
+                                         cusift_match_row *);
+__global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
+                                       const cusift_match_row *, float, float, int, int *, float *, int *);
 __global__ void homography_gather_kernel(const cusift_point *, int, float *);
 __global__ void homography_solve_kernel(const float *, int, const int *, int, float *);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
 template <bool k3D>
-__global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *);
-__global__ void rigid_score_kernel(const float *, int, int, const float *, int, float, int *, const int *);
+__global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *,
+                                   RigidBatch);
+__global__ void rigid_score_kernel(const float *, int, int, const float *, int, float, int *, const int *, RigidBatch);
 template <bool k3D>
 __global__ void rigid_select_kernel(const float *, int, const float *, const int *, int, float, float *, char *,
-                                    const int *);
+                                    const int *, RigidBatch);
 __global__ void rgbd_lift_kernel(cusift_point *, const unsigned int *, int, const unsigned short *, int, int, int, size_t,
                                  cusift_camera);
 __global__ void match_select_count_kernel(const cusift_point *, int, const cusift_point *, int, float, float, int, int *);
@@ -153,6 +161,12 @@ struct cusift_ctx {
   // per-workgroup keep counts of cusift_select_matches
   int *select_scratch = nullptr;
   size_t select_scratch_bytes = 0;
+  // cusift_match_batch / cusift_register_rgbd_batch: the pair list and the matcher's per-split partials; the match rows,
+  // the selection and the RANSAC state of every pair (what travels back comes first)
+  char *pairs_scratch = nullptr;
+  size_t pairs_scratch_bytes = 0;
+  char *sequence_scratch = nullptr;
+  size_t sequence_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;

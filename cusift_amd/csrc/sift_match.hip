@@ -42,12 +42,16 @@ __device__ __forceinline__ void top2_scan(float &best, float &second, int &idx, 
   }
 }
 
+// the 1e-6 is a double constant in the reference (extras/matching.cu:143,222): evaluate in double, store float
+__device__ __forceinline__ float match_ambiguity(float best, float second, bool l2) {
+  return l2 ? (float)(best / (second + 1e-6)) : (float)((1 - best) / (1 - second + 1e-6));
+}
+
 // the tail of FindMinCorr/FindMaxCorr (extras/matching.cu:140-150,220-229): the five fields MatchSiftData fills
 __device__ __forceinline__ void write_match(cusift_point *pt, const cusift_point *__restrict__ sift2, int n2,
                                             float best, float second, int idx, bool l2) {
   pt->score = best;
-  // the 1e-6 is a double constant in the reference (:143,:222): evaluate in double, store float
-  pt->ambiguity = l2 ? (float)(best / (second + 1e-6)) : (float)((1 - best) / (1 - second + 1e-6));
+  pt->ambiguity = match_ambiguity(best, second, l2);
   pt->match = idx;
   const int m = (idx >= 0 && idx < n2) ? idx : 0;  // the reference reads sift2[-1] here
   pt->match_xpos = sift2[m].coords2D[0];
@@ -86,107 +90,7 @@ __global__ void __launch_bounds__(256) match_kernel(cusift_point *__restrict__ s
   const int col_end = min(col_begin + cols_per_split, n2);  // padded columns (:57) can never win: skip them
   constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;       // also what a masked column scores: it changes nothing
 
-  // A fragments: lane (r, g) holds elements 16u + 4g + j of descriptor p1_base + r (u = 0..7, j = 0..3)
-  float a[8][4];
-  {
-    const float *d1 = sift1[min(p1_base + r, n1 - 1)].data;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const f4u v = *reinterpret_cast<const f4u *>(d1 + 16 * u + 4 * g);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[u][j] = v[j];
-    }
-  }
-  // running top-2 of rows 4g + q for the columns this lane sees (p2 = r mod 16): reference thread tx = r
-  float best[4], second[4];
-  int bidx[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    best[q] = second[q] = kInit;
-    bidx[q] = -1;
-  }
-
-  // staging: thread t moves four 16-byte chunks per tile; chunk c = t + 256 i -> descriptor c >> 5, floats 4 (c & 31).
-  // Raw buffer loads from a descriptor based at this split's first column: the lane offset is computed once, the tile
-  // and the chunk row advance in the scalar offset, and columns past col_end read as 0 (their scores are masked below).
-  const __amdgpu_buffer_rsrc_t rsrc2 = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)(sift2 + col_begin), 0, (int)((col_end > col_begin ? col_end - col_begin : 0) * sizeof(cusift_point)),
-      kBufFlags);
-  constexpr int kRec = (int)sizeof(cusift_point);
-  const int voff = (int)(threadIdx.x >> 5) * kRec + (int)offsetof(cusift_point, data) + 16 * (int)(threadIdx.x & 31);
-  u4 stage[4];
-  auto fetch = [&](int c0) {
-    const int soff = __builtin_amdgcn_readfirstlane((c0 - col_begin) * kRec);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) stage[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc2, voff, soff + 8 * i * kRec, 0);
-  };
-  if (col_begin < col_end) fetch(col_begin);
-  const float *brow = sB + r * kBStride + 4 * g;
-  for (int c0 = col_begin; c0 < col_end; c0 += kMatchTileCols) {
-    __syncthreads();  // the previous tile has been consumed
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = threadIdx.x + 256 * i;
-      *reinterpret_cast<u4 *>(sB + (c >> 5) * kBStride + 4 * (c & 31)) = stage[i];
-    }
-    __syncthreads();
-    if (c0 + kMatchTileCols < col_end) fetch(c0 + kMatchTileCols);  // in flight while this tile is multiplied
-
-    // two independent 16x16 accumulators (columns c0 + r and c0 + 16 + r), each a k-ordered chain; the B fragments
-    // of step u + 1 are read from LDS before the MFMAs of step u are issued
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    __builtin_amdgcn_s_setprio(1);  // a wave with MFMAs to issue goes before its SIMD's waves that are in the update
-    f4 b0 = *reinterpret_cast<const f4 *>(brow);
-    f4 b1 = *reinterpret_cast<const f4 *>(brow + 16 * kBStride);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      f4 n0 = b0, n1v = b1;
-      if (u < 7) {
-        n0 = *reinterpret_cast<const f4 *>(brow + 16 * (u + 1));
-        n1v = *reinterpret_cast<const f4 *>(brow + 16 * kBStride + 16 * (u + 1));
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b0[j], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b1[j], acc1, 0, 0, 0);
-      }
-      b0 = n0;
-      b1 = n1v;
-    }
-    __builtin_amdgcn_s_setprio(0);
-    // acc[q] = <descriptor p1_base + 4g + q, descriptor p2>.  (Deferring this update into the next tile's MFMA gaps
-    // -- one score per step u -- was built and measured: no change, 110-112 TFLOP/s at 16k either way.)
-    {
-      const bool full = c0 + kMatchTileCols <= col_end;  // wave-uniform: only a split's last tile can be partial
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int p2 = c0 + 16 * t + r;
-        const bool live = full || p2 < col_end;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float dot = t ? acc1[q] : acc0[q];
-          // ComputeL2Distance :71-72, 2 - 2*dot (2*dot is exact, so the fused form has the same bits)
-          float val = kL2 ? (dot > -1.0f ? __builtin_fmaf(-2.0f, dot, 2.0f) : kMatchFltMax) : dot;
-          val = live ? val : kInit;
-          top2_update<kL2>(best[q], second[q], bidx[q], val, p2);
-        }
-      }
-    }
-  }
-  // tree over tx = r (extras/matching.cu:122-138,201-218): lane r < len takes lane r + len; ties keep the lower r
-#pragma unroll
-  for (int len = 8; len > 0; len >>= 1) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float ob = __shfl_down(best[q], len, 16);
-      const float os = __shfl_down(second[q], len, 16);
-      const int oi = __shfl_down(bidx[q], len, 16);
-      if (r < len) {
-        top2_scan(best[q], second[q], bidx[q], ob, oi, kL2);
-        if (beats(os, second[q], kL2)) second[q] = os;
-      }
-    }
-  }
+#include "match_tile.inc"
   if (r == 0) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -223,6 +127,92 @@ __global__ void __launch_bounds__(256) match_merge_kernel(cusift_point *__restri
     if (beats(o.second, m.second, l2)) m.second = o.second;
   }
   write_match(sift1 + p1, sift2, n2, m.best, m.second, m.idx, l2);
+}
+
+// ---- the same matcher over a pair list (cusift_match_batch) -----------------------------------------------------------
+// points[n_images][max_pts] + counters[n_images] as cusift_extract_batch leaves them; pairs[p] = (frame 1, frame 2).
+// A workgroup is (row block, column split, pair): blockIdx.z picks the pair, the two record counts come from device
+// memory (clamped to max_pts like rgbd_lift_kernel's), and a workgroup without rows or without columns returns before
+// it loads a record.  The grid is sized from max_pts because the host does not know the counts.  Results go to
+// rows[pair][max_pts] (score, ambiguity, match: write_match's arithmetic), never into the records, so that a frame can
+// be the first member of any number of pairs.  Rows past frame 1's count are not written; a pair whose frame 2 is empty
+// writes no row at all.
+__device__ __forceinline__ void write_match_row(cusift_match_row *__restrict__ row, float best, float second, int idx,
+                                                bool l2) {
+  f4 v;
+  v[0] = best;
+  v[1] = match_ambiguity(best, second, l2);
+  v[2] = __int_as_float(idx);
+  v[3] = 0.0f;  // reserved
+  *reinterpret_cast<f4 *>(row) = v;
+}
+
+// partials[pair][split][n1_pad]; NULL with one split: the rows are final
+template <bool kL2>
+__global__ void __launch_bounds__(256) match_batch_kernel(const cusift_point *__restrict__ points,
+                                                         const unsigned int *__restrict__ counters, int max_pts,
+                                                         const int *__restrict__ pairs, int cols_per_split,
+                                                         MatchPartial *__restrict__ partials, int n1_pad,
+                                                         cusift_match_row *__restrict__ rows) {
+  __shared__ float sB[kMatchTileCols * kBStride];
+  const int pair = blockIdx.z;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const int col_begin = blockIdx.y * cols_per_split;
+  if ((int)blockIdx.x * kMatchRowsPerBlock >= n1 || col_begin >= n2) return;  // uniform: no rows or no columns
+  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
+  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+
+#include "match_tile.inc"
+  if (r == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p1 = p1_base + 4 * g + q;
+      if (p1 >= n1) continue;
+      if (partials) {
+        MatchPartial mp;
+        mp.best = best[q];
+        mp.second = second[q];
+        mp.idx = bidx[q];
+        partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = mp;
+      } else {
+        write_match_row(rows + (size_t)pair * max_pts + p1, best[q], second[q], bidx[q], kL2);
+      }
+    }
+  }
+}
+
+template __global__ void match_batch_kernel<false>(const cusift_point *, const unsigned int *, int, const int *, int,
+                                                   MatchPartial *, int, cusift_match_row *);
+template __global__ void match_batch_kernel<true>(const cusift_point *, const unsigned int *, int, const int *, int,
+                                                  MatchPartial *, int, cusift_match_row *);
+
+// match_merge_kernel per pair (blockIdx.y): folds the splits that had columns, in column order.
+__global__ void __launch_bounds__(256) match_batch_merge_kernel(const unsigned int *__restrict__ counters, int max_pts,
+                                                               const int *__restrict__ pairs, int l2_mode,
+                                                               int cols_per_split,
+                                                               const MatchPartial *__restrict__ partials, int n1_pad,
+                                                               int n_splits, cusift_match_row *__restrict__ rows) {
+  const bool l2 = l2_mode != 0;
+  const int pair = blockIdx.y;
+  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const int p1 = blockIdx.x * 256 + threadIdx.x;
+  if (p1 >= n1 || n2 <= 0) return;
+  const int live = min(n_splits, (n2 + cols_per_split - 1) / cols_per_split);  // the others wrote nothing
+  const MatchPartial *__restrict__ mine = partials + (size_t)pair * n_splits * n1_pad + p1;
+  MatchPartial m = mine[0];
+  for (int s = 1; s < live; ++s) {
+    const MatchPartial o = mine[(size_t)s * n1_pad];
+    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
+    if (beats(o.second, m.second, l2)) m.second = o.second;
+  }
+  write_match_row(rows + (size_t)pair * max_pts + p1, m.best, m.second, m.idx, l2);
 }
 
 }  // namespace cusift

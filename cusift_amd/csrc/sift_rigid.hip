@@ -12,6 +12,10 @@
 //   rigid_select_kernel  one workgroup: the winner (64-bit max over count << 32 | loop: the highest count and, among
 //                        equals, the highest loop -- the reference's `>=` at :450), its inlier flags, and for the 3-D
 //                        type the refit over all its inliers in a fixed reduction order (same bits every run)
+// Every kernel has a pair dimension, blockIdx.z: pair p works on its own coordinates, point count, samples, hypotheses,
+// counts, head and flags, RigidBatch's strides apart, and draws from seed + p (64-bit, wrapping).  One pair
+// (cusift_estimate_rigid, cusift_register_rgbd) is gridDim.z == 1; cusift_register_rgbd_batch runs all its pairs in
+// the same three launches.
 // The reference's num_loops x num_pts byte matrix of flags (:427) does not exist here: only the winner's row is read.
 //
 // PRECISION.  Scoring is fp32 like the reference (fused multiply-adds written out).  Both solves and the refit are
@@ -167,9 +171,16 @@ template <bool k3D>
 __global__ void __launch_bounds__(64) rigid_solve_kernel(const float *__restrict__ coord, int num_pts,
                                                          int *__restrict__ indices, int num_loops, int draw,
                                                          unsigned long long seed, float *__restrict__ rt_all,
-                                                         int *__restrict__ counts, const int *__restrict__ count) {
+                                                         int *__restrict__ counts, const int *__restrict__ count,
+                                                         RigidBatch nb) {
   const int loop = blockIdx.x * 64 + threadIdx.x;
   if (loop >= num_loops) return;
+  {
+    const size_t pz = blockIdx.z;
+    coord += pz * nb.coord, indices += pz * nb.indices, rt_all += pz * nb.rt, counts += pz * nb.counts;
+    if (count) count += pz * nb.count;
+    seed += pz;
+  }
   if (count) {  // the point count is on the device (see rigid_num_pts); too few: rigid_select_kernel answers alone
     num_pts = rigid_num_pts(count, num_pts);
     if (num_pts < (k3D ? 3 : 2)) return;
@@ -242,8 +253,14 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_score_kernel(const float 
                                                                     int pts_per_split,
                                                                     const float *__restrict__ rt_all, int num_loops,
                                                                     float thresh2, int *__restrict__ counts,
-                                                                    const int *__restrict__ count) {
+                                                                    const int *__restrict__ count,
+                                                                    RigidBatch nb) {
   __shared__ float s_pt[6][kRigidTile + 1];
+  {
+    const size_t pz = blockIdx.z;
+    coord += pz * nb.coord, rt_all += pz * nb.rt, counts += pz * nb.counts;
+    if (count) count += pz * nb.count;
+  }
   num_pts = rigid_num_pts(count, num_pts);
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kRigidThreads + tx;
@@ -288,10 +305,16 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float
                                                                      const int *__restrict__ counts, int num_loops,
                                                                      float thresh2, float *__restrict__ head,
                                                                      char *__restrict__ flags,
-                                                                     const int *__restrict__ count) {
+                                                                     const int *__restrict__ count,
+                                                                     RigidBatch nb) {
   __shared__ unsigned long long s_key[kRigidThreads];
   __shared__ double s_red[kRigidThreads];
   const int tx = threadIdx.x;
+  {
+    const size_t pz = blockIdx.z;
+    coord += pz * nb.coord, rt_all += pz * nb.rt, counts += pz * nb.counts, head += pz * nb.head, flags += pz * nb.flags;
+    if (count) count += pz * nb.count;
+  }
   if (count) {
     num_pts = rigid_num_pts(count, num_pts);
     if (tx == 0) ((int *)head)[14] = num_pts;
@@ -360,12 +383,12 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float
 }
 
 template __global__ void rigid_solve_kernel<false>(const float *, int, int *, int, int, unsigned long long, float *,
-                                                   int *, const int *);
+                                                   int *, const int *, RigidBatch);
 template __global__ void rigid_solve_kernel<true>(const float *, int, int *, int, int, unsigned long long, float *,
-                                                  int *, const int *);
+                                                  int *, const int *, RigidBatch);
 template __global__ void rigid_select_kernel<false>(const float *, int, const float *, const int *, int, float,
-                                                    float *, char *, const int *);
+                                                    float *, char *, const int *, RigidBatch);
 template __global__ void rigid_select_kernel<true>(const float *, int, const float *, const int *, int, float, float *,
-                                                   char *, const int *);
+                                                   char *, const int *, RigidBatch);
 
 }  // namespace cusift

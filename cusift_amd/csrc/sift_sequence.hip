@@ -1,0 +1,78 @@
+// sift_sequence.hip -- the selection stage of the batched RGB-D registration (cusift_register_rgbd_batch): a batch of
+// frames and a pair list in, one [R | t] per pair out, in a fixed number of launches:
+//
+//   rgbd_lift_kernel           (sift_rgbd.hip)   coords3D of every frame, one launch
+//   match_batch_kernel         (sift_match.hip)  every pair's best / second-best, grid (row block, column split, pair)
+//   match_batch_merge_kernel   (sift_match.hip)  the splits folded in column order -> rows[pair][max_pts]
+//   sequence_select_kernel     (here)            the threshold filter of every pair -> pairs / coord / count per pair
+//   rigid_solve / score / select (sift_rigid.hip) the RANSAC of every pair, blockIdx.z = pair
+//
+// THE SELECTION is match_select_*'s rule (sift_rgbd.hip; include/matching.h:43-58) read from the match rows instead of
+// the records: row i of pair (f1, f2) is kept iff score < score_thresh2 && ambiguity < ambiguity_thresh2 &&
+// 0 <= match < n2 and, for the 3-D type, coords3D[2] != 0 in record i of f1 and in record `match` of f2.  One workgroup
+// per pair walks frame 1's records 256 at a time with a running base, ranks its keeps with ballot + mbcnt inside a wave
+// and a 4-entry scan across its waves: ascending record order, no atomics, the same output every run.  The record
+// counts come from device memory (frame_count); nothing is written past a pair's count.
+// No scratch memory, vector stores only.
+#include "sift_device.h"
+
+namespace cusift {
+
+constexpr int kSequenceSelectThreads = 256;
+
+// sel_pairs[pair][max_pts][2], coord[pair][max_pts][6], sel_count[pair]
+__global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel(
+    const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
+    const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, float score_thresh2,
+    float ambiguity_thresh2, int type3d, int *__restrict__ sel_pairs, float *__restrict__ coord,
+    int *__restrict__ sel_count) {
+  __shared__ int s_wave[kSequenceSelectThreads / 64];
+  const int tx = threadIdx.x;
+  const int pair = blockIdx.x;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
+  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
+  rows += (size_t)pair * max_pts;
+  sel_pairs += 2 * (size_t)pair * max_pts;
+  coord += 6 * (size_t)pair * max_pts;
+  int base = 0;
+  // n2 == 0: the matcher wrote no row of this pair (nothing to match, extras/matching.cu:241-242)
+  for (int chunk = 0; n2 > 0 && chunk < n1; chunk += kSequenceSelectThreads) {
+    const int i = chunk + tx;
+    bool keep = false;
+    int partner = -1;
+    if (i < n1) {
+      const f4 row = *reinterpret_cast<const f4 *>(rows + i);  // score, ambiguity, match, reserved
+      const int m = __float_as_int(row[2]);
+      keep = row[0] < score_thresh2 && row[1] < ambiguity_thresh2 && m >= 0 && m < n2;
+      if (keep && type3d) keep = sift1[i].coords3D[2] != 0.0f && sift2[m].coords3D[2] != 0.0f;
+      partner = keep ? m : -1;
+    }
+    const unsigned long long mask = __ballot(keep);
+    const int rank =
+        __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
+    if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(mask);
+    __syncthreads();
+    int wave_base = 0, total = 0;
+#pragma unroll
+    for (int wv = 0; wv < kSequenceSelectThreads / 64; ++wv) {
+      wave_base += wv < (tx >> 6) ? s_wave[wv] : 0;
+      total += s_wave[wv];
+    }
+    if (keep) {
+      const int k = base + wave_base + rank;  // < n1: every keep before this one is a distinct record below i
+      sel_pairs[2 * (size_t)k + 0] = i;
+      sel_pairs[2 * (size_t)k + 1] = partner;
+      const float *a = sift1[i].coords3D, *b = sift2[partner].coords3D;
+      float *c = coord + 6 * (size_t)k;
+      c[0] = a[0], c[1] = a[1], c[2] = a[2];
+      c[3] = b[0], c[4] = b[1], c[5] = b[2];
+    }
+    base += total;
+    __syncthreads();  // s_wave is rewritten by the next chunk
+  }
+  if (tx == 0) sel_count[pair] = base;
+}
+
+}  // namespace cusift

@@ -736,31 +736,33 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
 // ------------------------------------------------------------------------------------------------
 // The three launches of sift_rigid.hip over d_coord[num_pts][6].  d_count == NULL: num_pts is the number of points;
 // otherwise it is their capacity (the grids are sized by it) and the kernels read the number from *d_count.
+// n_pairs > 1: that many independent problems, `nb` elements apart in every array, pair p drawing from seed + p.
 static void rigid_launch(cusift_ctx *ctx, const float *d_coord, int num_pts, const int *d_count, int *d_idx,
                          int num_loops, int draw, float thresh2, int type, uint64_t seed, float *d_rt, int *d_counts,
-                         float *d_head, char *d_flags) {
+                         float *d_head, char *d_flags, int n_pairs = 1, RigidBatch nb = RigidBatch{}) {
   // scoring: 256 hypotheses per workgroup; split the points until the launch has ~4 workgroups per CU, but keep
   // at least one 256-point tile per split
   const int loop_blocks = idiv_up(num_loops, 256);
-  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks), idiv_up(num_pts, 256)));
+  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks * n_pairs), idiv_up(num_pts, 256)));
   splits = std::min(splits, 65535);
   const int pts_per_split = idiv_up(num_pts, splits);
   splits = idiv_up(num_pts, pts_per_split);
-  if (type == 1) {
-    hipLaunchKernelGGL(rigid_solve_kernel<true>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
-                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count);
-    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
-                       pts_per_split, d_rt, num_loops, thresh2, d_counts, d_count);
-    hipLaunchKernelGGL(rigid_select_kernel<true>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt, d_counts,
-                       num_loops, thresh2, d_head, d_flags, d_count);
-  } else {
-    hipLaunchKernelGGL(rigid_solve_kernel<false>, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord,
-                       num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count);
-    hipLaunchKernelGGL(rigid_score_kernel, dim3(loop_blocks, splits), dim3(256), 0, ctx->stream, d_coord, num_pts,
-                       pts_per_split, d_rt, num_loops, thresh2, d_counts, d_count);
-    hipLaunchKernelGGL(rigid_select_kernel<false>, dim3(1), dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
-                       d_counts, num_loops, thresh2, d_head, d_flags, d_count);
-  }
+  const dim3 solve_grid(idiv_up(num_loops, 64), 1, n_pairs), score_grid(loop_blocks, splits, n_pairs);
+  const dim3 select_grid(1, 1, n_pairs);
+  if (type == 1)
+    hipLaunchKernelGGL(rigid_solve_kernel<true>, solve_grid, dim3(64), 0, ctx->stream, d_coord, num_pts, d_idx,
+                       num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count, nb);
+  else
+    hipLaunchKernelGGL(rigid_solve_kernel<false>, solve_grid, dim3(64), 0, ctx->stream, d_coord, num_pts, d_idx,
+                       num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count, nb);
+  hipLaunchKernelGGL(rigid_score_kernel, score_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, pts_per_split, d_rt,
+                     num_loops, thresh2, d_counts, d_count, nb);
+  if (type == 1)
+    hipLaunchKernelGGL(rigid_select_kernel<true>, select_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
+                       d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
+  else
+    hipLaunchKernelGGL(rigid_select_kernel<false>, select_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
+                       d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
 }
 
 extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int num_pts, const int *h_indices,
@@ -968,6 +970,147 @@ extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int 
   *num_matches = n;
   if (h_inliers) memcpy(h_inliers, back.data() + head_b, (size_t)n);
   if (h_pairs) memcpy(h_pairs, back.data() + pair_off, sizeof(int) * 2 * (size_t)n);
+  return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same over a batch of frames and a pair list (sift_sequence.hip)
+// ------------------------------------------------------------------------------------------------
+static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int max_pts, const char *who) {
+  if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_pairs %d outside [0, 65535]", who, n_pairs);
+  if (n_images < 0 || n_images > 65535)
+    return fail(CUSIFT_ERR_INVALID, "%s: n_images %d outside [0, 65535]", who, n_images);
+  if (max_pts < 0 || max_pts > (1 << 20)) return fail(CUSIFT_ERR_INVALID, "%s: max_pts %d outside [0, 2^20]", who, max_pts);
+  if (n_pairs > 0 && !h_pairs) return fail(CUSIFT_ERR_INVALID, "%s: NULL pair list", who);
+  for (int p = 0; p < 2 * n_pairs; ++p)
+    if (h_pairs[p] < 0 || h_pairs[p] >= n_images)
+      return fail(CUSIFT_ERR_INVALID, "%s: pair %d names frame %d outside [0, %d)", who, p / 2, h_pairs[p], n_images);
+  return CUSIFT_OK;
+}
+
+// Uploads the pair list and enqueues the matcher of every pair: one launch, plus the merge when the columns are split.
+// *d_pairs_out: the list on the device, for the stages behind it.  n_pairs >= 1, max_pts >= 1, the list is checked.
+static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
+                              const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
+                              const int **d_pairs_out) {
+  // Column splits, sized from max_pts (the counts stay on the device): aim at >= 4 workgroups per CU over all pairs,
+  // keep >= 4 LDS tiles (128 columns) per split.  max_pts <= 2^20 records fit one split's 32-bit byte offsets.
+  const int row_blocks = idiv_up(max_pts, 64);
+  const long blocks = (long)row_blocks * n_pairs;
+  int splits = (int)std::max(1L, std::min((4L * ctx->num_cus + blocks - 1) / blocks, (long)idiv_up(max_pts, 128)));
+  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(max_pts, 32));
+  splits = std::min(splits, 65535);
+  const int cols_per_split = idiv_up(idiv_up(max_pts, splits), 32) * 32;
+  splits = idiv_up(max_pts, cols_per_split);
+  const int n1_pad = row_blocks * 64;
+  const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
+  const size_t part_b = splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0;
+  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b, "", false));
+  int *d_pairs = (int *)ctx->pairs_scratch;
+  MatchPartial *partials = splits > 1 ? (MatchPartial *)(ctx->pairs_scratch + list_b) : nullptr;
+  HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  const dim3 grid(row_blocks, splits, n_pairs);
+  if (distance)
+    hipLaunchKernelGGL(match_batch_kernel<true>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
+                       cols_per_split, partials, n1_pad, d_rows);
+  else
+    hipLaunchKernelGGL(match_batch_kernel<false>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
+                       cols_per_split, partials, n1_pad, d_rows);
+  if (splits > 1)
+    hipLaunchKernelGGL(match_batch_merge_kernel, dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream,
+                       d_counters, max_pts, d_pairs, distance, cols_per_split, partials, n1_pad, splits, d_rows);
+  *d_pairs_out = d_pairs;
+  return check_launch("match_batch");
+}
+
+extern "C" int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                  int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                  cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "MatchBatch: distance must be 0 or 1");
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "MatchBatch"));
+  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatch: missing data");
+  const int *d_pairs = nullptr;
+  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs);
+}
+
+extern "C" int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters,
+                                          int n_images, int max_pts, const uint16_t *d_depth, int width, int height,
+                                          int pitch_elems, size_t image_stride_elems, const cusift_camera *camera,
+                                          const int *h_pairs, int n_pairs, int distance, float score_thresh,
+                                          float ambiguity_thresh, int num_loops, float thresh2, int rigid_type,
+                                          uint64_t seed, float *h_rt, int *h_num_matches, int *h_num_inliers,
+                                          int *h_sel_pairs, char *h_inliers) {
+  TRY(enter(ctx));
+  if (!h_rt || !h_num_matches || !h_num_inliers) return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: NULL output");
+  TRY(check_camera(camera, "RegisterRGBDBatch"));
+  if (rigid_type != 0 && rigid_type != 1)
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: rigid_type must be 0 (2D) or 1 (3D)");
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: distance must be 0 or 1");
+  if (num_loops < 1 || num_loops > (1 << 24))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: num_loops %d outside [1, 2^24]", num_loops);
+  if (!(thresh2 > 0.0f)) return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: thresh2 must be > 0");
+  if (std::isnan(score_thresh) || std::isnan(ambiguity_thresh))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: a threshold is NaN");
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "RegisterRGBDBatch"));
+  if (n_images > 0 && max_pts > 0 && (!d_points || !d_depth))
+    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: missing data");
+  TRY(check_depth_geometry(width, height, pitch_elems, image_stride_elems, n_images, "RegisterRGBDBatch"));
+  if (n_pairs == 0) return CUSIFT_OK;
+  static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  if (max_pts == 0) {  // every frame is empty: nothing to match (extras/matching.cu:241-242)
+    for (int p = 0; p < n_pairs; ++p) {
+      memcpy(h_rt + 12 * (size_t)p, ident, sizeof(ident));
+      h_num_matches[p] = h_num_inliers[p] = 0;
+    }
+    return CUSIFT_OK;
+  }
+  // [heads | flags | selected pairs] is what travels back, in one copy; behind it what stays on the device.  A head is
+  // rigid_select_kernel's 16 words.
+  const size_t P = (size_t)n_pairs, M = (size_t)max_pts, L = (size_t)num_loops;
+  const size_t head_b = align_up_sz(64 * P, 256), flag_b = align_up_sz(P * M, 256);
+  const size_t pair_b = align_up_sz(sizeof(int) * 2 * P * M, 256), row_b = align_up_sz(sizeof(cusift_match_row) * P * M, 256);
+  const size_t coord_b = align_up_sz(sizeof(float) * 6 * P * M, 256), count_b = align_up_sz(sizeof(int) * P, 256);
+  const size_t rt_b = align_up_sz(sizeof(float) * 12 * P * L, 256), cnt_b = align_up_sz(sizeof(int) * P * L, 256);
+  const size_t idx_b = align_up_sz(sizeof(int) * 3 * P * L, 256);
+  const size_t flag_off = head_b, pair_off = flag_off + flag_b, row_off = pair_off + pair_b, coord_off = row_off + row_b;
+  const size_t count_off = coord_off + coord_b, rt_off = count_off + count_b, cnt_off = rt_off + rt_b;
+  const size_t idx_off = cnt_off + cnt_b;
+  TRY(grow_scratch(ctx, ctx->sequence_scratch, ctx->sequence_scratch_bytes, idx_off + idx_b, "", false));
+  char *base = ctx->sequence_scratch;
+  float *d_head = (float *)base, *d_coord = (float *)(base + coord_off), *d_rt = (float *)(base + rt_off);
+  char *d_flags = base + flag_off;
+  int *d_sel = (int *)(base + pair_off), *d_count = (int *)(base + count_off), *d_counts = (int *)(base + cnt_off);
+  int *d_idx = (int *)(base + idx_off);
+  cusift_match_row *d_rows = (cusift_match_row *)(base + row_off);
+  hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(max_pts, 256), n_images), dim3(256), 0, ctx->stream, d_points,
+                     d_counters, max_pts, (const unsigned short *)d_depth, width, height, pitch_elems,
+                     image_stride_elems, *camera);
+  const int *d_pairs = nullptr;
+  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs));
+  hipLaunchKernelGGL(sequence_select_kernel, dim3(n_pairs), dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
+                     d_pairs, d_rows, score_thresh * score_thresh, ambiguity_thresh * ambiguity_thresh, 1, d_sel,
+                     d_coord, d_count);
+  RigidBatch nb;
+  nb.coord = 6 * M, nb.indices = 3 * L, nb.rt = 12 * L, nb.counts = L, nb.head = 16, nb.flags = M, nb.count = 1;
+  rigid_launch(ctx, d_coord, max_pts, d_count, d_idx, num_loops, 1, thresh2, rigid_type, seed, d_rt, d_counts, d_head,
+               d_flags, n_pairs, nb);
+  TRY(check_launch("register_rgbd_batch"));
+  // the one blocking read-back
+  std::vector<char> back(h_sel_pairs ? row_off : (h_inliers ? pair_off : 64 * P));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (size_t p = 0; p < P; ++p) {
+    int tail[3];
+    memcpy(tail, back.data() + 64 * p + sizeof(float) * 12, sizeof(tail));
+    const size_t n = (size_t)std::min(std::max(tail[2], 0), max_pts);
+    memcpy(h_rt + 12 * p, back.data() + 64 * p, sizeof(float) * 12);
+    h_num_inliers[p] = tail[0];
+    h_num_matches[p] = (int)n;
+    if (h_inliers) memcpy(h_inliers + p * M, back.data() + flag_off + p * M, n);
+    if (h_sel_pairs) memcpy(h_sel_pairs + 2 * p * M, back.data() + pair_off + sizeof(int) * 2 * p * M, sizeof(int) * 2 * n);
+  }
   return CUSIFT_OK;
 }
 

@@ -144,6 +144,12 @@ struct MatchPartial {
   int idx;
 };
 
+// elements between consecutive pairs of a batched RANSAC (blockIdx.z of the rigid_* kernels); all 0 for one pair
+struct RigidBatch {
+  size_t coord, indices, rt, counts, head, flags;
+  int count;
+};
+
 static_assert(sizeof(cusift_point) == 588, "SiftPoint is a 588-byte ABI record (cuSIFT.h:10-30)");
 
 }  // namespace cusift

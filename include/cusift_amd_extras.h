@@ -1,6 +1,7 @@
 /*
  * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography, the
- * RANSAC rigid transform and the RGB-D registration built on them (depth lift, match selection, the fused call).
+ * RANSAC rigid transform and the RGB-D registration built on them (depth lift, match selection, the fused call for
+ * one frame pair and for a pair list over a batch of frames).
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
@@ -123,6 +124,64 @@ int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, c
                          float ambiguity_thresh, int num_loops, float thresh2, int rigid_type /* 0 = 2D, 1 = 3D */,
                          uint64_t seed, float h_rt[12], int *num_matches, int *num_inliers,
                          int *h_pairs /* may be NULL */, char *h_inliers /* may be NULL */);
+
+/* ---- the same over a sequence: a batch of frames and a pair list (sift_sequence.hip) ----------------------------- */
+/* The reference registers sequences -- main.cpp: compareMatchingWithMATLAB walks its frames i -> i + 1, test/test.cpp
+ * registers SUN3D frames -- one MatchSiftData (extras/matching.cu:232-362) and one EstimateRigidTransformH
+ * (extras/rigidTransform.cu:388-520) per pair.  The calls below take the layout cusift_extract_batch produces,
+ * d_points[n_images][max_pts] + d_counters[n_images], and a list of frame pairs, and do every pair in the same launches.
+ *
+ * One row of cusift_match_batch: the fields FindMinCorr / FindMaxCorr compute (extras/matching.cu:140-150,219-229),
+ * kept out of the records so that a frame can be the first member of any number of pairs. */
+typedef struct {
+  float score, ambiguity;
+  int match;
+  int reserved; /* written as 0 */
+} cusift_match_row;
+
+/* cusift_match over a pair list: h_pairs[p] = (frame 1, frame 2), host memory, read before the call returns (keep it
+ * valid until the stream has passed the call if it is page-locked).  For pair p and every record i of frame 1,
+ * d_rows[p * max_pts + i] = score, ambiguity and match (an index into frame 2) exactly as cusift_match would write them
+ * into record i: the same dot products in the same order, the same double-precision 1e-6 in the ambiguity; only between
+ * columns whose best scores are exactly equal may `match` name another one of them.  The records per frame are
+ * min(d_counters[frame], max_pts), read on the device (d_counters == NULL: max_pts each); rows past frame 1's count are
+ * not written, and a pair whose frame 2 has no record writes no row (extras/matching.cu:241-242).  The records are not
+ * written at all.  A frame may appear in any number of pairs, on either side; (a, a) is legal.  d_rows: device memory,
+ * [n_pairs][max_pts], 16-byte aligned.
+ * CUSIFT_ERR_INVALID (nothing enqueued): a pair index outside [0, n_images), n_pairs or n_images outside [0, 65535],
+ * max_pts outside [0, 2^20], a NULL h_pairs with n_pairs > 0, an unknown distance, missing buffers.  n_pairs == 0 or
+ * max_pts == 0: CUSIFT_OK, nothing enqueued.  Asynchronous on the context's stream. */
+int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
+                       int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
+                       cusift_match_row *d_rows);
+
+/* cusift_register_rgbd for every pair of a list, device-resident from the extractor's batch + depth images to one
+ * [R | t] per pair: ONE cusift_lift_depth over all frames (frame k's depth image at d_depth + k * image_stride_elems),
+ * cusift_match_batch, the 3-D selection of cusift_select_matches per pair, and the RANSAC + refit of
+ * cusift_estimate_rigid per pair -- sampling, tie rule and refit exactly as documented there, pair p drawing from
+ * seed + p (64-bit, wrapping).  Pair p = (a, b) maps frame b into frame a: x_a ~ R x_b + t, h_rt[12 p .. 12 p + 11].
+ * Every output of pair p has the bits cusift_register_rgbd(frame a, frame b, ..., seed + p) returns.  h_num_matches[p]
+ * = selected matches, h_num_inliers[p] = the winner's count; h_sel_pairs ([n_pairs][max_pts][2], may be NULL) and
+ * h_inliers ([n_pairs][max_pts], may be NULL) receive the first h_num_matches[p] entries of pair p's block, the rest of
+ * a block is not written.  Fewer than 3 selected matches (2 for rigid_type 0), an empty frame included: identity, 0
+ * inliers, CUSIFT_OK.  Of the records only coords3D is written.  A frame may appear in any number of pairs, on either
+ * side; (a, a) is legal.  The launch count does not depend on n_pairs, and the host takes no decision between the
+ * stages.  Scratch lives in the context and grows on demand.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing of the caller's written): every case of cusift_register_rgbd -- NULL
+ * h_rt / h_num_matches / h_num_inliers / camera, fx or fy 0 or not finite, units_per_metre not > 0, an unknown encoding
+ * / distance / rigid_type, num_loops < 1, thresh2 not > 0, a NaN threshold, missing buffers, pitch_elems < width --
+ * and: image_stride_elems smaller than one image (n_images > 1), a pair index outside [0, n_images), n_pairs or
+ * n_images outside [0, 65535], max_pts outside [0, 2^20], a NULL h_pairs with n_pairs > 0.  n_pairs == 0: CUSIFT_OK,
+ * nothing enqueued.
+ * Blocking: ONE stream synchronisation, at the one read-back. */
+int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
+                               int n_images, int max_pts, const uint16_t *d_depth, int width, int height,
+                               int pitch_elems, size_t image_stride_elems, const cusift_camera *camera,
+                               const int *h_pairs /* [n_pairs][2]: (frame 1, frame 2) */, int n_pairs, int distance,
+                               float score_thresh, float ambiguity_thresh, int num_loops, float thresh2,
+                               int rigid_type /* 0 = 2D, 1 = 3D */, uint64_t seed, float *h_rt /* [n_pairs][12] */,
+                               int *h_num_matches, int *h_num_inliers, int *h_sel_pairs /* may be NULL */,
+                               char *h_inliers /* may be NULL */);
 
 #ifdef __cplusplus
 }

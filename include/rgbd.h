@@ -6,7 +6,8 @@
 //     EstimateRigidTransform(matches, Rt, &numInliers, 1024, 0.05, RigidTransformType3D);  // rigidTransform.h, unchanged
 // RegisterRGBD does the same without the two host filters and the re-upload in between (cusift_register_rgbd,
 // cusift_amd_extras.h: one stream synchronisation, at the read-back).  The lift convention is documented at
-// cusift_lift_depth.  Plain C++ over the C ABI: no HIP headers.
+// cusift_lift_depth.  RegisterRGBDSequence does a whole sequence -- a pair list over n frames -- in one such call
+// (cusift_register_rgbd_batch).  Plain C++ over the C ABI: no HIP headers.
 #ifndef CUSIFT_AMD_RGBD_H
 #define CUSIFT_AMD_RGBD_H
 
@@ -85,6 +86,86 @@ inline void RegisterRGBD(SiftData &data1, SiftData &data2, const unsigned short 
     for (int k = 0; k < matches; k++) pairs->push_back(std::make_pair(h_pairs[2 * (size_t)k], h_pairs[2 * (size_t)k + 1]));
   }
   if (inliers) inliers->assign(h_flags.begin(), h_flags.begin() + matches);
+}
+
+// Registration of a whole sequence in one call (cusift_register_rgbd_batch): pair k = (a, b) of `pairs` maps frame b
+// into frame a, Rt[12 k .. 12 k + 11] = [R | t] row-major with x_a ~ R x_b + t; an empty `pairs` means (i, i + 1) for
+// every consecutive frame, the walk of main.cpp: compareMatchingWithMATLAB.  The frames' device records are packed
+// into one [n][maxPts] block with device-to-device copies (maxPts = the largest numPts), the depth images (w x h
+// 16-bit samples each, dense rows) are uploaded into one block, and every pair is matched, filtered and estimated in
+// the same launches, with one synchronisation.  Pair k draws from seed + k (seed 0: time(0)), so with the same seed
+// pair 0 has the bits RegisterRGBD gives for it.  A frame may be in any number of pairs.  The frames themselves are not
+// written: coords3D and the match results live in the packed block and in the outputs.  selected / inliers (optional)
+// receive, per pair, what RegisterRGBD's pairs / inliers receive.
+inline void RegisterRGBDSequence(std::vector<SiftData *> &frames, const std::vector<const unsigned short *> &h_depths,
+                                 int w, int h, const cusift_camera &camera, std::vector<std::pair<int, int> > pairs,
+                                 std::vector<float> &Rt, std::vector<int> *numInliers = NULL,
+                                 std::vector<int> *numMatches = NULL, int numLoops = 1024, float thresh = 0.05f,
+                                 RigidTransformType type = RigidTransformType3D,
+                                 MatchSiftDistance distance = MatchSiftDistanceL2, float scoreThreshold = 999.0f,
+                                 float ambiguityThreshold = 1.0f, uint64_t seed = 0,
+                                 std::vector<std::vector<std::pair<int, int> > > *selected = NULL,
+                                 std::vector<std::vector<char> > *inliers = NULL) {
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  const int n = (int)frames.size();
+  if (pairs.empty())
+    for (int i = 0; i + 1 < n; i++) pairs.push_back(std::make_pair(i, i + 1));
+  const int n_pairs = (int)pairs.size();
+  int max_pts = 1;
+  std::vector<unsigned int> counts((size_t)(n > 0 ? n : 1), 0u);
+  for (int i = 0; i < n; i++) {
+    counts[i] = frames[i]->d_data != nullptr && frames[i]->numPts > 0 ? (unsigned int)frames[i]->numPts : 0u;
+    if ((int)counts[i] > max_pts) max_pts = (int)counts[i];
+  }
+  struct block {
+    void *ptr = nullptr;
+    explicit block(size_t bytes) { safeCall(cusift_malloc(&ptr, bytes > 0 ? bytes : 1)); }
+    ~block() { cusift_free(ptr); }
+    block(const block &) = delete;
+    block &operator=(const block &) = delete;
+  };
+  const size_t image = (size_t)w * (size_t)h;
+  block points(sizeof(SiftPoint) * (size_t)n * (size_t)max_pts), counters(sizeof(unsigned int) * counts.size());
+  block depth(sizeof(unsigned short) * image * (size_t)n);
+  safeCall(cusift_memcpy_h2d(ctx, counters.ptr, counts.data(), sizeof(unsigned int) * counts.size()));
+  for (int i = 0; i < n; i++) {
+    if (counts[i] > 0)
+      safeCall(cusift_memcpy_d2d(ctx, static_cast<SiftPoint *>(points.ptr) + (size_t)i * max_pts, frames[i]->d_data,
+                                 sizeof(SiftPoint) * (size_t)counts[i]));
+    safeCall(cusift_memcpy_h2d(ctx, static_cast<unsigned short *>(depth.ptr) + (size_t)i * image, h_depths[i],
+                               sizeof(unsigned short) * image));
+  }
+  std::vector<int> h_pairs(2 * (size_t)(n_pairs > 0 ? n_pairs : 1)), matches((size_t)(n_pairs > 0 ? n_pairs : 1)),
+      found(matches.size());
+  for (int k = 0; k < n_pairs; k++) h_pairs[2 * (size_t)k] = pairs[k].first, h_pairs[2 * (size_t)k + 1] = pairs[k].second;
+  std::vector<int> h_sel(selected ? 2 * (size_t)n_pairs * max_pts : 0);
+  std::vector<char> h_flags(inliers ? (size_t)n_pairs * max_pts : 0);
+  Rt.assign(12 * (size_t)n_pairs, 0.0f);
+  std::vector<float> rt(12 * matches.size());
+  safeCall(cusift_register_rgbd_batch(ctx, static_cast<cusift_point *>(points.ptr),
+                                      static_cast<const unsigned int *>(counters.ptr), n, max_pts,
+                                      static_cast<const uint16_t *>(depth.ptr), w, h, w, image, &camera, h_pairs.data(),
+                                      n_pairs, distance == MatchSiftDistanceL2 ? 1 : 0, scoreThreshold,
+                                      ambiguityThreshold, numLoops, thresh * thresh,
+                                      type == RigidTransformType3D ? 1 : 0, seed ? seed : (uint64_t)std::time(0),
+                                      rt.data(), matches.data(), found.data(), selected ? h_sel.data() : NULL,
+                                      inliers ? h_flags.data() : NULL));
+  for (size_t i = 0; i < Rt.size(); i++) Rt[i] = rt[i];
+  if (numInliers) numInliers->assign(found.begin(), found.begin() + n_pairs);
+  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + n_pairs);
+  if (selected) {
+    selected->assign((size_t)n_pairs, std::vector<std::pair<int, int> >());
+    for (int k = 0; k < n_pairs; k++)
+      for (int m = 0; m < matches[k]; m++) {
+        const int *row = h_sel.data() + 2 * ((size_t)k * max_pts + (size_t)m);
+        (*selected)[k].push_back(std::make_pair(row[0], row[1]));
+      }
+  }
+  if (inliers) {
+    inliers->assign((size_t)n_pairs, std::vector<char>());
+    for (int k = 0; k < n_pairs; k++)
+      (*inliers)[k].assign(h_flags.begin() + (size_t)k * max_pts, h_flags.begin() + (size_t)k * max_pts + matches[k]);
+  }
 }
 
 #endif  // CUSIFT_AMD_RGBD_H
