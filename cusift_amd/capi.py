@@ -74,6 +74,7 @@ class Params(C.Structure):
         ("fused_detect", C.c_int),
         ("root_sift", C.c_int),
         ("concurrent_batches", C.c_int),
+        ("upsample", C.c_int),
     ]
 
 
@@ -183,6 +184,7 @@ SIGNATURES = {
     "cusift_u8_to_f32": (_i, [_vp, _vp, _i, _sz, _vp, _i, _i, _i, _sz, _i]),
     "cusift_gaussian3x3": (_i, [_vp, _vp, _i, _sz, _vp, _i, _i, _i, _sz, _i, _f]),
     "cusift_scale_down": (_i, [_vp, _vp, _i, _sz, _vp, _i, _i, _i, _sz, _i, _f]),
+    "cusift_scale_up": (_i, [_vp, _vp, _i, _sz, _vp, _i, _i, _i, _sz, _i]),
     "cusift_scale_down_levels": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _vp, _vp, _i, _i, _f]),
     "cusift_extract_bands": (_i, [_vp, _vp, _i, _f, _f, _vp, _i, _vp, _i, _i, _vp]),
     "cusift_laplace_multi": (_i, [_vp, _vp, _i, _i, _i, _sz, _f, _vp, _sz, _i]),
@@ -343,6 +345,23 @@ def check_rigid_args(coord, indices=None, loops=None, thresh2=0.0025, kind="3d")
     return coord, np.ascontiguousarray(indices), indices.shape[0], RIGID_KINDS[kind]
 
 
+def check_scale_up_args(d_dst, dst_pitch, d_src, w, h, src_pitch, n_images=1, dst_stride=None, src_stride=None):
+    """What Context.scale_up checks before it calls the library (needs no device): returns (dst_stride, src_stride) in
+    floats.  ValueError for anything cusift_scale_up would refuse."""
+    if not d_dst or not d_src:
+        raise ValueError("scale_up: missing data")
+    w, h, n_images = int(w), int(h), int(n_images)
+    if n_images < 1 or n_images > 65535 or w < 1 or h < 1 or int(src_pitch) < w or w > (1 << 27) or h > 4 * 65535:
+        raise ValueError("scale_up: bad geometry n=%d w=%d h=%d pitch=%d" % (n_images, w, h, src_pitch))
+    if int(dst_pitch) < 2 * w:
+        raise ValueError("scale_up: dst_pitch %d < 2 w = %d" % (dst_pitch, 2 * w))
+    dst_stride = 2 * h * int(dst_pitch) if dst_stride is None else int(dst_stride)
+    src_stride = h * int(src_pitch) if src_stride is None else int(src_stride)
+    if n_images > 1 and (src_stride < h * int(src_pitch) or dst_stride < 2 * h * int(dst_pitch)):
+        raise ValueError("scale_up: image stride too small")
+    return dst_stride, src_stride
+
+
 def pair_list(pairs):
     """A pair list as the C ABI takes it: contiguous int32 [P, 2] of (frame 1, frame 2)."""
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -494,6 +513,13 @@ class Context:
         src_stride = h * src_pitch if src_stride is None else src_stride
         check(lib().cusift_scale_down(self.handle, d_dst, dst_pitch, dst_stride, d_src, w, h, src_pitch, src_stride,
                                       n_images, variance))
+
+    def scale_up(self, d_dst, dst_pitch, d_src, w, h, src_pitch, n_images=1, dst_stride=None, src_stride=None):
+        """cusift_scale_up: the 2x enlargement octave -1 is searched in (dst is 2w x 2h, dst_pitch >= 2w)."""
+        dst_stride, src_stride = check_scale_up_args(d_dst, dst_pitch, d_src, w, h, src_pitch, n_images, dst_stride,
+                                                     src_stride)
+        check(lib().cusift_scale_up(self.handle, d_dst, dst_pitch, dst_stride, d_src, w, h, src_pitch, src_stride,
+                                    n_images))
 
     def scale_down_levels(self, d_src, w, h, src_pitch, d_levels, pitches, n_images=1, src_stride=None, strides=None,
                           variance=0.5):

@@ -218,6 +218,7 @@ extern "C" void cusift_default_params(cusift_params *p) {
   p->fused_detect = 1;
   p->root_sift = 0;
   p->concurrent_batches = 1;
+  p->upsample = 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -97,8 +97,7 @@ static bool wants_self_join(int n_images, int w, int h) {
 // ------------------------------------------------------------------------------------------------
 // The launch sequence of a plan whose geometry and arena layout are made.  `may_fork` false: the sequence of a call that
 // found no side stream -- everything that follows from `forked` is decided again, on the same layout.
-static void resolve_launches(Plan &pl, const cusift_ctx *ctx, const cusift_params *prm, const float *d_imgs,
-                             size_t image_stride, bool may_fork) {
+static void resolve_launches(Plan &pl, const cusift_ctx *ctx, const cusift_params *prm, bool may_fork) {
   const int n_images = pl.n_images, w = pl.w[0], h = pl.h[0];
   const bool generic = ctx->knobs.force_generic;
   // With fused_detect the keypoint stages run once, after the last octave's detection, over the flattened list
@@ -115,7 +114,7 @@ static void resolve_launches(Plan &pl, const cusift_ctx *ctx, const cusift_param
     if (!(prm->lowest_scale < pl.sub[o] * 2.0f)) continue;  // cuSIFT.cu:194
     const size_t plane = (size_t)pl.h[o] * pl.p[o];
     const bool fused = prm->fused_detect && !generic &&
-                       detect_fused_ok(o == 0 ? d_imgs : nullptr, pl.w[o], pl.h[o], pl.p[o], o == 0 ? image_stride : plane);
+                       detect_fused_ok(o == 0 ? pl.img0 : nullptr, pl.w[o], pl.h[o], pl.p[o], o == 0 ? pl.stride0 : plane);
     pl.detect[o] = fused ? kFused : kTwoStage;
     if (!fused) pl.dog_bytes = std::max(pl.dog_bytes, (size_t)n_images * kNumDog * plane * sizeof(float));
     all_fused = all_fused && fused;
@@ -165,6 +164,11 @@ static void resolve_launches(Plan &pl, const cusift_ctx *ctx, const cusift_param
 
 // One extraction, decided (Plan, sift_host.h).  Nothing here touches the device: `d_imgs` is looked at for its alignment only
 // (NULL: not known yet, as aligned as the arena).
+// Octave -1 (cusift_params.upsample): octave 0 OF THE PLAN is the 2x enlarged image -- 2w x 2h at a pitch of whole 128
+// floats, at the head of the arena, written by cusift_scale_up before anything else runs -- with half the caller's
+// subsampling and twice its init_blur (the enlargement stretches the blur the input already has).  Everything below, the
+// launch policies included, sees that image as it would see a caller's: the same plan, launch for launch, as for an
+// enlarged image handed in with subsampling * 0.5 and init_blur * 2.
 static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *prm, int n_images, int w, int h, int pitch,
                         const float *d_imgs, size_t image_stride) {
   if (!prm) return fail(CUSIFT_ERR_INVALID, "params is NULL");
@@ -173,12 +177,23 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
   if (n_images > 65535) return fail(CUSIFT_ERR_INVALID, "at most 65535 images per batch (grid.z), got %d", n_images);
   if (prm->max_pts < 1) return fail(CUSIFT_ERR_INVALID, "max_pts must be >= 1");
   int n = std::max(1, std::min(prm->num_octaves, kMaxOctaves));
+  pl.upsample = prm->upsample != 0;
+  if (pl.upsample) {
+    if (w > (1 << 27) || h > 4 * 65535) return fail(CUSIFT_ERR_INVALID, "upsample: %dx%d is too large to enlarge", w, h);
+    w *= 2;
+    h *= 2;
+    pitch = ialign_up(w, 128);
+    d_imgs = nullptr;  // in the arena
+    image_stride = (size_t)h * pitch;
+  }
+  pl.img0 = d_imgs;
+  pl.stride0 = image_stride;
   pl.n_images = n_images;
   pl.w[0] = w;
   pl.h[0] = h;
   pl.p[0] = pitch;
-  pl.blur[0] = prm->init_blur;
-  pl.sub[0] = prm->subsampling;
+  pl.blur[0] = pl.upsample ? 2.0 * prm->init_blur : prm->init_blur;
+  pl.sub[0] = pl.upsample ? prm->subsampling * 0.5f : prm->subsampling;
   pl.n_oct = 1;
   for (int o = 1; o < n; ++o) {
     int ww = pl.w[o - 1] / 2, hh = pl.h[o - 1] / 2;  // integer division, cuSIFT.cu:182
@@ -192,8 +207,8 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
     pl.sub[o] = pl.sub[o - 1] * 2.0f;
     pl.n_oct = o + 1;
   }
-  size_t off = 0;
   pl.base_off[0] = 0;
+  size_t off = pl.upsample ? align_up_sz((size_t)n_images * image_stride * sizeof(float), 256) : 0;
   for (int o = 1; o < pl.n_oct; ++o) {
     pl.base_off[o] = off;
     off = align_up_sz(off + (size_t)n_images * pl.h[o] * pl.p[o] * sizeof(float), 256);
@@ -211,7 +226,7 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
     off = align_up_sz(off + per_octave * pl.staged_octaves, 256);
   }
   pl.total = off;
-  resolve_launches(pl, ctx, prm, d_imgs, image_stride, true);
+  resolve_launches(pl, ctx, prm, true);
   return CUSIFT_OK;
 }
 
@@ -245,14 +260,17 @@ extern "C" int cusift_extract_batch(cusift_ctx *ctx, const float *d_imgs, int n_
   TRY(resolve_plan(pl, ctx, prm, n_images, w, h, pitch, d_imgs, image_stride));
   TRY(prepare(ctx, pl));
   // no stream runs beside this one: one stream (ensure_side_stream has set side_failed: later calls no longer ask)
-  if (pl.forked && ensure_side_stream(ctx) != CUSIFT_OK) resolve_launches(pl, ctx, prm, d_imgs, image_stride, false);
+  if (pl.forked && ensure_side_stream(ctx) != CUSIFT_OK) resolve_launches(pl, ctx, prm, false);
 
   StageTimer total(ctx, CUSIFT_STAGE_TOTAL);
 
   const float *base[kMaxOctaves];
   size_t stride[kMaxOctaves];
-  base[0] = d_imgs;
-  stride[0] = image_stride;
+  base[0] = pl.upsample ? (const float *)(ctx->arena + pl.base_off[0]) : d_imgs;
+  stride[0] = pl.stride0;
+  // octave -1: the enlargement first, on the context's stream (a forked octave 0 waits for it through ev_fork)
+  if (pl.upsample)
+    TRY(cusift_scale_up(ctx, const_cast<float *>(base[0]), pl.p[0], stride[0], d_imgs, w, h, pitch, image_stride, n_images));
   for (int o = 1; o < pl.n_oct; ++o) {
     base[o] = (const float *)(ctx->arena + pl.base_off[o]);
     stride[o] = (size_t)pl.h[o] * pl.p[o];

@@ -29,6 +29,8 @@ namespace cusift {
 __global__ void scale_down_kernel(float *, int, long, const float *, int, int, int, long, int, ScaleDownTaps);
 __global__ void scale_down_fast_kernel(float *, int, long, const float *, int, int, int, long, int, ScaleDownTaps,
                                        RowWindow, int, int, int);
+__global__ void scale_up_kernel(float *, int, long, const float *, int, int, int, long, int);
+__global__ void scale_up_fast_kernel(float *, int, long, const float *, int, int, int, long, int);
 __global__ void laplace_multi_kernel(const float *, float *, int, int, int, long, long, int, int, LaplaceTaps);
 template <int kStoreAux>
 __global__ void laplace_multi_fast_kernel(const float *, float *, int, int, int, long, long, int, LaplaceTapsPk);
@@ -242,11 +244,15 @@ enum SegClear : unsigned char { kNoLists, kByPyramid, kByMemset };
 // alignment of the caller's images (resolve_plan, sift_driver.hip); cusift_extract_batch enqueues what it says.
 struct Plan {
   int n_images = 0, n_oct = 0;
+  // octave 0: the caller's images, or (cusift_params.upsample) their 2x enlargement in the arena at base_off[0]
+  bool upsample = false;
+  const float *img0 = nullptr;  // looked at for its alignment only (NULL: as aligned as the arena)
+  size_t stride0 = 0;           // floats between the images of octave 0
   int w[kMaxOctaves], h[kMaxOctaves], p[kMaxOctaves];
   double blur[kMaxOctaves];
   float sub[kMaxOctaves];
   // arena offsets in bytes
-  size_t base_off[kMaxOctaves];  // octave >= 1 base images (n * h*p floats each); [0] unused
+  size_t base_off[kMaxOctaves];  // octave >= 1 base images (n * h*p floats each); [0]: the enlarged images
   size_t first_off = 0, total = 0;
   // staging lists of keypoint heads ([octave][image][max_pts] x kStagedRecBytes), see cusift_extract_batch:
   // staged_octaves == 0: none; 1: octave 0's (searched on the side stream); n_oct: every octave's

@@ -234,6 +234,38 @@ extern "C" int cusift_scale_down(cusift_ctx *ctx, float *d_dst, int dst_pitch, s
                          RowWindow{0, h}, 0, 0, h / 2, false);
 }
 
+// The 2x enlargement in front of octave -1 (scale_up_fast_kernel, sift_stencils.hip).  Everything is checked before
+// anything is enqueued.
+extern "C" int cusift_scale_up(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_stride, const float *d_src, int w,
+                               int h, int src_pitch, size_t src_stride, int n_images) {
+  TRY(enter(ctx));
+  if (!d_dst || !d_src) return fail(CUSIFT_ERR_INVALID, "ScaleUp: missing data");
+  if (n_images < 1 || n_images > 65535 || w < 1 || h < 1 || src_pitch < w || w > (1 << 27) || h > 4 * 65535)  // (rows per wave >= 4, grid.y <= 65535)
+    return fail(CUSIFT_ERR_INVALID, "ScaleUp: bad geometry n=%d w=%d h=%d pitch=%d", n_images, w, h, src_pitch);
+  if (dst_pitch < 2 * w) return fail(CUSIFT_ERR_INVALID, "ScaleUp: dst_pitch %d < 2 w = %d", dst_pitch, 2 * w);
+  if (n_images > 1 && (src_stride < (size_t)h * src_pitch || dst_stride < (size_t)2 * h * dst_pitch))
+    return fail(CUSIFT_ERR_INVALID, "ScaleUp: image stride too small");
+  const bool fast = w >= 2 && (src_pitch % 2 == 0) && (((uintptr_t)d_src % 8) == 0) && (src_stride % 2 == 0) &&
+                    (dst_pitch % 4 == 0) && (((uintptr_t)d_dst % 16) == 0) && (dst_stride % 4 == 0) &&
+                    ((size_t)h * src_pitch * sizeof(float) < (1ull << 31)) && !ctx->knobs.force_generic;
+  StageTimer t(ctx, CUSIFT_STAGE_SCALEDOWN);  // (the pyramid's stage: its first image)
+  if (fast) {
+    const int strips = idiv_up(w, 128);  // kUpStrip
+    // a chunk re-reads one source row (the row below its last): 16 rows keep that at 1/80 of the traffic
+    const int rows = pick_rows(h, strips, n_images, 4, 16);
+    dim3 grid(idiv_up(strips, kWavesPerBlock), idiv_up(h, rows), n_images);
+    hipLaunchKernelGGL(scale_up_fast_kernel, grid, dim3(256), 0, ctx->stream, d_dst, dst_pitch, (long)dst_stride, d_src,
+                       w, h, src_pitch, (long)src_stride, rows);
+  } else {
+    const int strips = idiv_up(w, 64);
+    const int rows = pick_rows(h, strips, n_images, 4, 16);
+    dim3 grid(strips, idiv_up(idiv_up(h, rows), kWavesPerBlock), n_images);
+    hipLaunchKernelGGL(scale_up_kernel, grid, dim3(256), 0, ctx->stream, d_dst, dst_pitch, (long)dst_stride, d_src, w, h,
+                       src_pitch, (long)src_stride, rows);
+  }
+  return check_launch("scale_up");
+}
+
 extern "C" int cusift_scale_down_band(cusift_ctx *ctx, float *d_dst, int dst_pitch, int dst_row0, int r_begin,
                                       int r_end, const float *d_src, int w, int h_src, int src_pitch, int src_row0,
                                       int h_src_global, float variance) {

@@ -374,6 +374,112 @@ __global__ void __launch_bounds__(256) scale_down_fast_kernel(float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// ScaleUp: the 2x enlarged image that octave -1 is searched in (Lowe's first octave; the reference has no counterpart).
+// With x1 = min(x+1, w-1), y1 = min(y+1, h-1), all in fp32 with exactly this association:
+//   d(2x,  2y  ) = s(x,y)                          d(2x+1,2y  ) = 0.5*(s(x,y)+s(x1,y))
+//   d(2x,  2y+1) = 0.5*(s(x,y)+s(x,y1))            d(2x+1,2y+1) = 0.25*((s(x,y)+s(x1,y)) + (s(x,y1)+s(x1,y1)))
+// Output pixel 2x sits on source pixel x, so coordinates found in the enlarged image times 0.5 are base-image pixels.
+// HBM-bound: 4 bytes read and 16 written per source pixel.  Generic form: one lane per source column, any pitch.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) scale_up_kernel(float *__restrict__ dst, int dst_pitch, long dst_stride,
+                                                      const float *__restrict__ src, int w, int h, int src_pitch,
+                                                      long src_stride, int rows_per_wave) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave id: uniform, say so
+  const int x = blockIdx.x * 64 + lane;
+  const int y0 = (blockIdx.y * kWavesPerBlock + wv) * rows_per_wave;
+  if (y0 >= h) return;
+  const int y1 = min(y0 + rows_per_wave, h);
+  src += (long)blockIdx.z * src_stride;
+  dst += (long)blockIdx.z * dst_stride;
+  const int xa = min(x, w - 1), xb = min(x + 1, w - 1);
+  const float *s = src + (long)y0 * src_pitch;
+  float a = s[xa], hc = a + s[xb];  // s(x,y) and the horizontal sum s(x,y) + s(x1,y) of the current row
+  for (int y = y0; y < y1; ++y) {
+    const float *sn = src + (long)min(y + 1, h - 1) * src_pitch;
+    const float an = sn[xa], hn = an + sn[xb];
+    if (x < w) {
+      float *d = dst + (long)(2 * y) * dst_pitch + 2 * x;
+      d[0] = a;
+      d[1] = 0.5f * hc;
+      d[dst_pitch] = 0.5f * (a + an);
+      d[dst_pitch + 1] = 0.25f * (hc + hn);
+    }
+    a = an;
+    hc = hn;
+  }
+}
+
+// ScaleUp, fast path (8-byte aligned source rows, any w >= 2, 16-byte aligned destination rows).  Same arithmetic as
+// scale_up_kernel.  A lane loads source columns 2l, 2l+1 as one float2 and stores output columns 4l..4l+3 of BOTH output
+// rows as one float4 each: every store instruction of a wave writes 1 KiB of one row, contiguous and 1 KiB aligned --
+// the stores are 4/5 of the traffic.  Column 2l+2 comes from the next lane by DPP; lane 63 has no next lane and reads
+// it again (one dword: the other 63 lanes' offsets are out of range, which costs no memory access).  The row below is
+// the next iteration's row: one load per source row, plus one halo row per chunk.
+constexpr int kUpStrip = 64 * 2;  // source columns per wave
+
+__global__ void __launch_bounds__(256) scale_up_fast_kernel(float *__restrict__ dst, int dst_pitch, long dst_stride,
+                                                           const float *__restrict__ src, int w, int h, int src_pitch,
+                                                           long src_stride, int rows_per_wave) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave id: uniform, say so
+  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+  xcd_remap(bx, by, bz);
+  // the 4 waves of a block take 4 horizontally adjacent strips: 4 KiB of one output row per store
+  const int strip = bx * kWavesPerBlock + wv;
+  const int y0 = by * rows_per_wave;
+  if (strip * kUpStrip >= w || y0 >= h) return;  // wave-uniform
+  const int y1 = min(y0 + rows_per_wave, h);
+  src += (long)bz * src_stride;
+  dst += (long)bz * dst_stride;
+
+  const int cs = strip * kUpStrip + lane * 2;  // first source column of this lane's float2
+  const EdgeFix2 edge(cs, w);  // source columns beyond the image replicate column w-1: x1 = min(x+1, w-1) for free
+  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
+      (void *)src, 0, (int)((unsigned int)h * (unsigned int)src_pitch * 4u), kBufFlags);
+  const int voff_next = lane == 63 ? min(cs + 2, w - 1) * 4 : kOobOffset;
+  // output columns >= 2w are dropped by num_records = 2w*4, per component (odd w: the last lane's first two columns only)
+  const int voff_out = cs < w ? cs * 8 : kOobOffset;
+
+  struct Raw {  // a row as loaded: nothing waits for it until it is used, one iteration later
+    u2 v;
+    unsigned int next;
+  };
+  struct Row {
+    f2 v;  // s(x,y) of the lane's two columns
+    f2 h;  // s(x,y) + s(x1,y)
+  };
+  auto load_row = [&](int y) -> Raw {
+    const int so = min(y, h - 1) * src_pitch * 4;
+    return Raw{__builtin_amdgcn_raw_buffer_load_b64(rin, edge.voff, so, 0),
+               __builtin_amdgcn_raw_buffer_load_b32(rin, voff_next, so, 0)};
+  };
+  auto finish = [&](const Raw &r) -> Row {
+    const f2 v = edge(__builtin_bit_cast(f2, r.v));
+    const float shifted = from_next_lane(v.x);  // by every lane: a DPP move reads 0 from a lane that sits out
+    const float p2 = lane == 63 ? __builtin_bit_cast(float, r.next) : shifted;  // lane 63: s(min(x+2, w-1), y)
+    return Row{v, f2{v.x + v.y, v.y + p2}};
+  };
+
+  Row cur = finish(load_row(y0));
+  Raw nxt = load_row(y0 + 1);
+  for (int y = y0; y < y1; ++y) {
+    const Raw raw = nxt;
+    if (y + 2 <= y1) nxt = load_row(y + 2);  // the next iteration's row below, requested now (wave-uniform)
+    const Row below = finish(raw);
+    const f4 even = {cur.v.x, 0.5f * cur.h.x, cur.v.y, 0.5f * cur.h.y};
+    const f4 odd = {0.5f * (cur.v.x + below.v.x), 0.25f * (cur.h.x + below.h.x), 0.5f * (cur.v.y + below.v.y),
+                    0.25f * (cur.h.y + below.h.y)};
+    float *row = dst + (long)(2 * y) * dst_pitch;
+    const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc((void *)row, 0, w * 8, kBufFlags);
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)(row + dst_pitch), 0, w * 8, kBufFlags);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, even), re, voff_out, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, odd), ro, voff_out, 0, 0);
+    cur = below;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // FindPointsMulti: 26-neighbour DoG extrema for the 5 searchable scales, edge test, 3-D quadratic
 // refinement and append.  Reference: FindPointsMulti_D, cuSIFT_D.cu:402-523.
 //

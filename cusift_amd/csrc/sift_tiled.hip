@@ -184,6 +184,7 @@ extern "C" int cusift_tiled_create(cusift_tiled **out, cusift_ctx *ctx, cusift_c
   if (!ctx || !prm) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: ctx / params is NULL");
   if (rank < 0 || rank >= world) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: bad rank %d of %d", rank, world);
   if (prm->max_pts < 1) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: max_pts must be >= 1");
+  if (prm->upsample) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: upsample = 1 (octave -1) is not tiled; enlarge the strips' image first");
   if (comm) {
     int cr = -1, cw = -1;
     TRY(cusift_comm_rank(comm, &cr, &cw));

@@ -349,11 +349,16 @@ class SiftData {
   // ExtractRootSift, cuSIFT.cu:122-134, ran ConvertSiftToRootSift as a second pass).  Last field: layout of the
   // reference's members is unchanged.
   bool rootSift;
+  // new: also search Lowe's octave -1 -- Extract enlarges the image 2x on the device first (cusift_params.upsample;
+  // upstream CudaSift's scaleUp) and numOctaves counts from the enlarged octave: its keypoints come last, with
+  // subsampling 0.5 * the call's.  Meant for initBlur <= 0.5.  Trailing field, default false: source-compatible, the
+  // layout of the reference's members is unchanged.  (initSubsampling stays unread, as in the reference.)
+  bool scaleUp;
 
   // cuSIFT.cu:13-32
   explicit SiftData(int maxPts_ = 1024, bool host = false, bool dev = false)
       : numPts(0), maxPts(0), h_data(nullptr), d_data(nullptr), numOctaves(5), numScales(5), initBlur(0.0),
-        initSubsampling(1.0f), peakThresh(0.1f), edgeThresh(10.0f), lowestScale(0.0f), rootSift(false) {
+        initSubsampling(1.0f), peakThresh(0.1f), edgeThresh(10.0f), lowestScale(0.0f), rootSift(false), scaleUp(false) {
     allocate(maxPts_, host, dev);
   }
   ~SiftData() { release(); }
@@ -444,6 +449,7 @@ class SiftData {
     p.subsampling = subsampling;
     p.max_pts = maxPts;
     p.root_sift = rootSift ? 1 : 0;
+    p.upsample = scaleUp ? 1 : 0;
     return p;
   }
   void require_device(const char *who) const {
@@ -479,14 +485,16 @@ inline double ScaleDown(cuImage &res, cuImage &src, float variance) {
 // commented bodies at cuSIFT.cu:123-134,272-303).  edgeThresh has no legacy argument: 10.0 as everywhere.
 inline void InitSiftData(SiftData &data, int num, bool host, bool dev) { data.allocate(num, host, dev); }
 inline void FreeSiftData(SiftData &data) { data.release(); }
+// scaleUp (new, trailing, default false): SiftData::scaleUp for this call.
 inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double initBlur, float thresh,
-                        float lowestScale = 0.0f, float subsampling = 1.0f) {
+                        float lowestScale = 0.0f, float subsampling = 1.0f, bool scaleUp = false) {
   siftData.numOctaves = numOctaves;
   siftData.initBlur = initBlur;
   siftData.peakThresh = thresh;
   siftData.lowestScale = lowestScale;
   siftData.edgeThresh = 10.0f;
   siftData.rootSift = false;
+  siftData.scaleUp = scaleUp;
   siftData.Extract(img, subsampling);
 }
 // The reference's ExtractRootSift is commented out ("TODO: bring rootsift back", cuSIFT.cu:122-134: ExtractSift,

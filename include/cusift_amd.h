@@ -8,9 +8,9 @@
  * (SiftPoint / SiftData / cuImage / ExtractSift ...) on top of exactly these functions; Python binds
  * them with ctypes (cusift_amd/capi.py).  See INTEGRATION.md.
  *
- * Map of the C ABI (111 entry points in four headers; cusift_amd_all.h includes them all):
- *   cusift_amd.h (THIS FILE, 46): the drop-in boundary -- everything include/cuSIFT.h is built on (process / device,
- *     context, device memory helpers, cusift_extract / _extract_host / _scale_down / _rootsift / _sort_points_host,
+ * Map of the C ABI (112 entry points in four headers; cusift_amd_all.h includes them all):
+ *   cusift_amd.h (THIS FILE, 47): the drop-in boundary -- everything include/cuSIFT.h is built on (process / device,
+ *     context, device memory helpers, cusift_extract / _extract_host / _scale_down / _scale_up / _rootsift / _sort_points_host,
  *     cusift_event_* for TimerGPU), the batch driver a throughput caller needs (cusift_extract_batch, cusift_graph_*,
  *     cusift_ctx_wait / _reserve / _set_policy) and the host-to-host pipeline (cusift_pipe_*).
  *   cusift_amd_stages.h: one entry point per kernel of the reference (LaplaceMulti, FindPointsMulti, the fused
@@ -98,6 +98,13 @@ typedef struct cusift_params {
                           work (about as many chunks per launch as the chip holds waves).
                           cusift_amd.batch.PipelinedExtractor sets it to its stream count.  Same SiftData either way,
                           coarsest octave first. */
+  int upsample;        /* 0 (default): the octaves are searched from the input image down, exactly as the reference.
+                          1: Lowe's octave -1 -- the drivers first enlarge every image 2x (cusift_scale_up, into the
+                          context's arena) and run the octave sequence on the enlarged image with subsampling * 0.5 and
+                          init_blur * 2, so its keypoints come out with subsampling 0.5 * `subsampling`, in input-image
+                          pixels, as the LAST block of SiftData (coarsest octave first).  num_octaves counts from the
+                          enlarged octave: 6 means octaves -1 .. 4.  Meant for init_blur <= 0.5 (with 1.0 the enlarged
+                          image's blur is 2.0 and its first levels are identities).  cusift_tiled_* refuses it. */
 } cusift_params;
 
 typedef struct cusift_ctx cusift_ctx; /* opaque: device, stream, scratch arena, timers */
@@ -200,6 +207,14 @@ int cusift_free_host(void *h_ptr);
  * dst is (w/2) x (h/2); writes are bounds-checked (the reference's are not). */
 int cusift_scale_down(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_stride, const float *d_src, int w,
                       int h, int src_pitch, size_t src_stride, int n_images, float variance);
+/* New (the reference has no counterpart; upstream CudaSift calls it ScaleUp): the 2x enlargement that octave -1 is
+ * searched in.  dst is 2w x 2h, dst_pitch >= 2w.  With x1 = min(x+1, w-1), y1 = min(y+1, h-1), in fp32, associated as written:
+ *   d(2x,2y) = s(x,y)                      d(2x+1,2y)   = 0.5*(s(x,y)+s(x1,y))
+ *   d(2x,2y+1) = 0.5*(s(x,y)+s(x,y1))      d(2x+1,2y+1) = 0.25*((s(x,y)+s(x1,y)) + (s(x,y1)+s(x1,y1)))
+ * Output pixel 2x sits on source pixel x.  Asynchronous on the context's stream; CUSIFT_ERR_INVALID (nothing enqueued)
+ * for bad geometry or dst_pitch < 2w.  cusift_params.upsample makes the drivers call it themselves. */
+int cusift_scale_up(cusift_ctx *ctx, float *d_dst, int dst_pitch, size_t dst_stride, const float *d_src, int w, int h,
+                    int src_pitch, size_t src_stride, int n_images);
 /* SiftData::ConvertSiftToRootSift, cuSIFT.cu:383-395 + cuSIFT_D.cu:299-317. */
 int cusift_rootsift(cusift_ctx *ctx, cusift_point *d_points, int num_pts);
 
