@@ -105,6 +105,15 @@ class BatchExtractor:
                                             d_depth.data_ptr(), self.w, self.h, camera, pairs,
                                             pitch=d_depth.shape[2], image_stride=self.h * d_depth.shape[2], **ransac)
 
+    def register_planar(self, i, j, slot=0, **opts):
+        """Planar registration of frames i and j of the last extract() into `slot`: cusift_register_planar over this
+        extractor's device records (frame i's match fields and match_error are written).  The two counts are read with
+        one call.  **opts goes to capi.Context.register_planar (distance, rule, lo, hi, loops, thresh, refine_loops,
+        refine_thresh, seed, want_all).  Returns its PlanarResult: homography maps frame i onto frame j.  Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
+        return self.ctx.register_planar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
+
     def valid_counts(self):
         return torch.clamp(self.counts, max=self.max_pts)
 

@@ -3,6 +3,7 @@
 There is no CPU fallback: if the HIP extension is missing this module raises at import of the
 library handle (`lib()`), and every call that needs a GPU fails with the library's error text.
 """
+import collections
 import ctypes as C
 import os
 
@@ -202,6 +203,10 @@ SIGNATURES = {
     "cusift_match": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "cusift_memcpy2d_d2h": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
     "cusift_find_homography": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, C.POINTER(_i), _vp, _vp]),
+    "cusift_estimate_homography": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp, C.POINTER(_i),
+                                        C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "cusift_register_planar": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp,
+                                    C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
     "cusift_estimate_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp,
                                    _vp, _vp]),
     "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
@@ -306,6 +311,11 @@ POLICY_SIDE_STREAM, POLICY_OCTAVE_LISTS, POLICY_GENERIC_KERNELS, POLICY_LAUNCH_P
     POLICY_TILED_PER_OCTAVE, POLICY_PYRAMID_IN_DETECT = range(7)
 
 
+PLANAR_RULES = {"dot": 0, "l2": 1}  # the candidate rule of cusift_estimate_homography, by the distance it is meant for
+# what cusift_estimate_homography / cusift_register_planar return: homography (refined, [9]), ransac (the winner, [9]),
+# the counts, the winner's flags bool [num_pts] and, with want_all, drawn [4, L], all_homographies [8, L], all_counts [L]
+PlanarResult = collections.namedtuple("PlanarResult", "homography ransac num_candidates num_matches num_fit best_loop "
+                                      "inliers drawn all_homographies all_counts")
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
 
 
@@ -633,6 +643,44 @@ class Context:
                                            hom.ctypes.data, C.byref(n), all_h.ctypes.data if want_all else None,
                                            all_c.ctypes.data if want_all else None))
         return (hom, n.value, all_h, all_c) if want_all else (hom, n.value)
+
+    def _planar(self, call, num_pts, loops, want_all):
+        hom, ransac = np.zeros(9, dtype=np.float32), np.zeros(9, dtype=np.float32)
+        n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        flags = np.zeros(max(num_pts, 1), dtype=np.int8)
+        drawn = np.zeros((4, loops), dtype=np.int32) if want_all else None
+        all_h = np.zeros((8, loops), dtype=np.float32) if want_all else None
+        all_c = np.zeros(loops, dtype=np.int32) if want_all else None
+        check(call(hom.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
+                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_h.ctypes.data if want_all else None,
+                   all_c.ctypes.data if want_all else None))
+        return PlanarResult(hom, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
+                            flags[:max(num_pts, 0)].astype(bool), drawn, all_h, all_c)
+
+    def estimate_homography(self, d_sift, num_pts, num_pts2=-1, rule=0, lo=0.0, hi=0.8, loops=10000, thresh=5.0,
+                            refine_loops=5, refine_thresh=3.0, seed=0, want_all=False):
+        """cusift_estimate_homography: FindHomography + ImproveHomography on device records that carry match fields --
+        candidates by `rule` (0: score > lo && ambiguity < hi; 1: score < lo^2 && ambiguity < hi^2), samples drawn on the
+        device from `seed`, the first hypothesis with the most inliers, `refine_loops` rounds of the fp64 refit;
+        match_error of every device record is written.  One synchronisation.  Returns a PlanarResult; with want_all its
+        drawn [4, L] / all_homographies [8, L] / all_counts [L] are filled."""
+        loops = int(loops)
+        return self._planar(lambda *out: lib().cusift_estimate_homography(
+            self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi, loops, thresh, refine_loops,
+            refine_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, *out), num_pts, max(loops, 0), want_all)
+
+    def register_planar(self, d_sift1, n1, d_sift2, n2, distance=1, rule=None, lo=None, hi=None, loops=10000,
+                        thresh=5.0, refine_loops=5, refine_thresh=3.0, seed=0, want_all=False):
+        """cusift_register_planar: match(distance), then estimate_homography over d_sift1 with num_pts2 = n2 -- one
+        synchronisation, the staged route's bits.  rule defaults to the one that fits the distance (1 = L2: rule 1 with
+        lo = 999, hi = 0.8 as score / ambiguity thresholds; 0 = dot product: rule 0 with lo = 0, hi = 0.8)."""
+        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
+        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
+        hi = 0.8 if hi is None else hi
+        loops = int(loops)
+        return self._planar(lambda *out: lib().cusift_register_planar(
+            self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, *out), n1, max(loops, 0), want_all)
 
     def estimate_rigid(self, coord, indices=None, loops=None, thresh2=0.0025, kind="3d", seed=0, want_all=False):
         """cusift_estimate_rigid: RANSAC rigid transform x ~ R y + t from coord float32 [N, 6] (reference xyz, moving

@@ -65,7 +65,14 @@ __global__ void match_batch_merge_kernel(const unsigned int *, int, const int *,
 __global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                        const cusift_match_row *, float, float, int, int *, float *, int *);
 __global__ void homography_gather_kernel(const cusift_point *, int, float *);
-__global__ void homography_solve_kernel(const float *, int, const int *, int, float *);
+__global__ void homography_solve_kernel(const float *, int, int *, int, float *, int, unsigned long long, const int *,
+                                        const int *, int *, PlanarBatch);
+__global__ void planar_mark_kernel(const cusift_point *, int, int, int, float, float, float *, unsigned char *, int *,
+                                   PlanarBatch);
+__global__ void planar_compact_kernel(const unsigned char *, int, const int *, int *, int *, PlanarBatch);
+__global__ void planar_score_kernel(const float *, int, int, const float *, int, float, int *, const int *, PlanarBatch);
+__global__ void planar_select_kernel(cusift_point *, int, const float *, const unsigned char *, const float *, const int *,
+                                     int, float, int, float, float *, char *, PlanarBatch);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
 template <bool k3D>
 __global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *,
@@ -154,7 +161,7 @@ struct cusift_ctx {
   // per-split partial results of the matcher (cusift_match)
   MatchPartial *match_scratch = nullptr;
   size_t match_scratch_bytes = 0;
-  // coordinates / samples / hypotheses / counts of cusift_find_homography
+  // coordinates / samples / hypotheses / counts of cusift_find_homography; the state of cusift_estimate_homography
   char *homo_scratch = nullptr;
   size_t homo_scratch_bytes = 0;
   // result head / flags / hypotheses / counts / samples / coordinates of cusift_estimate_rigid

@@ -1,0 +1,376 @@
+// sift_planar.hip -- planar registration on the device: from matched SiftData to a refined homography without a host
+// decision.  Reference: FindHomography (extras/homography.cu:182-269) followed by ImproveHomography (:271-336), the
+// chain its demo runs (main.cpp:331-335).  cusift_estimate_homography / cusift_register_planar enqueue, on the context's
+// stream, with no host round trip in between:
+//
+//   planar_mark_kernel      per record: candidate? member of the refit set?  SoA coordinates [x1 | y1 | x2 | y2] of ALL
+//                           records (TestHomographies counts over all of them); candidates per 256-record workgroup
+//   planar_compact_kernel   the candidates' record indices in ASCENDING order and their number.  No atomics: the
+//                           workgroups before this one are summed in a fixed tree, the own keeps are ranked with ballot +
+//                           mbcnt inside a wave and a 4-entry scan across the waves (as match_select_* of sift_rgbd.hip)
+//   homography_solve_kernel (sift_homography.hip) drawing its own four samples per hypothesis from the candidate list
+//   planar_score_kernel     TestHomographies: one hypothesis per lane, its 8 coefficients (as doubles) and its count in
+//                           registers; 64-point tiles in LDS as SoA rows of doubles, every lane reads the same point (a
+//                           broadcast); grid (loops / 64, point splits); the splits' partial counts meet in one integer
+//                           atomic add per lane (order-free)
+//   planar_select_kernel    one workgroup: the winner (64-bit max over count << 32 | ~loop: the most inliers and, among
+//                           equals, the FIRST, :249-254), its inlier flags, ImproveHomography's rounds of weighted normal
+//                           equations, then match_error of every record and the number of records with err < limit
+// Every kernel has a pair index, blockIdx.z: pair p's records lie PlanarBatch::records records further and its scratch
+// block PlanarBatch::scratch bytes further, and it draws from seed + p.  One pair is launched today (both 0).
+//
+// CANDIDATES.  rule 0: score > lo && ambiguity < hi (FindHomography, :218-219; dot-product distance).  rule 1: score <
+// lo^2 && ambiguity < hi^2 (cusift_select_matches type 0; L2 distance; the squares arrive computed in fp32).  Both: finite
+// coords2D / match_xpos / match_ypos and, when num_pts2 >= 0, 0 <= match < num_pts2.
+//
+// SAMPLING extends the recipe of sift_rigid.hip to four slots (same mix):
+//     draw k of loop l = cand[(mix(seed ^ mix((l << 32) | k)) >> 32) mod n_cand]
+//     p1..p4 = draws 0..3; then, with k counting on from 4: while p2 == p1 redraw p2; while p3 is p1 or p2 redraw p3;
+//     while p4 is p1, p2 or p3 redraw p4 (:222-235).  A slot redrawn 64 times takes the lowest candidate not taken yet.
+// Integer arithmetic only; tests/test_planar.py restates it and demands identical indices.
+//
+// PRECISION.  Hypotheses and counts are fp32 with the arithmetic of sift_homography.hip (bit for bit the oracle's; the
+// inlier test multiplies with round-toward-zero like __fmul_rz: the double product of two floats is exact, so keeping
+// the operands as doubles changes no bit).  The refit's 8x8 sums and its Cholesky solve are fp64 like the reference's
+// host code: the normal matrix of the UNNORMALISED system has a condition number of 1.4e13 .. 2.2e13 on the planted sets
+// of tests/test_homography.py (measured with numpy), so fp32 sums are useless; in fp64 two different summation orders
+// move the mapped corners of a 1280 x 960 frame by about 1e-10 px.  The partial sums are reduced in a fixed order (lane
+// tree inside a wave, then waves 0..3), so every run gives the same bits.  Only the structurally non-zero entries are
+// summed: Yx = [x, y, 1, 0, 0, 0, -x mx, -y mx] and Yy = [0, 0, 0, x, y, 1, -x my, -y my] have three zeros each, the
+// [3..5][3..5] block of M equals the [0..2][0..2] block and the [0..2][3..5] block is 0 -- 21 sums of M, 8 of X.
+// A normal matrix that is not positive definite (NaN included) keeps the previous A, as cholesky_solve8 of
+// include/homography.h does.
+// Kernels use no scratch memory and write with vector stores only.
+#include "sift_device.h"
+
+namespace cusift {
+
+constexpr int kPlanarThreads = 256;  // mark / compact / select
+constexpr int kPlanarTile = 64;      // hypotheses per workgroup of the scoring kernel, points per LDS tile
+constexpr int kPlanarSums = 29;
+
+template <class T>
+__device__ __forceinline__ T *planar_pair(T *p, size_t bytes) {
+  return (T *)((char *)p + (size_t)blockIdx.z * bytes);
+}
+
+__device__ __forceinline__ bool planar_finite(float v) { return fabsf(v) < __builtin_inff(); }
+
+// coord [4][num_pts], fitset [num_pts], block_counts [ceil(num_pts / 256)]
+__global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusift_point *__restrict__ pts, int num_pts,
+                                                                     int num_pts2, int rule, float lo, float hi,
+                                                                     float *__restrict__ coord,
+                                                                     unsigned char *__restrict__ marks,
+                                                                     int *__restrict__ block_counts, PlanarBatch nb) {
+  __shared__ int s_wave[kPlanarThreads / 64];
+  pts += (size_t)blockIdx.z * nb.records;
+  coord = planar_pair(coord, nb.scratch), marks = planar_pair(marks, nb.scratch);
+  block_counts = planar_pair(block_counts, nb.scratch);
+  const int tx = threadIdx.x;
+  const int i = blockIdx.x * kPlanarThreads + tx;
+  bool cand = false;
+  if (i < num_pts) {
+    const cusift_point *p = pts + i;
+    const float x1 = p->coords2D[0], y1 = p->coords2D[1], x2 = p->match_xpos, y2 = p->match_ypos;
+    const float score = p->score, amb = p->ambiguity;
+    const int m = p->match;
+    coord[i] = x1;
+    coord[i + num_pts] = y1;
+    coord[i + 2 * (size_t)num_pts] = x2;
+    coord[i + 3 * (size_t)num_pts] = y2;
+    cand = rule == 0 ? (score > lo && amb < hi) : (score < lo && amb < hi);
+    cand = cand && planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
+    cand = cand && (num_pts2 < 0 || (m >= 0 && m < num_pts2));
+    // the refit's point set: ImproveHomography's literal predicate (:286) under rule 0, the candidates under rule 1
+    const bool fit = rule == 0 ? !(score < lo || amb > hi) : cand;
+    marks[i] = (unsigned char)((cand ? 1 : 0) | (fit ? 2 : 0));
+  }
+  const unsigned long long m = __ballot(cand);
+  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
+  __syncthreads();
+  if (tx == 0) block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// cand[k] = record index of the k-th candidate; the last workgroup writes their number into head[18].
+__global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const unsigned char *__restrict__ marks,
+                                                                        int num_pts,
+                                                                        const int *__restrict__ block_counts,
+                                                                        int *__restrict__ cand, int *__restrict__ head,
+                                                                        PlanarBatch nb) {
+  __shared__ int s_red[kPlanarThreads];
+  __shared__ int s_wave[kPlanarThreads / 64];
+  marks = planar_pair(marks, nb.scratch), block_counts = planar_pair(block_counts, nb.scratch);
+  cand = planar_pair(cand, nb.scratch), head = planar_pair(head, nb.scratch);
+  const int tx = threadIdx.x;
+  int before = 0;  // integer sums: any order gives the same value
+  for (int b = tx; b < (int)blockIdx.x; b += kPlanarThreads) before += block_counts[b];
+  s_red[tx] = before;
+  __syncthreads();
+#pragma unroll
+  for (int half = kPlanarThreads / 2; half > 0; half >>= 1) {
+    if (tx < half) s_red[tx] += s_red[tx + half];
+    __syncthreads();
+  }
+  const int base = s_red[0];
+  const int i = blockIdx.x * kPlanarThreads + tx;
+  const bool keep = i < num_pts && (marks[i] & 1);
+  const unsigned long long m = __ballot(keep);
+  const int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
+  __syncthreads();
+  int wave_base = 0;
+#pragma unroll
+  for (int wv = 0; wv < kPlanarThreads / 64; ++wv) wave_base += wv < (tx >> 6) ? s_wave[wv] : 0;
+  if (keep) cand[base + wave_base + rank] = i;  // < num_pts: every keep before this one is a distinct record below i
+  if (blockIdx.x == gridDim.x - 1 && tx == 0) head[18] = base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+// a * b rounded toward zero for a, b that hold fp32 values: the product is exact in fp64; round it to nearest, then step
+// back towards zero if that overshot (f != 0 there, so the step is one off the magnitude bits -- nextafterf(f, 0)).
+__device__ __forceinline__ float planar_mul_rz(double a, double b) {
+  const double p = a * b;
+  const float f = (float)p;
+  const unsigned int bits = __builtin_bit_cast(unsigned int, f);
+  return fabs((double)f) > fabs(p) ? __builtin_bit_cast(float, bits - 1u) : f;
+}
+
+// TestHomographies' inlier test (extras/homography.cu:160-171), the expressions of homography_test_kernel; the one
+// function both the scoring and the winner's flags use, so the flags add up to the winner's count.
+__device__ __forceinline__ bool planar_inlier(const double (&a)[8], float a2, float a5, double x1, double y1, double x2,
+                                              double y2, double thresh2) {
+  const float nomx = planar_mul_rz(a[0], x1) + planar_mul_rz(a[1], y1) + a2;
+  const float nomy = planar_mul_rz(a[3], x1) + planar_mul_rz(a[4], y1) + a5;
+  const float deno = planar_mul_rz(a[6], x1) + planar_mul_rz(a[7], y1) + 1.0f;
+  const double dd = (double)deno;
+  const float errx = planar_mul_rz(x2, dd) - nomx;
+  const float erry = planar_mul_rz(y2, dd) - nomy;
+  const float err2 = planar_mul_rz((double)errx, (double)errx) + planar_mul_rz((double)erry, (double)erry);
+  return err2 < planar_mul_rz(thresh2, (double)planar_mul_rz(dd, dd));
+}
+
+// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the points [y * pts_per_split, (y + 1) * pts_per_split).
+// counts were zeroed by the solve kernel.
+__global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *__restrict__ coord, int num_pts,
+                                                                   int pts_per_split, const float *__restrict__ homo,
+                                                                   int num_loops, float thresh2,
+                                                                   int *__restrict__ counts,
+                                                                   const int *__restrict__ head, PlanarBatch nb) {
+  __shared__ double s_pt[4][kPlanarTile];
+  coord = planar_pair(coord, nb.scratch), homo = planar_pair(homo, nb.scratch);
+  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.scratch);
+  if (head[18] < 8) return;  // uniform; nothing was solved: planar_select_kernel answers alone
+  const int tx = threadIdx.x;
+  const int loop = blockIdx.x * kPlanarTile + tx;
+  const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
+  double a[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = (double)homo[(size_t)i * num_loops + src];
+  const float a2 = (float)a[2], a5 = (float)a[5];
+  const double t2 = (double)thresh2;
+  const int begin = blockIdx.y * pts_per_split;
+  const int end = min(num_pts, begin + pts_per_split);
+  int cnt = 0;
+  for (int tile = begin; tile < end; tile += kPlanarTile) {
+    const int n = min(kPlanarTile, end - tile);
+    __syncthreads();
+    if (tx < n) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s_pt[c][tx] = (double)coord[(size_t)c * num_pts + tile + tx];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < n; ++j)
+      cnt += planar_inlier(a, a2, a5, s_pt[0][j], s_pt[1][j], s_pt[2][j], s_pt[3][j], t2) ? 1 : 0;
+  }
+  if (loop < num_loops && cnt) atomicAdd(&counts[loop], cnt);
+}
+
+// cholesky_solve8 of include/homography.h on M (lower triangle read), fully unrolled so that every index is static;
+// false (a untouched) if M is not positive definite.
+__device__ __forceinline__ bool planar_cholesky8(const double (&M)[8][8], const double (&x)[8], double (&a)[8]) {
+  double L[8][8];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      double s = M[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+      if (i == j) {
+        ok = ok && (s > 0.0);
+        L[i][i] = sqrt(s);
+      } else {
+        L[i][j] = s / L[j][j];
+      }
+    }
+  double y[8], r[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    double s = x[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = 7; i >= 0; --i) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 8; ++k) s -= L[k][i] * r[k];
+    r[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = ok ? r[i] : a[i];
+  return ok;
+}
+
+// The reprojection error of ImproveHomography, include/homography.h:116-120 and :134-137 (the same expressions).
+__device__ __forceinline__ float planar_err(const double (&A)[8], float px, float py, float mx, float my) {
+  const float den = (float)(A[6] * px + A[7] * py + 1.0);
+  const float dx = (float)((A[0] * px + A[1] * py + A[2]) / den - mx);
+  const float dy = (float)((A[3] * px + A[4] * py + A[5]) / den - my);
+  return dx * dx + dy * dy;
+}
+
+// head: H[9] (refined), R[9] (the winner) as float, then n_cand, the winner's count, num_fit, the winning loop as int.
+__global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_point *__restrict__ pts, int num_pts,
+                                                                       const float *__restrict__ coord,
+                                                                       const unsigned char *__restrict__ marks,
+                                                                       const float *__restrict__ homo,
+                                                                       const int *__restrict__ counts, int num_loops,
+                                                                       float thresh2, int refine_loops, float limit,
+                                                                       float *__restrict__ head,
+                                                                       char *__restrict__ flags, PlanarBatch nb) {
+  __shared__ unsigned long long s_key[kPlanarThreads];
+  __shared__ double s_part[kPlanarThreads / 64][kPlanarSums];
+  __shared__ double s_sum[kPlanarSums];
+  __shared__ double s_a[8];
+  __shared__ int s_cnt[kPlanarThreads];
+  pts += (size_t)blockIdx.z * nb.records;
+  coord = planar_pair(coord, nb.scratch), marks = planar_pair(marks, nb.scratch), homo = planar_pair(homo, nb.scratch);
+  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.scratch), flags = planar_pair(flags, nb.scratch);
+  const float *__restrict__ cx1 = coord, *__restrict__ cy1 = coord + num_pts;
+  const float *__restrict__ cx2 = coord + 2 * (size_t)num_pts, *__restrict__ cy2 = coord + 3 * (size_t)num_pts;
+  const int tx = threadIdx.x;
+  int *ihead = (int *)head;
+  if (ihead[18] < 8) {  // uniform; extras/homography.cu:220: the identity, no inlier, the records stay as they are
+    for (int i = tx; i < num_pts; i += kPlanarThreads) flags[i] = 0;
+    if (tx < 18) head[tx] = (tx % 9 == 0 || tx % 9 == 4 || tx % 9 == 8) ? 1.0f : 0.0f;
+    if (tx >= 19 && tx < 22) ihead[tx] = 0;
+    return;
+  }
+  // ---- the first hypothesis with the most inliers ----
+  unsigned long long key = 0;
+  for (int l = tx; l < num_loops; l += kPlanarThreads) {
+    const unsigned long long k = ((unsigned long long)(unsigned int)counts[l] << 32) | (unsigned int)~(unsigned int)l;
+    key = k > key ? k : key;
+  }
+  s_key[tx] = key;
+  __syncthreads();
+#pragma unroll
+  for (int half = kPlanarThreads / 2; half > 0; half >>= 1) {
+    if (tx < half) s_key[tx] = s_key[tx + half] > s_key[tx] ? s_key[tx + half] : s_key[tx];
+    __syncthreads();
+  }
+  key = s_key[0];
+  const int best = (int)~(unsigned int)(key & 0xffffffffull), best_count = (int)(unsigned int)(key >> 32);
+  float win[8];
+  double A[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    win[i] = homo[(size_t)i * num_loops + best];
+    A[i] = (double)win[i];
+  }
+  for (int i = tx; i < num_pts; i += kPlanarThreads)
+    flags[i] = planar_inlier(A, win[2], win[5], (double)cx1[i], (double)cy1[i], (double)cx2[i], (double)cy2[i],
+                             (double)thresh2)
+                   ? 1
+                   : 0;
+  // ---- ImproveHomography: refine_loops rounds of weighted least squares, A starts as the winner (h[8] = 1) ----
+#pragma unroll 1
+  for (int round = 0; round < refine_loops; ++round) {
+    double s[kPlanarSums];
+#pragma unroll
+    for (int q = 0; q < kPlanarSums; ++q) s[q] = 0.0;
+    for (int i = tx; i < num_pts; i += kPlanarThreads) {  // thread tx owns records tx, tx + 256, ...
+      if (!(marks[i] & 2)) continue;
+      const float px = cx1[i], py = cy1[i], mx = cx2[i], my = cy2[i];
+      const float err = planar_err(A, px, py, mx, my);
+      const double w = (double)(limit / (err + limit));
+      const double x = px, y = py, u = mx, v = my;
+      const double x6 = -(double)(px * mx), x7 = -(double)(py * mx), y6 = -(double)(px * my), y7 = -(double)(py * my);
+      s[0] += x * x * w, s[1] += x * y * w, s[2] += x * w, s[3] += y * y * w, s[4] += y * w, s[5] += w;
+      s[6] += x * x6 * w, s[7] += x * x7 * w, s[8] += y * x6 * w, s[9] += y * x7 * w, s[10] += x6 * w, s[11] += x7 * w;
+      s[12] += x * y6 * w, s[13] += x * y7 * w, s[14] += y * y6 * w, s[15] += y * y7 * w, s[16] += y6 * w, s[17] += y7 * w;
+      s[18] += x6 * x6 * w + y6 * y6 * w, s[19] += x6 * x7 * w + y6 * y7 * w, s[20] += x7 * x7 * w + y7 * y7 * w;
+      s[21] += x * u * w, s[22] += y * u * w, s[23] += u * w;
+      s[24] += x * v * w, s[25] += y * v * w, s[26] += v * w;
+      s[27] += x6 * u * w + y6 * v * w, s[28] += x7 * u * w + y7 * v * w;
+    }
+    // fixed order: the lane tree of every wave, then waves 0, 1, 2, 3
+#pragma unroll
+    for (int q = 0; q < kPlanarSums; ++q) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off);
+    }
+    __syncthreads();
+    if ((tx & 63) == 0) {
+#pragma unroll
+      for (int q = 0; q < kPlanarSums; ++q) s_part[tx >> 6][q] = s[q];
+    }
+    __syncthreads();
+    if (tx < kPlanarSums) s_sum[tx] = ((s_part[0][tx] + s_part[1][tx]) + s_part[2][tx]) + s_part[3][tx];
+    __syncthreads();
+    if (tx == 0) {  // one lane solves, everybody reads the answer
+      double t[kPlanarSums];
+#pragma unroll
+      for (int q = 0; q < kPlanarSums; ++q) t[q] = s_sum[q];
+      const double M[8][8] = {{t[0], t[1], t[2], 0.0, 0.0, 0.0, t[6], t[7]},
+                              {t[1], t[3], t[4], 0.0, 0.0, 0.0, t[8], t[9]},
+                              {t[2], t[4], t[5], 0.0, 0.0, 0.0, t[10], t[11]},
+                              {0.0, 0.0, 0.0, t[0], t[1], t[2], t[12], t[13]},
+                              {0.0, 0.0, 0.0, t[1], t[3], t[4], t[14], t[15]},
+                              {0.0, 0.0, 0.0, t[2], t[4], t[5], t[16], t[17]},
+                              {t[6], t[8], t[10], t[12], t[14], t[16], t[18], t[19]},
+                              {t[7], t[9], t[11], t[13], t[15], t[17], t[19], t[20]}};
+      const double X[8] = {t[21], t[22], t[23], t[24], t[25], t[26], t[27], t[28]};
+      double r[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) r[i] = A[i];
+      planar_cholesky8(M, X, r);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s_a[i] = r[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) A[i] = s_a[i];
+  }
+  // ---- match_error of every record, the number that fit (include/homography.h:131-140) ----
+  int fit = 0;
+  for (int i = tx; i < num_pts; i += kPlanarThreads) {
+    const float err = planar_err(A, cx1[i], cy1[i], cx2[i], cy2[i]);
+    fit += err < limit ? 1 : 0;
+    pts[i].match_error = sqrtf(err);
+  }
+  s_cnt[tx] = fit;
+  __syncthreads();
+#pragma unroll
+  for (int half = kPlanarThreads / 2; half > 0; half >>= 1) {
+    if (tx < half) s_cnt[tx] += s_cnt[tx + half];
+    __syncthreads();
+  }
+  if (tx == 0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      head[i] = (float)A[i];
+      head[9 + i] = win[i];
+    }
+    head[8] = 1.0f;
+    head[17] = 1.0f;
+    ihead[19] = best_count;
+    ihead[20] = s_cnt[0];
+    ihead[21] = best;
+  }
+}
+
+}  // namespace cusift

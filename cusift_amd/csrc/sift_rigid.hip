@@ -53,17 +53,6 @@ constexpr int kRigidTile = 256;     // points per LDS tile
 constexpr int kRigidSweeps = 6;     // cyclic Jacobi sweeps over the 6 off-diagonal pairs (fp64 4x4: converged after 5)
 constexpr int kRigidRedraws = 64;
 
-__device__ __forceinline__ unsigned long long rigid_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ int rigid_draw(unsigned long long seed, int loop, unsigned int k, int num_pts) {
-  const unsigned long long u = rigid_mix(seed ^ rigid_mix(((unsigned long long)(unsigned int)loop << 32) | k));
-  return (int)((unsigned int)(u >> 32) % (unsigned int)num_pts);
-}
-
 // One Jacobi rotation that annihilates a[P][Q] of the symmetric a (upper triangle kept, P < Q) and rotates columns
 // P, Q of v.  No branch: an off-diagonal entry that is already zero (or a NaN matrix) takes the identity rotation.
 template <int P, int Q>

@@ -740,7 +740,8 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
   hipLaunchKernelGGL(homography_gather_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream, d_sift, num_pts,
                      d_coord);
   hipLaunchKernelGGL(homography_solve_kernel, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord, num_pts,
-                     d_rand, num_loops, d_homo);
+                     d_rand, num_loops, d_homo, 0, 0ull, (const int *)nullptr, (const int *)nullptr, (int *)nullptr,
+                     PlanarBatch{});
   hipLaunchKernelGGL(homography_test_kernel, dim3(num_loops), dim3(64), 0, ctx->stream, d_coord, num_pts, d_homo,
                      num_loops, thresh * thresh, d_counts);
   TRY(check_launch("find_homography"));
@@ -761,6 +762,155 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
   if (h_all_homo) memcpy(h_all_homo, homo.data(), sizeof(float) * homo.size());
   if (h_all_counts) memcpy(h_all_counts, counts.data(), sizeof(int) * counts.size());
   return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// planar registration (sift_planar.hip): candidates, seeded RANSAC homography, refit -- one read-back
+// ------------------------------------------------------------------------------------------------
+struct PlanarOut {
+  float *h_homography, *h_ransac;
+  int *num_candidates, *num_matches, *num_fit, *best_loop;
+  char *h_inliers;
+  int *h_drawn;
+  float *h_all_homo;
+  int *h_all_counts;
+};
+
+// every refusal of cusift_estimate_homography, before anything is enqueued or written
+static int planar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
+                        int num_loops, float thresh, int refine_loops, float refine_thresh, const PlanarOut &o) {
+  if (!o.h_homography || !o.h_ransac || !o.num_candidates || !o.num_matches || !o.num_fit)
+    return fail(CUSIFT_ERR_INVALID, "%s: NULL output", who);
+  if (rule != 0 && rule != 1) return fail(CUSIFT_ERR_INVALID, "%s: rule must be 0 (score > lo) or 1 (score < lo^2)", who);
+  if (std::isnan(lo) || std::isnan(hi)) return fail(CUSIFT_ERR_INVALID, "%s: a threshold is NaN", who);
+  if (num_loops < 1 || num_loops > (1 << 24))
+    return fail(CUSIFT_ERR_INVALID, "%s: num_loops %d outside [1, 2^24]", who, num_loops);
+  if (!(thresh > 0.0f) || !(refine_thresh > 0.0f))
+    return fail(CUSIFT_ERR_INVALID, "%s: thresh and refine_thresh must be > 0", who);
+  if (refine_loops < 0) return fail(CUSIFT_ERR_INVALID, "%s: refine_loops %d < 0", who, refine_loops);
+  if (num_pts < 0 || num_pts > (1 << 26)) return fail(CUSIFT_ERR_INVALID, "%s: num_pts %d outside [0, 2^26]", who, num_pts);
+  if (num_pts > 0 && !d_sift) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
+  return CUSIFT_OK;
+}
+
+static void planar_identity(int num_pts, int num_loops, const PlanarOut &o) {
+  static const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // extras/homography.cu:184-187
+  memcpy(o.h_homography, ident, sizeof(ident));
+  memcpy(o.h_ransac, ident, sizeof(ident));
+  *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
+  if (o.best_loop) *o.best_loop = 0;
+  if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
+  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 4 * (size_t)num_loops);
+  if (o.h_all_homo) memset(o.h_all_homo, 0, sizeof(float) * 8 * (size_t)num_loops);
+  if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
+}
+
+// The five launches and the one read-back; the arguments are checked and num_pts >= 8.
+static int planar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
+                      int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
+                      const PlanarOut &o) {
+  // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
+  const size_t head_b = 256;
+  const size_t flag_b = align_up_sz((size_t)num_pts, 256);
+  const size_t idx_b = align_up_sz(sizeof(int) * 4 * (size_t)num_loops, 256);
+  const size_t homo_b = align_up_sz(sizeof(float) * 8 * (size_t)num_loops, 256);
+  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
+  const size_t coord_b = align_up_sz(sizeof(float) * 4 * (size_t)num_pts, 256);
+  const size_t cand_b = align_up_sz(sizeof(int) * (size_t)num_pts, 256);
+  const size_t mark_b = flag_b;
+  const int blocks = idiv_up(num_pts, 256);
+  const size_t block_b = align_up_sz(sizeof(int) * (size_t)blocks, 256);
+  const size_t idx_off = head_b + flag_b, homo_off = idx_off + idx_b, cnt_off = homo_off + homo_b;
+  const size_t coord_off = cnt_off + cnt_b, cand_off = coord_off + coord_b, mark_off = cand_off + cand_b;
+  const size_t block_off = mark_off + mark_b;
+  TRY(grow_scratch(ctx, ctx->homo_scratch, ctx->homo_scratch_bytes, block_off + block_b, "", false));
+  char *base = ctx->homo_scratch;
+  float *d_head = (float *)base, *d_homo = (float *)(base + homo_off), *d_coord = (float *)(base + coord_off);
+  char *d_flags = base + head_b;
+  int *d_idx = (int *)(base + idx_off), *d_counts = (int *)(base + cnt_off), *d_cand = (int *)(base + cand_off);
+  unsigned char *d_marks = (unsigned char *)(base + mark_off);
+  int *d_blocks = (int *)(base + block_off);
+  const PlanarBatch nb{};
+  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
+  // scoring: 64 hypotheses per one-wave workgroup; split the points until the launch has ~8 waves per CU, but keep at
+  // least one 64-point tile per split
+  const int loop_blocks = idiv_up(num_loops, 64);
+  int splits = std::max(1, std::min(idiv_up(8 * ctx->num_cus, loop_blocks), idiv_up(num_pts, 64)));
+  splits = std::min(splits, 65535);
+  const int pts_per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
+  splits = idiv_up(num_pts, pts_per_split);
+  hipLaunchKernelGGL(planar_mark_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const cusift_point *)d_sift, num_pts,
+                     num_pts2, rule, t_lo, t_hi, d_coord, d_marks, d_blocks, nb);
+  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const unsigned char *)d_marks,
+                     num_pts, (const int *)d_blocks, d_cand, (int *)d_head, nb);
+  hipLaunchKernelGGL(homography_solve_kernel, dim3(loop_blocks), dim3(64), 0, ctx->stream, (const float *)d_coord,
+                     num_pts, d_idx, num_loops, d_homo, 1, (unsigned long long)seed, (const int *)d_cand,
+                     (const int *)d_head + 18, d_counts, nb);
+  hipLaunchKernelGGL(planar_score_kernel, dim3(loop_blocks, splits), dim3(64), 0, ctx->stream, (const float *)d_coord,
+                     num_pts, pts_per_split, (const float *)d_homo, num_loops, thresh * thresh, d_counts,
+                     (const int *)d_head, nb);
+  hipLaunchKernelGGL(planar_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, (const float *)d_coord,
+                     (const unsigned char *)d_marks, (const float *)d_homo, (const int *)d_counts, num_loops,
+                     thresh * thresh, refine_loops, refine_thresh * refine_thresh, d_head, d_flags, nb);
+  TRY(check_launch("estimate_homography"));
+  // the one blocking read-back
+  const bool all = o.h_drawn || o.h_all_homo || o.h_all_counts;
+  std::vector<char> back(all ? coord_off : head_b + (o.h_inliers ? flag_b : 0));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  int tail[4];
+  memcpy(tail, back.data() + sizeof(float) * 18, sizeof(tail));
+  if (tail[0] < 8) {  // extras/homography.cu:220; the kernels left the records alone
+    planar_identity(num_pts, num_loops, o);
+    *o.num_candidates = tail[0];
+    return CUSIFT_OK;
+  }
+  memcpy(o.h_homography, back.data(), sizeof(float) * 9);
+  memcpy(o.h_ransac, back.data() + sizeof(float) * 9, sizeof(float) * 9);
+  *o.num_candidates = tail[0], *o.num_matches = tail[1], *o.num_fit = tail[2];
+  if (o.best_loop) *o.best_loop = tail[3];
+  if (o.h_inliers) memcpy(o.h_inliers, back.data() + head_b, (size_t)num_pts);
+  if (o.h_drawn) memcpy(o.h_drawn, back.data() + idx_off, sizeof(int) * 4 * (size_t)num_loops);
+  if (o.h_all_homo) memcpy(o.h_all_homo, back.data() + homo_off, sizeof(float) * 8 * (size_t)num_loops);
+  if (o.h_all_counts) memcpy(o.h_all_counts, back.data() + cnt_off, sizeof(int) * (size_t)num_loops);
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
+                                          float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                          float refine_thresh, uint64_t seed, float h_homography[9], float h_ransac[9],
+                                          int *num_candidates, int *num_matches, int *num_fit, int *best_loop,
+                                          char *h_inliers, int *h_drawn, float *h_all_homo, int *h_all_counts) {
+  TRY(enter(ctx));
+  const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
+  TRY(planar_check("EstimateHomography", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  if (num_pts < 8) {  // extras/homography.cu:205
+    planar_identity(num_pts, num_loops, o);
+    return CUSIFT_OK;
+  }
+  return planar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed, o);
+}
+
+extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                      int num_pts2, int distance, int rule, float lo, float hi, int num_loops,
+                                      float thresh, int refine_loops, float refine_thresh, uint64_t seed,
+                                      float h_homography[9], float h_ransac[9], int *num_candidates, int *num_matches,
+                                      int *num_fit, int *best_loop, char *h_inliers, int *h_drawn, float *h_all_homo,
+                                      int *h_all_counts) {
+  TRY(enter(ctx));
+  const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
+  TRY(planar_check("RegisterPlanar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterPlanar: distance must be 0 or 1");
+  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterPlanar: missing data");
+  TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
+  if (num_pts1 < 8) {  // as the staged route: the matcher stays enqueued, the answer needs no device work
+    planar_identity(num_pts1, num_loops, o);
+    return CUSIFT_OK;
+  }
+  return planar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed,
+                    o);
 }
 
 // ------------------------------------------------------------------------------------------------

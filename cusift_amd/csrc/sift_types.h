@@ -150,6 +150,12 @@ struct RigidBatch {
   int count;
 };
 
+// between consecutive pairs of a batched planar registration (blockIdx.z of the planar_* kernels and of the drawing
+// homography_solve_kernel): records between the pairs' record arrays, bytes between their scratch blocks; 0 for one pair
+struct PlanarBatch {
+  size_t records, scratch;
+};
+
 static_assert(sizeof(cusift_point) == 588, "SiftPoint is a 588-byte ABI record (cuSIFT.h:10-30)");
 
 }  // namespace cusift

@@ -20,7 +20,7 @@
  *   cusift_amd_multigpu.h: SiftData on the wire (pack / trimmed / compact records), the communicator over RCCL, the
  *     all-gatherv of SiftData, halo exchange, the strip tiling of one large image over the ranks and its band kernels.
  *   cusift_amd_extras.h: the next rows of SURVEY 8f -- cusift_match, cusift_find_homography,
- *                        cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd.
+ *                        cusift_estimate_homography, cusift_register_planar, cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd.
  *
  * Conventions
  *  - every function returns CUSIFT_OK (0) or a negative cusift_status; cusift_last_error() gives text.

@@ -1,7 +1,8 @@
 /*
  * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography, the
- * RANSAC rigid transform and the RGB-D registration built on them (depth lift, match selection, the fused call for
- * one frame pair and for a pair list over a batch of frames).
+ * planar registration built on both (seeded RANSAC + refit on the device), the RANSAC rigid transform and the RGB-D
+ * registration built on them (depth lift, match selection, the fused call for one frame pair and for a pair list over a
+ * batch of frames).
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
@@ -39,6 +40,62 @@ int cusift_memcpy2d_d2h(cusift_ctx *ctx, void *h_dst, size_t dst_pitch, const vo
 int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sift, int num_pts, const int *h_rand_pts,
                            int num_loops, float thresh, float h_homography[9], int *num_matches, float *h_all_homo,
                            int *h_all_counts);
+
+/* ---- planar registration on the device: seeded homography RANSAC + refit (sift_planar.hip) ------------------- */
+/* FindHomography followed by ImproveHomography (extras/homography.cu:182-336, the chain of main.cpp:331-335) on device
+ * records that already carry match fields: records in, H out, reproducible from `seed`, no host decision and no host
+ * round trip between the stages.
+ * CANDIDATES, in ASCENDING record order (ordered compaction without atomics, as cusift_select_matches: the same input
+ * gives the same list), by `rule`:
+ *     0: score > lo && ambiguity < hi          FindHomography's predicate (:218-219), for the dot-product distance
+ *     1: score < lo^2 && ambiguity < hi^2      cusift_select_matches' type-0 predicate, for the L2 distance
+ *   under both rules also: coords2D, match_xpos and match_ypos finite and, when num_pts2 >= 0, 0 <= match < num_pts2.
+ * SAMPLES are drawn on the device, four distinct candidates per hypothesis, integer arithmetic only:
+ *     draw k of loop l:  cand[(mix(seed ^ mix((l << 32) | k)) >> 32) mod n_cand]
+ *     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)              (64-bit unsigned, wrapping)
+ *     p1..p4 = draws 0..3; then with k = 4, 5, ...: while p2 == p1 redraw p2; while p3 is p1 or p2 redraw p3; while p4
+ *     is p1, p2 or p3 redraw p4 (the reference's order, :222-235); a slot redrawn 64 times takes the lowest candidate
+ *     not taken yet.
+ * HYPOTHESES AND COUNTS are ComputeHomographies (:89-130) and TestHomographies (:135-178) with the arithmetic of
+ * cusift_find_homography, counted over ALL num_pts records.  The WINNER is the first hypothesis with the most inliers
+ * (:237-258), selected on the device: h_ransac[0..7], h_ransac[8] = 1, *num_matches = its count, *best_loop its index,
+ * h_inliers[i] = 1 for its inliers.
+ * REFIT is ImproveHomography (:271-336) on the device, starting from the winner: refine_loops rounds of the weighted
+ * normal equations, weight limit / (err + limit) with limit = refine_thresh^2, over the records with !(score < lo ||
+ * ambiguity > hi) under rule 0 (ImproveHomography's literal predicate) and over the candidates under rule 1.  The 8x8
+ * sums and the Cholesky solve are fp64 (the unnormalised normal matrix has a condition number above 1e13); the partial
+ * sums are reduced in a fixed order, so every run gives the same bits.  A matrix that is not positive definite keeps the
+ * previous estimate.  Afterwards match_error = sqrtf(err) is written into EVERY device record (the reference writes the
+ * host records) and *num_fit = the number of records with err < limit; h_homography[0..7] is the refined estimate,
+ * h_homography[8] = 1.  refine_loops == 0 skips the refit: h_homography = h_ransac, match_error and *num_fit are
+ * evaluated with the winner.
+ * *num_candidates = the candidates.  Optional (may be NULL): best_loop, h_inliers [num_pts], h_drawn [4][num_loops]
+ * (the samples as record indices, the layout cusift_find_homography takes), h_all_homo [8][num_loops], h_all_counts
+ * [num_loops].  The same seed gives the same bytes in every output and in the records.
+ * num_pts < 8 or fewer than 8 candidates (the reference's own limits, :205,220): identity in both matrices, every count
+ * 0 (*num_candidates still reports the candidates), the optional arrays zeroed, CUSIFT_OK; the records are untouched.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): a NULL h_homography / h_ransac / num_candidates / num_matches
+ * / num_fit, num_loops < 1, thresh or refine_thresh not > 0 (NaN included), a NaN lo / hi, an unknown rule, refine_loops
+ * < 0, missing buffers.  Any num_loops >= 1 is accepted (the rounding to 16 of :200 belongs to the C++ wrapper).
+ * Scratch lives in the context and grows on demand.  Blocking: ONE stream synchronisation, at the one read-back. */
+int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2 /* < 0: no check */,
+                               int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                               float refine_thresh, uint64_t seed, float h_homography[9], float h_ransac[9],
+                               int *num_candidates, int *num_matches, int *num_fit, int *best_loop /* may be NULL */,
+                               char *h_inliers /* may be NULL */, int *h_drawn /* may be NULL */,
+                               float *h_all_homo /* may be NULL */, int *h_all_counts /* may be NULL */);
+
+/* cusift_match(d_sift1, d_sift2, distance) followed by cusift_estimate_homography(d_sift1, num_pts1, num_pts2, ...) with
+ * ONE synchronisation, at the read-back: the same bits as the staged route in every output and in the records.  Also
+ * CUSIFT_ERR_INVALID for an unknown distance. */
+int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                           int num_pts2, int distance, int rule, float lo, float hi, int num_loops, float thresh,
+                           int refine_loops, float refine_thresh, uint64_t seed, float h_homography[9],
+                           float h_ransac[9], int *num_candidates, int *num_matches, int *num_fit,
+                           int *best_loop /* may be NULL */, char *h_inliers /* may be NULL */,
+                           int *h_drawn /* may be NULL */, float *h_all_homo /* may be NULL */,
+                           int *h_all_counts /* may be NULL */);
 
 /* ---- RANSAC rigid transform from matched 3-D points -------------------------- */
 /* EstimateRigidTransformH(h_coord, Rt, numInliers, numLoops, numPts, thresh2, type, h_indices, h_inliers),

@@ -7,10 +7,15 @@
 // hypothesis with the most inliers.  ImproveHomography (extras/homography.cu:271-336) is host arithmetic; the
 // reference solves its 8x8 normal equations with cv::solve(..., DECOMP_CHOLESKY) -- here a plain Cholesky in
 // double, so the header needs no OpenCV.
+//
+// EstimateHomography and RegisterPlanar are the same chain without the host in it (cusift_estimate_homography /
+// cusift_register_planar, cusift_amd_extras.h): candidates, samples drawn from a seed, hypotheses, counts, selection
+// and the refit all run on the device, with one synchronisation; the same seed gives the same bits.
 #ifndef CUSIFT_AMD_HOMOGRAPHY_H
 #define CUSIFT_AMD_HOMOGRAPHY_H
 
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <vector>
 
@@ -141,6 +146,46 @@ inline int ImproveHomography(SiftData &data, float *homography, int numLoops, fl
   for (int i = 0; i < 8; i++) homography[i] = (float)A[i];
   homography[8] = 1.0f;
   return numfit;
+}
+
+// FindHomography + ImproveHomography on the device records of `data` (which carry match fields), with the defaults of
+// the reference's demo (main.cpp:334-335).  homography: 9 floats, the refined estimate; *numMatches: inliers of the
+// winning hypothesis; *numFit: records within refineThresh of the refined estimate.  match_error is written into the
+// DEVICE records (data.Synchronize() brings it to the host).  rule 0: score > minScore && ambiguity < maxAmbiguity;
+// rule 1: score < minScore^2 && ambiguity < maxAmbiguity^2 (for MatchSiftDistanceL2).  ransac (may be NULL): the winning
+// hypothesis before the refit.  Returns the elapsed milliseconds.
+inline double EstimateHomography(SiftData &data, float *homography, int *numMatches, int *numFit, int numLoops = 10000,
+                                 float minScore = 0.0f, float maxAmbiguity = 0.8f, float thresh = 5.0f,
+                                 int refineLoops = 5, float refineThresh = 3.0f, uint64_t seed = 0, int rule = 0,
+                                 float *ransac = nullptr, int numPts2 = -1) {
+  TimerGPU timer;
+  numLoops = iDivUp(numLoops, 16) * 16;  // extras/homography.cu:200
+  float winner[9];
+  int numCandidates = 0;
+  safeCall(cusift_estimate_homography(cusift_dropin::ctx(), reinterpret_cast<cusift_point *>(data.d_data), data.numPts,
+                                      numPts2, rule, minScore, maxAmbiguity, numLoops, thresh, refineLoops,
+                                      refineThresh, seed, homography, ransac ? ransac : winner, &numCandidates,
+                                      numMatches, numFit, nullptr, nullptr, nullptr, nullptr, nullptr));
+  return timer.read();
+}
+
+// MatchSiftData's device part, then EstimateHomography over data1, in one call with one synchronisation
+// (cusift_register_planar): homography maps data1's image onto data2's.  distance: 0 = MatchSiftDistanceDotProduct,
+// 1 = MatchSiftDistanceL2 (use rule 1 with it).  Writes the match fields and match_error of data1's device records.
+inline double RegisterPlanar(SiftData &data1, SiftData &data2, float *homography, int *numMatches, int *numFit,
+                             int numLoops = 10000, float minScore = 0.0f, float maxAmbiguity = 0.8f,
+                             float thresh = 5.0f, int refineLoops = 5, float refineThresh = 3.0f, uint64_t seed = 0,
+                             int distance = 0, int rule = 0, float *ransac = nullptr) {
+  TimerGPU timer;
+  numLoops = iDivUp(numLoops, 16) * 16;  // extras/homography.cu:200
+  float winner[9];
+  int numCandidates = 0;
+  safeCall(cusift_register_planar(cusift_dropin::ctx(), reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
+                                  reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts, distance, rule,
+                                  minScore, maxAmbiguity, numLoops, thresh, refineLoops, refineThresh, seed, homography,
+                                  ransac ? ransac : winner, &numCandidates, numMatches, numFit, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr));
+  return timer.read();
 }
 
 #endif  // CUSIFT_AMD_HOMOGRAPHY_H
