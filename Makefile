@@ -54,6 +54,7 @@ cpp-tests: $(LIB)
 	$(MAKE) -C $(ROOT)/tests/cpp_rgbd
 	$(MAKE) -C $(ROOT)/tests/cpp_rgbd_batch
 	$(MAKE) -C $(ROOT)/tests/cpp_planar
+	$(MAKE) -C $(ROOT)/tests/cpp_planar_batch
 
 check: cpp-tests
 	$(MAKE) -C $(ROOT)/tests/cpp check

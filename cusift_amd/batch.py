@@ -114,6 +114,20 @@ class BatchExtractor:
         n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
         return self.ctx.register_planar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
 
+    def register_planar_sequence(self, pairs=None, slot=0, **opts):
+        """Planar registration of the frames of the last extract() into `slot` against each other:
+        cusift_register_planar_batch over this extractor's own device records and raw counters -- no count is read
+        back and the records are not written, so a frame may be the first member of any number of pairs.  pairs:
+        (frame a, frame b) rows; None: (i, i + 1) for every consecutive frame.  **opts goes to
+        capi.Context.register_planar_batch (distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh, seed,
+        want_inliers, want_errors).  Returns its PlanarBatchResult: homography[p] maps frame a onto frame b;
+        capi.chain_homographies(homography) turns the default pair list's result into per-frame maps into frame 0.
+        Blocking."""
+        if pairs is None:
+            pairs = [(i, i + 1) for i in range(self.n - 1)]
+        points, counts = self.slots[slot]
+        return self.ctx.register_planar_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts, pairs, **opts)
+
     def valid_counts(self):
         return torch.clamp(self.counts, max=self.max_pts)
 

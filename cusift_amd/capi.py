@@ -216,6 +216,8 @@ SIGNATURES = {
     "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cusift_pack_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_compact": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_trimmed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -316,6 +318,11 @@ PLANAR_RULES = {"dot": 0, "l2": 1}  # the candidate rule of cusift_estimate_homo
 # the counts, the winner's flags bool [num_pts] and, with want_all, drawn [4, L], all_homographies [8, L], all_counts [L]
 PlanarResult = collections.namedtuple("PlanarResult", "homography ransac num_candidates num_matches num_fit best_loop "
                                       "inliers drawn all_homographies all_counts")
+# what cusift_register_planar_batch returns, one entry per pair: homography float32 [P, 9], ransac [P, 9], int32 [P]
+# counts, counts = the records of each pair's first frame (as the device read them), and -- when asked for -- lists of
+# P bool [count] inlier flags and P float32 [count] match errors (NaN where a pair has no fit: nothing was evaluated)
+PlanarBatchResult = collections.namedtuple("PlanarBatchResult", "homography ransac num_candidates num_matches num_fit "
+                                           "best_loop counts inliers match_error")
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
 
 
@@ -396,6 +403,25 @@ def chain_poses(rts, pairs=None):
         step[:3, :] = rt
         poses[i + 1] = poses[i] @ step
     return poses
+
+
+def chain_homographies(h, pairs=None):
+    """Homographies of the frames of a sequence into frame 0, float64 [n_images, 3, 3], from those of consecutive pairs:
+    h[k] maps frame k onto frame k + 1 (what register_planar_batch returns for pair (k, k + 1)), so G[0] = I and
+    G[k + 1] = G[k] @ inv(h[k]), each normalised by its [2, 2].  pairs (optional) must be (0, 1), (1, 2), ...: anything
+    else is a ValueError, as for chain_poses."""
+    h = np.asarray(h, dtype=np.float64).reshape(-1, 3, 3)
+    if pairs is not None:
+        pairs = np.asarray(pairs).reshape(-1, 2)
+        want = np.stack([np.arange(len(h)), np.arange(len(h)) + 1], axis=1)
+        if pairs.shape != want.shape or not np.array_equal(pairs, want):
+            raise ValueError("chain_homographies composes consecutive pairs (i, i + 1) only")
+    chain = np.zeros((len(h) + 1, 3, 3), dtype=np.float64)
+    chain[0] = np.eye(3)
+    for k, step in enumerate(h):
+        g = chain[k] @ np.linalg.inv(step)
+        chain[k + 1] = g / g[2, 2]
+    return chain
 
 
 class Context:
@@ -774,6 +800,34 @@ class Context:
                                                flags.ctypes.data))
         return (rt, n_match, n_in, [sel[p, :n_match[p]].copy() for p in range(n_pairs)],
                 [flags[p, :n_match[p]].astype(bool) for p in range(n_pairs)])
+
+    def register_planar_batch(self, d_points, d_counters, n_images, max_pts, pairs, distance=1, rule=None, lo=None,
+                              hi=None, loops=10000, thresh=5.0, refine_loops=5, refine_thresh=3.0, seed=0,
+                              want_inliers=True, want_errors=False):
+        """cusift_register_planar_batch: register_planar for every pair of `pairs` (int32 [P, 2]) over
+        d_points[n_images][max_pts] + d_counters[n_images] (None: max_pts each) in a fixed number of launches and one
+        synchronisation.  Pair p = (a, b) maps frame a onto frame b and draws from seed + p; the records are not written.
+        rule / lo / hi default as in register_planar.  Returns a PlanarBatchResult."""
+        pairs = pair_list(pairs)
+        n_pairs = len(pairs)
+        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
+        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
+        hi = 0.8 if hi is None else hi
+        hom, ransac = np.zeros((n_pairs, 9), dtype=np.float32), np.zeros((n_pairs, 9), dtype=np.float32)
+        n_cand, n_match, n_fit, best = (np.zeros(n_pairs, dtype=np.int32) for _ in range(4))
+        # the call writes 0 / 1 into the first count entries of a pair's block and nothing behind them
+        flags = np.full((n_pairs, max(max_pts, 1)), -1, dtype=np.int8)
+        err = np.full((n_pairs, max(max_pts, 1)), np.nan, dtype=np.float32) if want_errors else None
+        check(lib().cusift_register_planar_batch(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
+                                                 n_pairs, distance, rule, lo, hi, int(loops), thresh, refine_loops,
+                                                 refine_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, hom.ctypes.data,
+                                                 ransac.ctypes.data, n_cand.ctypes.data, n_match.ctypes.data,
+                                                 n_fit.ctypes.data, best.ctypes.data, flags.ctypes.data,
+                                                 err.ctypes.data if want_errors else None))
+        counts = (flags >= 0).sum(axis=1).astype(np.int32) if max_pts > 0 else np.zeros(n_pairs, dtype=np.int32)
+        return PlanarBatchResult(hom, ransac, n_cand, n_match, n_fit, best, counts,
+                                 [flags[p, :counts[p]] == 1 for p in range(n_pairs)] if want_inliers else None,
+                                 [err[p, :counts[p]].copy() for p in range(n_pairs)] if want_errors else None)
 
     # ---- drivers ----
     def extract_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):

@@ -33,6 +33,9 @@ __device__ __forceinline__ int frame_count(const unsigned int *__restrict__ coun
   return counters ? (int)min(counters[frame], (unsigned int)max_pts) : max_pts;
 }
 
+// a candidate's coordinates are finite (planar_mark_kernel, sequence_mark_kernel)
+__device__ __forceinline__ bool planar_finite(float v) { return fabsf(v) < __builtin_inff(); }
+
 // The sample generator of the RANSAC kernels (sift_rigid.hip, sift_homography.hip): draw k of loop l is
 // mix(seed ^ mix((l << 32) | k)), its upper half modulo n.  Integer arithmetic only, documented in cusift_amd_extras.h.
 __device__ __forceinline__ unsigned long long rigid_mix(unsigned long long z) {

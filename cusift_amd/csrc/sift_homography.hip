@@ -81,7 +81,8 @@ __global__ void __launch_bounds__(kHomoThreads) homography_solve_kernel(const fl
     const size_t off = (size_t)blockIdx.z * nb.scratch;
     coord = (const float *)((const char *)coord + off), rand_pts = (int *)((char *)rand_pts + off);
     homo = (float *)((char *)homo + off), cand = (const int *)((const char *)cand + off);
-    n_cand = (const int *)((const char *)n_cand + off), counts = (int *)((char *)counts + off);
+    counts = (int *)((char *)counts + off);
+    n_cand = (const int *)((const char *)n_cand + (size_t)blockIdx.z * nb.head);  // the heads have a stride of their own
     const int n = min(*n_cand, num_pts);
     if (n < 8) return;
     int p[4];

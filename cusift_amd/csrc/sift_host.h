@@ -72,7 +72,10 @@ __global__ void planar_mark_kernel(const cusift_point *, int, int, int, float, f
 __global__ void planar_compact_kernel(const unsigned char *, int, const int *, int *, int *, PlanarBatch);
 __global__ void planar_score_kernel(const float *, int, int, const float *, int, float, int *, const int *, PlanarBatch);
 __global__ void planar_select_kernel(cusift_point *, int, const float *, const unsigned char *, const float *, const int *,
-                                     int, float, int, float, float *, char *, PlanarBatch);
+                                     int, float, int, float, float *, char *, float *, PlanarBatch);
+__global__ void sequence_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
+                                     const cusift_match_row *, int, float, float, float *, unsigned char *, int *, int *,
+                                     PlanarBatch);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
 template <bool k3D>
 __global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *,
@@ -170,8 +173,8 @@ struct cusift_ctx {
   // per-workgroup keep counts of cusift_select_matches
   int *select_scratch = nullptr;
   size_t select_scratch_bytes = 0;
-  // cusift_match_batch / cusift_register_rgbd_batch: the pair list and the matcher's per-split partials; the match rows,
-  // the selection and the RANSAC state of every pair (what travels back comes first)
+  // cusift_match_batch / cusift_register_rgbd_batch / cusift_register_planar_batch: the pair list and the matcher's
+  // per-split partials; the match rows, the selection and the RANSAC state of every pair (what travels back comes first)
   char *pairs_scratch = nullptr;
   size_t pairs_scratch_bytes = 0;
   char *sequence_scratch = nullptr;

@@ -16,8 +16,14 @@
 //   planar_select_kernel    one workgroup: the winner (64-bit max over count << 32 | ~loop: the most inliers and, among
 //                           equals, the FIRST, :249-254), its inlier flags, ImproveHomography's rounds of weighted normal
 //                           equations, then match_error of every record and the number of records with err < limit
-// Every kernel has a pair index, blockIdx.z: pair p's records lie PlanarBatch::records records further and its scratch
-// block PlanarBatch::scratch bytes further, and it draws from seed + p.  One pair is launched today (both 0).
+// Every kernel has a pair index, blockIdx.z: pair p's arrays lie PlanarBatch's strides further and it draws from seed + p.
+// One pair (cusift_estimate_homography, cusift_register_planar) is gridDim.z == 1 with every stride 0.
+// cusift_register_planar_batch runs all its pairs in the same launches: sequence_mark_kernel (sift_sequence.hip) takes
+// planar_mark_kernel's place -- it reads the match rows of cusift_match_batch instead of the records' match fields and
+// leaves each pair's record count in its head -- and the other kernels read that count (planar_count): num_pts is then
+// the capacity of a pair, the stride of its coordinate rows.  The refit's lane and wave assignment depends on the record
+// index alone, so a pair of a batch sums in the order of the pair call.  A batch's planar_select_kernel writes
+// match_error to an array of its own: the records are read only.
 //
 // CANDIDATES.  rule 0: score > lo && ambiguity < hi (FindHomography, :218-219; dot-product distance).  rule 1: score <
 // lo^2 && ambiguity < hi^2 (cusift_select_matches type 0; L2 distance; the squares arrive computed in fp32).  Both: finite
@@ -54,7 +60,11 @@ __device__ __forceinline__ T *planar_pair(T *p, size_t bytes) {
   return (T *)((char *)p + (size_t)blockIdx.z * bytes);
 }
 
-__device__ __forceinline__ bool planar_finite(float v) { return fabsf(v) < __builtin_inff(); }
+// The number of points of this workgroup's pair: num_pts, or -- batched -- what sequence_mark_kernel left in its head
+// (num_pts is then the capacity of a pair and the stride of its coordinate rows).  `head` is the pair's own.
+__device__ __forceinline__ int planar_count(const int *__restrict__ head, int num_pts, PlanarBatch nb) {
+  return nb.count ? min(head[kPlanarHeadCount], num_pts) : num_pts;
+}
 
 // coord [4][num_pts], fitset [num_pts], block_counts [ceil(num_pts / 256)]
 __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusift_point *__restrict__ pts, int num_pts,
@@ -100,8 +110,9 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const un
   __shared__ int s_red[kPlanarThreads];
   __shared__ int s_wave[kPlanarThreads / 64];
   marks = planar_pair(marks, nb.scratch), block_counts = planar_pair(block_counts, nb.scratch);
-  cand = planar_pair(cand, nb.scratch), head = planar_pair(head, nb.scratch);
+  cand = planar_pair(cand, nb.scratch), head = planar_pair(head, nb.head);
   const int tx = threadIdx.x;
+  const int n = planar_count(head, num_pts, nb);
   int before = 0;  // integer sums: any order gives the same value
   for (int b = tx; b < (int)blockIdx.x; b += kPlanarThreads) before += block_counts[b];
   s_red[tx] = before;
@@ -113,7 +124,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const un
   }
   const int base = s_red[0];
   const int i = blockIdx.x * kPlanarThreads + tx;
-  const bool keep = i < num_pts && (marks[i] & 1);
+  const bool keep = i < n && (marks[i] & 1);
   const unsigned long long m = __ballot(keep);
   const int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
   if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
@@ -121,8 +132,10 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const un
   int wave_base = 0;
 #pragma unroll
   for (int wv = 0; wv < kPlanarThreads / 64; ++wv) wave_base += wv < (tx >> 6) ? s_wave[wv] : 0;
-  if (keep) cand[base + wave_base + rank] = i;  // < num_pts: every keep before this one is a distinct record below i
-  if (blockIdx.x == gridDim.x - 1 && tx == 0) head[18] = base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  if (keep) cand[base + wave_base + rank] = i;  // < n: every keep before this one is a distinct record below i
+  // a pair of a batch with fewer than 8 records reports no candidate, as the pair call answers before it counts
+  if (blockIdx.x == gridDim.x - 1 && tx == 0)
+    head[18] = (nb.count && n < 8) ? 0 : base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
 // a * b rounded toward zero for a, b that hold fp32 values: the product is exact in fp64; round it to nearest, then step
@@ -148,7 +161,8 @@ __device__ __forceinline__ bool planar_inlier(const double (&a)[8], float a2, fl
   return err2 < planar_mul_rz(thresh2, (double)planar_mul_rz(dd, dd));
 }
 
-// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the points [y * pts_per_split, (y + 1) * pts_per_split).
+// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the points [y * pts_per_split, (y + 1) * pts_per_split) -- of a
+// batch the splits are sized from the capacity, and one that lies past its pair's count adds nothing.
 // counts were zeroed by the solve kernel.
 __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *__restrict__ coord, int num_pts,
                                                                    int pts_per_split, const float *__restrict__ homo,
@@ -157,7 +171,7 @@ __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *
                                                                    const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[4][kPlanarTile];
   coord = planar_pair(coord, nb.scratch), homo = planar_pair(homo, nb.scratch);
-  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.scratch);
+  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.head);
   if (head[18] < 8) return;  // uniform; nothing was solved: planar_select_kernel answers alone
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kPlanarTile + tx;
@@ -168,7 +182,7 @@ __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *
   const float a2 = (float)a[2], a5 = (float)a[5];
   const double t2 = (double)thresh2;
   const int begin = blockIdx.y * pts_per_split;
-  const int end = min(num_pts, begin + pts_per_split);
+  const int end = min(planar_count(head, num_pts, nb), begin + pts_per_split);
   int cnt = 0;
   for (int tile = begin; tile < end; tile += kPlanarTile) {
     const int n = min(kPlanarTile, end - tile);
@@ -233,6 +247,7 @@ __device__ __forceinline__ float planar_err(const double (&A)[8], float px, floa
 }
 
 // head: H[9] (refined), R[9] (the winner) as float, then n_cand, the winner's count, num_fit, the winning loop as int.
+// errors == NULL: match_error goes into the records; otherwise into errors[] (a batch, whose records stay as they are).
 __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_point *__restrict__ pts, int num_pts,
                                                                        const float *__restrict__ coord,
                                                                        const unsigned char *__restrict__ marks,
@@ -240,7 +255,8 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
                                                                        const int *__restrict__ counts, int num_loops,
                                                                        float thresh2, int refine_loops, float limit,
                                                                        float *__restrict__ head,
-                                                                       char *__restrict__ flags, PlanarBatch nb) {
+                                                                       char *__restrict__ flags,
+                                                                       float *__restrict__ errors, PlanarBatch nb) {
   __shared__ unsigned long long s_key[kPlanarThreads];
   __shared__ double s_part[kPlanarThreads / 64][kPlanarSums];
   __shared__ double s_sum[kPlanarSums];
@@ -248,13 +264,16 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
   __shared__ int s_cnt[kPlanarThreads];
   pts += (size_t)blockIdx.z * nb.records;
   coord = planar_pair(coord, nb.scratch), marks = planar_pair(marks, nb.scratch), homo = planar_pair(homo, nb.scratch);
-  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.scratch), flags = planar_pair(flags, nb.scratch);
+  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.head);
+  flags += (size_t)blockIdx.z * nb.flags;
+  if (errors) errors += (size_t)blockIdx.z * nb.flags;
   const float *__restrict__ cx1 = coord, *__restrict__ cy1 = coord + num_pts;
   const float *__restrict__ cx2 = coord + 2 * (size_t)num_pts, *__restrict__ cy2 = coord + 3 * (size_t)num_pts;
   const int tx = threadIdx.x;
   int *ihead = (int *)head;
+  const int n = planar_count(ihead, num_pts, nb);
   if (ihead[18] < 8) {  // uniform; extras/homography.cu:220: the identity, no inlier, the records stay as they are
-    for (int i = tx; i < num_pts; i += kPlanarThreads) flags[i] = 0;
+    for (int i = tx; i < n; i += kPlanarThreads) flags[i] = 0;
     if (tx < 18) head[tx] = (tx % 9 == 0 || tx % 9 == 4 || tx % 9 == 8) ? 1.0f : 0.0f;
     if (tx >= 19 && tx < 22) ihead[tx] = 0;
     return;
@@ -281,7 +300,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
     win[i] = homo[(size_t)i * num_loops + best];
     A[i] = (double)win[i];
   }
-  for (int i = tx; i < num_pts; i += kPlanarThreads)
+  for (int i = tx; i < n; i += kPlanarThreads)
     flags[i] = planar_inlier(A, win[2], win[5], (double)cx1[i], (double)cy1[i], (double)cx2[i], (double)cy2[i],
                              (double)thresh2)
                    ? 1
@@ -292,7 +311,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
     double s[kPlanarSums];
 #pragma unroll
     for (int q = 0; q < kPlanarSums; ++q) s[q] = 0.0;
-    for (int i = tx; i < num_pts; i += kPlanarThreads) {  // thread tx owns records tx, tx + 256, ...
+    for (int i = tx; i < n; i += kPlanarThreads) {  // thread tx owns records tx, tx + 256, ...
       if (!(marks[i] & 2)) continue;
       const float px = cx1[i], py = cy1[i], mx = cx2[i], my = cy2[i];
       const float err = planar_err(A, px, py, mx, my);
@@ -347,10 +366,13 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
   }
   // ---- match_error of every record, the number that fit (include/homography.h:131-140) ----
   int fit = 0;
-  for (int i = tx; i < num_pts; i += kPlanarThreads) {
+  for (int i = tx; i < n; i += kPlanarThreads) {
     const float err = planar_err(A, cx1[i], cy1[i], cx2[i], cy2[i]);
     fit += err < limit ? 1 : 0;
-    pts[i].match_error = sqrtf(err);
+    if (errors)
+      errors[i] = sqrtf(err);
+    else
+      pts[i].match_error = sqrtf(err);
   }
   s_cnt[tx] = fit;
   __syncthreads();

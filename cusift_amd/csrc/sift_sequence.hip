@@ -1,5 +1,6 @@
-// sift_sequence.hip -- the selection stage of the batched RGB-D registration (cusift_register_rgbd_batch): a batch of
-// frames and a pair list in, one [R | t] per pair out, in a fixed number of launches:
+// sift_sequence.hip -- the per-pair stages of the registrations of a whole sequence that read cusift_match_batch's rows.
+// The selection stage of the batched RGB-D registration (cusift_register_rgbd_batch): a batch of frames and a pair list
+// in, one [R | t] per pair out, in a fixed number of launches:
 //
 //   rgbd_lift_kernel           (sift_rgbd.hip)   coords3D of every frame, one launch
 //   match_batch_kernel         (sift_match.hip)  every pair's best / second-best, grid (row block, column split, pair)
@@ -13,6 +14,19 @@
 // per pair walks frame 1's records 256 at a time with a running base, ranks its keeps with ballot + mbcnt inside a wave
 // and a 4-entry scan across its waves: ascending record order, no atomics, the same output every run.  The record
 // counts come from device memory (frame_count); nothing is written past a pair's count.
+//
+// THE PLANAR MARKING (cusift_register_planar_batch) is planar_mark_kernel (sift_planar.hip) for every pair of a list in
+// one launch, grid (record block, 1, pair), reading the pair's match rows instead of the records' match fields:
+//
+//   match_batch_kernel (+ merge)  (sift_match.hip)   rows[pair][max_pts]
+//   sequence_mark_kernel          (here)             coord / marks / block counts of every pair, its count into its head
+//   planar_compact / homography_solve / planar_score / planar_select (sift_planar.hip, sift_homography.hip), blockIdx.z = pair
+//
+// Record i of pair (f1, f2) gives x1, y1 = its coords2D and x2, y2 = coords2D of record `match` of f2 -- of record 0 when
+// `match` is outside [0, n2), the value cusift_match puts into match_xpos / match_ypos (sift_match.hip) -- one 16-byte
+// row and two coords2D per record.  Candidates and the refit's set follow planar_mark_kernel's predicates with num_pts2
+// = n2.  A pair whose frame 2 is empty has no row (the matcher wrote none): no candidate, nothing read.  The records are
+// never written.
 // No scratch memory, vector stores only.
 #include "sift_device.h"
 
@@ -73,6 +87,57 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
     __syncthreads();  // s_wave is rewritten by the next chunk
   }
   if (tx == 0) sel_count[pair] = base;
+}
+
+// coord [pair][4][max_pts], marks [pair][max_pts], block_counts [pair][ceil(max_pts / 256)] in the pairs' scratch blocks
+// (nb.scratch bytes apart); head[kPlanarHeadCount] of pair p (nb.head bytes apart) = its record count
+__global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
+    const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
+    const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, int rule, float lo, float hi,
+    float *__restrict__ coord, unsigned char *__restrict__ marks, int *__restrict__ block_counts, int *__restrict__ head,
+    PlanarBatch nb) {
+  __shared__ int s_wave[kSequenceSelectThreads / 64];
+  const int tx = threadIdx.x;
+  const int pair = blockIdx.z;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
+  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
+  rows += (size_t)pair * max_pts;
+  coord = (float *)((char *)coord + (size_t)pair * nb.scratch);
+  marks = (unsigned char *)((char *)marks + (size_t)pair * nb.scratch);
+  block_counts = (int *)((char *)block_counts + (size_t)pair * nb.scratch);
+  head = (int *)((char *)head + (size_t)pair * nb.head);
+  const int i = blockIdx.x * kSequenceSelectThreads + tx;
+  bool cand = false;
+  if (i < n1) {
+    const float x1 = sift1[i].coords2D[0], y1 = sift1[i].coords2D[1];
+    float x2 = 0.0f, y2 = 0.0f;
+    bool fit = false;
+    if (n2 > 0) {
+      const f4 row = *reinterpret_cast<const f4 *>(rows + i);  // score, ambiguity, match, reserved
+      const float score = row[0], amb = row[1];
+      const int m = __float_as_int(row[2]);
+      const bool valid = m >= 0 && m < n2;
+      const cusift_point *q = sift2 + (valid ? m : 0);  // the partner cusift_match takes the position from
+      x2 = q->coords2D[0], y2 = q->coords2D[1];
+      cand = rule == 0 ? (score > lo && amb < hi) : (score < lo && amb < hi);
+      cand = cand && planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2) && valid;
+      fit = rule == 0 ? !(score < lo || amb > hi) : cand;  // as planar_mark_kernel
+    }
+    coord[i] = x1;
+    coord[i + max_pts] = y1;
+    coord[i + 2 * (size_t)max_pts] = x2;
+    coord[i + 3 * (size_t)max_pts] = y2;
+    marks[i] = (unsigned char)((cand ? 1 : 0) | (fit ? 2 : 0));
+  }
+  const unsigned long long mask = __ballot(cand);
+  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(mask);
+  __syncthreads();
+  if (tx == 0) {
+    block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    if (blockIdx.x == 0) head[kPlanarHeadCount] = n1;
+  }
 }
 
 }  // namespace cusift

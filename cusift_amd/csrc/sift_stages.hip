@@ -851,7 +851,8 @@ static int planar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int nu
                      (const int *)d_head, nb);
   hipLaunchKernelGGL(planar_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, (const float *)d_coord,
                      (const unsigned char *)d_marks, (const float *)d_homo, (const int *)d_counts, num_loops,
-                     thresh * thresh, refine_loops, refine_thresh * refine_thresh, d_head, d_flags, nb);
+                     thresh * thresh, refine_loops, refine_thresh * refine_thresh, d_head, d_flags, (float *)nullptr,
+                     nb);
   TRY(check_launch("estimate_homography"));
   // the one blocking read-back
   const bool all = o.h_drawn || o.h_all_homo || o.h_all_counts;
@@ -1292,6 +1293,107 @@ extern "C" int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_point
     h_num_matches[p] = (int)n;
     if (h_inliers) memcpy(h_inliers + p * M, back.data() + flag_off + p * M, n);
     if (h_sel_pairs) memcpy(h_sel_pairs + 2 * p * M, back.data() + pair_off + sizeof(int) * 2 * p * M, sizeof(int) * 2 * n);
+  }
+  return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// planar registration of a pair list (sift_sequence.hip, sift_planar.hip) -- one read-back
+// ------------------------------------------------------------------------------------------------
+extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                            int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                            int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                            float refine_thresh, uint64_t seed, float *h_homography, float *h_ransac,
+                                            int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
+                                            char *h_inliers, float *h_match_error) {
+  TRY(enter(ctx));
+  const PlanarOut o{h_homography, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
+                    h_inliers,    nullptr,  nullptr,          nullptr};
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "RegisterPlanarBatch"));
+  TRY(planar_check("RegisterPlanarBatch", d_points, n_images > 0 ? max_pts : 0, rule, lo, hi, num_loops, thresh,
+                   refine_loops, refine_thresh, o));
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterPlanarBatch: distance must be 0 or 1");
+  if (n_pairs == 0) return CUSIFT_OK;
+  const size_t P = (size_t)n_pairs, M = (size_t)max_pts, L = (size_t)num_loops;
+  if (max_pts == 0) {  // every frame is empty, known from the arguments alone
+    for (size_t p = 0; p < P; ++p) {
+      const PlanarOut one{h_homography + 9 * p,  h_ransac + 9 * p, h_num_candidates + p,
+                          h_num_matches + p,     h_num_fit + p,    h_best_loop ? h_best_loop + p : nullptr,
+                          nullptr,               nullptr,          nullptr,
+                          nullptr};
+      planar_identity(0, num_loops, one);
+    }
+    return CUSIFT_OK;
+  }
+  // [heads | flags | errors] is what travels back, in one copy; behind it what stays on the device: one block per pair
+  // [samples | hypotheses | counts | coordinates | candidates | marks | block counts], then the match rows
+  const int blocks = idiv_up(max_pts, 256);
+  const size_t head_b = align_up_sz(kPlanarHeadBytes * P, 256), flag_b = align_up_sz(P * M, 256);
+  const size_t err_b = align_up_sz(sizeof(float) * P * M, 256);
+  const size_t idx_b = align_up_sz(sizeof(int) * 4 * L, 256), homo_b = align_up_sz(sizeof(float) * 8 * L, 256);
+  const size_t cnt_b = align_up_sz(sizeof(int) * L, 256), coord_b = align_up_sz(sizeof(float) * 4 * M, 256);
+  const size_t cand_b = align_up_sz(sizeof(int) * M, 256), mark_b = align_up_sz(M, 256);
+  const size_t block_b = align_up_sz(sizeof(int) * (size_t)blocks, 256);
+  const size_t flag_off = head_b, err_off = flag_off + flag_b, pair_off = err_off + err_b;
+  const size_t homo_in = idx_b, cnt_in = homo_in + homo_b, coord_in = cnt_in + cnt_b, cand_in = coord_in + coord_b;
+  const size_t mark_in = cand_in + cand_b, block_in = mark_in + mark_b, pair_b = block_in + block_b;
+  const size_t row_off = pair_off + pair_b * P;
+  TRY(grow_scratch(ctx, ctx->sequence_scratch, ctx->sequence_scratch_bytes, row_off + sizeof(cusift_match_row) * P * M,
+                   "", false));
+  char *base = ctx->sequence_scratch, *first = base + pair_off;
+  float *d_head = (float *)base, *d_err = (float *)(base + err_off);
+  char *d_flags = base + flag_off;
+  int *d_idx = (int *)first, *d_counts = (int *)(first + cnt_in), *d_cand = (int *)(first + cand_in);
+  float *d_homo = (float *)(first + homo_in), *d_coord = (float *)(first + coord_in);
+  unsigned char *d_marks = (unsigned char *)(first + mark_in);
+  int *d_blocks = (int *)(first + block_in);
+  cusift_match_row *d_rows = (cusift_match_row *)(base + row_off);
+  PlanarBatch nb;
+  nb.records = 0, nb.scratch = pair_b, nb.head = kPlanarHeadBytes, nb.flags = M, nb.count = 1;
+  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
+  // scoring as planar_run, the splits sized from the capacity (the counts stay on the device) over all pairs
+  const int loop_blocks = idiv_up(num_loops, 64);
+  const long wgs = (long)loop_blocks * n_pairs;
+  int splits = (int)std::max(1L, std::min((8L * ctx->num_cus + wgs - 1) / wgs, (long)idiv_up(max_pts, 64)));
+  splits = std::min(splits, 65535);
+  const int pts_per_split = idiv_up(idiv_up(max_pts, splits), 64) * 64;
+  splits = idiv_up(max_pts, pts_per_split);
+  const int *d_pairs = nullptr;
+  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs));
+  hipLaunchKernelGGL(sequence_mark_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_points, d_counters,
+                     max_pts, d_pairs, (const cusift_match_row *)d_rows, rule, t_lo, t_hi, d_coord, d_marks, d_blocks,
+                     (int *)d_head, nb);
+  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream,
+                     (const unsigned char *)d_marks, max_pts, (const int *)d_blocks, d_cand, (int *)d_head, nb);
+  hipLaunchKernelGGL(homography_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream,
+                     (const float *)d_coord, max_pts, d_idx, num_loops, d_homo, 1, (unsigned long long)seed,
+                     (const int *)d_cand, (const int *)d_head + 18, d_counts, nb);
+  hipLaunchKernelGGL(planar_score_kernel, dim3(loop_blocks, splits, n_pairs), dim3(64), 0, ctx->stream,
+                     (const float *)d_coord, max_pts, pts_per_split, (const float *)d_homo, num_loops, thresh * thresh,
+                     d_counts, (const int *)d_head, nb);
+  hipLaunchKernelGGL(planar_select_kernel, dim3(1, 1, n_pairs), dim3(256), 0, ctx->stream, (cusift_point *)nullptr,
+                     max_pts, (const float *)d_coord, (const unsigned char *)d_marks, (const float *)d_homo,
+                     (const int *)d_counts, num_loops, thresh * thresh, refine_loops, refine_thresh * refine_thresh,
+                     d_head, d_flags, d_err, nb);
+  TRY(check_launch("register_planar_batch"));
+  // the one blocking read-back
+  std::vector<char> back(h_match_error ? err_off + sizeof(float) * P * M
+                                       : (h_inliers ? flag_off + P * M : kPlanarHeadBytes * P));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (size_t p = 0; p < P; ++p) {  // the kernels decided every pair, the degenerate ones included: copies only
+    const char *head = back.data() + kPlanarHeadBytes * p;
+    int tail[5];  // candidates, matches, fit, loop, records of frame 1
+    memcpy(tail, head + sizeof(float) * 18, sizeof(tail));
+    const size_t n = (size_t)std::min(std::max(tail[4], 0), max_pts);
+    memcpy(h_homography + 9 * p, head, sizeof(float) * 9);
+    memcpy(h_ransac + 9 * p, head + sizeof(float) * 9, sizeof(float) * 9);
+    h_num_candidates[p] = tail[0], h_num_matches[p] = tail[1], h_num_fit[p] = tail[2];
+    if (h_best_loop) h_best_loop[p] = tail[3];
+    if (h_inliers) memcpy(h_inliers + p * M, back.data() + flag_off + p * M, n);
+    // a pair without a fit has no error, as the pair call leaves match_error alone then
+    if (h_match_error && tail[0] >= 8)
+      memcpy(h_match_error + p * M, back.data() + err_off + sizeof(float) * p * M, sizeof(float) * n);
   }
   return CUSIFT_OK;
 }

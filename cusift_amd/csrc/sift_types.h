@@ -151,10 +151,17 @@ struct RigidBatch {
 };
 
 // between consecutive pairs of a batched planar registration (blockIdx.z of the planar_* kernels and of the drawing
-// homography_solve_kernel): records between the pairs' record arrays, bytes between their scratch blocks; 0 for one pair
+// homography_solve_kernel); all 0 for one pair.  records: records between the pairs' record arrays; scratch: bytes
+// between their device-only blocks (samples, hypotheses, counts, coordinates, candidates, marks, block counts); head:
+// bytes between their result heads; flags: entries between their inlier flags and between their match errors.
+// count != 0: the kernels' num_pts is the CAPACITY of a pair (the stride of its coordinate rows) and its number of
+// points is word kPlanarHeadCount of its head, written by sequence_mark_kernel (as RigidBatch::count).
 struct PlanarBatch {
-  size_t records, scratch;
+  size_t records, scratch, head, flags;
+  int count;
 };
+constexpr int kPlanarHeadCount = 22;                  // a head: H[9], R[9], n_cand, matches, fit, loop, then the count
+constexpr size_t kPlanarHeadBytes = 128;              // between the heads of a batch
 
 static_assert(sizeof(cusift_point) == 588, "SiftPoint is a 588-byte ABI record (cuSIFT.h:10-30)");
 

@@ -240,6 +240,44 @@ int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_points, const un
                                int *h_num_matches, int *h_num_inliers, int *h_sel_pairs /* may be NULL */,
                                char *h_inliers /* may be NULL */);
 
+/* cusift_register_planar for every pair of a list: the extractor's batch and a pair list in, one homography per pair out,
+ * in a number of launches that does not depend on n_pairs and with no host decision between the stages.  Pair p = (a, b)
+ * maps frame a's coords2D onto frame b: h_homography[9 p .. 9 p + 8] (refined), h_ransac[9 p .. 9 p + 8] (the winner).
+ * The records per frame are min(d_counters[frame], max_pts), read on the device (d_counters == NULL: max_pts each); no
+ * count reaches the host before the one read-back.  A frame may appear in any number of pairs, on either side; (a, a) is
+ * legal.  Pair p draws from seed + p (64-bit, wrapping).
+ * STAGES: cusift_match_batch into rows in the context's scratch; a marking kernel that builds each pair's coordinates,
+ * candidates and refit set from its rows and from coords2D of frame a's records and of their partners in frame b (the
+ * value cusift_match puts into match_xpos / match_ypos); then the compaction, the drawing solver, the scoring and the
+ * selection + refit of cusift_estimate_homography with one grid layer per pair.
+ * THE RECORDS ARE NEVER WRITTEN.  match_error = sqrtf(err) of every record of frame a goes to h_match_error
+ * ([n_pairs][max_pts], may be NULL) and the winner's inlier flags to h_inliers ([n_pairs][max_pts], may be NULL): the
+ * first count_a entries of pair p's block, the rest of a block is not written.
+ * EQUALITY: every output of pair p has the bits of the staged route -- pair p's row of cusift_match_batch scattered into a
+ * copy of frame a's records (score, ambiguity, match, match_xpos / match_ypos = the partner's coords2D), then
+ * cusift_estimate_homography(copy, count_a, count_b, rule, lo, hi, ..., seed + p); h_match_error is the match_error that
+ * call writes.  Where the rows equal what cusift_match writes (cusift_match_batch documents the one licence to differ:
+ * exactly tied best scores) these are the bits of cusift_register_planar(frame a, frame b, ..., seed + p).
+ * DEGENERATE PAIRS are decided on the device and disturb no other pair: count_a < 8 -- identity in both matrices, every
+ * count 0, h_num_candidates[p] = 0; fewer than 8 candidates -- identity, counts 0, h_num_candidates[p] as counted;
+ * count_b == 0 -- no row exists, 0 candidates.  Their flags are 0 and their block of h_match_error is not written (the
+ * pair call leaves match_error alone).
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of cusift_register_planar -- a NULL h_homography /
+ * h_ransac / h_num_candidates / h_num_matches / h_num_fit, num_loops < 1, thresh or refine_thresh not > 0, a NaN lo / hi,
+ * an unknown rule or distance, refine_loops < 0, missing buffers -- and: a pair index outside [0, n_images), n_pairs or
+ * n_images outside [0, 65535], max_pts outside [0, 2^20], a NULL h_pairs with n_pairs > 0.  n_pairs == 0: CUSIFT_OK,
+ * nothing enqueued.  Scratch lives in the context and grows on demand.
+ * Blocking: ONE stream synchronisation, at the one read-back. */
+int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point *d_points,
+                                 const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                                 const int *h_pairs /* [n_pairs][2]: (frame a, frame b) */, int n_pairs, int distance,
+                                 int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                 float refine_thresh, uint64_t seed, float *h_homography /* [n_pairs][9] */,
+                                 float *h_ransac /* [n_pairs][9] */, int *h_num_candidates, int *h_num_matches,
+                                 int *h_num_fit, int *h_best_loop /* may be NULL */,
+                                 char *h_inliers /* [n_pairs][max_pts], may be NULL */,
+                                 float *h_match_error /* [n_pairs][max_pts], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,12 +11,14 @@
 // EstimateHomography and RegisterPlanar are the same chain without the host in it (cusift_estimate_homography /
 // cusift_register_planar, cusift_amd_extras.h): candidates, samples drawn from a seed, hypotheses, counts, selection
 // and the refit all run on the device, with one synchronisation; the same seed gives the same bits.
+// RegisterPlanarSequence is RegisterPlanar for every pair of a list in one call (cusift_register_planar_batch).
 #ifndef CUSIFT_AMD_HOMOGRAPHY_H
 #define CUSIFT_AMD_HOMOGRAPHY_H
 
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "cuSIFT.h"
@@ -185,6 +187,76 @@ inline double RegisterPlanar(SiftData &data1, SiftData &data2, float *homography
                                   minScore, maxAmbiguity, numLoops, thresh, refineLoops, refineThresh, seed, homography,
                                   ransac ? ransac : winner, &numCandidates, numMatches, numFit, nullptr, nullptr,
                                   nullptr, nullptr, nullptr));
+  return timer.read();
+}
+
+// RegisterPlanar for a whole sequence in one call (cusift_register_planar_batch): pair k = (a, b) of `pairs` maps frame
+// a's image onto frame b's, homographies[9 k .. 9 k + 8]; an empty `pairs` means (i, i + 1) for every consecutive frame.
+// The frames' device records are packed into one [n][maxPts] block with device-to-device copies (maxPts = the largest
+// numPts) and every pair is matched, marked, drawn, scored and refitted in the same launches, with one synchronisation.
+// Pair k draws from seed + k, so every pair has the bits RegisterPlanar gives for it with that seed (numLoops is rounded
+// up to 16 in the same way).  A frame may be in any number of pairs, on either side.  The frames themselves are NOT
+// written: what RegisterPlanar leaves in data1's records arrives in the outputs -- matchErrors[k][i] is match_error of
+// record i of frame a (empty for a pair without a fit), inliers[k][i] the winner's flag.  ransac (optional): the
+// winning hypotheses before the refit, [9 k .. 9 k + 8].  Returns the elapsed milliseconds.
+inline double RegisterPlanarSequence(std::vector<SiftData *> &frames, std::vector<std::pair<int, int> > pairs,
+                                     std::vector<float> &homographies, std::vector<int> *numMatches = NULL,
+                                     std::vector<int> *numFit = NULL, int numLoops = 10000, float minScore = 0.0f,
+                                     float maxAmbiguity = 0.8f, float thresh = 5.0f, int refineLoops = 5,
+                                     float refineThresh = 3.0f, uint64_t seed = 0, int distance = 0, int rule = 0,
+                                     std::vector<float> *ransac = NULL,
+                                     std::vector<std::vector<float> > *matchErrors = NULL,
+                                     std::vector<std::vector<char> > *inliers = NULL) {
+  TimerGPU timer;
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  numLoops = iDivUp(numLoops, 16) * 16;  // extras/homography.cu:200
+  const int n = (int)frames.size();
+  if (pairs.empty())
+    for (int i = 0; i + 1 < n; i++) pairs.push_back(std::make_pair(i, i + 1));
+  const int n_pairs = (int)pairs.size();
+  int max_pts = 1;
+  std::vector<unsigned int> counts((size_t)(n > 0 ? n : 1), 0u);
+  for (int i = 0; i < n; i++) {
+    counts[i] = frames[i]->d_data != nullptr && frames[i]->numPts > 0 ? (unsigned int)frames[i]->numPts : 0u;
+    if ((int)counts[i] > max_pts) max_pts = (int)counts[i];
+  }
+  struct block {
+    void *ptr = nullptr;
+    explicit block(size_t bytes) { safeCall(cusift_malloc(&ptr, bytes > 0 ? bytes : 1)); }
+    ~block() { cusift_free(ptr); }
+    block(const block &) = delete;
+    block &operator=(const block &) = delete;
+  };
+  block points(sizeof(SiftPoint) * (size_t)n * (size_t)max_pts), counters(sizeof(unsigned int) * counts.size());
+  safeCall(cusift_memcpy_h2d(ctx, counters.ptr, counts.data(), sizeof(unsigned int) * counts.size()));
+  for (int i = 0; i < n; i++)
+    if (counts[i] > 0)
+      safeCall(cusift_memcpy_d2d(ctx, static_cast<SiftPoint *>(points.ptr) + (size_t)i * max_pts, frames[i]->d_data,
+                                 sizeof(SiftPoint) * (size_t)counts[i]));
+  const size_t slots = (size_t)(n_pairs > 0 ? n_pairs : 1);
+  std::vector<int> h_pairs(2 * slots), candidates(slots), matches(slots), fit(slots);
+  for (int k = 0; k < n_pairs; k++) h_pairs[2 * (size_t)k] = pairs[k].first, h_pairs[2 * (size_t)k + 1] = pairs[k].second;
+  std::vector<float> hom(9 * slots), win(9 * slots);
+  std::vector<char> h_flags(inliers ? (size_t)n_pairs * max_pts : 0);
+  std::vector<float> h_err(matchErrors ? (size_t)n_pairs * max_pts : 0);
+  safeCall(cusift_register_planar_batch(ctx, static_cast<const cusift_point *>(points.ptr),
+                                        static_cast<const unsigned int *>(counters.ptr), n, max_pts, h_pairs.data(),
+                                        n_pairs, distance, rule, minScore, maxAmbiguity, numLoops, thresh, refineLoops,
+                                        refineThresh, seed, hom.data(), win.data(), candidates.data(), matches.data(),
+                                        fit.data(), NULL, inliers ? h_flags.data() : NULL,
+                                        matchErrors ? h_err.data() : NULL));
+  homographies.assign(hom.begin(), hom.begin() + 9 * (size_t)n_pairs);
+  if (ransac) ransac->assign(win.begin(), win.begin() + 9 * (size_t)n_pairs);
+  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + n_pairs);
+  if (numFit) numFit->assign(fit.begin(), fit.begin() + n_pairs);
+  if (inliers) inliers->assign((size_t)n_pairs, std::vector<char>());
+  if (matchErrors) matchErrors->assign((size_t)n_pairs, std::vector<float>());
+  for (int k = 0; k < n_pairs; k++) {
+    const size_t first = (size_t)k * max_pts, count = counts[pairs[k].first];
+    if (inliers) (*inliers)[k].assign(h_flags.begin() + first, h_flags.begin() + first + count);
+    if (matchErrors && candidates[k] >= 8)
+      (*matchErrors)[k].assign(h_err.begin() + first, h_err.begin() + first + count);
+  }
   return timer.read();
 }
 
