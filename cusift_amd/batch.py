@@ -16,9 +16,12 @@ class BatchExtractor:
     allocation, no host read-back -- and returns device tensors:
         points  uint8  [n, max_pts, 588]   (SiftPoint records, cuSIFT.h:10-30)
         counts  int32  [n]                 raw counters; valid points = min(count, max_pts)
+    keep_strongest = K > 0: every image keeps its K strongest keypoints (cusift_ctx_set_keep_strongest; K <= max_pts),
+    selected on the device before anything is described; counts are then the kept counts.
     """
 
-    def __init__(self, n_images, w, h, params=None, device=None, pitch=None, n_slots=1, **param_overrides):
+    def __init__(self, n_images, w, h, params=None, device=None, pitch=None, n_slots=1, keep_strongest=0,
+                 **param_overrides):
         if not torch.cuda.is_available():
             raise capi.CusiftError("BatchExtractor needs a GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -26,9 +29,12 @@ class BatchExtractor:
         self.pitch = capi.ialign_up(self.w, 128) if pitch is None else int(pitch)
         self.params = params if params is not None else capi.default_params(**param_overrides)
         self.max_pts = self.params.max_pts
+        self.keep_strongest = capi.check_keep_strongest(keep_strongest, self.max_pts)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream()
             self.ctx = capi.Context(self.device.index, stream=self.stream.cuda_stream)
+            if self.keep_strongest:
+                self.ctx.set_keep_strongest(self.keep_strongest)
             self.ctx.reserve(self.n, self.w, self.h, self.params)
             # n_slots > 1: output ring, so that a consumer (D2H copy, all-gatherv on another stream) can still
             # read step i's SiftData while step i+1 is being extracted

@@ -164,6 +164,7 @@ SIGNATURES = {
     "cusift_pipe_in_flight": (_i, [_vp]),
     "cusift_pipe_destroy": (_i, [_vp]),
     "cusift_ctx_set_policy": (_i, [_vp, _i, _i]),
+    "cusift_ctx_set_keep_strongest": (_i, [_vp, _i]),
     "cusift_ctx_get_policy": (_i, [_vp, _i, C.POINTER(C.c_int)]),
     "cusift_ctx_arena_bytes": (_sz, [_vp]),
     "cusift_ctx_forks": (C.c_ulong, [_vp]),
@@ -211,6 +212,7 @@ SIGNATURES = {
                                    _vp, _vp]),
     "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
     "cusift_select_matches": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
+    "cusift_select_strongest": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "cusift_register_rgbd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(Camera), _i, _f, _f, _i, _f, _i,
                                   C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
     "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
@@ -377,6 +379,32 @@ def check_scale_up_args(d_dst, dst_pitch, d_src, w, h, src_pitch, n_images=1, ds
     if n_images > 1 and (src_stride < h * int(src_pitch) or dst_stride < 2 * h * int(dst_pitch)):
         raise ValueError("scale_up: image stride too small")
     return dst_stride, src_stride
+
+
+def check_keep_strongest(k, max_pts=None):
+    """What Context.set_keep_strongest checks before it calls the library (needs no device): returns K as an int.
+    ValueError for K < 0, a K that is no integer, or (max_pts given) K > max_pts, which the next extraction would refuse."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("keep_strongest: K must be an integer, got %r" % (k,))
+    if k < 0 or k > 0x7fffffff:
+        raise ValueError("keep_strongest: K must be >= 0 (0 = off), got %d" % k)
+    if max_pts is not None and k > max_pts:
+        raise ValueError("keep_strongest: K = %d exceeds max_pts = %d" % (k, max_pts))
+    return int(k)
+
+
+def check_select_strongest_args(d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
+    """What Context.select_strongest checks before it calls the library (needs no device).  ValueError for anything
+    cusift_select_strongest would refuse."""
+    if not d_heads or not d_counts or not d_kept:
+        raise ValueError("select_strongest: missing data")
+    if not (1 <= n_lists <= 16 and 1 <= n_images <= 65535 and capacity >= 1):
+        raise ValueError("select_strongest: bad geometry lists=%d (1..16) images=%d (1..65535) capacity=%d"
+                         % (n_lists, n_images, capacity))
+    if keep < 1 or keep > 0x7fffffff:
+        raise ValueError("select_strongest: keep must be >= 1, got %d" % keep)
+    if n_lists * capacity > 0x7fffffff or n_images * n_lists * capacity > 1 << 32:
+        raise ValueError("select_strongest: %d lists x %d images x %d heads are too many" % (n_lists, n_images, capacity))
 
 
 def pair_list(pairs):
@@ -741,6 +769,20 @@ class Context:
         image_stride = h * pitch if image_stride is None else image_stride
         check(lib().cusift_lift_depth(self.handle, d_points, d_counters, n_images, max_pts, d_depth, w, h, pitch,
                                       image_stride, C.byref(camera)))
+
+    def set_keep_strongest(self, k):
+        """cusift_ctx_set_keep_strongest: every later extraction on this context (and every graph recorded from now on)
+        keeps the K strongest keypoints per image, selected on the device before they are described; 0 turns it off.
+        K > max_pts is refused by the extraction."""
+        k = check_keep_strongest(k)
+        check(lib().cusift_ctx_set_keep_strongest(self.handle, k))
+
+    def select_strongest(self, d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
+        """cusift_select_strongest: the selection alone, on lists of 64-byte record heads.  d_heads [n_lists, n_images,
+        capacity, 64 B], d_counts uint32 [n_lists, n_images] (in: held, out: kept) and d_kept uint32 [n_images] are
+        device pointers.  Asynchronous."""
+        check_select_strongest_args(d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept)
+        check(lib().cusift_select_strongest(self.handle, d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept))
 
     def select_matches(self, d_sift1, n1, d_sift2, n2, d_pairs, d_coord, d_count, score_threshold=999.0,
                        ambiguity_threshold=1.0, kind="3d"):

@@ -363,6 +363,15 @@ extern "C" int cusift_ctx_set_policy(cusift_ctx *ctx, int key, int value) {
   return fail(CUSIFT_ERR_INVALID, "unknown policy key %d", key);
 }
 
+// Sticky per context, read by resolve_plan (sift_driver.hip) on every extraction; K against max_pts is checked there.
+extern "C" int cusift_ctx_set_keep_strongest(cusift_ctx *ctx, int k) {
+  if (!ctx) return fail(CUSIFT_ERR_INVALID, "ctx is NULL");
+  if (k < 0) return fail(CUSIFT_ERR_INVALID, "keep_strongest: K must be >= 0 (0 = off), got %d", k);
+  ctx->keep_strongest = k;
+  return CUSIFT_OK;
+}
+int cusift_keep_strongest_of(const cusift_ctx *ctx) { return ctx ? ctx->keep_strongest : 0; }
+
 extern "C" int cusift_ctx_get_policy(cusift_ctx *ctx, int key, int *value) {
   if (!ctx || !value) return fail(CUSIFT_ERR_INVALID, "ctx / value is NULL");
   const Knobs &k = ctx->knobs;

@@ -176,6 +176,17 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
     return fail(CUSIFT_ERR_INVALID, "bad geometry n=%d w=%d h=%d pitch=%d", n_images, w, h, pitch);
   if (n_images > 65535) return fail(CUSIFT_ERR_INVALID, "at most 65535 images per batch (grid.z), got %d", n_images);
   if (prm->max_pts < 1) return fail(CUSIFT_ERR_INVALID, "max_pts must be >= 1");
+  // Keep the K strongest keypoints per image (cusift_ctx_set_keep_strongest; sift_select.hip): the selection works on the
+  // staged heads, so such a call takes a list per octave whatever the policy or the size of the call says -- or is refused.
+  pl.keep = ctx->keep_strongest;
+  if (pl.keep < 0 || pl.keep > prm->max_pts)
+    return fail(CUSIFT_ERR_INVALID, "keep_strongest: K = %d must lie in 0 .. max_pts = %d", pl.keep, prm->max_pts);
+  if (pl.keep && !prm->fused_detect)
+    return fail(CUSIFT_ERR_INVALID, "keep_strongest: needs the keypoint lists of fused_detect = 1");
+  if (pl.keep && ctx->knobs.force_generic)
+    return fail(CUSIFT_ERR_INVALID, "keep_strongest: needs the keypoint lists, which CUSIFT_POLICY_GENERIC_KERNELS rules out");
+  if (pl.keep && n_images > kMaxFlatImages)
+    return fail(CUSIFT_ERR_INVALID, "keep_strongest: at most %d images per call, got %d", kMaxFlatImages, n_images);
   int n = std::max(1, std::min(prm->num_octaves, kMaxOctaves));
   pl.upsample = prm->upsample != 0;
   if (pl.upsample) {
@@ -219,14 +230,26 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
   off = align_up_sz(off + (size_t)n_images * kMaxOctaves * sizeof(unsigned int), 256);
   const size_t per_octave = (size_t)n_images * prm->max_pts * kStagedRecBytes;
   pl.fork = wants_side_stream(ctx, prm, n_images, w, h) && pl.n_oct >= 2 && per_octave <= kMaxStagedBytes;
-  const bool lists = wants_stage_all(ctx, prm, n_images, w, h) && pl.n_oct >= 2 && per_octave * pl.n_oct <= kMaxStagedAllBytes;
+  if (pl.keep && per_octave * pl.n_oct > kMaxStagedAllBytes)
+    return fail(CUSIFT_ERR_INVALID, "keep_strongest: the keypoint lists (%d octaves x %d images x max_pts %d heads) exceed %zu bytes",
+                pl.n_oct, n_images, prm->max_pts, kMaxStagedAllBytes);
+  const bool lists = pl.keep ? true
+                             : wants_stage_all(ctx, prm, n_images, w, h) && pl.n_oct >= 2 &&
+                                   per_octave * pl.n_oct <= kMaxStagedAllBytes;
   pl.staged_octaves = lists ? pl.n_oct : (pl.fork ? 1 : 0);
   if (pl.staged_octaves) {
     pl.staged_off = off;
     off = align_up_sz(off + per_octave * pl.staged_octaves, 256);
   }
+  if (pl.keep) {
+    pl.select_off = off;
+    off = align_up_sz(off + select_scratch_bytes(pl.n_oct, n_images, prm->max_pts), 256);
+  }
   pl.total = off;
   resolve_launches(pl, ctx, prm, true);
+  if (pl.keep && !pl.stage_all)
+    return fail(CUSIFT_ERR_INVALID, "keep_strongest: an octave of this %dx%d call (pitch %d) is not one the fused detection takes, "
+                "so its keypoints have no list", w, h, pitch);
   return CUSIFT_OK;
 }
 
@@ -383,6 +406,10 @@ extern "C" int cusift_extract_batch(cusift_ctx *ctx, const float *d_imgs, int n_
     if (rc_main == CUSIFT_OK) HIP_TRY(e);
   }
   if (rc_main != CUSIFT_OK || !pl.flat) return rc_main;
+  // keep_strongest: every detection has appended; the lists shrink to the kept heads and their counters to the kept
+  // counts before anything joins or describes them (three launches on this stream, whatever the images hold)
+  if (pl.keep)
+    TRY(select_strongest_impl(ctx, G, n_images, prm->max_pts, pl.keep, ctx->arena + pl.select_off, nullptr));
   OctaveTable T;
   memset(&T, 0, sizeof(T));
   T.n_oct = pl.n_oct;

@@ -4,6 +4,7 @@
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, matcher, homography, rigid
 //                     transform, RGB-D registration, packing)
+//   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 #pragma once
@@ -194,6 +195,7 @@ struct cusift_ctx {
   bool side_failed = false;  // no stream was found that runs beside the context's stream: never fork
   bool side_probed = false;  // `side` passed the concurrency probe (policy value 2 accepts no other)
   bool recording = false;  // inside cusift_graph_create's capture
+  int keep_strongest = 0;  // cusift_ctx_set_keep_strongest: K > 0, every extraction keeps the K strongest keypoints per image
   unsigned long forks = 0;  // extractions that took the side stream
   // the lists' counters in the arena that the last extraction's join_counts_kernel left zero (stream order): the next
   // extraction that uses exactly them skips its memset.  Anything else that writes the arena resets this.
@@ -268,6 +270,9 @@ struct Plan {
   // staged_octaves == 0: none; 1: octave 0's (searched on the side stream); n_oct: every octave's
   size_t staged_off = 0, seg_end_off = 0;
   int staged_octaves = 0;
+  // keep_strongest = K > 0: the selection's scratch (sift_select.hip) behind the lists; it runs after the last detection
+  int keep = 0;
+  size_t select_off = 0;
   bool fork = false;     // the layout has octave 0's list for the side stream (stays set when no side stream is found)
   size_t dog_bytes = 0;  // DoG planes of the largest kTwoStage octave (0: none)
   // the launch sequence
@@ -332,6 +337,9 @@ int detect_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, si
                 bool heads = false, bool side = false, const DownOut *down = nullptr);
 int detect_multi_impl(cusift_ctx *ctx, const MultiOctave *octaves, int n_octaves, float peak_thresh, float edge_thresh,
                       int max_pts, int n_images, int concurrent, unsigned int *d_queue);
+size_t select_scratch_bytes(int n_lists, int n_images, int capacity);
+int select_strongest_impl(cusift_ctx *ctx, const SegmentTable &G, int n_images, int capacity, int keep, char *scratch,
+                          unsigned int *d_kept);
 int descriptors_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride,
                      cusift_point *d_points, int max_pts, const unsigned int *d_first, const unsigned int *d_counters,
                      float subsampling, int tex_frac_bits, int n_images, RowWindow rw, int root_sift = 0,

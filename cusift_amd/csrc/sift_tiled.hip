@@ -177,6 +177,9 @@ extern "C" int cusift_tiled_plan(int W, int H, int world, int num_octaves, int h
 // ------------------------------------------------------------------------------------------------
 // one rank
 // ------------------------------------------------------------------------------------------------
+// (the strongest K of a strip are not the strip's share of the image's strongest K)
+static const char kTiledKeepStrongest[] =
+    "tiled: the context keeps the strongest keypoints per image (cusift_ctx_set_keep_strongest), which is not tiled; set it to 0";
 extern "C" int cusift_tiled_create(cusift_tiled **out, cusift_ctx *ctx, cusift_comm *comm, int rank, int world, int W,
                                    int H, const cusift_params *prm, int halo_rows) {
   if (!out) return cusift_fail(CUSIFT_ERR_INVALID, "out is NULL");
@@ -185,6 +188,7 @@ extern "C" int cusift_tiled_create(cusift_tiled **out, cusift_ctx *ctx, cusift_c
   if (rank < 0 || rank >= world) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: bad rank %d of %d", rank, world);
   if (prm->max_pts < 1) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: max_pts must be >= 1");
   if (prm->upsample) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: upsample = 1 (octave -1) is not tiled; enlarge the strips' image first");
+  if (cusift_keep_strongest_of(ctx)) return cusift_fail(CUSIFT_ERR_INVALID, kTiledKeepStrongest);
   if (comm) {
     int cr = -1, cw = -1;
     TRY(cusift_comm_rank(comm, &cr, &cw));
@@ -404,6 +408,7 @@ extern "C" int cusift_tiled_exchange_virtual(cusift_tiled **ranks, int n, int o)
 extern "C" int cusift_tiled_process(cusift_tiled *t, cusift_point *d_points, unsigned int *d_counter) {
   TRY(tiled_enter(t));
   if (!d_points || !d_counter) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: missing output");
+  if (cusift_keep_strongest_of(t->ctx)) return cusift_fail(CUSIFT_ERR_INVALID, kTiledKeepStrongest);
   const StripPlan &pl = t->pl;
   const cusift_params &p = t->prm;
   HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned int), t->stream));  // cuSIFT.cu:69

@@ -354,11 +354,16 @@ class SiftData {
   // subsampling 0.5 * the call's.  Meant for initBlur <= 0.5.  Trailing field, default false: source-compatible, the
   // layout of the reference's members is unchanged.  (initSubsampling stays unread, as in the reference.)
   bool scaleUp;
+  // new: keep only the keepStrongest strongest keypoints of the image (by |sharpness|; ties: the coarser octave, then y,
+  // x, scale -- cusift_ctx_set_keep_strongest), selected on the device before anything is described.  0 (default): all,
+  // up to maxPts.  At most maxPts.  Handed to the calling thread's context on every Extract.  Trailing field, default 0.
+  int keepStrongest;
 
   // cuSIFT.cu:13-32
   explicit SiftData(int maxPts_ = 1024, bool host = false, bool dev = false)
       : numPts(0), maxPts(0), h_data(nullptr), d_data(nullptr), numOctaves(5), numScales(5), initBlur(0.0),
-        initSubsampling(1.0f), peakThresh(0.1f), edgeThresh(10.0f), lowestScale(0.0f), rootSift(false), scaleUp(false) {
+        initSubsampling(1.0f), peakThresh(0.1f), edgeThresh(10.0f), lowestScale(0.0f), rootSift(false), scaleUp(false),
+        keepStrongest(0) {
     allocate(maxPts_, host, dev);
   }
   ~SiftData() { release(); }
@@ -387,6 +392,7 @@ class SiftData {
     CUSIFT_REPORT_TIMER(timer);
     require_device("Extract");
     cusift_params p = params(subsampling);
+    safeCall(cusift_ctx_set_keep_strongest(cusift_dropin::ctx(), keepStrongest));
     safeCall(cusift_extract_host(cusift_dropin::ctx(), im, width, height, &p, as_c(d_data), as_c(h_data), &numPts));
     report(CUSIFT_REPORT_READ(timer));
   }
@@ -400,6 +406,7 @@ class SiftData {
       return;
     }
     cusift_params p = params(subsampling);
+    safeCall(cusift_ctx_set_keep_strongest(cusift_dropin::ctx(), keepStrongest));
     safeCall(cusift_extract(cusift_dropin::ctx(), img.d_data, img.width, img.height, img.pitch, &p, as_c(d_data),
                             as_c(h_data), &numPts));
     report(CUSIFT_REPORT_READ(timer));
@@ -485,9 +492,10 @@ inline double ScaleDown(cuImage &res, cuImage &src, float variance) {
 // commented bodies at cuSIFT.cu:123-134,272-303).  edgeThresh has no legacy argument: 10.0 as everywhere.
 inline void InitSiftData(SiftData &data, int num, bool host, bool dev) { data.allocate(num, host, dev); }
 inline void FreeSiftData(SiftData &data) { data.release(); }
-// scaleUp (new, trailing, default false): SiftData::scaleUp for this call.
-inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double initBlur, float thresh,
-                        float lowestScale = 0.0f, float subsampling = 1.0f, bool scaleUp = false) {
+// scaleUp (new, trailing, default false): SiftData::scaleUp for this call.  keepStrongest (new, trailing, 0 when left
+// out): SiftData::keepStrongest for this call -- the form with it is an overload, the shorter one hands on 0.
+inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double initBlur, float thresh, float lowestScale,
+                        float subsampling, bool scaleUp, int keepStrongest) {
   siftData.numOctaves = numOctaves;
   siftData.initBlur = initBlur;
   siftData.peakThresh = thresh;
@@ -495,7 +503,12 @@ inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double
   siftData.edgeThresh = 10.0f;
   siftData.rootSift = false;
   siftData.scaleUp = scaleUp;
+  siftData.keepStrongest = keepStrongest;
   siftData.Extract(img, subsampling);
+}
+inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double initBlur, float thresh,
+                        float lowestScale = 0.0f, float subsampling = 1.0f, bool scaleUp = false) {
+  ExtractSift(siftData, img, numOctaves, initBlur, thresh, lowestScale, subsampling, scaleUp, 0);
 }
 // The reference's ExtractRootSift is commented out ("TODO: bring rootsift back", cuSIFT.cu:122-134: ExtractSift,
 // then ConvertSiftToRootSift, then Synchronize; its argument list lost thresh/lowestScale).  Same result in one

@@ -8,11 +8,11 @@
  * (SiftPoint / SiftData / cuImage / ExtractSift ...) on top of exactly these functions; Python binds
  * them with ctypes (cusift_amd/capi.py).  See INTEGRATION.md.
  *
- * Map of the C ABI (112 entry points in four headers; cusift_amd_all.h includes them all):
- *   cusift_amd.h (THIS FILE, 47): the drop-in boundary -- everything include/cuSIFT.h is built on (process / device,
+ * Map of the C ABI (114 entry points in four headers; cusift_amd_all.h includes them all):
+ *   cusift_amd.h (THIS FILE, 48): the drop-in boundary -- everything include/cuSIFT.h is built on (process / device,
  *     context, device memory helpers, cusift_extract / _extract_host / _scale_down / _scale_up / _rootsift / _sort_points_host,
  *     cusift_event_* for TimerGPU), the batch driver a throughput caller needs (cusift_extract_batch, cusift_graph_*,
- *     cusift_ctx_wait / _reserve / _set_policy) and the host-to-host pipeline (cusift_pipe_*).
+ *     cusift_ctx_wait / _reserve / _set_policy / _set_keep_strongest) and the host-to-host pipeline (cusift_pipe_*).
  *   cusift_amd_stages.h: one entry point per kernel of the reference (LaplaceMulti, FindPointsMulti, the fused
  *     detection, ComputeOrientations, ExtractSiftDescriptors ...), the caller-side front-end (8-bit frames, 3 x 3
  *     pre-blur), the stage timers and other diagnostics -- for callers that drive the stages themselves and for the
@@ -20,7 +20,7 @@
  *   cusift_amd_multigpu.h: SiftData on the wire (pack / trimmed / compact records), the communicator over RCCL, the
  *     all-gatherv of SiftData, halo exchange, the strip tiling of one large image over the ranks and its band kernels.
  *   cusift_amd_extras.h: the next rows of SURVEY 8f -- cusift_match, cusift_find_homography,
- *                        cusift_estimate_homography, cusift_register_planar, cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd.
+ *                        cusift_estimate_homography, cusift_register_planar, cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd, cusift_select_strongest.
  *
  * Conventions
  *  - every function returns CUSIFT_OK (0) or a negative cusift_status; cusift_last_error() gives text.
@@ -172,6 +172,29 @@ enum {
  * cusift_graph refuses to replay after such a re-allocation.) */
 int cusift_ctx_set_policy(cusift_ctx *ctx, int key, int value);
 int cusift_ctx_get_policy(cusift_ctx *ctx, int key, int *value);
+/* Keep the K strongest keypoints per image, selected on the device (new; the reference bounds SiftData with maxPts alone,
+ * which under saturation keeps the coarser octaves whole and whichever octave-0 keypoints won the append race).  Sticky
+ * per context; k = 0 (the default) turns it off and extraction is bit for bit what it was.  With k > 0 every
+ * cusift_extract / _extract_host / _extract_batch on this context, and every cusift_graph recorded while it is set,
+ * leaves per image the first k records of ALL the image's keypoints under this total order:
+ *   1. strength: larger key first, key = |sharpness| taken as its IEEE bit pattern, or 0 when sharpness is not finite;
+ *   2. octave: larger subsampling first (the coarser octave wins a tie);
+ *   3. position: smaller coords2D[1] (y), then smaller coords2D[0] (x), then smaller scale.
+ * Two records equal in all of these are interchangeable, so the kept SET is a function of the image alone: not of the
+ * append order, the launch policy or the image's place in the batch.  The layout keeps its rules: kept records come
+ * coarsest octave first, in unspecified order inside an octave; every field extraction writes has the bits the same
+ * record has with k = 0; nothing else and no record beyond the count is touched.  d_counters[i] is the number KEPT,
+ * min(k, keypoints held) -- the raw count is not reported in this mode.  max_pts stays the capacity of the record array AND
+ * of every octave's candidate list: the result is defined when no single octave of the image finds more than max_pts
+ * keypoints; candidates beyond max_pts in one octave are lost before the selection sees them, as today.
+ * The keypoints are selected as 64-byte heads between detection and description (three launches on the context's
+ * stream, the same number whatever the images hold; no host read-back), so a dropped keypoint is never oriented or
+ * described.  That needs a list of heads per octave: the call takes that launch plan whatever CUSIFT_POLICY_* and
+ * concurrent_batches say, and is refused with CUSIFT_ERR_INVALID when it cannot -- fused_detect = 0,
+ * CUSIFT_POLICY_GENERIC_KERNELS, more than 256 images per call, lists beyond 1 GiB, an octave the fused detection does
+ * not take (a caller's odd pitch) -- or when k > max_pts.  k < 0 is refused here.  cusift_tiled_* refuses a context with
+ * k > 0; cusift_pipe_* creates its own contexts and does not select. */
+int cusift_ctx_set_keep_strongest(cusift_ctx *ctx, int k);
 /* An event on a context's stream: record, then the GPU time between two of them (blocks until `stop` has happened).
  * What the reference's TimerGPU does with cudaEvents (cutils.h:94-114); include/cuSIFT.h builds TimerGPU on these. */
 typedef struct cusift_event cusift_event;

@@ -161,6 +161,15 @@ int cusift_lift_depth(cusift_ctx *ctx, cusift_point *d_points, const unsigned in
 int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
                           int num_pts2, float score_thresh, float ambiguity_thresh, int type /* 0 = 2D, 1 = 3D */,
                           int *d_pairs, float *d_coord, int *d_count);
+/* The selection behind cusift_ctx_set_keep_strongest (cusift_amd.h has the total order) as a stage of its own, on lists
+ * of 64-byte record heads (the first 16 floats of a cusift_point: coords2D .. subsampling) as the staged detections leave them.
+ * d_heads is [list][image][capacity] x 64 B; d_counts is [list][image]: on input the counts held (the call clamps them at
+ * `capacity`), on output the counts kept.  Per image the `keep` (>= 1) first heads of all its lists together survive, each
+ * list compacted to its kept heads in unspecified order -- heads at and beyond a list's new count hold nothing in
+ * particular -- and d_kept[image] = min(keep, heads held).  Uses the context's arena as scratch (8 bytes per head of
+ * capacity); asynchronous on the context's stream: the call does not synchronise. */
+int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_images, int capacity,
+                            unsigned int *d_counts, int keep, unsigned int *d_kept);
 
 /* Frame-to-frame registration of an RGB-D pair, device-resident from SiftData + depth to [R | t]: cusift_lift_depth
  * of both frames (one width x height image each, rows pitch_elems apart), cusift_match(distance), the 3-D selection
