@@ -61,6 +61,73 @@ def gpu_match(ctx, s1, s2, distance):
     return d1.to_numpy(SIFT_POINT_DTYPE, (len(s1),))
 
 
+SCORE_TOL = 2e-6  # the suite's tolerance on a score
+
+
+def float64_candidates(s1, s2, distance):
+    """The float64 anchor of a match: (best [n1], second [n1], candidates bool [n1, n2]).  A row's candidates are the
+    columns within 2 * SCORE_TOL of its float64 best -- two scores that each carry SCORE_TOL of error can swap no
+    further apart.  The second-best counts a column of the initial value, as the scan does when n2 == 1."""
+    dot = s1["data"].astype(np.float64) @ s2["data"].astype(np.float64).T
+    assert (dot > -1).all()  # no clamp in these inputs
+    sc = 2.0 - 2.0 * dot if distance == 1 else -dot  # ascending either way
+    init = 999.0 if distance == 1 else 1.0
+    srt = np.sort(np.c_[sc, np.full(len(sc), init)], axis=1)
+    cand = sc <= srt[:, :1] + 2 * SCORE_TOL
+    sign = 1.0 if distance == 1 else -1.0
+    return sign * srt[:, 0], sign * srt[:, 1], cand
+
+
+def assert_float64_anchor(got, s1, s2, distance, what=""):
+    """Every row, not 99 % of them: the index is a float64 candidate, the score is the float64 best, and the ambiguity
+    follows from the float64 best and second whether or not the index agrees with anybody's."""
+    best, second, cand = float64_candidates(s1, s2, distance)
+    rows = np.arange(len(s1))
+    assert ((got["match"] >= 0) & (got["match"] < len(s2))).all(), what
+    off = np.nonzero(~cand[rows, got["match"]])[0]
+    assert not len(off), (what, "index outside the float64 candidates on rows", off[:10])
+    np.testing.assert_allclose(got["score"], best, atol=SCORE_TOL, rtol=0, err_msg=what)
+    amb = best / (second + 1e-6) if distance == 1 else (1 - best) / (1 - second + 1e-6)
+    np.testing.assert_allclose(got["ambiguity"], amb, rtol=1e-4, atol=3e-5, err_msg=what)
+    # a condition on the input: rows where the candidates leave a choice are at most 1 % (change a seed, not this cap)
+    loose = (cand.sum(axis=1) > 1).sum()
+    assert loose <= 0.01 * len(s1), (what, "rows with more than one candidate", int(loose))
+
+
+RAGGED = [(1, 1), (1, 40), (17, 16), (64, 33), (65, 257), (300, 7), (1000, 999)]
+SPLIT_SIZES = [(3000, 2900), (200, 5000), (5000, 130)]
+
+
+@pytest.mark.parametrize("n1,n2,seed", [(n1, n2, n1 * 1000 + n2) for n1, n2 in RAGGED]
+                         + [(n1, n2, n1 + n2) for n1, n2 in SPLIT_SIZES])
+def test_float64_anchor_holds_for_the_oracle_on_the_gpu_tests_inputs(oracle, n1, n2, seed):
+    """The anchor the GPU tests below apply, on their own descriptors without a GPU: its conditions on the input (no
+    clamp, at most 1 % of rows with a choice of candidates) hold at every shape, and at the ragged shapes the reference
+    itself passes it (the oracle over the split sizes is minutes of CPU and adds nothing to that)."""
+    s1, s2 = random_unit_points(np.random.default_rng(seed), n1, n2)
+    for distance in (1, 0):
+        _, _, cand = float64_candidates(s1, s2, distance)
+        loose = (cand.sum(axis=1) > 1).sum()
+        print("(%d, %d) distance %d: %d rows with more than one candidate" % (n1, n2, distance, loose))
+        assert loose <= 0.01 * n1
+        if (n1, n2) in RAGGED:
+            want = s1.copy()
+            oracle.match(want, s2, distance)
+            assert_float64_anchor(want, s1, s2, distance, "oracle (%d, %d) d%d" % (n1, n2, distance))
+
+
+def random_unit_points(rng, n1, n2):
+    """The inputs of test_gpu_matcher_ragged_sizes and test_gpu_matcher_column_splits_fold_to_the_single_scan."""
+    def rand_pts(n):
+        p = np.zeros(n, dtype=SIFT_POINT_DTYPE)
+        d = np.abs(rng.normal(size=(n, 128))).astype(np.float32)
+        p["data"] = d / np.linalg.norm(d, axis=1, keepdims=True)
+        p["coords2D"] = rng.uniform(0, 1000, (n, 2)).astype(np.float32)
+        return p
+
+    return rand_pts(n1), rand_pts(n2)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("distance", [1, 0])
 def test_gpu_matcher_vs_oracle_on_reference_fixture(ctx, oracle, vl_pair, distance):
@@ -93,18 +160,9 @@ def test_gpu_matcher_passes_the_reference_tests(ctx, vl_pair):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n1,n2", [(1, 1), (1, 40), (17, 16), (64, 33), (65, 257), (300, 7), (1000, 999)])
+@pytest.mark.parametrize("n1,n2", RAGGED)
 def test_gpu_matcher_ragged_sizes(ctx, oracle, n1, n2):
-    rng = np.random.default_rng(n1 * 1000 + n2)
-
-    def rand_pts(n):
-        p = np.zeros(n, dtype=SIFT_POINT_DTYPE)
-        d = np.abs(rng.normal(size=(n, 128))).astype(np.float32)
-        p["data"] = d / np.linalg.norm(d, axis=1, keepdims=True)
-        p["coords2D"] = rng.uniform(0, 1000, (n, 2)).astype(np.float32)
-        return p
-
-    s1, s2 = rand_pts(n1), rand_pts(n2)
+    s1, s2 = random_unit_points(np.random.default_rng(n1 * 1000 + n2), n1, n2)
     for distance in (1, 0):
         want = s1.copy()
         oracle.match(want, s2, distance)
@@ -114,6 +172,9 @@ def test_gpu_matcher_ragged_sizes(ctx, oracle, n1, n2):
         assert same.mean() >= 0.99
         np.testing.assert_allclose(got["ambiguity"][same], want["ambiguity"][same], rtol=1e-4, atol=3e-5)
         assert (got["match"] >= 0).all() and (got["match"] < n2).all()
+        assert_float64_anchor(got, s1, s2, distance, "(%d, %d) distance %d" % (n1, n2, distance))
+        np.testing.assert_array_equal(got["match_xpos"], s2["coords2D"][got["match"], 0])
+        np.testing.assert_array_equal(got["match_ypos"], s2["coords2D"][got["match"], 1])
 
 
 @pytest.mark.gpu
@@ -150,28 +211,21 @@ def test_gpu_matcher_signed_descriptors_hit_the_l2_clamp(ctx, oracle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n1,n2", [(3000, 2900), (200, 5000), (5000, 130)])
+@pytest.mark.parametrize("n1,n2", SPLIT_SIZES)
 def test_gpu_matcher_column_splits_fold_to_the_single_scan(ctx, oracle, n1, n2):
     """The matcher splits image 2's columns over the grid (auto: several splits at these sizes) and folds the splits
     in column order; forced to one split it is the plain scan.  Both must agree with each other and the oracle."""
     from cusift_amd import capi
 
-    rng = np.random.default_rng(n1 + n2)
-
-    def rand_pts(n):
-        p = np.zeros(n, dtype=SIFT_POINT_DTYPE)
-        d = np.abs(rng.normal(size=(n, 128))).astype(np.float32)
-        p["data"] = d / np.linalg.norm(d, axis=1, keepdims=True)
-        p["coords2D"] = rng.uniform(0, 1000, (n, 2)).astype(np.float32)
-        return p
-
-    s1, s2 = rand_pts(n1), rand_pts(n2)
+    s1, s2 = random_unit_points(np.random.default_rng(n1 + n2), n1, n2)
     for distance in (1, 0):
         runs = {}
-        for splits in ("auto", "1", "7", "1000"):
-            ctx.set_policy(capi.POLICY_MATCH_SPLITS, 0 if splits == "auto" else int(splits))
-            runs[splits] = gpu_match(ctx, s1, s2, distance)
-        ctx.set_policy(capi.POLICY_MATCH_SPLITS, 0)
+        try:
+            for splits in ("auto", "1", "7", "1000"):
+                ctx.set_policy(capi.POLICY_MATCH_SPLITS, 0 if splits == "auto" else int(splits))
+                runs[splits] = gpu_match(ctx, s1, s2, distance)
+        finally:
+            ctx.set_policy(capi.POLICY_MATCH_SPLITS, 0)
         for k in ("auto", "7", "1000"):
             for f in ("score", "ambiguity", "match", "match_xpos", "match_ypos"):
                 np.testing.assert_array_equal(runs[k][f], runs["1"][f], err_msg="%s splits, %s" % (k, f))
@@ -180,6 +234,9 @@ def test_gpu_matcher_column_splits_fold_to_the_single_scan(ctx, oracle, n1, n2):
         np.testing.assert_allclose(runs["auto"]["score"], want["score"], atol=2e-6, rtol=0)
         assert (runs["auto"]["match"] == want["match"]).mean() >= 0.99
         np.testing.assert_array_equal(runs["auto"]["match_xpos"], s2["coords2D"][runs["auto"]["match"], 0])
+        np.testing.assert_array_equal(runs["auto"]["match_ypos"], s2["coords2D"][runs["auto"]["match"], 1])
+        for k in ("auto", "1"):
+            assert_float64_anchor(runs[k], s1, s2, distance, "(%d, %d) distance %d, %s splits" % (n1, n2, distance, k))
 
 
 @pytest.mark.gpu
