@@ -279,11 +279,8 @@ extern "C" int cusift_ctx_destroy(cusift_ctx *ctx) {
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->dog) (void)hipFree(ctx->dog);
   if (ctx->u8_stage) (void)hipFree(ctx->u8_stage);
-  if (ctx->homo_scratch) (void)hipFree(ctx->homo_scratch);
-  if (ctx->rigid_scratch) (void)hipFree(ctx->rigid_scratch);
-  if (ctx->select_scratch) (void)hipFree(ctx->select_scratch);
+  if (ctx->register_scratch) (void)hipFree(ctx->register_scratch);
   if (ctx->pairs_scratch) (void)hipFree(ctx->pairs_scratch);
-  if (ctx->sequence_scratch) (void)hipFree(ctx->sequence_scratch);
   if (ctx->match_scratch) (void)hipFree(ctx->match_scratch);
   if (ctx->d_counter1) (void)hipFree(ctx->d_counter1);
   if (ctx->d_queue) (void)hipFree(ctx->d_queue);

@@ -2,8 +2,9 @@
 // the context object, the octave plan and the helpers of the launch wrappers.
 //   sift_context.hip  errors, context + arena + policy + stage timers, memory helpers
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
-//                     FindPointsMulti, fused detection, orientation, descriptors, bands, matcher, homography, rigid
-//                     transform, RGB-D registration, packing)
+//                     FindPointsMulti, fused detection, orientation, descriptors, bands, math-eval, packing)
+//   sift_register.hip the registration host layer: matcher, FindHomography, planar registration, rigid RANSAC, RGB-D
+//                     registration and the pair-list forms of the three
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
@@ -127,6 +128,21 @@ static inline int idiv_up(int a, int b) { return (a + b - 1) / b; }
 static inline int ialign_up(int a, int b) { return idiv_up(a, b) * b; }  // cutils.h:17
 static inline size_t align_up_sz(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// Lays the arrays of a scratch block out one behind the other, each on a 256-byte boundary: take() returns the offset of
+// the next array, `size` is the offset behind the last one (the bytes the block needs).
+struct ScratchLayout {
+  size_t size = 0;
+  size_t take(size_t bytes) {
+    const size_t at = size;
+    size += align_up_sz(bytes, 256);
+    return at;
+  }
+};
+template <class T>
+static T *at(char *base, size_t offset) {  // the array at `offset` of a block
+  return reinterpret_cast<T *>(base + offset);
+}
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
@@ -165,21 +181,15 @@ struct cusift_ctx {
   // per-split partial results of the matcher (cusift_match)
   MatchPartial *match_scratch = nullptr;
   size_t match_scratch_bytes = 0;
-  // coordinates / samples / hypotheses / counts of cusift_find_homography; the state of cusift_estimate_homography
-  char *homo_scratch = nullptr;
-  size_t homo_scratch_bytes = 0;
-  // result head / flags / hypotheses / counts / samples / coordinates of cusift_estimate_rigid
-  char *rigid_scratch = nullptr;
-  size_t rigid_scratch_bytes = 0;
-  // per-workgroup keep counts of cusift_select_matches
-  int *select_scratch = nullptr;
-  size_t select_scratch_bytes = 0;
+  // the state of one registration call (sift_register.hip): FindHomography, planar, rigid, RGB-D, the selection's block
+  // counts, the pair-list forms -- what travels back comes first.  Every call lays it out anew and writes what it reads:
+  // nothing is carried from one call to the next.
+  char *register_scratch = nullptr;
+  size_t register_scratch_bytes = 0;
   // cusift_match_batch / cusift_register_rgbd_batch / cusift_register_planar_batch: the pair list and the matcher's
-  // per-split partials; the match rows, the selection and the RANSAC state of every pair (what travels back comes first)
+  // per-split partials (live together with register_scratch in the last two)
   char *pairs_scratch = nullptr;
   size_t pairs_scratch_bytes = 0;
-  char *sequence_scratch = nullptr;
-  size_t sequence_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;
@@ -320,7 +330,7 @@ static int grow_scratch(cusift_ctx *ctx, T *&ptr, size_t &have, size_t bytes, co
   return CUSIFT_OK;
 }
 
-// shared between sift_context.hip, sift_stages.hip and sift_driver.hip
+// shared between sift_context.hip, sift_stages.hip, sift_register.hip and sift_driver.hip
 int enter(cusift_ctx *ctx);
 int check_launch(const char *what);
 int ensure_arena(cusift_ctx *ctx, size_t bytes);

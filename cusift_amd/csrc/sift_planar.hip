@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusif
   if (tx == 0) block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
-// cand[k] = record index of the k-th candidate; the last workgroup writes their number into head[18].
+// cand[k] = record index of the k-th candidate; the last workgroup writes their number into head[kPlanarHeadCand].
 __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const unsigned char *__restrict__ marks,
                                                                         int num_pts,
                                                                         const int *__restrict__ block_counts,
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const un
   if (keep) cand[base + wave_base + rank] = i;  // < n: every keep before this one is a distinct record below i
   // a pair of a batch with fewer than 8 records reports no candidate, as the pair call answers before it counts
   if (blockIdx.x == gridDim.x - 1 && tx == 0)
-    head[18] = (nb.count && n < 8) ? 0 : base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    head[kPlanarHeadCand] = (nb.count && n < 8) ? 0 : base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
 }
 
 // a * b rounded toward zero for a, b that hold fp32 values: the product is exact in fp64; round it to nearest, then step
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *
   __shared__ double s_pt[4][kPlanarTile];
   coord = planar_pair(coord, nb.scratch), homo = planar_pair(homo, nb.scratch);
   counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.head);
-  if (head[18] < 8) return;  // uniform; nothing was solved: planar_select_kernel answers alone
+  if (head[kPlanarHeadCand] < 8) return;  // uniform; nothing was solved: planar_select_kernel answers alone
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kPlanarTile + tx;
   const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
@@ -272,10 +272,10 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
   const int tx = threadIdx.x;
   int *ihead = (int *)head;
   const int n = planar_count(ihead, num_pts, nb);
-  if (ihead[18] < 8) {  // uniform; extras/homography.cu:220: the identity, no inlier, the records stay as they are
+  if (ihead[kPlanarHeadCand] < 8) {  // uniform; extras/homography.cu:220: the identity, no inlier, the records stay as they are
     for (int i = tx; i < n; i += kPlanarThreads) flags[i] = 0;
-    if (tx < 18) head[tx] = (tx % 9 == 0 || tx % 9 == 4 || tx % 9 == 8) ? 1.0f : 0.0f;
-    if (tx >= 19 && tx < 22) ihead[tx] = 0;
+    if (tx < kPlanarHeadCand) head[tx] = (tx % 9 == 0 || tx % 9 == 4 || tx % 9 == 8) ? 1.0f : 0.0f;
+    if (tx >= kPlanarHeadMatches && tx <= kPlanarHeadLoop) ihead[tx] = 0;
     return;
   }
   // ---- the first hypothesis with the most inliers ----
@@ -384,14 +384,14 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
   if (tx == 0) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      head[i] = (float)A[i];
-      head[9 + i] = win[i];
+      head[kPlanarHeadH + i] = (float)A[i];
+      head[kPlanarHeadR + i] = win[i];
     }
-    head[8] = 1.0f;
-    head[17] = 1.0f;
-    ihead[19] = best_count;
-    ihead[20] = s_cnt[0];
-    ihead[21] = best;
+    head[kPlanarHeadH + 8] = 1.0f;
+    head[kPlanarHeadR + 8] = 1.0f;
+    ihead[kPlanarHeadMatches] = best_count;
+    ihead[kPlanarHeadFit] = s_cnt[0];
+    ihead[kPlanarHeadLoop] = best;
   }
 }
 

@@ -306,11 +306,11 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float
   }
   if (count) {
     num_pts = rigid_num_pts(count, num_pts);
-    if (tx == 0) ((int *)head)[14] = num_pts;
+    if (tx == 0) ((int *)head)[kRigidHeadCount] = num_pts;
     if (num_pts < (k3D ? 3 : 2)) {  // uniform; nothing was solved: the identity, no inlier
       for (int i = tx; i < num_pts; i += kRigidThreads) flags[i] = 0;
-      if (tx < 12) head[tx] = (tx % 5 == 0) ? 1.0f : 0.0f;
-      if (tx == 0) ((int *)head)[12] = 0, ((int *)head)[13] = 0;
+      if (tx < kRigidHeadInliers) head[tx] = (tx % 5 == 0) ? 1.0f : 0.0f;
+      if (tx == 0) ((int *)head)[kRigidHeadInliers] = 0, ((int *)head)[kRigidHeadLoop] = 0;
       return;
     }
   }
@@ -366,8 +366,8 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float
   if (tx == 0) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) head[i] = rt[i];
-    ((int *)head)[12] = best_count;  // the winner's count before the refit, like :455
-    ((int *)head)[13] = best;
+    ((int *)head)[kRigidHeadInliers] = best_count;  // the winner's count before the refit, like :455
+    ((int *)head)[kRigidHeadLoop] = best;
   }
 }
 

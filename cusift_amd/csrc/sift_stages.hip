@@ -1,6 +1,6 @@
 // sift_stages.hip -- the stage entry points of the C ABI (include/cusift_amd.h) and their launch wrappers: one function per
-// kernel of the reference (cuSIFT.cu:313-455) plus the fused detection, the band forms of the strip tiling, the matcher,
-// the homography and the packing of SiftData.
+// kernel of the reference (cuSIFT.cu:313-455) plus the fused detection, the band forms of the strip tiling and the packing
+// of SiftData.  The matcher and everything behind it (homography, rigid transform, registration): sift_register.hip.
 #include "sift_host.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -668,734 +668,6 @@ extern "C" int cusift_math_eval(cusift_ctx *ctx, int op, const float *d_a, const
   const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 256 * 16);
   hipLaunchKernelGGL(math_eval_kernel, dim3(blocks), dim3(256), 0, ctx->stream, op, d_a, d_b, d_out, d_out2, (long)n);
   return check_launch("math_eval");
-}
-
-// ------------------------------------------------------------------------------------------------
-// matcher
-// ------------------------------------------------------------------------------------------------
-extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
-                            int num_pts2, int distance) {
-  TRY(enter(ctx));
-  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // extras/matching.cu:241-242: nothing to match
-  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: missing data");
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: distance must be 0 or 1");
-  // Column splits: aim at >= 4 workgroups per CU, keep >= 4 LDS tiles (128 columns) per split.
-  const int row_blocks = idiv_up(num_pts1, 64);
-  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, row_blocks), idiv_up(num_pts2, 128)));
-  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, 32));
-  splits = std::min(splits, 65535);
-  // the kernel addresses a split's columns through a buffer resource with 32-bit byte offsets: a split may span at most
-  // 2^31 / 588 records (3.65 M) -- more points than that force further splits
-  constexpr int kMaxColsPerSplit = (int)((0x7fffffffu / sizeof(cusift_point)) / 32 * 32);
-  splits = std::max(splits, idiv_up(num_pts2, kMaxColsPerSplit));
-  if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: too many points in image 2 (%d)", num_pts2);
-  const int cols_per_split = idiv_up(idiv_up(num_pts2, splits), 32) * 32;
-  splits = idiv_up(num_pts2, cols_per_split);
-  const int n1_pad = row_blocks * 64;
-  MatchPartial *partials = nullptr;
-  if (splits > 1) {
-    const size_t bytes = sizeof(MatchPartial) * (size_t)splits * n1_pad;
-    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
-    partials = ctx->match_scratch;
-  }
-  if (distance)
-    hipLaunchKernelGGL(match_kernel<true>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, cols_per_split, partials, n1_pad);
-  else
-    hipLaunchKernelGGL(match_kernel<false>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, cols_per_split, partials, n1_pad);
-  if (splits > 1)
-    hipLaunchKernelGGL(match_merge_kernel, dim3(idiv_up(num_pts1, 256)), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, distance, partials, n1_pad, splits);
-  return check_launch("match");
-}
-
-// ------------------------------------------------------------------------------------------------
-// RANSAC homography
-// ------------------------------------------------------------------------------------------------
-extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sift, int num_pts, const int *h_rand_pts,
-                                      int num_loops, float thresh, float h_homography[9], int *num_matches,
-                                      float *h_all_homo, int *h_all_counts) {
-  TRY(enter(ctx));
-  if (!h_homography || !num_matches) return fail(CUSIFT_ERR_INVALID, "FindHomography: NULL output");
-  static const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // extras/homography.cu:184-187
-  memcpy(h_homography, ident, sizeof(ident));
-  *num_matches = 0;
-  if (!d_sift || !h_rand_pts) return fail(CUSIFT_ERR_INVALID, "FindHomography: missing data");
-  if (num_pts < 1 || num_loops < 1) return fail(CUSIFT_ERR_INVALID, "FindHomography: num_pts and num_loops must be >= 1");
-  for (long i = 0; i < 4L * num_loops; ++i)
-    if (h_rand_pts[i] < 0 || h_rand_pts[i] >= num_pts)
-      return fail(CUSIFT_ERR_INVALID, "FindHomography: sample index %d out of range [0, %d)", h_rand_pts[i], num_pts);
-  const size_t coord_b = align_up_sz(sizeof(float) * 4 * (size_t)num_pts, 256);
-  const size_t rand_b = align_up_sz(sizeof(int) * 4 * (size_t)num_loops, 256);
-  const size_t homo_b = align_up_sz(sizeof(float) * 8 * (size_t)num_loops, 256);
-  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
-  const size_t bytes = coord_b + rand_b + homo_b + cnt_b;
-  TRY(grow_scratch(ctx, ctx->homo_scratch, ctx->homo_scratch_bytes, bytes, "", false));
-  float *d_coord = (float *)ctx->homo_scratch;
-  int *d_rand = (int *)(ctx->homo_scratch + coord_b);
-  float *d_homo = (float *)(ctx->homo_scratch + coord_b + rand_b);
-  int *d_counts = (int *)(ctx->homo_scratch + coord_b + rand_b + homo_b);
-  HIP_TRY(hipMemcpyAsync(d_rand, h_rand_pts, sizeof(int) * 4 * (size_t)num_loops, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(homography_gather_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream, d_sift, num_pts,
-                     d_coord);
-  hipLaunchKernelGGL(homography_solve_kernel, dim3(idiv_up(num_loops, 64)), dim3(64), 0, ctx->stream, d_coord, num_pts,
-                     d_rand, num_loops, d_homo, 0, 0ull, (const int *)nullptr, (const int *)nullptr, (int *)nullptr,
-                     PlanarBatch{});
-  hipLaunchKernelGGL(homography_test_kernel, dim3(num_loops), dim3(64), 0, ctx->stream, d_coord, num_pts, d_homo,
-                     num_loops, thresh * thresh, d_counts);
-  TRY(check_launch("find_homography"));
-  std::vector<int> counts((size_t)num_loops);
-  std::vector<float> homo(8 * (size_t)num_loops);
-  HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * (size_t)num_loops, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(homo.data(), d_homo, sizeof(float) * 8 * (size_t)num_loops, hipMemcpyDeviceToHost,
-                         ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  int best = -1, best_count = -1;  // extras/homography.cu:249-254: first maximum
-  for (int i = 0; i < num_loops; ++i)
-    if (counts[i] > best_count) {
-      best_count = counts[i];
-      best = i;
-    }
-  *num_matches = best_count;
-  for (int j = 0; j < 8; ++j) h_homography[j] = homo[(size_t)j * num_loops + best];
-  if (h_all_homo) memcpy(h_all_homo, homo.data(), sizeof(float) * homo.size());
-  if (h_all_counts) memcpy(h_all_counts, counts.data(), sizeof(int) * counts.size());
-  return CUSIFT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// planar registration (sift_planar.hip): candidates, seeded RANSAC homography, refit -- one read-back
-// ------------------------------------------------------------------------------------------------
-struct PlanarOut {
-  float *h_homography, *h_ransac;
-  int *num_candidates, *num_matches, *num_fit, *best_loop;
-  char *h_inliers;
-  int *h_drawn;
-  float *h_all_homo;
-  int *h_all_counts;
-};
-
-// every refusal of cusift_estimate_homography, before anything is enqueued or written
-static int planar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
-                        int num_loops, float thresh, int refine_loops, float refine_thresh, const PlanarOut &o) {
-  if (!o.h_homography || !o.h_ransac || !o.num_candidates || !o.num_matches || !o.num_fit)
-    return fail(CUSIFT_ERR_INVALID, "%s: NULL output", who);
-  if (rule != 0 && rule != 1) return fail(CUSIFT_ERR_INVALID, "%s: rule must be 0 (score > lo) or 1 (score < lo^2)", who);
-  if (std::isnan(lo) || std::isnan(hi)) return fail(CUSIFT_ERR_INVALID, "%s: a threshold is NaN", who);
-  if (num_loops < 1 || num_loops > (1 << 24))
-    return fail(CUSIFT_ERR_INVALID, "%s: num_loops %d outside [1, 2^24]", who, num_loops);
-  if (!(thresh > 0.0f) || !(refine_thresh > 0.0f))
-    return fail(CUSIFT_ERR_INVALID, "%s: thresh and refine_thresh must be > 0", who);
-  if (refine_loops < 0) return fail(CUSIFT_ERR_INVALID, "%s: refine_loops %d < 0", who, refine_loops);
-  if (num_pts < 0 || num_pts > (1 << 26)) return fail(CUSIFT_ERR_INVALID, "%s: num_pts %d outside [0, 2^26]", who, num_pts);
-  if (num_pts > 0 && !d_sift) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
-  return CUSIFT_OK;
-}
-
-static void planar_identity(int num_pts, int num_loops, const PlanarOut &o) {
-  static const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // extras/homography.cu:184-187
-  memcpy(o.h_homography, ident, sizeof(ident));
-  memcpy(o.h_ransac, ident, sizeof(ident));
-  *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
-  if (o.best_loop) *o.best_loop = 0;
-  if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
-  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 4 * (size_t)num_loops);
-  if (o.h_all_homo) memset(o.h_all_homo, 0, sizeof(float) * 8 * (size_t)num_loops);
-  if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
-}
-
-// The five launches and the one read-back; the arguments are checked and num_pts >= 8.
-static int planar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
-                      int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                      const PlanarOut &o) {
-  // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
-  const size_t head_b = 256;
-  const size_t flag_b = align_up_sz((size_t)num_pts, 256);
-  const size_t idx_b = align_up_sz(sizeof(int) * 4 * (size_t)num_loops, 256);
-  const size_t homo_b = align_up_sz(sizeof(float) * 8 * (size_t)num_loops, 256);
-  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
-  const size_t coord_b = align_up_sz(sizeof(float) * 4 * (size_t)num_pts, 256);
-  const size_t cand_b = align_up_sz(sizeof(int) * (size_t)num_pts, 256);
-  const size_t mark_b = flag_b;
-  const int blocks = idiv_up(num_pts, 256);
-  const size_t block_b = align_up_sz(sizeof(int) * (size_t)blocks, 256);
-  const size_t idx_off = head_b + flag_b, homo_off = idx_off + idx_b, cnt_off = homo_off + homo_b;
-  const size_t coord_off = cnt_off + cnt_b, cand_off = coord_off + coord_b, mark_off = cand_off + cand_b;
-  const size_t block_off = mark_off + mark_b;
-  TRY(grow_scratch(ctx, ctx->homo_scratch, ctx->homo_scratch_bytes, block_off + block_b, "", false));
-  char *base = ctx->homo_scratch;
-  float *d_head = (float *)base, *d_homo = (float *)(base + homo_off), *d_coord = (float *)(base + coord_off);
-  char *d_flags = base + head_b;
-  int *d_idx = (int *)(base + idx_off), *d_counts = (int *)(base + cnt_off), *d_cand = (int *)(base + cand_off);
-  unsigned char *d_marks = (unsigned char *)(base + mark_off);
-  int *d_blocks = (int *)(base + block_off);
-  const PlanarBatch nb{};
-  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
-  // scoring: 64 hypotheses per one-wave workgroup; split the points until the launch has ~8 waves per CU, but keep at
-  // least one 64-point tile per split
-  const int loop_blocks = idiv_up(num_loops, 64);
-  int splits = std::max(1, std::min(idiv_up(8 * ctx->num_cus, loop_blocks), idiv_up(num_pts, 64)));
-  splits = std::min(splits, 65535);
-  const int pts_per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
-  splits = idiv_up(num_pts, pts_per_split);
-  hipLaunchKernelGGL(planar_mark_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const cusift_point *)d_sift, num_pts,
-                     num_pts2, rule, t_lo, t_hi, d_coord, d_marks, d_blocks, nb);
-  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const unsigned char *)d_marks,
-                     num_pts, (const int *)d_blocks, d_cand, (int *)d_head, nb);
-  hipLaunchKernelGGL(homography_solve_kernel, dim3(loop_blocks), dim3(64), 0, ctx->stream, (const float *)d_coord,
-                     num_pts, d_idx, num_loops, d_homo, 1, (unsigned long long)seed, (const int *)d_cand,
-                     (const int *)d_head + 18, d_counts, nb);
-  hipLaunchKernelGGL(planar_score_kernel, dim3(loop_blocks, splits), dim3(64), 0, ctx->stream, (const float *)d_coord,
-                     num_pts, pts_per_split, (const float *)d_homo, num_loops, thresh * thresh, d_counts,
-                     (const int *)d_head, nb);
-  hipLaunchKernelGGL(planar_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, (const float *)d_coord,
-                     (const unsigned char *)d_marks, (const float *)d_homo, (const int *)d_counts, num_loops,
-                     thresh * thresh, refine_loops, refine_thresh * refine_thresh, d_head, d_flags, (float *)nullptr,
-                     nb);
-  TRY(check_launch("estimate_homography"));
-  // the one blocking read-back
-  const bool all = o.h_drawn || o.h_all_homo || o.h_all_counts;
-  std::vector<char> back(all ? coord_off : head_b + (o.h_inliers ? flag_b : 0));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  int tail[4];
-  memcpy(tail, back.data() + sizeof(float) * 18, sizeof(tail));
-  if (tail[0] < 8) {  // extras/homography.cu:220; the kernels left the records alone
-    planar_identity(num_pts, num_loops, o);
-    *o.num_candidates = tail[0];
-    return CUSIFT_OK;
-  }
-  memcpy(o.h_homography, back.data(), sizeof(float) * 9);
-  memcpy(o.h_ransac, back.data() + sizeof(float) * 9, sizeof(float) * 9);
-  *o.num_candidates = tail[0], *o.num_matches = tail[1], *o.num_fit = tail[2];
-  if (o.best_loop) *o.best_loop = tail[3];
-  if (o.h_inliers) memcpy(o.h_inliers, back.data() + head_b, (size_t)num_pts);
-  if (o.h_drawn) memcpy(o.h_drawn, back.data() + idx_off, sizeof(int) * 4 * (size_t)num_loops);
-  if (o.h_all_homo) memcpy(o.h_all_homo, back.data() + homo_off, sizeof(float) * 8 * (size_t)num_loops);
-  if (o.h_all_counts) memcpy(o.h_all_counts, back.data() + cnt_off, sizeof(int) * (size_t)num_loops);
-  return CUSIFT_OK;
-}
-
-extern "C" int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
-                                          float lo, float hi, int num_loops, float thresh, int refine_loops,
-                                          float refine_thresh, uint64_t seed, float h_homography[9], float h_ransac[9],
-                                          int *num_candidates, int *num_matches, int *num_fit, int *best_loop,
-                                          char *h_inliers, int *h_drawn, float *h_all_homo, int *h_all_counts) {
-  TRY(enter(ctx));
-  const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
-                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
-  TRY(planar_check("EstimateHomography", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
-  if (num_pts < 8) {  // extras/homography.cu:205
-    planar_identity(num_pts, num_loops, o);
-    return CUSIFT_OK;
-  }
-  return planar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed, o);
-}
-
-extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
-                                      int num_pts2, int distance, int rule, float lo, float hi, int num_loops,
-                                      float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                                      float h_homography[9], float h_ransac[9], int *num_candidates, int *num_matches,
-                                      int *num_fit, int *best_loop, char *h_inliers, int *h_drawn, float *h_all_homo,
-                                      int *h_all_counts) {
-  TRY(enter(ctx));
-  const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
-                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
-  TRY(planar_check("RegisterPlanar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterPlanar: distance must be 0 or 1");
-  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterPlanar: missing data");
-  TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
-  if (num_pts1 < 8) {  // as the staged route: the matcher stays enqueued, the answer needs no device work
-    planar_identity(num_pts1, num_loops, o);
-    return CUSIFT_OK;
-  }
-  return planar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed,
-                    o);
-}
-
-// ------------------------------------------------------------------------------------------------
-// RANSAC rigid transform (sift_rigid.hip)
-// ------------------------------------------------------------------------------------------------
-// The three launches of sift_rigid.hip over d_coord[num_pts][6].  d_count == NULL: num_pts is the number of points;
-// otherwise it is their capacity (the grids are sized by it) and the kernels read the number from *d_count.
-// n_pairs > 1: that many independent problems, `nb` elements apart in every array, pair p drawing from seed + p.
-static void rigid_launch(cusift_ctx *ctx, const float *d_coord, int num_pts, const int *d_count, int *d_idx,
-                         int num_loops, int draw, float thresh2, int type, uint64_t seed, float *d_rt, int *d_counts,
-                         float *d_head, char *d_flags, int n_pairs = 1, RigidBatch nb = RigidBatch{}) {
-  // scoring: 256 hypotheses per workgroup; split the points until the launch has ~4 workgroups per CU, but keep
-  // at least one 256-point tile per split
-  const int loop_blocks = idiv_up(num_loops, 256);
-  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks * n_pairs), idiv_up(num_pts, 256)));
-  splits = std::min(splits, 65535);
-  const int pts_per_split = idiv_up(num_pts, splits);
-  splits = idiv_up(num_pts, pts_per_split);
-  const dim3 solve_grid(idiv_up(num_loops, 64), 1, n_pairs), score_grid(loop_blocks, splits, n_pairs);
-  const dim3 select_grid(1, 1, n_pairs);
-  if (type == 1)
-    hipLaunchKernelGGL(rigid_solve_kernel<true>, solve_grid, dim3(64), 0, ctx->stream, d_coord, num_pts, d_idx,
-                       num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count, nb);
-  else
-    hipLaunchKernelGGL(rigid_solve_kernel<false>, solve_grid, dim3(64), 0, ctx->stream, d_coord, num_pts, d_idx,
-                       num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count, nb);
-  hipLaunchKernelGGL(rigid_score_kernel, score_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, pts_per_split, d_rt,
-                     num_loops, thresh2, d_counts, d_count, nb);
-  if (type == 1)
-    hipLaunchKernelGGL(rigid_select_kernel<true>, select_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
-                       d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
-  else
-    hipLaunchKernelGGL(rigid_select_kernel<false>, select_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
-                       d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
-}
-
-extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int num_pts, const int *h_indices,
-                                     int num_loops, float thresh2, int type, uint64_t seed, float h_rt[12],
-                                     int *num_inliers, int *best_loop, char *h_inliers, float *h_all_rt,
-                                     int *h_all_counts, int *h_drawn) {
-  TRY(enter(ctx));
-  if (!h_rt || !num_inliers) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: NULL output");
-  if (!h_coord) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: missing data");
-  if (type != 0 && type != 1) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: type must be 0 (2D) or 1 (3D)");
-  const int used = type == 1 ? 3 : 2;  // the 2-D estimate never reads a hypothesis' third sample
-  const int min_pts = h_indices ? used : 3;  // drawing takes three distinct points for either type
-  if (num_pts < min_pts || num_pts > (1 << 26))
-    return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: num_pts %d outside [%d, 2^26]", num_pts, min_pts);
-  if (num_loops < 1 || num_loops > (1 << 24))
-    return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: num_loops %d outside [1, 2^24]", num_loops);
-  if (!(thresh2 > 0.0f)) return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: thresh2 must be > 0");
-  if (h_indices)
-    for (int l = 0; l < num_loops; ++l)
-      for (int i = 0; i < used; ++i) {
-        const int v = h_indices[3 * (size_t)l + i];
-        if (v < 0 || v >= num_pts)
-          return fail(CUSIFT_ERR_INVALID, "EstimateRigidTransform: sample index %d out of range [0, %d)", v, num_pts);
-      }
-  // [head | flags | hypotheses | counts | samples] is what travels back, in one copy; the coordinates come last
-  const size_t head_b = 256;
-  const size_t flag_b = align_up_sz((size_t)num_pts, 256);
-  const size_t rt_b = align_up_sz(sizeof(float) * 12 * (size_t)num_loops, 256);
-  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
-  const size_t idx_b = align_up_sz(sizeof(int) * 3 * (size_t)num_loops, 256);
-  const size_t coord_b = align_up_sz(sizeof(float) * 6 * (size_t)num_pts, 256);
-  const size_t rt_off = head_b + flag_b, cnt_off = rt_off + rt_b, idx_off = cnt_off + cnt_b, coord_off = idx_off + idx_b;
-  TRY(grow_scratch(ctx, ctx->rigid_scratch, ctx->rigid_scratch_bytes, coord_off + coord_b, "", false));
-  char *base = ctx->rigid_scratch;
-  float *d_head = (float *)base, *d_rt = (float *)(base + rt_off), *d_coord = (float *)(base + coord_off);
-  char *d_flags = base + head_b;
-  int *d_counts = (int *)(base + cnt_off), *d_idx = (int *)(base + idx_off);
-  HIP_TRY(hipMemcpyAsync(d_coord, h_coord, sizeof(float) * 6 * (size_t)num_pts, hipMemcpyHostToDevice, ctx->stream));
-  if (h_indices)
-    HIP_TRY(hipMemcpyAsync(d_idx, h_indices, sizeof(int) * 3 * (size_t)num_loops, hipMemcpyHostToDevice, ctx->stream));
-  rigid_launch(ctx, d_coord, num_pts, nullptr, d_idx, num_loops, h_indices ? 0 : 1, thresh2, type, seed, d_rt, d_counts,
-               d_head, d_flags);
-  TRY(check_launch("estimate_rigid"));
-  // the one blocking read-back
-  const bool all = h_all_rt || h_all_counts || h_drawn;
-  std::vector<char> back(all ? coord_off : head_b + (h_inliers ? flag_b : 0));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  memcpy(h_rt, back.data(), sizeof(float) * 12);
-  int tail[2];
-  memcpy(tail, back.data() + sizeof(float) * 12, sizeof(tail));
-  *num_inliers = tail[0];
-  if (best_loop) *best_loop = tail[1];
-  if (h_inliers) memcpy(h_inliers, back.data() + head_b, (size_t)num_pts);
-  if (h_all_rt) memcpy(h_all_rt, back.data() + rt_off, sizeof(float) * 12 * (size_t)num_loops);
-  if (h_all_counts) memcpy(h_all_counts, back.data() + cnt_off, sizeof(int) * (size_t)num_loops);
-  if (h_drawn) memcpy(h_drawn, back.data() + idx_off, sizeof(int) * 3 * (size_t)num_loops);
-  return CUSIFT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// RGB-D registration (sift_rgbd.hip): depth lift, match selection, the fused frame-pair call
-// ------------------------------------------------------------------------------------------------
-static int check_camera(const cusift_camera *cam, const char *who) {
-  if (!cam) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
-  if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || cam->fx == 0.0f || cam->fy == 0.0f ||
-      !std::isfinite(cam->cx) || !std::isfinite(cam->cy) || !std::isfinite(cam->origin))
-    return fail(CUSIFT_ERR_INVALID, "%s: fx and fy must be finite and not 0, cx / cy / origin finite", who);
-  if (!(cam->units_per_metre > 0.0f) || !std::isfinite(cam->units_per_metre))
-    return fail(CUSIFT_ERR_INVALID, "%s: units_per_metre must be > 0", who);
-  if (cam->encoding != 0 && cam->encoding != 1)
-    return fail(CUSIFT_ERR_INVALID, "%s: encoding must be 0 (plain) or 1 (rotated by 3 bits)", who);
-  return CUSIFT_OK;
-}
-
-static int check_depth_geometry(int w, int h, int pitch, size_t image_stride, int n_images, const char *who) {
-  if (w < 1 || h < 1 || w > (1 << 24) || h > (1 << 24) || pitch < w)
-    return fail(CUSIFT_ERR_INVALID, "%s: depth image %d x %d, pitch %d", who, w, h, pitch);
-  if (n_images > 1 && image_stride < (size_t)(h - 1) * (size_t)pitch + (size_t)w)
-    return fail(CUSIFT_ERR_INVALID, "%s: image stride %zu is smaller than one image", who, image_stride);
-  return CUSIFT_OK;
-}
-
-extern "C" int cusift_lift_depth(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters, int n_images,
-                                 int max_pts, const uint16_t *d_depth, int width, int height, int pitch_elems,
-                                 size_t image_stride_elems, const cusift_camera *camera) {
-  TRY(enter(ctx));
-  TRY(check_camera(camera, "LiftDepth"));
-  if (n_images < 0 || n_images > 65535 || max_pts < 0)
-    return fail(CUSIFT_ERR_INVALID, "LiftDepth: n_images %d outside [0, 65535] or max_pts %d < 0", n_images, max_pts);
-  if (n_images == 0 || max_pts == 0) return CUSIFT_OK;
-  if (!d_points || !d_depth) return fail(CUSIFT_ERR_INVALID, "LiftDepth: missing data");
-  TRY(check_depth_geometry(width, height, pitch_elems, image_stride_elems, n_images, "LiftDepth"));
-  hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(max_pts, 256), n_images), dim3(256), 0, ctx->stream, d_points,
-                     d_counters, max_pts, (const unsigned short *)d_depth, width, height, pitch_elems,
-                     image_stride_elems, *camera);
-  return check_launch("lift_depth");
-}
-
-// the two launches of the selection; d_blocks: idiv_up(n1, 256) ints.  n1 >= 1.
-static void select_launch(cusift_ctx *ctx, const cusift_point *d_sift1, int n1, const cusift_point *d_sift2, int n2,
-                          float score_thresh, float ambiguity_thresh, int type, int *d_blocks, int *d_pairs,
-                          float *d_coord, int *d_count) {
-  const float s2 = score_thresh * score_thresh, a2 = ambiguity_thresh * ambiguity_thresh;  // include/matching.h:43-44
-  const int blocks = idiv_up(n1, 256);
-  hipLaunchKernelGGL(match_select_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_sift1, n1, d_sift2, n2, s2,
-                     a2, type, d_blocks);
-  hipLaunchKernelGGL(match_select_write_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_sift1, n1, d_sift2, n2, s2,
-                     a2, type, d_blocks, d_pairs, d_coord, d_count);
-}
-
-extern "C" int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1,
-                                     const cusift_point *d_sift2, int num_pts2, float score_thresh,
-                                     float ambiguity_thresh, int type, int *d_pairs, float *d_coord, int *d_count) {
-  TRY(enter(ctx));
-  if (!d_count) return fail(CUSIFT_ERR_INVALID, "SelectMatches: NULL d_count");
-  if (type != 0 && type != 1) return fail(CUSIFT_ERR_INVALID, "SelectMatches: type must be 0 (2D) or 1 (3D)");
-  if (num_pts1 < 0 || num_pts2 < 0 || num_pts1 > (1 << 26))
-    return fail(CUSIFT_ERR_INVALID, "SelectMatches: num_pts1 %d outside [0, 2^26] or num_pts2 %d < 0", num_pts1, num_pts2);
-  if (std::isnan(score_thresh) || std::isnan(ambiguity_thresh))
-    return fail(CUSIFT_ERR_INVALID, "SelectMatches: a threshold is NaN");
-  if (num_pts1 == 0) {
-    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
-    return CUSIFT_OK;
-  }
-  if (!d_sift1 || (!d_sift2 && num_pts2 > 0) || !d_pairs || !d_coord)
-    return fail(CUSIFT_ERR_INVALID, "SelectMatches: missing data");
-  TRY(grow_scratch(ctx, ctx->select_scratch, ctx->select_scratch_bytes, sizeof(int) * (size_t)idiv_up(num_pts1, 256), "",
-                   false));
-  select_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, type, ctx->select_scratch,
-                d_pairs, d_coord, d_count);
-  return check_launch("select_matches");
-}
-
-extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const uint16_t *d_depth1,
-                                    cusift_point *d_sift2, int num_pts2, const uint16_t *d_depth2, int width,
-                                    int height, int pitch_elems, const cusift_camera *camera, int distance,
-                                    float score_thresh, float ambiguity_thresh, int num_loops, float thresh2,
-                                    int rigid_type, uint64_t seed, float h_rt[12], int *num_matches, int *num_inliers,
-                                    int *h_pairs, char *h_inliers) {
-  TRY(enter(ctx));
-  if (!h_rt || !num_matches || !num_inliers) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: NULL output");
-  TRY(check_camera(camera, "RegisterRGBD"));
-  if (rigid_type != 0 && rigid_type != 1) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: rigid_type must be 0 (2D) or 1 (3D)");
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: distance must be 0 or 1");
-  if (num_pts1 < 0 || num_pts2 < 0 || num_pts1 > (1 << 26))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: num_pts1 %d outside [0, 2^26] or num_pts2 %d < 0", num_pts1, num_pts2);
-  if (num_loops < 1 || num_loops > (1 << 24))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: num_loops %d outside [1, 2^24]", num_loops);
-  if (!(thresh2 > 0.0f)) return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: thresh2 must be > 0");
-  if (std::isnan(score_thresh) || std::isnan(ambiguity_thresh))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: a threshold is NaN");
-  if ((num_pts1 > 0 && (!d_sift1 || !d_depth1)) || (num_pts2 > 0 && (!d_sift2 || !d_depth2)))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: missing data");
-  TRY(check_depth_geometry(width, height, pitch_elems, 0, 1, "RegisterRGBD"));
-  const int n1 = num_pts1;
-  // [head | flags | pairs] is what travels back, in one copy; behind it what stays on the device
-  const size_t head_b = 256;
-  const size_t flag_b = align_up_sz((size_t)std::max(n1, 1), 256);
-  const size_t pair_b = align_up_sz(sizeof(int) * 2 * (size_t)n1, 256);
-  const size_t rt_b = align_up_sz(sizeof(float) * 12 * (size_t)num_loops, 256);
-  const size_t cnt_b = align_up_sz(sizeof(int) * (size_t)num_loops, 256);
-  const size_t idx_b = align_up_sz(sizeof(int) * 3 * (size_t)num_loops, 256);
-  const size_t coord_b = align_up_sz(sizeof(float) * 6 * (size_t)n1, 256);
-  const size_t block_b = align_up_sz(sizeof(int) * (size_t)idiv_up(std::max(n1, 1), 256), 256);
-  const size_t pair_off = head_b + flag_b, rt_off = pair_off + pair_b, cnt_off = rt_off + rt_b;
-  const size_t idx_off = cnt_off + cnt_b, coord_off = idx_off + idx_b, block_off = coord_off + coord_b;
-  const size_t count_off = block_off + block_b;
-  TRY(grow_scratch(ctx, ctx->rigid_scratch, ctx->rigid_scratch_bytes, count_off + 256, "", false));
-  char *base = ctx->rigid_scratch;
-  float *d_head = (float *)base, *d_rt = (float *)(base + rt_off), *d_coord = (float *)(base + coord_off);
-  char *d_flags = base + head_b;
-  int *d_pairs = (int *)(base + pair_off), *d_counts = (int *)(base + cnt_off), *d_idx = (int *)(base + idx_off);
-  int *d_blocks = (int *)(base + block_off), *d_count = (int *)(base + count_off);
-  if (n1 > 0)
-    hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(n1, 256), 1), dim3(256), 0, ctx->stream, d_sift1, nullptr, n1,
-                       (const unsigned short *)d_depth1, width, height, pitch_elems, (size_t)0, *camera);
-  if (num_pts2 > 0)
-    hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(num_pts2, 256), 1), dim3(256), 0, ctx->stream, d_sift2, nullptr,
-                       num_pts2, (const unsigned short *)d_depth2, width, height, pitch_elems, (size_t)0, *camera);
-  TRY(check_launch("register_rgbd lift"));
-  static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  if (n1 == 0 || num_pts2 == 0) {  // nothing to match (extras/matching.cu:241-242); known from the arguments alone
-    memcpy(h_rt, ident, sizeof(ident));
-    *num_matches = 0;
-    *num_inliers = 0;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // blocking like the full route: the depth images may be freed
-    return CUSIFT_OK;
-  }
-  TRY(cusift_match(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
-  select_launch(ctx, d_sift1, n1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, 1, d_blocks, d_pairs, d_coord,
-                d_count);
-  rigid_launch(ctx, d_coord, n1, d_count, d_idx, num_loops, 1, thresh2, rigid_type, seed, d_rt, d_counts, d_head,
-               d_flags);
-  TRY(check_launch("register_rgbd"));
-  // the one blocking read-back
-  std::vector<char> back(h_pairs ? rt_off : (h_inliers ? pair_off : head_b));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  int tail[3];
-  memcpy(tail, back.data() + sizeof(float) * 12, sizeof(tail));
-  const int n = std::min(std::max(tail[2], 0), n1);
-  memcpy(h_rt, back.data(), sizeof(float) * 12);
-  *num_inliers = tail[0];
-  *num_matches = n;
-  if (h_inliers) memcpy(h_inliers, back.data() + head_b, (size_t)n);
-  if (h_pairs) memcpy(h_pairs, back.data() + pair_off, sizeof(int) * 2 * (size_t)n);
-  return CUSIFT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// the same over a batch of frames and a pair list (sift_sequence.hip)
-// ------------------------------------------------------------------------------------------------
-static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int max_pts, const char *who) {
-  if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_pairs %d outside [0, 65535]", who, n_pairs);
-  if (n_images < 0 || n_images > 65535)
-    return fail(CUSIFT_ERR_INVALID, "%s: n_images %d outside [0, 65535]", who, n_images);
-  if (max_pts < 0 || max_pts > (1 << 20)) return fail(CUSIFT_ERR_INVALID, "%s: max_pts %d outside [0, 2^20]", who, max_pts);
-  if (n_pairs > 0 && !h_pairs) return fail(CUSIFT_ERR_INVALID, "%s: NULL pair list", who);
-  for (int p = 0; p < 2 * n_pairs; ++p)
-    if (h_pairs[p] < 0 || h_pairs[p] >= n_images)
-      return fail(CUSIFT_ERR_INVALID, "%s: pair %d names frame %d outside [0, %d)", who, p / 2, h_pairs[p], n_images);
-  return CUSIFT_OK;
-}
-
-// Uploads the pair list and enqueues the matcher of every pair: one launch, plus the merge when the columns are split.
-// *d_pairs_out: the list on the device, for the stages behind it.  n_pairs >= 1, max_pts >= 1, the list is checked.
-static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
-                              const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
-                              const int **d_pairs_out) {
-  // Column splits, sized from max_pts (the counts stay on the device): aim at >= 4 workgroups per CU over all pairs,
-  // keep >= 4 LDS tiles (128 columns) per split.  max_pts <= 2^20 records fit one split's 32-bit byte offsets.
-  const int row_blocks = idiv_up(max_pts, 64);
-  const long blocks = (long)row_blocks * n_pairs;
-  int splits = (int)std::max(1L, std::min((4L * ctx->num_cus + blocks - 1) / blocks, (long)idiv_up(max_pts, 128)));
-  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(max_pts, 32));
-  splits = std::min(splits, 65535);
-  const int cols_per_split = idiv_up(idiv_up(max_pts, splits), 32) * 32;
-  splits = idiv_up(max_pts, cols_per_split);
-  const int n1_pad = row_blocks * 64;
-  const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
-  const size_t part_b = splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0;
-  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b, "", false));
-  int *d_pairs = (int *)ctx->pairs_scratch;
-  MatchPartial *partials = splits > 1 ? (MatchPartial *)(ctx->pairs_scratch + list_b) : nullptr;
-  HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
-  const dim3 grid(row_blocks, splits, n_pairs);
-  if (distance)
-    hipLaunchKernelGGL(match_batch_kernel<true>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
-                       cols_per_split, partials, n1_pad, d_rows);
-  else
-    hipLaunchKernelGGL(match_batch_kernel<false>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
-                       cols_per_split, partials, n1_pad, d_rows);
-  if (splits > 1)
-    hipLaunchKernelGGL(match_batch_merge_kernel, dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream,
-                       d_counters, max_pts, d_pairs, distance, cols_per_split, partials, n1_pad, splits, d_rows);
-  *d_pairs_out = d_pairs;
-  return check_launch("match_batch");
-}
-
-extern "C" int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
-                                  int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
-                                  cusift_match_row *d_rows) {
-  TRY(enter(ctx));
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "MatchBatch: distance must be 0 or 1");
-  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "MatchBatch"));
-  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
-  if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatch: missing data");
-  const int *d_pairs = nullptr;
-  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs);
-}
-
-extern "C" int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters,
-                                          int n_images, int max_pts, const uint16_t *d_depth, int width, int height,
-                                          int pitch_elems, size_t image_stride_elems, const cusift_camera *camera,
-                                          const int *h_pairs, int n_pairs, int distance, float score_thresh,
-                                          float ambiguity_thresh, int num_loops, float thresh2, int rigid_type,
-                                          uint64_t seed, float *h_rt, int *h_num_matches, int *h_num_inliers,
-                                          int *h_sel_pairs, char *h_inliers) {
-  TRY(enter(ctx));
-  if (!h_rt || !h_num_matches || !h_num_inliers) return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: NULL output");
-  TRY(check_camera(camera, "RegisterRGBDBatch"));
-  if (rigid_type != 0 && rigid_type != 1)
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: rigid_type must be 0 (2D) or 1 (3D)");
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: distance must be 0 or 1");
-  if (num_loops < 1 || num_loops > (1 << 24))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: num_loops %d outside [1, 2^24]", num_loops);
-  if (!(thresh2 > 0.0f)) return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: thresh2 must be > 0");
-  if (std::isnan(score_thresh) || std::isnan(ambiguity_thresh))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: a threshold is NaN");
-  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "RegisterRGBDBatch"));
-  if (n_images > 0 && max_pts > 0 && (!d_points || !d_depth))
-    return fail(CUSIFT_ERR_INVALID, "RegisterRGBDBatch: missing data");
-  TRY(check_depth_geometry(width, height, pitch_elems, image_stride_elems, n_images, "RegisterRGBDBatch"));
-  if (n_pairs == 0) return CUSIFT_OK;
-  static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  if (max_pts == 0) {  // every frame is empty: nothing to match (extras/matching.cu:241-242)
-    for (int p = 0; p < n_pairs; ++p) {
-      memcpy(h_rt + 12 * (size_t)p, ident, sizeof(ident));
-      h_num_matches[p] = h_num_inliers[p] = 0;
-    }
-    return CUSIFT_OK;
-  }
-  // [heads | flags | selected pairs] is what travels back, in one copy; behind it what stays on the device.  A head is
-  // rigid_select_kernel's 16 words.
-  const size_t P = (size_t)n_pairs, M = (size_t)max_pts, L = (size_t)num_loops;
-  const size_t head_b = align_up_sz(64 * P, 256), flag_b = align_up_sz(P * M, 256);
-  const size_t pair_b = align_up_sz(sizeof(int) * 2 * P * M, 256), row_b = align_up_sz(sizeof(cusift_match_row) * P * M, 256);
-  const size_t coord_b = align_up_sz(sizeof(float) * 6 * P * M, 256), count_b = align_up_sz(sizeof(int) * P, 256);
-  const size_t rt_b = align_up_sz(sizeof(float) * 12 * P * L, 256), cnt_b = align_up_sz(sizeof(int) * P * L, 256);
-  const size_t idx_b = align_up_sz(sizeof(int) * 3 * P * L, 256);
-  const size_t flag_off = head_b, pair_off = flag_off + flag_b, row_off = pair_off + pair_b, coord_off = row_off + row_b;
-  const size_t count_off = coord_off + coord_b, rt_off = count_off + count_b, cnt_off = rt_off + rt_b;
-  const size_t idx_off = cnt_off + cnt_b;
-  TRY(grow_scratch(ctx, ctx->sequence_scratch, ctx->sequence_scratch_bytes, idx_off + idx_b, "", false));
-  char *base = ctx->sequence_scratch;
-  float *d_head = (float *)base, *d_coord = (float *)(base + coord_off), *d_rt = (float *)(base + rt_off);
-  char *d_flags = base + flag_off;
-  int *d_sel = (int *)(base + pair_off), *d_count = (int *)(base + count_off), *d_counts = (int *)(base + cnt_off);
-  int *d_idx = (int *)(base + idx_off);
-  cusift_match_row *d_rows = (cusift_match_row *)(base + row_off);
-  hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(max_pts, 256), n_images), dim3(256), 0, ctx->stream, d_points,
-                     d_counters, max_pts, (const unsigned short *)d_depth, width, height, pitch_elems,
-                     image_stride_elems, *camera);
-  const int *d_pairs = nullptr;
-  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs));
-  hipLaunchKernelGGL(sequence_select_kernel, dim3(n_pairs), dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
-                     d_pairs, d_rows, score_thresh * score_thresh, ambiguity_thresh * ambiguity_thresh, 1, d_sel,
-                     d_coord, d_count);
-  RigidBatch nb;
-  nb.coord = 6 * M, nb.indices = 3 * L, nb.rt = 12 * L, nb.counts = L, nb.head = 16, nb.flags = M, nb.count = 1;
-  rigid_launch(ctx, d_coord, max_pts, d_count, d_idx, num_loops, 1, thresh2, rigid_type, seed, d_rt, d_counts, d_head,
-               d_flags, n_pairs, nb);
-  TRY(check_launch("register_rgbd_batch"));
-  // the one blocking read-back
-  std::vector<char> back(h_sel_pairs ? row_off : (h_inliers ? pair_off : 64 * P));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (size_t p = 0; p < P; ++p) {
-    int tail[3];
-    memcpy(tail, back.data() + 64 * p + sizeof(float) * 12, sizeof(tail));
-    const size_t n = (size_t)std::min(std::max(tail[2], 0), max_pts);
-    memcpy(h_rt + 12 * p, back.data() + 64 * p, sizeof(float) * 12);
-    h_num_inliers[p] = tail[0];
-    h_num_matches[p] = (int)n;
-    if (h_inliers) memcpy(h_inliers + p * M, back.data() + flag_off + p * M, n);
-    if (h_sel_pairs) memcpy(h_sel_pairs + 2 * p * M, back.data() + pair_off + sizeof(int) * 2 * p * M, sizeof(int) * 2 * n);
-  }
-  return CUSIFT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// planar registration of a pair list (sift_sequence.hip, sift_planar.hip) -- one read-back
-// ------------------------------------------------------------------------------------------------
-extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
-                                            int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
-                                            int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
-                                            float refine_thresh, uint64_t seed, float *h_homography, float *h_ransac,
-                                            int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
-                                            char *h_inliers, float *h_match_error) {
-  TRY(enter(ctx));
-  const PlanarOut o{h_homography, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
-                    h_inliers,    nullptr,  nullptr,          nullptr};
-  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "RegisterPlanarBatch"));
-  TRY(planar_check("RegisterPlanarBatch", d_points, n_images > 0 ? max_pts : 0, rule, lo, hi, num_loops, thresh,
-                   refine_loops, refine_thresh, o));
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "RegisterPlanarBatch: distance must be 0 or 1");
-  if (n_pairs == 0) return CUSIFT_OK;
-  const size_t P = (size_t)n_pairs, M = (size_t)max_pts, L = (size_t)num_loops;
-  if (max_pts == 0) {  // every frame is empty, known from the arguments alone
-    for (size_t p = 0; p < P; ++p) {
-      const PlanarOut one{h_homography + 9 * p,  h_ransac + 9 * p, h_num_candidates + p,
-                          h_num_matches + p,     h_num_fit + p,    h_best_loop ? h_best_loop + p : nullptr,
-                          nullptr,               nullptr,          nullptr,
-                          nullptr};
-      planar_identity(0, num_loops, one);
-    }
-    return CUSIFT_OK;
-  }
-  // [heads | flags | errors] is what travels back, in one copy; behind it what stays on the device: one block per pair
-  // [samples | hypotheses | counts | coordinates | candidates | marks | block counts], then the match rows
-  const int blocks = idiv_up(max_pts, 256);
-  const size_t head_b = align_up_sz(kPlanarHeadBytes * P, 256), flag_b = align_up_sz(P * M, 256);
-  const size_t err_b = align_up_sz(sizeof(float) * P * M, 256);
-  const size_t idx_b = align_up_sz(sizeof(int) * 4 * L, 256), homo_b = align_up_sz(sizeof(float) * 8 * L, 256);
-  const size_t cnt_b = align_up_sz(sizeof(int) * L, 256), coord_b = align_up_sz(sizeof(float) * 4 * M, 256);
-  const size_t cand_b = align_up_sz(sizeof(int) * M, 256), mark_b = align_up_sz(M, 256);
-  const size_t block_b = align_up_sz(sizeof(int) * (size_t)blocks, 256);
-  const size_t flag_off = head_b, err_off = flag_off + flag_b, pair_off = err_off + err_b;
-  const size_t homo_in = idx_b, cnt_in = homo_in + homo_b, coord_in = cnt_in + cnt_b, cand_in = coord_in + coord_b;
-  const size_t mark_in = cand_in + cand_b, block_in = mark_in + mark_b, pair_b = block_in + block_b;
-  const size_t row_off = pair_off + pair_b * P;
-  TRY(grow_scratch(ctx, ctx->sequence_scratch, ctx->sequence_scratch_bytes, row_off + sizeof(cusift_match_row) * P * M,
-                   "", false));
-  char *base = ctx->sequence_scratch, *first = base + pair_off;
-  float *d_head = (float *)base, *d_err = (float *)(base + err_off);
-  char *d_flags = base + flag_off;
-  int *d_idx = (int *)first, *d_counts = (int *)(first + cnt_in), *d_cand = (int *)(first + cand_in);
-  float *d_homo = (float *)(first + homo_in), *d_coord = (float *)(first + coord_in);
-  unsigned char *d_marks = (unsigned char *)(first + mark_in);
-  int *d_blocks = (int *)(first + block_in);
-  cusift_match_row *d_rows = (cusift_match_row *)(base + row_off);
-  PlanarBatch nb;
-  nb.records = 0, nb.scratch = pair_b, nb.head = kPlanarHeadBytes, nb.flags = M, nb.count = 1;
-  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
-  // scoring as planar_run, the splits sized from the capacity (the counts stay on the device) over all pairs
-  const int loop_blocks = idiv_up(num_loops, 64);
-  const long wgs = (long)loop_blocks * n_pairs;
-  int splits = (int)std::max(1L, std::min((8L * ctx->num_cus + wgs - 1) / wgs, (long)idiv_up(max_pts, 64)));
-  splits = std::min(splits, 65535);
-  const int pts_per_split = idiv_up(idiv_up(max_pts, splits), 64) * 64;
-  splits = idiv_up(max_pts, pts_per_split);
-  const int *d_pairs = nullptr;
-  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs));
-  hipLaunchKernelGGL(sequence_mark_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_points, d_counters,
-                     max_pts, d_pairs, (const cusift_match_row *)d_rows, rule, t_lo, t_hi, d_coord, d_marks, d_blocks,
-                     (int *)d_head, nb);
-  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream,
-                     (const unsigned char *)d_marks, max_pts, (const int *)d_blocks, d_cand, (int *)d_head, nb);
-  hipLaunchKernelGGL(homography_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream,
-                     (const float *)d_coord, max_pts, d_idx, num_loops, d_homo, 1, (unsigned long long)seed,
-                     (const int *)d_cand, (const int *)d_head + 18, d_counts, nb);
-  hipLaunchKernelGGL(planar_score_kernel, dim3(loop_blocks, splits, n_pairs), dim3(64), 0, ctx->stream,
-                     (const float *)d_coord, max_pts, pts_per_split, (const float *)d_homo, num_loops, thresh * thresh,
-                     d_counts, (const int *)d_head, nb);
-  hipLaunchKernelGGL(planar_select_kernel, dim3(1, 1, n_pairs), dim3(256), 0, ctx->stream, (cusift_point *)nullptr,
-                     max_pts, (const float *)d_coord, (const unsigned char *)d_marks, (const float *)d_homo,
-                     (const int *)d_counts, num_loops, thresh * thresh, refine_loops, refine_thresh * refine_thresh,
-                     d_head, d_flags, d_err, nb);
-  TRY(check_launch("register_planar_batch"));
-  // the one blocking read-back
-  std::vector<char> back(h_match_error ? err_off + sizeof(float) * P * M
-                                       : (h_inliers ? flag_off + P * M : kPlanarHeadBytes * P));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (size_t p = 0; p < P; ++p) {  // the kernels decided every pair, the degenerate ones included: copies only
-    const char *head = back.data() + kPlanarHeadBytes * p;
-    int tail[5];  // candidates, matches, fit, loop, records of frame 1
-    memcpy(tail, head + sizeof(float) * 18, sizeof(tail));
-    const size_t n = (size_t)std::min(std::max(tail[4], 0), max_pts);
-    memcpy(h_homography + 9 * p, head, sizeof(float) * 9);
-    memcpy(h_ransac + 9 * p, head + sizeof(float) * 9, sizeof(float) * 9);
-    h_num_candidates[p] = tail[0], h_num_matches[p] = tail[1], h_num_fit[p] = tail[2];
-    if (h_best_loop) h_best_loop[p] = tail[3];
-    if (h_inliers) memcpy(h_inliers + p * M, back.data() + flag_off + p * M, n);
-    // a pair without a fit has no error, as the pair call leaves match_error alone then
-    if (h_match_error && tail[0] >= 8)
-      memcpy(h_match_error + p * M, back.data() + err_off + sizeof(float) * p * M, sizeof(float) * n);
-  }
-  return CUSIFT_OK;
 }
 
 extern "C" int cusift_memcpy2d_d2h(cusift_ctx *ctx, void *h_dst, size_t dst_pitch, const void *d_src,

@@ -160,8 +160,16 @@ struct PlanarBatch {
   size_t records, scratch, head, flags;
   int count;
 };
-constexpr int kPlanarHeadCount = 22;                  // a head: H[9], R[9], n_cand, matches, fit, loop, then the count
+// A planar result head, in 4-byte words: H[9] (refined) and R[9] (the winner) as float, then as int the candidates, the
+// winner's count, num_fit, the winning loop and -- batched -- the pair's record count.
+constexpr int kPlanarHeadH = 0, kPlanarHeadR = 9, kPlanarHeadCand = 18, kPlanarHeadMatches = 19, kPlanarHeadFit = 20;
+constexpr int kPlanarHeadLoop = 21, kPlanarHeadCount = 22;
 constexpr size_t kPlanarHeadBytes = 128;              // between the heads of a batch
+// A rigid result head: Rt[12] as float, then as int the winner's count, the winning loop and -- with a device-side point
+// count -- that count.
+constexpr int kRigidHeadInliers = 12, kRigidHeadLoop = 13, kRigidHeadCount = 14;
+constexpr size_t kRigidHeadWords = 16;                // between the heads of a batch (RigidBatch::head)
+constexpr size_t kRigidHeadBytes = 4 * kRigidHeadWords;
 
 static_assert(sizeof(cusift_point) == 588, "SiftPoint is a 588-byte ABI record (cuSIFT.h:10-30)");
 

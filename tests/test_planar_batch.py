@@ -1,5 +1,5 @@
 """Planar registration of a pair list: cusift_register_planar_batch (cusift_amd/csrc/sift_sequence.hip: the marking
-kernel; sift_planar.hip / sift_homography.hip: the per-pair RANSAC and refit; sift_stages.hip: the entry point),
+kernel; sift_planar.hip / sift_homography.hip: the per-pair RANSAC and refit; sift_register.hip: the entry point),
 capi.Context.register_planar_batch, capi.chain_homographies, BatchExtractor.register_planar_sequence and
 RegisterPlanarSequence of include/homography.h.
 
@@ -108,20 +108,22 @@ def test_batch_kernels_compile_for_gfx950_without_scratch_and_with_vector_stores
 
 
 def test_one_synchronisation_in_the_batch_entry_point():
-    text = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_stages.hip")).read()
+    text = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
     begin = text.index('extern "C" int %s(' % NAME)
-    section = text[begin:text.index('extern "C" int ', begin + 20)]
+    section = text[begin:]  # the last entry point of the file
+    assert section.count('extern "C" int ') == 1
     code = "\n".join(line.split("//")[0] for line in section.splitlines())
     assert code.count("hipStreamSynchronize(") == 1
     for blocking in ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(",
                      "hipFree(", "cusift_ctx_synchronize", "cusift_memcpy"):
         assert blocking not in code, blocking
-    order = [code.index(k) for k in ("match_batch_launch(", "sequence_mark_kernel", "planar_compact_kernel",
-                                     "homography_solve_kernel", "planar_score_kernel", "planar_select_kernel",
-                                     "hipMemcpyAsync(", "hipStreamSynchronize(")]
+    order = [code.index(k) for k in ("match_batch_launch(", "sequence_mark_kernel", "planar_launch(", "hipMemcpyAsync(",
+                                     "hipStreamSynchronize(")]
     assert order == sorted(order)
     assert code.count("hipMemcpyAsync(") == 1  # one read-back; the pair list is uploaded by the matcher's launcher
-    assert code.count("hipLaunchKernelGGL(") == 5  # and no launch sits in a loop over the pairs
+    # five launches -- the marking here, compact / solve / score / select in planar_launch -- none in a loop over the pairs
+    assert code.count("hipLaunchKernelGGL(") == 1 and code.count("planar_launch(") == 1
+    test_planar.check_planar_launch("\n".join(line.split("//")[0] for line in text.splitlines()))
     launches = code[code.index("match_batch_launch("):code.index("hipMemcpyAsync(")]
     assert "for (" not in launches and "while (" not in launches
 
