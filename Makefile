@@ -56,6 +56,7 @@ cpp-tests: $(LIB)
 	$(MAKE) -C $(ROOT)/tests/cpp_planar
 	$(MAKE) -C $(ROOT)/tests/cpp_planar_batch
 	$(MAKE) -C $(ROOT)/tests/cpp_keep_strongest
+	$(MAKE) -C $(ROOT)/tests/cpp_mutual
 
 check: cpp-tests
 	$(MAKE) -C $(ROOT)/tests/cpp check

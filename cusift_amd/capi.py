@@ -202,6 +202,7 @@ SIGNATURES = {
     "cusift_detect_band": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _i, _vp]),
     "cusift_describe_band": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _i, _i, _vp]),
     "cusift_match": (_i, [_vp, _vp, _i, _vp, _i, _i]),
+    "cusift_match_mutual": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "cusift_memcpy2d_d2h": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
     "cusift_find_homography": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, C.POINTER(_i), _vp, _vp]),
     "cusift_estimate_homography": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp, C.POINTER(_i),
@@ -212,10 +213,12 @@ SIGNATURES = {
                                    _vp, _vp]),
     "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
     "cusift_select_matches": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
+    "cusift_select_mutual": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
     "cusift_select_strongest": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "cusift_register_rgbd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(Camera), _i, _f, _f, _i, _f, _i,
                                   C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
     "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "cusift_match_batch_mutual": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
@@ -683,6 +686,12 @@ class Context:
         """MatchSiftData on device records: distance 1 = L2 (2 - 2 x.y), 0 = dot product."""
         check(lib().cusift_match(self.handle, d_sift1, n1, d_sift2, n2, distance))
 
+    def match_mutual(self, d_sift1, n1, d_sift2, n2, distance=1):
+        """cusift_match_mutual: both directions from one pass -- d_sift1 receives what match() writes, d_sift2 the same
+        five fields over the records of d_sift1 (lowest record on exactly tied best scores).  Both record sets are
+        written: overlapping ranges are refused.  Asynchronous."""
+        check(lib().cusift_match_mutual(self.handle, d_sift1, n1, d_sift2, n2, distance))
+
     def find_homography(self, d_sift, num_pts, rand_pts, thresh=5.0, want_all=False):
         """cusift_find_homography: rand_pts is an int32 array [4, num_loops] of sample indices into d_sift.
         Returns (H[9], num_matches) or, with want_all, (H, num_matches, all_homographies[8, L], all_counts[L])."""
@@ -792,6 +801,14 @@ class Context:
         check(lib().cusift_select_matches(self.handle, d_sift1, n1, d_sift2, n2, score_threshold, ambiguity_threshold,
                                           RIGID_KINDS[kind], d_pairs, d_coord, d_count))
 
+    def select_mutual(self, d_sift1, n1, d_sift2, n2, d_pairs, d_coord, d_count, score_threshold=999.0,
+                      ambiguity_threshold=1.0, kind="3d"):
+        """cusift_select_mutual: select_matches() plus the cross-check -- record i is kept only if the match of its
+        partner in d_sift2 is i (after match_mutual(), or match() in both directions).  The same outputs, in ascending
+        record order.  Asynchronous."""
+        check(lib().cusift_select_mutual(self.handle, d_sift1, n1, d_sift2, n2, score_threshold, ambiguity_threshold,
+                                         RIGID_KINDS[kind], d_pairs, d_coord, d_count))
+
     def register_rgbd(self, d_sift1, n1, d_depth1, d_sift2, n2, d_depth2, w, h, camera, pitch=None, distance=1,
                       score_threshold=999.0, ambiguity_threshold=1.0, loops=1024, thresh2=0.0025, kind="3d", seed=0):
         """cusift_register_rgbd: lift both frames, match, select (3-D), RANSAC + refit -- one synchronisation, at the
@@ -817,6 +834,14 @@ class Context:
         pairs = pair_list(pairs)
         check(lib().cusift_match_batch(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
                                        len(pairs), distance, d_rows))
+
+    def match_batch_mutual(self, d_points, d_counters, n_images, max_pts, pairs, d_rows, d_rows_back, distance=1):
+        """cusift_match_batch_mutual: match_batch() plus, from the same pass, d_rows_back[P][max_pts] of MatchRow (device
+        pointer): for every record of frame 2 its best and second best of frame 1, `match` an index into frame 1.  The
+        records are not written.  Asynchronous."""
+        pairs = pair_list(pairs)
+        check(lib().cusift_match_batch_mutual(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
+                                              len(pairs), distance, d_rows, d_rows_back))
 
     def register_rgbd_batch(self, d_points, d_counters, n_images, max_pts, d_depth, w, h, camera, pairs, pitch=None,
                             image_stride=None, distance=1, score_threshold=999.0, ambiguity_threshold=1.0, loops=1024,

@@ -1,8 +1,11 @@
 // match_tile.inc -- the body shared by match_kernel and match_batch_kernel (sift_match.hip): one workgroup's 64 rows
 // (descriptors p1_base .. p1_base + 15 of this wave) against the columns [col_begin, col_end) of sift2.  Included inside
-// a kernel that has in scope: kL2, kInit, sB, r, g, p1_base, sift1, n1, sift2, col_begin, col_end.  On exit lane r == 0
-// of every 16-lane group g holds best[q], second[q], bidx[q] of rows p1_base + 4 g + q (q = 0..3).  One text, so that a
-// (row, column) dot product is the same k-ordered MFMA chain whichever kernel computes it.
+// a kernel that has in scope: kL2, kInit, sB, lane, wv, r, g, p1_base, sift1, n1, sift2, col_begin, col_end, cols.  On
+// exit lane r == 0 of every 16-lane group g holds best[q], second[q], bidx[q] of rows p1_base + 4 g + q (q = 0..3).
+// One text, so that a (row, column) dot product is the same k-ordered MFMA chain whichever kernel computes it.
+// `cols` is the column side (sift_match.hip): NoColumnSide in the one-directional kernels, whose three calls below are
+// empty inline functions -- no barrier, no LDS, no register (tools/kernel_regs.py: 96 VGPRs, 16,896 B as before);
+// ColumnSide in the mutual kernels.
   // A fragments: lane (r, g) holds elements 16u + 4g + j of descriptor p1_base + r (u = 0..7, j = 0..3)
   float a[8][4];
   {
@@ -48,6 +51,7 @@
     }
     __syncthreads();
     if (c0 + kMatchTileCols < col_end) fetch(c0 + kMatchTileCols);  // in flight while this tile is multiplied
+    if (c0 > col_begin) cols.drain(c0 - kMatchTileCols, col_begin, col_end, lane, wv);  // the previous tile's columns
 
     // two independent 16x16 accumulators (columns c0 + r and c0 + 16 + r), each a k-ordered chain; the B fragments
     // of step u + 1 are read from LDS before the MFMAs of step u are issued
@@ -89,7 +93,9 @@
         }
       }
     }
+    cols.tile(c0, col_begin, acc0, acc1, p1_base, lane, wv);
   }
+  cols.finish(col_begin, col_end, lane, wv);
   // tree over tx = r (extras/matching.cu:122-138,201-218): lane r < len takes lane r + len; ties keep the lower r
 #pragma unroll
   for (int len = 8; len > 0; len >>= 1) {

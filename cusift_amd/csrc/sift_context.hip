@@ -282,6 +282,7 @@ extern "C" int cusift_ctx_destroy(cusift_ctx *ctx) {
   if (ctx->register_scratch) (void)hipFree(ctx->register_scratch);
   if (ctx->pairs_scratch) (void)hipFree(ctx->pairs_scratch);
   if (ctx->match_scratch) (void)hipFree(ctx->match_scratch);
+  if (ctx->match_col_scratch) (void)hipFree(ctx->match_col_scratch);
   if (ctx->d_counter1) (void)hipFree(ctx->d_counter1);
   if (ctx->d_queue) (void)hipFree(ctx->d_queue);
   if (ctx->h_counter1) (void)hipHostFree(ctx->h_counter1);

@@ -64,6 +64,14 @@ __global__ void match_batch_kernel(const cusift_point *, const unsigned int *, i
                                    cusift_match_row *);
 __global__ void match_batch_merge_kernel(const unsigned int *, int, const int *, int, int, const MatchPartial *, int, int,
                                          cusift_match_row *);
+template <bool kL2>
+__global__ void match_mutual_kernel(cusift_point *, int, cusift_point *, int, int, MatchPartial *, int, MatchPartial *);
+__global__ void match_mutual_merge_kernel(cusift_point *, int, const cusift_point *, int, int, const MatchPartial *, int);
+template <bool kL2>
+__global__ void match_batch_mutual_kernel(const cusift_point *, const unsigned int *, int, const int *, int,
+                                          MatchPartial *, int, cusift_match_row *, MatchPartial *, cusift_match_row *);
+__global__ void match_batch_mutual_merge_kernel(const unsigned int *, int, const int *, int, const MatchPartial *, int,
+                                                cusift_match_row *);
 __global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                        const cusift_match_row *, float, float, int, int *, float *, int *);
 __global__ void homography_gather_kernel(const cusift_point *, int, float *);
@@ -181,6 +189,9 @@ struct cusift_ctx {
   // per-split partial results of the matcher (cusift_match)
   MatchPartial *match_scratch = nullptr;
   size_t match_scratch_bytes = 0;
+  // per-row-block partial results of the column side (cusift_match_mutual): [row blocks][num_pts2]
+  MatchPartial *match_col_scratch = nullptr;
+  size_t match_col_scratch_bytes = 0;
   // the state of one registration call (sift_register.hip): FindHomography, planar, rigid, RGB-D, the selection's block
   // counts, the pair-list forms -- what travels back comes first.  Every call lays it out anew and writes what it reads:
   // nothing is carried from one call to the next.

@@ -72,6 +72,18 @@ __device__ __forceinline__ void top2_update(float &best, float &second, int &idx
   best = win ? val : best;
 }
 
+// The column side of a tile as match_tile.inc sees it: tile() once a tile's scores are in the accumulators, drain() for
+// the previous tile behind the next tile's barriers, finish() behind the loop.  NoColumnSide is the one-directional
+// kernels': every call is an empty inline function.  ColumnSide (cusift_match_mutual) is defined with its kernels below.
+struct NoColumnSide {
+  template <class... A>
+  __device__ __forceinline__ void tile(A...) const {}
+  template <class... A>
+  __device__ __forceinline__ void drain(A...) const {}
+  template <class... A>
+  __device__ __forceinline__ void finish(A...) const {}
+};
+
 // One workgroup = 64 descriptors of image 1 (16 per wave) x one contiguous range of image 2's columns
 // (blockIdx.y = column split; the host picks the number of splits so that the grid fills 256 CUs even for a few
 // thousand keypoints).  With one split the kernel writes the final fields; otherwise the (best, second, index)
@@ -89,6 +101,7 @@ __global__ void __launch_bounds__(256) match_kernel(cusift_point *__restrict__ s
   const int col_begin = blockIdx.y * cols_per_split;
   const int col_end = min(col_begin + cols_per_split, n2);  // padded columns (:57) can never win: skip them
   constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;       // also what a masked column scores: it changes nothing
+  const NoColumnSide cols;
 
 #include "match_tile.inc"
   if (r == 0) {
@@ -168,6 +181,7 @@ __global__ void __launch_bounds__(256) match_batch_kernel(const cusift_point *__
   const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
   const int col_end = min(col_begin + cols_per_split, n2);
   constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+  const NoColumnSide cols;
 
 #include "match_tile.inc"
   if (r == 0) {
@@ -213,6 +227,245 @@ __global__ void __launch_bounds__(256) match_batch_merge_kernel(const unsigned i
     if (beats(o.second, m.second, l2)) m.second = o.second;
   }
   write_match_row(rows + (size_t)pair * max_pts + p1, m.best, m.second, m.idx, l2);
+}
+
+// ---- both directions from one pass (cusift_match_mutual, cusift_match_batch_mutual) -----------------------------------
+// The row side is match_kernel's, from the same text.  The column side -- for every descriptor of image 2 the best and
+// second best of image 1 -- is reduced from the same accumulators (match_tile.inc's `cols`) and is defined by
+// a plain model: top2_scan over the rows 0 .. n1 - 1 in ascending order from (kInit, kInit, -1).  Best and second of that
+// scan do not depend on the order in which partial scans are merged, the index does: every merge takes the lower rows
+// first and compares strictly, so an exactly tied best keeps the LOWEST row, whatever the grid.  Column splits
+// (blockIdx.y) partition the columns; row blocks (blockIdx.x) each see every column of their split, so with more than
+// one row block a column's triple goes to col_partials[row block][column] and match_mutual_merge_kernel folds the row
+// blocks in ascending order.  No atomics: the same input gives the same bytes on every run.
+//
+// Per tile a wave folds its 16 rows of every column -- in the lane over q, then the 16-lane groups g + 1 and g + 2 into g
+// -- and leaves 32 triples in LDS (two buffers, by tile parity); behind the next tile's barriers eight lanes of every
+// wave fold the four waves of a column and hand it to `out`.  A buffer is written again two tiles later, behind a
+// barrier that every wave reaches only after its drain.
+typedef float ColFloats[4][kMatchTileCols];  // [wave][column of the tile]
+typedef int ColInts[4][kMatchTileCols];
+
+template <bool kL2, class Out>
+struct ColumnSide {
+  ColFloats *best, *second;  // [2]: tile parity
+  ColInts *idx;
+  int n1;
+  Out out;  // out(column, best, second, idx): the column's result over this workgroup's 64 rows
+  static constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+
+  __device__ __forceinline__ void tile(int c0, int col_begin, const f32x4 &acc0, const f32x4 &acc1, int p1_base, int lane,
+                                       int wv) const {
+    const int r = lane & 15, g = lane >> 4;
+    const int par = ((c0 - col_begin) / kMatchTileCols) & 1;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float cb = kInit, cs = kInit;
+      int ci = -1;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {  // rows 4g .. 4g + 3 in ascending order: the model's scan
+        const int p1 = p1_base + 4 * g + q;
+        const float dot = t ? acc1[q] : acc0[q];
+        float val = kL2 ? (dot > -1.0f ? __builtin_fmaf(-2.0f, dot, 2.0f) : kMatchFltMax) : dot;
+        val = p1 < n1 ? val : kInit;  // a padding row is a copy of the last descriptor: it changes nothing
+        top2_update<kL2>(cb, cs, ci, val, p1);
+      }
+      // group g takes g + 1, then g + 2 (their rows lie above): lanes 0..15 end with the wave's 16 rows
+#pragma unroll
+      for (int d = 16; d <= 32; d <<= 1) {
+        const float ob = __shfl_down(cb, d);
+        const float os = __shfl_down(cs, d);
+        const int oi = __shfl_down(ci, d);
+        top2_scan(cb, cs, ci, ob, oi, kL2);
+        if (beats(os, cs, kL2)) cs = os;
+      }
+      if (g == 0) {
+        best[par][wv][16 * t + r] = cb;
+        second[par][wv][16 * t + r] = cs;
+        idx[par][wv][16 * t + r] = ci;
+      }
+    }
+  }
+
+  // the columns of the tile at c_prev: lane j < 8 of wave wv folds the four waves of column 8 wv + j, lower rows first
+  __device__ __forceinline__ void drain(int c_prev, int col_begin, int col_end, int lane, int wv) const {
+    const int j = 8 * wv + lane, col = c_prev + j;
+    if (lane < 8 && col < col_end) {
+      const int par = ((c_prev - col_begin) / kMatchTileCols) & 1;
+      float cb = best[par][0][j], cs = second[par][0][j];
+      int ci = idx[par][0][j];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) {
+        top2_scan(cb, cs, ci, best[par][w][j], idx[par][w][j], kL2);
+        const float os = second[par][w][j];
+        if (beats(os, cs, kL2)) cs = os;
+      }
+      out(col, cb, cs, ci);
+    }
+  }
+
+  // the last tile's columns (a split always has columns where this is reached with col_begin < col_end)
+  __device__ __forceinline__ void finish(int col_begin, int col_end, int lane, int wv) const {
+    if (col_begin >= col_end) return;
+    __syncthreads();
+    drain(col_begin + (col_end - col_begin - 1) / kMatchTileCols * kMatchTileCols, col_begin, col_end, lane, wv);
+  }
+};
+
+template <bool kL2>
+__global__ void __launch_bounds__(256) match_mutual_kernel(cusift_point *sift1, int n1, cusift_point *sift2, int n2,
+                                                          int cols_per_split, MatchPartial *__restrict__ partials,
+                                                          int n1_pad, MatchPartial *__restrict__ col_partials) {
+  __shared__ float sB[kMatchTileCols * kBStride];
+  __shared__ ColFloats sColBest[2], sColSecond[2];
+  __shared__ ColInts sColIdx[2];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  const int col_begin = blockIdx.y * cols_per_split;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+  auto col_out = [&](int col, float cb, float cs, int ci) {
+    if (col_partials) {
+      MatchPartial mp;
+      mp.best = cb;
+      mp.second = cs;
+      mp.idx = ci;
+      col_partials[(size_t)blockIdx.x * n2 + col] = mp;
+    } else {
+      write_match(sift2 + col, sift1, n1, cb, cs, ci, kL2);
+    }
+  };
+  const ColumnSide<kL2, decltype(col_out)> cols{sColBest, sColSecond, sColIdx, n1, col_out};
+
+#include "match_tile.inc"
+  if (r == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p1 = p1_base + 4 * g + q;
+      if (p1 >= n1) continue;
+      if (partials) {
+        MatchPartial mp;
+        mp.best = best[q];
+        mp.second = second[q];
+        mp.idx = bidx[q];
+        partials[(size_t)blockIdx.y * n1_pad + p1] = mp;
+      } else {
+        write_match(sift1 + p1, sift2, n2, best[q], second[q], bidx[q], kL2);
+      }
+    }
+  }
+}
+
+template __global__ void match_mutual_kernel<false>(cusift_point *, int, cusift_point *, int, int, MatchPartial *, int,
+                                                    MatchPartial *);
+template __global__ void match_mutual_kernel<true>(cusift_point *, int, cusift_point *, int, int, MatchPartial *, int,
+                                                   MatchPartial *);
+
+// The twin of match_merge_kernel for the column side: folds the row blocks of one column in ascending row order.
+__global__ void __launch_bounds__(256) match_mutual_merge_kernel(cusift_point *sift2, int n2, const cusift_point *sift1,
+                                                                int n1, int l2_mode,
+                                                                const MatchPartial *__restrict__ col_partials,
+                                                                int row_blocks) {
+  const bool l2 = l2_mode != 0;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n2) return;
+  MatchPartial m = col_partials[j];
+  for (int b = 1; b < row_blocks; ++b) {
+    const MatchPartial o = col_partials[(size_t)b * n2 + j];
+    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
+    if (beats(o.second, m.second, l2)) m.second = o.second;
+  }
+  write_match(sift2 + j, sift1, n1, m.best, m.second, m.idx, l2);
+}
+
+// match_batch_kernel with the column side: rows_back[pair][max_pts] receives, for record j of frame 2, what the model
+// above gives over the records of frame 1.  col_partials[pair][row block][max_pts]; NULL when max_pts fits one row block.
+template <bool kL2>
+__global__ void __launch_bounds__(256) match_batch_mutual_kernel(const cusift_point *__restrict__ points,
+                                                                const unsigned int *__restrict__ counters,
+                                                                int max_pts, const int *__restrict__ pairs,
+                                                                int cols_per_split, MatchPartial *__restrict__ partials,
+                                                                int n1_pad, cusift_match_row *__restrict__ rows,
+                                                                MatchPartial *__restrict__ col_partials,
+                                                                cusift_match_row *__restrict__ rows_back) {
+  __shared__ float sB[kMatchTileCols * kBStride];
+  __shared__ ColFloats sColBest[2], sColSecond[2];
+  __shared__ ColInts sColIdx[2];
+  const int pair = blockIdx.z;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const int col_begin = blockIdx.y * cols_per_split;
+  if ((int)blockIdx.x * kMatchRowsPerBlock >= n1 || col_begin >= n2) return;  // uniform: no rows or no columns
+  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
+  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+  auto col_out = [&](int col, float cb, float cs, int ci) {
+    if (col_partials) {
+      MatchPartial mp;
+      mp.best = cb;
+      mp.second = cs;
+      mp.idx = ci;
+      col_partials[((size_t)pair * gridDim.x + blockIdx.x) * max_pts + col] = mp;
+    } else {
+      write_match_row(rows_back + (size_t)pair * max_pts + col, cb, cs, ci, kL2);
+    }
+  };
+  const ColumnSide<kL2, decltype(col_out)> cols{sColBest, sColSecond, sColIdx, n1, col_out};
+
+#include "match_tile.inc"
+  if (r == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p1 = p1_base + 4 * g + q;
+      if (p1 >= n1) continue;
+      if (partials) {
+        MatchPartial mp;
+        mp.best = best[q];
+        mp.second = second[q];
+        mp.idx = bidx[q];
+        partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = mp;
+      } else {
+        write_match_row(rows + (size_t)pair * max_pts + p1, best[q], second[q], bidx[q], kL2);
+      }
+    }
+  }
+}
+
+template __global__ void match_batch_mutual_kernel<false>(const cusift_point *, const unsigned int *, int, const int *,
+                                                          int, MatchPartial *, int, cusift_match_row *, MatchPartial *,
+                                                          cusift_match_row *);
+template __global__ void match_batch_mutual_kernel<true>(const cusift_point *, const unsigned int *, int, const int *,
+                                                         int, MatchPartial *, int, cusift_match_row *, MatchPartial *,
+                                                         cusift_match_row *);
+
+// match_mutual_merge_kernel per pair (blockIdx.y): folds the row blocks that had rows, in ascending order.
+__global__ void __launch_bounds__(256) match_batch_mutual_merge_kernel(const unsigned int *__restrict__ counters,
+                                                                      int max_pts, const int *__restrict__ pairs,
+                                                                      int l2_mode,
+                                                                      const MatchPartial *__restrict__ col_partials,
+                                                                      int row_blocks,
+                                                                      cusift_match_row *__restrict__ rows_back) {
+  const bool l2 = l2_mode != 0;
+  const int pair = blockIdx.y;
+  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n2 || n1 <= 0) return;
+  const int live = min(row_blocks, (n1 + kMatchRowsPerBlock - 1) / kMatchRowsPerBlock);  // the others wrote nothing
+  const MatchPartial *__restrict__ mine = col_partials + (size_t)pair * row_blocks * max_pts + j;
+  MatchPartial m = mine[0];
+  for (int b = 1; b < live; ++b) {
+    const MatchPartial o = mine[(size_t)b * max_pts];
+    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
+    if (beats(o.second, m.second, l2)) m.second = o.second;
+  }
+  write_match_row(rows_back + (size_t)pair * max_pts + j, m.best, m.second, m.idx, l2);
 }
 
 }  // namespace cusift

@@ -33,13 +33,9 @@ static const float kIdentRt[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
 // ------------------------------------------------------------------------------------------------
 // matcher
 // ------------------------------------------------------------------------------------------------
-extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
-                            int num_pts2, int distance) {
-  TRY(enter(ctx));
-  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // extras/matching.cu:241-242: nothing to match
-  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: missing data");
-  TRY(check_distance("MatchSiftData", distance));
-  // Column splits: aim at >= 4 workgroups per CU, keep >= 4 LDS tiles (128 columns) per split.
+// The column splits of cusift_match and cusift_match_mutual: aim at >= 4 workgroups per CU, keep >= 4 LDS tiles (128
+// columns) per split.
+static int match_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int *splits_out, int *cols_per_split_out) {
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, row_blocks), idiv_up(num_pts2, 128)));
   if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, 32));
@@ -50,7 +46,20 @@ extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1
   splits = std::max(splits, idiv_up(num_pts2, kMaxColsPerSplit));
   if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: too many points in image 2 (%d)", num_pts2);
   const int cols_per_split = idiv_up(idiv_up(num_pts2, splits), 32) * 32;
-  splits = idiv_up(num_pts2, cols_per_split);
+  *splits_out = idiv_up(num_pts2, cols_per_split);
+  *cols_per_split_out = cols_per_split;
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                            int num_pts2, int distance) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // extras/matching.cu:241-242: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: missing data");
+  TRY(check_distance("MatchSiftData", distance));
+  const int row_blocks = idiv_up(num_pts1, 64);
+  int splits, cols_per_split;
+  TRY(match_split_plan(ctx, num_pts1, num_pts2, &splits, &cols_per_split));
   const int n1_pad = row_blocks * 64;
   MatchPartial *partials = nullptr;
   if (splits > 1) {
@@ -68,6 +77,48 @@ extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1
     hipLaunchKernelGGL(match_merge_kernel, dim3(idiv_up(num_pts1, 256)), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
                        d_sift2, num_pts2, distance, partials, n1_pad, splits);
   return check_launch("match");
+}
+
+// Both directions from one pass over the scores: the row side is cusift_match's, the column side is folded from the same
+// accumulators (sift_match.hip).  Both record sets are written, so their ranges must not overlap.
+extern "C" int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, cusift_point *d_sift2,
+                                   int num_pts2, int distance) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // nothing to match, on either side
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchMutual: missing data");
+  TRY(check_distance("MatchMutual", distance));
+  const uintptr_t a = (uintptr_t)d_sift1, b = (uintptr_t)d_sift2;
+  if (a < b + sizeof(cusift_point) * (size_t)num_pts2 && b < a + sizeof(cusift_point) * (size_t)num_pts1)
+    return fail(CUSIFT_ERR_INVALID, "MatchMutual: the two record ranges overlap (both are written; match a copy)");
+  const int row_blocks = idiv_up(num_pts1, 64);
+  int splits, cols_per_split;
+  TRY(match_split_plan(ctx, num_pts1, num_pts2, &splits, &cols_per_split));
+  const int n1_pad = row_blocks * 64;
+  MatchPartial *partials = nullptr, *col_partials = nullptr;
+  if (splits > 1) {
+    const size_t bytes = sizeof(MatchPartial) * (size_t)splits * n1_pad;
+    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
+    partials = ctx->match_scratch;
+  }
+  if (row_blocks > 1) {
+    const size_t bytes = sizeof(MatchPartial) * (size_t)row_blocks * num_pts2;
+    TRY(grow_scratch(ctx, ctx->match_col_scratch, ctx->match_col_scratch_bytes, bytes, "", false));
+    col_partials = ctx->match_col_scratch;
+  }
+  if (distance)
+    hipLaunchKernelGGL(match_mutual_kernel<true>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
+                       d_sift2, num_pts2, cols_per_split, partials, n1_pad, col_partials);
+  else
+    hipLaunchKernelGGL(match_mutual_kernel<false>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1,
+                       num_pts1, d_sift2, num_pts2, cols_per_split, partials, n1_pad, col_partials);
+  if (splits > 1)
+    hipLaunchKernelGGL(match_merge_kernel, dim3(idiv_up(num_pts1, 256)), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
+                       (const cusift_point *)d_sift2, num_pts2, distance, (const MatchPartial *)partials, n1_pad, splits);
+  if (row_blocks > 1)
+    hipLaunchKernelGGL(match_mutual_merge_kernel, dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_sift2,
+                       num_pts2, (const cusift_point *)d_sift1, num_pts1, distance, (const MatchPartial *)col_partials,
+                       row_blocks);
+  return check_launch("match_mutual");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -421,27 +472,43 @@ static void select_launch(cusift_ctx *ctx, const cusift_point *d_sift1, int n1, 
                      a2, type, d_blocks, d_pairs, d_coord, d_count);
 }
 
-extern "C" int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1,
-                                     const cusift_point *d_sift2, int num_pts2, float score_thresh,
-                                     float ambiguity_thresh, int type, int *d_pairs, float *d_coord, int *d_count) {
+// cusift_select_matches and cusift_select_mutual; `who` is the entry point's name in the messages
+static int select_impl(cusift_ctx *ctx, const char *who, bool mutual, const cusift_point *d_sift1, int num_pts1,
+                       const cusift_point *d_sift2, int num_pts2, float score_thresh, float ambiguity_thresh, int type,
+                       int *d_pairs, float *d_coord, int *d_count) {
   TRY(enter(ctx));
-  if (!d_count) return fail(CUSIFT_ERR_INVALID, "SelectMatches: NULL d_count");
-  TRY(check_dims("SelectMatches", "type", type));
+  if (!d_count) return fail(CUSIFT_ERR_INVALID, "%s: NULL d_count", who);
+  TRY(check_dims(who, "type", type));
   if (num_pts1 < 0 || num_pts2 < 0 || num_pts1 > (1 << 26))
-    return fail(CUSIFT_ERR_INVALID, "SelectMatches: num_pts1 %d outside [0, 2^26] or num_pts2 %d < 0", num_pts1, num_pts2);
-  TRY(check_not_nan("SelectMatches", score_thresh, ambiguity_thresh));
+    return fail(CUSIFT_ERR_INVALID, "%s: num_pts1 %d outside [0, 2^26] or num_pts2 %d < 0", who, num_pts1, num_pts2);
+  TRY(check_not_nan(who, score_thresh, ambiguity_thresh));
   if (num_pts1 == 0) {
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
     return CUSIFT_OK;
   }
   if (!d_sift1 || (!d_sift2 && num_pts2 > 0) || !d_pairs || !d_coord)
-    return fail(CUSIFT_ERR_INVALID, "SelectMatches: missing data");
+    return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
   // the per-workgroup keep counts
   TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, sizeof(int) * (size_t)idiv_up(num_pts1, 256),
                    "", false));
-  select_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, type,
+  select_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, type | (mutual ? 2 : 0),
                 (int *)ctx->register_scratch, d_pairs, d_coord, d_count);
-  return check_launch("select_matches");
+  return check_launch(mutual ? "select_mutual" : "select_matches");
+}
+
+extern "C" int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1,
+                                     const cusift_point *d_sift2, int num_pts2, float score_thresh,
+                                     float ambiguity_thresh, int type, int *d_pairs, float *d_coord, int *d_count) {
+  return select_impl(ctx, "SelectMatches", false, d_sift1, num_pts1, d_sift2, num_pts2, score_thresh, ambiguity_thresh,
+                     type, d_pairs, d_coord, d_count);
+}
+
+// cusift_select_matches plus the cross-check: record i is kept only if d_sift2[match].match == i
+extern "C" int cusift_select_mutual(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1,
+                                    const cusift_point *d_sift2, int num_pts2, float score_thresh,
+                                    float ambiguity_thresh, int type, int *d_pairs, float *d_coord, int *d_count) {
+  return select_impl(ctx, "SelectMutual", true, d_sift1, num_pts1, d_sift2, num_pts2, score_thresh, ambiguity_thresh,
+                     type, d_pairs, d_coord, d_count);
 }
 
 extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const uint16_t *d_depth1,
@@ -532,7 +599,7 @@ static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int ma
 // *d_pairs_out: the list on the device, for the stages behind it.  n_pairs >= 1, max_pts >= 1, the list is checked.
 static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
                               const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
-                              const int **d_pairs_out) {
+                              const int **d_pairs_out, cusift_match_row *d_rows_back = nullptr) {
   // Column splits, sized from max_pts (the counts stay on the device): aim at >= 4 workgroups per CU over all pairs,
   // keep >= 4 LDS tiles (128 columns) per split.  max_pts <= 2^20 records fit one split's 32-bit byte offsets.
   const int row_blocks = idiv_up(max_pts, 64);
@@ -544,21 +611,36 @@ static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, con
   splits = idiv_up(max_pts, cols_per_split);
   const int n1_pad = row_blocks * 64;
   const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
-  const size_t part_b = splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0;
-  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b, "", false));
+  const size_t part_b = align_up_sz(splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0, 256);
+  // the column side (cusift_match_batch_mutual): [pair][row block][max_pts] partials when there is more than one row block
+  const size_t col_b = d_rows_back && row_blocks > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * row_blocks * max_pts : 0;
+  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b + col_b, "", false));
   int *d_pairs = (int *)ctx->pairs_scratch;
   MatchPartial *partials = splits > 1 ? (MatchPartial *)(ctx->pairs_scratch + list_b) : nullptr;
+  MatchPartial *col_partials = col_b ? (MatchPartial *)(ctx->pairs_scratch + list_b + part_b) : nullptr;
   HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
   const dim3 grid(row_blocks, splits, n_pairs);
-  if (distance)
+  if (d_rows_back) {
+    if (distance)
+      hipLaunchKernelGGL(match_batch_mutual_kernel<true>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
+                         d_pairs, cols_per_split, partials, n1_pad, d_rows, col_partials, d_rows_back);
+    else
+      hipLaunchKernelGGL(match_batch_mutual_kernel<false>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
+                         d_pairs, cols_per_split, partials, n1_pad, d_rows, col_partials, d_rows_back);
+  } else if (distance) {
     hipLaunchKernelGGL(match_batch_kernel<true>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
                        cols_per_split, partials, n1_pad, d_rows);
-  else
+  } else {
     hipLaunchKernelGGL(match_batch_kernel<false>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
                        cols_per_split, partials, n1_pad, d_rows);
+  }
   if (splits > 1)
     hipLaunchKernelGGL(match_batch_merge_kernel, dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream,
                        d_counters, max_pts, d_pairs, distance, cols_per_split, partials, n1_pad, splits, d_rows);
+  if (col_partials)
+    hipLaunchKernelGGL(match_batch_mutual_merge_kernel, dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream,
+                       d_counters, max_pts, d_pairs, distance, (const MatchPartial *)col_partials, row_blocks,
+                       d_rows_back);
   *d_pairs_out = d_pairs;
   return check_launch("match_batch");
 }
@@ -573,6 +655,21 @@ extern "C" int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points,
   if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatch: missing data");
   const int *d_pairs = nullptr;
   return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs);
+}
+
+// cusift_match_batch with the column side of every pair in d_rows_back (sift_match.hip: match_batch_mutual_kernel)
+extern "C" int cusift_match_batch_mutual(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                         int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                         cusift_match_row *d_rows, cusift_match_row *d_rows_back) {
+  TRY(enter(ctx));
+  TRY(check_distance("MatchBatchMutual", distance));
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "MatchBatchMutual"));
+  if (!d_rows_back) return fail(CUSIFT_ERR_INVALID, "MatchBatchMutual: NULL d_rows_back");
+  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatchMutual: missing data");
+  const int *d_pairs = nullptr;
+  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs,
+                            d_rows_back);
 }
 
 extern "C" int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_points, const unsigned int *d_counters,

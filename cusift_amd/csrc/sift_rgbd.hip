@@ -22,8 +22,8 @@
 //
 // THE SELECTION keeps record i of frame 1 iff score < score_thresh2 && ambiguity < ambiguity_thresh2 && 0 <= match < n2
 // and, for the 3-D type, coords3D[2] != 0 on both sides -- the comparisons of include/matching.h:43-58 in the same
-// precision.  Order-preserving compaction without atomics: every 256-record workgroup counts its keeps (ballot +
-// popcount), the second launch sums the counts of the workgroups before it (a fixed tree), ranks its own keeps with
+// precision; cusift_select_mutual adds the cross-check sift2[match].match == i.
+// Order-preserving compaction without atomics: every 256-record workgroup counts its keeps (ballot + popcount), the second launch sums the counts of the workgroups before it (a fixed tree), ranks its own keeps with
 // ballot + mbcnt inside a wave and a 4-entry scan across its waves, and writes.  Same input, same output, every run.
 // Kernels use no scratch memory and write with vector stores only.
 #include "sift_device.h"
@@ -59,7 +59,8 @@ __global__ void __launch_bounds__(256) rgbd_lift_kernel(cusift_point *__restrict
   pt->coords3D[2] = Z;
 }
 
-// include/matching.h:47-49
+// include/matching.h:47-49.  `type3d`: bit 0 the 3-D type, bit 1 (cusift_select_mutual) the cross-check -- the partner's
+// own match must name record i.
 __device__ __forceinline__ bool match_selected(const cusift_point *__restrict__ sift1, int i, int n1,
                                                const cusift_point *__restrict__ sift2, int n2, float score_thresh2,
                                                float ambiguity_thresh2, int type3d, int &partner) {
@@ -69,7 +70,8 @@ __device__ __forceinline__ bool match_selected(const cusift_point *__restrict__ 
   if (!(p->score < score_thresh2 && p->ambiguity < ambiguity_thresh2)) return false;
   const int m = p->match;
   if (m < 0 || m >= n2) return false;
-  if (type3d && !(p->coords3D[2] != 0.0f && sift2[m].coords3D[2] != 0.0f)) return false;
+  if ((type3d & 1) && !(p->coords3D[2] != 0.0f && sift2[m].coords3D[2] != 0.0f)) return false;
+  if ((type3d & 2) && sift2[m].match != i) return false;
   partner = m;
   return true;
 }

@@ -24,6 +24,24 @@ extern "C" {
  * (:318-349) and stay on the caller's side (include/matching.h does it).  Asynchronous on the context's stream. */
 int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
                  int distance);
+/* Mutual nearest neighbours: both directions from ONE pass over the scores S[i][j] (the k-ordered MFMA chain of
+ * cusift_match, from the same text; for distance 1 the same 2 - 2 dot / 999 transform).
+ * ROW SIDE: score, ambiguity, match, match_xpos, match_ypos of d_sift1[0 .. num_pts1) receive exactly the bytes
+ * cusift_match(d_sift1, num_pts1, d_sift2, num_pts2, distance) writes (the same scan, tree and column splits;
+ * CUSIFT_POLICY_MATCH_SPLITS is honoured the same way).
+ * COLUMN SIDE: the same five fields of d_sift2[j], j in [0, num_pts2), by this model: scan the rows i = 0, 1, ...,
+ * num_pts1 - 1 in ascending order from (best, second, match) = (init, init, -1), init = 999 for distance 1 and -1 for
+ * distance 0, with strict compares -- a score that beats best moves best to second and takes its place, otherwise a
+ * score that beats second replaces it; a NaN score changes nothing.  So `match` is the LOWEST row among exactly tied best
+ * scores, and a tie for best gives second == best.  score = best; ambiguity as cusift_match computes it (the 1e-6 is a
+ * double); match_xpos / match_ypos = coords2D of d_sift1[match], of record 0 when match is outside [0, num_pts1).  The
+ * result does not depend on the split count or the grid: the same input gives the same bytes on every run (no atomics).
+ * Nothing but these fields of these records is written.  A count <= 0 on either side: CUSIFT_OK, nothing enqueued, no
+ * record of either set touched.  Scratch (12 bytes per row block of 64 and column) lives in the context.
+ * CUSIFT_ERR_INVALID (nothing enqueued): what cusift_match refuses, and record ranges of d_sift1 and d_sift2 that overlap
+ * -- both are written; match a set against a copy of itself.  Asynchronous on the context's stream. */
+int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, cusift_point *d_sift2, int num_pts2,
+                        int distance);
 /* cudaMemcpy2D device->host (extras/matching.cu:311-315 copies the 5 match fields of every record); blocking. */
 int cusift_memcpy2d_d2h(cusift_ctx *ctx, void *h_dst, size_t dst_pitch, const void *d_src, size_t src_pitch,
                         size_t width_bytes, size_t rows);
@@ -161,6 +179,12 @@ int cusift_lift_depth(cusift_ctx *ctx, cusift_point *d_points, const unsigned in
 int cusift_select_matches(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
                           int num_pts2, float score_thresh, float ambiguity_thresh, int type /* 0 = 2D, 1 = 3D */,
                           int *d_pairs, float *d_coord, int *d_count);
+/* cusift_select_matches with the cross-check as one more condition: record i is kept only if, besides the above,
+ * d_sift2[match].match == i (the fields as they stand, whatever wrote them: cusift_match_mutual, or cusift_match in both
+ * directions).  The same outputs, order, argument checks and absence of atomics. */
+int cusift_select_mutual(cusift_ctx *ctx, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                         int num_pts2, float score_thresh, float ambiguity_thresh, int type /* 0 = 2D, 1 = 3D */,
+                         int *d_pairs, float *d_coord, int *d_count);
 /* The selection behind cusift_ctx_set_keep_strongest (cusift_amd.h has the total order) as a stage of its own, on lists
  * of 64-byte record heads (the first 16 floats of a cusift_point: coords2D .. subsampling) as the staged detections leave them.
  * d_heads is [list][image][capacity] x 64 B; d_counts is [list][image]: on input the counts held (the call clamps them at
@@ -220,6 +244,18 @@ typedef struct {
 int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
                        int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
                        cusift_match_row *d_rows);
+
+/* cusift_match_batch with both directions from one pass (cusift_match_mutual over a pair list).  d_rows is exactly what
+ * cusift_match_batch writes.  d_rows_back[p * max_pts + j] = score, ambiguity and match (an index into frame 1) of
+ * record j of pair p's frame 2 by the column-side model of cusift_match_mutual over the records of frame 1 (lowest row on
+ * exactly tied best scores; independent of the split count).  Rows past frame 2's count are not written, and a pair whose
+ * frame 1 has no record writes no back row.  The records are not written; (a, a) is legal.  The counts are read on the
+ * device and the launch count does not depend on the list.  d_rows_back: device memory, [n_pairs][max_pts], 16-byte
+ * aligned, distinct from d_rows.
+ * CUSIFT_ERR_INVALID (nothing enqueued): every case of cusift_match_batch, and a NULL d_rows_back. */
+int cusift_match_batch_mutual(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
+                              int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
+                              cusift_match_row *d_rows, cusift_match_row *d_rows_back);
 
 /* cusift_register_rgbd for every pair of a list, device-resident from the extractor's batch + depth images to one
  * [R | t] per pair: ONE cusift_lift_depth over all frames (frame k's depth image at d_depth + k * image_stride_elems),

@@ -59,4 +59,47 @@ inline std::vector<SiftMatch *> MatchSiftData(SiftData &data1, SiftData &data2,
   return matches;
 }
 
+// MatchSiftData with the cross-check (not in the reference): one cusift_match_mutual() fills the match fields of BOTH
+// sets -- data1's as MatchSiftData does, data2's with its best and second best in data1 (the lowest record on exactly
+// tied best scores) -- and a pair (i, j) is returned only if it passes MatchSiftData's filter and record j's match is i.
+// Both SiftData need host AND device buffers; both host copies are synchronised.  The two sets must be distinct.
+inline std::vector<SiftMatch *> MatchSiftDataMutual(SiftData &data1, SiftData &data2,
+                                                    MatchSiftDistance distance = MatchSiftDistanceL2,
+                                                    float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                                    MatchType type = MatchType2D) {
+  std::vector<SiftMatch *> matches;
+  if (!data1.numPts || !data2.numPts) return matches;
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match_mutual(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
+                               reinterpret_cast<cusift_point *>(data2.d_data), data2.numPts,
+                               distance == MatchSiftDistanceL2 ? 1 : 0));
+  if (data1.h_data == nullptr || data2.h_data == nullptr) {
+    safeCall(cusift_ctx_synchronize(ctx));
+    return matches;
+  }
+  safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score, sizeof(SiftPoint),
+                               5 * sizeof(float), (size_t)data1.numPts));
+  safeCall(cusift_memcpy2d_d2h(ctx, &data2.h_data[0].score, sizeof(SiftPoint), &data2.d_data[0].score, sizeof(SiftPoint),
+                               5 * sizeof(float), (size_t)data2.numPts));
+  const float thresh2 = scoreThreshold * scoreThreshold;
+  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
+  for (int i = 0; i < data1.numPts; i++) {
+    SiftPoint &p = data1.h_data[i];
+    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
+    if (p.match < 0 || p.match >= data2.numPts) continue;
+    SiftPoint &q = data2.h_data[p.match];
+    if (type == MatchType3D && !(p.coords3D[2] != 0 && q.coords3D[2] != 0)) continue;
+    if (q.match != i) continue;  // the cross-check
+    SiftMatch *m = new SiftMatch();
+    m->pt1 = &p;
+    m->pt2 = &q;
+    m->score = p.score;
+    m->ambiguity = p.ambiguity;
+    m->error = 0.0f;
+    matches.push_back(m);
+  }
+  return matches;
+}
+
 #endif  // CUSIFT_AMD_MATCHING_H
