@@ -57,6 +57,7 @@ cpp-tests: $(LIB)
 	$(MAKE) -C $(ROOT)/tests/cpp_planar_batch
 	$(MAKE) -C $(ROOT)/tests/cpp_keep_strongest
 	$(MAKE) -C $(ROOT)/tests/cpp_mutual
+	$(MAKE) -C $(ROOT)/tests/cpp_cross_check
 
 check: cpp-tests
 	$(MAKE) -C $(ROOT)/tests/cpp check

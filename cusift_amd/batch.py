@@ -18,10 +18,12 @@ class BatchExtractor:
         counts  int32  [n]                 raw counters; valid points = min(count, max_pts)
     keep_strongest = K > 0: every image keeps its K strongest keypoints (cusift_ctx_set_keep_strongest; K <= max_pts),
     selected on the device before anything is described; counts are then the kept counts.
+    cross_check = True: register_planar, register_planar_sequence and register_sequence feed their RANSAC mutual
+    matches only (cusift_ctx_set_cross_check on this extractor's context).
     """
 
     def __init__(self, n_images, w, h, params=None, device=None, pitch=None, n_slots=1, keep_strongest=0,
-                 **param_overrides):
+                 cross_check=False, **param_overrides):
         if not torch.cuda.is_available():
             raise capi.CusiftError("BatchExtractor needs a GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -30,11 +32,14 @@ class BatchExtractor:
         self.params = params if params is not None else capi.default_params(**param_overrides)
         self.max_pts = self.params.max_pts
         self.keep_strongest = capi.check_keep_strongest(keep_strongest, self.max_pts)
+        self.cross_check = bool(capi.check_cross_check(cross_check))
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream()
             self.ctx = capi.Context(self.device.index, stream=self.stream.cuda_stream)
             if self.keep_strongest:
                 self.ctx.set_keep_strongest(self.keep_strongest)
+            if self.cross_check:
+                self.ctx.set_cross_check(True)
             self.ctx.reserve(self.n, self.w, self.h, self.params)
             # n_slots > 1: output ring, so that a consumer (D2H copy, all-gatherv on another stream) can still
             # read step i's SiftData while step i+1 is being extracted

@@ -165,6 +165,7 @@ SIGNATURES = {
     "cusift_pipe_destroy": (_i, [_vp]),
     "cusift_ctx_set_policy": (_i, [_vp, _i, _i]),
     "cusift_ctx_set_keep_strongest": (_i, [_vp, _i]),
+    "cusift_ctx_set_cross_check": (_i, [_vp, _i]),
     "cusift_ctx_get_policy": (_i, [_vp, _i, C.POINTER(C.c_int)]),
     "cusift_ctx_arena_bytes": (_sz, [_vp]),
     "cusift_ctx_forks": (C.c_ulong, [_vp]),
@@ -382,6 +383,14 @@ def check_scale_up_args(d_dst, dst_pitch, d_src, w, h, src_pitch, n_images=1, ds
     if n_images > 1 and (src_stride < h * int(src_pitch) or dst_stride < 2 * h * int(dst_pitch)):
         raise ValueError("scale_up: image stride too small")
     return dst_stride, src_stride
+
+
+def check_cross_check(on):
+    """What Context.set_cross_check checks before it calls the library (needs no device): returns 0 or 1.  ValueError
+    for anything but a bool, 0 or 1."""
+    if not isinstance(on, (bool, int, np.integer)) or on not in (0, 1):
+        raise ValueError("cross_check: False / True (0 / 1), got %r" % (on,))
+    return int(on)
 
 
 def check_keep_strongest(k, max_pts=None):
@@ -785,6 +794,13 @@ class Context:
         K > max_pts is refused by the extraction."""
         k = check_keep_strongest(k)
         check(lib().cusift_ctx_set_keep_strongest(self.handle, k))
+
+    def set_cross_check(self, on):
+        """cusift_ctx_set_cross_check: while on, register_planar, register_rgbd, register_planar_batch and
+        register_rgbd_batch on this context keep mutual matches only -- record i of frame 1 takes part only if the
+        column side's best for its match is i (the lowest record on exactly tied best scores).  register_planar then
+        writes the match fields of d_sift2 as well and refuses overlapping record ranges.  Nothing else changes."""
+        check(lib().cusift_ctx_set_cross_check(self.handle, check_cross_check(on)))
 
     def select_strongest(self, d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
         """cusift_select_strongest: the selection alone, on lists of 64-byte record heads.  d_heads [n_lists, n_images,

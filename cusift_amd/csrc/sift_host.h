@@ -73,19 +73,20 @@ __global__ void match_batch_mutual_kernel(const cusift_point *, const unsigned i
 __global__ void match_batch_mutual_merge_kernel(const unsigned int *, int, const int *, int, const MatchPartial *, int,
                                                 cusift_match_row *);
 __global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
-                                       const cusift_match_row *, float, float, int, int *, float *, int *);
+                                       const cusift_match_row *, float, float, int, int *, float *, int *,
+                                       const cusift_match_row *);
 __global__ void homography_gather_kernel(const cusift_point *, int, float *);
 __global__ void homography_solve_kernel(const float *, int, int *, int, float *, int, unsigned long long, const int *,
                                         const int *, int *, PlanarBatch);
 __global__ void planar_mark_kernel(const cusift_point *, int, int, int, float, float, float *, unsigned char *, int *,
-                                   PlanarBatch);
+                                   PlanarBatch, const cusift_point *);
 __global__ void planar_compact_kernel(const unsigned char *, int, const int *, int *, int *, PlanarBatch);
 __global__ void planar_score_kernel(const float *, int, int, const float *, int, float, int *, const int *, PlanarBatch);
 __global__ void planar_select_kernel(cusift_point *, int, const float *, const unsigned char *, const float *, const int *,
                                      int, float, int, float, float *, char *, float *, PlanarBatch);
 __global__ void sequence_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                      const cusift_match_row *, int, float, float, float *, unsigned char *, int *, int *,
-                                     PlanarBatch);
+                                     PlanarBatch, const cusift_match_row *);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
 template <bool k3D>
 __global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *,
@@ -217,6 +218,7 @@ struct cusift_ctx {
   bool side_probed = false;  // `side` passed the concurrency probe (policy value 2 accepts no other)
   bool recording = false;  // inside cusift_graph_create's capture
   int keep_strongest = 0;  // cusift_ctx_set_keep_strongest: K > 0, every extraction keeps the K strongest keypoints per image
+  int cross_check = 0;     // cusift_ctx_set_cross_check: 1, the four cusift_register_* calls keep mutual matches only
   unsigned long forks = 0;  // extractions that took the side stream
   // the lists' counters in the arena that the last extraction's join_counts_kernel left zero (stream order): the next
   // extraction that uses exactly them skips its memset.  Anything else that writes the arena resets this.

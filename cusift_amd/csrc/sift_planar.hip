@@ -27,7 +27,10 @@
 //
 // CANDIDATES.  rule 0: score > lo && ambiguity < hi (FindHomography, :218-219; dot-product distance).  rule 1: score <
 // lo^2 && ambiguity < hi^2 (cusift_select_matches type 0; L2 distance; the squares arrive computed in fp32).  Both: finite
-// coords2D / match_xpos / match_ypos and, when num_pts2 >= 0, 0 <= match < num_pts2.
+// coords2D / match_xpos / match_ypos and, when num_pts2 >= 0, 0 <= match < num_pts2.  With the context's cross-check on,
+// the registrations add `mutual`: 0 <= match < num_pts2 and record `match` of image 2 names this record as ITS best (the
+// column side of cusift_match_mutual; an exactly tied best keeps the lowest record of image 1) -- for the candidates and
+// for the refit set, rule 0's literal predicate included.
 //
 // SAMPLING extends the recipe of sift_rigid.hip to four slots (same mix):
 //     draw k of loop l = cand[(mix(seed ^ mix((l << 32) | k)) >> 32) mod n_cand]
@@ -66,12 +69,15 @@ __device__ __forceinline__ int planar_count(const int *__restrict__ head, int nu
   return nb.count ? min(head[kPlanarHeadCount], num_pts) : num_pts;
 }
 
-// coord [4][num_pts], fitset [num_pts], block_counts [ceil(num_pts / 256)]
+// coord [4][num_pts], fitset [num_pts], block_counts [ceil(num_pts / 256)].  pts2 != NULL (cusift_ctx_set_cross_check): the
+// num_pts2 records of image 2 with cusift_match_mutual's fields; a record that is not its partner's match is neither a
+// candidate nor in the refit set, under either rule.
 __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusift_point *__restrict__ pts, int num_pts,
                                                                      int num_pts2, int rule, float lo, float hi,
                                                                      float *__restrict__ coord,
                                                                      unsigned char *__restrict__ marks,
-                                                                     int *__restrict__ block_counts, PlanarBatch nb) {
+                                                                     int *__restrict__ block_counts, PlanarBatch nb,
+                                                                     const cusift_point *__restrict__ pts2) {
   __shared__ int s_wave[kPlanarThreads / 64];
   pts += (size_t)blockIdx.z * nb.records;
   coord = planar_pair(coord, nb.scratch), marks = planar_pair(marks, nb.scratch);
@@ -92,7 +98,12 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusif
     cand = cand && planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
     cand = cand && (num_pts2 < 0 || (m >= 0 && m < num_pts2));
     // the refit's point set: ImproveHomography's literal predicate (:286) under rule 0, the candidates under rule 1
-    const bool fit = rule == 0 ? !(score < lo || amb > hi) : cand;
+    bool fit = rule == 0 ? !(score < lo || amb > hi) : cand;
+    if (pts2) {  // the cross-check: the partner's own match (cusift_match_mutual's column side) must name record i
+      const bool mutual = m >= 0 && m < num_pts2 && pts2[m].match == i;
+      cand = cand && mutual;
+      fit = fit && mutual;
+    }
     marks[i] = (unsigned char)((cand ? 1 : 0) | (fit ? 2 : 0));
   }
   const unsigned long long m = __ballot(cand);

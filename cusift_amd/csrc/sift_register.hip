@@ -20,6 +20,14 @@ static int check_thresh2(const char *who, float thresh2) {
 static int check_not_nan(const char *who, float a, float b) {
   return std::isnan(a) || std::isnan(b) ? fail(CUSIFT_ERR_INVALID, "%s: a threshold is NaN", who) : CUSIFT_OK;
 }
+// the mutual matcher writes both record sets: their ranges must not overlap
+static int check_disjoint(const char *who, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                          int num_pts2) {
+  const uintptr_t a = (uintptr_t)d_sift1, b = (uintptr_t)d_sift2;
+  if (a < b + sizeof(cusift_point) * (size_t)num_pts2 && b < a + sizeof(cusift_point) * (size_t)num_pts1)
+    return fail(CUSIFT_ERR_INVALID, "%s: the two record ranges overlap (both are written; match a copy)", who);
+  return CUSIFT_OK;
+}
 
 // word `word` of a result head that was read back (sift_types.h names the words)
 static int head_int(const char *head, int word) {
@@ -87,9 +95,7 @@ extern "C" int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int n
   if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // nothing to match, on either side
   if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchMutual: missing data");
   TRY(check_distance("MatchMutual", distance));
-  const uintptr_t a = (uintptr_t)d_sift1, b = (uintptr_t)d_sift2;
-  if (a < b + sizeof(cusift_point) * (size_t)num_pts2 && b < a + sizeof(cusift_point) * (size_t)num_pts1)
-    return fail(CUSIFT_ERR_INVALID, "MatchMutual: the two record ranges overlap (both are written; match a copy)");
+  TRY(check_disjoint("MatchMutual", d_sift1, num_pts1, d_sift2, num_pts2));
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits, cols_per_split;
   TRY(match_split_plan(ctx, num_pts1, num_pts2, &splits, &cols_per_split));
@@ -258,10 +264,11 @@ static void planar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, in
                      refine_thresh * refine_thresh, d_head, d_flags, d_err, nb);
 }
 
-// The five launches and the one read-back; the arguments are checked.
+// The five launches and the one read-back; the arguments are checked.  d_cross != NULL: the cross-check against the
+// num_pts2 records of image 2, which carry cusift_match_mutual's fields.
 static int planar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
                       int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                      const PlanarOut &o) {
+                      const PlanarOut &o, const cusift_point *d_cross) {
   if (num_pts < 8) {  // extras/homography.cu:205: the answer needs no device work
     planar_identity(num_pts, num_loops, o);
     return CUSIFT_OK;
@@ -277,7 +284,7 @@ static int planar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int nu
   const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
   hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream,
                      (const cusift_point *)d_sift, num_pts, num_pts2, rule, t_lo, t_hi, at<float>(d_block, b.coord),
-                     at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), PlanarBatch{});
+                     at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), PlanarBatch{}, d_cross);
   planar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
                 base + flag_off, nullptr, 1, PlanarBatch{});
   TRY(check_launch("estimate_homography"));
@@ -313,7 +320,8 @@ extern "C" int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift,
   const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
                     best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
   TRY(planar_check("EstimateHomography", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
-  return planar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed, o);
+  return planar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed, o,
+                    nullptr);
 }
 
 extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
@@ -328,9 +336,16 @@ extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, in
   TRY(planar_check("RegisterPlanar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
   TRY(check_distance("RegisterPlanar", distance));
   if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterPlanar: missing data");
-  TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));  // stays enqueued with fewer than 8 records too
+  // the matcher stays enqueued with fewer than 8 records too.  Cross-check (cusift_ctx_set_cross_check): the mutual
+  // matcher writes the match fields of d_sift2 as well -- the parameter keeps its const spelling for the callers -- and
+  // refuses overlapping ranges before it enqueues anything
+  const bool cross = ctx->cross_check != 0;
+  if (cross)
+    TRY(cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance));
+  else
+    TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
   return planar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed,
-                    o);
+                    o, cross ? d_sift2 : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -530,6 +545,8 @@ extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int 
   if ((num_pts1 > 0 && (!d_sift1 || !d_depth1)) || (num_pts2 > 0 && (!d_sift2 || !d_depth2)))
     return fail(CUSIFT_ERR_INVALID, "RegisterRGBD: missing data");
   TRY(check_depth_geometry(width, height, pitch_elems, 0, 1, "RegisterRGBD"));
+  const bool cross = ctx->cross_check != 0;  // cusift_ctx_set_cross_check: refuse what the mutual matcher refuses, first
+  if (cross && num_pts1 > 0 && num_pts2 > 0) TRY(check_disjoint("RegisterRGBD", d_sift1, num_pts1, d_sift2, num_pts2));
   const int n1 = num_pts1;
   // [head | flags | pairs] is what travels back, in one copy; behind it what stays on the device, the selection's count
   // in a 256-byte slot of its own at the end
@@ -561,9 +578,13 @@ extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int 
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // blocking like the full route: the depth images may be freed
     return CUSIFT_OK;
   }
-  TRY(cusift_match(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
-  select_launch(ctx, d_sift1, n1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, 1, at<int>(base, block_off),
-                at<int>(base, pair_off), d_coord, d_count);
+  // cross-check (cusift_ctx_set_cross_check): both directions from the one pass, then the selection's cross-check bit
+  if (cross)
+    TRY(cusift_match_mutual(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
+  else
+    TRY(cusift_match(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
+  select_launch(ctx, d_sift1, n1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, cross ? 1 | 2 : 1,
+                at<int>(base, block_off), at<int>(base, pair_off), d_coord, d_count);
   rigid_launch(ctx, d_coord, n1, d_count, at<int>(base, idx_off), num_loops, 1, thresh2, rigid_type, seed,
                at<float>(base, rt_off), at<int>(base, cnt_off), (float *)base, base + flag_off);
   TRY(check_launch("register_rgbd"));
@@ -711,19 +732,22 @@ extern "C" int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_point
   const size_t rt_off = s.take(sizeof(float) * 12 * P * L);
   const size_t cnt_off = s.take(sizeof(int) * P * L);
   const size_t idx_off = s.take(sizeof(int) * 3 * P * L);
+  // cross-check (cusift_ctx_set_cross_check): the matcher's back rows, behind everything else
+  const size_t back_off = ctx->cross_check ? s.take(sizeof(cusift_match_row) * P * M) : 0;
   TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
   char *base = ctx->register_scratch;
   float *d_coord = at<float>(base, coord_off);
   int *d_count = at<int>(base, count_off);
   cusift_match_row *d_rows = at<cusift_match_row>(base, row_off);
+  cusift_match_row *d_rows_back = ctx->cross_check ? at<cusift_match_row>(base, back_off) : nullptr;
   hipLaunchKernelGGL(rgbd_lift_kernel, dim3(idiv_up(max_pts, 256), n_images), dim3(256), 0, ctx->stream, d_points,
                      d_counters, max_pts, (const unsigned short *)d_depth, width, height, pitch_elems,
                      image_stride_elems, *camera);
   const int *d_pairs = nullptr;
-  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs));
+  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, d_rows_back));
   hipLaunchKernelGGL(sequence_select_kernel, dim3(n_pairs), dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
                      d_pairs, d_rows, score_thresh * score_thresh, ambiguity_thresh * ambiguity_thresh, 1,
-                     at<int>(base, pair_off), d_coord, d_count);
+                     at<int>(base, pair_off), d_coord, d_count, (const cusift_match_row *)d_rows_back);
   RigidBatch nb;
   nb.coord = 6 * M, nb.indices = 3 * L, nb.rt = 12 * L, nb.counts = L, nb.head = kRigidHeadWords, nb.flags = M, nb.count = 1;
   rigid_launch(ctx, d_coord, max_pts, d_count, at<int>(base, idx_off), num_loops, 1, thresh2, rigid_type, seed,
@@ -774,7 +798,7 @@ extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point 
     return CUSIFT_OK;
   }
   // [heads | flags | errors] is what travels back, in one copy; behind it what stays on the device: one PlanarBlock per
-  // pair, then the match rows
+  // pair, then the match rows and -- with the cross-check (cusift_ctx_set_cross_check) -- the matcher's back rows
   const PlanarBlock b(max_pts, num_loops);
   ScratchLayout s;
   s.take(kPlanarHeadBytes * P);  // the heads, at 0
@@ -782,18 +806,20 @@ extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point 
   const size_t err_off = s.take(sizeof(float) * P * M);
   const size_t block_off = s.take(b.bytes * P);
   const size_t row_off = s.take(sizeof(cusift_match_row) * P * M);
+  const size_t back_off = ctx->cross_check ? s.take(sizeof(cusift_match_row) * P * M) : 0;
   TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
   char *base = ctx->register_scratch, *d_block = base + block_off;
   cusift_match_row *d_rows = at<cusift_match_row>(base, row_off);
+  cusift_match_row *d_rows_back = ctx->cross_check ? at<cusift_match_row>(base, back_off) : nullptr;
   PlanarBatch nb;
   nb.records = 0, nb.scratch = b.bytes, nb.head = kPlanarHeadBytes, nb.flags = M, nb.count = 1;
   const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
   const int *d_pairs = nullptr;
-  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs));
+  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, d_rows_back));
   hipLaunchKernelGGL(sequence_mark_kernel, dim3(idiv_up(max_pts, 256), 1, n_pairs), dim3(256), 0, ctx->stream, d_points,
                      d_counters, max_pts, d_pairs, (const cusift_match_row *)d_rows, rule, t_lo, t_hi,
                      at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks),
-                     (int *)base, nb);
+                     (int *)base, nb, (const cusift_match_row *)d_rows_back);
   planar_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
                 base + flag_off, at<float>(base, err_off), n_pairs, nb);
   TRY(check_launch("register_planar_batch"));

@@ -27,6 +27,12 @@
 // row and two coords2D per record.  Candidates and the refit's set follow planar_mark_kernel's predicates with num_pts2
 // = n2.  A pair whose frame 2 is empty has no row (the matcher wrote none): no candidate, nothing read.  The records are
 // never written.
+//
+// THE CROSS-CHECK (cusift_ctx_set_cross_check).  Both kernels take rows_back[pair][max_pts], the column side that
+// cusift_match_batch_mutual's kernels leave (NULL = off): record i stays only if back row `match` names i.  The matcher
+// writes back rows 0 .. n2 - 1 of a pair with n1 > 0 and n2 > 0 and none otherwise; a back row is read only for a record
+// i < n1 with 0 <= match < n2, inside the n2 > 0 branch, so no unwritten row is ever read.  In a self pair (a, a) every
+// record is its own best in both directions.
 // No scratch memory, vector stores only.
 #include "sift_device.h"
 
@@ -39,7 +45,7 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
     const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
     const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, float score_thresh2,
     float ambiguity_thresh2, int type3d, int *__restrict__ sel_pairs, float *__restrict__ coord,
-    int *__restrict__ sel_count) {
+    int *__restrict__ sel_count, const cusift_match_row *__restrict__ rows_back) {
   __shared__ int s_wave[kSequenceSelectThreads / 64];
   const int tx = threadIdx.x;
   const int pair = blockIdx.x;
@@ -48,6 +54,7 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
   const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
   const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
   rows += (size_t)pair * max_pts;
+  if (rows_back) rows_back += (size_t)pair * max_pts;
   sel_pairs += 2 * (size_t)pair * max_pts;
   coord += 6 * (size_t)pair * max_pts;
   int base = 0;
@@ -61,6 +68,8 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
       const int m = __float_as_int(row[2]);
       keep = row[0] < score_thresh2 && row[1] < ambiguity_thresh2 && m >= 0 && m < n2;
       if (keep && type3d) keep = sift1[i].coords3D[2] != 0.0f && sift2[m].coords3D[2] != 0.0f;
+      // the cross-check: back row m was written (n1 > 0, m < n2) and must name record i
+      if (keep && rows_back) keep = __float_as_int((*reinterpret_cast<const f4 *>(rows_back + m))[2]) == i;
       partner = keep ? m : -1;
     }
     const unsigned long long mask = __ballot(keep);
@@ -95,7 +104,7 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
     const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
     const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, int rule, float lo, float hi,
     float *__restrict__ coord, unsigned char *__restrict__ marks, int *__restrict__ block_counts, int *__restrict__ head,
-    PlanarBatch nb) {
+    PlanarBatch nb, const cusift_match_row *__restrict__ rows_back) {
   __shared__ int s_wave[kSequenceSelectThreads / 64];
   const int tx = threadIdx.x;
   const int pair = blockIdx.z;
@@ -124,6 +133,12 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
       cand = rule == 0 ? (score > lo && amb < hi) : (score < lo && amb < hi);
       cand = cand && planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2) && valid;
       fit = rule == 0 ? !(score < lo || amb > hi) : cand;  // as planar_mark_kernel
+      if (rows_back) {  // the cross-check, as planar_mark_kernel: back row m was written (i < n1, m < n2)
+        const cusift_match_row *back = rows_back + (size_t)pair * max_pts + (valid ? m : 0);
+        const bool mutual = valid && __float_as_int((*reinterpret_cast<const f4 *>(back))[2]) == i;
+        cand = cand && mutual;
+        fit = fit && mutual;
+      }
     }
     coord[i] = x1;
     coord[i + max_pts] = y1;

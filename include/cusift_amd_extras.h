@@ -106,7 +106,11 @@ int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift, int num_pt
 
 /* cusift_match(d_sift1, d_sift2, distance) followed by cusift_estimate_homography(d_sift1, num_pts1, num_pts2, ...) with
  * ONE synchronisation, at the read-back: the same bits as the staged route in every output and in the records.  Also
- * CUSIFT_ERR_INVALID for an unknown distance. */
+ * CUSIFT_ERR_INVALID for an unknown distance.
+ * While cusift_ctx_set_cross_check is on, the matcher is cusift_match_mutual: THE MATCH FIELDS OF d_sift2 ARE WRITTEN
+ * (score, ambiguity, match, match_xpos, match_ypos; the parameter keeps its const spelling for source compatibility),
+ * overlapping record ranges are refused with CUSIFT_ERR_INVALID before anything is enqueued or written, and a record
+ * that is not mutual is neither a candidate nor a member of the refit set (see cusift_ctx_set_cross_check). */
 int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
                            int num_pts2, int distance, int rule, float lo, float hi, int num_loops, float thresh,
                            int refine_loops, float refine_thresh, uint64_t seed, float h_homography[9],
@@ -194,6 +198,24 @@ int cusift_select_mutual(cusift_ctx *ctx, const cusift_point *d_sift1, int num_p
  * capacity); asynchronous on the context's stream: the call does not synchronise. */
 int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_images, int capacity,
                             unsigned int *d_counts, int keep, unsigned int *d_kept);
+
+/* The cross-check of the registrations, a setting of the context (0 = off, the default; 1 = on; anything else:
+ * CUSIFT_ERR_INVALID, the setting unchanged).  It affects cusift_register_planar, cusift_register_rgbd,
+ * cusift_register_planar_batch and cusift_register_rgbd_batch and nothing else; with 0 they enqueue the launches and
+ * return the bytes they always did.  With 1, record i of frame 1 takes part only if it is MUTUAL: its match m lies in
+ * [0, n2) and the column side's best for record m of frame 2 is i -- the column side exactly as cusift_match_mutual /
+ * cusift_match_batch_mutual define it, so an exactly tied best keeps the lowest record of frame 1.  Every many-to-one
+ * match but one drops out before RANSAC draws.  The pair calls enqueue cusift_match_mutual in place of cusift_match
+ * (both record sets' match fields are written; overlapping ranges are refused before anything is enqueued), the planar
+ * marking drops a non-mutual record from the candidates and from the refit set under either rule, and the RGB-D
+ * selection is cusift_select_mutual's.  The pair-list forms take the column side from cusift_match_batch_mutual's back
+ * rows, kept in the context's scratch behind everything that is read back: the records stay unwritten, (a, a) stays legal
+ * (every record is then its own mutual match), a pair with an empty frame has no candidate as before, and pair p has the
+ * bits of the pair call with the setting on and seed + p.  Still one synchronisation, one read-back and no count read
+ * back; one more launch (the column merge) when a frame 1 has more than 64 record slots.  Scratch: the batch matcher's
+ * column partials take 12 bytes x n_pairs x ceil(max_pts / 64) x max_pts -- quadratic in max_pts: 12.7 GB for 64 frames
+ * (63 consecutive pairs) at max_pts 32768, 0.8 GB at 8192 -- plus 16 bytes x n_pairs x max_pts of back rows. */
+int cusift_ctx_set_cross_check(cusift_ctx *ctx, int on);
 
 /* Frame-to-frame registration of an RGB-D pair, device-resident from SiftData + depth to [R | t]: cusift_lift_depth
  * of both frames (one width x height image each, rows pitch_elems apart), cusift_match(distance), the 3-D selection

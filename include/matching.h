@@ -102,4 +102,11 @@ inline std::vector<SiftMatch *> MatchSiftDataMutual(SiftData &data1, SiftData &d
   return matches;
 }
 
+// The cross-check inside the registrations (not in the reference; cusift_ctx_set_cross_check): while on, RegisterPlanar,
+// RegisterRGBD and their ...Sequence forms (homography.h, rgbd.h) feed their RANSAC mutual matches only -- record i of
+// the first set must be the best of its own match, the lowest record on exactly tied best scores.  Acts on the calling
+// thread's implicit context, the one those calls use.  RegisterPlanar then writes the match fields of data2's device
+// records too.  MatchSiftData, MatchSiftDataMutual, FindHomography and EstimateRigidTransform do not change.
+inline void SetCrossCheck(bool on) { safeCall(cusift_ctx_set_cross_check(cusift_dropin::ctx(), on ? 1 : 0)); }
+
 #endif  // CUSIFT_AMD_MATCHING_H
