@@ -18,8 +18,8 @@ class BatchExtractor:
         counts  int32  [n]                 raw counters; valid points = min(count, max_pts)
     keep_strongest = K > 0: every image keeps its K strongest keypoints (cusift_ctx_set_keep_strongest; K <= max_pts),
     selected on the device before anything is described; counts are then the kept counts.
-    cross_check = True: register_planar, register_planar_sequence and register_sequence feed their RANSAC mutual
-    matches only (cusift_ctx_set_cross_check on this extractor's context).
+    cross_check = True: register_planar, register_epipolar, register_planar_sequence and register_sequence feed their
+    RANSAC mutual matches only (cusift_ctx_set_cross_check on this extractor's context).
     """
 
     def __init__(self, n_images, w, h, params=None, device=None, pitch=None, n_slots=1, keep_strongest=0,
@@ -124,6 +124,15 @@ class BatchExtractor:
         points, counts = self.slots[slot]
         n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
         return self.ctx.register_planar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
+
+    def register_epipolar(self, i, j, slot=0, **opts):
+        """Epipolar registration of frames i and j of the last extract() into `slot`: cusift_register_epipolar over this
+        extractor's device records (frame i's match fields and match_error are written).  The two counts are read with
+        one call.  **opts goes to capi.Context.register_epipolar (distance, rule, lo, hi, loops, thresh, refine_loops,
+        refine_thresh, seed, want_all).  Returns its EpipolarResult: x_j^T F x_i = 0.  Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
+        return self.ctx.register_epipolar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
 
     def register_planar_sequence(self, pairs=None, slot=0, **opts):
         """Planar registration of the frames of the last extract() into `slot` against each other:

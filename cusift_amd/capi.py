@@ -210,6 +210,10 @@ SIGNATURES = {
                                         C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
     "cusift_register_planar": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp,
                                     C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "cusift_estimate_fundamental": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp, C.POINTER(_i),
+                                         C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "cusift_register_epipolar": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp,
+                                      C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
     "cusift_estimate_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp,
                                    _vp, _vp]),
     "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
@@ -329,6 +333,11 @@ PlanarResult = collections.namedtuple("PlanarResult", "homography ransac num_can
 # P bool [count] inlier flags and P float32 [count] match errors (NaN where a pair has no fit: nothing was evaluated)
 PlanarBatchResult = collections.namedtuple("PlanarBatchResult", "homography ransac num_candidates num_matches num_fit "
                                            "best_loop counts inliers match_error")
+# what cusift_estimate_fundamental / cusift_register_epipolar return: fundamental (refined, float64 [9], row-major, x2^T F
+# x1 = 0), ransac (the winner, [9]), the counts, the winner's flags bool [num_pts] and, with want_all, drawn [8, L],
+# all_fundamentals float64 [9, L], all_counts [L]
+EpipolarResult = collections.namedtuple("EpipolarResult", "fundamental ransac num_candidates num_matches num_fit best_loop "
+                                        "inliers drawn all_fundamentals all_counts")
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
 
 
@@ -751,6 +760,45 @@ class Context:
         hi = 0.8 if hi is None else hi
         loops = int(loops)
         return self._planar(lambda *out: lib().cusift_register_planar(
+            self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, *out), n1, max(loops, 0), want_all)
+
+    def _epipolar(self, call, num_pts, loops, want_all):
+        fund, ransac = np.zeros(9, dtype=np.float64), np.zeros(9, dtype=np.float64)
+        n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        flags = np.zeros(max(num_pts, 1), dtype=np.int8)
+        drawn = np.zeros((8, loops), dtype=np.int32) if want_all else None
+        all_f = np.zeros((9, loops), dtype=np.float64) if want_all else None
+        all_c = np.zeros(loops, dtype=np.int32) if want_all else None
+        check(call(fund.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
+                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_f.ctypes.data if want_all else None,
+                   all_c.ctypes.data if want_all else None))
+        return EpipolarResult(fund, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
+                              flags[:max(num_pts, 0)].astype(bool), drawn, all_f, all_c)
+
+    def estimate_fundamental(self, d_sift, num_pts, num_pts2=-1, rule=0, lo=0.0, hi=0.8, loops=10000, thresh=1.0,
+                             refine_loops=5, refine_thresh=1.0, seed=0, want_all=False):
+        """cusift_estimate_fundamental: fundamental-matrix RANSAC + refit, all fp64, on device records that carry match
+        fields -- candidates by `rule` as estimate_homography, eight samples per hypothesis drawn on the device from
+        `seed`, the normalised 8-point solve, Sampson inlier counts over the candidates, the first hypothesis with the
+        most inliers, `refine_loops` rounds of the refit over the current inliers; match_error (the Sampson distance) of
+        every device record is written.  thresh / refine_thresh are in pixels.  One synchronisation.  Returns an
+        EpipolarResult; with want_all its drawn [8, L] / all_fundamentals [9, L] / all_counts [L] are filled."""
+        loops = int(loops)
+        return self._epipolar(lambda *out: lib().cusift_estimate_fundamental(
+            self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi, loops, thresh, refine_loops,
+            refine_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, *out), num_pts, max(loops, 0), want_all)
+
+    def register_epipolar(self, d_sift1, n1, d_sift2, n2, distance=1, rule=None, lo=None, hi=None, loops=10000,
+                          thresh=1.0, refine_loops=5, refine_thresh=1.0, seed=0, want_all=False):
+        """cusift_register_epipolar: match(distance), then estimate_fundamental over d_sift1 with num_pts2 = n2 -- one
+        synchronisation, the staged route's bytes.  rule / lo / hi default as in register_planar; the cross-check setting
+        is honoured as there."""
+        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
+        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
+        hi = 0.8 if hi is None else hi
+        loops = int(loops)
+        return self._epipolar(lambda *out: lib().cusift_register_epipolar(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
             int(seed) & 0xFFFFFFFFFFFFFFFF, *out), n1, max(loops, 0), want_all)
 

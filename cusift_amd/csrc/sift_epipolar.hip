@@ -1,0 +1,550 @@
+// sift_epipolar.hip -- epipolar registration on the device: from matched SiftData to a refined fundamental matrix without
+// a host decision.  The reference has no fundamental-matrix code: the definition is this library's own, written out in
+// include/cusift_amd_extras.h, and all of it is fp64.  cusift_estimate_fundamental / cusift_register_epipolar enqueue, on
+// the context's stream, with no host round trip in between:
+//
+//   planar_mark_kernel      (sift_planar.hip, unchanged) candidate?  SoA coordinates [x1 | y1 | x2 | y2] of all records
+//   planar_compact_kernel   (sift_planar.hip, unchanged) the candidates' record indices in ascending order, their number
+//   epipolar_solve_kernel   one hypothesis per lane: its eight samples drawn from the candidate list, Hartley
+//                           normalisation, the null vector of the 8 x 9 system, rank 2, denormalisation, unit norm and
+//                           sign.  The launch's threads together also gather the candidates' coordinates into a compacted
+//                           SoA, which is all the scoring and the refit read
+//   epipolar_score_kernel   one hypothesis per lane, its 9 coefficients and its count in registers; 64-candidate tiles in
+//                           LDS as SoA rows of doubles, every lane reads the same candidate (a broadcast); grid (loops /
+//                           64, candidate splits); the splits' partial counts meet in one integer atomic add per lane
+//   epipolar_select_kernel  one workgroup: the winner (64-bit max over count << 32 | ~loop, planar_select_kernel's), its
+//                           inlier flags, the refit rounds (normalised 9 x 9 sums over the current inliers, cyclic Jacobi,
+//                           rank 2), then match_error of every record and the number of candidates that fit
+// Every kernel has a pair index, blockIdx.z, and PlanarBatch's strides; one pair is gridDim.z == 1 with every stride 0.
+//
+// CANDIDATES ONLY.  Counts, flags, the refit set and num_fit run over the candidates, not over all records as the planar
+// path does: the epipolar constraint is one-dimensional, so a rejected match lies within a pixel of a random epipolar
+// line far more often than within a pixel of a homography's image of its point.  The scoring's cost follows n_cand.
+//
+// THE NULL VECTOR of the 8 x 9 system is found by Gaussian elimination with complete pivoting (rows and columns) and
+// back substitution from x[8] = 1: exact rank 8 has a one-dimensional null space, no squaring of the condition number as
+// a 9 x 9 normal matrix would bring, about 500 flops.  The system lives in LDS, one column per lane, because the pivot
+// search indexes it dynamically; everything else is in registers with static indices.  The refit's 9 x 9 matrix is a sum
+// over many points: there the eigenvector of the smallest eigenvalue is taken by cyclic Jacobi, kEpiSweeps9 sweeps over
+// the 36 pairs in row-major order, whatever the data.  RANK 2: F' = F (I - v v^T) with v the eigenvector of the smallest
+// eigenvalue of F^T F (3 x 3 cyclic Jacobi, kEpiSweeps3 sweeps) -- the nearest rank-2 matrix in the Frobenius norm.
+// The partial sums of the refit are reduced in a fixed order (lane tree inside a wave, then waves 0..3), so every run
+// gives the same bits.  Kernels use no scratch memory and write with vector stores only.
+// COST (profiles/epipolar.json, 10,000 loops): solve 42 us, scoring 58 us at 4,096 candidates and 511 us at 32,768, select
+// 819 us and 1,580 us.  The select kernel carries the call: every refit round ends in one lane's Jacobi (288 rotations,
+// each two divisions and two square roots in fp64, 126 doubles of state that overflow into AGPRs) while 255 lanes wait.
+#include "sift_device.h"
+
+namespace cusift {
+
+constexpr int kEpiThreads = 256;  // select
+constexpr int kEpiTile = 64;      // hypotheses per workgroup of the solve and scoring kernels, candidates per LDS tile
+constexpr int kEpiRedraws = 64;
+constexpr int kEpiSums = 45;      // the upper triangle of the 9 x 9 normal matrix
+// Cyclic Jacobi converges quadratically: on the refit matrices of planted scenes of 12 to 3,300 records (float64 numpy
+// restatement) the eigenvector stops moving after 6 sweeps of the 9 x 9 matrix; two more are the margin.
+constexpr int kEpiSweeps9 = 8, kEpiSweeps3 = 8;
+
+template <class T>
+__device__ __forceinline__ T *epipolar_pair(T *p, size_t bytes) {
+  return (T *)((char *)p + (size_t)blockIdx.z * bytes);
+}
+
+// as planar_count of sift_planar.hip: num_pts, or -- batched -- the pair's own record count from its head
+__device__ __forceinline__ int epipolar_count(const int *__restrict__ head, int num_pts, PlanarBatch nb) {
+  return nb.count ? min(head[kPlanarHeadCount], num_pts) : num_pts;
+}
+
+// The eight samples of hypothesis `loop`, as positions in the candidate list (n >= 8): homography_draw's recipe with eight
+// slots -- draws 0..7, then slots 2..8 in order redrawn while they equal an earlier slot, the draw counter running on
+// from 8; a slot redrawn 64 times takes the lowest position not taken yet.
+__device__ __forceinline__ void epipolar_draw(unsigned long long seed, int loop, int n, int (&p)[8]) {
+  unsigned int k = 8;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) p[s] = rigid_draw(seed, loop, (unsigned int)s, n);
+#pragma unroll
+  for (int s = 1; s < 8; ++s) {
+    int tries = 0;
+    bool clash = true;
+    while (true) {
+      clash = false;
+#pragma unroll
+      for (int q = 0; q < s; ++q) clash = clash || p[s] == p[q];
+      if (!clash || tries >= kEpiRedraws) break;
+      p[s] = rigid_draw(seed, loop, k++, n);
+      ++tries;
+    }
+    if (clash) {
+      int v = 0;
+      bool taken = true;
+      while (taken) {  // n >= 8 > s: at most s steps
+        taken = false;
+#pragma unroll
+        for (int q = 0; q < s; ++q) taken = taken || v == p[q];
+        v += taken ? 1 : 0;
+      }
+      p[s] = v;
+    }
+  }
+}
+
+// The inlier test: the Sampson distance without a division or a root, in exactly the expressions of
+// include/cusift_amd_extras.h.  *e2 and *den leave for match_error.  A NaN or den == 0 is no inlier.
+__device__ __forceinline__ bool epipolar_inlier(const double (&F)[9], double x1, double y1, double x2, double y2,
+                                                double t2, double *e2 = nullptr, double *den_out = nullptr) {
+  const double l0 = (F[0] * x1 + F[1] * y1) + F[2];
+  const double l1 = (F[3] * x1 + F[4] * y1) + F[5];
+  const double l2 = (F[6] * x1 + F[7] * y1) + F[8];
+  const double m0 = (F[0] * x2 + F[3] * y2) + F[6];
+  const double m1 = (F[1] * x2 + F[4] * y2) + F[7];
+  const double e = (x2 * l0 + y2 * l1) + l2;
+  const double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
+  if (e2) *e2 = e * e;
+  if (den_out) *den_out = den;
+  return e * e < t2 * den;
+}
+
+// Entry (i, j) of a symmetric matrix kept in its upper triangle.
+#define EPI_SYM(a, i, j) a[(i) < (j) ? (i) : (j)][(i) < (j) ? (j) : (i)]
+
+// Cyclic Jacobi on the symmetric N x N matrix `a` (upper triangle used): `sweeps` sweeps over the pairs (p, q), p < q, in
+// row-major order, whatever the data.  Afterwards a[j][j] are the eigenvalues and column j of v the eigenvectors.  Every
+// index is static; a pair whose off-diagonal entry is 0 is rotated by the identity.
+template <int N>
+__device__ __forceinline__ void epipolar_jacobi(double (&a)[N][N], double (&v)[N][N], int sweeps) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll 1
+  for (int sw = 0; sw < sweeps; ++sw) {
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p)
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = a[p][q];
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+        t = theta < 0.0 ? -t : t;
+        t = apq == 0.0 ? 0.0 : t;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        a[p][p] -= t * apq;
+        a[q][q] += t * apq;
+        a[p][q] = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          if (k != p && k != q) {
+            const double akp = EPI_SYM(a, k, p), akq = EPI_SYM(a, k, q);
+            EPI_SYM(a, k, p) = c * akp - s * akq;
+            EPI_SYM(a, k, q) = s * akp + c * akq;
+          }
+          const double vkp = v[k][p], vkq = v[k][q];
+          v[k][p] = c * vkp - s * vkq;
+          v[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+}
+
+// Column of v that belongs to the smallest a[j][j]; among equals the first.
+template <int N>
+__device__ __forceinline__ void epipolar_smallest(const double (&a)[N][N], const double (&v)[N][N], double (&x)[N]) {
+  double best = a[0][0];
+#pragma unroll
+  for (int i = 0; i < N; ++i) x[i] = v[i][0];
+#pragma unroll
+  for (int j = 1; j < N; ++j) {
+    const bool take = a[j][j] < best;
+    best = take ? a[j][j] : best;
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = take ? v[i][j] : x[i];
+  }
+}
+
+// A Hartley normalisation x~ = (x - cx) * s of one image.
+struct EpiNorm {
+  double cx, cy, s;
+};
+
+// From the null vector fh of the normalised system to F: rank 2, F = T2^T F^ T1, Frobenius norm 1, the largest-magnitude
+// entry positive (the first in row-major order among equals).  false: the result is not finite or all zero, F is nine
+// zeros.
+__device__ __forceinline__ bool epipolar_finish(const double (&fh)[9], EpiNorm n1, EpiNorm n2, double (&F)[9]) {
+  // rank 2: remove the right singular vector of the smallest singular value
+  double g[3][3], v[3][3], w[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j) g[i][j] = (fh[i] * fh[j] + fh[3 + i] * fh[3 + j]) + fh[6 + i] * fh[6 + j];
+  epipolar_jacobi<3>(g, v, kEpiSweeps3);
+  epipolar_smallest<3>(g, v, w);
+  double r[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double d = (fh[3 * i] * w[0] + fh[3 * i + 1] * w[1]) + fh[3 * i + 2] * w[2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r[3 * i + j] = fh[3 * i + j] - d * w[j];
+  }
+  // B = F^ T1, then F = T2^T B
+  const double tx1 = -(n1.s * n1.cx), ty1 = -(n1.s * n1.cy), tx2 = -(n2.s * n2.cx), ty2 = -(n2.s * n2.cy);
+  double b[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    b[3 * i] = r[3 * i] * n1.s;
+    b[3 * i + 1] = r[3 * i + 1] * n1.s;
+    b[3 * i + 2] = (r[3 * i] * tx1 + r[3 * i + 1] * ty1) + r[3 * i + 2];
+  }
+  double f[9];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    f[j] = n2.s * b[j];
+    f[3 + j] = n2.s * b[3 + j];
+    f[6 + j] = (tx2 * b[j] + ty2 * b[3 + j]) + b[6 + j];
+  }
+  double sq = 0.0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) sq += f[i] * f[i];
+  const double norm = sqrt(sq);
+  const bool ok = norm > 0.0 && norm < __builtin_inf();  // NaN fails both
+  double big = -1.0;
+  bool neg = false;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    f[i] = f[i] / norm;
+    const bool more = fabs(f[i]) > big;
+    big = more ? fabs(f[i]) : big;
+    neg = more ? f[i] < 0.0 : neg;
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) F[i] = ok ? (neg ? -f[i] : f[i]) : 0.0;
+  return ok;
+}
+
+// drawn [8][num_loops] (record indices), fund [9][num_loops], counts [num_loops] (zeroed here for the scoring kernel),
+// ccoord [4][num_pts]: the coordinates of candidate k at column k.  Fewer than 8 candidates: nothing is done.
+__global__ void __launch_bounds__(kEpiTile) epipolar_solve_kernel(const float *__restrict__ coord, int num_pts,
+                                                                  const int *__restrict__ cand,
+                                                                  const int *__restrict__ head, unsigned long long seed,
+                                                                  int num_loops, int *__restrict__ drawn,
+                                                                  double *__restrict__ fund, int *__restrict__ counts,
+                                                                  float *__restrict__ ccoord, PlanarBatch nb) {
+  __shared__ double s_m[72 * kEpiTile];  // the 8 x 9 system, one column of the array per lane
+  __shared__ int s_col[9 * kEpiTile];    // the column permutation of the pivoting
+  coord = epipolar_pair(coord, nb.scratch), cand = epipolar_pair(cand, nb.scratch);
+  drawn = epipolar_pair(drawn, nb.scratch), fund = epipolar_pair(fund, nb.scratch);
+  counts = epipolar_pair(counts, nb.scratch), ccoord = epipolar_pair(ccoord, nb.scratch);
+  head = epipolar_pair(head, nb.head);
+  const int tx = threadIdx.x;
+  const int n = min(head[kPlanarHeadCand], epipolar_count(head, num_pts, nb));
+  if (n < 8) return;  // uniform
+  // the launch's threads together: candidate k's coordinates to column k (k < n <= num_pts)
+  for (int k = blockIdx.x * kEpiTile + tx; k < n; k += gridDim.x * kEpiTile) {
+    const int r = clampi(cand[k], 0, num_pts - 1);  // memory safety only: the list holds record indices
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ccoord[(size_t)c * num_pts + k] = coord[(size_t)c * num_pts + r];
+  }
+  const int idx = blockIdx.x * kEpiTile + tx;
+  if (idx >= num_loops) return;  // no barrier below: every thread touches only its own LDS column
+  int p[8];
+  epipolar_draw(seed + blockIdx.z, idx, n, p);
+  double x1[8], y1[8], x2[8], y2[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int r = clampi(cand[p[i]], 0, num_pts - 1);
+    drawn[(size_t)i * num_loops + idx] = r;
+    x1[i] = (double)coord[r], y1[i] = (double)coord[(size_t)num_pts + r];
+    x2[i] = (double)coord[2 * (size_t)num_pts + r], y2[i] = (double)coord[3 * (size_t)num_pts + r];
+  }
+  counts[idx] = 0;
+  // Hartley: centroid to 0, mean distance sqrt(2), per image
+  EpiNorm n1, n2;
+  {
+    double sx1 = 0.0, sy1 = 0.0, sx2 = 0.0, sy2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sx1 += x1[i], sy1 += y1[i], sx2 += x2[i], sy2 += y2[i];
+    n1.cx = sx1 / 8.0, n1.cy = sy1 / 8.0, n2.cx = sx2 / 8.0, n2.cy = sy2 / 8.0;
+    double d1 = 0.0, d2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const double ax = x1[i] - n1.cx, ay = y1[i] - n1.cy, bx = x2[i] - n2.cx, by = y2[i] - n2.cy;
+      d1 += sqrt(ax * ax + ay * ay);
+      d2 += sqrt(bx * bx + by * by);
+    }
+    n1.s = sqrt(2.0) / (d1 / 8.0), n2.s = sqrt(2.0) / (d2 / 8.0);
+  }
+#define M(i, j) s_m[((i) * 9 + (j)) * kEpiTile + tx]
+#define COL(j) s_col[(j) * kEpiTile + tx]
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const double u1 = (x1[i] - n1.cx) * n1.s, v1 = (y1[i] - n1.cy) * n1.s;
+    const double u2 = (x2[i] - n2.cx) * n2.s, v2 = (y2[i] - n2.cy) * n2.s;
+    M(i, 0) = u2 * u1, M(i, 1) = u2 * v1, M(i, 2) = u2;
+    M(i, 3) = v2 * u1, M(i, 4) = v2 * v1, M(i, 5) = v2;
+    M(i, 6) = u1, M(i, 7) = v1, M(i, 8) = 1.0;
+  }
+#pragma unroll
+  for (int j = 0; j < 9; ++j) COL(j) = j;
+  // Gaussian elimination with complete pivoting.  A pivot of 0 or NaN divides into something not finite, which
+  // epipolar_finish turns into nine zeros.
+#pragma unroll 1
+  for (int k = 0; k < 8; ++k) {
+    double big = -1.0;
+    int pi = k, pj = k;
+    for (int i = k; i < 8; ++i)
+      for (int j = k; j < 9; ++j) {
+        const double t = fabs(M(i, j));
+        const bool more = t > big;
+        big = more ? t : big;
+        pi = more ? i : pi;
+        pj = more ? j : pj;
+      }
+    for (int j = k; j < 9; ++j) {  // rows k and pi, from column k on (in front of it the rows are done with)
+      const double a = M(k, j), b = M(pi, j);
+      M(k, j) = b, M(pi, j) = a;
+    }
+    for (int i = 0; i < 8; ++i) {  // columns k and pj, in every row: the rows above belong to the triangle
+      const double a = M(i, k), b = M(i, pj);
+      M(i, k) = b, M(i, pj) = a;
+    }
+    const int ck = COL(k), cj = COL(pj);
+    COL(k) = cj, COL(pj) = ck;
+    const double piv = M(k, k);
+    for (int i = k + 1; i < 8; ++i) {
+      const double f = M(i, k) / piv;
+      for (int j = k + 1; j < 9; ++j) M(i, j) -= f * M(k, j);
+    }
+  }
+  // back substitution from x[8] = 1 (static indices), then back through the column permutation by way of row 0 of the
+  // system, which nothing reads any more once x is complete
+  double x[9];
+  x[8] = 1.0;
+#pragma unroll
+  for (int k = 7; k >= 0; --k) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = k + 1; j < 9; ++j) s += M(k, j) * x[j];
+    x[k] = -s / M(k, k);
+  }
+  int col[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) col[j] = clampi(COL(j), 0, 8);
+#pragma unroll
+  for (int j = 0; j < 9; ++j) M(0, col[j]) = x[j];
+  double fh[9], F[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) fh[j] = M(0, j);
+#undef M
+#undef COL
+  epipolar_finish(fh, n1, n2, F);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) fund[(size_t)i * num_loops + idx] = F[i];
+}
+
+// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the candidates [y * per_split, (y + 1) * per_split) -- the splits
+// are sized from the capacity num_pts, and one that lies past the candidates adds nothing.  counts were zeroed by the
+// solve kernel.
+__global__ void __launch_bounds__(kEpiTile) epipolar_score_kernel(const float *__restrict__ ccoord, int num_pts,
+                                                                  int per_split, const double *__restrict__ fund,
+                                                                  int num_loops, float thresh, int *__restrict__ counts,
+                                                                  const int *__restrict__ head, PlanarBatch nb) {
+  __shared__ double s_pt[4][kEpiTile];
+  ccoord = epipolar_pair(ccoord, nb.scratch), fund = epipolar_pair(fund, nb.scratch);
+  counts = epipolar_pair(counts, nb.scratch), head = epipolar_pair(head, nb.head);
+  const int n_cand = min(head[kPlanarHeadCand], epipolar_count(head, num_pts, nb));
+  if (n_cand < 8) return;  // uniform; nothing was solved: epipolar_select_kernel answers alone
+  const int tx = threadIdx.x;
+  const int loop = blockIdx.x * kEpiTile + tx;
+  const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
+  double F[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) F[i] = fund[(size_t)i * num_loops + src];
+  const double t2 = (double)thresh * (double)thresh;
+  const int begin = blockIdx.y * per_split;
+  const int end = min(n_cand, begin + per_split);
+  int cnt = 0;
+  for (int tile = begin; tile < end; tile += kEpiTile) {
+    const int n = min(kEpiTile, end - tile);
+    __syncthreads();
+    if (tx < n) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s_pt[c][tx] = (double)ccoord[(size_t)c * num_pts + tile + tx];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) cnt += epipolar_inlier(F, s_pt[0][j], s_pt[1][j], s_pt[2][j], s_pt[3][j], t2) ? 1 : 0;
+  }
+  if (loop < num_loops && cnt) atomicAdd(&counts[loop], cnt);
+}
+
+// Sums s[0 .. K) over the workgroup in a fixed order -- the lane tree of every wave, then waves 0, 1, 2, 3 -- into s_sum.
+template <int K>
+__device__ __forceinline__ void epipolar_reduce(double (&s)[K], double (*s_part)[kEpiSums], double *s_sum, int tx) {
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off);
+  }
+  __syncthreads();  // whoever still reads the previous sums is done
+  if ((tx & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) s_part[tx >> 6][q] = s[q];
+  }
+  __syncthreads();
+  if (tx < K) s_sum[tx] = ((s_part[0][tx] + s_part[1][tx]) + s_part[2][tx]) + s_part[3][tx];
+  __syncthreads();
+}
+
+// head: words kPlanarHeadCand .. kPlanarHeadCount as the planar head's (planar_compact_kernel writes the first); then as
+// doubles F[9] (refined) at kEpiHeadF and R[9] (the winner) at kEpiHeadR.  errors == NULL: match_error goes into the
+// records; otherwise into errors[] (a batch, whose records stay as they are).
+__global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_point *__restrict__ pts, int num_pts,
+                                                                      const float *__restrict__ coord,
+                                                                      const float *__restrict__ ccoord,
+                                                                      const unsigned char *__restrict__ marks,
+                                                                      const double *__restrict__ fund,
+                                                                      const int *__restrict__ counts, int num_loops,
+                                                                      float thresh, int refine_loops, float refine_thresh,
+                                                                      int *__restrict__ head, char *__restrict__ flags,
+                                                                      float *__restrict__ errors, PlanarBatch nb) {
+  __shared__ unsigned long long s_key[kEpiThreads];
+  __shared__ double s_part[kEpiThreads / 64][kEpiSums];
+  __shared__ double s_sum[kEpiSums];
+  __shared__ double s_f[9];
+  __shared__ int s_ok;
+  __shared__ int s_cnt[kEpiThreads];
+  pts += (size_t)blockIdx.z * nb.records;
+  coord = epipolar_pair(coord, nb.scratch), ccoord = epipolar_pair(ccoord, nb.scratch);
+  marks = epipolar_pair(marks, nb.scratch), fund = epipolar_pair(fund, nb.scratch);
+  counts = epipolar_pair(counts, nb.scratch), head = epipolar_pair(head, nb.head);
+  flags += (size_t)blockIdx.z * nb.flags;
+  if (errors) errors += (size_t)blockIdx.z * nb.flags;
+  const float *__restrict__ cx1 = coord, *__restrict__ cy1 = coord + num_pts;
+  const float *__restrict__ cx2 = coord + 2 * (size_t)num_pts, *__restrict__ cy2 = coord + 3 * (size_t)num_pts;
+  const float *__restrict__ kx1 = ccoord, *__restrict__ ky1 = ccoord + num_pts;
+  const float *__restrict__ kx2 = ccoord + 2 * (size_t)num_pts, *__restrict__ ky2 = ccoord + 3 * (size_t)num_pts;
+  const int tx = threadIdx.x;
+  double *dhead = (double *)head;
+  const int n = epipolar_count(head, num_pts, nb);
+  const int n_cand = min(head[kPlanarHeadCand], n);
+  if (n_cand < 8) {  // uniform: nine zeros in both matrices, no inlier, the records stay as they are
+    for (int i = tx; i < n; i += kEpiThreads) flags[i] = 0;
+    if (tx < 9) dhead[kEpiHeadF + tx] = 0.0, dhead[kEpiHeadR + tx] = 0.0;
+    if (tx >= kPlanarHeadMatches && tx <= kPlanarHeadLoop) head[tx] = 0;
+    return;
+  }
+  // ---- the first hypothesis with the most inliers ----
+  unsigned long long key = 0;
+  for (int l = tx; l < num_loops; l += kEpiThreads) {
+    const unsigned long long k = ((unsigned long long)(unsigned int)counts[l] << 32) | (unsigned int)~(unsigned int)l;
+    key = k > key ? k : key;
+  }
+  s_key[tx] = key;
+  __syncthreads();
+#pragma unroll
+  for (int half = kEpiThreads / 2; half > 0; half >>= 1) {
+    if (tx < half) s_key[tx] = s_key[tx + half] > s_key[tx] ? s_key[tx + half] : s_key[tx];
+    __syncthreads();
+  }
+  key = s_key[0];
+  const int best = (int)~(unsigned int)(key & 0xffffffffull), best_count = (int)(unsigned int)(key >> 32);
+  double R[9], F[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) F[i] = R[i] = fund[(size_t)i * num_loops + best];
+  const double t2 = (double)thresh * (double)thresh, rt2 = (double)refine_thresh * (double)refine_thresh;
+  for (int i = tx; i < n; i += kEpiThreads)  // a record that is no candidate is no inlier
+    flags[i] = (marks[i] & 1) && epipolar_inlier(R, (double)cx1[i], (double)cy1[i], (double)cx2[i], (double)cy2[i], t2)
+                   ? 1
+                   : 0;
+  // ---- the refit: thread tx owns candidates tx, tx + 256, ... ----
+#pragma unroll 1
+  for (int round = 0; round < refine_loops; ++round) {
+    // S = the candidates that pass under the current F; its size and centroids
+    double a5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = tx; k < n_cand; k += kEpiThreads) {
+      const double x1 = kx1[k], y1 = ky1[k], x2 = kx2[k], y2 = ky2[k];
+      if (!epipolar_inlier(F, x1, y1, x2, y2, rt2)) continue;
+      a5[0] += 1.0, a5[1] += x1, a5[2] += y1, a5[3] += x2, a5[4] += y2;
+    }
+    epipolar_reduce<5>(a5, s_part, s_sum, tx);
+    const double size = s_sum[0];
+    if (size < 8.0) break;  // uniform: keep F
+    EpiNorm n1, n2;
+    n1.cx = s_sum[1] / size, n1.cy = s_sum[2] / size, n2.cx = s_sum[3] / size, n2.cy = s_sum[4] / size;
+    double d2[2] = {0.0, 0.0};
+    for (int k = tx; k < n_cand; k += kEpiThreads) {
+      const double x1 = kx1[k], y1 = ky1[k], x2 = kx2[k], y2 = ky2[k];
+      if (!epipolar_inlier(F, x1, y1, x2, y2, rt2)) continue;
+      const double ax = x1 - n1.cx, ay = y1 - n1.cy, bx = x2 - n2.cx, by = y2 - n2.cy;
+      d2[0] += sqrt(ax * ax + ay * ay);
+      d2[1] += sqrt(bx * bx + by * by);
+    }
+    epipolar_reduce<2>(d2, s_part, s_sum, tx);
+    n1.s = sqrt(2.0) / (s_sum[0] / size), n2.s = sqrt(2.0) / (s_sum[1] / size);
+    double s[kEpiSums];
+#pragma unroll
+    for (int q = 0; q < kEpiSums; ++q) s[q] = 0.0;
+    for (int k = tx; k < n_cand; k += kEpiThreads) {
+      const double x1 = kx1[k], y1 = ky1[k], x2 = kx2[k], y2 = ky2[k];
+      if (!epipolar_inlier(F, x1, y1, x2, y2, rt2)) continue;
+      const double u1 = (x1 - n1.cx) * n1.s, v1 = (y1 - n1.cy) * n1.s;
+      const double u2 = (x2 - n2.cx) * n2.s, v2 = (y2 - n2.cy) * n2.s;
+      const double a[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1.0};
+      int q = 0;
+#pragma unroll
+      for (int i = 0; i < 9; ++i)
+#pragma unroll
+        for (int j = i; j < 9; ++j) s[q++] += a[i] * a[j];
+    }
+    epipolar_reduce<kEpiSums>(s, s_part, s_sum, tx);
+    if (tx == 0) {  // one lane solves, everybody reads the answer
+      double m[9][9], v[9][9], fh[9], G[9];
+      int q = 0;
+#pragma unroll
+      for (int i = 0; i < 9; ++i)
+#pragma unroll
+        for (int j = i; j < 9; ++j) m[i][j] = s_sum[q++];
+      epipolar_jacobi<9>(m, v, kEpiSweeps9);
+      epipolar_smallest<9>(m, v, fh);
+      const bool ok = epipolar_finish(fh, n1, n2, G);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) s_f[i] = G[i];
+      s_ok = ok ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_ok) break;  // uniform: a result that is not finite keeps the previous F and ends the refit
+#pragma unroll
+    for (int i = 0; i < 9; ++i) F[i] = s_f[i];
+  }
+  // ---- match_error of every record, the number of candidates that fit ----
+  for (int i = tx; i < n; i += kEpiThreads) {
+    double e2, den;
+    epipolar_inlier(F, (double)cx1[i], (double)cy1[i], (double)cx2[i], (double)cy2[i], rt2, &e2, &den);
+    const float err = (float)sqrt(e2 / den);
+    if (errors)
+      errors[i] = err;
+    else
+      pts[i].match_error = err;
+  }
+  int fit = 0;
+  for (int k = tx; k < n_cand; k += kEpiThreads)
+    fit += epipolar_inlier(F, (double)kx1[k], (double)ky1[k], (double)kx2[k], (double)ky2[k], rt2) ? 1 : 0;
+  s_cnt[tx] = fit;
+  __syncthreads();
+#pragma unroll
+  for (int half = kEpiThreads / 2; half > 0; half >>= 1) {
+    if (tx < half) s_cnt[tx] += s_cnt[tx + half];
+    __syncthreads();
+  }
+  if (tx == 0) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      dhead[kEpiHeadF + i] = F[i];
+      dhead[kEpiHeadR + i] = R[i];
+    }
+    head[kPlanarHeadMatches] = best_count;
+    head[kPlanarHeadFit] = s_cnt[0];
+    head[kPlanarHeadLoop] = best;
+  }
+}
+
+}  // namespace cusift

@@ -4,7 +4,7 @@
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, math-eval, packing)
 //   sift_register.hip the registration host layer: matcher, FindHomography, planar registration, rigid RANSAC, RGB-D
-//                     registration and the pair-list forms of the three
+//                     and epipolar registration and the pair-list forms of the first three
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
@@ -84,6 +84,12 @@ __global__ void planar_compact_kernel(const unsigned char *, int, const int *, i
 __global__ void planar_score_kernel(const float *, int, int, const float *, int, float, int *, const int *, PlanarBatch);
 __global__ void planar_select_kernel(cusift_point *, int, const float *, const unsigned char *, const float *, const int *,
                                      int, float, int, float, float *, char *, float *, PlanarBatch);
+__global__ void epipolar_solve_kernel(const float *, int, const int *, const int *, unsigned long long, int, int *, double *,
+                                      int *, float *, PlanarBatch);
+__global__ void epipolar_score_kernel(const float *, int, int, const double *, int, float, int *, const int *, PlanarBatch);
+__global__ void epipolar_select_kernel(cusift_point *, int, const float *, const float *, const unsigned char *,
+                                       const double *, const int *, int, float, int, float, int *, char *, float *,
+                                       PlanarBatch);
 __global__ void sequence_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                      const cusift_match_row *, int, float, float, float *, unsigned char *, int *, int *,
                                      PlanarBatch, const cusift_match_row *);

@@ -1,6 +1,6 @@
 // sift_register.hip -- the registration host layer of the C ABI: the matcher, FindHomography, planar registration, rigid
-// RANSAC, RGB-D registration and the pair-list forms.  An entry point that reads results back lays its state out in the
-// context's register_scratch, what travels back first, and ends in one copy and one synchronisation.
+// RANSAC, RGB-D registration, epipolar registration and the pair-list forms.  An entry point that reads results back lays
+// its state out in the context's register_scratch, what travels back first, and ends in one copy and one synchronisation.
 #include "sift_host.h"
 
 // the refusals that several entry points share; `who` is the entry point's name in the message
@@ -191,11 +191,11 @@ struct PlanarOut {
   int *h_all_counts;
 };
 
-// every refusal of cusift_estimate_homography, before anything is enqueued or written
-static int planar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
-                        int num_loops, float thresh, int refine_loops, float refine_thresh, const PlanarOut &o) {
-  if (!o.h_homography || !o.h_ransac || !o.num_candidates || !o.num_matches || !o.num_fit)
-    return fail(CUSIFT_ERR_INVALID, "%s: NULL output", who);
+// every refusal of cusift_estimate_homography and cusift_estimate_fundamental, before anything is enqueued or written;
+// `outputs`: none of the required output pointers is NULL
+static int ransac_check(const char *who, bool outputs, const cusift_point *d_sift, int num_pts, int rule, float lo,
+                        float hi, int num_loops, float thresh, int refine_loops, float refine_thresh) {
+  if (!outputs) return fail(CUSIFT_ERR_INVALID, "%s: NULL output", who);
   if (rule != 0 && rule != 1) return fail(CUSIFT_ERR_INVALID, "%s: rule must be 0 (score > lo) or 1 (score < lo^2)", who);
   TRY(check_not_nan(who, lo, hi));
   TRY(check_num_loops(who, num_loops));
@@ -205,6 +205,11 @@ static int planar_check(const char *who, const cusift_point *d_sift, int num_pts
   if (num_pts < 0 || num_pts > (1 << 26)) return fail(CUSIFT_ERR_INVALID, "%s: num_pts %d outside [0, 2^26]", who, num_pts);
   if (num_pts > 0 && !d_sift) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
   return CUSIFT_OK;
+}
+static int planar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
+                        int num_loops, float thresh, int refine_loops, float refine_thresh, const PlanarOut &o) {
+  return ransac_check(who, o.h_homography && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift, num_pts,
+                      rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh);
 }
 
 static void planar_identity(int num_pts, int num_loops, const PlanarOut &o) {
@@ -599,6 +604,170 @@ extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int 
   if (h_inliers) memcpy(h_inliers, back.data() + flag_off, (size_t)n);
   if (h_pairs) memcpy(h_pairs, back.data() + pair_off, sizeof(int) * 2 * (size_t)n);
   return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// epipolar registration (sift_epipolar.hip): candidates, seeded fundamental-matrix RANSAC, refit -- one read-back
+// ------------------------------------------------------------------------------------------------
+struct EpipolarOut {
+  double *h_fundamental, *h_ransac;
+  int *num_candidates, *num_matches, *num_fit, *best_loop;
+  char *h_inliers;
+  int *h_drawn;
+  double *h_all_f;
+  int *h_all_counts;
+};
+
+static int epipolar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
+                          int num_loops, float thresh, int refine_loops, float refine_thresh, const EpipolarOut &o) {
+  return ransac_check(who, o.h_fundamental && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift,
+                      num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh);
+}
+
+// fewer than 8 records or candidates: there is no fundamental matrix to report, so both are nine zeros
+static void epipolar_nothing(int num_pts, int num_loops, const EpipolarOut &o) {
+  memset(o.h_fundamental, 0, sizeof(double) * 9);
+  memset(o.h_ransac, 0, sizeof(double) * 9);
+  *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
+  if (o.best_loop) *o.best_loop = 0;
+  if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
+  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 8 * (size_t)num_loops);
+  if (o.h_all_f) memset(o.h_all_f, 0, sizeof(double) * 9 * (size_t)num_loops);
+  if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
+}
+
+// What one pair keeps on the device, as byte offsets into its block (PlanarBatch::scratch apart in a batch): samples,
+// hypotheses and counts -- which the call can read back, so they come first -- then the coordinates of all records,
+// candidates, marks, the marking's block counts and the candidates' own coordinates.
+struct EpipolarBlock {
+  size_t idx, fund, counts, coord, cand, marks, blocks, ccoord, bytes;
+  EpipolarBlock(int num_pts, int num_loops) {
+    ScratchLayout s;
+    idx = s.take(sizeof(int) * 8 * (size_t)num_loops);
+    fund = s.take(sizeof(double) * 9 * (size_t)num_loops);
+    counts = s.take(sizeof(int) * (size_t)num_loops);
+    coord = s.take(sizeof(float) * 4 * (size_t)num_pts);
+    cand = s.take(sizeof(int) * (size_t)num_pts);
+    marks = s.take((size_t)num_pts);
+    blocks = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
+    ccoord = s.take(sizeof(float) * 4 * (size_t)num_pts);
+    bytes = s.size;
+  }
+};
+
+// The four launches behind the marking, over the block(s) at d_block; n_pairs and nb as planar_launch.
+static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh,
+                            int refine_loops, float refine_thresh, uint64_t seed, char *d_block, const EpipolarBlock &b,
+                            int *d_head, char *d_flags, float *d_err, int n_pairs, PlanarBatch nb) {
+  const float *d_coord = at<float>(d_block, b.coord);
+  float *d_ccoord = at<float>(d_block, b.ccoord);
+  const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
+  double *d_fund = at<double>(d_block, b.fund);
+  int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
+  // scoring: 64 hypotheses per one-wave workgroup; split the candidates -- at most num_pts of them, the number stays on
+  // the device -- until the launch has ~8 waves per CU over all pairs, but keep at least one 64-candidate tile per split
+  const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
+  const long wgs = (long)loop_blocks * n_pairs;
+  int splits = (int)std::max(1L, std::min((8L * ctx->num_cus + wgs - 1) / wgs, (long)idiv_up(num_pts, 64)));
+  splits = std::min(splits, 65535);
+  const int per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
+  splits = idiv_up(num_pts, per_split);
+  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_marks, num_pts,
+                     (const int *)at<int>(d_block, b.blocks), d_cand, d_head, nb);
+  hipLaunchKernelGGL(epipolar_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream, d_coord, num_pts,
+                     (const int *)d_cand, (const int *)d_head, (unsigned long long)seed, num_loops,
+                     at<int>(d_block, b.idx), d_fund, d_counts, d_ccoord, nb);
+  hipLaunchKernelGGL(epipolar_score_kernel, dim3(loop_blocks, splits, n_pairs), dim3(64), 0, ctx->stream,
+                     (const float *)d_ccoord, num_pts, per_split, (const double *)d_fund, num_loops, thresh, d_counts,
+                     (const int *)d_head, nb);
+  hipLaunchKernelGGL(epipolar_select_kernel, dim3(1, 1, n_pairs), dim3(256), 0, ctx->stream, d_sift, num_pts, d_coord,
+                     (const float *)d_ccoord, d_marks, (const double *)d_fund, (const int *)d_counts, num_loops, thresh,
+                     refine_loops, refine_thresh, d_head, d_flags, d_err, nb);
+}
+
+// The five launches and the one read-back; the arguments are checked.  d_cross as planar_run's.
+static int epipolar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
+                        int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
+                        const EpipolarOut &o, const cusift_point *d_cross) {
+  if (num_pts < 8) {  // eight correspondences are the least that fix F: the answer needs no device work
+    epipolar_nothing(num_pts, num_loops, o);
+    return CUSIFT_OK;
+  }
+  // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
+  const EpipolarBlock b(num_pts, num_loops);
+  ScratchLayout s;
+  s.take(kEpiHeadBytes);  // the head, at 0
+  const size_t flag_off = s.take((size_t)num_pts);
+  const size_t block_off = s.take(b.bytes);
+  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
+  char *base = ctx->register_scratch, *d_block = base + block_off;
+  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
+  hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream,
+                     (const cusift_point *)d_sift, num_pts, num_pts2, rule, t_lo, t_hi, at<float>(d_block, b.coord),
+                     at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), PlanarBatch{}, d_cross);
+  epipolar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
+                  base + flag_off, nullptr, 1, PlanarBatch{});
+  TRY(check_launch("estimate_fundamental"));
+  // the one blocking read-back
+  const bool all = o.h_drawn || o.h_all_f || o.h_all_counts;
+  std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const char *head = back.data(), *block = back.data() + block_off;
+  if (head_int(head, kPlanarHeadCand) < 8) {  // the kernels left the records alone
+    epipolar_nothing(num_pts, num_loops, o);
+    *o.num_candidates = head_int(head, kPlanarHeadCand);
+    return CUSIFT_OK;
+  }
+  memcpy(o.h_fundamental, head + sizeof(double) * kEpiHeadF, sizeof(double) * 9);
+  memcpy(o.h_ransac, head + sizeof(double) * kEpiHeadR, sizeof(double) * 9);
+  *o.num_candidates = head_int(head, kPlanarHeadCand), *o.num_matches = head_int(head, kPlanarHeadMatches);
+  *o.num_fit = head_int(head, kPlanarHeadFit);
+  if (o.best_loop) *o.best_loop = head_int(head, kPlanarHeadLoop);
+  if (o.h_inliers) memcpy(o.h_inliers, back.data() + flag_off, (size_t)num_pts);
+  if (o.h_drawn) memcpy(o.h_drawn, block + b.idx, sizeof(int) * 8 * (size_t)num_loops);
+  if (o.h_all_f) memcpy(o.h_all_f, block + b.fund, sizeof(double) * 9 * (size_t)num_loops);
+  if (o.h_all_counts) memcpy(o.h_all_counts, block + b.counts, sizeof(int) * (size_t)num_loops);
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_estimate_fundamental(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
+                                           float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                           float refine_thresh, uint64_t seed, double h_fundamental[9],
+                                           double h_ransac[9], int *num_candidates, int *num_matches, int *num_fit,
+                                           int *best_loop, char *h_inliers, int *h_drawn, double *h_all_f,
+                                           int *h_all_counts) {
+  TRY(enter(ctx));
+  const EpipolarOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
+                      best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
+  TRY(epipolar_check("EstimateFundamental", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+                     o));
+  return epipolar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed,
+                      o, nullptr);
+}
+
+extern "C" int cusift_register_epipolar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1,
+                                        const cusift_point *d_sift2, int num_pts2, int distance, int rule, float lo,
+                                        float hi, int num_loops, float thresh, int refine_loops, float refine_thresh,
+                                        uint64_t seed, double h_fundamental[9], double h_ransac[9], int *num_candidates,
+                                        int *num_matches, int *num_fit, int *best_loop, char *h_inliers, int *h_drawn,
+                                        double *h_all_f, int *h_all_counts) {
+  TRY(enter(ctx));
+  const EpipolarOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
+                      best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
+  TRY(epipolar_check("RegisterEpipolar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+                     o));
+  TRY(check_distance("RegisterEpipolar", distance));
+  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterEpipolar: missing data");
+  // as cusift_register_planar: the matcher stays enqueued with fewer than 8 records too, and with the cross-check on it
+  // is the mutual one, which writes the match fields of d_sift2 and refuses overlapping ranges before it enqueues
+  const bool cross = ctx->cross_check != 0;
+  if (cross)
+    TRY(cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance));
+  else
+    TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
+  return epipolar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+                      seed, o, cross ? d_sift2 : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

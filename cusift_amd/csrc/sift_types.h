@@ -165,6 +165,10 @@ struct PlanarBatch {
 constexpr int kPlanarHeadH = 0, kPlanarHeadR = 9, kPlanarHeadCand = 18, kPlanarHeadMatches = 19, kPlanarHeadFit = 20;
 constexpr int kPlanarHeadLoop = 21, kPlanarHeadCount = 22;
 constexpr size_t kPlanarHeadBytes = 128;              // between the heads of a batch
+// An epipolar result head (sift_epipolar.hip): the int words kPlanarHeadCand .. kPlanarHeadCount where the planar head has
+// them (planar_compact_kernel writes the first), then, counted in doubles, F[9] (refined) and R[9] (the winner).
+constexpr int kEpiHeadF = 16, kEpiHeadR = 32;
+constexpr size_t kEpiHeadBytes = 384;                 // between the heads of a batch
 // A rigid result head: Rt[12] as float, then as int the winner's count, the winning loop and -- with a device-side point
 // count -- that count.
 constexpr int kRigidHeadInliers = 12, kRigidHeadLoop = 13, kRigidHeadCount = 14;

@@ -119,6 +119,71 @@ int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1,
                            int *h_drawn /* may be NULL */, float *h_all_homo /* may be NULL */,
                            int *h_all_counts /* may be NULL */);
 
+/* ---- epipolar registration on the device: seeded fundamental-matrix RANSAC + refit (sift_epipolar.hip) --------- */
+/* Two views of a general 3-D scene from an ordinary camera: device records that carry match fields in, the fundamental
+ * matrix out, reproducible from `seed`, no host decision and no host round trip between the stages.  The reference has no
+ * fundamental-matrix code; this definition is the library's own, and ALL OF IT IS FP64 (an fp32 normalised 8-point solve
+ * moved the unit-norm F by up to 3e-4 on planted scenes; vector fp64 runs at the unpacked fp32 rate on this device).
+ * CONVENTION: x1 = (coords2D, 1), x2 = (match_xpos, match_ypos, 1), floats widened to double; F is row-major 3 x 3 and
+ * x2^T F x1 = 0.
+ * CANDIDATES are those of cusift_estimate_homography, by the same kernels: rule 0 / 1, finite coordinates, when num_pts2
+ * >= 0 also 0 <= match < num_pts2, the cross-check of cusift_register_epipolar, ascending record order, no atomics.
+ * EVERYTHING BELOW RUNS OVER THE CANDIDATES ONLY -- counts, flags, the refit set, *num_fit -- not over all records as the
+ * planar path does: the epipolar constraint is one-dimensional, so a rejected match lies near a random epipolar line far
+ * more often than near a homography's image of its point.
+ * SAMPLES: cusift_estimate_homography's recipe (same draw, same mix) with eight slots: p1..p8 = draws 0..7; then, with k
+ * counting on from 8, for slot s = 2..8 in order: while p_s equals an earlier slot redraw it; a slot redrawn 64 times
+ * takes the lowest candidate not taken yet.  Integer arithmetic only.
+ * HYPOTHESIS of one loop: Hartley-normalise the eight samples per image (centroid to 0, mean distance sqrt 2: x~ = (x -
+ * c) * s), build the 8 x 9 system with rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1], take its null vector
+ * (Gaussian elimination with complete pivoting, back substitution), project to rank 2 (remove the right singular vector
+ * of the smallest singular value), denormalise F = T2^T F^ T1, scale to Frobenius norm 1 with the largest-magnitude entry
+ * positive (among equals the first in row-major order decides).  A result that is not finite or all zero is nine zeros
+ * and counts nothing.
+ * INLIER TEST, the Sampson distance, pinned to these expressions (the build uses -ffp-contract=off) so that a float64
+ * restatement gives the same bit:
+ *     l0 = (F0*x1 + F1*y1) + F2;  l1 = (F3*x1 + F4*y1) + F5;  l2 = (F6*x1 + F7*y1) + F8;
+ *     m0 = (F0*x2 + F3*y2) + F6;  m1 = (F1*x2 + F4*y2) + F7;  e = (x2*l0 + y2*l1) + l2;
+ *     den = ((l0*l0 + l1*l1) + m0*m0) + m1*m1;    inlier <=> e*e < t2*den,   t2 = (double)thresh * (double)thresh
+ * No division, no square root; a NaN or den == 0 is no inlier.  One device function serves the scoring, the winner's
+ * flags and the refit's membership.  match_error = (float)sqrt(e*e / den), as IEEE gives it.
+ * WINNER: the most inliers, among equals the first loop: h_ransac its matrix, *num_matches its count, *best_loop its
+ * index, h_inliers its flags (0 for a record that is no candidate).
+ * REFIT, starting from the winner, refine_loops rounds: S = the candidates that pass the inlier test under the current
+ * F at refine_thresh; |S| < 8 ends the refit and keeps F; normalise over S, accumulate the 45 sums of the 9 x 9 matrix
+ * sum a a^T (reduced in a fixed order: lane tree, then waves 0..3), take the eigenvector of its smallest eigenvalue by
+ * cyclic Jacobi with a fixed sweep schedule, project to rank 2, denormalise, fix norm and sign; a result that is not
+ * finite keeps the previous F and ends the refit.  Afterwards match_error is written into EVERY device record [0,
+ * num_pts), *num_fit = the candidates that pass at refine_thresh and h_fundamental = F.  refine_loops == 0: h_fundamental
+ * equals h_ransac byte for byte.
+ * Optional (may be NULL): best_loop, h_inliers [num_pts], h_drawn [8][num_loops] (record indices), h_all_f
+ * [9][num_loops], h_all_counts [num_loops].  The same seed gives the same bytes in every output and in the records.
+ * num_pts < 8 or fewer than 8 candidates: nine zeros in both matrices, every count 0, the optional arrays zeroed,
+ * CUSIFT_OK; the records are untouched.  *num_candidates still reports the candidates when num_pts >= 8; with fewer than
+ * 8 records nothing is marked and it is 0, as cusift_estimate_homography answers.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of cusift_estimate_homography.
+ * Scratch lives in the context and grows on demand.  Blocking: ONE stream synchronisation, at the one read-back. */
+int cusift_estimate_fundamental(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2 /* < 0: no check */,
+                                int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                float refine_thresh, uint64_t seed, double h_fundamental[9], double h_ransac[9],
+                                int *num_candidates, int *num_matches, int *num_fit, int *best_loop /* may be NULL */,
+                                char *h_inliers /* may be NULL */, int *h_drawn /* may be NULL */,
+                                double *h_all_f /* may be NULL */, int *h_all_counts /* may be NULL */);
+
+/* cusift_match(d_sift1, d_sift2, distance) followed by cusift_estimate_fundamental(d_sift1, num_pts1, num_pts2, ...) with
+ * ONE synchronisation, at the read-back: the same bytes as the staged route in every output and in the records.  Also
+ * CUSIFT_ERR_INVALID for an unknown distance.  It honours cusift_ctx_set_cross_check exactly as cusift_register_planar
+ * does: while it is on, the matcher is cusift_match_mutual, THE MATCH FIELDS OF d_sift2 ARE WRITTEN (the parameter keeps
+ * its const spelling), overlapping record ranges are refused with CUSIFT_ERR_INVALID before anything is enqueued or
+ * written, and a record that is not mutual is no candidate. */
+int cusift_register_epipolar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                             int num_pts2, int distance, int rule, float lo, float hi, int num_loops, float thresh,
+                             int refine_loops, float refine_thresh, uint64_t seed, double h_fundamental[9],
+                             double h_ransac[9], int *num_candidates, int *num_matches, int *num_fit,
+                             int *best_loop /* may be NULL */, char *h_inliers /* may be NULL */,
+                             int *h_drawn /* may be NULL */, double *h_all_f /* may be NULL */,
+                             int *h_all_counts /* may be NULL */);
+
 /* ---- RANSAC rigid transform from matched 3-D points -------------------------- */
 /* EstimateRigidTransformH(h_coord, Rt, numInliers, numLoops, numPts, thresh2, type, h_indices, h_inliers),
  * extras/rigidTransform.cu:388-520.  h_coord[i] = reference-frame xyz, then moving-frame xyz of match i (coords3D of
@@ -201,7 +266,7 @@ int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_i
 
 /* The cross-check of the registrations, a setting of the context (0 = off, the default; 1 = on; anything else:
  * CUSIFT_ERR_INVALID, the setting unchanged).  It affects cusift_register_planar, cusift_register_rgbd,
- * cusift_register_planar_batch and cusift_register_rgbd_batch and nothing else; with 0 they enqueue the launches and
+ * cusift_register_planar_batch, cusift_register_rgbd_batch and cusift_register_epipolar and nothing else; with 0 they enqueue the launches and
  * return the bytes they always did.  With 1, record i of frame 1 takes part only if it is MUTUAL: its match m lies in
  * [0, n2) and the column side's best for record m of frame 2 is i -- the column side exactly as cusift_match_mutual /
  * cusift_match_batch_mutual define it, so an exactly tied best keeps the lowest record of frame 1.  Every many-to-one
