@@ -1,5 +1,5 @@
-// sift_device.h -- device-side helpers shared by the stencil kernels (sift_stencils.hip) and the keypoint
-// kernels (sift_keypoints.hip).
+// sift_device.h -- device-side helpers shared by every device unit; what only the registration units share is in
+// sift_ransac.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,19 +35,6 @@ __device__ __forceinline__ int frame_count(const unsigned int *__restrict__ coun
 
 // a candidate's coordinates are finite (planar_mark_kernel, sequence_mark_kernel)
 __device__ __forceinline__ bool planar_finite(float v) { return fabsf(v) < __builtin_inff(); }
-
-// The sample generator of the RANSAC kernels (sift_rigid.hip, sift_homography.hip): draw k of loop l is
-// mix(seed ^ mix((l << 32) | k)), its upper half modulo n.  Integer arithmetic only, documented in cusift_amd_extras.h.
-__device__ __forceinline__ unsigned long long rigid_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ int rigid_draw(unsigned long long seed, int loop, unsigned int k, int num_pts) {
-  const unsigned long long u = rigid_mix(seed ^ rigid_mix(((unsigned long long)(unsigned int)loop << 32) | k));
-  return (int)((unsigned int)(u >> 32) % (unsigned int)num_pts);
-}
 
 // lane i receives the value of lane i-1 (lane 0 receives 0): DPP wave_shr:1.  bound_ctrl makes the hardware
 // write 0 for the lane without a source, so no "old" value has to be materialised in front of every DPP move.

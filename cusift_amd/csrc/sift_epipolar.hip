@@ -12,7 +12,7 @@
 //   epipolar_score_kernel   one hypothesis per lane, its 9 coefficients and its count in registers; 64-candidate tiles in
 //                           LDS as SoA rows of doubles, every lane reads the same candidate (a broadcast); grid (loops /
 //                           64, candidate splits); the splits' partial counts meet in one integer atomic add per lane
-//   epipolar_select_kernel  one workgroup: the winner (64-bit max over count << 32 | ~loop, planar_select_kernel's), its
+//   epipolar_select_kernel  one workgroup: the winner (ransac_winner<true>: among equals the first), its
 //                           inlier flags, the refit rounds (normalised 9 x 9 sums over the current inliers, cyclic Jacobi,
 //                           rank 2), then match_error of every record and the number of candidates that fit
 // Every kernel has a pair index, blockIdx.z, and PlanarBatch's strides; one pair is gridDim.z == 1 with every stride 0.
@@ -28,65 +28,21 @@
 // over many points: there the eigenvector of the smallest eigenvalue is taken by cyclic Jacobi, kEpiSweeps9 sweeps over
 // the 36 pairs in row-major order, whatever the data.  RANK 2: F' = F (I - v v^T) with v the eigenvector of the smallest
 // eigenvalue of F^T F (3 x 3 cyclic Jacobi, kEpiSweeps3 sweeps) -- the nearest rank-2 matrix in the Frobenius norm.
-// The partial sums of the refit are reduced in a fixed order (lane tree inside a wave, then waves 0..3), so every run
-// gives the same bits.  Kernels use no scratch memory and write with vector stores only.
+// The partial sums of the refit are reduced in a fixed order (wave_tree_sum of sift_ransac.h), so every run gives the
+// same bits.  Kernels use no scratch memory and write with vector stores only.
 // COST (profiles/epipolar.json, 10,000 loops): solve 42 us, scoring 58 us at 4,096 candidates and 511 us at 32,768, select
 // 819 us and 1,580 us.  The select kernel carries the call: every refit round ends in one lane's Jacobi (288 rotations,
 // each two divisions and two square roots in fp64, 126 doubles of state that overflow into AGPRs) while 255 lanes wait.
-#include "sift_device.h"
+#include "sift_ransac.h"
 
 namespace cusift {
 
 constexpr int kEpiThreads = 256;  // select
 constexpr int kEpiTile = 64;      // hypotheses per workgroup of the solve and scoring kernels, candidates per LDS tile
-constexpr int kEpiRedraws = 64;
 constexpr int kEpiSums = 45;      // the upper triangle of the 9 x 9 normal matrix
 // Cyclic Jacobi converges quadratically: on the refit matrices of planted scenes of 12 to 3,300 records (float64 numpy
 // restatement) the eigenvector stops moving after 6 sweeps of the 9 x 9 matrix; two more are the margin.
 constexpr int kEpiSweeps9 = 8, kEpiSweeps3 = 8;
-
-template <class T>
-__device__ __forceinline__ T *epipolar_pair(T *p, size_t bytes) {
-  return (T *)((char *)p + (size_t)blockIdx.z * bytes);
-}
-
-// as planar_count of sift_planar.hip: num_pts, or -- batched -- the pair's own record count from its head
-__device__ __forceinline__ int epipolar_count(const int *__restrict__ head, int num_pts, PlanarBatch nb) {
-  return nb.count ? min(head[kPlanarHeadCount], num_pts) : num_pts;
-}
-
-// The eight samples of hypothesis `loop`, as positions in the candidate list (n >= 8): homography_draw's recipe with eight
-// slots -- draws 0..7, then slots 2..8 in order redrawn while they equal an earlier slot, the draw counter running on
-// from 8; a slot redrawn 64 times takes the lowest position not taken yet.
-__device__ __forceinline__ void epipolar_draw(unsigned long long seed, int loop, int n, int (&p)[8]) {
-  unsigned int k = 8;
-#pragma unroll
-  for (int s = 0; s < 8; ++s) p[s] = rigid_draw(seed, loop, (unsigned int)s, n);
-#pragma unroll
-  for (int s = 1; s < 8; ++s) {
-    int tries = 0;
-    bool clash = true;
-    while (true) {
-      clash = false;
-#pragma unroll
-      for (int q = 0; q < s; ++q) clash = clash || p[s] == p[q];
-      if (!clash || tries >= kEpiRedraws) break;
-      p[s] = rigid_draw(seed, loop, k++, n);
-      ++tries;
-    }
-    if (clash) {
-      int v = 0;
-      bool taken = true;
-      while (taken) {  // n >= 8 > s: at most s steps
-        taken = false;
-#pragma unroll
-        for (int q = 0; q < s; ++q) taken = taken || v == p[q];
-        v += taken ? 1 : 0;
-      }
-      p[s] = v;
-    }
-  }
-}
 
 // The inlier test: the Sampson distance without a division or a root, in exactly the expressions of
 // include/cusift_amd_extras.h.  *e2 and *den leave for match_error.  A NaN or den == 0 is no inlier.
@@ -230,12 +186,12 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_solve_kernel(const float *_
                                                                   float *__restrict__ ccoord, PlanarBatch nb) {
   __shared__ double s_m[72 * kEpiTile];  // the 8 x 9 system, one column of the array per lane
   __shared__ int s_col[9 * kEpiTile];    // the column permutation of the pivoting
-  coord = epipolar_pair(coord, nb.scratch), cand = epipolar_pair(cand, nb.scratch);
-  drawn = epipolar_pair(drawn, nb.scratch), fund = epipolar_pair(fund, nb.scratch);
-  counts = epipolar_pair(counts, nb.scratch), ccoord = epipolar_pair(ccoord, nb.scratch);
-  head = epipolar_pair(head, nb.head);
+  coord = pair_ptr(coord, nb.scratch), cand = pair_ptr(cand, nb.scratch);
+  drawn = pair_ptr(drawn, nb.scratch), fund = pair_ptr(fund, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), ccoord = pair_ptr(ccoord, nb.scratch);
+  head = pair_ptr(head, nb.head);
   const int tx = threadIdx.x;
-  const int n = min(head[kPlanarHeadCand], epipolar_count(head, num_pts, nb));
+  const int n = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
   if (n < 8) return;  // uniform
   // the launch's threads together: candidate k's coordinates to column k (k < n <= num_pts)
   for (int k = blockIdx.x * kEpiTile + tx; k < n; k += gridDim.x * kEpiTile) {
@@ -245,8 +201,8 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_solve_kernel(const float *_
   }
   const int idx = blockIdx.x * kEpiTile + tx;
   if (idx >= num_loops) return;  // no barrier below: every thread touches only its own LDS column
-  int p[8];
-  epipolar_draw(seed + blockIdx.z, idx, n, p);
+  int p[8];  // positions in the candidate list
+  ransac_sample<8>(seed + blockIdx.z, idx, n, p);
   double x1[8], y1[8], x2[8], y2[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -348,9 +304,9 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_score_kernel(const float *_
                                                                   int num_loops, float thresh, int *__restrict__ counts,
                                                                   const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[4][kEpiTile];
-  ccoord = epipolar_pair(ccoord, nb.scratch), fund = epipolar_pair(fund, nb.scratch);
-  counts = epipolar_pair(counts, nb.scratch), head = epipolar_pair(head, nb.head);
-  const int n_cand = min(head[kPlanarHeadCand], epipolar_count(head, num_pts, nb));
+  ccoord = pair_ptr(ccoord, nb.scratch), fund = pair_ptr(fund, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
+  const int n_cand = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
   if (n_cand < 8) return;  // uniform; nothing was solved: epipolar_select_kernel answers alone
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kEpiTile + tx;
@@ -376,24 +332,6 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_score_kernel(const float *_
   if (loop < num_loops && cnt) atomicAdd(&counts[loop], cnt);
 }
 
-// Sums s[0 .. K) over the workgroup in a fixed order -- the lane tree of every wave, then waves 0, 1, 2, 3 -- into s_sum.
-template <int K>
-__device__ __forceinline__ void epipolar_reduce(double (&s)[K], double (*s_part)[kEpiSums], double *s_sum, int tx) {
-#pragma unroll
-  for (int q = 0; q < K; ++q) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off);
-  }
-  __syncthreads();  // whoever still reads the previous sums is done
-  if ((tx & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) s_part[tx >> 6][q] = s[q];
-  }
-  __syncthreads();
-  if (tx < K) s_sum[tx] = ((s_part[0][tx] + s_part[1][tx]) + s_part[2][tx]) + s_part[3][tx];
-  __syncthreads();
-}
-
 // head: words kPlanarHeadCand .. kPlanarHeadCount as the planar head's (planar_compact_kernel writes the first); then as
 // doubles F[9] (refined) at kEpiHeadF and R[9] (the winner) at kEpiHeadR.  errors == NULL: match_error goes into the
 // records; otherwise into errors[] (a batch, whose records stay as they are).
@@ -413,9 +351,9 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
   __shared__ int s_ok;
   __shared__ int s_cnt[kEpiThreads];
   pts += (size_t)blockIdx.z * nb.records;
-  coord = epipolar_pair(coord, nb.scratch), ccoord = epipolar_pair(ccoord, nb.scratch);
-  marks = epipolar_pair(marks, nb.scratch), fund = epipolar_pair(fund, nb.scratch);
-  counts = epipolar_pair(counts, nb.scratch), head = epipolar_pair(head, nb.head);
+  coord = pair_ptr(coord, nb.scratch), ccoord = pair_ptr(ccoord, nb.scratch);
+  marks = pair_ptr(marks, nb.scratch), fund = pair_ptr(fund, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
   flags += (size_t)blockIdx.z * nb.flags;
   if (errors) errors += (size_t)blockIdx.z * nb.flags;
   const float *__restrict__ cx1 = coord, *__restrict__ cy1 = coord + num_pts;
@@ -424,7 +362,7 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
   const float *__restrict__ kx2 = ccoord + 2 * (size_t)num_pts, *__restrict__ ky2 = ccoord + 3 * (size_t)num_pts;
   const int tx = threadIdx.x;
   double *dhead = (double *)head;
-  const int n = epipolar_count(head, num_pts, nb);
+  const int n = pair_count(head, num_pts, nb);
   const int n_cand = min(head[kPlanarHeadCand], n);
   if (n_cand < 8) {  // uniform: nine zeros in both matrices, no inlier, the records stay as they are
     for (int i = tx; i < n; i += kEpiThreads) flags[i] = 0;
@@ -433,20 +371,8 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
     return;
   }
   // ---- the first hypothesis with the most inliers ----
-  unsigned long long key = 0;
-  for (int l = tx; l < num_loops; l += kEpiThreads) {
-    const unsigned long long k = ((unsigned long long)(unsigned int)counts[l] << 32) | (unsigned int)~(unsigned int)l;
-    key = k > key ? k : key;
-  }
-  s_key[tx] = key;
-  __syncthreads();
-#pragma unroll
-  for (int half = kEpiThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_key[tx] = s_key[tx + half] > s_key[tx] ? s_key[tx + half] : s_key[tx];
-    __syncthreads();
-  }
-  key = s_key[0];
-  const int best = (int)~(unsigned int)(key & 0xffffffffull), best_count = (int)(unsigned int)(key >> 32);
+  int best, best_count;
+  ransac_winner<true>(counts, num_loops, s_key, best, best_count);
   double R[9], F[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) F[i] = R[i] = fund[(size_t)i * num_loops + best];
@@ -465,7 +391,7 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
       if (!epipolar_inlier(F, x1, y1, x2, y2, rt2)) continue;
       a5[0] += 1.0, a5[1] += x1, a5[2] += y1, a5[3] += x2, a5[4] += y2;
     }
-    epipolar_reduce<5>(a5, s_part, s_sum, tx);
+    wave_tree_sum<5>(a5, s_part, s_sum, tx);
     const double size = s_sum[0];
     if (size < 8.0) break;  // uniform: keep F
     EpiNorm n1, n2;
@@ -478,7 +404,7 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
       d2[0] += sqrt(ax * ax + ay * ay);
       d2[1] += sqrt(bx * bx + by * by);
     }
-    epipolar_reduce<2>(d2, s_part, s_sum, tx);
+    wave_tree_sum<2>(d2, s_part, s_sum, tx);
     n1.s = sqrt(2.0) / (s_sum[0] / size), n2.s = sqrt(2.0) / (s_sum[1] / size);
     double s[kEpiSums];
 #pragma unroll
@@ -495,7 +421,7 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
 #pragma unroll
         for (int j = i; j < 9; ++j) s[q++] += a[i] * a[j];
     }
-    epipolar_reduce<kEpiSums>(s, s_part, s_sum, tx);
+    wave_tree_sum<kEpiSums>(s, s_part, s_sum, tx);
     if (tx == 0) {  // one lane solves, everybody reads the answer
       double m[9][9], v[9][9], fh[9], G[9];
       int q = 0;
@@ -528,13 +454,7 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
   int fit = 0;
   for (int k = tx; k < n_cand; k += kEpiThreads)
     fit += epipolar_inlier(F, (double)kx1[k], (double)ky1[k], (double)kx2[k], (double)ky2[k], rt2) ? 1 : 0;
-  s_cnt[tx] = fit;
-  __syncthreads();
-#pragma unroll
-  for (int half = kEpiThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_cnt[tx] += s_cnt[tx + half];
-    __syncthreads();
-  }
+  fit = block_sum_256(fit, s_cnt);
   if (tx == 0) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
@@ -542,7 +462,7 @@ __global__ void __launch_bounds__(kEpiThreads) epipolar_select_kernel(cusift_poi
       dhead[kEpiHeadR + i] = R[i];
     }
     head[kPlanarHeadMatches] = best_count;
-    head[kPlanarHeadFit] = s_cnt[0];
+    head[kPlanarHeadFit] = fit;
     head[kPlanarHeadLoop] = best;
   }
 }

@@ -8,7 +8,7 @@
 // The work is tiny (1000 hypotheses x a few thousand points), so the design goal is only "no scratch memory":
 // the reference keeps two 8x8 matrices per thread in local memory with data-dependent row swaps; here they live
 // in LDS, entry-major / thread-minor (conflict-free), one 64-thread workgroup per 64 hypotheses.
-#include "sift_device.h"
+#include "sift_ransac.h"
 
 namespace cusift {
 
@@ -24,44 +24,11 @@ __global__ void __launch_bounds__(256) homography_gather_kernel(const cusift_poi
 }
 
 constexpr int kHomoThreads = 64;
-constexpr int kHomoRedraws = 64;
-
-// The four samples of hypothesis `loop`, as positions in the candidate list (n >= 4): the recipe of sift_planar.hip's
-// header -- draws 0..3, then p2, p3, p4 redrawn in the reference's order (extras/homography.cu:222-235) with the draw
-// counter running on; a slot redrawn 64 times takes the lowest position not taken yet.
-__device__ __forceinline__ void homography_draw(unsigned long long seed, int loop, int n, int (&p)[4]) {
-  unsigned int k = 4;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) p[s] = rigid_draw(seed, loop, (unsigned int)s, n);
-#pragma unroll
-  for (int s = 1; s < 4; ++s) {
-    int tries = 0;
-    bool clash = true;
-    while (true) {
-      clash = false;
-#pragma unroll
-      for (int q = 0; q < s; ++q) clash = clash || p[s] == p[q];
-      if (!clash || tries >= kHomoRedraws) break;
-      p[s] = rigid_draw(seed, loop, k++, n);
-      ++tries;
-    }
-    if (clash) {
-      int v = 0;
-      bool taken = true;
-      while (taken) {  // n >= 4 > s: at most s steps
-        taken = false;
-#pragma unroll
-        for (int q = 0; q < s; ++q) taken = taken || v == p[q];
-        v += taken ? 1 : 0;
-      }
-      p[s] = v;
-    }
-  }
-}
 
 // rand_pts [4][num_loops]: the samples (record indices).  draw == 0: read from it (cusift_find_homography).  draw != 0:
-// drawn here from `seed` out of the candidate list cand[0 .. *n_cand) and written to it, and counts[loop] is zeroed for
-// the scoring kernel; fewer than 8 candidates (extras/homography.cu:220): nothing is solved.
+// drawn here from `seed` out of the candidate list cand[0 .. *n_cand) (ransac_sample<4> of sift_ransac.h gives the
+// positions) and written to it, and counts[loop] is zeroed for the scoring kernel; fewer than 8 candidates
+// (extras/homography.cu:220): nothing is solved.
 __global__ void __launch_bounds__(kHomoThreads) homography_solve_kernel(const float *__restrict__ coord, int num_pts,
                                                                        int *__restrict__ rand_pts, int num_loops,
                                                                        float *__restrict__ homo, int draw,
@@ -78,15 +45,13 @@ __global__ void __launch_bounds__(kHomoThreads) homography_solve_kernel(const fl
   const int idx = blockIdx.x * kHomoThreads + tx;
   if (idx >= num_loops) return;  // no barrier below: every thread touches only its own LDS column
   if (draw) {
-    const size_t off = (size_t)blockIdx.z * nb.scratch;
-    coord = (const float *)((const char *)coord + off), rand_pts = (int *)((char *)rand_pts + off);
-    homo = (float *)((char *)homo + off), cand = (const int *)((const char *)cand + off);
-    counts = (int *)((char *)counts + off);
-    n_cand = (const int *)((const char *)n_cand + (size_t)blockIdx.z * nb.head);  // the heads have a stride of their own
+    coord = pair_ptr(coord, nb.scratch), rand_pts = pair_ptr(rand_pts, nb.scratch), homo = pair_ptr(homo, nb.scratch);
+    cand = pair_ptr(cand, nb.scratch), counts = pair_ptr(counts, nb.scratch);
+    n_cand = pair_ptr(n_cand, nb.head);  // the heads have a stride of their own
     const int n = min(*n_cand, num_pts);
     if (n < 8) return;
     int p[4];
-    homography_draw(seed + blockIdx.z, idx, n, p);
+    ransac_sample<4>(seed + blockIdx.z, idx, n, p);
 #pragma unroll
     for (int i = 0; i < 4; ++i) rand_pts[i * num_loops + idx] = cand[p[i]];
     counts[idx] = 0;

@@ -8,6 +8,8 @@
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
+// The device units share sift_device.h (all of them) and sift_ransac.h (the six registration units: sampling, winner,
+// reductions, ordered compaction, pair strides).
 #pragma once
 
 #include <hip/hip_runtime.h>

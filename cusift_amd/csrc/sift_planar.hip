@@ -6,21 +6,20 @@
 //   planar_mark_kernel      per record: candidate? member of the refit set?  SoA coordinates [x1 | y1 | x2 | y2] of ALL
 //                           records (TestHomographies counts over all of them); candidates per 256-record workgroup
 //   planar_compact_kernel   the candidates' record indices in ASCENDING order and their number.  No atomics: the
-//                           workgroups before this one are summed in a fixed tree, the own keeps are ranked with ballot +
-//                           mbcnt inside a wave and a 4-entry scan across the waves (as match_select_* of sift_rgbd.hip)
+//                           workgroups before this one are summed, the own keeps are ranked by keep_rank_256
 //   homography_solve_kernel (sift_homography.hip) drawing its own four samples per hypothesis from the candidate list
 //   planar_score_kernel     TestHomographies: one hypothesis per lane, its 8 coefficients (as doubles) and its count in
 //                           registers; 64-point tiles in LDS as SoA rows of doubles, every lane reads the same point (a
 //                           broadcast); grid (loops / 64, point splits); the splits' partial counts meet in one integer
 //                           atomic add per lane (order-free)
-//   planar_select_kernel    one workgroup: the winner (64-bit max over count << 32 | ~loop: the most inliers and, among
-//                           equals, the FIRST, :249-254), its inlier flags, ImproveHomography's rounds of weighted normal
+//   planar_select_kernel    one workgroup: the winner (the most inliers and, among equals, the FIRST, :249-254:
+//                           ransac_winner<true>), its inlier flags, ImproveHomography's rounds of weighted normal
 //                           equations, then match_error of every record and the number of records with err < limit
 // Every kernel has a pair index, blockIdx.z: pair p's arrays lie PlanarBatch's strides further and it draws from seed + p.
 // One pair (cusift_estimate_homography, cusift_register_planar) is gridDim.z == 1 with every stride 0.
 // cusift_register_planar_batch runs all its pairs in the same launches: sequence_mark_kernel (sift_sequence.hip) takes
 // planar_mark_kernel's place -- it reads the match rows of cusift_match_batch instead of the records' match fields and
-// leaves each pair's record count in its head -- and the other kernels read that count (planar_count): num_pts is then
+// leaves each pair's record count in its head -- and the other kernels read that count (pair_count): num_pts is then
 // the capacity of a pair, the stride of its coordinate rows.  The refit's lane and wave assignment depends on the record
 // index alone, so a pair of a batch sums in the order of the pair call.  A batch's planar_select_kernel writes
 // match_error to an array of its own: the records are read only.
@@ -32,42 +31,27 @@
 // column side of cusift_match_mutual; an exactly tied best keeps the lowest record of image 1) -- for the candidates and
 // for the refit set, rule 0's literal predicate included.
 //
-// SAMPLING extends the recipe of sift_rigid.hip to four slots (same mix):
-//     draw k of loop l = cand[(mix(seed ^ mix((l << 32) | k)) >> 32) mod n_cand]
-//     p1..p4 = draws 0..3; then, with k counting on from 4: while p2 == p1 redraw p2; while p3 is p1 or p2 redraw p3;
-//     while p4 is p1, p2 or p3 redraw p4 (:222-235).  A slot redrawn 64 times takes the lowest candidate not taken yet.
-// Integer arithmetic only; tests/test_planar.py restates it and demands identical indices.
+// SAMPLING.  The four samples of a loop are cand[ransac_sample<4>] (sift_ransac.h): positions in the candidate list.
 //
 // PRECISION.  Hypotheses and counts are fp32 with the arithmetic of sift_homography.hip (bit for bit the oracle's; the
 // inlier test multiplies with round-toward-zero like __fmul_rz: the double product of two floats is exact, so keeping
 // the operands as doubles changes no bit).  The refit's 8x8 sums and its Cholesky solve are fp64 like the reference's
 // host code: the normal matrix of the UNNORMALISED system has a condition number of 1.4e13 .. 2.2e13 on the planted sets
 // of tests/test_homography.py (measured with numpy), so fp32 sums are useless; in fp64 two different summation orders
-// move the mapped corners of a 1280 x 960 frame by about 1e-10 px.  The partial sums are reduced in a fixed order (lane
-// tree inside a wave, then waves 0..3), so every run gives the same bits.  Only the structurally non-zero entries are
+// move the mapped corners of a 1280 x 960 frame by about 1e-10 px.  The partial sums are reduced in a fixed order
+// (wave_tree_sum), so every run gives the same bits.  Only the structurally non-zero entries are
 // summed: Yx = [x, y, 1, 0, 0, 0, -x mx, -y mx] and Yy = [0, 0, 0, x, y, 1, -x my, -y my] have three zeros each, the
 // [3..5][3..5] block of M equals the [0..2][0..2] block and the [0..2][3..5] block is 0 -- 21 sums of M, 8 of X.
 // A normal matrix that is not positive definite (NaN included) keeps the previous A, as cholesky_solve8 of
 // include/homography.h does.
 // Kernels use no scratch memory and write with vector stores only.
-#include "sift_device.h"
+#include "sift_ransac.h"
 
 namespace cusift {
 
 constexpr int kPlanarThreads = 256;  // mark / compact / select
 constexpr int kPlanarTile = 64;      // hypotheses per workgroup of the scoring kernel, points per LDS tile
 constexpr int kPlanarSums = 29;
-
-template <class T>
-__device__ __forceinline__ T *planar_pair(T *p, size_t bytes) {
-  return (T *)((char *)p + (size_t)blockIdx.z * bytes);
-}
-
-// The number of points of this workgroup's pair: num_pts, or -- batched -- what sequence_mark_kernel left in its head
-// (num_pts is then the capacity of a pair and the stride of its coordinate rows).  `head` is the pair's own.
-__device__ __forceinline__ int planar_count(const int *__restrict__ head, int num_pts, PlanarBatch nb) {
-  return nb.count ? min(head[kPlanarHeadCount], num_pts) : num_pts;
-}
 
 // coord [4][num_pts], fitset [num_pts], block_counts [ceil(num_pts / 256)].  pts2 != NULL (cusift_ctx_set_cross_check): the
 // num_pts2 records of image 2 with cusift_match_mutual's fields; a record that is not its partner's match is neither a
@@ -80,8 +64,8 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusif
                                                                      const cusift_point *__restrict__ pts2) {
   __shared__ int s_wave[kPlanarThreads / 64];
   pts += (size_t)blockIdx.z * nb.records;
-  coord = planar_pair(coord, nb.scratch), marks = planar_pair(marks, nb.scratch);
-  block_counts = planar_pair(block_counts, nb.scratch);
+  coord = pair_ptr(coord, nb.scratch), marks = pair_ptr(marks, nb.scratch);
+  block_counts = pair_ptr(block_counts, nb.scratch);
   const int tx = threadIdx.x;
   const int i = blockIdx.x * kPlanarThreads + tx;
   bool cand = false;
@@ -94,22 +78,17 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusif
     coord[i + num_pts] = y1;
     coord[i + 2 * (size_t)num_pts] = x2;
     coord[i + 3 * (size_t)num_pts] = y2;
-    cand = rule == 0 ? (score > lo && amb < hi) : (score < lo && amb < hi);
-    cand = cand && planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
-    cand = cand && (num_pts2 < 0 || (m >= 0 && m < num_pts2));
-    // the refit's point set: ImproveHomography's literal predicate (:286) under rule 0, the candidates under rule 1
-    bool fit = rule == 0 ? !(score < lo || amb > hi) : cand;
-    if (pts2) {  // the cross-check: the partner's own match (cusift_match_mutual's column side) must name record i
-      const bool mutual = m >= 0 && m < num_pts2 && pts2[m].match == i;
-      cand = cand && mutual;
-      fit = fit && mutual;
-    }
-    marks[i] = (unsigned char)((cand ? 1 : 0) | (fit ? 2 : 0));
+    const bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
+    const bool inside = m >= 0 && m < num_pts2;
+    // the cross-check: the partner's own match (cusift_match_mutual's column side) must name record i
+    const bool mutual = pts2 && inside && pts2[m].match == i;
+    const unsigned char mk =
+        planar_marks(rule, score, amb, lo, hi, finite, num_pts2 < 0 || inside, pts2 != nullptr, mutual);
+    marks[i] = mk;
+    cand = mk & 1;
   }
-  const unsigned long long m = __ballot(cand);
-  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
-  __syncthreads();
-  if (tx == 0) block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  const int keeps = keep_count_256(cand, s_wave);
+  if (tx == 0) block_counts[blockIdx.x] = keeps;
 }
 
 // cand[k] = record index of the k-th candidate; the last workgroup writes their number into head[kPlanarHeadCand].
@@ -120,33 +99,20 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const un
                                                                         PlanarBatch nb) {
   __shared__ int s_red[kPlanarThreads];
   __shared__ int s_wave[kPlanarThreads / 64];
-  marks = planar_pair(marks, nb.scratch), block_counts = planar_pair(block_counts, nb.scratch);
-  cand = planar_pair(cand, nb.scratch), head = planar_pair(head, nb.head);
+  marks = pair_ptr(marks, nb.scratch), block_counts = pair_ptr(block_counts, nb.scratch);
+  cand = pair_ptr(cand, nb.scratch), head = pair_ptr(head, nb.head);
   const int tx = threadIdx.x;
-  const int n = planar_count(head, num_pts, nb);
-  int before = 0;  // integer sums: any order gives the same value
+  const int n = pair_count(head, num_pts, nb);
+  int before = 0;
   for (int b = tx; b < (int)blockIdx.x; b += kPlanarThreads) before += block_counts[b];
-  s_red[tx] = before;
-  __syncthreads();
-#pragma unroll
-  for (int half = kPlanarThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_red[tx] += s_red[tx + half];
-    __syncthreads();
-  }
-  const int base = s_red[0];
+  const int base = block_sum_256(before, s_red);
   const int i = blockIdx.x * kPlanarThreads + tx;
   const bool keep = i < n && (marks[i] & 1);
-  const unsigned long long m = __ballot(keep);
-  const int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
-  __syncthreads();
-  int wave_base = 0;
-#pragma unroll
-  for (int wv = 0; wv < kPlanarThreads / 64; ++wv) wave_base += wv < (tx >> 6) ? s_wave[wv] : 0;
-  if (keep) cand[base + wave_base + rank] = i;  // < n: every keep before this one is a distinct record below i
+  int total;
+  const int rank = keep_rank_256(keep, s_wave, total);
+  if (keep) cand[base + rank] = i;  // < n: every keep before this one is a distinct record below i
   // a pair of a batch with fewer than 8 records reports no candidate, as the pair call answers before it counts
-  if (blockIdx.x == gridDim.x - 1 && tx == 0)
-    head[kPlanarHeadCand] = (nb.count && n < 8) ? 0 : base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  if (blockIdx.x == gridDim.x - 1 && tx == 0) head[kPlanarHeadCand] = (nb.count && n < 8) ? 0 : base + total;
 }
 
 // a * b rounded toward zero for a, b that hold fp32 values: the product is exact in fp64; round it to nearest, then step
@@ -181,8 +147,8 @@ __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *
                                                                    int *__restrict__ counts,
                                                                    const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[4][kPlanarTile];
-  coord = planar_pair(coord, nb.scratch), homo = planar_pair(homo, nb.scratch);
-  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.head);
+  coord = pair_ptr(coord, nb.scratch), homo = pair_ptr(homo, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
   if (head[kPlanarHeadCand] < 8) return;  // uniform; nothing was solved: planar_select_kernel answers alone
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kPlanarTile + tx;
@@ -193,7 +159,7 @@ __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *
   const float a2 = (float)a[2], a5 = (float)a[5];
   const double t2 = (double)thresh2;
   const int begin = blockIdx.y * pts_per_split;
-  const int end = min(planar_count(head, num_pts, nb), begin + pts_per_split);
+  const int end = min(pair_count(head, num_pts, nb), begin + pts_per_split);
   int cnt = 0;
   for (int tile = begin; tile < end; tile += kPlanarTile) {
     const int n = min(kPlanarTile, end - tile);
@@ -274,15 +240,15 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
   __shared__ double s_a[8];
   __shared__ int s_cnt[kPlanarThreads];
   pts += (size_t)blockIdx.z * nb.records;
-  coord = planar_pair(coord, nb.scratch), marks = planar_pair(marks, nb.scratch), homo = planar_pair(homo, nb.scratch);
-  counts = planar_pair(counts, nb.scratch), head = planar_pair(head, nb.head);
+  coord = pair_ptr(coord, nb.scratch), marks = pair_ptr(marks, nb.scratch), homo = pair_ptr(homo, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
   flags += (size_t)blockIdx.z * nb.flags;
   if (errors) errors += (size_t)blockIdx.z * nb.flags;
   const float *__restrict__ cx1 = coord, *__restrict__ cy1 = coord + num_pts;
   const float *__restrict__ cx2 = coord + 2 * (size_t)num_pts, *__restrict__ cy2 = coord + 3 * (size_t)num_pts;
   const int tx = threadIdx.x;
   int *ihead = (int *)head;
-  const int n = planar_count(ihead, num_pts, nb);
+  const int n = pair_count(ihead, num_pts, nb);
   if (ihead[kPlanarHeadCand] < 8) {  // uniform; extras/homography.cu:220: the identity, no inlier, the records stay as they are
     for (int i = tx; i < n; i += kPlanarThreads) flags[i] = 0;
     if (tx < kPlanarHeadCand) head[tx] = (tx % 9 == 0 || tx % 9 == 4 || tx % 9 == 8) ? 1.0f : 0.0f;
@@ -290,20 +256,8 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
     return;
   }
   // ---- the first hypothesis with the most inliers ----
-  unsigned long long key = 0;
-  for (int l = tx; l < num_loops; l += kPlanarThreads) {
-    const unsigned long long k = ((unsigned long long)(unsigned int)counts[l] << 32) | (unsigned int)~(unsigned int)l;
-    key = k > key ? k : key;
-  }
-  s_key[tx] = key;
-  __syncthreads();
-#pragma unroll
-  for (int half = kPlanarThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_key[tx] = s_key[tx + half] > s_key[tx] ? s_key[tx + half] : s_key[tx];
-    __syncthreads();
-  }
-  key = s_key[0];
-  const int best = (int)~(unsigned int)(key & 0xffffffffull), best_count = (int)(unsigned int)(key >> 32);
+  int best, best_count;
+  ransac_winner<true>(counts, num_loops, s_key, best, best_count);
   float win[8];
   double A[8];
 #pragma unroll
@@ -337,20 +291,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
       s[24] += x * v * w, s[25] += y * v * w, s[26] += v * w;
       s[27] += x6 * u * w + y6 * v * w, s[28] += x7 * u * w + y7 * v * w;
     }
-    // fixed order: the lane tree of every wave, then waves 0, 1, 2, 3
-#pragma unroll
-    for (int q = 0; q < kPlanarSums; ++q) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[q] += __shfl_down(s[q], off);
-    }
-    __syncthreads();
-    if ((tx & 63) == 0) {
-#pragma unroll
-      for (int q = 0; q < kPlanarSums; ++q) s_part[tx >> 6][q] = s[q];
-    }
-    __syncthreads();
-    if (tx < kPlanarSums) s_sum[tx] = ((s_part[0][tx] + s_part[1][tx]) + s_part[2][tx]) + s_part[3][tx];
-    __syncthreads();
+    wave_tree_sum<kPlanarSums>(s, s_part, s_sum, tx);
     if (tx == 0) {  // one lane solves, everybody reads the answer
       double t[kPlanarSums];
 #pragma unroll
@@ -385,13 +326,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
     else
       pts[i].match_error = sqrtf(err);
   }
-  s_cnt[tx] = fit;
-  __syncthreads();
-#pragma unroll
-  for (int half = kPlanarThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_cnt[tx] += s_cnt[tx + half];
-    __syncthreads();
-  }
+  fit = block_sum_256(fit, s_cnt);
   if (tx == 0) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -401,7 +336,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
     head[kPlanarHeadH + 8] = 1.0f;
     head[kPlanarHeadR + 8] = 1.0f;
     ihead[kPlanarHeadMatches] = best_count;
-    ihead[kPlanarHeadFit] = s_cnt[0];
+    ihead[kPlanarHeadFit] = fit;
     ihead[kPlanarHeadLoop] = best;
   }
 }

@@ -41,15 +41,16 @@ static const float kIdentRt[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
 // ------------------------------------------------------------------------------------------------
 // matcher
 // ------------------------------------------------------------------------------------------------
-// The column splits of cusift_match and cusift_match_mutual: aim at >= 4 workgroups per CU, keep >= 4 LDS tiles (128
-// columns) per split.
-static int match_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int *splits_out, int *cols_per_split_out) {
-  const int row_blocks = idiv_up(num_pts1, 64);
-  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, row_blocks), idiv_up(num_pts2, 128)));
+// The column splits of the matchers, over n_pairs pairs (a batch: sized from max_pts, the counts stay on the device):
+// aim at >= 4 workgroups per CU over all pairs, keep >= 4 LDS tiles (128 columns) per split.
+static int match_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int n_pairs, int *splits_out,
+                            int *cols_per_split_out) {
+  const long blocks = (long)idiv_up(num_pts1, 64) * n_pairs;
+  int splits = (int)std::max(1L, std::min((4L * ctx->num_cus + blocks - 1) / blocks, (long)idiv_up(num_pts2, 128)));
   if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, 32));
   splits = std::min(splits, 65535);
   // the kernel addresses a split's columns through a buffer resource with 32-bit byte offsets: a split may span at most
-  // 2^31 / 588 records (3.65 M) -- more points than that force further splits
+  // 2^31 / 588 records (3.65 M) -- more points than that force further splits (never a batch: max_pts <= 2^20)
   constexpr int kMaxColsPerSplit = (int)((0x7fffffffu / sizeof(cusift_point)) / 32 * 32);
   splits = std::max(splits, idiv_up(num_pts2, kMaxColsPerSplit));
   if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: too many points in image 2 (%d)", num_pts2);
@@ -67,7 +68,7 @@ extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1
   TRY(check_distance("MatchSiftData", distance));
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits, cols_per_split;
-  TRY(match_split_plan(ctx, num_pts1, num_pts2, &splits, &cols_per_split));
+  TRY(match_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
   const int n1_pad = row_blocks * 64;
   MatchPartial *partials = nullptr;
   if (splits > 1) {
@@ -98,7 +99,7 @@ extern "C" int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int n
   TRY(check_disjoint("MatchMutual", d_sift1, num_pts1, d_sift2, num_pts2));
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits, cols_per_split;
-  TRY(match_split_plan(ctx, num_pts1, num_pts2, &splits, &cols_per_split));
+  TRY(match_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
   const int n1_pad = row_blocks * 64;
   MatchPartial *partials = nullptr, *col_partials = nullptr;
   if (splits > 1) {
@@ -179,6 +180,18 @@ extern "C" int cusift_find_homography(cusift_ctx *ctx, const cusift_point *d_sif
   return CUSIFT_OK;
 }
 
+// The point splits of a RANSAC scoring launch (grid.y): `wgs` workgroups before splitting; split the points until the
+// launch has ~per_cu workgroups per CU, but keep at least one `tile` of points per split.  round_to_tile: a split is a
+// whole number of tiles.
+static int score_splits(cusift_ctx *ctx, int num_pts, long wgs, int per_cu, int tile, bool round_to_tile,
+                        int *per_split_out) {
+  const long target = ((long)per_cu * ctx->num_cus + wgs - 1) / wgs;
+  int splits = (int)std::max(1L, std::min(std::min(target, (long)idiv_up(num_pts, tile)), 65535L));
+  const int per_split = round_to_tile ? idiv_up(idiv_up(num_pts, splits), tile) * tile : idiv_up(num_pts, splits);
+  *per_split_out = per_split;
+  return idiv_up(num_pts, per_split);
+}
+
 // ------------------------------------------------------------------------------------------------
 // planar registration (sift_planar.hip): candidates, seeded RANSAC homography, refit -- one read-back
 // ------------------------------------------------------------------------------------------------
@@ -249,14 +262,10 @@ static void planar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, in
   const float *d_coord = at<float>(d_block, b.coord), *d_homo = at<float>(d_block, b.homo);
   const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
   int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
-  // scoring: 64 hypotheses per one-wave workgroup; split the points until the launch has ~8 waves per CU over all pairs,
-  // but keep at least one 64-point tile per split
+  // scoring: 64 hypotheses per one-wave workgroup, ~8 waves per CU over all pairs, whole 64-point tiles
   const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
-  const long wgs = (long)loop_blocks * n_pairs;
-  int splits = (int)std::max(1L, std::min((8L * ctx->num_cus + wgs - 1) / wgs, (long)idiv_up(num_pts, 64)));
-  splits = std::min(splits, 65535);
-  const int pts_per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
-  splits = idiv_up(num_pts, pts_per_split);
+  int pts_per_split;
+  const int splits = score_splits(ctx, num_pts, (long)loop_blocks * n_pairs, 8, 64, true, &pts_per_split);
   hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_marks, num_pts,
                      (const int *)at<int>(d_block, b.blocks), d_cand, (int *)d_head, nb);
   hipLaunchKernelGGL(homography_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream, d_coord, num_pts,
@@ -362,13 +371,10 @@ extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, in
 static void rigid_launch(cusift_ctx *ctx, const float *d_coord, int num_pts, const int *d_count, int *d_idx,
                          int num_loops, int draw, float thresh2, int type, uint64_t seed, float *d_rt, int *d_counts,
                          float *d_head, char *d_flags, int n_pairs = 1, RigidBatch nb = RigidBatch{}) {
-  // scoring: 256 hypotheses per workgroup; split the points until the launch has ~4 workgroups per CU, but keep
-  // at least one 256-point tile per split
+  // scoring: 256 hypotheses per workgroup, ~4 workgroups per CU, at least one 256-point tile per split
   const int loop_blocks = idiv_up(num_loops, 256);
-  int splits = std::max(1, std::min(idiv_up(4 * ctx->num_cus, loop_blocks * n_pairs), idiv_up(num_pts, 256)));
-  splits = std::min(splits, 65535);
-  const int pts_per_split = idiv_up(num_pts, splits);
-  splits = idiv_up(num_pts, pts_per_split);
+  int pts_per_split;
+  const int splits = score_splits(ctx, num_pts, (long)loop_blocks * n_pairs, 4, 256, false, &pts_per_split);
   const dim3 solve_grid(idiv_up(num_loops, 64), 1, n_pairs), score_grid(loop_blocks, splits, n_pairs);
   const dim3 select_grid(1, 1, n_pairs);
   if (type == 1)
@@ -664,14 +670,10 @@ static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, 
   const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
   double *d_fund = at<double>(d_block, b.fund);
   int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
-  // scoring: 64 hypotheses per one-wave workgroup; split the candidates -- at most num_pts of them, the number stays on
-  // the device -- until the launch has ~8 waves per CU over all pairs, but keep at least one 64-candidate tile per split
+  // scoring: as planar_launch, over the candidates -- at most num_pts of them, the number stays on the device
   const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
-  const long wgs = (long)loop_blocks * n_pairs;
-  int splits = (int)std::max(1L, std::min((8L * ctx->num_cus + wgs - 1) / wgs, (long)idiv_up(num_pts, 64)));
-  splits = std::min(splits, 65535);
-  const int per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
-  splits = idiv_up(num_pts, per_split);
+  int per_split;
+  const int splits = score_splits(ctx, num_pts, (long)loop_blocks * n_pairs, 8, 64, true, &per_split);
   hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_marks, num_pts,
                      (const int *)at<int>(d_block, b.blocks), d_cand, d_head, nb);
   hipLaunchKernelGGL(epipolar_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream, d_coord, num_pts,
@@ -790,15 +792,9 @@ static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int ma
 static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
                               const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
                               const int **d_pairs_out, cusift_match_row *d_rows_back = nullptr) {
-  // Column splits, sized from max_pts (the counts stay on the device): aim at >= 4 workgroups per CU over all pairs,
-  // keep >= 4 LDS tiles (128 columns) per split.  max_pts <= 2^20 records fit one split's 32-bit byte offsets.
   const int row_blocks = idiv_up(max_pts, 64);
-  const long blocks = (long)row_blocks * n_pairs;
-  int splits = (int)std::max(1L, std::min((4L * ctx->num_cus + blocks - 1) / blocks, (long)idiv_up(max_pts, 128)));
-  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(max_pts, 32));
-  splits = std::min(splits, 65535);
-  const int cols_per_split = idiv_up(idiv_up(max_pts, splits), 32) * 32;
-  splits = idiv_up(max_pts, cols_per_split);
+  int splits, cols_per_split;
+  TRY(match_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
   const int n1_pad = row_blocks * 64;
   const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
   const size_t part_b = align_up_sz(splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0, 256);

@@ -23,10 +23,11 @@
 // THE SELECTION keeps record i of frame 1 iff score < score_thresh2 && ambiguity < ambiguity_thresh2 && 0 <= match < n2
 // and, for the 3-D type, coords3D[2] != 0 on both sides -- the comparisons of include/matching.h:43-58 in the same
 // precision; cusift_select_mutual adds the cross-check sift2[match].match == i.
-// Order-preserving compaction without atomics: every 256-record workgroup counts its keeps (ballot + popcount), the second launch sums the counts of the workgroups before it (a fixed tree), ranks its own keeps with
-// ballot + mbcnt inside a wave and a 4-entry scan across its waves, and writes.  Same input, same output, every run.
+// Order-preserving compaction without atomics: every 256-record workgroup counts its keeps (keep_count_256 of
+// sift_ransac.h), the second launch sums the counts of the workgroups before it, ranks its own keeps (keep_rank_256) and
+// writes.  Same input, same output, every run.
 // Kernels use no scratch memory and write with vector stores only.
-#include "sift_device.h"
+#include "sift_ransac.h"
 
 namespace cusift {
 
@@ -88,10 +89,8 @@ __global__ void __launch_bounds__(kSelectThreads) match_select_count_kernel(cons
   int partner;
   const bool keep = match_selected(sift1, blockIdx.x * kSelectThreads + tx, n1, sift2, n2, score_thresh2,
                                    ambiguity_thresh2, type3d, partner);
-  const unsigned long long m = __ballot(keep);
-  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
-  __syncthreads();
-  if (tx == 0) block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  const int keeps = keep_count_256(keep, s_wave);
+  if (tx == 0) block_counts[blockIdx.x] = keeps;
 }
 
 // pairs[k] = (i, match), coord[k] = coords3D of record i, then of its partner; the last workgroup writes *count.
@@ -107,37 +106,17 @@ __global__ void __launch_bounds__(kSelectThreads) match_select_write_kernel(cons
   __shared__ int s_red[kSelectThreads];
   __shared__ int s_wave[kSelectThreads / 64];
   const int tx = threadIdx.x;
-  // keeps of the workgroups before this one: integer sums, any order gives the same value
-  int before = 0;
+  int before = 0;  // keeps of the workgroups before this one
   for (int b = tx; b < (int)blockIdx.x; b += kSelectThreads) before += block_counts[b];
-  s_red[tx] = before;
-  __syncthreads();
-#pragma unroll
-  for (int half = kSelectThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_red[tx] += s_red[tx + half];
-    __syncthreads();
-  }
-  const int base = s_red[0];
+  const int base = block_sum_256(before, s_red);
   const int i = blockIdx.x * kSelectThreads + tx;
   int partner;
   const bool keep = match_selected(sift1, i, n1, sift2, n2, score_thresh2, ambiguity_thresh2, type3d, partner);
-  const unsigned long long m = __ballot(keep);
-  const int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(m);
-  __syncthreads();
-  int wave_base = 0;
-#pragma unroll
-  for (int wv = 0; wv < kSelectThreads / 64; ++wv) wave_base += wv < (tx >> 6) ? s_wave[wv] : 0;
-  if (keep) {
-    const int k = base + wave_base + rank;  // < n1: every keep before this one is a distinct record below i
-    pairs[2 * (size_t)k + 0] = i;
-    pairs[2 * (size_t)k + 1] = partner;
-    const float *a = sift1[i].coords3D, *b = sift2[partner].coords3D;
-    float *c = coord + 6 * (size_t)k;
-    c[0] = a[0], c[1] = a[1], c[2] = a[2];
-    c[3] = b[0], c[4] = b[1], c[5] = b[2];
-  }
-  if (blockIdx.x == gridDim.x - 1 && tx == 0) *count = base + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  int total;
+  const int rank = keep_rank_256(keep, s_wave, total);
+  // base + rank < n1: every keep before this one is a distinct record below i
+  if (keep) write_selected(pairs, coord, base + rank, i, partner, sift1[i].coords3D, sift2[partner].coords3D);
+  if (blockIdx.x == gridDim.x - 1 && tx == 0) *count = base + total;
 }
 
 }  // namespace cusift

@@ -28,13 +28,8 @@
 // selects instead of branches gives the same eigenvector up to sign (the sign does not change R), in registers, with
 // all 64 lanes converged.
 //
-// SAMPLING.  The reference seeds cuRAND with time(0) (:411), which cannot be reproduced.  Here draw number k of loop l is
-//     u(seed, l, k) = mix(seed ^ mix((l << 32) | k)),         index = (u >> 32) mod num_pts
-//     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
-//             z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)          (all modulo 2^64)
-// p1 = draw 0, p2 = draw 1, p3 = draw 2; then, with k counting on from 3: while p2 == p1 redraw p2; while p3 is p1 or
-// p2 redraw p3 (:343-349).  A slot that has been redrawn 64 times takes the lowest index not taken yet, so the loop
-// is bounded.  Integer arithmetic only: tests/test_rigid.py restates it and demands identical indices.
+// SAMPLING.  The reference seeds cuRAND with time(0) (:411), which cannot be reproduced: the three samples of a loop
+// are ransac_sample<3> of sift_ransac.h, drawn from the point indices.
 //
 // NOT reproduced from the reference:
 //   * testRigidTransform writes the counts into d_indices while other threads still read their samples from it
@@ -44,14 +39,13 @@
 //   * a winner without inliers is refitted over zero points (0/0); a 3-D winner with fewer than 3 inliers keeps its
 //     own hypothesis here.
 // Kernels use no scratch memory and write with vector stores only.
-#include "sift_device.h"
+#include "sift_ransac.h"
 
 namespace cusift {
 
 constexpr int kRigidThreads = 256;  // hypotheses per workgroup of the scoring kernel, threads of the select kernel
 constexpr int kRigidTile = 256;     // points per LDS tile
 constexpr int kRigidSweeps = 6;     // cyclic Jacobi sweeps over the 6 off-diagonal pairs (fp64 4x4: converged after 5)
-constexpr int kRigidRedraws = 64;
 
 // One Jacobi rotation that annihilates a[P][Q] of the symmetric a (upper triangle kept, P < Q) and rotates columns
 // P, Q of v.  No branch: an off-diagonal entry that is already zero (or a NaN matrix) takes the identity rotation.
@@ -176,19 +170,7 @@ __global__ void __launch_bounds__(64) rigid_solve_kernel(const float *__restrict
   }
   int p[3];
   if (draw) {
-    unsigned int k = 3;
-    p[0] = rigid_draw(seed, loop, 0, num_pts);
-    p[1] = rigid_draw(seed, loop, 1, num_pts);
-    p[2] = rigid_draw(seed, loop, 2, num_pts);
-    int tries = 0;
-    while (p[1] == p[0] && tries < kRigidRedraws) p[1] = rigid_draw(seed, loop, k++, num_pts), ++tries;
-    if (p[1] == p[0]) p[1] = p[0] == 0 ? 1 : 0;
-    tries = 0;
-    while ((p[2] == p[0] || p[2] == p[1]) && tries < kRigidRedraws) p[2] = rigid_draw(seed, loop, k++, num_pts), ++tries;
-    if (p[2] == p[0] || p[2] == p[1]) {
-      p[2] = 0;
-      while (p[2] == p[0] || p[2] == p[1]) ++p[2];  // num_pts >= 3: at most two steps
-    }
+    ransac_sample<3>(seed, loop, num_pts, p);
     indices[3 * loop + 0] = p[0];
     indices[3 * loop + 1] = p[1];
     indices[3 * loop + 2] = p[2];
@@ -314,20 +296,8 @@ __global__ void __launch_bounds__(kRigidThreads) rigid_select_kernel(const float
       return;
     }
   }
-  unsigned long long key = 0;
-  for (int l = tx; l < num_loops; l += kRigidThreads) {
-    const unsigned long long k = ((unsigned long long)(unsigned int)counts[l] << 32) | (unsigned int)l;
-    key = k > key ? k : key;
-  }
-  s_key[tx] = key;
-  __syncthreads();
-#pragma unroll
-  for (int half = kRigidThreads / 2; half > 0; half >>= 1) {
-    if (tx < half) s_key[tx] = s_key[tx + half] > s_key[tx] ? s_key[tx + half] : s_key[tx];
-    __syncthreads();
-  }
-  key = s_key[0];
-  const int best = (int)(unsigned int)(key & 0xffffffffull), best_count = (int)(unsigned int)(key >> 32);
+  int best, best_count;
+  ransac_winner<false>(counts, num_loops, s_key, best, best_count);
   float rt[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) rt[i] = rt_all[12 * (size_t)best + i];

@@ -11,8 +11,8 @@
 // THE SELECTION is match_select_*'s rule (sift_rgbd.hip; include/matching.h:43-58) read from the match rows instead of
 // the records: row i of pair (f1, f2) is kept iff score < score_thresh2 && ambiguity < ambiguity_thresh2 &&
 // 0 <= match < n2 and, for the 3-D type, coords3D[2] != 0 in record i of f1 and in record `match` of f2.  One workgroup
-// per pair walks frame 1's records 256 at a time with a running base, ranks its keeps with ballot + mbcnt inside a wave
-// and a 4-entry scan across its waves: ascending record order, no atomics, the same output every run.  The record
+// per pair walks frame 1's records 256 at a time with a running base and ranks its keeps with keep_rank_256
+// (sift_ransac.h): ascending record order, no atomics, the same output every run.  The record
 // counts come from device memory (frame_count); nothing is written past a pair's count.
 //
 // THE PLANAR MARKING (cusift_register_planar_batch) is planar_mark_kernel (sift_planar.hip) for every pair of a list in
@@ -34,7 +34,7 @@
 // i < n1 with 0 <= match < n2, inside the n2 > 0 branch, so no unwritten row is ever read.  In a self pair (a, a) every
 // record is its own best in both directions.
 // No scratch memory, vector stores only.
-#include "sift_device.h"
+#include "sift_ransac.h"
 
 namespace cusift {
 
@@ -72,26 +72,10 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
       if (keep && rows_back) keep = __float_as_int((*reinterpret_cast<const f4 *>(rows_back + m))[2]) == i;
       partner = keep ? m : -1;
     }
-    const unsigned long long mask = __ballot(keep);
-    const int rank =
-        __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
-    if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(mask);
-    __syncthreads();
-    int wave_base = 0, total = 0;
-#pragma unroll
-    for (int wv = 0; wv < kSequenceSelectThreads / 64; ++wv) {
-      wave_base += wv < (tx >> 6) ? s_wave[wv] : 0;
-      total += s_wave[wv];
-    }
-    if (keep) {
-      const int k = base + wave_base + rank;  // < n1: every keep before this one is a distinct record below i
-      sel_pairs[2 * (size_t)k + 0] = i;
-      sel_pairs[2 * (size_t)k + 1] = partner;
-      const float *a = sift1[i].coords3D, *b = sift2[partner].coords3D;
-      float *c = coord + 6 * (size_t)k;
-      c[0] = a[0], c[1] = a[1], c[2] = a[2];
-      c[3] = b[0], c[4] = b[1], c[5] = b[2];
-    }
+    int total;
+    const int rank = keep_rank_256(keep, s_wave, total);
+    // base + rank < n1: every keep before this one is a distinct record below i
+    if (keep) write_selected(sel_pairs, coord, base + rank, i, partner, sift1[i].coords3D, sift2[partner].coords3D);
     base += total;
     __syncthreads();  // s_wave is rewritten by the next chunk
   }
@@ -113,16 +97,14 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
   const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
   const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
   rows += (size_t)pair * max_pts;
-  coord = (float *)((char *)coord + (size_t)pair * nb.scratch);
-  marks = (unsigned char *)((char *)marks + (size_t)pair * nb.scratch);
-  block_counts = (int *)((char *)block_counts + (size_t)pair * nb.scratch);
-  head = (int *)((char *)head + (size_t)pair * nb.head);
+  coord = pair_ptr(coord, nb.scratch), marks = pair_ptr(marks, nb.scratch);
+  block_counts = pair_ptr(block_counts, nb.scratch), head = pair_ptr(head, nb.head);
   const int i = blockIdx.x * kSequenceSelectThreads + tx;
   bool cand = false;
   if (i < n1) {
     const float x1 = sift1[i].coords2D[0], y1 = sift1[i].coords2D[1];
     float x2 = 0.0f, y2 = 0.0f;
-    bool fit = false;
+    unsigned char mk = 0;
     if (n2 > 0) {
       const f4 row = *reinterpret_cast<const f4 *>(rows + i);  // score, ambiguity, match, reserved
       const float score = row[0], amb = row[1];
@@ -130,27 +112,24 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
       const bool valid = m >= 0 && m < n2;
       const cusift_point *q = sift2 + (valid ? m : 0);  // the partner cusift_match takes the position from
       x2 = q->coords2D[0], y2 = q->coords2D[1];
-      cand = rule == 0 ? (score > lo && amb < hi) : (score < lo && amb < hi);
-      cand = cand && planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2) && valid;
-      fit = rule == 0 ? !(score < lo || amb > hi) : cand;  // as planar_mark_kernel
-      if (rows_back) {  // the cross-check, as planar_mark_kernel: back row m was written (i < n1, m < n2)
+      const bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
+      bool mutual = false;
+      if (rows_back) {  // the cross-check: back row m was written (i < n1, m < n2)
         const cusift_match_row *back = rows_back + (size_t)pair * max_pts + (valid ? m : 0);
-        const bool mutual = valid && __float_as_int((*reinterpret_cast<const f4 *>(back))[2]) == i;
-        cand = cand && mutual;
-        fit = fit && mutual;
+        mutual = valid && __float_as_int((*reinterpret_cast<const f4 *>(back))[2]) == i;
       }
+      mk = planar_marks(rule, score, amb, lo, hi, finite, valid, rows_back != nullptr, mutual);
+      cand = mk & 1;
     }
     coord[i] = x1;
     coord[i + max_pts] = y1;
     coord[i + 2 * (size_t)max_pts] = x2;
     coord[i + 3 * (size_t)max_pts] = y2;
-    marks[i] = (unsigned char)((cand ? 1 : 0) | (fit ? 2 : 0));
+    marks[i] = mk;
   }
-  const unsigned long long mask = __ballot(cand);
-  if ((tx & 63) == 0) s_wave[tx >> 6] = __builtin_popcountll(mask);
-  __syncthreads();
+  const int keeps = keep_count_256(cand, s_wave);
   if (tx == 0) {
-    block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    block_counts[blockIdx.x] = keeps;
     if (blockIdx.x == 0) head[kPlanarHeadCount] = n1;
   }
 }
