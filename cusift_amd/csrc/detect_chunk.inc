@@ -146,63 +146,64 @@
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (c0 + j < 1 || c0 + j > w - 2) cand &= ~(0x11111u << j);
-      if (__builtin_amdgcn_ballot_w64(cand != 0) != 0) {  // wave-uniform, rare
-#pragma unroll 1
-        for (int s = 0; s < kNumScales; ++s) {
-          const unsigned int m = (cand >> (4 * s)) & 0xfu;
-          if (__builtin_amdgcn_ballot_w64(m != 0) == 0) continue;  // wave-uniform
-          // A candidate's refinement reads 19 DoG values: the 3x3 of its own plane, and the centre with its four
-          // neighbours in the planes below and above.  All of them are in the registers of the detecting lane, except
-          // the column beyond its float4 (from the lane before for column 0, the lane after for column 3: five DPP
-          // moves).  The scale index and the column are made compile-time constants -- one case per scale, one block
-          // per column -- so every value is a named register and the lane stores its entry directly.  (Round 2 first
-          // dumped the three planes of the strip into an LDS cube, 9 KB per wave, and copied from there: ~1,750
-          // cycles per row-and-scale with a candidate by the phase stamps.)
-          auto emit = [&](auto scale_c) {
-            constexpr int k = decltype(scale_c)::value;  // planes k (below), k + 1 (the candidate's), k + 2 (above)
-            auto column = [&](auto col_c) {
-              constexpr int j = decltype(col_c)::value;
-              const bool mine = (m >> j) & 1u;
-              if (__builtin_amdgcn_ballot_w64(mine) == 0) return;  // wave-uniform
-              // value of plane p, row set D, column j + dx
-              auto at = [&](const f4 (&D)[kNumDog], int p, int dx) -> float {
-                const int col = j + dx;
-                if (col < 0) return from_prev_lane(D[p][3]);
-                if (col > 3) return from_next_lane(D[p][0]);
-                return D[p][col];
-              };
-              // all lanes take part in the DPP moves; only the candidates' lanes store
-              const float c00 = at(D0, k + 1, -1), c01 = at(D0, k + 1, 0), c02 = at(D0, k + 1, 1);
-              const float c10 = at(D1, k + 1, -1), c11 = at(D1, k + 1, 0), c12 = at(D1, k + 1, 1);
-              const float c20 = at(D2, k + 1, -1), c21 = at(D2, k + 1, 0), c22 = at(D2, k + 1, 1);
-              const float l0 = at(D1, k, 0), l1 = at(D1, k, -1), l2 = at(D1, k, 1), l3 = at(D0, k, 0), l4 = at(D2, k, 0);
-              const float h0 = at(D1, k + 2, 0), h1 = at(D1, k + 2, -1), h2 = at(D1, k + 2, 1), h3 = at(D0, k + 2, 0),
-                          h4 = at(D2, k + 2, 0);
-              float *e = cands.reserve(mine);  // at most 64 more entries
-              if (mine) {
-                e[0] = c00, e[1] = c01, e[2] = c02, e[3] = c10, e[4] = c11, e[5] = c12, e[6] = c20, e[7] = c21, e[8] = c22;
-                e[9] = l0, e[10] = l1, e[11] = l2, e[12] = l3, e[13] = l4;
-                e[14] = h0, e[15] = h1, e[16] = h2, e[17] = h3, e[18] = h4;
-                e[19] = __builtin_bit_cast(float, c0 + j);
-                e[20] = __builtin_bit_cast(float, ((y + rw.row0) << 3) | k);
-              }
-              if (cands.n >= 64) {
-                cands.refine_batch<kRecBytes>(list, max_pts, counter, P, lane);
-              }
-            };
-            column(std::integral_constant<int, 0>{});
-            column(std::integral_constant<int, 1>{});
-            column(std::integral_constant<int, 2>{});
-            column(std::integral_constant<int, 3>{});
+      if (__builtin_expect_with_probability(__builtin_amdgcn_ballot_w64(cand != 0) != 0, 0, 1.0)) {  // wave-uniform, rare
+        // A candidate's refinement reads 19 DoG values: the 3x3 of its own plane, and the centre with its four
+        // neighbours in the planes below and above.  All of them are in the registers of the detecting lane, except
+        // the column beyond its float4 (from the lane before for column 0, the lane after for column 3: five DPP
+        // moves).  The scale index and the column are made compile-time constants -- one case per (scale, column) --
+        // so every value is a named register and the lane stores its entry directly.  (Round 2 first dumped the three
+        // planes of the strip into an LDS cube, 9 KB per wave, and copied from there: ~1,750 cycles per
+        // row-and-scale with a candidate by the phase stamps.)
+        // The cases only PUSH; the check-and-refine behind the switch is the row step's one copy of refine_batch
+        // (inside each of the 20 cases it was inlined 60 times per chunk body, ~95 KB of a 112 KB kernel).
+        auto push = [&](auto scale_c, auto col_c, float *e) {
+          constexpr int k = decltype(scale_c)::value;  // planes k (below), k + 1 (the candidate's), k + 2 (above)
+          constexpr int j = decltype(col_c)::value;
+          // value of plane p, row set D, column j + dx
+          auto at = [&](const f4 (&D)[kNumDog], int p, int dx) -> float {
+            const int col = j + dx;
+            if (col < 0) return from_prev_lane(D[p][3]);
+            if (col > 3) return from_next_lane(D[p][0]);
+            return D[p][col];
           };
-          switch (s) {
-            case 0: emit(std::integral_constant<int, 0>{}); break;
-            case 1: emit(std::integral_constant<int, 1>{}); break;
-            case 2: emit(std::integral_constant<int, 2>{}); break;
-            case 3: emit(std::integral_constant<int, 3>{}); break;
-            default: emit(std::integral_constant<int, 4>{}); break;
+          // all lanes take part in the DPP moves and in the stores: `e` of a lane without a candidate is its spare words
+          const float c00 = at(D0, k + 1, -1), c01 = at(D0, k + 1, 0), c02 = at(D0, k + 1, 1);
+          const float c10 = at(D1, k + 1, -1), c11 = at(D1, k + 1, 0), c12 = at(D1, k + 1, 1);
+          const float c20 = at(D2, k + 1, -1), c21 = at(D2, k + 1, 0), c22 = at(D2, k + 1, 1);
+          const float l0 = at(D1, k, 0), l1 = at(D1, k, -1), l2 = at(D1, k, 1), l3 = at(D0, k, 0), l4 = at(D2, k, 0);
+          const float h0 = at(D1, k + 2, 0), h1 = at(D1, k + 2, -1), h2 = at(D1, k + 2, 1), h3 = at(D0, k + 2, 0),
+                      h4 = at(D2, k + 2, 0);
+          e[0] = c00, e[1] = c01, e[2] = c02, e[3] = c10, e[4] = c11, e[5] = c12, e[6] = c20, e[7] = c21, e[8] = c22;
+          e[9] = l0, e[10] = l1, e[11] = l2, e[12] = l3, e[13] = l4;
+          e[14] = h0, e[15] = h1, e[16] = h2, e[17] = h3, e[18] = h4;
+        };
+#define CUSIFT_PUSH_CASE(S, J) \
+  case 4 * S + J: push(std::integral_constant<int, S>{}, std::integral_constant<int, J>{}, e); break;
+#define CUSIFT_PUSH_SCALE(S) CUSIFT_PUSH_CASE(S, 0) CUSIFT_PUSH_CASE(S, 1) CUSIFT_PUSH_CASE(S, 2) CUSIFT_PUSH_CASE(S, 3)
+        // the 20 (scale, column) items of the row, scale ascending, then column ascending: bit 4*s + j of `cand`
+        // (one OR over the wave instead of a ballot per item: the loop below visits the non-empty items only)
+        unsigned int items = wave_or(cand);
+        while (items != 0) {
+          const int it = __builtin_ctz(items);
+          items &= items - 1;
+          const bool mine = (cand >> it) & 1u;
+          float *e = cands.reserve(mine, lane);  // at most kDetCandLanes more entries
+          e[19] = __builtin_bit_cast(float, c0 + (it & 3));
+          e[20] = __builtin_bit_cast(float, ((y + rw.row0) << 3) | (it >> 2));
+          switch (it) {
+            CUSIFT_PUSH_SCALE(0)
+            CUSIFT_PUSH_SCALE(1)
+            CUSIFT_PUSH_SCALE(2)
+            CUSIFT_PUSH_SCALE(3)
+            default: CUSIFT_PUSH_SCALE(4)
+          }
+          // fewer than 64 were waiting and one item pushes at most 64: never more than kCandCap entries
+          if (cands.n >= 64) {
+            cands.refine_batch<kRecBytes>(list, max_pts, counter, P, lane);
           }
         }
+#undef CUSIFT_PUSH_SCALE
+#undef CUSIFT_PUSH_CASE
       }
     }
 #pragma unroll

@@ -46,6 +46,23 @@ __device__ __forceinline__ float from_next_lane(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
 
+// The OR of all 64 lanes' values, wave-uniform: four row_shr steps gather a row of 16 in its last lane, row_bcast:15 and
+// row_bcast:31 carry the rows' last lanes on, lane 63 holds everything.  OR is idempotent, so every step may write all
+// lanes (no row masks), and bound_ctrl's 0 for a lane without a source is its identity.
+template <int kCtrl>
+__device__ __forceinline__ unsigned int or_dpp(unsigned int v) {
+  return v | (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xf, 0xf, true);
+}
+__device__ __forceinline__ unsigned int wave_or(unsigned int v) {
+  v = or_dpp<0x111>(v);  // row_shr:1
+  v = or_dpp<0x112>(v);  // row_shr:2
+  v = or_dpp<0x114>(v);  // row_shr:4
+  v = or_dpp<0x118>(v);  // row_shr:8
+  v = or_dpp<0x142>(v);  // row_bcast:15
+  v = or_dpp<0x143>(v);  // row_bcast:31
+  return (unsigned int)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 // Right/left image border for lanes that own GROUPS of 4 (or 2) adjacent columns of a 16-byte (8-byte) aligned row,
 // for ANY width w >= 4 (>= 2): the lane's vector load is clamped to the last column group that starts inside the
 // image -- always aligned and inside the pitch, because pitch % 4 == 0 (% 2) -- and the components that lie outside

@@ -860,6 +860,14 @@ constexpr int kDetStrip = (64 - 2 * kDetHaloLanes) * kBlurCols;  // 240 columns 
 constexpr int kCandWords = 21;                                   // 19 DoG values, x, (y << 3) | scale index
 constexpr int kCandCap = 128;                                    // < 64 waiting + at most 64 pushed at a time
 static_assert(kCandCap * kCandWords == kDetectWaveLdsFloats, "host and kernel agree on the LDS size");
+// Only the 64 - 2 * kDetHaloLanes centre lanes ever hold a candidate, so at most 63 + 60 entries are in use and the
+// words behind them are spare: lane i's spare words are [kCandSpare0 + i, kCandSpare0 + i + kCandWords).  The 63 is the
+// caller's side of the bargain (detect_chunk.inc): it calls refine_batch as soon as n >= 64, after EVERY reserve(), and
+// refine_batch takes 64 of at most 63 + 60 -- so reserve() is entered with n < 64.  A caller that pushed twice between
+// two checks would write live entries into the spare words.
+constexpr int kDetCandLanes = 64 - 2 * kDetHaloLanes;
+constexpr int kCandSpare0 = (63 + kDetCandLanes) * kCandWords;
+static_assert(kCandSpare0 + 63 + kCandWords <= kCandCap * kCandWords, "the spare words lie inside the wave's list");
 
 // kIdent0: levels 0 and 1 have identity taps (initBlur >= their sigma: the "var <= 1e-6 => identity" rule, e.g.
 // octave 0 of the initBlur = 1.0 configuration).  1*c and fma(0, x, c) are exact for finite x, so the pair is
@@ -926,11 +934,15 @@ struct CandList {
   float *buf;  // [kCandCap][kCandWords] in LDS; an entry's stride is odd: lane i reading word k of entry i is conflict-free
   int n;       // wave-uniform
   // Called by ALL lanes (convergent): the entry of a lane with `mine` set (its rank among them, after the `n` entries
-  // already waiting), nullptr for the others; the caller fills the kCandWords words.
-  __device__ __forceinline__ float *reserve(bool mine) {
+  // already waiting); the caller fills the kCandWords words.
+  // The others get kCandWords SPARE words of their own behind the last entry that can be in use, so that the caller
+  // stores without a branch (a divergent branch inside each case of its switch cost the kernel its scalar jump and a
+  // dozen SGPR spills): spare words start at word kCandSpare0 + lane, so one store instruction hits 64 different banks.
+  __device__ __forceinline__ float *reserve(bool mine, int lane) {
     const unsigned long long m = __builtin_amdgcn_ballot_w64(mine);
     const int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-    float *e = mine ? buf + (n + rank) * kCandWords : nullptr;
+    const int entry = __mul24(n + rank, kCandWords), spare = kCandSpare0 + lane;  // (both, then a select: no branch)
+    float *e = buf + (mine ? entry : spare);
     n += __builtin_popcountll(m);
     return e;
   }

@@ -30,14 +30,17 @@ microbenchmark's cycles are time at the nominal 2.4 GHz with the whole chip load
 
 Classes are counted over the basic blocks (split at labels AND at the assembler's fall-through block comments) that
 sit INSIDE A LOOP (between a label and a later backward branch to it): the prologue, the window fill and other
-once-per-wave code do not weigh in.  For the fused detection that is still not the hot path: its loop holds 60 inlined
-copies of the 122-instruction candidate refinement (cold: ~1 % of the dynamic instructions).  Its row step (x3
-unrolled) is two kinds of block: the BLUR blocks (packed instructions: blur + DoG, then the ten-instruction threshold
-pre-test) that every wave-row executes, and the ANALYSIS blocks (v_min3 / v_max3 trees of the 26-neighbour test) that
-only the wave-rows run in which the pre-test finds a centre above the threshold.  They are reported separately
-("mix" + "analysis") and bench.py weighs the second with the measured pass fraction of the content.  The count is
-static -- every counted block weighs one -- so it is an estimate of the dynamic mix, not a trace; the PMC total it is
-applied to is exact.
+once-per-wave code do not weigh in.  For the fused detection the loop is the row step (x3 unrolled), and it holds three
+kinds of block: the BLUR blocks (packed instructions: blur + DoG, then the ten-instruction threshold pre-test) that
+every wave-row executes, the ANALYSIS blocks (v_min3 / v_max3 trees of the 26-neighbour test) that only the wave-rows
+run in which the pre-test finds a centre above the threshold, and the CANDIDATE blocks behind them (cold: ~1 % of the
+dynamic instructions) -- per row step one walk over the non-empty (scale, column) items, a switch of 20 push bodies
+(five DPP moves and the stores of a list entry each) and ONE inlined copy of CandList::refine_batch (until the row step
+had one check-and-refine, each of the 60 push bodies carried its own copy: 14,400 static VALU instructions per kernel
+instead of 3,300).  Blur and analysis are reported separately ("mix" + "analysis") and bench.py weighs the second with
+the measured pass fraction of the content; the candidate blocks are only sized ("candidate": what is left of the loop,
+and the refinement copies in it, counted by their five v_div_fmas_f32).  The count is static -- every counted block
+weighs one -- so it is an estimate of the dynamic mix, not a trace; the PMC total it is applied to is exact.
 """
 import json
 import os
@@ -147,6 +150,7 @@ def loop_mix(body, selector):
     """Class counts over the loop blocks.  selector "loop": all of them; "detect": (blur blocks, analysis blocks)."""
     blocks, total_all = loop_blocks(body)
     main, ana, n_main, n_ana = {}, {}, 0, 0
+    cold = {"valu": 0, "divisions": 0}  # "detect": the candidate blocks -- whatever is neither blur, pre-test nor analysis
     for blk, ops in blocks:
         if selector == "loop":
             add(main, blk)
@@ -159,7 +163,10 @@ def loop_mix(body, selector):
             n_ana += 1
         elif ops.get("v_max3_f32", 0) == 10 and sum(blk.values()) <= 16:  # the threshold pre-test: every row
             add(main, blk)
-    return main, total_all, n_main, ana, n_ana
+        else:
+            cold["valu"] += sum(blk.values())
+            cold["divisions"] += ops.get("v_div_fmas_f32", 0)
+    return main, total_all, n_main, ana, n_ana, cold
 
 
 def main():
@@ -176,7 +183,7 @@ def main():
     for name, (src, needle, selector) in KERNELS.items():
         if src not in cache:
             cache[src] = assembly(src)
-        counts, total_all, n_blocks, ana, n_ana = loop_mix(kernel_body(cache[src], needle), selector)
+        counts, total_all, n_blocks, ana, n_ana, cold = loop_mix(kernel_body(cache[src], needle), selector)
         n = sum(counts.values())
         own = CYCLES[WAVES[name]]
         frac = {k: round(v / n, 4) for k, v in sorted(counts.items())}
@@ -197,8 +204,14 @@ def main():
                                      "cycles_per_instruction_at_occupancy": round(priced(ana, own), 3),
                                      "instructions_per_row_step": round(na / max(1, n_blocks), 1)}
             out[name]["instructions_per_row_step"] = round(n / max(1, n_blocks), 1)
+            out[name]["candidate"] = {"blocks": "the rest of the row loop: item walk, 20 push bodies and the refinement, per row step "
+                                                "(cold)",
+                                      "counted_valu_instructions_static": cold["valu"],
+                                      "refinement_copies": cold["divisions"] // 5}
             print("%-28s analysis  %5d in %d blocks %s -> %.2f best, %.2f at occupancy" % (
                 "", na, n_ana, out[name]["analysis"]["mix"], priced(ana, BEST), priced(ana, own)))
+            print("%-28s candidate %5d cold VALU instructions in the loop, %d copies of the refinement" % (
+                "", cold["valu"], cold["divisions"] // 5))
     dst = os.path.join(ROOT, "profiles", "isa_mix.json")
     with open(dst, "w") as f:
         json.dump(out, f, indent=1)

@@ -3,6 +3,8 @@
 # Usage: tools/profile_gpu.sh <tag> [bench args...]
 # Results land under gpurun_out/<tag>/ ; tools/summarize_profile.py condenses them into profiles/.
 # PMC passes use --kernel-trace only (never combined with sys/hip/hsa tracing).
+# ICACHE_ONLY=1 tools/profile_gpu.sh <tag>: the instruction-fetch passes (tools/summarize_profile.py --icache).  They run in
+# that mode ONLY: the passes of the full run below have no time limit and no status check to gate them on.
 set -u
 TAG=${1:-r01}; shift || true
 OUT=$PWD/gpurun_out/$TAG
@@ -15,6 +17,38 @@ export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=8 HSA_ENABLE_IPC_MODE_LEGACY=0
 echo "GPU_MAX_HW_QUEUES=$GPU_MAX_HW_QUEUES HSA_ENABLE_IPC_MODE_LEGACY=$HSA_ENABLE_IPC_MODE_LEGACY (every pass)" > "$OUT/environment.txt"
 BENCH_ARGS="--steps 5 --warmup 2 --legs single,two_stage --profile-run $*"
+# Instruction fetch: the SQC's instruction-cache requests / hits / misses and the SQ's fetches, then the waits they would
+# explain, for BOTH forms of the step -- the default four-stream one (four kernels' code share the cache) and one stream
+# alone.  Each pass has a time limit of its own, and a failed one ends the sequence.
+icache_passes() {
+  local form args rc
+  for form in four one; do
+    if [ $form = four ]; then args="--steps 5 --warmup 2 --legs none --profile-run $*"
+    else args="--steps 5 --warmup 2 --streams 1 --legs single --profile-run $*"; fi
+    echo "icache_$form: python3 bench.py $args" >> "$OUT/command.txt"
+    echo "progress: icache passes ($form)"
+    pass() {  # <name> <counters...>
+      local name=$1; shift
+      timeout -k 10 240 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$OUT/icache_${form}_$name" -- python3 bench.py $args > "$OUT/icache_${form}_$name.log" 2>&1
+    }
+    # all six fetch counters are SQ events: one pass if the block takes them together, else two (a time limit ends it all)
+    pass fetch SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_IFETCH_LEVEL SQ_INSTS_VALU
+    rc=$?
+    if [ $rc -ge 124 ]; then return $rc; fi  # time limit, abort, fault: nothing more on the GPU
+    if [ $rc -ne 0 ]; then
+      rm -rf "$OUT/icache_${form}_fetch"
+      pass sqc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_INSTS_VALU || return 1
+      pass ifetch SQ_IFETCH SQ_IFETCH_LEVEL SQ_INSTS_VALU || return 1
+    fi
+    pass wait SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVES || return 1
+  done
+}
+if [ "${ICACHE_ONLY:-0}" = 1 ]; then
+  : > "$OUT/command.txt"
+  icache_passes "$@"; rc=$?
+  du -sh "$OUT"
+  exit $rc
+fi
 # the kernel-trace pass runs the DRIVER's steps (--steps 20 --warmup 5), behind the same set-up check and pre-flight as the
 # un-profiled command: its per-kernel averages are at the clocks the line's numbers are measured at (round 5's pass ran 5
 # steps from a cold start and read the blur + DoG kernel 13 % slower than the driver's line)

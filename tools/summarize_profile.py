@@ -2,6 +2,7 @@
 """Condense a tools/profile_gpu.sh run (gpurun_out/<tag>/) into a small text summary for profiles/.
 
     python tools/summarize_profile.py gpurun_out/r01a profiles/r01a_summary.txt
+    python tools/summarize_profile.py --icache <run directory> profiles/icache/before.txt   # the instruction-fetch passes only
 
 Per kernel: calls, avg/min/max duration (kernel trace), and PMC counters averaged per launch.
 For the stencil kernels the largest launches (octave 0 of the batch) are also listed on their own,
@@ -30,7 +31,76 @@ def read_csv(path):
         return list(csv.DictReader(f))
 
 
+def short_instance(name):
+    """Like short(), but one row per template instantiation of the fused detection: their code differs."""
+    n = name.split("(")[0].replace("cusift::", "").replace("void ", "")
+    return n[:60]
+
+
+def icache_lines(src):
+    """The instruction-fetch passes of tools/profile_gpu.sh (icache_<four|one>_<pass>/): per kernel and form of the step
+    the instruction cache's hit rate, its misses per 1,000 VALU wave-instructions, and the share of wave-cycles spent
+    waiting for an instruction.  Counters are summed over all launches of a kernel within a pass; rates compare counters of
+    ONE pass, the misses per VALU instruction use the SQ_INSTS_VALU of the same pass."""
+    lines = []
+    try:
+        lines += ["commands:"] + ["  " + l.strip() for l in open(os.path.join(src, "command.txt")) if l.startswith("icache_")]
+    except OSError:
+        pass
+    for form, title in (("four", "the default four-stream step"), ("one", "one stream (--streams 1 --legs single)")):
+        tot = defaultdict(lambda: defaultdict(float))   # kernel -> counter -> sum over launches (fetch passes)
+        wait = defaultdict(lambda: defaultdict(float))  # the wait pass, kept apart (its own SQ_INSTS_VALU)
+        launches = defaultdict(set)
+        for d in sorted(glob.glob(os.path.join(src, "icache_%s_*" % form))):
+            if not os.path.isdir(d):
+                continue
+            into = wait if d.endswith("_wait") else tot
+            for f in glob.glob(os.path.join(d, "**", "*_counter_collection.csv"), recursive=True):
+                for r in read_csv(f):
+                    k = short_instance(r["Kernel_Name"])
+                    if d.endswith("_sqc") and r["Counter_Name"] == "SQ_INSTS_VALU":
+                        continue  # (split fetch passes: the ifetch pass carries the VALU count)
+                    into[k][r["Counter_Name"]] += float(r["Counter_Value"])
+                    launches[k].add((os.path.basename(d), r["Dispatch_Id"]))
+        kernels = sorted(k for k in set(tot) | set(wait) if "_kernel" in k and "at::" not in k)
+        if not kernels:
+            lines += ["", "== instruction fetch, %s: no counter files ==" % title]
+            continue
+        lines += ["", "== instruction fetch, %s ==" % title,
+                  "%-52s %12s %12s %10s %9s %12s %13s %11s %10s" % ("kernel", "ICACHE_REQ", "MISSES", "DUPLICATE", "hit rate",
+                                                                "miss/1k VALU", "IFETCH", "IFETCH_LEVEL", "wait inst")]
+        for k in kernels:
+            c, w = tot[k], wait[k]
+            req, hits, miss = c.get("SQC_ICACHE_REQ"), c.get("SQC_ICACHE_HITS"), c.get("SQC_ICACHE_MISSES")
+            valu = c.get("SQ_INSTS_VALU")
+
+            def cell(v, fmt="%.4g"):
+                return fmt % v if v is not None else "n/a"
+
+            hit_rate = hits / req if req and hits is not None else (1.0 - miss / req if req and miss is not None else None)
+            per_k = 1e3 * miss / valu if valu and miss is not None else None
+            wait_share = w["SQ_WAIT_INST_ANY"] / w["SQ_WAVE_CYCLES"] if w.get("SQ_WAVE_CYCLES") else None
+            lines.append("%-52s %12s %12s %10s %9s %12s %13s %11s %10s" % (
+                k[:52], cell(req), cell(miss), cell(c.get("SQC_ICACHE_MISSES_DUPLICATE")), cell(hit_rate, "%.5f"),
+                cell(per_k, "%.3f"), cell(c.get("SQ_IFETCH")), cell(c.get("SQ_IFETCH_LEVEL")), cell(wait_share, "%.4f")))
+        lines.append("(wait inst = SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES of the wait pass; SQ_BUSY_CYCLES per kernel: %s)" % ", ".join(
+            "%s %.4g" % (k[:40], wait[k]["SQ_BUSY_CYCLES"]) for k in kernels if wait[k].get("SQ_BUSY_CYCLES")))
+        missing = [c for c in ("SQC_ICACHE_REQ", "SQC_ICACHE_HITS", "SQC_ICACHE_MISSES", "SQC_ICACHE_MISSES_DUPLICATE", "SQ_IFETCH",
+                               "SQ_IFETCH_LEVEL") if not any(c in tot[k] for k in kernels)]
+        if missing:
+            lines.append("not collected on this device: " + ", ".join(missing))
+    return lines
+
+
 def main():
+    if sys.argv[1] == "--icache":
+        src, dst = sys.argv[2], sys.argv[3]
+        lines = icache_lines(src)
+        os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
+        with open(dst, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     src, dst = sys.argv[1], sys.argv[2]
     lines = []
     stats = glob.glob(os.path.join(src, "trace", "**", "*_kernel_stats.csv"), recursive=True)
@@ -214,6 +284,8 @@ def main():
                      % (kern, insts, entry["launches_profiled"]))
     with open(os.path.join(os.path.dirname(dst) or ".", "valu.json"), "w") as f:
         json.dump(valu_json, f, indent=1)
+    if glob.glob(os.path.join(src, "icache_*")):
+        lines += [""] + icache_lines(src)
     os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
     with open(dst, "w") as f:
         f.write("\n".join(lines) + "\n")
