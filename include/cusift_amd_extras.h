@@ -148,14 +148,16 @@ int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1,
  * No division, no square root; a NaN or den == 0 is no inlier.  One device function serves the scoring, the winner's
  * flags and the refit's membership.  match_error = (float)sqrt(e*e / den), as IEEE gives it.
  * WINNER: the most inliers, among equals the first loop: h_ransac its matrix, *num_matches its count, *best_loop its
- * index, h_inliers its flags (0 for a record that is no candidate).
+ * index, h_inliers its flags (0 for a record that is no candidate).  When no hypothesis is solvable every count is 0
+ * and the first rule still holds: *best_loop = 0, *num_matches = 0, h_ransac nine zeros.
  * REFIT, starting from the winner, refine_loops rounds: S = the candidates that pass the inlier test under the current
  * F at refine_thresh; |S| < 8 ends the refit and keeps F; normalise over S, accumulate the 45 sums of the 9 x 9 matrix
  * sum a a^T (reduced in a fixed order: lane tree, then waves 0..3), take the eigenvector of its smallest eigenvalue by
  * cyclic Jacobi with a fixed sweep schedule, project to rank 2, denormalise, fix norm and sign; a result that is not
  * finite keeps the previous F and ends the refit.  Afterwards match_error is written into EVERY device record [0,
  * num_pts), *num_fit = the candidates that pass at refine_thresh and h_fundamental = F.  refine_loops == 0: h_fundamental
- * equals h_ransac byte for byte.
+ * equals h_ransac byte for byte.  Under nine zeros e*e / den is 0 / 0: when nothing was solvable match_error of every
+ * record is NaN, *num_fit = 0 and h_fundamental is nine zeros.
  * Optional (may be NULL): best_loop, h_inliers [num_pts], h_drawn [8][num_loops] (record indices), h_all_f
  * [9][num_loops], h_all_counts [num_loops].  The same seed gives the same bytes in every output and in the records.
  * num_pts < 8 or fewer than 8 candidates: nine zeros in both matrices, every count 0, the optional arrays zeroed,

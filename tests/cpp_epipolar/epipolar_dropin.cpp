@@ -5,8 +5,9 @@
 // dot product of 1.  Checked:
 //   * F has Frobenius norm 1 and determinant 0 within 1e-12, and lies close to the planted geometry: at least 99 % of the
 //     planted inliers have match_error < 1 px (printed beside it: how many the planted F itself keeps within 1 px);
-//   * numFit and match_error against a double restatement of the pinned inlier test with the device's own F: numFit
-//     exactly, match_error within 1e-5 relative;
+//   * the two thresholds differ (0.75 px for the hypotheses, 1 px for the refit), so that neither can stand in for the
+//     other: numMatches against a double restatement of the pinned inlier test with the device's own winner at 0.75 px,
+//     numFit with the device's own F at 1 px, both exactly; match_error within 1e-5 relative;
 //   * RegisterEpipolar = cusift_match + EstimateFundamental, byte for byte; the same seed twice gives the same bytes;
 //   * fewer than 8 records: nine zeros, zero counts.
 // Plain C++ (g++), no HIP headers.
@@ -60,6 +61,8 @@ int main() {
   {
     const int nIn = 600, nOut = 400, n = nIn + nOut;
     const float lo = 0.85f, hi = 0.95f;
+    const float thresh = 0.75f, refineThresh = 1.0f;  // apart: the winner's count is taken at one, numFit at the other
+    const double t2 = (double)thresh * thresh, rt2 = (double)refineThresh * refineThresh;
     const double f = 1000.0, cx = 640.0, cy = 480.0, ang = 0.15, base = 0.8;
     const double ca = std::cos(ang), sa = std::sin(ang);
     // X2 = R X1 + t with R a turn about y and t = -R C, C = (base, 0, 0); F = K^-T [t]x R K^-1
@@ -127,9 +130,10 @@ int main() {
                           reinterpret_cast<const cusift_point *>(a2.d_data), n, 0));
     double Fdev[9], Rdev[9];
     int numMatches = -1, numFit = -1;
-    EstimateFundamental(a1, Fdev, &numMatches, &numFit, 1000, lo, hi, 1.0f, 5, 1.0f, 11, 0, Rdev, n);
+    EstimateFundamental(a1, Fdev, &numMatches, &numFit, 1000, lo, hi, thresh, 5, refineThresh, 11, 0, Rdev, n);
     a1.Synchronize();
-    std::printf("EstimateFundamental: %d inliers, %d within 1 px of the refit (%d planted of %d)\n", numMatches, numFit, nIn, n);
+    std::printf("EstimateFundamental: %d inliers within %.2f px of the winner, %d within %.2f px of the refit (%d planted of %d)\n",
+                numMatches, thresh, numFit, refineThresh, nIn, n);
     int paired = 0;
     for (int i = 0; i < n; i++) paired += a1.h_data[i].match == (i * 7 + 3) % n;
     EXPECT(paired == n, "%d of %d records found their partner", paired, n);
@@ -139,26 +143,32 @@ int main() {
                        Fdev[2] * (Fdev[3] * Fdev[7] - Fdev[4] * Fdev[6]);
     EXPECT(std::fabs(std::sqrt(norm) - 1.0) <= 1e-12 && std::fabs(det) <= 1e-12, "norm %.17g, det %.3g", std::sqrt(norm), det);
     // numFit and match_error from the device's own F, in double
-    int fit = 0, good = 0, goodTrue = 0;
+    int fit = 0, fitTight = 0, won = 0, good = 0, goodTrue = 0;
     double worst = 0.0;
     for (int i = 0; i < n; i++) {
       const SiftPoint &pt = a1.h_data[i];
       double e2, den;
       sampson(Fdev, pt.coords2D[0], pt.coords2D[1], pt.match_xpos, pt.match_ypos, &e2, &den);
-      fit += e2 < 1.0 * den;  // every record is a candidate here (the matcher's scores are 1)
+      fit += e2 < rt2 * den;  // every record is a candidate here (the matcher's scores are 1)
+      fitTight += e2 < t2 * den;
       const double err = std::sqrt(e2 / den);
       worst = std::fmax(worst, std::fabs(err - pt.match_error) / std::fmax(err, 1e-30));
       good += planted[i] && pt.match_error < 1.0f;
       sampson(Ftrue, pt.coords2D[0], pt.coords2D[1], pt.match_xpos, pt.match_ypos, &e2, &den);
       goodTrue += planted[i] && e2 < den;
+      sampson(Rdev, pt.coords2D[0], pt.coords2D[1], pt.match_xpos, pt.match_ypos, &e2, &den);
+      won += e2 < t2 * den;
     }
     std::printf("planted inliers within 1 px: %d under the device's F, %d under the planted F, of %d; match_error off by "
                 "%.3g relative\n", good, goodTrue, nIn, worst);
     EXPECT(fit == numFit, "numFit %d, the restatement counts %d", numFit, fit);
+    EXPECT(won == numMatches, "numMatches %d, the restatement counts %d under the winner", numMatches, won);
     EXPECT(worst <= 1e-5, "match_error off by %.3g relative", worst);
     EXPECT(good >= (int)std::ceil(0.99 * nIn), "%d of %d planted inliers within 1 px", good, nIn);
     // the winner comes from eight noisy points: it holds its own samples, and the refit over its inliers gains on it
-    EXPECT(numMatches >= 8 && numMatches <= n && numFit >= numMatches, "%d inliers, %d fit", numMatches, numFit);
+    // -- at the winner's own threshold, and all the more at the wider one
+    EXPECT(numMatches >= 8 && numMatches <= n && fitTight >= numMatches && numFit >= numMatches,
+           "%d inliers, %d fit at the same threshold, %d fit", numMatches, fitTight, numFit);
     std::vector<float> devErr((size_t)n);
     for (int i = 0; i < n; i++) devErr[i] = a1.h_data[i].match_error;
 
@@ -169,7 +179,7 @@ int main() {
       SiftData b1, b2;
       upload(b1, f1);
       upload(b2, f2);
-      RegisterEpipolar(b1, b2, F1, &m1, &fit1, 1000, lo, hi, 1.0f, 5, 1.0f, 11, 0, 0, R1);
+      RegisterEpipolar(b1, b2, F1, &m1, &fit1, 1000, lo, hi, thresh, 5, refineThresh, 11, 0, 0, R1);
       b1.Synchronize();
       int same = 0;
       for (int i = 0; i < n; i++) same += std::memcmp(&b1.h_data[i].match_error, &devErr[i], sizeof(float)) == 0;
@@ -179,7 +189,7 @@ int main() {
       SiftData b1, b2;
       upload(b1, f1);
       upload(b2, f2);
-      RegisterEpipolar(b1, b2, F2, &m2, &fit2, 1000, lo, hi, 1.0f, 5, 1.0f, 11, 0, 0, R2);
+      RegisterEpipolar(b1, b2, F2, &m2, &fit2, 1000, lo, hi, thresh, 5, refineThresh, 11, 0, 0, R2);
     }
     std::printf("RegisterEpipolar: %d inliers, %d fit\n", m1, fit1);
     EXPECT(std::memcmp(F1, Fdev, sizeof(F1)) == 0 && std::memcmp(R1, Rdev, sizeof(R1)) == 0 && m1 == numMatches && fit1 == numFit,

@@ -554,11 +554,15 @@ def test_edges_and_refusals(ctx):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("distance,rule_args", [(1, dict(rule=1, lo=999.0, hi=0.8)), (0, dict(rule=0, lo=0.0, hi=0.95))])
+@pytest.mark.parametrize("distance,rule_args", [(1, dict(rule=1, lo=999.0, hi=0.8)), (0, dict(rule=0, lo=0.0, hi=0.95)),
+                                                (1, dict(rule=1, lo=999.0, hi=0.8, thresh=2.0, refine_thresh=0.75)),
+                                                (0, dict(rule=0, lo=0.0, hi=0.95, thresh=2.0, refine_thresh=0.75))])
 def test_fused_equals_staged_byte_for_byte(ctx, distance, rule_args):
+    """The last two sets carry thresholds of their own, thresh and refine_thresh apart; the others run both at THRESH."""
     s1 = read_vlfeat_sift(os.path.join(GOLDEN, "vlfeat_sift1.bin"))
     s2 = read_vlfeat_sift(os.path.join(GOLDEN, "vlfeat_sift2.bin"))
-    kw = dict(loops=512, thresh=THRESH, refine_loops=REFINE_LOOPS, refine_thresh=THRESH, seed=9, want_all=True, **rule_args)
+    kw = dict(loops=512, thresh=THRESH, refine_loops=REFINE_LOOPS, refine_thresh=THRESH, seed=9, want_all=True)
+    kw.update(rule_args)
     b1, b2 = upload(ctx, s1), upload(ctx, s2)
     fused = ctx.register_epipolar(b1.ptr, len(s1), b2.ptr, len(s2), distance=distance, **kw)
     f1 = b1.to_numpy(SIFT_POINT_DTYPE, (len(s1),))
