@@ -18,7 +18,7 @@ class BatchExtractor:
         counts  int32  [n]                 raw counters; valid points = min(count, max_pts)
     keep_strongest = K > 0: every image keeps its K strongest keypoints (cusift_ctx_set_keep_strongest; K <= max_pts),
     selected on the device before anything is described; counts are then the kept counts.
-    cross_check = True: register_planar, register_epipolar, register_planar_sequence and register_sequence feed their
+    cross_check = True: register_planar, register_epipolar, register_pose, register_planar_sequence and register_sequence feed their
     RANSAC mutual matches only (cusift_ctx_set_cross_check on this extractor's context).
     """
 
@@ -133,6 +133,16 @@ class BatchExtractor:
         points, counts = self.slots[slot]
         n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
         return self.ctx.register_epipolar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
+
+    def register_pose(self, i, j, camera, camera2=None, slot=0, **opts):
+        """Calibrated two-view pose of frames i and j of the last extract() into `slot`: cusift_register_pose over this
+        extractor's device records (frame i's match fields, match_error and coords3D are written).  camera: the
+        capi.Camera of frame i, camera2 of frame j (None: the same).  The two counts are read with one call.  **opts goes
+        to capi.Context.register_pose.  Returns its RegisterPoseResult: X_i = R X_j + t with |t| = 1.  Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
+        return self.ctx.register_pose(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), camera, camera2,
+                                      **opts)
 
     def register_planar_sequence(self, pairs=None, slot=0, **opts):
         """Planar registration of the frames of the last extract() into `slot` against each other:

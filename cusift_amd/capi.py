@@ -214,6 +214,11 @@ SIGNATURES = {
                                          C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
     "cusift_register_epipolar": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp,
                                       C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "cusift_estimate_pose": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _f, C.POINTER(Camera), C.POINTER(Camera), _vp,
+                                  C.POINTER(_i), _vp, _vp]),
+    "cusift_register_pose": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, C.POINTER(Camera),
+                                  C.POINTER(Camera), _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                                  _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp, _vp]),
     "cusift_estimate_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp,
                                    _vp, _vp]),
     "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
@@ -338,6 +343,11 @@ PlanarBatchResult = collections.namedtuple("PlanarBatchResult", "homography rans
 # all_fundamentals float64 [9, L], all_counts [L]
 EpipolarResult = collections.namedtuple("EpipolarResult", "fundamental ransac num_candidates num_matches num_fit best_loop "
                                         "inliers drawn all_fundamentals all_counts")
+# what cusift_estimate_pose returns: rt float64 [3, 4] = [R | t] with X1 = R X2 + t and |t| = 1, num_front (the winner's
+# vote), votes int32 [4] (the four candidates'), sigma float64 [3] (the singular values of E)
+PoseResult = collections.namedtuple("PoseResult", "rt num_front votes sigma")
+# what cusift_register_pose returns: the EpipolarResult, then the PoseResult
+RegisterPoseResult = collections.namedtuple("RegisterPoseResult", EpipolarResult._fields + PoseResult._fields)
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
 
 
@@ -801,6 +811,43 @@ class Context:
         return self._epipolar(lambda *out: lib().cusift_register_epipolar(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
             int(seed) & 0xFFFFFFFFFFFFFFFF, *out), n1, max(loops, 0), want_all)
+
+    @staticmethod
+    def _pose(call):
+        rt, votes, sigma = np.zeros((3, 4), dtype=np.float64), np.zeros(4, dtype=np.int32), np.zeros(3, dtype=np.float64)
+        front = C.c_int(0)
+        out = call(rt.ctypes.data, C.byref(front), votes.ctypes.data, sigma.ctypes.data)
+        return out, PoseResult(rt, front.value, votes, sigma)
+
+    def estimate_pose(self, d_sift, num_pts, fundamental, camera, camera2=None, num_pts2=-1, rule=0, lo=0.0, hi=0.8,
+                      thresh=1.0):
+        """cusift_estimate_pose: from a fundamental matrix (float64 [9], as estimate_fundamental returns it) and the two
+        views' intrinsics (capi.Camera; camera2 None: both views use `camera`) to [R | t] -- the essential matrix's four
+        candidates, the cheirality vote over the candidates that fit F at `thresh`, all fp64 on the device -- and to a
+        triangulated point in coords3D of every record that is in front (zeros elsewhere), at the scale |t| = 1.  One
+        synchronisation.  Returns a PoseResult."""
+        f = np.ascontiguousarray(fundamental, dtype=np.float64).ravel()
+        if f.size != 9:
+            raise ValueError("fundamental must hold 9 values, not %d" % f.size)
+        _, res = self._pose(lambda *out: check(lib().cusift_estimate_pose(
+            self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi, f.ctypes.data, thresh,
+            C.byref(camera), C.byref(camera2) if camera2 is not None else None, *out)))
+        return res
+
+    def register_pose(self, d_sift1, n1, d_sift2, n2, camera, camera2=None, distance=1, rule=None, lo=None, hi=None,
+                      loops=10000, thresh=1.0, refine_loops=5, refine_thresh=1.0, seed=0, want_all=False):
+        """cusift_register_pose: register_epipolar, then estimate_pose at refine_thresh with the refined F where the
+        device left it -- one synchronisation, the staged route's bytes.  Returns a RegisterPoseResult: the
+        EpipolarResult's fields, then rt, num_front, votes, sigma."""
+        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
+        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
+        hi = 0.8 if hi is None else hi
+        loops = int(loops)
+        epi, pose = self._pose(lambda *pout: self._epipolar(lambda *out: lib().cusift_register_pose(
+            self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(camera), C.byref(camera2) if camera2 is not None else None,
+            *(out + pout)), n1, max(loops, 0), want_all))
+        return RegisterPoseResult(*(epi + pose))
 
     def estimate_rigid(self, coord, indices=None, loops=None, thresh2=0.0025, kind="3d", seed=0, want_all=False):
         """cusift_estimate_rigid: RANSAC rigid transform x ~ R y + t from coord float32 [N, 6] (reference xyz, moving

@@ -4,11 +4,11 @@
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, math-eval, packing)
 //   sift_register.hip the registration host layer: matcher, FindHomography, planar registration, rigid RANSAC, RGB-D
-//                     and epipolar registration and the pair-list forms of the first three
+//                     and epipolar registration, the calibrated pose and the pair-list forms of the first three
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
-// The device units share sift_device.h (all of them) and sift_ransac.h (the six registration units: sampling, winner,
+// The device units share sift_device.h (all of them) and sift_ransac.h (the seven registration units: sampling, winner,
 // reductions, ordered compaction, pair strides).
 #pragma once
 
@@ -92,6 +92,10 @@ __global__ void epipolar_score_kernel(const float *, int, int, const double *, i
 __global__ void epipolar_select_kernel(cusift_point *, int, const float *, const float *, const unsigned char *,
                                        const double *, const int *, int, float, int, float, int *, char *, float *,
                                        PlanarBatch);
+__global__ void pose_vote_kernel(const float *, const unsigned char *, int, const int *, PoseCams, float, int *,
+                                 PlanarBatch);
+__global__ void pose_write_kernel(cusift_point *, const float *, const unsigned char *, int, const int *, PoseCams, float,
+                                  int *, PlanarBatch);
 __global__ void sequence_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                      const cusift_match_row *, int, float, float, float *, unsigned char *, int *, int *,
                                      PlanarBatch, const cusift_match_row *);

@@ -1,5 +1,5 @@
 // sift_ransac.h -- the device helpers that the registration units share (sift_rigid.hip, sift_homography.hip,
-// sift_planar.hip, sift_epipolar.hip, sift_sequence.hip, sift_rgbd.hip).  Inline functions only: the LDS arrays stay
+// sift_planar.hip, sift_epipolar.hip, sift_pose.hip, sift_sequence.hip, sift_rgbd.hip).  Inline functions only: the LDS arrays stay
 // declared in the kernels and are passed in.  Every rule here is pinned bit for bit by the units' tests.
 //
 // SAMPLING.  The reference seeds cuRAND with time(0) (extras/rigidTransform.cu:411), which cannot be reproduced.  Here

@@ -1,5 +1,5 @@
 // sift_register.hip -- the registration host layer of the C ABI: the matcher, FindHomography, planar registration, rigid
-// RANSAC, RGB-D registration, epipolar registration and the pair-list forms.  An entry point that reads results back lays
+// RANSAC, RGB-D registration, epipolar registration, the calibrated pose and the pair-list forms.  An entry point that reads results back lays
 // its state out in the context's register_scratch, what travels back first, and ends in one copy and one synchronisation.
 #include "sift_host.h"
 
@@ -450,11 +450,16 @@ extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int 
 // ------------------------------------------------------------------------------------------------
 // RGB-D registration (sift_rgbd.hip): depth lift, match selection, the fused frame-pair call
 // ------------------------------------------------------------------------------------------------
-static int check_camera(const cusift_camera *cam, const char *who) {
-  if (!cam) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
+// the intrinsics alone: all that the calibrated pose looks at
+static int check_pinhole(const cusift_camera *cam, const char *who) {
   if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || cam->fx == 0.0f || cam->fy == 0.0f ||
       !std::isfinite(cam->cx) || !std::isfinite(cam->cy) || !std::isfinite(cam->origin))
     return fail(CUSIFT_ERR_INVALID, "%s: fx and fy must be finite and not 0, cx / cy / origin finite", who);
+  return CUSIFT_OK;
+}
+static int check_camera(const cusift_camera *cam, const char *who) {
+  if (!cam) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
+  TRY(check_pinhole(cam, who));
   if (!(cam->units_per_metre > 0.0f) || !std::isfinite(cam->units_per_metre))
     return fail(CUSIFT_ERR_INVALID, "%s: units_per_metre must be > 0", who);
   if (cam->encoding != 0 && cam->encoding != 1)
@@ -613,6 +618,103 @@ extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// calibrated two-view pose (sift_pose.hip): the stage behind the epipolar selection -- [R | t], coords3D -- one read-back
+// ------------------------------------------------------------------------------------------------
+struct PoseOut {
+  double *h_rt;
+  int *num_front, *h_votes;
+  double *h_sigma;
+};
+// One call's pose stage: what its two kernels take besides the epipolar state, and the pose head as it was read back.
+struct PoseStage {
+  PoseCams cams;
+  float thresh;
+  PoseOut out;
+  char back[kPoseHeadBytes];
+};
+
+// every refusal that the pose adds to the epipolar calls'; camera2 == NULL: both views use camera1.  units_per_metre and
+// encoding belong to the depth image and are not looked at
+static int pose_check(const char *who, const cusift_camera *camera1, const cusift_camera *camera2, const PoseOut &o) {
+  if (!camera1 || !o.h_rt || !o.num_front) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera or output", who);
+  TRY(check_pinhole(camera1, who));
+  return camera2 ? check_pinhole(camera2, who) : CUSIFT_OK;
+}
+static PoseStage pose_stage(const cusift_camera *camera1, const cusift_camera *camera2, float thresh, const PoseOut &o) {
+  const cusift_camera *c2 = camera2 ? camera2 : camera1;
+  PoseStage st{};
+  st.cams = PoseCams{(double)camera1->fx, (double)camera1->fy, (double)camera1->cx - (double)camera1->origin,
+                     (double)camera1->cy - (double)camera1->origin, (double)c2->fx, (double)c2->fy,
+                     (double)c2->cx - (double)c2->origin, (double)c2->cy - (double)c2->origin};
+  st.thresh = thresh;
+  st.out = o;
+  return st;
+}
+
+// The pose head zeroed, the two launches, and the head's copy to the host -- adjacent to the caller's one read-back, in
+// front of its one synchronisation.  d_head: the epipolar head with F at kEpiHeadF.  num_pts == 0: one workgroup, which
+// writes the head.
+static int pose_enqueue(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, const float *d_coord,
+                        const unsigned char *d_marks, const int *d_head, int *d_pose, PoseStage &st) {
+  const dim3 grid(std::max(idiv_up(num_pts, 256), 1));
+  HIP_TRY(hipMemsetAsync(d_pose, 0, kPoseHeadBytes, ctx->stream));
+  hipLaunchKernelGGL(pose_vote_kernel, grid, dim3(256), 0, ctx->stream, d_coord, d_marks, num_pts, d_head, st.cams,
+                     st.thresh, d_pose, PlanarBatch{});
+  hipLaunchKernelGGL(pose_write_kernel, grid, dim3(256), 0, ctx->stream, d_sift, d_coord, d_marks, num_pts, d_head,
+                     st.cams, st.thresh, d_pose, PlanarBatch{});
+  HIP_TRY(hipMemcpyAsync(st.back, d_pose, kPoseHeadBytes, hipMemcpyDeviceToHost, ctx->stream));
+  return CUSIFT_OK;
+}
+
+// after the synchronisation: the pose head into the caller's outputs
+static void pose_report(const PoseStage &st) {
+  memcpy(st.out.h_rt, st.back + sizeof(double) * kPoseHeadRt, sizeof(double) * 12);
+  *st.out.num_front = head_int(st.back, kPoseHeadFront);
+  if (st.out.h_votes) memcpy(st.out.h_votes, st.back + sizeof(int) * kPoseHeadVotes, sizeof(int) * 4);
+  if (st.out.h_sigma) memcpy(st.out.h_sigma, st.back + sizeof(double) * kPoseHeadSigma, sizeof(double) * 3);
+}
+
+// The staged route: F from the host, the marking, the pose stage; the arguments are checked.
+static int pose_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
+                    const double *h_fundamental, PoseStage &st) {
+  // [epipolar head | pose head] in front, behind them what stays on the device
+  ScratchLayout s;
+  s.take(kEpiHeadBytes);  // the head, at 0: only F is filled in
+  const size_t pose_off = s.take(kPoseHeadBytes);
+  const size_t coord_off = s.take(sizeof(float) * 4 * (size_t)num_pts);
+  const size_t mark_off = s.take((size_t)num_pts);
+  const size_t block_off = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
+  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
+  char *base = ctx->register_scratch;
+  HIP_TRY(hipMemcpyAsync(base + sizeof(double) * kEpiHeadF, h_fundamental, sizeof(double) * 9, hipMemcpyHostToDevice,
+                         ctx->stream));
+  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
+  if (num_pts > 0)
+    hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream,
+                       (const cusift_point *)d_sift, num_pts, num_pts2, rule, t_lo, t_hi, at<float>(base, coord_off),
+                       at<unsigned char>(base, mark_off), at<int>(base, block_off), PlanarBatch{},
+                       (const cusift_point *)nullptr);
+  TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(base, coord_off), at<unsigned char>(base, mark_off), (const int *)base,
+                   at<int>(base, pose_off), st));
+  TRY(check_launch("estimate_pose"));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  pose_report(st);
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_estimate_pose(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo,
+                                    float hi, const double h_fundamental_in[9], float thresh,
+                                    const cusift_camera *camera1, const cusift_camera *camera2, double h_rt[12],
+                                    int *num_front, int *h_votes, double *h_sigma) {
+  TRY(enter(ctx));
+  const PoseOut o{h_rt, num_front, h_votes, h_sigma};
+  TRY(pose_check("EstimatePose", camera1, camera2, o));
+  TRY(ransac_check("EstimatePose", h_fundamental_in != nullptr, d_sift, num_pts, rule, lo, hi, 1, thresh, 0, thresh));
+  PoseStage st = pose_stage(camera1, camera2, thresh, o);
+  return pose_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, h_fundamental_in, st);
+}
+
+// ------------------------------------------------------------------------------------------------
 // epipolar registration (sift_epipolar.hip): candidates, seeded fundamental-matrix RANSAC, refit -- one read-back
 // ------------------------------------------------------------------------------------------------
 struct EpipolarOut {
@@ -687,13 +789,15 @@ static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, 
                      refine_loops, refine_thresh, d_head, d_flags, d_err, nb);
 }
 
-// The five launches and the one read-back; the arguments are checked.  d_cross as planar_run's.
+// The five launches and the one read-back; the arguments are checked.  d_cross as planar_run's.  pose != NULL
+// (cusift_register_pose): its stage behind the selection, at refine_thresh, and its head behind everything else.
 static int epipolar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
                         int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                        const EpipolarOut &o, const cusift_point *d_cross) {
+                        const EpipolarOut &o, const cusift_point *d_cross, PoseStage *pose = nullptr) {
   if (num_pts < 8) {  // eight correspondences are the least that fix F: the answer needs no device work
     epipolar_nothing(num_pts, num_loops, o);
-    return CUSIFT_OK;
+    // a pose stage still owes coords3D of the records: the staged route from the nine zeros just reported
+    return pose ? pose_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, o.h_fundamental, *pose) : CUSIFT_OK;
   }
   // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
   const EpipolarBlock b(num_pts, num_loops);
@@ -701,6 +805,7 @@ static int epipolar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int 
   s.take(kEpiHeadBytes);  // the head, at 0
   const size_t flag_off = s.take((size_t)num_pts);
   const size_t block_off = s.take(b.bytes);
+  const size_t pose_off = pose ? s.take(kPoseHeadBytes) : 0;
   TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
   char *base = ctx->register_scratch, *d_block = base + block_off;
   const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
@@ -709,12 +814,16 @@ static int epipolar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int 
                      at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), PlanarBatch{}, d_cross);
   epipolar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
                   base + flag_off, nullptr, 1, PlanarBatch{});
+  if (pose)
+    TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
+                     (const int *)base, at<int>(base, pose_off), *pose));
   TRY(check_launch("estimate_fundamental"));
   // the one blocking read-back
   const bool all = o.h_drawn || o.h_all_f || o.h_all_counts;
   std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
   HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (pose) pose_report(*pose);
   const char *head = back.data(), *block = back.data() + block_off;
   if (head_int(head, kPlanarHeadCand) < 8) {  // the kernels left the records alone
     epipolar_nothing(num_pts, num_loops, o);
@@ -932,6 +1041,35 @@ extern "C" int cusift_register_rgbd_batch(cusift_ctx *ctx, cusift_point *d_point
     if (h_sel_pairs) memcpy(h_sel_pairs + 2 * p * M, back.data() + pair_off + sizeof(int) * 2 * p * M, sizeof(int) * 2 * n);
   }
   return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the fused pose call: matcher, epipolar registration and the pose stage (sift_pose.hip) -- one read-back
+// ------------------------------------------------------------------------------------------------
+extern "C" int cusift_register_pose(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                    int num_pts2, int distance, int rule, float lo, float hi, int num_loops, float thresh,
+                                    int refine_loops, float refine_thresh, uint64_t seed, const cusift_camera *camera1,
+                                    const cusift_camera *camera2, double h_fundamental[9], double h_ransac[9],
+                                    int *num_candidates, int *num_matches, int *num_fit, int *best_loop, char *h_inliers,
+                                    int *h_drawn, double *h_all_f, int *h_all_counts, double h_rt[12], int *num_front,
+                                    int *h_votes, double *h_sigma) {
+  TRY(enter(ctx));
+  const EpipolarOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
+                      best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
+  const PoseOut po{h_rt, num_front, h_votes, h_sigma};
+  TRY(pose_check("RegisterPose", camera1, camera2, po));
+  TRY(epipolar_check("RegisterPose", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  TRY(check_distance("RegisterPose", distance));
+  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterPose: missing data");
+  // the matcher exactly as cusift_register_epipolar enqueues it, cross-check included
+  const bool cross = ctx->cross_check != 0;
+  if (cross)
+    TRY(cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance));
+  else
+    TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
+  PoseStage st = pose_stage(camera1, camera2, refine_thresh, po);
+  return epipolar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+                      seed, o, cross ? d_sift2 : nullptr, &st);
 }
 
 // ------------------------------------------------------------------------------------------------

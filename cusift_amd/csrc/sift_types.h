@@ -169,6 +169,15 @@ constexpr size_t kPlanarHeadBytes = 128;              // between the heads of a 
 // them (planar_compact_kernel writes the first), then, counted in doubles, F[9] (refined) and R[9] (the winner).
 constexpr int kEpiHeadF = 16, kEpiHeadR = 32;
 constexpr size_t kEpiHeadBytes = 384;                 // between the heads of a batch
+// A pose head (sift_pose.hip), a block of its own behind everything the epipolar call keeps: counted in doubles [R | t]
+// (12) and sigma (3); counted in 4-byte words the four candidates' votes and num_front.
+constexpr int kPoseHeadRt = 0, kPoseHeadSigma = 12, kPoseHeadVotes = 32, kPoseHeadFront = 36;
+constexpr size_t kPoseHeadBytes = 256;                // between the heads of a batch
+// The two views' intrinsics as the pose kernels take them: K = [[fx, 0, px], [0, fy, py], [0, 0, 1]] with px = cx - origin
+// and py = cy - origin, the camera's floats widened to double before the subtraction.
+struct PoseCams {
+  double fx1, fy1, px1, py1, fx2, fy2, px2, py2;
+};
 // A rigid result head: Rt[12] as float, then as int the winner's count, the winning loop and -- with a device-side point
 // count -- that count.
 constexpr int kRigidHeadInliers = 12, kRigidHeadLoop = 13, kRigidHeadCount = 14;

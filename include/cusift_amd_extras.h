@@ -2,7 +2,7 @@
  * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography, the
  * planar registration built on both (seeded RANSAC + refit on the device), the RANSAC rigid transform and the RGB-D
  * registration built on them (depth lift, match selection, the fused call for one frame pair and for a pair list over a
- * batch of frames).
+ * batch of frames), the epipolar registration and the calibrated pose behind it.
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
@@ -226,6 +226,79 @@ typedef struct cusift_camera {
   int encoding;          /* 0: the sample is the depth; 1: SUN3D PNG, the depth rotated left by 3 bits */
 } cusift_camera;
 
+/* ---- calibrated two-view pose on the device: [R | t] and triangulated points from F (sift_pose.hip) ------------- */
+/* The stage behind cusift_estimate_fundamental for a calibrated camera: from F and the intrinsics to the relative pose
+ * and to a 3-D point in coords3D of every record that fits, as the RGB-D path ends -- without reading F back, decomposing
+ * the essential matrix, testing cheirality and triangulating on the host.  The definition is the library's own and ALL OF
+ * IT IS FP64; every expression is evaluated in the order written (the build uses -ffp-contract=off).
+ * CAMERAS: K = [[fx, 0, px], [0, fy, py], [0, 0, 1]], px = cx - origin, py = cy - origin, the cusift_camera's floats
+ * widened to double first; units_per_metre and encoding are ignored.  camera1 belongs to the records' own image (x1 =
+ * coords2D), camera2 to the matches' (x2 = match_xpos / match_ypos); camera2 == NULL: both views use camera1.
+ * ESSENTIAL MATRIX: E = K2^T (F K1) with F row-major, x2^T F x1 = 0, the epipolar calls' convention:
+ *     A[i][0] = F[3i]*fx1;  A[i][1] = F[3i+1]*fy1;  A[i][2] = (F[3i]*px1 + F[3i+1]*py1) + F[3i+2]
+ *     E[0][j] = fx2*A[0][j];  E[1][j] = fy2*A[1][j];  E[2][j] = (px2*A[0][j] + py2*A[1][j]) + A[2][j]
+ * DECOMPOSITION: G = E^T E, G[i][j] = (E[0][i]*E[0][j] + E[1][i]*E[1][j]) + E[2][i]*E[2][j]; its eigenpairs by the cyclic
+ * Jacobi of the epipolar refit's rank-2 step (3 x 3, the same fixed sweep schedule), ordered l1 >= l2 >= l3, the first
+ * among equals; sigma_i = sqrt(l_i > 0 ? l_i : 0);  v3 = v1 x v2;  u1 = E v1 / sigma_1;  u2 = w / |w| with w = E v2 -
+ * (E v2 . u1) u1;  u3 = u1 x u2 -- U = [u1 u2 u3] and V = [v1 v2 v3] are proper rotations by construction (dot products
+ * and matrix-vector rows are (a0*b0 + a1*b1) + a2*b2).  sigma_3 is then replaced by |u3 . (E v3)| where that is finite:
+ * l3 of a rank-2 F is rounding noise of size eps * l1, and its root would keep only half the digits of a value whose
+ * distance from 0 is what the caller looks at.  With W = [[0,-1,0],[1,0,0],[0,0,1]] the four candidates (R21,
+ * t21), each meaning X2 = R21 X1 + t21, are in this order
+ *     (Ra, +u3), (Ra, -u3), (Rb, +u3), (Rb, -u3)
+ *     Ra = U W V^T:    Ra[i][j] = (u2[i]*v1[j] - u1[i]*v2[j]) + u3[i]*v3[j]
+ *     Rb = U W^T V^T:  Rb[i][j] = (u1[i]*v2[j] - u2[i]*v1[j]) + u3[i]*v3[j]
+ * FIT SET: the candidates -- marked exactly as cusift_estimate_fundamental marks them: rule, lo, hi, finite coordinates,
+ * 0 <= match < num_pts2 when num_pts2 >= 0 -- that pass the epipolar calls' inlier test under F at `thresh`.
+ * DEPTHS of one record under one candidate (R21, t21):
+ *     d1 = ((x1 - px1) / fx1, (y1 - py1) / fy1, 1);  d2 = ((x2 - px2) / fx2, (y2 - py2) / fy2, 1)
+ *     a[i] = (R21[i][0]*d1x + R21[i][1]*d1y) + R21[i][2]
+ *     aa = (a0*a0 + a1*a1) + a2*a2;  bb = (d2x*d2x + d2y*d2y) + 1;  ab = (a0*d2x + a1*d2y) + a2
+ *     at = (a0*t0 + a1*t1) + a2*t2;  bt = (d2x*t0 + d2y*t1) + t2
+ *     det = aa*bb - ab*ab;  z1 = (ab*bt - bb*at) / det;  z2 = (aa*bt - ab*at) / det
+ * the least-squares solution of z1 a + t21 = z2 d2.  IN FRONT: z1 > 0 && z2 > 0; a NaN fails.  (Under -t21 both depths
+ * change sign and nothing else, exactly.)
+ * WINNER: the candidate with the most records of the fit set in front, among equals the first.  h_votes[4] (may be NULL)
+ * = the four counts, *num_front = the winner's.
+ * h_rt is double [12], row-major [R | t] in the direction of cusift_register_rgbd, X1 = R X2 + t: R = R21^T, t[i] =
+ * -((R21[0][i]*t0 + R21[1][i]*t1) + R21[2][i]*t2), |t| = 1 -- the baseline is the unit of length.  h_sigma[3] (may be
+ * NULL) = the singular values of E as computed above: sigma_2 / sigma_1 far from 1 says that F and the intrinsics
+ * disagree or that F is poorly determined.
+ * coords3D IS WRITTEN FOR EVERY RECORD in [0, num_pts): ((float)(z1*d1x), (float)(z1*d1y), (float)z1) under the winner
+ * if the record is in the fit set, in front, and the three floats are finite with z > 0; (0, 0, 0) otherwise.  The point
+ * lies on the record's own pixel ray in the camera coordinates of frame 1, cusift_lift_depth's convention, z == 0 its
+ * "no depth" mark.  No other byte of any record changes.
+ * DEGENERATE ANSWERS, CUSIFT_OK: F is nine zeros or not finite, sigma_2 is not > 0, an entry of Ra, Rb, u3 or sigma is
+ * not finite, or the best vote is 0 (num_pts == 0 included) -- h_rt = [I | 0], *num_front = 0, coords3D of every record in
+ * [0, num_pts) zeros; the votes are 0 in all these cases, h_sigma is what was computed.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): a NULL camera1 / h_rt / num_front / h_fundamental_in; fx or fy
+ * zero or not finite, cx, cy or origin not finite, in either camera; thresh not > 0 (NaN included); what
+ * cusift_estimate_fundamental refuses of d_sift, num_pts, rule, lo, hi.
+ * Launches: the marking, then pose_vote_kernel and pose_write_kernel (the candidate list itself is not needed, so the
+ * compaction is not run).  Blocking: ONE stream synchronisation, at the read-back.  The same input gives the same bytes. */
+int cusift_estimate_pose(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2 /* < 0: no check */, int rule,
+                         float lo, float hi, const double h_fundamental_in[9], float thresh,
+                         const cusift_camera *camera1, const cusift_camera *camera2 /* NULL: camera1 */,
+                         double h_rt[12], int *num_front, int *h_votes /* [4], may be NULL */,
+                         double *h_sigma /* [3], may be NULL */);
+
+/* cusift_register_epipolar followed by cusift_estimate_pose(d_sift1, num_pts1, num_pts2, rule, lo, hi, the returned
+ * h_fundamental, refine_thresh, ...) with ONE synchronisation: the two pose launches follow the selection kernel on the
+ * stream and read F where it left it.  Every epipolar output and every record byte other than coords3D of d_sift1 equals
+ * cusift_register_epipolar's (cross-check included: the marks are the fused call's, so with it on a record that is not
+ * mutual is not in the fit set); the pose outputs and coords3D equal the staged call's.  With fewer than 8 records or
+ * candidates F is nine zeros: the degenerate answer, coords3D of d_sift1 zeroed.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of cusift_register_epipolar and of the cameras and
+ * pose outputs above. */
+int cusift_register_pose(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
+                         int distance, int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                         float refine_thresh, uint64_t seed, const cusift_camera *camera1,
+                         const cusift_camera *camera2 /* NULL: camera1 */, double h_fundamental[9], double h_ransac[9],
+                         int *num_candidates, int *num_matches, int *num_fit, int *best_loop /* may be NULL */,
+                         char *h_inliers /* may be NULL */, int *h_drawn /* may be NULL */,
+                         double *h_all_f /* may be NULL */, int *h_all_counts /* may be NULL */, double h_rt[12],
+                         int *num_front, int *h_votes /* [4], may be NULL */, double *h_sigma /* [3], may be NULL */);
+
 /* Writes coords3D of every record from its coords2D = (x, y) (0-based pixels at base-image scale) and the depth image
  * of its frame, all in fp32:
  *     u = roundf(x), v = roundf(y);  not finite or outside [0, width) x [0, height)  ->  (0, 0, 0)
@@ -268,7 +341,7 @@ int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_i
 
 /* The cross-check of the registrations, a setting of the context (0 = off, the default; 1 = on; anything else:
  * CUSIFT_ERR_INVALID, the setting unchanged).  It affects cusift_register_planar, cusift_register_rgbd,
- * cusift_register_planar_batch, cusift_register_rgbd_batch and cusift_register_epipolar and nothing else; with 0 they enqueue the launches and
+ * cusift_register_planar_batch, cusift_register_rgbd_batch, cusift_register_epipolar and cusift_register_pose and nothing else; with 0 they enqueue the launches and
  * return the bytes they always did.  With 1, record i of frame 1 takes part only if it is MUTUAL: its match m lies in
  * [0, n2) and the column side's best for record m of frame 2 is i -- the column side exactly as cusift_match_mutual /
  * cusift_match_batch_mutual define it, so an exactly tied best keeps the lowest record of frame 1.  Every many-to-one
