@@ -215,16 +215,16 @@ def unit_descriptors(r, n):
     return d / np.linalg.norm(d.astype(np.float64), axis=1, keepdims=True).astype(np.float32)
 
 
-def planted_frames(template, n_a=MAX_PTS, n_b=900, seed=13):
+def planted_frames(template, n_a=MAX_PTS, n_b=900, seed=13, n_planted=700):
     """Two frames of unit-norm random descriptors related by a planted homography: frame B holds n_b of frame A's points
-    (700 mapped with 0.3 px of noise, the rest anywhere), in shuffled order, with A's descriptors plus 1 % noise.  Random
-    real-valued descriptors: no two scores are exactly equal."""
+    (n_planted = 700 mapped with 0.3 px of noise, the rest anywhere), in shuffled order, with A's descriptors plus 1 %
+    noise.  Random real-valued descriptors: no two scores are exactly equal."""
     r = np.random.default_rng(seed)
     H = np.array([[0.95, -0.08, 30.0], [0.07, 1.03, -18.0], [1.8e-5, -2.6e-5, 1.0]])
     xa = np.c_[r.uniform(0, 1280, n_a), r.uniform(0, 960, n_a)]
     seen = r.permutation(n_a)[:n_b]
     xb = apply(H, xa[seen]) + r.normal(0, 0.3, (n_b, 2))
-    xb[700:] = np.c_[r.uniform(0, 1280, n_b - 700), r.uniform(0, 960, n_b - 700)]
+    xb[n_planted:] = np.c_[r.uniform(0, 1280, n_b - n_planted), r.uniform(0, 960, n_b - n_planted)]
     desc_a = unit_descriptors(r, n_a)
     desc_b = desc_a[seen] + r.normal(0, 0.01 / np.sqrt(128), (n_b, 128)).astype(np.float32)
     desc_b = (desc_b / np.linalg.norm(desc_b.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
@@ -277,22 +277,24 @@ def frames():
 def register_batch(ctx, fb, seed, distance=1, pairs=PAIRS, counters="own", loops=LOOPS, refine_loops=5, **kw):
     """The batch call on a fresh upload; returns (PlanarBatchResult, the records afterwards)."""
     pts, cnt = fb.upload(ctx, counters)
+    n_frames, max_pts = fb.points.shape
     args = dict(RULES[distance])
     args.update(kw)
-    res = ctx.register_planar_batch(pts.ptr, cnt.ptr if cnt is not None else None, N_FRAMES, MAX_PTS, pairs,
+    res = ctx.register_planar_batch(pts.ptr, cnt.ptr if cnt is not None else None, n_frames, max_pts, pairs,
                                     distance=distance, loops=loops, thresh=5.0, refine_loops=refine_loops,
                                     refine_thresh=3.0, seed=seed, want_inliers=True, want_errors=True, **args)
-    return res, pts.to_numpy(SIFT_POINT_DTYPE, (N_FRAMES, MAX_PTS))
+    return res, pts.to_numpy(SIFT_POINT_DTYPE, (n_frames, max_pts))
 
 
 def match_rows(ctx, fb, pairs, distance, counters="own"):
     from cusift_amd import capi
 
     pts, cnt = fb.upload(ctx, counters)
-    rows = upload(ctx, np.full((len(pairs), MAX_PTS, 16), SENTINEL, np.uint8))
-    ctx.match_batch(pts.ptr, cnt.ptr if cnt is not None else None, N_FRAMES, MAX_PTS, pairs, rows.ptr, distance)
+    n_frames, max_pts = fb.points.shape
+    rows = upload(ctx, np.full((len(pairs), max_pts, 16), SENTINEL, np.uint8))
+    ctx.match_batch(pts.ptr, cnt.ptr if cnt is not None else None, n_frames, max_pts, pairs, rows.ptr, distance)
     ctx.synchronize()
-    return rows.to_numpy(capi.MatchRow, (len(pairs), MAX_PTS))
+    return rows.to_numpy(capi.MatchRow, (len(pairs), max_pts))
 
 
 def staged(ctx, fb, rows_p, a, b, seed, distance, counts=None, loops=LOOPS, refine_loops=5):

@@ -175,38 +175,56 @@ def unit_descriptors(r, n):
     return d / np.linalg.norm(d.astype(np.float64), axis=1, keepdims=True).astype(np.float32)
 
 
-def synthetic_frames(template, n_a=MAX_PTS, n_b=900, seed=11):
+def synthetic_frames(template, n_a=MAX_PTS, n_b=900, seed=11, n_c=0):
     """Two frames of unit-norm random descriptors at integer pixels with a depth image each: frame B sees n_b of frame
     A's points after the planted motion x_A = R x_B + t, its descriptors are A's plus 1 % noise.  Pixel and millimetre
-    rounding move a lifted point by a few millimetres, far inside the 0.05 m RANSAC threshold."""
+    rounding move a lifted point by a few millimetres, far inside the 0.05 m RANSAC threshold.
+    n_c > 0: a third frame C, n_c of A's points moved once more (x_A = R2 x_C + t2), drawn after everything of A and B, so
+    that those two are the same with and without it; (fc, dc, seen_c, its motion) are appended to the result."""
     r = np.random.default_rng(seed)
     fx, fy, cx, cy = intrinsics()
-    R, t = planted(axis=(0.1, 1.0, 0.05), angle=0.08, t=(0.05, -0.02, 0.04))
     flat = r.choice((W - 80) * (H - 80), n_a, replace=False)
     ua, va = 40 + flat % (W - 80), 40 + flat // (W - 80)
     za = r.integers(900, 2800, n_a)
     xa = np.c_[((ua + 1) - cx) * za / 1000.0 / fx, ((va + 1) - cy) * za / 1000.0 / fy, za / 1000.0]
-    xb = (xa - t) @ R  # R^T (x_A - t)
-    ub = np.rint(xb[:, 0] * fx / xb[:, 2] + cx - 1).astype(np.int64)
-    vb = np.rint(xb[:, 1] * fy / xb[:, 2] + cy - 1).astype(np.int64)
-    zb = np.rint(xb[:, 2] * 1000).astype(np.int64)
-    ok = (ub >= 0) & (ub < W) & (vb >= 0) & (vb < H) & (zb > 0) & (zb < 8192)
-    _, first = np.unique(vb * W + ub, return_index=True)  # one point per pixel of frame B
-    uniq = np.zeros(n_a, bool)
-    uniq[first] = True
-    seen = r.permutation(np.nonzero(ok & uniq)[0])[:n_b]
-    assert len(seen) == n_b
+
+    def view(R, t, n):
+        """n of A's points as the moved camera sees them: (their indices in A, pixel u, v, depth in mm)."""
+        xb = (xa - t) @ R  # R^T (x_A - t)
+        ub = np.rint(xb[:, 0] * fx / xb[:, 2] + cx - 1).astype(np.int64)
+        vb = np.rint(xb[:, 1] * fy / xb[:, 2] + cy - 1).astype(np.int64)
+        zb = np.rint(xb[:, 2] * 1000).astype(np.int64)
+        ok = (ub >= 0) & (ub < W) & (vb >= 0) & (vb < H) & (zb > 0) & (zb < 8192)
+        _, first = np.unique(vb * W + ub, return_index=True)  # one point per pixel of the moved frame
+        uniq = np.zeros(n_a, bool)
+        uniq[first] = True
+        seen = r.permutation(np.nonzero(ok & uniq)[0])[:n]
+        assert len(seen) == n
+        return seen, ub[seen], vb[seen], zb[seen]
+
+    def frame(seen, u, v, z, desc):
+        f = np.zeros(len(seen), SIFT_POINT_DTYPE)
+        f[:] = template[0]
+        f["coords2D"], f["data"] = np.c_[u, v].astype(np.float32), desc
+        d = np.zeros((H, W), np.uint16)
+        d[v, u] = encode_depth(z)
+        return f, d
+
+    def noisy(desc):
+        desc = desc + r.normal(0, 0.01 / np.sqrt(128), desc.shape).astype(np.float32)
+        return (desc / np.linalg.norm(desc.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+
+    R, t = planted(axis=(0.1, 1.0, 0.05), angle=0.08, t=(0.05, -0.02, 0.04))
+    seen, ub, vb, zb = view(R, t, n_b)
     desc_a = unit_descriptors(r, n_a)
-    desc_b = desc_a[seen] + r.normal(0, 0.01 / np.sqrt(128), (n_b, 128)).astype(np.float32)
-    desc_b = (desc_b / np.linalg.norm(desc_b.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
-    fa, fb = np.zeros(n_a, SIFT_POINT_DTYPE), np.zeros(n_b, SIFT_POINT_DTYPE)
-    fa[:], fb[:] = template[0], template[0]
-    fa["coords2D"], fa["data"] = np.c_[ua, va].astype(np.float32), desc_a
-    fb["coords2D"], fb["data"] = np.c_[ub[seen], vb[seen]].astype(np.float32), desc_b
-    da, db = np.zeros((H, W), np.uint16), np.zeros((H, W), np.uint16)
-    da[va, ua] = encode_depth(za)
-    db[vb[seen], ub[seen]] = encode_depth(zb[seen])
-    return fa, fb, da, db, seen, np.hstack([R, t[:, None]])
+    fa, da = frame(np.arange(n_a), ua, va, za, desc_a)
+    fb, db = frame(seen, ub, vb, zb, noisy(desc_a[seen]))
+    out = (fa, fb, da, db, seen, np.hstack([R, t[:, None]]))
+    if n_c:
+        R2, t2 = planted(axis=(-0.2, 1.0, 0.1), angle=-0.03, t=(-0.02, 0.015, 0.03))
+        seen_c, uc, vc, zc = view(R2, t2, n_c)
+        out += frame(seen_c, uc, vc, zc, noisy(desc_a[seen_c])) + (seen_c, np.hstack([R2, t2[:, None]]))
+    return out
 
 
 class FrameBatch:
@@ -243,10 +261,11 @@ def frames(pair):  # noqa: F811
 
 def register_batch(ctx, fb, seed, kind="3d", counters="own", pairs=PAIRS, loops=LOOPS):
     pts, cnt, dep = fb.upload(ctx, counters)
-    out = ctx.register_rgbd_batch(pts.ptr, cnt.ptr if cnt is not None else None, 6, MAX_PTS, dep.ptr, W, H, camera(),
-                                  pairs, distance=1, score_threshold=999.0, ambiguity_threshold=0.6, loops=loops,
+    n_images, max_pts = fb.points.shape
+    out = ctx.register_rgbd_batch(pts.ptr, cnt.ptr if cnt is not None else None, n_images, max_pts, dep.ptr, W, H,
+                                  camera(), pairs, distance=1, score_threshold=999.0, ambiguity_threshold=0.6, loops=loops,
                                   thresh2=THRESH2, kind=kind, seed=seed)
-    return out + (pts.to_numpy(SIFT_POINT_DTYPE, (6, MAX_PTS)),)
+    return out + (pts.to_numpy(SIFT_POINT_DTYPE, (n_images, max_pts)),)
 
 
 def register_pair(ctx, fb, a, b, seed, kind="3d", loops=LOOPS):

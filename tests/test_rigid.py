@@ -391,7 +391,9 @@ SCENES = [(114, 6, 4096), (1500, 2500, 4096), (3, 0, 1), (700, 333, 1000)]
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_in,n_out,loops", SCENES)
 def test_scenes_scoring_solve_selection_and_refit(ctx, n_in, n_out, loops):
-    """Items 2, 3, 4 and 7: 4000 and 1033 points are no multiple of the 256-point tile, 1000 loops no multiple of 64."""
+    """Items 2, 3, 4 and 7: 4000 and 1033 points are no multiple of the 256-point tile, 1000 loops no multiple of 64.  On a
+    part with 256 CUs the 4000 points are scored in 16 splits of 250, so every workgroup still sees ONE partial tile; splits
+    of several tiles, whole and ragged, are tests/test_ransac_sizes.py's."""
     coord = scene(n_in, n_out, seed=n_in + loops)
     n_pts = len(coord)
     idx = triples(n_pts, loops, seed=n_out + 7)
