@@ -351,6 +351,18 @@ RegisterPoseResult = collections.namedtuple("RegisterPoseResult", EpipolarResult
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
 
 
+def _rule_defaults(distance, rule, lo, hi):
+    """(rule, lo, hi) of a fused call: where None, the rule that fits the distance (1 = L2: rule 1 with lo = 999, hi = 0.8
+    as score / ambiguity thresholds; 0 = dot product: rule 0 with lo = 0, hi = 0.8)."""
+    rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
+    return rule, (999.0 if rule == 1 else 0.0) if lo is None else lo, 0.8 if hi is None else hi
+
+
+def _seed64(seed):
+    """Any Python int as the uint64_t seed of the C ABI."""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 def check_rigid_args(coord, indices=None, loops=None, thresh2=0.0025, kind="3d"):
     """What Context.estimate_rigid checks before it calls the library (needs no device): returns (coord float32 [N, 6],
     indices int32 [L, 3] or None, L, type).  ValueError for anything cusift_estimate_rigid would refuse."""
@@ -735,18 +747,25 @@ class Context:
                                            all_c.ctypes.data if want_all else None))
         return (hom, n.value, all_h, all_c) if want_all else (hom, n.value)
 
-    def _planar(self, call, num_pts, loops, want_all):
-        hom, ransac = np.zeros(9, dtype=np.float32), np.zeros(9, dtype=np.float32)
+    # (result type, dtype, samples and values per hypothesis) of the two models that _ransac serves
+    _H = (PlanarResult, np.float32, 4, 8)
+    _F = (EpipolarResult, np.float64, 8, 9)
+
+    @staticmethod
+    def _ransac(kind, call, num_pts, loops, want_all):
+        """Allocates the outputs of a homography or fundamental-matrix call, calls it with them, returns the result."""
+        result, dtype, samples, values = kind
+        model, ransac = np.zeros(9, dtype=dtype), np.zeros(9, dtype=dtype)
         n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         flags = np.zeros(max(num_pts, 1), dtype=np.int8)
-        drawn = np.zeros((4, loops), dtype=np.int32) if want_all else None
-        all_h = np.zeros((8, loops), dtype=np.float32) if want_all else None
+        drawn = np.zeros((samples, loops), dtype=np.int32) if want_all else None
+        all_m = np.zeros((values, loops), dtype=dtype) if want_all else None
         all_c = np.zeros(loops, dtype=np.int32) if want_all else None
-        check(call(hom.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
-                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_h.ctypes.data if want_all else None,
+        check(call(model.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
+                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_m.ctypes.data if want_all else None,
                    all_c.ctypes.data if want_all else None))
-        return PlanarResult(hom, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
-                            flags[:max(num_pts, 0)].astype(bool), drawn, all_h, all_c)
+        return result(model, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
+                      flags[:max(num_pts, 0)].astype(bool), drawn, all_m, all_c)
 
     def estimate_homography(self, d_sift, num_pts, num_pts2=-1, rule=0, lo=0.0, hi=0.8, loops=10000, thresh=5.0,
                             refine_loops=5, refine_thresh=3.0, seed=0, want_all=False):
@@ -756,35 +775,20 @@ class Context:
         match_error of every device record is written.  One synchronisation.  Returns a PlanarResult; with want_all its
         drawn [4, L] / all_homographies [8, L] / all_counts [L] are filled."""
         loops = int(loops)
-        return self._planar(lambda *out: lib().cusift_estimate_homography(
+        return self._ransac(self._H, lambda *out: lib().cusift_estimate_homography(
             self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi, loops, thresh, refine_loops,
-            refine_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, *out), num_pts, max(loops, 0), want_all)
+            refine_thresh, _seed64(seed), *out), num_pts, max(loops, 0), want_all)
 
     def register_planar(self, d_sift1, n1, d_sift2, n2, distance=1, rule=None, lo=None, hi=None, loops=10000,
                         thresh=5.0, refine_loops=5, refine_thresh=3.0, seed=0, want_all=False):
         """cusift_register_planar: match(distance), then estimate_homography over d_sift1 with num_pts2 = n2 -- one
         synchronisation, the staged route's bits.  rule defaults to the one that fits the distance (1 = L2: rule 1 with
         lo = 999, hi = 0.8 as score / ambiguity thresholds; 0 = dot product: rule 0 with lo = 0, hi = 0.8)."""
-        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
-        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
-        hi = 0.8 if hi is None else hi
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
         loops = int(loops)
-        return self._planar(lambda *out: lib().cusift_register_planar(
+        return self._ransac(self._H, lambda *out: lib().cusift_register_planar(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
-            int(seed) & 0xFFFFFFFFFFFFFFFF, *out), n1, max(loops, 0), want_all)
-
-    def _epipolar(self, call, num_pts, loops, want_all):
-        fund, ransac = np.zeros(9, dtype=np.float64), np.zeros(9, dtype=np.float64)
-        n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-        flags = np.zeros(max(num_pts, 1), dtype=np.int8)
-        drawn = np.zeros((8, loops), dtype=np.int32) if want_all else None
-        all_f = np.zeros((9, loops), dtype=np.float64) if want_all else None
-        all_c = np.zeros(loops, dtype=np.int32) if want_all else None
-        check(call(fund.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
-                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_f.ctypes.data if want_all else None,
-                   all_c.ctypes.data if want_all else None))
-        return EpipolarResult(fund, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
-                              flags[:max(num_pts, 0)].astype(bool), drawn, all_f, all_c)
+            _seed64(seed), *out), n1, max(loops, 0), want_all)
 
     def estimate_fundamental(self, d_sift, num_pts, num_pts2=-1, rule=0, lo=0.0, hi=0.8, loops=10000, thresh=1.0,
                              refine_loops=5, refine_thresh=1.0, seed=0, want_all=False):
@@ -795,22 +799,20 @@ class Context:
         every device record is written.  thresh / refine_thresh are in pixels.  One synchronisation.  Returns an
         EpipolarResult; with want_all its drawn [8, L] / all_fundamentals [9, L] / all_counts [L] are filled."""
         loops = int(loops)
-        return self._epipolar(lambda *out: lib().cusift_estimate_fundamental(
+        return self._ransac(self._F, lambda *out: lib().cusift_estimate_fundamental(
             self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi, loops, thresh, refine_loops,
-            refine_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, *out), num_pts, max(loops, 0), want_all)
+            refine_thresh, _seed64(seed), *out), num_pts, max(loops, 0), want_all)
 
     def register_epipolar(self, d_sift1, n1, d_sift2, n2, distance=1, rule=None, lo=None, hi=None, loops=10000,
                           thresh=1.0, refine_loops=5, refine_thresh=1.0, seed=0, want_all=False):
         """cusift_register_epipolar: match(distance), then estimate_fundamental over d_sift1 with num_pts2 = n2 -- one
         synchronisation, the staged route's bytes.  rule / lo / hi default as in register_planar; the cross-check setting
         is honoured as there."""
-        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
-        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
-        hi = 0.8 if hi is None else hi
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
         loops = int(loops)
-        return self._epipolar(lambda *out: lib().cusift_register_epipolar(
+        return self._ransac(self._F, lambda *out: lib().cusift_register_epipolar(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
-            int(seed) & 0xFFFFFFFFFFFFFFFF, *out), n1, max(loops, 0), want_all)
+            _seed64(seed), *out), n1, max(loops, 0), want_all)
 
     @staticmethod
     def _pose(call):
@@ -839,13 +841,11 @@ class Context:
         """cusift_register_pose: register_epipolar, then estimate_pose at refine_thresh with the refined F where the
         device left it -- one synchronisation, the staged route's bytes.  Returns a RegisterPoseResult: the
         EpipolarResult's fields, then rt, num_front, votes, sigma."""
-        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
-        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
-        hi = 0.8 if hi is None else hi
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
         loops = int(loops)
-        epi, pose = self._pose(lambda *pout: self._epipolar(lambda *out: lib().cusift_register_pose(
+        epi, pose = self._pose(lambda *pout: self._ransac(self._F, lambda *out: lib().cusift_register_pose(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
-            int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(camera), C.byref(camera2) if camera2 is not None else None,
+            _seed64(seed), C.byref(camera), C.byref(camera2) if camera2 is not None else None,
             *(out + pout)), n1, max(loops, 0), want_all))
         return RegisterPoseResult(*(epi + pose))
 
@@ -865,7 +865,7 @@ class Context:
         drawn = np.zeros((loops, 3), dtype=np.int32) if want_all else None
         check(lib().cusift_estimate_rigid(self.handle, coord.ctypes.data, n_pts,
                                           indices.ctypes.data if indices is not None else None, loops, float(thresh2),
-                                          rtype, int(seed) & 0xFFFFFFFFFFFFFFFF, rt.ctypes.data, C.byref(n),
+                                          rtype, _seed64(seed), rt.ctypes.data, C.byref(n),
                                           C.byref(best), flags.ctypes.data, all_rt.ctypes.data if want_all else None,
                                           all_c.ctypes.data if want_all else None,
                                           drawn.ctypes.data if want_all else None))
@@ -891,10 +891,11 @@ class Context:
         check(lib().cusift_ctx_set_keep_strongest(self.handle, k))
 
     def set_cross_check(self, on):
-        """cusift_ctx_set_cross_check: while on, register_planar, register_rgbd, register_planar_batch and
-        register_rgbd_batch on this context keep mutual matches only -- record i of frame 1 takes part only if the
-        column side's best for its match is i (the lowest record on exactly tied best scores).  register_planar then
-        writes the match fields of d_sift2 as well and refuses overlapping record ranges.  Nothing else changes."""
+        """cusift_ctx_set_cross_check: while on, register_planar, register_epipolar, register_pose, register_rgbd,
+        register_planar_batch and register_rgbd_batch on this context keep mutual matches only -- record i of frame 1
+        takes part only if the column side's best for its match is i (the lowest record on exactly tied best scores).
+        The four pair calls then write the match fields of d_sift2 as well and refuse overlapping record ranges.  Nothing
+        else changes."""
         check(lib().cusift_ctx_set_cross_check(self.handle, check_cross_check(on)))
 
     def select_strongest(self, d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
@@ -932,7 +933,7 @@ class Context:
         flags = np.zeros(max(n1, 1), dtype=np.int8)
         check(lib().cusift_register_rgbd(self.handle, d_sift1, n1, d_depth1, d_sift2, n2, d_depth2, w, h, pitch,
                                          C.byref(camera), distance, score_threshold, ambiguity_threshold, int(loops),
-                                         float(thresh2), RIGID_KINDS[kind], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                         float(thresh2), RIGID_KINDS[kind], _seed64(seed),
                                          rt.ctypes.data, C.byref(n_match), C.byref(n_in), pairs.ctypes.data,
                                          flags.ctypes.data))
         return rt, pairs[:n_match.value].copy(), flags[:n_match.value].astype(bool), n_in.value
@@ -973,7 +974,7 @@ class Context:
         check(lib().cusift_register_rgbd_batch(self.handle, d_points, d_counters, n_images, max_pts, d_depth, w, h,
                                                pitch, image_stride, C.byref(camera), pairs.ctypes.data, n_pairs,
                                                distance, score_threshold, ambiguity_threshold, int(loops),
-                                               float(thresh2), RIGID_KINDS[kind], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               float(thresh2), RIGID_KINDS[kind], _seed64(seed),
                                                rt.ctypes.data, n_match.ctypes.data, n_in.ctypes.data, sel.ctypes.data,
                                                flags.ctypes.data))
         return (rt, n_match, n_in, [sel[p, :n_match[p]].copy() for p in range(n_pairs)],
@@ -988,9 +989,7 @@ class Context:
         rule / lo / hi default as in register_planar.  Returns a PlanarBatchResult."""
         pairs = pair_list(pairs)
         n_pairs = len(pairs)
-        rule = (1 if distance == 1 else 0) if rule is None else PLANAR_RULES.get(rule, rule)
-        lo = (999.0 if rule == 1 else 0.0) if lo is None else lo
-        hi = 0.8 if hi is None else hi
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
         hom, ransac = np.zeros((n_pairs, 9), dtype=np.float32), np.zeros((n_pairs, 9), dtype=np.float32)
         n_cand, n_match, n_fit, best = (np.zeros(n_pairs, dtype=np.int32) for _ in range(4))
         # the call writes 0 / 1 into the first count entries of a pair's block and nothing behind them
@@ -998,7 +997,7 @@ class Context:
         err = np.full((n_pairs, max(max_pts, 1)), np.nan, dtype=np.float32) if want_errors else None
         check(lib().cusift_register_planar_batch(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
                                                  n_pairs, distance, rule, lo, hi, int(loops), thresh, refine_loops,
-                                                 refine_thresh, int(seed) & 0xFFFFFFFFFFFFFFFF, hom.ctypes.data,
+                                                 refine_thresh, _seed64(seed), hom.ctypes.data,
                                                  ransac.ctypes.data, n_cand.ctypes.data, n_match.ctypes.data,
                                                  n_fit.ctypes.data, best.ctypes.data, flags.ctypes.data,
                                                  err.ctypes.data if want_errors else None))

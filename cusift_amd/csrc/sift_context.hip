@@ -370,7 +370,7 @@ extern "C" int cusift_ctx_set_keep_strongest(cusift_ctx *ctx, int k) {
 }
 int cusift_keep_strongest_of(const cusift_ctx *ctx) { return ctx ? ctx->keep_strongest : 0; }
 
-// Sticky per context, read by the four cusift_register_* calls (sift_register.hip) when they enqueue.
+// Sticky per context, read by the six cusift_register_* calls (sift_register.hip) when they enqueue their matcher.
 extern "C" int cusift_ctx_set_cross_check(cusift_ctx *ctx, int on) {
   if (!ctx) return fail(CUSIFT_ERR_INVALID, "ctx is NULL");
   if (on != 0 && on != 1) return fail(CUSIFT_ERR_INVALID, "cross_check: 0 (off) or 1 (on), got %d", on);

@@ -3,8 +3,8 @@
 //   sift_context.hip  errors, context + arena + policy + stage timers, memory helpers
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, math-eval, packing)
-//   sift_register.hip the registration host layer: matcher, FindHomography, planar registration, rigid RANSAC, RGB-D
-//                     and epipolar registration, the calibrated pose and the pair-list forms of the first three
+//   sift_register.hip the registration host layer: matcher, FindHomography, rigid RANSAC, RGB-D registration, the
+//                     calibrated pose, planar and epipolar registration on one chain, the pair-list forms
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
@@ -205,9 +205,9 @@ struct cusift_ctx {
   // per-row-block partial results of the column side (cusift_match_mutual): [row blocks][num_pts2]
   MatchPartial *match_col_scratch = nullptr;
   size_t match_col_scratch_bytes = 0;
-  // the state of one registration call (sift_register.hip): FindHomography, planar, rigid, RGB-D, the selection's block
-  // counts, the pair-list forms -- what travels back comes first.  Every call lays it out anew and writes what it reads:
-  // nothing is carried from one call to the next.
+  // the state of one registration call (sift_register.hip): FindHomography, rigid, RGB-D, pose, planar, epipolar, the
+  // selection's block counts, the pair-list forms -- what travels back comes first.  Every call lays it out anew and
+  // writes what it reads: nothing is carried from one call to the next.
   char *register_scratch = nullptr;
   size_t register_scratch_bytes = 0;
   // cusift_match_batch / cusift_register_rgbd_batch / cusift_register_planar_batch: the pair list and the matcher's
@@ -230,7 +230,7 @@ struct cusift_ctx {
   bool side_probed = false;  // `side` passed the concurrency probe (policy value 2 accepts no other)
   bool recording = false;  // inside cusift_graph_create's capture
   int keep_strongest = 0;  // cusift_ctx_set_keep_strongest: K > 0, every extraction keeps the K strongest keypoints per image
-  int cross_check = 0;     // cusift_ctx_set_cross_check: 1, the four cusift_register_* calls keep mutual matches only
+  int cross_check = 0;     // cusift_ctx_set_cross_check: 1, the six cusift_register_* calls keep mutual matches only
   unsigned long forks = 0;  // extractions that took the side stream
   // the lists' counters in the arena that the last extraction's join_counts_kernel left zero (stream order): the next
   // extraction that uses exactly them skips its memset.  Anything else that writes the arena resets this.

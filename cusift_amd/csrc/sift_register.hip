@@ -1,6 +1,8 @@
-// sift_register.hip -- the registration host layer of the C ABI: the matcher, FindHomography, planar registration, rigid
-// RANSAC, RGB-D registration, epipolar registration, the calibrated pose and the pair-list forms.  An entry point that reads results back lays
-// its state out in the context's register_scratch, what travels back first, and ends in one copy and one synchronisation.
+// sift_register.hip -- the registration host layer of the C ABI: the matcher, FindHomography, rigid RANSAC, RGB-D
+// registration, the calibrated pose, planar and epipolar registration, the pair-list forms.  An entry point that reads
+// results back lays its state out in the context's register_scratch, what travels back first, and ends in one copy and
+// one synchronisation.  Shared: match_launch (either pair matcher), match_enqueue (a fused call's matcher), mark_launch
+// (the candidate marking), ransac_run (the chain of the homography and of the fundamental matrix, told apart by data).
 #include "sift_host.h"
 
 // the refusals that several entry points share; `who` is the entry point's name in the message
@@ -60,43 +62,11 @@ static int match_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int n_p
   return CUSIFT_OK;
 }
 
-extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
-                            int num_pts2, int distance) {
-  TRY(enter(ctx));
-  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // extras/matching.cu:241-242: nothing to match
-  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: missing data");
-  TRY(check_distance("MatchSiftData", distance));
-  const int row_blocks = idiv_up(num_pts1, 64);
-  int splits, cols_per_split;
-  TRY(match_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
-  const int n1_pad = row_blocks * 64;
-  MatchPartial *partials = nullptr;
-  if (splits > 1) {
-    const size_t bytes = sizeof(MatchPartial) * (size_t)splits * n1_pad;
-    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
-    partials = ctx->match_scratch;
-  }
-  if (distance)
-    hipLaunchKernelGGL(match_kernel<true>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, cols_per_split, partials, n1_pad);
-  else
-    hipLaunchKernelGGL(match_kernel<false>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, cols_per_split, partials, n1_pad);
-  if (splits > 1)
-    hipLaunchKernelGGL(match_merge_kernel, dim3(idiv_up(num_pts1, 256)), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, distance, partials, n1_pad, splits);
-  return check_launch("match");
-}
-
-// Both directions from one pass over the scores: the row side is cusift_match's, the column side is folded from the same
-// accumulators (sift_match.hip).  Both record sets are written, so their ranges must not overlap.
-extern "C" int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, cusift_point *d_sift2,
-                                   int num_pts2, int distance) {
-  TRY(enter(ctx));
-  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // nothing to match, on either side
-  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchMutual: missing data");
-  TRY(check_distance("MatchMutual", distance));
-  TRY(check_disjoint("MatchMutual", d_sift1, num_pts1, d_sift2, num_pts2));
+// The matcher of one pair: one launch, plus the row-side merge when the columns are split.  d_back != NULL
+// (cusift_match_mutual): image 2's records again, to receive the column side -- folded from the same accumulators
+// (sift_match.hip), merged when there are several row blocks.  Both counts >= 1, the arguments are checked.
+static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
+                        int distance, cusift_point *d_back) {
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits, cols_per_split;
   TRY(match_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
@@ -107,25 +77,61 @@ extern "C" int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int n
     TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
     partials = ctx->match_scratch;
   }
-  if (row_blocks > 1) {
+  if (d_back && row_blocks > 1) {
     const size_t bytes = sizeof(MatchPartial) * (size_t)row_blocks * num_pts2;
     TRY(grow_scratch(ctx, ctx->match_col_scratch, ctx->match_col_scratch_bytes, bytes, "", false));
     col_partials = ctx->match_col_scratch;
   }
-  if (distance)
-    hipLaunchKernelGGL(match_mutual_kernel<true>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       d_sift2, num_pts2, cols_per_split, partials, n1_pad, col_partials);
+  const dim3 grid(row_blocks, splits);
+  if (d_back)
+    hipLaunchKernelGGL(distance ? match_mutual_kernel<true> : match_mutual_kernel<false>, grid, dim3(256), 0,
+                       ctx->stream, d_sift1, num_pts1, d_back, num_pts2, cols_per_split, partials, n1_pad,
+                       col_partials);
   else
-    hipLaunchKernelGGL(match_mutual_kernel<false>, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1,
-                       num_pts1, d_sift2, num_pts2, cols_per_split, partials, n1_pad, col_partials);
+    hipLaunchKernelGGL(distance ? match_kernel<true> : match_kernel<false>, grid, dim3(256), 0, ctx->stream, d_sift1,
+                       num_pts1, d_sift2, num_pts2, cols_per_split, partials, n1_pad);
   if (splits > 1)
     hipLaunchKernelGGL(match_merge_kernel, dim3(idiv_up(num_pts1, 256)), dim3(256), 0, ctx->stream, d_sift1, num_pts1,
-                       (const cusift_point *)d_sift2, num_pts2, distance, (const MatchPartial *)partials, n1_pad, splits);
-  if (row_blocks > 1)
-    hipLaunchKernelGGL(match_mutual_merge_kernel, dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_sift2,
+                       d_sift2, num_pts2, distance, (const MatchPartial *)partials, n1_pad, splits);
+  if (col_partials)
+    hipLaunchKernelGGL(match_mutual_merge_kernel, dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_back,
                        num_pts2, (const cusift_point *)d_sift1, num_pts1, distance, (const MatchPartial *)col_partials,
                        row_blocks);
-  return check_launch("match_mutual");
+  return check_launch(d_back ? "match_mutual" : "match");
+}
+
+extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                            int num_pts2, int distance) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // extras/matching.cu:241-242: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: missing data");
+  TRY(check_distance("MatchSiftData", distance));
+  return match_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, nullptr);
+}
+
+// Both directions from one pass over the scores.  Both record sets are written, so their ranges must not overlap.
+extern "C" int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, cusift_point *d_sift2,
+                                   int num_pts2, int distance) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // nothing to match, on either side
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchMutual: missing data");
+  TRY(check_distance("MatchMutual", distance));
+  TRY(check_disjoint("MatchMutual", d_sift1, num_pts1, d_sift2, num_pts2));
+  return match_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, d_sift2);
+}
+
+// The matcher of a fused call `who`, behind the refusals that go with it; it stays enqueued with fewer than 8 records
+// too.  Cross-check (cusift_ctx_set_cross_check): the mutual matcher, which writes the match fields of d_sift2 as well
+// -- the callers' parameter keeps its const spelling -- and refuses overlapping ranges before it enqueues anything.
+// *d_cross: what the marking or the selection then takes, the records of image 2 or NULL.
+static int match_enqueue(cusift_ctx *ctx, const char *who, cusift_point *d_sift1, int num_pts1,
+                         const cusift_point *d_sift2, int num_pts2, int distance, const cusift_point **d_cross) {
+  TRY(check_distance(who, distance));
+  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
+  *d_cross = ctx->cross_check ? d_sift2 : nullptr;
+  if (ctx->cross_check)
+    return cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance);
+  return cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -192,15 +198,42 @@ static int score_splits(cusift_ctx *ctx, int num_pts, long wgs, int per_cu, int 
   return idiv_up(num_pts, per_split);
 }
 
+// The marking's thresholds: rule 1 compares squared scores (include/matching.h:43-44).
+static float mark_thresh(int rule, float t) { return rule == 1 ? t * t : t; }
+
+// The candidate marking over num_pts >= 1 records: coordinates, marks and block counts.  d_cross != NULL: the
+// cross-check against the num_pts2 records of image 2, which carry cusift_match_mutual's fields.
+static void mark_launch(cusift_ctx *ctx, const cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo,
+                        float hi, float *d_coord, unsigned char *d_marks, int *d_blocks, const cusift_point *d_cross) {
+  hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream, d_sift, num_pts,
+                     num_pts2, rule, mark_thresh(rule, lo), mark_thresh(rule, hi), d_coord, d_marks, d_blocks,
+                     PlanarBatch{}, d_cross);
+}
+
 // ------------------------------------------------------------------------------------------------
-// planar registration (sift_planar.hip): candidates, seeded RANSAC homography, refit -- one read-back
+// the marked-RANSAC chain (sift_planar.hip, sift_epipolar.hip): candidates, seeded RANSAC, refit -- its parts up to the
+// planar launches; its run stands behind the pose stage, which it can take
 // ------------------------------------------------------------------------------------------------
-struct PlanarOut {
-  float *h_homography, *h_ransac;
+// What tells the homography from the fundamental matrix, as data: every output is copied by its size.
+struct RansacModel {
+  size_t elem, head_bytes;      // bytes of a model value -- float (H) or double (F) -- and of the result head
+  int samples, values;          // of a hypothesis: the records drawn, the values kept
+  int head_model, head_ransac;  // where the head holds the refined and the winning model, in values (sift_types.h)
+  const void *nothing;          // the nine values reported when there is nothing to fit: the identity, zeros
+  bool epipolar;                // the epipolar kernels, whose block ends in the candidates' own coordinates (ccoord)
+  const char *label;            // check_launch's
+};
+static const double kZeroF[9] = {};
+static const RansacModel kHomography{sizeof(float), kPlanarHeadBytes, 4, 8, kPlanarHeadH, kPlanarHeadR, kIdentH, false,
+                                     "estimate_homography"};
+static const RansacModel kFundamental{sizeof(double), kEpiHeadBytes, 8, 9, kEpiHeadF, kEpiHeadR, kZeroF, true,
+                                      "estimate_fundamental"};
+struct RansacOut {
+  void *h_model, *h_ransac;  // nine values each
   int *num_candidates, *num_matches, *num_fit, *best_loop;
   char *h_inliers;
   int *h_drawn;
-  float *h_all_homo;
+  void *h_all;
   int *h_all_counts;
 };
 
@@ -219,37 +252,39 @@ static int ransac_check(const char *who, bool outputs, const cusift_point *d_sif
   if (num_pts > 0 && !d_sift) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
   return CUSIFT_OK;
 }
-static int planar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
-                        int num_loops, float thresh, int refine_loops, float refine_thresh, const PlanarOut &o) {
-  return ransac_check(who, o.h_homography && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift, num_pts,
+static int precheck(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
+                    int num_loops, float thresh, int refine_loops, float refine_thresh, const RansacOut &o) {
+  return ransac_check(who, o.h_model && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift, num_pts,
                       rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh);
 }
 
-static void planar_identity(int num_pts, int num_loops, const PlanarOut &o) {
-  memcpy(o.h_homography, kIdentH, sizeof(kIdentH));
-  memcpy(o.h_ransac, kIdentH, sizeof(kIdentH));
+// fewer than 8 records or candidates: there is nothing to fit
+static void ransac_nothing(const RansacModel &m, int num_pts, int num_loops, const RansacOut &o) {
+  memcpy(o.h_model, m.nothing, m.elem * 9);
+  memcpy(o.h_ransac, m.nothing, m.elem * 9);
   *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
   if (o.best_loop) *o.best_loop = 0;
   if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
-  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 4 * (size_t)num_loops);
-  if (o.h_all_homo) memset(o.h_all_homo, 0, sizeof(float) * 8 * (size_t)num_loops);
+  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * m.samples * (size_t)num_loops);
+  if (o.h_all) memset(o.h_all, 0, m.elem * m.values * (size_t)num_loops);
   if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
 }
 
 // What one pair keeps on the device, as byte offsets into its block (PlanarBatch::scratch apart in a batch): samples,
-// hypotheses and counts -- which the pair call can read back, so they come first -- then coordinates, candidates, marks
-// and the marking's block counts.
-struct PlanarBlock {
-  size_t idx, homo, counts, coord, cand, marks, blocks, bytes;
-  PlanarBlock(int num_pts, int num_loops) {
+// hypotheses and counts -- which the pair call can read back, so they come first -- then all records' coordinates,
+// candidates, marks, the marking's block counts and, for the fundamental matrix, the candidates' own coordinates.
+struct RansacBlock {
+  size_t idx, model, counts, coord, cand, marks, blocks, ccoord, bytes;
+  RansacBlock(const RansacModel &m, int num_pts, int num_loops) {
     ScratchLayout s;
-    idx = s.take(sizeof(int) * 4 * (size_t)num_loops);
-    homo = s.take(sizeof(float) * 8 * (size_t)num_loops);
+    idx = s.take(sizeof(int) * m.samples * (size_t)num_loops);
+    model = s.take(m.elem * m.values * (size_t)num_loops);
     counts = s.take(sizeof(int) * (size_t)num_loops);
     coord = s.take(sizeof(float) * 4 * (size_t)num_pts);
     cand = s.take(sizeof(int) * (size_t)num_pts);
     marks = s.take((size_t)num_pts);
     blocks = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
+    ccoord = m.epipolar ? s.take(sizeof(float) * 4 * (size_t)num_pts) : 0;
     bytes = s.size;
   }
 };
@@ -257,9 +292,9 @@ struct PlanarBlock {
 // The four launches behind the marking, over the block(s) at d_block.  n_pairs > 1: that many independent problems,
 // PlanarBatch's strides apart, pair p drawing from seed + p; num_pts is then the capacity of a pair.
 static void planar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh,
-                          int refine_loops, float refine_thresh, uint64_t seed, char *d_block, const PlanarBlock &b,
+                          int refine_loops, float refine_thresh, uint64_t seed, char *d_block, const RansacBlock &b,
                           float *d_head, char *d_flags, float *d_err, int n_pairs, PlanarBatch nb) {
-  const float *d_coord = at<float>(d_block, b.coord), *d_homo = at<float>(d_block, b.homo);
+  const float *d_coord = at<float>(d_block, b.coord), *d_homo = at<float>(d_block, b.model);
   const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
   int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
   // scoring: 64 hypotheses per one-wave workgroup, ~8 waves per CU over all pairs, whole 64-point tiles
@@ -269,97 +304,13 @@ static void planar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, in
   hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_marks, num_pts,
                      (const int *)at<int>(d_block, b.blocks), d_cand, (int *)d_head, nb);
   hipLaunchKernelGGL(homography_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream, d_coord, num_pts,
-                     at<int>(d_block, b.idx), num_loops, at<float>(d_block, b.homo), 1, (unsigned long long)seed,
+                     at<int>(d_block, b.idx), num_loops, at<float>(d_block, b.model), 1, (unsigned long long)seed,
                      (const int *)d_cand, (const int *)d_head + kPlanarHeadCand, d_counts, nb);
   hipLaunchKernelGGL(planar_score_kernel, dim3(loop_blocks, splits, n_pairs), dim3(64), 0, ctx->stream, d_coord, num_pts,
                      pts_per_split, d_homo, num_loops, thresh * thresh, d_counts, (const int *)d_head, nb);
   hipLaunchKernelGGL(planar_select_kernel, dim3(1, 1, n_pairs), dim3(256), 0, ctx->stream, d_sift, num_pts, d_coord,
                      d_marks, d_homo, (const int *)d_counts, num_loops, thresh * thresh, refine_loops,
                      refine_thresh * refine_thresh, d_head, d_flags, d_err, nb);
-}
-
-// The five launches and the one read-back; the arguments are checked.  d_cross != NULL: the cross-check against the
-// num_pts2 records of image 2, which carry cusift_match_mutual's fields.
-static int planar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
-                      int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                      const PlanarOut &o, const cusift_point *d_cross) {
-  if (num_pts < 8) {  // extras/homography.cu:205: the answer needs no device work
-    planar_identity(num_pts, num_loops, o);
-    return CUSIFT_OK;
-  }
-  // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
-  const PlanarBlock b(num_pts, num_loops);
-  ScratchLayout s;
-  s.take(kPlanarHeadBytes);  // the head, at 0
-  const size_t flag_off = s.take((size_t)num_pts);
-  const size_t block_off = s.take(b.bytes);
-  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
-  char *base = ctx->register_scratch, *d_block = base + block_off;
-  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
-  hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream,
-                     (const cusift_point *)d_sift, num_pts, num_pts2, rule, t_lo, t_hi, at<float>(d_block, b.coord),
-                     at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), PlanarBatch{}, d_cross);
-  planar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
-                base + flag_off, nullptr, 1, PlanarBatch{});
-  TRY(check_launch("estimate_homography"));
-  // the one blocking read-back
-  const bool all = o.h_drawn || o.h_all_homo || o.h_all_counts;
-  std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const char *head = back.data(), *block = back.data() + block_off;
-  if (head_int(head, kPlanarHeadCand) < 8) {  // extras/homography.cu:220; the kernels left the records alone
-    planar_identity(num_pts, num_loops, o);
-    *o.num_candidates = head_int(head, kPlanarHeadCand);
-    return CUSIFT_OK;
-  }
-  memcpy(o.h_homography, head + sizeof(float) * kPlanarHeadH, sizeof(float) * 9);
-  memcpy(o.h_ransac, head + sizeof(float) * kPlanarHeadR, sizeof(float) * 9);
-  *o.num_candidates = head_int(head, kPlanarHeadCand), *o.num_matches = head_int(head, kPlanarHeadMatches);
-  *o.num_fit = head_int(head, kPlanarHeadFit);
-  if (o.best_loop) *o.best_loop = head_int(head, kPlanarHeadLoop);
-  if (o.h_inliers) memcpy(o.h_inliers, back.data() + flag_off, (size_t)num_pts);
-  if (o.h_drawn) memcpy(o.h_drawn, block + b.idx, sizeof(int) * 4 * (size_t)num_loops);
-  if (o.h_all_homo) memcpy(o.h_all_homo, block + b.homo, sizeof(float) * 8 * (size_t)num_loops);
-  if (o.h_all_counts) memcpy(o.h_all_counts, block + b.counts, sizeof(int) * (size_t)num_loops);
-  return CUSIFT_OK;
-}
-
-extern "C" int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
-                                          float lo, float hi, int num_loops, float thresh, int refine_loops,
-                                          float refine_thresh, uint64_t seed, float h_homography[9], float h_ransac[9],
-                                          int *num_candidates, int *num_matches, int *num_fit, int *best_loop,
-                                          char *h_inliers, int *h_drawn, float *h_all_homo, int *h_all_counts) {
-  TRY(enter(ctx));
-  const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
-                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
-  TRY(planar_check("EstimateHomography", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
-  return planar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed, o,
-                    nullptr);
-}
-
-extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
-                                      int num_pts2, int distance, int rule, float lo, float hi, int num_loops,
-                                      float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                                      float h_homography[9], float h_ransac[9], int *num_candidates, int *num_matches,
-                                      int *num_fit, int *best_loop, char *h_inliers, int *h_drawn, float *h_all_homo,
-                                      int *h_all_counts) {
-  TRY(enter(ctx));
-  const PlanarOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
-                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
-  TRY(planar_check("RegisterPlanar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
-  TRY(check_distance("RegisterPlanar", distance));
-  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterPlanar: missing data");
-  // the matcher stays enqueued with fewer than 8 records too.  Cross-check (cusift_ctx_set_cross_check): the mutual
-  // matcher writes the match fields of d_sift2 as well -- the parameter keeps its const spelling for the callers -- and
-  // refuses overlapping ranges before it enqueues anything
-  const bool cross = ctx->cross_check != 0;
-  if (cross)
-    TRY(cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance));
-  else
-    TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
-  return planar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed,
-                    o, cross ? d_sift2 : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -377,20 +328,13 @@ static void rigid_launch(cusift_ctx *ctx, const float *d_coord, int num_pts, con
   const int splits = score_splits(ctx, num_pts, (long)loop_blocks * n_pairs, 4, 256, false, &pts_per_split);
   const dim3 solve_grid(idiv_up(num_loops, 64), 1, n_pairs), score_grid(loop_blocks, splits, n_pairs);
   const dim3 select_grid(1, 1, n_pairs);
-  if (type == 1)
-    hipLaunchKernelGGL(rigid_solve_kernel<true>, solve_grid, dim3(64), 0, ctx->stream, d_coord, num_pts, d_idx,
-                       num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count, nb);
-  else
-    hipLaunchKernelGGL(rigid_solve_kernel<false>, solve_grid, dim3(64), 0, ctx->stream, d_coord, num_pts, d_idx,
-                       num_loops, draw, (unsigned long long)seed, d_rt, d_counts, d_count, nb);
+  hipLaunchKernelGGL(type == 1 ? rigid_solve_kernel<true> : rigid_solve_kernel<false>, solve_grid, dim3(64), 0,
+                     ctx->stream, d_coord, num_pts, d_idx, num_loops, draw, (unsigned long long)seed, d_rt, d_counts,
+                     d_count, nb);
   hipLaunchKernelGGL(rigid_score_kernel, score_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, pts_per_split, d_rt,
                      num_loops, thresh2, d_counts, d_count, nb);
-  if (type == 1)
-    hipLaunchKernelGGL(rigid_select_kernel<true>, select_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
-                       d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
-  else
-    hipLaunchKernelGGL(rigid_select_kernel<false>, select_grid, dim3(256), 0, ctx->stream, d_coord, num_pts, d_rt,
-                       d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
+  hipLaunchKernelGGL(type == 1 ? rigid_select_kernel<true> : rigid_select_kernel<false>, select_grid, dim3(256), 0,
+                     ctx->stream, d_coord, num_pts, d_rt, d_counts, num_loops, thresh2, d_head, d_flags, d_count, nb);
 }
 
 extern "C" int cusift_estimate_rigid(cusift_ctx *ctx, const float *h_coord, int num_pts, const int *h_indices,
@@ -594,12 +538,10 @@ extern "C" int cusift_register_rgbd(cusift_ctx *ctx, cusift_point *d_sift1, int 
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // blocking like the full route: the depth images may be freed
     return CUSIFT_OK;
   }
-  // cross-check (cusift_ctx_set_cross_check): both directions from the one pass, then the selection's cross-check bit
-  if (cross)
-    TRY(cusift_match_mutual(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
-  else
-    TRY(cusift_match(ctx, d_sift1, n1, d_sift2, num_pts2, distance));
-  select_launch(ctx, d_sift1, n1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, cross ? 1 | 2 : 1,
+  // the matcher as the other fused calls enqueue it; with the cross-check the selection takes its bit as well
+  const cusift_point *d_cross;
+  TRY(match_enqueue(ctx, "RegisterRGBD", d_sift1, n1, d_sift2, num_pts2, distance, &d_cross));
+  select_launch(ctx, d_sift1, n1, d_sift2, num_pts2, score_thresh, ambiguity_thresh, d_cross ? 1 | 2 : 1,
                 at<int>(base, block_off), at<int>(base, pair_off), d_coord, d_count);
   rigid_launch(ctx, d_coord, n1, d_count, at<int>(base, idx_off), num_loops, 1, thresh2, rigid_type, seed,
                at<float>(base, rt_off), at<int>(base, cnt_off), (float *)base, base + flag_off);
@@ -688,12 +630,9 @@ static int pose_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_
   char *base = ctx->register_scratch;
   HIP_TRY(hipMemcpyAsync(base + sizeof(double) * kEpiHeadF, h_fundamental, sizeof(double) * 9, hipMemcpyHostToDevice,
                          ctx->stream));
-  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
   if (num_pts > 0)
-    hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream,
-                       (const cusift_point *)d_sift, num_pts, num_pts2, rule, t_lo, t_hi, at<float>(base, coord_off),
-                       at<unsigned char>(base, mark_off), at<int>(base, block_off), PlanarBatch{},
-                       (const cusift_point *)nullptr);
+    mark_launch(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, at<float>(base, coord_off),
+                at<unsigned char>(base, mark_off), at<int>(base, block_off), nullptr);
   TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(base, coord_off), at<unsigned char>(base, mark_off), (const int *)base,
                    at<int>(base, pose_off), st));
   TRY(check_launch("estimate_pose"));
@@ -715,62 +654,16 @@ extern "C" int cusift_estimate_pose(cusift_ctx *ctx, cusift_point *d_sift, int n
 }
 
 // ------------------------------------------------------------------------------------------------
-// epipolar registration (sift_epipolar.hip): candidates, seeded fundamental-matrix RANSAC, refit -- one read-back
+// the run of the marked-RANSAC chain, and planar and epipolar registration on it -- one read-back
 // ------------------------------------------------------------------------------------------------
-struct EpipolarOut {
-  double *h_fundamental, *h_ransac;
-  int *num_candidates, *num_matches, *num_fit, *best_loop;
-  char *h_inliers;
-  int *h_drawn;
-  double *h_all_f;
-  int *h_all_counts;
-};
-
-static int epipolar_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
-                          int num_loops, float thresh, int refine_loops, float refine_thresh, const EpipolarOut &o) {
-  return ransac_check(who, o.h_fundamental && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift,
-                      num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh);
-}
-
-// fewer than 8 records or candidates: there is no fundamental matrix to report, so both are nine zeros
-static void epipolar_nothing(int num_pts, int num_loops, const EpipolarOut &o) {
-  memset(o.h_fundamental, 0, sizeof(double) * 9);
-  memset(o.h_ransac, 0, sizeof(double) * 9);
-  *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
-  if (o.best_loop) *o.best_loop = 0;
-  if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
-  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 8 * (size_t)num_loops);
-  if (o.h_all_f) memset(o.h_all_f, 0, sizeof(double) * 9 * (size_t)num_loops);
-  if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
-}
-
-// What one pair keeps on the device, as byte offsets into its block (PlanarBatch::scratch apart in a batch): samples,
-// hypotheses and counts -- which the call can read back, so they come first -- then the coordinates of all records,
-// candidates, marks, the marking's block counts and the candidates' own coordinates.
-struct EpipolarBlock {
-  size_t idx, fund, counts, coord, cand, marks, blocks, ccoord, bytes;
-  EpipolarBlock(int num_pts, int num_loops) {
-    ScratchLayout s;
-    idx = s.take(sizeof(int) * 8 * (size_t)num_loops);
-    fund = s.take(sizeof(double) * 9 * (size_t)num_loops);
-    counts = s.take(sizeof(int) * (size_t)num_loops);
-    coord = s.take(sizeof(float) * 4 * (size_t)num_pts);
-    cand = s.take(sizeof(int) * (size_t)num_pts);
-    marks = s.take((size_t)num_pts);
-    blocks = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
-    ccoord = s.take(sizeof(float) * 4 * (size_t)num_pts);
-    bytes = s.size;
-  }
-};
-
 // The four launches behind the marking, over the block(s) at d_block; n_pairs and nb as planar_launch.
 static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh,
-                            int refine_loops, float refine_thresh, uint64_t seed, char *d_block, const EpipolarBlock &b,
+                            int refine_loops, float refine_thresh, uint64_t seed, char *d_block, const RansacBlock &b,
                             int *d_head, char *d_flags, float *d_err, int n_pairs, PlanarBatch nb) {
   const float *d_coord = at<float>(d_block, b.coord);
   float *d_ccoord = at<float>(d_block, b.ccoord);
   const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
-  double *d_fund = at<double>(d_block, b.fund);
+  double *d_fund = at<double>(d_block, b.model);
   int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
   // scoring: as planar_launch, over the candidates -- at most num_pts of them, the number stays on the device
   const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
@@ -789,57 +682,88 @@ static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, 
                      refine_loops, refine_thresh, d_head, d_flags, d_err, nb);
 }
 
-// The five launches and the one read-back; the arguments are checked.  d_cross as planar_run's.  pose != NULL
-// (cusift_register_pose): its stage behind the selection, at refine_thresh, and its head behind everything else.
-static int epipolar_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
-                        int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                        const EpipolarOut &o, const cusift_point *d_cross, PoseStage *pose = nullptr) {
-  if (num_pts < 8) {  // eight correspondences are the least that fix F: the answer needs no device work
-    epipolar_nothing(num_pts, num_loops, o);
+// The marking, the model's four launches and the one read-back; the arguments are checked.  d_cross as mark_launch's.
+// pose != NULL (cusift_register_pose, on F): its stage behind the selection, at refine_thresh, its head last.
+static int ransac_run(cusift_ctx *ctx, const RansacModel &m, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
+                      float lo, float hi, int num_loops, float thresh, int refine_loops, float refine_thresh,
+                      uint64_t seed, const RansacOut &o, const cusift_point *d_cross, PoseStage *pose = nullptr) {
+  if (num_pts < 8) {  // fewer than either solver takes (extras/homography.cu:205): the answer needs no device work
+    ransac_nothing(m, num_pts, num_loops, o);
     // a pose stage still owes coords3D of the records: the staged route from the nine zeros just reported
-    return pose ? pose_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, o.h_fundamental, *pose) : CUSIFT_OK;
+    return pose ? pose_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, (const double *)o.h_model, *pose) : CUSIFT_OK;
   }
   // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
-  const EpipolarBlock b(num_pts, num_loops);
+  const RansacBlock b(m, num_pts, num_loops);
   ScratchLayout s;
-  s.take(kEpiHeadBytes);  // the head, at 0
+  s.take(m.head_bytes);  // the head, at 0
   const size_t flag_off = s.take((size_t)num_pts);
   const size_t block_off = s.take(b.bytes);
   const size_t pose_off = pose ? s.take(kPoseHeadBytes) : 0;
   TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
   char *base = ctx->register_scratch, *d_block = base + block_off;
-  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
-  hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream,
-                     (const cusift_point *)d_sift, num_pts, num_pts2, rule, t_lo, t_hi, at<float>(d_block, b.coord),
-                     at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), PlanarBatch{}, d_cross);
-  epipolar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
+  mark_launch(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, at<float>(d_block, b.coord),
+              at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), d_cross);
+  if (m.epipolar)
+    epipolar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
+                    base + flag_off, nullptr, 1, PlanarBatch{});
+  else
+    planar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
                   base + flag_off, nullptr, 1, PlanarBatch{});
   if (pose)
     TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
                      (const int *)base, at<int>(base, pose_off), *pose));
-  TRY(check_launch("estimate_fundamental"));
+  TRY(check_launch(m.label));
   // the one blocking read-back
-  const bool all = o.h_drawn || o.h_all_f || o.h_all_counts;
+  const bool all = o.h_drawn || o.h_all || o.h_all_counts;
   std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
   HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (pose) pose_report(*pose);
   const char *head = back.data(), *block = back.data() + block_off;
-  if (head_int(head, kPlanarHeadCand) < 8) {  // the kernels left the records alone
-    epipolar_nothing(num_pts, num_loops, o);
+  if (head_int(head, kPlanarHeadCand) < 8) {  // extras/homography.cu:220; the kernels left the records alone
+    ransac_nothing(m, num_pts, num_loops, o);
     *o.num_candidates = head_int(head, kPlanarHeadCand);
     return CUSIFT_OK;
   }
-  memcpy(o.h_fundamental, head + sizeof(double) * kEpiHeadF, sizeof(double) * 9);
-  memcpy(o.h_ransac, head + sizeof(double) * kEpiHeadR, sizeof(double) * 9);
+  memcpy(o.h_model, head + m.elem * m.head_model, m.elem * 9);
+  memcpy(o.h_ransac, head + m.elem * m.head_ransac, m.elem * 9);
   *o.num_candidates = head_int(head, kPlanarHeadCand), *o.num_matches = head_int(head, kPlanarHeadMatches);
   *o.num_fit = head_int(head, kPlanarHeadFit);
   if (o.best_loop) *o.best_loop = head_int(head, kPlanarHeadLoop);
   if (o.h_inliers) memcpy(o.h_inliers, back.data() + flag_off, (size_t)num_pts);
-  if (o.h_drawn) memcpy(o.h_drawn, block + b.idx, sizeof(int) * 8 * (size_t)num_loops);
-  if (o.h_all_f) memcpy(o.h_all_f, block + b.fund, sizeof(double) * 9 * (size_t)num_loops);
+  if (o.h_drawn) memcpy(o.h_drawn, block + b.idx, sizeof(int) * m.samples * (size_t)num_loops);
+  if (o.h_all) memcpy(o.h_all, block + b.model, m.elem * m.values * (size_t)num_loops);
   if (o.h_all_counts) memcpy(o.h_all_counts, block + b.counts, sizeof(int) * (size_t)num_loops);
   return CUSIFT_OK;
+}
+
+extern "C" int cusift_estimate_homography(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
+                                          float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                          float refine_thresh, uint64_t seed, float h_homography[9], float h_ransac[9],
+                                          int *num_candidates, int *num_matches, int *num_fit, int *best_loop,
+                                          char *h_inliers, int *h_drawn, float *h_all_homo, int *h_all_counts) {
+  TRY(enter(ctx));
+  const RansacOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
+  TRY(precheck("EstimateHomography", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  return ransac_run(ctx, kHomography, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops,
+                    refine_thresh, seed, o, nullptr);
+}
+
+extern "C" int cusift_register_planar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                      int num_pts2, int distance, int rule, float lo, float hi, int num_loops,
+                                      float thresh, int refine_loops, float refine_thresh, uint64_t seed,
+                                      float h_homography[9], float h_ransac[9], int *num_candidates, int *num_matches,
+                                      int *num_fit, int *best_loop, char *h_inliers, int *h_drawn, float *h_all_homo,
+                                      int *h_all_counts) {
+  TRY(enter(ctx));
+  const RansacOut o{h_homography, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,    h_inliers, h_drawn,       h_all_homo,  h_all_counts};
+  TRY(precheck("RegisterPlanar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  const cusift_point *d_cross;
+  TRY(match_enqueue(ctx, "RegisterPlanar", d_sift1, num_pts1, d_sift2, num_pts2, distance, &d_cross));
+  return ransac_run(ctx, kHomography, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops,
+                    refine_thresh, seed, o, d_cross);
 }
 
 extern "C" int cusift_estimate_fundamental(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
@@ -849,12 +773,12 @@ extern "C" int cusift_estimate_fundamental(cusift_ctx *ctx, cusift_point *d_sift
                                            int *best_loop, char *h_inliers, int *h_drawn, double *h_all_f,
                                            int *h_all_counts) {
   TRY(enter(ctx));
-  const EpipolarOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
-                      best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
-  TRY(epipolar_check("EstimateFundamental", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
-                     o));
-  return epipolar_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, seed,
-                      o, nullptr);
+  const RansacOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
+  TRY(precheck("EstimateFundamental", d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+               o));
+  return ransac_run(ctx, kFundamental, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops,
+                    refine_thresh, seed, o, nullptr);
 }
 
 extern "C" int cusift_register_epipolar(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1,
@@ -864,21 +788,13 @@ extern "C" int cusift_register_epipolar(cusift_ctx *ctx, cusift_point *d_sift1, 
                                         int *num_matches, int *num_fit, int *best_loop, char *h_inliers, int *h_drawn,
                                         double *h_all_f, int *h_all_counts) {
   TRY(enter(ctx));
-  const EpipolarOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
-                      best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
-  TRY(epipolar_check("RegisterEpipolar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
-                     o));
-  TRY(check_distance("RegisterEpipolar", distance));
-  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterEpipolar: missing data");
-  // as cusift_register_planar: the matcher stays enqueued with fewer than 8 records too, and with the cross-check on it
-  // is the mutual one, which writes the match fields of d_sift2 and refuses overlapping ranges before it enqueues
-  const bool cross = ctx->cross_check != 0;
-  if (cross)
-    TRY(cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance));
-  else
-    TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
-  return epipolar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
-                      seed, o, cross ? d_sift2 : nullptr);
+  const RansacOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
+  TRY(precheck("RegisterEpipolar", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  const cusift_point *d_cross;
+  TRY(match_enqueue(ctx, "RegisterEpipolar", d_sift1, num_pts1, d_sift2, num_pts2, distance, &d_cross));
+  return ransac_run(ctx, kFundamental, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops,
+                    refine_thresh, seed, o, d_cross);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -915,20 +831,13 @@ static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, con
   MatchPartial *col_partials = col_b ? (MatchPartial *)(ctx->pairs_scratch + list_b + part_b) : nullptr;
   HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
   const dim3 grid(row_blocks, splits, n_pairs);
-  if (d_rows_back) {
-    if (distance)
-      hipLaunchKernelGGL(match_batch_mutual_kernel<true>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
-                         d_pairs, cols_per_split, partials, n1_pad, d_rows, col_partials, d_rows_back);
-    else
-      hipLaunchKernelGGL(match_batch_mutual_kernel<false>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts,
-                         d_pairs, cols_per_split, partials, n1_pad, d_rows, col_partials, d_rows_back);
-  } else if (distance) {
-    hipLaunchKernelGGL(match_batch_kernel<true>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
-                       cols_per_split, partials, n1_pad, d_rows);
-  } else {
-    hipLaunchKernelGGL(match_batch_kernel<false>, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, d_pairs,
-                       cols_per_split, partials, n1_pad, d_rows);
-  }
+  if (d_rows_back)
+    hipLaunchKernelGGL(distance ? match_batch_mutual_kernel<true> : match_batch_mutual_kernel<false>, grid, dim3(256),
+                       0, ctx->stream, d_points, d_counters, max_pts, d_pairs, cols_per_split, partials, n1_pad, d_rows,
+                       col_partials, d_rows_back);
+  else
+    hipLaunchKernelGGL(distance ? match_batch_kernel<true> : match_batch_kernel<false>, grid, dim3(256), 0, ctx->stream,
+                       d_points, d_counters, max_pts, d_pairs, cols_per_split, partials, n1_pad, d_rows);
   if (splits > 1)
     hipLaunchKernelGGL(match_batch_merge_kernel, dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream,
                        d_counters, max_pts, d_pairs, distance, cols_per_split, partials, n1_pad, splits, d_rows);
@@ -1054,22 +963,16 @@ extern "C" int cusift_register_pose(cusift_ctx *ctx, cusift_point *d_sift1, int 
                                     int *h_drawn, double *h_all_f, int *h_all_counts, double h_rt[12], int *num_front,
                                     int *h_votes, double *h_sigma) {
   TRY(enter(ctx));
-  const EpipolarOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
-                      best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
+  const RansacOut o{h_fundamental, h_ransac, num_candidates, num_matches, num_fit,
+                    best_loop,     h_inliers, h_drawn,       h_all_f,     h_all_counts};
   const PoseOut po{h_rt, num_front, h_votes, h_sigma};
   TRY(pose_check("RegisterPose", camera1, camera2, po));
-  TRY(epipolar_check("RegisterPose", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
-  TRY(check_distance("RegisterPose", distance));
-  if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "RegisterPose: missing data");
-  // the matcher exactly as cusift_register_epipolar enqueues it, cross-check included
-  const bool cross = ctx->cross_check != 0;
-  if (cross)
-    TRY(cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance));
-  else
-    TRY(cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance));
+  TRY(precheck("RegisterPose", d_sift1, num_pts1, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
+  const cusift_point *d_cross;
+  TRY(match_enqueue(ctx, "RegisterPose", d_sift1, num_pts1, d_sift2, num_pts2, distance, &d_cross));
   PoseStage st = pose_stage(camera1, camera2, refine_thresh, po);
-  return epipolar_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
-                      seed, o, cross ? d_sift2 : nullptr, &st);
+  return ransac_run(ctx, kFundamental, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops,
+                    refine_thresh, seed, o, d_cross, &st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1082,27 +985,25 @@ extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point 
                                             int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
                                             char *h_inliers, float *h_match_error) {
   TRY(enter(ctx));
-  const PlanarOut o{h_homography, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
+  const RansacOut o{h_homography, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
                     h_inliers,    nullptr,  nullptr,          nullptr};
   TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "RegisterPlanarBatch"));
-  TRY(planar_check("RegisterPlanarBatch", d_points, n_images > 0 ? max_pts : 0, rule, lo, hi, num_loops, thresh,
-                   refine_loops, refine_thresh, o));
+  TRY(precheck("RegisterPlanarBatch", d_points, n_images > 0 ? max_pts : 0, rule, lo, hi, num_loops, thresh,
+               refine_loops, refine_thresh, o));
   TRY(check_distance("RegisterPlanarBatch", distance));
   if (n_pairs == 0) return CUSIFT_OK;
   const size_t P = (size_t)n_pairs, M = (size_t)max_pts;
   if (max_pts == 0) {  // every frame is empty, known from the arguments alone
     for (size_t p = 0; p < P; ++p) {
-      const PlanarOut one{h_homography + 9 * p,  h_ransac + 9 * p, h_num_candidates + p,
-                          h_num_matches + p,     h_num_fit + p,    h_best_loop ? h_best_loop + p : nullptr,
-                          nullptr,               nullptr,          nullptr,
-                          nullptr};
-      planar_identity(0, num_loops, one);
+      const RansacOut one{h_homography + 9 * p, h_ransac + 9 * p, h_num_candidates + p, h_num_matches + p,
+                          h_num_fit + p, h_best_loop ? h_best_loop + p : nullptr, nullptr, nullptr, nullptr, nullptr};
+      ransac_nothing(kHomography, 0, num_loops, one);
     }
     return CUSIFT_OK;
   }
-  // [heads | flags | errors] is what travels back, in one copy; behind it what stays on the device: one PlanarBlock per
+  // [heads | flags | errors] is what travels back, in one copy; behind it what stays on the device: one RansacBlock per
   // pair, then the match rows and -- with the cross-check (cusift_ctx_set_cross_check) -- the matcher's back rows
-  const PlanarBlock b(max_pts, num_loops);
+  const RansacBlock b(kHomography, max_pts, num_loops);
   ScratchLayout s;
   s.take(kPlanarHeadBytes * P);  // the heads, at 0
   const size_t flag_off = s.take(P * M);
@@ -1116,13 +1017,12 @@ extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point 
   cusift_match_row *d_rows_back = ctx->cross_check ? at<cusift_match_row>(base, back_off) : nullptr;
   PlanarBatch nb;
   nb.records = 0, nb.scratch = b.bytes, nb.head = kPlanarHeadBytes, nb.flags = M, nb.count = 1;
-  const float t_lo = rule == 1 ? lo * lo : lo, t_hi = rule == 1 ? hi * hi : hi;  // include/matching.h:43-44
   const int *d_pairs = nullptr;
   TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, d_rows_back));
   hipLaunchKernelGGL(sequence_mark_kernel, dim3(idiv_up(max_pts, 256), 1, n_pairs), dim3(256), 0, ctx->stream, d_points,
-                     d_counters, max_pts, d_pairs, (const cusift_match_row *)d_rows, rule, t_lo, t_hi,
-                     at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks),
-                     (int *)base, nb, (const cusift_match_row *)d_rows_back);
+                     d_counters, max_pts, d_pairs, (const cusift_match_row *)d_rows, rule, mark_thresh(rule, lo),
+                     mark_thresh(rule, hi), at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
+                     at<int>(d_block, b.blocks), (int *)base, nb, (const cusift_match_row *)d_rows_back);
   planar_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
                 base + flag_off, at<float>(base, err_off), n_pairs, nb);
   TRY(check_launch("register_planar_batch"));

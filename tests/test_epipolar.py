@@ -330,28 +330,6 @@ def test_epipolar_kernels_compile_for_gfx950_without_scratch():
     assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", text, flags=re.M)
 
 
-def test_one_synchronisation_in_the_epipolar_entry_points():
-    text = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
-    begin = text.index("// epipolar registration (sift_epipolar.hip)")
-    section = text[begin:text.index("// the same over a batch of frames and a pair list", begin)]
-    assert 'extern "C" int cusift_estimate_fundamental(' in section and 'extern "C" int cusift_register_epipolar(' in section
-    code = "\n".join(line.split("//")[0] for line in section.splitlines())
-    assert code.count("hipStreamSynchronize(") == 1 and code.count("epipolar_run(") == 3  # the definition + two callers
-    for blocking in ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(",
-                     "hipFree(", "cusift_ctx_synchronize", "cusift_memcpy"):
-        assert blocking not in code, blocking
-    run = code[code.index("static int epipolar_run("):code.index('extern "C" int cusift_estimate_fundamental(')]
-    order = [run.index(k) for k in ("planar_mark_kernel", "epipolar_launch(", "hipMemcpyAsync(", "hipStreamSynchronize(")]
-    assert order == sorted(order) and run.count("hipMemcpyAsync(") == 1
-    launch = code[code.index("static void epipolar_launch("):code.index("static int epipolar_run(")]
-    order = [launch.index("hipLaunchKernelGGL(" + k) for k in ("planar_compact_kernel",) + NEW_KERNELS]
-    assert order == sorted(order) and launch.count("hipLaunchKernelGGL(") == 4
-    for banned in ("for (", "while (", "hipMemcpy", "hipMemset", "Synchronize", "grow_scratch"):
-        assert banned not in launch, banned
-    reg = code[code.index('extern "C" int cusift_register_epipolar('):]
-    assert reg.index("cusift_match_mutual(") < reg.index("cusift_match(ctx") < reg.index("epipolar_run(")
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # on the GPU
 # ------------------------------------------------------------------------------------------------------------------

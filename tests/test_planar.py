@@ -16,8 +16,9 @@ Yardsticks, none fitted to what the kernels return:
     1e-4 of the limit, and that number is at most 1 % of the records for every input used (asserted on the CPU too).
 
 ONE SYNCHRONISATION is asserted on the source of the two entry points: tests/test_rgbd.py, which the feature request
-points to for the means, holds no run-time probe for cusift_register_rgbd, so the check here is that the whole planar
-section of sift_register.hip contains exactly one synchronising HIP call, the hipStreamSynchronize at the read-back.
+points to for the means, holds no run-time probe for cusift_register_rgbd, so the check (tests/test_register_source.py,
+with those of the other registration calls) is that the path of either through sift_register.hip contains exactly one
+synchronising HIP call, the hipStreamSynchronize at the read-back.
 """
 import ctypes as C
 import os
@@ -284,37 +285,6 @@ def test_planar_kernels_compile_for_gfx950_without_scratch_and_with_vector_store
         assert not [w for w in prefixes if w in text]
     new = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_planar.hip")).read()
     assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", new, flags=re.M)
-
-
-def test_one_synchronisation_in_the_planar_entry_points():
-    text = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
-    begin = text.index("// planar registration (sift_planar.hip)")
-    section = text[begin:text.index("// RANSAC rigid transform (sift_rigid.hip)", begin)]
-    assert 'extern "C" int cusift_estimate_homography(' in section and 'extern "C" int cusift_register_planar(' in section
-    code = "\n".join(line.split("//")[0] for line in section.splitlines())
-    assert code.count("hipStreamSynchronize(") == 1 and code.count("planar_run(") == 3  # the definition + two callers
-    for blocking in ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(",
-                     "hipFree(", "cusift_ctx_synchronize", "cusift_memcpy"):
-        assert blocking not in code, blocking
-    run = code[code.index("static int planar_run("):code.index('extern "C" int cusift_estimate_homography(')]
-    order = [run.index(k) for k in ("planar_mark_kernel", "planar_launch(", "hipMemcpyAsync(", "hipStreamSynchronize(")]
-    assert order == sorted(order)
-    assert run.count("hipMemcpyAsync(") == 1  # one read-back, nothing uploaded
-    assert run.count("hipLaunchKernelGGL(") == 1 and run.count("planar_launch(") == 1  # the marking, then the shared four
-    check_planar_launch(code)
-
-
-def check_planar_launch(code):
-    """planar_launch of sift_register.hip, which the pair and the pair-list routes share: the four launches behind the
-    marking, in their order, none in a loop, and nothing that copies or waits.  `code`: the source without comments."""
-    begin = code.index("static void planar_launch(")
-    launch = code[begin:code.index("\n}\n", begin)]
-    assert launch.count("hipLaunchKernelGGL(") == 4
-    order = [launch.index("hipLaunchKernelGGL(" + k) for k in ("planar_compact_kernel", "homography_solve_kernel",
-                                                               "planar_score_kernel", "planar_select_kernel")]
-    assert order == sorted(order)
-    for banned in ("for (", "while (", "hipMemcpy", "hipMemset", "Synchronize", "grow_scratch"):
-        assert banned not in launch, banned
 
 
 def build_cpp():

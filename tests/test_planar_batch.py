@@ -107,27 +107,6 @@ def test_batch_kernels_compile_for_gfx950_without_scratch_and_with_vector_stores
     assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", seq, flags=re.M)
 
 
-def test_one_synchronisation_in_the_batch_entry_point():
-    text = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
-    begin = text.index('extern "C" int %s(' % NAME)
-    section = text[begin:]  # the last entry point of the file
-    assert section.count('extern "C" int ') == 1
-    code = "\n".join(line.split("//")[0] for line in section.splitlines())
-    assert code.count("hipStreamSynchronize(") == 1
-    for blocking in ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(",
-                     "hipFree(", "cusift_ctx_synchronize", "cusift_memcpy"):
-        assert blocking not in code, blocking
-    order = [code.index(k) for k in ("match_batch_launch(", "sequence_mark_kernel", "planar_launch(", "hipMemcpyAsync(",
-                                     "hipStreamSynchronize(")]
-    assert order == sorted(order)
-    assert code.count("hipMemcpyAsync(") == 1  # one read-back; the pair list is uploaded by the matcher's launcher
-    # five launches -- the marking here, compact / solve / score / select in planar_launch -- none in a loop over the pairs
-    assert code.count("hipLaunchKernelGGL(") == 1 and code.count("planar_launch(") == 1
-    test_planar.check_planar_launch("\n".join(line.split("//")[0] for line in text.splitlines()))
-    launches = code[code.index("match_batch_launch("):code.index("hipMemcpyAsync(")]
-    assert "for (" not in launches and "while (" not in launches
-
-
 def planted_chain(n, seed=4):
     """n mild homographies H_k (frame k onto frame k + 1), float64, of the size the end-to-end test warps with."""
     r = np.random.default_rng(seed)

@@ -413,38 +413,6 @@ def test_pose_kernels_compile_for_gfx950_without_scratch():
     assert "__launch_bounds__(kPoseThreads)" in text and "constexpr int kPoseThreads = 256;" in text
 
 
-def test_one_synchronisation_in_the_pose_entry_points():
-    text = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
-    code = "\n".join(line.split("//")[0] for line in text.splitlines())
-    blocking = ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(", "hipFree(",
-                "cusift_ctx_synchronize", "cusift_memcpy")
-    # the staged call: its section ends where the epipolar one begins
-    begin = code.index("struct PoseOut {")
-    staged = code[begin:code.index("struct EpipolarOut {", begin)]
-    assert 'extern "C" int cusift_estimate_pose(' in staged
-    assert staged.count("hipStreamSynchronize(") == 1 and staged.count("pose_run(") == 2  # the definition + the caller
-    assert not [b for b in blocking if b in staged]
-    run_ = staged[staged.index("static int pose_run("):staged.index('extern "C" int cusift_estimate_pose(')]
-    order = [run_.index(k) for k in ("planar_mark_kernel", "pose_enqueue(", "hipStreamSynchronize(", "pose_report(")]
-    assert order == sorted(order) and run_.count("hipMemcpyAsync(") == 1  # F goes up; the head's copy is the stage's
-    enq = staged[staged.index("static int pose_enqueue("):staged.index("static void pose_report(")]
-    order = [enq.index(k) for k in ("hipMemsetAsync(", "hipLaunchKernelGGL(pose_vote_kernel",
-                                    "hipLaunchKernelGGL(pose_write_kernel", "hipMemcpyAsync(")]
-    assert order == sorted(order) and enq.count("hipLaunchKernelGGL(") == 2 and enq.count("hipMemcpyAsync(") == 1
-    for banned in ("for (", "while (", "Synchronize", "grow_scratch"):
-        assert banned not in enq, banned
-    # the fused call: the epipolar run with the stage behind its launches, in front of its one read-back and wait
-    begin = code.index('extern "C" int cusift_register_pose(')
-    fused = code[begin:code.index("\n}\n", begin)]
-    assert "Synchronize" not in fused and "hipMemcpy" not in fused and not [b for b in blocking if b in fused]
-    assert fused.index("cusift_match_mutual(") < fused.index("cusift_match(ctx") < fused.index("epipolar_run(")
-    assert fused.count("epipolar_run(") == 1 and "&st)" in fused
-    epi = code[code.index("static int epipolar_run("):code.index('extern "C" int cusift_estimate_fundamental(')]
-    order = [epi.index(k) for k in ("epipolar_launch(", "pose_enqueue(", "hipMemcpyAsync(", "hipStreamSynchronize(",
-                                    "pose_report(")]
-    assert order == sorted(order) and epi.count("hipStreamSynchronize(") == 1 and epi.count("pose_enqueue(") == 1
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # on the GPU
 # ------------------------------------------------------------------------------------------------------------------

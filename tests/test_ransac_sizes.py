@@ -41,7 +41,6 @@ part of the file, about 25 s each; everything else takes a few seconds.
 """
 import functools
 import os
-import re
 import time
 
 import numpy as np
@@ -56,6 +55,7 @@ from test_epipolar import run as run_epipolar
 from test_match_mutual import expected_selection
 from test_planar import RULE_ARGS, candidates, upload
 from test_pose import DIR_BOUND, ROT_BOUND, STALE, Case, camera, check_against_model, pose_model, stale, truth_errors
+from test_register_source import EPI, PLANAR, RIGID  # score_splits' arguments, held to the call sites there
 from test_rgbd import lift, other_bytes, select_numpy
 from test_rigid import THRESH2, U, beta_of, check_flags, check_scoring, errors2, horn, hypotheses, planted, rot_dist, trans_dist
 from test_rigid import scene as rigid_scene
@@ -63,10 +63,7 @@ from test_rigid import triples
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-CSRC = os.path.join(ROOT, "cusift_amd", "csrc")
 
-# (per_cu, tile, round_to_tile) of the three call sites of score_splits, in the order they stand in sift_register.hip
-PLANAR, RIGID, EPI = (8, 64, True), (4, 256, False), (8, 64, True)
 CU_COUNTS = (32, 64, 128, 256, 304)
 
 
@@ -316,41 +313,6 @@ LAUNCHES = [
 # ------------------------------------------------------------------------------------------------------------------
 # without a GPU
 # ------------------------------------------------------------------------------------------------------------------
-def test_call_sites_of_score_splits_pass_what_the_plans_here_assume():
-    """Whoever changes the planner or a call site learns here that the sizes of this file need another look."""
-    text = open(os.path.join(CSRC, "sift_register.hip")).read()
-    code = "\n".join(line.split("//")[0] for line in text.splitlines())
-    calls = re.findall(r"score_splits\(ctx, num_pts, \(long\)loop_blocks \* n_pairs, (\d+), (\d+), (true|false), &\w+\)", code)
-    want = [(str(p), str(t), "true" if r else "false") for p, t, r in (PLANAR, RIGID, EPI)]
-    assert calls == want and code.count("score_splits(") == 4, calls  # the definition and the three call sites
-    order = [code.index(k) for k in ("static int score_splits(", "static void planar_launch(", "8, 64, true, &pts_per_split",
-                                     "static void rigid_launch(", "4, 256, false, &pts_per_split",
-                                     "static void epipolar_launch(", "8, 64, true, &per_split")]
-    assert order == sorted(order)
-    for blocks in ("loop_blocks = idiv_up(num_loops, 64)", "loop_blocks = idiv_up(num_loops, 256)"):
-        assert blocks in code, blocks
-    body = code[code.index("static int score_splits("):code.index("struct PlanarOut {")]
-    for line in ("const long target = ((long)per_cu * ctx->num_cus + wgs - 1) / wgs;",
-                 "std::max(1L, std::min(std::min(target, (long)idiv_up(num_pts, tile)), 65535L))",
-                 "round_to_tile ? idiv_up(idiv_up(num_pts, splits), tile) * tile : idiv_up(num_pts, splits)",
-                 "return idiv_up(num_pts, per_split);"):
-        assert line in body, line
-    context = open(os.path.join(CSRC, "sift_context.hip")).read()
-    assert "hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device)" in context
-    for src, const in (("sift_epipolar.hip", "constexpr int kEpiTile = 64;"), ("sift_rigid.hip", "constexpr int kRigidTile = 256;"),
-                       ("sift_rigid.hip", "constexpr int kRigidThreads = 256;"), ("sift_planar.hip", "constexpr int kPlanarTile = 64;"),
-                       ("sift_planar.hip", "constexpr int kPlanarThreads = 256;"), ("sift_rgbd.hip", "constexpr int kSelectThreads = 256;"),
-                       ("sift_pose.hip", "constexpr int kPoseThreads = 256;")):
-        assert const in open(os.path.join(CSRC, src)).read(), const
-    # the walks this file is about stand as the plans here restate them
-    for src, walk in (("sift_epipolar.hip", "for (int tile = begin; tile < end; tile += kEpiTile) {"),
-                      ("sift_rigid.hip", "for (int tile = begin; tile < end; tile += kRigidTile) {"),
-                      ("sift_planar.hip", "for (int tile = begin; tile < end; tile += kPlanarTile) {"),
-                      ("sift_planar.hip", "for (int b = tx; b < (int)blockIdx.x; b += kPlanarThreads) before += block_counts[b];"),
-                      ("sift_rgbd.hip", "for (int b = tx; b < (int)blockIdx.x; b += kSelectThreads) before += block_counts[b];")):
-        assert walk in open(os.path.join(CSRC, src)).read(), walk
-
-
 def test_the_table_of_the_other_tests_plans_on_256_cus():
     """Not a claim about the code: the reason this file exists.  The largest epipolar and rigid cases of the other tests
     give one tile per split on 256 CUs, and so do the RGB-D batch and the eight-pair planar list; planar_score_kernel

@@ -1,0 +1,232 @@
+"""The properties of the registration host layer (cusift_amd/csrc/sift_register.hip) that cannot be seen from outside:
+one synchronisation per blocking call and nothing else that blocks, the order in which a call enqueues its work, no
+launches in loops, and the arguments of score_splits that tests/test_ransac_sizes.py plans with.  Everything is asserted
+on the bodies of functions, found by name, and on a call's path: its body plus the bodies of every function of the file
+that it reaches, each once.  No GPU."""
+import functools
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "cusift_amd", "csrc")
+
+BLOCKING = ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(", "hipFree(",
+            "cusift_ctx_synchronize", "cusift_memcpy")
+# (per_cu, tile, round_to_tile) of the three call sites of score_splits, in the order they stand in sift_register.hip;
+# tests/test_ransac_sizes.py plans its sizes with these
+PLANAR, RIGID, EPI = (8, 64, True), (4, 256, False), (8, 64, True)
+LAUNCH_BANNED = ("for (", "while (", "hipMemcpy", "hipMemset", "Synchronize", "grow_scratch")
+DEFINITION = r'^(?:static|extern "C") [^\n(;={]*?\b(\w+)\('
+
+
+@functools.lru_cache(maxsize=None)
+def code():
+    """sift_register.hip without its comments."""
+    text = open(os.path.join(CSRC, "sift_register.hip")).read()
+    return "\n".join(line.split("//")[0] for line in text.splitlines()) + "\n"
+
+
+def body(name):
+    """The function `name` of the file, from its signature to the closing brace at the start of a line."""
+    found = [m for m in re.finditer(DEFINITION, code(), flags=re.M) if m.group(1) == name]
+    assert len(found) == 1, (name, len(found))
+    begin = found[0].start()
+    line = code()[begin:code().index("\n", begin)]
+    return line if line.rstrip().endswith("}") else code()[begin:code().index("\n}\n", begin)]  # a one-line function
+
+
+def path(name, without=()):
+    """The body of `name` and of every function of the file that it reaches, each once; `without`: calls not followed."""
+    defined = set(re.findall(DEFINITION, code(), flags=re.M))
+    seen, todo = [], [name]
+    while todo:
+        f = todo.pop()
+        if f in seen or f in without:
+            continue
+        seen.append(f)
+        todo += [g for g in defined if re.search(r"\b%s\(" % g, body(f).split("{", 1)[1])]
+    return "\n".join(body(f) for f in seen)
+
+
+def in_order(text, *keys):
+    at = [text.index(k) for k in keys]
+    return at == sorted(at)
+
+
+def one_sync_nothing_else(name, without=()):
+    """The uniform rule of a blocking call: one hipStreamSynchronize on its path and nothing else that blocks."""
+    p = path(name, without)
+    assert p.count("hipStreamSynchronize(") == 1, (name, p.count("hipStreamSynchronize("))
+    assert not [b for b in BLOCKING if b in p], name
+    return p
+
+
+def check_four_launches(name, kernels):
+    """planar_launch / epipolar_launch: the four launches behind the marking, in their order, none in a loop, and nothing
+    that copies or waits."""
+    launch = body(name)
+    assert launch.count("hipLaunchKernelGGL(") == 4
+    assert in_order(launch, *("hipLaunchKernelGGL(" + k for k in kernels))
+    for banned in LAUNCH_BANNED:
+        assert banned not in launch, (name, banned)
+
+
+def check_planar_launch():
+    check_four_launches("planar_launch", ("planar_compact_kernel", "homography_solve_kernel", "planar_score_kernel",
+                                          "planar_select_kernel"))
+
+
+def check_matcher_of_a_fused_call(fused, run):
+    """The fused call enqueues the mutual matcher or the plain one, once, before the run; nothing in that helper blocks.
+    Replaces `reg.index("cusift_match_mutual(") < reg.index("cusift_match(ctx") < reg.index("..._run(")`."""
+    assert fused.count("match_enqueue(") == 1 and fused.count(run) == 1 and in_order(fused, "match_enqueue(", run)
+    helper = body("match_enqueue")
+    assert in_order(helper, "ctx->cross_check", "cusift_match_mutual(", "cusift_match(ctx")
+    reached = path("match_enqueue")
+    assert "Synchronize" not in reached and not [b for b in BLOCKING if b in reached]
+    assert "match_mutual_kernel<" in reached and "match_kernel<" in reached  # it does reach both matchers' launches
+
+
+def check_chain_run(launch):
+    """ransac_run, the run of both chains: mark -> four launches -> (pose enqueue) -> the one read-back -> the one wait ->
+    (pose report); the staged pose route of fewer than 8 records leaves before anything is enqueued."""
+    run = body("ransac_run")
+    # was: order of ("planar_mark_kernel", "planar_launch(" / "epipolar_launch(", "hipMemcpyAsync(", "hipStreamSynchronize(")
+    # in planar_run / epipolar_run, and of ("epipolar_launch(", "pose_enqueue(", "hipMemcpyAsync(", "hipStreamSynchronize(",
+    # "pose_report(") in epipolar_run
+    assert in_order(run, "mark_launch(", launch, "pose_enqueue(", "hipMemcpyAsync(", "hipStreamSynchronize(", "pose_report(")
+    # was: run.count("hipMemcpyAsync(") == 1 -- one read-back, nothing uploaded
+    assert run.count("hipMemcpyAsync(") == 1
+    # was: epi.count("hipStreamSynchronize(") == 1 and epi.count("pose_enqueue(") == 1
+    assert run.count("hipStreamSynchronize(") == 1 and run.count("pose_enqueue(") == 1
+    # was: run.count("hipLaunchKernelGGL(") == 1 and run.count("planar_launch(") == 1 -- the marking, then the shared four
+    assert run.count("hipLaunchKernelGGL(") == 0 and run.count("mark_launch(") == 1 and run.count(launch) == 1
+    mark = body("mark_launch")
+    assert mark.count("hipLaunchKernelGGL(") == 1 and "hipLaunchKernelGGL(planar_mark_kernel" in mark
+    for banned in LAUNCH_BANNED:
+        assert banned not in mark, banned
+    # the other way out: the answer that needs no device work, and from there the staged pose route, which has its own wait
+    assert run.count("pose_run(") == 1 and in_order(run, "if (num_pts < 8) {", "pose_run(", "\n  }\n", "grow_scratch(")
+    assert re.search(r"return pose \? pose_run\([^;]*\) : CUSIFT_OK;", run)
+
+
+# was tests/test_planar.py::test_one_synchronisation_in_the_planar_entry_points
+def test_one_synchronisation_in_the_planar_entry_points():
+    for name in ("cusift_estimate_homography", "cusift_register_planar"):
+        # was: one hipStreamSynchronize( and no blocking call in the planar section; planar_run( counted 3 times, the
+        # definition and its two callers.  The section held no pose route: neither call hands the run a stage
+        one_sync_nothing_else(name, without=("pose_run",))
+        assert body(name).count("ransac_run(") == 1 and "&st" not in body(name)
+    check_chain_run("planar_launch(")
+    check_planar_launch()
+
+
+# was tests/test_planar_batch.py::test_one_synchronisation_in_the_batch_entry_point
+def test_one_synchronisation_in_the_batch_entry_point():
+    # was: one hipStreamSynchronize( and no blocking call in the entry point's own text; now on its whole path
+    one_sync_nothing_else("cusift_register_planar_batch")
+    entry = body("cusift_register_planar_batch")
+    assert entry.count("hipStreamSynchronize(") == 1 and not [b for b in BLOCKING if b in entry]
+    assert in_order(entry, "match_batch_launch(", "sequence_mark_kernel", "planar_launch(", "hipMemcpyAsync(",
+                    "hipStreamSynchronize(")
+    assert entry.count("hipMemcpyAsync(") == 1  # one read-back; the pair list is uploaded by the matcher's launcher
+    # five launches -- the marking here, compact / solve / score / select in planar_launch -- none in a loop over the pairs
+    assert entry.count("hipLaunchKernelGGL(") == 1 and entry.count("planar_launch(") == 1
+    assert "hipLaunchKernelGGL(sequence_mark_kernel" in entry
+    check_planar_launch()
+    launches = entry[entry.index("match_batch_launch("):entry.index("hipMemcpyAsync(")]
+    assert "for (" not in launches and "while (" not in launches
+
+
+# was tests/test_epipolar.py::test_one_synchronisation_in_the_epipolar_entry_points
+def test_one_synchronisation_in_the_epipolar_entry_points():
+    for name in ("cusift_estimate_fundamental", "cusift_register_epipolar"):
+        # was: one hipStreamSynchronize( and no blocking call in the epipolar section (which did not hold pose_run);
+        # epipolar_run( counted 3 times, the definition and its two callers
+        one_sync_nothing_else(name, without=("pose_run",))
+        assert body(name).count("ransac_run(") == 1 and "&st" not in body(name)
+    check_chain_run("epipolar_launch(")
+    # was: the four launches of epipolar_launch in their order, and its banned list
+    check_four_launches("epipolar_launch", ("planar_compact_kernel", "epipolar_solve_kernel", "epipolar_score_kernel",
+                                            "epipolar_select_kernel"))
+    reg = body("cusift_register_epipolar")
+    check_matcher_of_a_fused_call(reg, "ransac_run(")
+    assert "Synchronize" not in reg and "hipMemcpy" not in reg  # nothing of its own
+
+
+# was tests/test_pose.py::test_one_synchronisation_in_the_pose_entry_points
+def test_one_synchronisation_in_the_pose_entry_points():
+    # the staged call.  was: one hipStreamSynchronize( and no blocking call between `struct PoseOut {` and
+    # `struct EpipolarOut {`; pose_run( counted twice, the definition and the caller
+    one_sync_nothing_else("cusift_estimate_pose")
+    assert body("cusift_estimate_pose").count("pose_run(") == 1
+    run = body("pose_run")
+    # was: order of ("planar_mark_kernel", "pose_enqueue(", "hipStreamSynchronize(", "pose_report(") in pose_run
+    assert in_order(run, "mark_launch(", "pose_enqueue(", "hipStreamSynchronize(", "pose_report(")
+    assert run.count("hipMemcpyAsync(") == 1 and run.count("hipStreamSynchronize(") == 1  # F goes up; the head's copy is the stage's
+    enq = body("pose_enqueue")
+    assert in_order(enq, "hipMemsetAsync(", "hipLaunchKernelGGL(pose_vote_kernel", "hipLaunchKernelGGL(pose_write_kernel",
+                    "hipMemcpyAsync(")
+    assert enq.count("hipLaunchKernelGGL(") == 2 and enq.count("hipMemcpyAsync(") == 1
+    for banned in ("for (", "while (", "Synchronize", "grow_scratch"):
+        assert banned not in enq, banned
+    # the fused call: the epipolar run with the stage behind its launches, in front of its one read-back and wait
+    fused = body("cusift_register_pose")
+    assert "Synchronize" not in fused and "hipMemcpy" not in fused and not [b for b in BLOCKING if b in fused]
+    check_matcher_of_a_fused_call(fused, "ransac_run(")
+    assert fused.count("ransac_run(") == 1 and "&st)" in fused
+    check_chain_run("epipolar_launch(")
+    # either way through the run there is one wait: the run's own, or -- fewer than 8 records -- the staged route's
+    one_sync_nothing_else("cusift_register_pose", without=("pose_run",))
+    staged = path("pose_run")
+    assert staged.count("hipStreamSynchronize(") == 1 and not [b for b in BLOCKING if b in staged]
+
+
+# the same rule on the blocking calls that no test held to it before
+def test_one_synchronisation_in_the_other_blocking_entry_points():
+    for name in ("cusift_find_homography", "cusift_estimate_rigid", "cusift_register_rgbd_batch"):
+        one_sync_nothing_else(name)
+    # cusift_register_rgbd waits in two places that exclude each other: where a frame is empty, and at the read-back
+    rgbd = path("cusift_register_rgbd")
+    assert not [b for b in BLOCKING if b in rgbd]
+    entry = body("cusift_register_rgbd")
+    assert rgbd.count("hipStreamSynchronize(") == 2 and entry.count("hipStreamSynchronize(") == 2
+    empty = entry[entry.index("if (n1 == 0 || num_pts2 == 0) {"):]
+    empty = empty[:empty.index("\n  }\n")]
+    assert empty.count("hipStreamSynchronize(") == 1 and "return CUSIFT_OK;" in empty
+    check_matcher_of_a_fused_call(entry, "rigid_launch(")
+    check_matcher_of_a_fused_call(body("cusift_register_planar"), "ransac_run(")
+
+
+# was tests/test_ransac_sizes.py::test_call_sites_of_score_splits_pass_what_the_plans_here_assume
+def test_call_sites_of_score_splits_pass_what_the_plans_here_assume():
+    """Whoever changes the planner or a call site learns here that the sizes of tests/test_ransac_sizes.py need another
+    look."""
+    calls = re.findall(r"score_splits\(ctx, num_pts, \(long\)loop_blocks \* n_pairs, (\d+), (\d+), (true|false), &\w+\)", code())
+    want = [(str(p), str(t), "true" if r else "false") for p, t, r in (PLANAR, RIGID, EPI)]
+    assert calls == want and code().count("score_splits(") == 4, calls  # the definition and the three call sites
+    assert in_order(code(), "static int score_splits(", "static void planar_launch(", "8, 64, true, &pts_per_split",
+                    "static void rigid_launch(", "4, 256, false, &pts_per_split", "static void epipolar_launch(",
+                    "8, 64, true, &per_split")
+    for blocks in ("loop_blocks = idiv_up(num_loops, 64)", "loop_blocks = idiv_up(num_loops, 256)"):
+        assert blocks in code(), blocks
+    planner = body("score_splits")  # was: from its signature to `struct PlanarOut {`
+    for line in ("const long target = ((long)per_cu * ctx->num_cus + wgs - 1) / wgs;",
+                 "std::max(1L, std::min(std::min(target, (long)idiv_up(num_pts, tile)), 65535L))",
+                 "round_to_tile ? idiv_up(idiv_up(num_pts, splits), tile) * tile : idiv_up(num_pts, splits)",
+                 "return idiv_up(num_pts, per_split);"):
+        assert line in planner, line
+    context = open(os.path.join(CSRC, "sift_context.hip")).read()
+    assert "hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device)" in context
+    for src, const in (("sift_epipolar.hip", "constexpr int kEpiTile = 64;"), ("sift_rigid.hip", "constexpr int kRigidTile = 256;"),
+                       ("sift_rigid.hip", "constexpr int kRigidThreads = 256;"), ("sift_planar.hip", "constexpr int kPlanarTile = 64;"),
+                       ("sift_planar.hip", "constexpr int kPlanarThreads = 256;"), ("sift_rgbd.hip", "constexpr int kSelectThreads = 256;"),
+                       ("sift_pose.hip", "constexpr int kPoseThreads = 256;")):
+        assert const in open(os.path.join(CSRC, src)).read(), const
+    # the walks test_ransac_sizes.py is about stand as its plans restate them
+    for src, walk in (("sift_epipolar.hip", "for (int tile = begin; tile < end; tile += kEpiTile) {"),
+                      ("sift_rigid.hip", "for (int tile = begin; tile < end; tile += kRigidTile) {"),
+                      ("sift_planar.hip", "for (int tile = begin; tile < end; tile += kPlanarTile) {"),
+                      ("sift_planar.hip", "for (int b = tx; b < (int)blockIdx.x; b += kPlanarThreads) before += block_counts[b];"),
+                      ("sift_rgbd.hip", "for (int b = tx; b < (int)blockIdx.x; b += kSelectThreads) before += block_counts[b];")):
+        assert walk in open(os.path.join(CSRC, src)).read(), walk
