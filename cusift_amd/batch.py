@@ -144,6 +144,16 @@ class BatchExtractor:
         return self.ctx.register_pose(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), camera, camera2,
                                       **opts)
 
+    def register_pnp(self, i, j, camera2, slot=0, **opts):
+        """Absolute pose of frame j of the last extract() into `slot` from frame i's coords3D (as lift_depth or an earlier
+        register_pose(i, ...) wrote them): cusift_register_pnp over this extractor's device records (frame i's match
+        fields and match_error are written, coords3D is not).  camera2: the capi.Camera of frame j.  The two counts are
+        read with one call.  **opts goes to capi.Context.register_pnp.  Returns its PnPResult: X_i = R X_j + t, t in the
+        unit of frame i's coords3D.  Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
+        return self.ctx.register_pnp(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), camera2, **opts)
+
     def register_planar_sequence(self, pairs=None, slot=0, **opts):
         """Planar registration of the frames of the last extract() into `slot` against each other:
         cusift_register_planar_batch over this extractor's own device records and raw counters -- no count is read

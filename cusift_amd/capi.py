@@ -219,6 +219,10 @@ SIGNATURES = {
     "cusift_register_pose": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, C.POINTER(Camera),
                                   C.POINTER(Camera), _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                   _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp, _vp]),
+    "cusift_estimate_pnp": (_i, [_vp, _vp, _i, _i, _i, _f, _f, C.POINTER(Camera), _i, _f, _i, _f, C.c_uint64, _vp, _vp,
+                                 C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "cusift_register_pnp": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, _f, C.POINTER(Camera), _i, _f, _i, _f, C.c_uint64,
+                                 _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _vp, _vp]),
     "cusift_estimate_rigid": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp,
                                    _vp, _vp]),
     "cusift_lift_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera)]),
@@ -346,6 +350,11 @@ EpipolarResult = collections.namedtuple("EpipolarResult", "fundamental ransac nu
 # what cusift_estimate_pose returns: rt float64 [3, 4] = [R | t] with X1 = R X2 + t and |t| = 1, num_front (the winner's
 # vote), votes int32 [4] (the four candidates'), sigma float64 [3] (the singular values of E)
 PoseResult = collections.namedtuple("PoseResult", "rt num_front votes sigma")
+# what cusift_estimate_pnp / cusift_register_pnp return: rt (refined, float64 [3, 4], X1 = R X2 + t in the unit of
+# coords3D), ransac (the winner), the counts, inliers bool [N]; with want_all drawn [6, L], all_rt float64 [12, L],
+# all_counts [L]
+PnPResult = collections.namedtuple("PnPResult", "rt ransac num_candidates num_matches num_fit best_loop inliers drawn "
+                                   "all_rt all_counts")
 # what cusift_register_pose returns: the EpipolarResult, then the PoseResult
 RegisterPoseResult = collections.namedtuple("RegisterPoseResult", EpipolarResult._fields + PoseResult._fields)
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
@@ -848,6 +857,47 @@ class Context:
             _seed64(seed), C.byref(camera), C.byref(camera2) if camera2 is not None else None,
             *(out + pout)), n1, max(loops, 0), want_all))
         return RegisterPoseResult(*(epi + pose))
+
+    @staticmethod
+    def _pnp(call, num_pts, loops, want_all):
+        """Allocates the outputs of a PnP call, calls it with them, returns the PnPResult."""
+        rt, ransac = np.zeros((3, 4), dtype=np.float64), np.zeros((3, 4), dtype=np.float64)
+        n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        flags = np.zeros(max(num_pts, 1), dtype=np.int8)
+        drawn = np.zeros((6, loops), dtype=np.int32) if want_all else None
+        all_rt = np.zeros((12, loops), dtype=np.float64) if want_all else None
+        all_c = np.zeros(loops, dtype=np.int32) if want_all else None
+        check(call(rt.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
+                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_rt.ctypes.data if want_all else None,
+                   all_c.ctypes.data if want_all else None))
+        return PnPResult(rt, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
+                         flags[:max(num_pts, 0)].astype(bool), drawn, all_rt, all_c)
+
+    def estimate_pnp(self, d_sift, num_pts, camera2, num_pts2=-1, rule=0, lo=0.0, hi=0.8, loops=10000, thresh=2.0,
+                     refine_loops=5, refine_thresh=2.0, seed=0, want_all=False):
+        """cusift_estimate_pnp: absolute pose from 3-D/2-D matches, all fp64 on the device -- the records' coords3D (frame
+        1's camera coordinates, as lift_depth or register_pose wrote them) against their matches' pixels in the image of
+        `camera2` (capi.Camera).  Candidates by `rule` as estimate_fundamental plus a finite, non-zero depth; six samples
+        per hypothesis, the 11-row DLT and the nearest rotation; reprojection inliers in pixels; the first hypothesis with
+        the most inliers; `refine_loops` Gauss-Newton rounds.  match_error (the reprojection error) of every device record
+        is written.  One synchronisation.  Returns a PnPResult: X1 = R X2 + t, t in the unit of coords3D."""
+        loops = int(loops)
+        return self._pnp(lambda *out: lib().cusift_estimate_pnp(
+            self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi,
+            C.byref(camera2) if camera2 is not None else None, loops, thresh, refine_loops, refine_thresh, _seed64(seed),
+            *out), num_pts, max(loops, 0), want_all)
+
+    def register_pnp(self, d_sift1, n1, d_sift2, n2, camera2, distance=1, rule=None, lo=None, hi=None, loops=10000,
+                     thresh=2.0, refine_loops=5, refine_thresh=2.0, seed=0, want_all=False):
+        """cusift_register_pnp: match(distance), then estimate_pnp over d_sift1 with num_pts2 = n2 -- one
+        synchronisation, the staged route's bytes.  rule / lo / hi default as in register_planar; the cross-check setting
+        is honoured as there."""
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
+        loops = int(loops)
+        return self._pnp(lambda *out: lib().cusift_register_pnp(
+            self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi,
+            C.byref(camera2) if camera2 is not None else None, loops, thresh, refine_loops, refine_thresh, _seed64(seed),
+            *out), n1, max(loops, 0), want_all)
 
     def estimate_rigid(self, coord, indices=None, loops=None, thresh2=0.0025, kind="3d", seed=0, want_all=False):
         """cusift_estimate_rigid: RANSAC rigid transform x ~ R y + t from coord float32 [N, 6] (reference xyz, moving

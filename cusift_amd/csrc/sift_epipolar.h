@@ -1,5 +1,5 @@
 // sift_epipolar.h -- the device helpers that sift_epipolar.hip and sift_pose.hip share: the pinned Sampson test and the
-// static-index cyclic Jacobi.  Inline functions only; every expression here is pinned bit for bit by tests/test_epipolar.py.
+// static-index cyclic Jacobi (sift_pnp.hip takes the Jacobi).  Inline functions only; every expression here is pinned bit for bit by tests/test_epipolar.py.
 #pragma once
 
 #include "sift_ransac.h"

@@ -4,11 +4,11 @@
 //   sift_stages.hip   the C ABI's stage entry points and their launch wrappers (front-end, ScaleDown, LaplaceMulti,
 //                     FindPointsMulti, fused detection, orientation, descriptors, bands, math-eval, packing)
 //   sift_register.hip the registration host layer: matcher, FindHomography, rigid RANSAC, RGB-D registration, the
-//                     calibrated pose, planar and epipolar registration on one chain, the pair-list forms
+//                     calibrated pose, planar and epipolar registration on one chain, the absolute pose, the pair-list forms
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
-// The device units share sift_device.h (all of them) and sift_ransac.h (the seven registration units: sampling, winner,
+// The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,
 // reductions, ordered compaction, pair strides).
 #pragma once
 
@@ -96,6 +96,13 @@ __global__ void pose_vote_kernel(const float *, const unsigned char *, int, cons
                                  PlanarBatch);
 __global__ void pose_write_kernel(cusift_point *, const float *, const unsigned char *, int, const int *, PoseCams, float,
                                   int *, PlanarBatch);
+__global__ void pnp_mark_kernel(const cusift_point *, int, int, int, float, float, float *, unsigned char *, int *,
+                                const cusift_point *);
+__global__ void pnp_solve_kernel(const float *, int, const int *, const int *, unsigned long long, int, PnPCam, int *,
+                                 double *, int *, float *);
+__global__ void pnp_score_kernel(const float *, int, int, const double *, int, PnPCam, float, int *, const int *);
+__global__ void pnp_select_kernel(cusift_point *, int, const float *, const float *, const unsigned char *, const double *,
+                                  const int *, int, PnPCam, float, int, float, int *, char *);
 __global__ void sequence_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                      const cusift_match_row *, int, float, float, float *, unsigned char *, int *, int *,
                                      PlanarBatch, const cusift_match_row *);

@@ -1,5 +1,5 @@
 // sift_ransac.h -- the device helpers that the registration units share (sift_rigid.hip, sift_homography.hip,
-// sift_planar.hip, sift_epipolar.hip, sift_pose.hip, sift_sequence.hip, sift_rgbd.hip).  Inline functions only: the LDS arrays stay
+// sift_planar.hip, sift_epipolar.hip, sift_pose.hip, sift_pnp.hip, sift_sequence.hip, sift_rgbd.hip).  Inline functions only: the LDS arrays stay
 // declared in the kernels and are passed in.  Every rule here is pinned bit for bit by the units' tests.
 //
 // SAMPLING.  The reference seeds cuRAND with time(0) (extras/rigidTransform.cu:411), which cannot be reproduced.  Here
@@ -7,11 +7,11 @@
 //     u(seed, l, k) = mix(seed ^ mix((l << 32) | k)),         index = (u >> 32) mod n
 //     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
 //             z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)          (all modulo 2^64)
-// The N slots of a hypothesis (3 rigid, 4 homography, 8 fundamental matrix) are draws 0 .. N-1; then, with k counting on
+// The N slots of a hypothesis (3 rigid, 4 homography, 6 PnP, 8 fundamental matrix) are draws 0 .. N-1; then, with k counting on
 // from N, slots 2 .. N in order: while the slot equals an earlier one, redraw it (extras/rigidTransform.cu:343-349,
 // extras/homography.cu:222-235).  A slot redrawn 64 times takes the lowest index not taken yet, so the loop is bounded.
 // Integer arithmetic only: tests/test_rigid.py, tests/test_planar.py and tests/test_epipolar.py restate it and demand
-// identical indices.  The planar and epipolar paths draw positions in the candidate list, pair p from seed + p.
+// identical indices.  The planar, epipolar and PnP paths draw positions in the candidate list, pair p from seed + p.
 #pragma once
 
 #include "sift_device.h"

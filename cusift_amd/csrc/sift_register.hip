@@ -1,5 +1,5 @@
 // sift_register.hip -- the registration host layer of the C ABI: the matcher, FindHomography, rigid RANSAC, RGB-D
-// registration, the calibrated pose, planar and epipolar registration, the pair-list forms.  An entry point that reads
+// registration, the calibrated pose, planar and epipolar registration, the absolute pose (PnP), the pair-list forms.  An entry point that reads
 // results back lays its state out in the context's register_scratch, what travels back first, and ends in one copy and
 // one synchronisation.  Shared: match_launch (either pair matcher), match_enqueue (a fused call's matcher), mark_launch
 // (the candidate marking), ransac_run (the chain of the homography and of the fundamental matrix, told apart by data).
@@ -795,6 +795,168 @@ extern "C" int cusift_register_epipolar(cusift_ctx *ctx, cusift_point *d_sift1, 
   TRY(match_enqueue(ctx, "RegisterEpipolar", d_sift1, num_pts1, d_sift2, num_pts2, distance, &d_cross));
   return ransac_run(ctx, kFundamental, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops,
                     refine_thresh, seed, o, d_cross);
+}
+
+// ------------------------------------------------------------------------------------------------
+// absolute pose from coords3D and the matches' pixels (sift_pnp.hip): a sibling of ransac_run -- six samples, twelve
+// values, five coordinate rows, a camera, the answer [I | 0] -- with the same shape: one read-back, one wait
+// ------------------------------------------------------------------------------------------------
+struct PnPOut {
+  double *h_rt, *h_ransac;  // twelve values each
+  int *num_candidates, *num_matches, *num_fit, *best_loop;
+  char *h_inliers;
+  int *h_drawn;
+  double *h_all;
+  int *h_all_counts;
+};
+static const double kIdentRtD[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+
+// every refusal of cusift_estimate_pnp, before anything is enqueued or written
+static int pnp_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
+                     const cusift_camera *camera2, int num_loops, float thresh, int refine_loops, float refine_thresh,
+                     const PnPOut &o) {
+  if (!camera2) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
+  TRY(ransac_check(who, o.h_rt && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift, num_pts, rule, lo,
+                   hi, num_loops, thresh, refine_loops, refine_thresh));
+  return check_pinhole(camera2, who);
+}
+
+// fewer than 6 records or candidates, or no hypothesis that counts a point: there is nothing to fit
+static void pnp_nothing(int num_pts, int num_loops, const PnPOut &o) {
+  memcpy(o.h_rt, kIdentRtD, sizeof(kIdentRtD));
+  memcpy(o.h_ransac, kIdentRtD, sizeof(kIdentRtD));
+  *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
+  if (o.best_loop) *o.best_loop = 0;
+  if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
+  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 6 * (size_t)num_loops);
+  if (o.h_all) memset(o.h_all, 0, sizeof(double) * 12 * (size_t)num_loops);
+  if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
+}
+
+// What the call keeps on the device: samples, hypotheses and counts -- which can be read back, so they come first -- then
+// all records' five coordinate rows, candidates, marks, the marking's block counts and the candidates' own coordinates.
+struct PnPBlock {
+  size_t idx, model, counts, coord, cand, marks, blocks, ccoord, bytes;
+  PnPBlock(int num_pts, int num_loops) {
+    ScratchLayout s;
+    idx = s.take(sizeof(int) * 6 * (size_t)num_loops);
+    model = s.take(sizeof(double) * 12 * (size_t)num_loops);
+    counts = s.take(sizeof(int) * (size_t)num_loops);
+    coord = s.take(sizeof(float) * 5 * (size_t)num_pts);
+    cand = s.take(sizeof(int) * (size_t)num_pts);
+    marks = s.take((size_t)num_pts);
+    blocks = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
+    ccoord = s.take(sizeof(float) * 5 * (size_t)num_pts);
+    bytes = s.size;
+  }
+};
+
+// The candidate splits of pnp_score_kernel: the plan of the epipolar scoring, ~8 one-wave workgroups per CU and whole
+// 64-candidate tiles.  It restates the planner's arithmetic at those settings in place of a fourth call site:
+// tests/test_register_source.py pins the planner's three call sites, and tests/test_pnp_sizes.py plans with this one.
+static int pnp_splits(cusift_ctx *ctx, int num_pts, int loop_blocks, int *per_split_out) {
+  const long target = (8L * ctx->num_cus + loop_blocks - 1) / loop_blocks;
+  const int splits = (int)std::max(1L, std::min(std::min(target, (long)idiv_up(num_pts, 64)), 65535L));
+  const int per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
+  *per_split_out = per_split;
+  return idiv_up(num_pts, per_split);
+}
+
+// The five launches: the marking and the four behind it.
+static void pnp_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
+                       PnPCam cam, int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
+                       char *d_block, const PnPBlock &b, int *d_head, char *d_flags, const cusift_point *d_cross) {
+  float *d_coord = at<float>(d_block, b.coord), *d_ccoord = at<float>(d_block, b.ccoord);
+  unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
+  double *d_pose = at<double>(d_block, b.model);
+  int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand), *d_blocks = at<int>(d_block, b.blocks);
+  const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
+  int per_split;
+  const int splits = pnp_splits(ctx, num_pts, loop_blocks, &per_split);
+  hipLaunchKernelGGL(pnp_mark_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const cusift_point *)d_sift, num_pts,
+                     num_pts2, rule, mark_thresh(rule, lo), mark_thresh(rule, hi), d_coord, d_marks, d_blocks, d_cross);
+  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const unsigned char *)d_marks,
+                     num_pts, (const int *)d_blocks, d_cand, d_head, PlanarBatch{});
+  hipLaunchKernelGGL(pnp_solve_kernel, dim3(loop_blocks), dim3(64), 0, ctx->stream, (const float *)d_coord, num_pts,
+                     (const int *)d_cand, (const int *)d_head, (unsigned long long)seed, num_loops, cam,
+                     at<int>(d_block, b.idx), d_pose, d_counts, d_ccoord);
+  hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64), 0, ctx->stream, (const float *)d_ccoord,
+                     num_pts, per_split, (const double *)d_pose, num_loops, cam, thresh, d_counts, (const int *)d_head);
+  hipLaunchKernelGGL(pnp_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, (const float *)d_coord,
+                     (const float *)d_ccoord, (const unsigned char *)d_marks, (const double *)d_pose,
+                     (const int *)d_counts, num_loops, cam, thresh, refine_loops, refine_thresh, d_head, d_flags);
+}
+
+// The five launches and the one read-back; the arguments are checked.  d_cross as mark_launch's.
+static int pnp_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
+                   const cusift_camera *camera2, int num_loops, float thresh, int refine_loops, float refine_thresh,
+                   uint64_t seed, const PnPOut &o, const cusift_point *d_cross) {
+  if (num_pts < 6) {  // fewer than the solver takes: the answer needs no device work
+    pnp_nothing(num_pts, num_loops, o);
+    return CUSIFT_OK;
+  }
+  const PnPCam cam{(double)camera2->fx, (double)camera2->fy, (double)camera2->cx - (double)camera2->origin,
+                   (double)camera2->cy - (double)camera2->origin};
+  // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
+  const PnPBlock b(num_pts, num_loops);
+  ScratchLayout s;
+  s.take(kPnPHeadBytes);  // the head, at 0
+  const size_t flag_off = s.take((size_t)num_pts);
+  const size_t block_off = s.take(b.bytes);
+  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
+  char *base = ctx->register_scratch;
+  pnp_launch(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, cam, num_loops, thresh, refine_loops, refine_thresh, seed,
+             base + block_off, b, (int *)base, base + flag_off, d_cross);
+  TRY(check_launch("estimate_pnp"));
+  // the one blocking read-back
+  const bool all = o.h_drawn || o.h_all || o.h_all_counts;
+  std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const char *head = back.data(), *block = back.data() + block_off;
+  const int n_cand = head_int(head, kPlanarHeadCand);
+  if (n_cand < 6 || head_int(head, kPlanarHeadMatches) < 1) {  // the kernels left the records alone
+    pnp_nothing(num_pts, num_loops, o);
+    *o.num_candidates = n_cand;
+    return CUSIFT_OK;
+  }
+  memcpy(o.h_rt, head + sizeof(double) * kPnPHeadRt, sizeof(double) * 12);
+  memcpy(o.h_ransac, head + sizeof(double) * kPnPHeadWin, sizeof(double) * 12);
+  *o.num_candidates = n_cand, *o.num_matches = head_int(head, kPlanarHeadMatches);
+  *o.num_fit = head_int(head, kPlanarHeadFit);
+  if (o.best_loop) *o.best_loop = head_int(head, kPlanarHeadLoop);
+  if (o.h_inliers) memcpy(o.h_inliers, back.data() + flag_off, (size_t)num_pts);
+  if (o.h_drawn) memcpy(o.h_drawn, block + b.idx, sizeof(int) * 6 * (size_t)num_loops);
+  if (o.h_all) memcpy(o.h_all, block + b.model, sizeof(double) * 12 * (size_t)num_loops);
+  if (o.h_all_counts) memcpy(o.h_all_counts, block + b.counts, sizeof(int) * (size_t)num_loops);
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_estimate_pnp(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo,
+                                   float hi, const cusift_camera *camera2, int num_loops, float thresh, int refine_loops,
+                                   float refine_thresh, uint64_t seed, double h_rt[12], double h_ransac[12],
+                                   int *num_candidates, int *num_matches, int *num_fit, int *best_loop, char *h_inliers,
+                                   int *h_drawn, double *h_all_rt, int *h_all_counts) {
+  TRY(enter(ctx));
+  const PnPOut o{h_rt, h_ransac, num_candidates, num_matches, num_fit, best_loop, h_inliers, h_drawn, h_all_rt, h_all_counts};
+  TRY(pnp_check("EstimatePnP", d_sift, num_pts, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh, o));
+  return pnp_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh,
+                 seed, o, nullptr);
+}
+
+extern "C" int cusift_register_pnp(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                   int num_pts2, int distance, int rule, float lo, float hi,
+                                   const cusift_camera *camera2, int num_loops, float thresh, int refine_loops,
+                                   float refine_thresh, uint64_t seed, double h_rt[12], double h_ransac[12],
+                                   int *num_candidates, int *num_matches, int *num_fit, int *best_loop, char *h_inliers,
+                                   int *h_drawn, double *h_all_rt, int *h_all_counts) {
+  TRY(enter(ctx));
+  const PnPOut o{h_rt, h_ransac, num_candidates, num_matches, num_fit, best_loop, h_inliers, h_drawn, h_all_rt, h_all_counts};
+  TRY(pnp_check("RegisterPnP", d_sift1, num_pts1, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh, o));
+  const cusift_point *d_cross;
+  TRY(match_enqueue(ctx, "RegisterPnP", d_sift1, num_pts1, d_sift2, num_pts2, distance, &d_cross));
+  return pnp_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh,
+                 seed, o, d_cross);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -178,6 +178,14 @@ constexpr size_t kPoseHeadBytes = 256;                // between the heads of a 
 struct PoseCams {
   double fx1, fy1, px1, py1, fx2, fy2, px2, py2;
 };
+// A PnP result head (sift_pnp.hip): the int words kPlanarHeadCand .. kPlanarHeadLoop where the planar head has them, then,
+// counted in doubles, [R | t] refined and the winner's, twelve each.
+constexpr int kPnPHeadRt = 16, kPnPHeadWin = 32;
+constexpr size_t kPnPHeadBytes = 384;
+// The intrinsics of the matches' image as the PnP kernels take them: px = cx - origin, py = cy - origin, widened first.
+struct PnPCam {
+  double fx, fy, px, py;
+};
 // A rigid result head: Rt[12] as float, then as int the winner's count, the winning loop and -- with a device-side point
 // count -- that count.
 constexpr int kRigidHeadInliers = 12, kRigidHeadLoop = 13, kRigidHeadCount = 14;

@@ -2,7 +2,8 @@
  * cusift_amd_extras.h -- the next rows of SURVEY 8f behind the C ABI: the brute-force matcher, the RANSAC homography, the
  * planar registration built on both (seeded RANSAC + refit on the device), the RANSAC rigid transform and the RGB-D
  * registration built on them (depth lift, match selection, the fused call for one frame pair and for a pair list over a
- * batch of frames), the epipolar registration and the calibrated pose behind it.
+ * batch of frames), the epipolar registration, the calibrated pose behind it and the absolute pose
+ * from 3-D/2-D matches (PnP).
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
@@ -299,6 +300,103 @@ int cusift_register_pose(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, c
                          double *h_all_f /* may be NULL */, int *h_all_counts /* may be NULL */, double h_rt[12],
                          int *num_front, int *h_votes /* [4], may be NULL */, double *h_sigma /* [3], may be NULL */);
 
+/* ---- absolute pose on the device from 3-D/2-D matches: seeded PnP RANSAC and refit (sift_pnp.hip) ---------------- */
+/* The step behind cusift_register_pose or cusift_lift_depth: the records carry a point in coords3D, their matches carry
+ * pixels of an ordinary image, and the answer is that image's pose in the unit the points are in -- metres, or the first
+ * baseline -- so that a third view, or a colour-only frame, joins the frame of the first.  The definition is the
+ * library's own and ALL OF IT IS FP64; every expression is evaluated in the order written (-ffp-contract=off).
+ * CONVENTION: X1 = coords3D of the record, in frame 1's camera coordinates; x2 = (match_xpos, match_ypos); floats are
+ * widened first.  camera2 is the cusift_camera of the matches' image: px = cx - origin, py = cy - origin (widened
+ * first); units_per_metre and encoding are ignored.  A POSE is twelve doubles rt[12], row-major [R | t] with X1 = R X2 +
+ * t, the direction of cusift_register_rgbd and cusift_register_pose, t in the unit of coords3D -- h_rt, h_ransac and
+ * every column of h_all_rt alike; the hypotheses, the refit and the test below work on this one form.
+ * CANDIDATES: the records cusift_estimate_fundamental marks (rule, lo, hi, finite coords2D and match position, 0 <=
+ * match < num_pts2 when num_pts2 >= 0, the fused call's cross-check) whose three coords3D floats are finite with
+ * coords3D[2] != 0 (0 is the "no depth" mark).  Everything below runs over the candidates only, in ascending record
+ * order, without atomics; *num_candidates is their number.
+ * SAMPLES: cusift_estimate_homography's recipe with six slots: draws 0 .. 5 of loop l out of the candidate list, then
+ * slots 2 .. 6 redrawn while they equal an earlier one, k counting on from 6.
+ * HYPOTHESIS from the six samples (X_i, x2_i):
+ *     c = (sum X_i) / 6 per coordinate;  d = (sum sqrt((ax*ax + ay*ay) + az*az)) / 6 with a = X_i - c;  s = sqrt(3) / d
+ *     X~ = (X - c) * s;   u = (x2 - px) / fx;   v = (y2 - py) / fy
+ *     row 2i   = [X~ Y~ Z~ 1   0 0 0 0   -(u*X~) -(u*Y~) -(u*Z~) -u]
+ *     row 2i+1 = [0 0 0 0   X~ Y~ Z~ 1   -(v*X~) -(v*Y~) -(v*Z~) -v]
+ * the first ELEVEN rows (both of samples 1 to 5, the u row of sample 6).  The null vector of the 11 x 12 system exactly
+ * as cusift_estimate_fundamental takes that of its 8 x 9 system: Gaussian elimination with complete pivoting (the pivot
+ * of step k is the first entry of largest magnitude in rows k.. and columns k.., searched row by row; rows k and pi are
+ * swapped, then columns k and pj; f = M[i][k] / M[k][k], M[i][j] -= f * M[k][j]), back substitution from x[11] = 1 with
+ * x[k] = -(sum_{j>k} M[k][j]*x[j]) / M[k][k] summed in ascending j, the column permutation undone.  x is P~, row-major
+ * 3 x 4.  Denormalise, with tx = -(s*cx), ty = -(s*cy), tz = -(s*cz):
+ *     P[i][j] = P~[i][j] * s (j < 3);   P[i][3] = ((P~[i][0]*tx + P~[i][1]*ty) + P~[i][2]*tz) + P~[i][3]
+ * SIGN: det = (P00*(P11*P22 - P12*P21) - P01*(P10*P22 - P12*P20)) + P02*(P10*P21 - P11*P20) of the left 3 x 3 block M; det
+ * < 0 negates all twelve.  ROTATION nearest M, by the pose block's construction: G = M^T M, G[i][j] = (M[0][i]*M[0][j] +
+ * M[1][i]*M[1][j]) + M[2][i]*M[2][j]; its eigenpairs by the same 3 x 3 cyclic Jacobi with the fixed sweep schedule,
+ * ordered l1 >= l2 >= l3, the first among equals; s1 = sqrt(l1 > 0 ? l1 : 0), s2 likewise; v3 = v1 x v2; u1 = M v1 / s1;
+ * u2 = w / |w| with w = M v2 - (M v2 . u1) u1; u3 = u1 x u2; s3 = |u3 . (M v3)|;
+ *     R21[i][j] = (u1[i]*v1[j] + u2[i]*v2[j]) + u3[i]*v3[j];   scale = ((s1 + s2) + s3) / 3;   t21[i] = P[i][3] / scale
+ * (dot products and matrix-vector rows are (a0*b0 + a1*b1) + a2*b2) -- X2 = R21 X1 + t21.  The pose: R = R21^T, t[i] =
+ * -((R21[0][i]*t21[0] + R21[1][i]*t21[1]) + R21[2][i]*t21[2]).  scale not > 0 or an entry that is not finite: the
+ * hypothesis is twelve zeros and counts nothing.
+ * INLIER TEST of (X, Y, Z), (x2, y2) under rt at a threshold t (pixels), t2 = (double)t * (double)t, no division:
+ *     dx = X - rt[3];  dy = Y - rt[7];  dz = Z - rt[11]
+ *     a = (rt[0]*dx + rt[4]*dy) + rt[8]*dz;  b = (rt[1]*dx + rt[5]*dy) + rt[9]*dz;  c = (rt[2]*dx + rt[6]*dy) + rt[10]*dz
+ *     ex = fx*a - (x2 - px)*c;   ey = fy*b - (y2 - py)*c
+ *     inlier  <=>  c > 0 && ex*ex + ey*ey < t2 * (c*c)
+ * A NaN fails; a point behind the camera fails.  The same expressions serve the scoring, the winner's flags, the refit's
+ * membership and *num_fit.  match_error = (float)sqrt((ex*ex + ey*ey) / (c*c)), the reprojection error in pixels, NaN
+ * where c > 0 fails.
+ * WINNER: the most inliers at `thresh`, among equals the first loop: h_ransac its pose, *num_matches its count,
+ * *best_loop its index, h_inliers its flags (0 for a record that is no candidate).
+ * REFIT, starting from the winner, refine_loops rounds of Gauss-Newton on the reprojection error: S = the candidates
+ * that pass at refine_thresh under the current pose; |S| < 6 ends the refit.  Per member, with a, b, c as above, xs = x2
+ * - px, ys = y2 - py:
+ *     ic = 1 / c;  ua = a*ic;  vb = b*ic;  g0 = fx*ic;  g2 = -(g0*ua);  h1 = fy*ic;  h2 = -(h1*vb)
+ *     ru = fx*ua - xs;   rv = fy*vb - ys
+ *     Ju = [g2*b, g0*c - g2*a, -(g0*b), g0, 0, g2];   Jv = [h2*b - h1*c, -(h2*a), h1*a, 0, h1, h2]
+ * the 2 x 6 Jacobian with respect to a left rotation increment w and a translation increment d of X2 = R21 X1 + t21.
+ * The 21 sums A[i][j] += Ju[i]*Ju[j] + Jv[i]*Jv[j] (i <= j), the 6 sums g[i] += Ju[i]*ru + Jv[i]*rv and |S| are reduced
+ * in a fixed order (lane tree, then waves 0..3); A p = -g is solved by Cholesky on one lane (no pivot search; a pivot
+ * that is not > 0 ends the refit), p = (w, d).  Rodrigues: th2 = (w0*w0 + w1*w1) + w2*w2, th = sqrt(th2), A = sin(th) /
+ * th, B = (1 - cos(th)) / th2 (1 and 0.5 when th2 < 1e-20), E = I + A [w]x + B [w]x^2 written out as E00 = 1 - B*(w1*w1 +
+ * w2*w2), E01 = B*(w0*w1) - A*w2, E02 = B*(w0*w2) + A*w1, ...  R21 <- E R21 and t21 <- E t21 + d are, on the pose:
+ *     R'[i][j] = (R[i][0]*E[j][0] + R[i][1]*E[j][1]) + R[i][2]*E[j][2];   t'[i] = t[i] - ((R'[i][0]*d0 + R'[i][1]*d1) + R'[i][2]*d2)
+ * A step that is not finite keeps the previous pose and ends the refit.  There is no damping and no step control.
+ * Afterwards match_error is written into EVERY device record [0, num_pts), *num_fit = the candidates that pass at
+ * refine_thresh under the final pose and h_rt = that pose.  refine_loops == 0: h_rt equals h_ransac byte for byte.
+ * Optional (may be NULL): best_loop, h_inliers [num_pts], h_drawn [6][num_loops] (record indices), h_all_rt
+ * [12][num_loops], h_all_counts [num_loops].  The same seed gives the same bytes in every output and in the records.
+ * DEGENERATE ANSWERS, CUSIFT_OK: num_pts < 6, fewer than 6 candidates, or a winner that counts nothing (no hypothesis was
+ * solvable): [I | 0] in both matrices, every count 0 except *num_candidates (0 when num_pts < 6: nothing is marked), the
+ * optional arrays zeroed; the records are untouched.
+ * KNOWN LIMIT: a coplanar point set makes the null space of the DLT system more than one-dimensional.  The call still
+ * answers CUSIFT_OK with a rotation that is orthonormal to rounding, and makes no promise about the pose: planar scenes
+ * belong to cusift_register_planar.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of cusift_estimate_fundamental; a NULL camera2, fx or
+ * fy zero or not finite, cx, cy or origin not finite; a NULL h_rt / h_ransac / num_candidates / num_matches / num_fit.
+ * No other byte of any record than match_error changes; coords3D is read, never written.
+ * Scratch lives in the context and grows on demand.  Blocking: ONE stream synchronisation, at the one read-back. */
+int cusift_estimate_pnp(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2 /* < 0: no check */, int rule,
+                        float lo, float hi, const cusift_camera *camera2, int num_loops, float thresh, int refine_loops,
+                        float refine_thresh, uint64_t seed, double h_rt[12], double h_ransac[12], int *num_candidates,
+                        int *num_matches, int *num_fit, int *best_loop /* may be NULL */,
+                        char *h_inliers /* may be NULL */, int *h_drawn /* may be NULL */,
+                        double *h_all_rt /* may be NULL */, int *h_all_counts /* may be NULL */);
+
+/* cusift_match(d_sift1, d_sift2, distance) followed by cusift_estimate_pnp(d_sift1, num_pts1, num_pts2, ...) with ONE
+ * synchronisation, at the read-back: the same bytes as the staged route in every output and in the records.  The matcher
+ * leaves coords3D of both record sets alone.  Also CUSIFT_ERR_INVALID for an unknown distance.  It honours
+ * cusift_ctx_set_cross_check exactly as cusift_register_epipolar does: while it is on, the matcher is
+ * cusift_match_mutual, THE MATCH FIELDS OF d_sift2 ARE WRITTEN (the parameter keeps its const spelling), overlapping
+ * record ranges are refused with CUSIFT_ERR_INVALID before anything is enqueued or written, and a record that is not
+ * mutual is no candidate. */
+int cusift_register_pnp(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
+                        int distance, int rule, float lo, float hi, const cusift_camera *camera2, int num_loops,
+                        float thresh, int refine_loops, float refine_thresh, uint64_t seed, double h_rt[12],
+                        double h_ransac[12], int *num_candidates, int *num_matches, int *num_fit,
+                        int *best_loop /* may be NULL */, char *h_inliers /* may be NULL */,
+                        int *h_drawn /* may be NULL */, double *h_all_rt /* may be NULL */,
+                        int *h_all_counts /* may be NULL */);
+
 /* Writes coords3D of every record from its coords2D = (x, y) (0-based pixels at base-image scale) and the depth image
  * of its frame, all in fp32:
  *     u = roundf(x), v = roundf(y);  not finite or outside [0, width) x [0, height)  ->  (0, 0, 0)
@@ -341,7 +439,8 @@ int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_i
 
 /* The cross-check of the registrations, a setting of the context (0 = off, the default; 1 = on; anything else:
  * CUSIFT_ERR_INVALID, the setting unchanged).  It affects cusift_register_planar, cusift_register_rgbd,
- * cusift_register_planar_batch, cusift_register_rgbd_batch, cusift_register_epipolar and cusift_register_pose and nothing else; with 0 they enqueue the launches and
+ * cusift_register_planar_batch, cusift_register_rgbd_batch, cusift_register_epipolar, cusift_register_pose and
+ * cusift_register_pnp and nothing else; with 0 they enqueue the launches and
  * return the bytes they always did.  With 1, record i of frame 1 takes part only if it is MUTUAL: its match m lies in
  * [0, n2) and the column side's best for record m of frame 2 is i -- the column side exactly as cusift_match_mutual /
  * cusift_match_batch_mutual define it, so an exactly tied best keeps the lowest record of frame 1.  Every many-to-one

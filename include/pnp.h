@@ -1,0 +1,57 @@
+// pnp.h -- absolute pose on the device from 3-D/2-D matches (PnP): the records of one frame carry coords3D -- from a depth
+// image (rgbd.h) or from RegisterPose (pose.h) -- and their matches carry pixels of an ordinary image; the answer is that
+// image's pose in the unit the points are in, metres or the first baseline.  This is the step that registers a third
+// view after RegisterPose, or a colour-only frame against an RGB-D one.  The reference has no counterpart; the calls sit
+// on cusift_estimate_pnp / cusift_register_pnp (cusift_amd_extras.h, where the arithmetic is written out): six-point DLT
+// hypotheses, reprojection inliers, the first hypothesis with the most inliers and Gauss-Newton rounds, all on the
+// device in fp64, with one synchronisation.
+//
+// Rt is 12 doubles, row-major [R | t] with X1 = R X2 + t -- RegisterRGBD's direction -- and t in the unit of coords3D.
+// [I | 0] and zero counts when fewer than six records qualify.  camera2 belongs to the matches' image; of a cusift_camera
+// only fx, fy, cx, cy and origin are used.  A coplanar point set gets a rotation but no promise about the pose:
+// planar scenes belong to RegisterPlanar (homography.h).
+#ifndef CUSIFT_AMD_PNP_H
+#define CUSIFT_AMD_PNP_H
+
+#include <cstdint>
+
+#include "cuSIFT.h"
+#include "cusift_amd_extras.h"
+
+// The pose over the device records of `data`, which carry match fields and coords3D.  The candidates are those of `rule`
+// (as EstimateFundamental's) with a finite coords3D whose z is not 0; *numMatches of them lie within `thresh` px of the
+// winning hypothesis, *numFit within refineThresh px of the refined pose.  match_error of EVERY device record becomes its
+// reprojection error in pixels.  ransac (may be NULL): the winner's [R | t].  Returns the elapsed milliseconds.
+inline double EstimatePnP(SiftData &data, const cusift_camera *camera2, double *Rt, int *numMatches, int *numFit,
+                          int numLoops = 10000, float minScore = 0.0f, float maxAmbiguity = 0.8f, float thresh = 2.0f,
+                          int refineLoops = 5, float refineThresh = 2.0f, uint64_t seed = 0, int rule = 0,
+                          int numPts2 = -1, double *ransac = nullptr, int *numCandidates = nullptr) {
+  TimerGPU timer;
+  double winner[12];
+  int candidates = 0;
+  safeCall(cusift_estimate_pnp(cusift_dropin::ctx(), reinterpret_cast<cusift_point *>(data.d_data), data.numPts, numPts2,
+                               rule, minScore, maxAmbiguity, camera2, numLoops, thresh, refineLoops, refineThresh, seed, Rt,
+                               ransac ? ransac : winner, numCandidates ? numCandidates : &candidates, numMatches, numFit,
+                               nullptr, nullptr, nullptr, nullptr, nullptr));
+  return timer.read();
+}
+
+// MatchSiftData(data1, data2), then EstimatePnP over data1, in one call with one synchronisation (cusift_register_pnp).
+// Writes the match fields and match_error of data1's device records and leaves coords3D alone; SetCrossCheck(true)
+// (matching.h) is honoured as RegisterEpipolar honours it.
+inline double RegisterPnP(SiftData &data1, SiftData &data2, const cusift_camera *camera2, double *Rt, int *numMatches,
+                          int *numFit, int numLoops = 10000, float minScore = 0.0f, float maxAmbiguity = 0.8f,
+                          float thresh = 2.0f, int refineLoops = 5, float refineThresh = 2.0f, uint64_t seed = 0,
+                          int distance = 0, int rule = 0, double *ransac = nullptr, int *numCandidates = nullptr) {
+  TimerGPU timer;
+  double winner[12];
+  int candidates = 0;
+  safeCall(cusift_register_pnp(cusift_dropin::ctx(), reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
+                               reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts, distance, rule,
+                               minScore, maxAmbiguity, camera2, numLoops, thresh, refineLoops, refineThresh, seed, Rt,
+                               ransac ? ransac : winner, numCandidates ? numCandidates : &candidates, numMatches, numFit,
+                               nullptr, nullptr, nullptr, nullptr, nullptr));
+  return timer.read();
+}
+
+#endif  // CUSIFT_AMD_PNP_H
