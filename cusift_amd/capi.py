@@ -756,15 +756,16 @@ class Context:
                                            all_c.ctypes.data if want_all else None))
         return (hom, n.value, all_h, all_c) if want_all else (hom, n.value)
 
-    # (result type, dtype, samples and values per hypothesis) of the two models that _ransac serves
-    _H = (PlanarResult, np.float32, 4, 8)
-    _F = (EpipolarResult, np.float64, 8, 9)
+    # (result type, dtype, shape of a reported model, samples and values per hypothesis) of the models that _ransac serves
+    _H = (PlanarResult, np.float32, 9, 4, 8)
+    _F = (EpipolarResult, np.float64, 9, 8, 9)
+    _P = (PnPResult, np.float64, (3, 4), 6, 12)
 
     @staticmethod
     def _ransac(kind, call, num_pts, loops, want_all):
-        """Allocates the outputs of a homography or fundamental-matrix call, calls it with them, returns the result."""
-        result, dtype, samples, values = kind
-        model, ransac = np.zeros(9, dtype=dtype), np.zeros(9, dtype=dtype)
+        """Allocates the outputs of a homography, fundamental-matrix or PnP call, calls it with them, returns the result."""
+        result, dtype, shape, samples, values = kind
+        model, ransac = np.zeros(shape, dtype=dtype), np.zeros(shape, dtype=dtype)
         n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         flags = np.zeros(max(num_pts, 1), dtype=np.int8)
         drawn = np.zeros((samples, loops), dtype=np.int32) if want_all else None
@@ -858,21 +859,6 @@ class Context:
             *(out + pout)), n1, max(loops, 0), want_all))
         return RegisterPoseResult(*(epi + pose))
 
-    @staticmethod
-    def _pnp(call, num_pts, loops, want_all):
-        """Allocates the outputs of a PnP call, calls it with them, returns the PnPResult."""
-        rt, ransac = np.zeros((3, 4), dtype=np.float64), np.zeros((3, 4), dtype=np.float64)
-        n_cand, n_match, n_fit, best = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-        flags = np.zeros(max(num_pts, 1), dtype=np.int8)
-        drawn = np.zeros((6, loops), dtype=np.int32) if want_all else None
-        all_rt = np.zeros((12, loops), dtype=np.float64) if want_all else None
-        all_c = np.zeros(loops, dtype=np.int32) if want_all else None
-        check(call(rt.ctypes.data, ransac.ctypes.data, C.byref(n_cand), C.byref(n_match), C.byref(n_fit), C.byref(best),
-                   flags.ctypes.data, drawn.ctypes.data if want_all else None, all_rt.ctypes.data if want_all else None,
-                   all_c.ctypes.data if want_all else None))
-        return PnPResult(rt, ransac, n_cand.value, n_match.value, n_fit.value, best.value,
-                         flags[:max(num_pts, 0)].astype(bool), drawn, all_rt, all_c)
-
     def estimate_pnp(self, d_sift, num_pts, camera2, num_pts2=-1, rule=0, lo=0.0, hi=0.8, loops=10000, thresh=2.0,
                      refine_loops=5, refine_thresh=2.0, seed=0, want_all=False):
         """cusift_estimate_pnp: absolute pose from 3-D/2-D matches, all fp64 on the device -- the records' coords3D (frame
@@ -882,7 +868,7 @@ class Context:
         the most inliers; `refine_loops` Gauss-Newton rounds.  match_error (the reprojection error) of every device record
         is written.  One synchronisation.  Returns a PnPResult: X1 = R X2 + t, t in the unit of coords3D."""
         loops = int(loops)
-        return self._pnp(lambda *out: lib().cusift_estimate_pnp(
+        return self._ransac(self._P, lambda *out: lib().cusift_estimate_pnp(
             self.handle, d_sift, num_pts, num_pts2, PLANAR_RULES.get(rule, rule), lo, hi,
             C.byref(camera2) if camera2 is not None else None, loops, thresh, refine_loops, refine_thresh, _seed64(seed),
             *out), num_pts, max(loops, 0), want_all)
@@ -894,7 +880,7 @@ class Context:
         is honoured as there."""
         rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
         loops = int(loops)
-        return self._pnp(lambda *out: lib().cusift_register_pnp(
+        return self._ransac(self._P, lambda *out: lib().cusift_register_pnp(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi,
             C.byref(camera2) if camera2 is not None else None, loops, thresh, refine_loops, refine_thresh, _seed64(seed),
             *out), n1, max(loops, 0), want_all)

@@ -2,7 +2,8 @@
 // registration, the calibrated pose, planar and epipolar registration, the absolute pose (PnP), the pair-list forms.  An entry point that reads
 // results back lays its state out in the context's register_scratch, what travels back first, and ends in one copy and
 // one synchronisation.  Shared: match_launch (either pair matcher), match_enqueue (a fused call's matcher), mark_launch
-// (the candidate marking), ransac_run (the chain of the homography and of the fundamental matrix, told apart by data).
+// (the candidate marking), ransac_run (the chain of the homography, of the fundamental matrix and of the absolute pose,
+// told apart by data).
 #include "sift_host.h"
 
 // the refusals that several entry points share; `who` is the entry point's name in the message
@@ -39,6 +40,7 @@ static int head_int(const char *head, int word) {
 }
 static const float kIdentH[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};             // extras/homography.cu:184-187
 static const float kIdentRt[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+static const double kIdentRtD[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
 
 // ------------------------------------------------------------------------------------------------
 // matcher
@@ -201,35 +203,49 @@ static int score_splits(cusift_ctx *ctx, int num_pts, long wgs, int per_cu, int 
 // The marking's thresholds: rule 1 compares squared scores (include/matching.h:43-44).
 static float mark_thresh(int rule, float t) { return rule == 1 ? t * t : t; }
 
-// The candidate marking over num_pts >= 1 records: coordinates, marks and block counts.  d_cross != NULL: the
-// cross-check against the num_pts2 records of image 2, which carry cusift_match_mutual's fields.
-static void mark_launch(cusift_ctx *ctx, const cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo,
-                        float hi, float *d_coord, unsigned char *d_marks, int *d_blocks, const cusift_point *d_cross) {
-  hipLaunchKernelGGL(planar_mark_kernel, dim3(idiv_up(num_pts, 256)), dim3(256), 0, ctx->stream, d_sift, num_pts,
-                     num_pts2, rule, mark_thresh(rule, lo), mark_thresh(rule, hi), d_coord, d_marks, d_blocks,
-                     PlanarBatch{}, d_cross);
-}
-
 // ------------------------------------------------------------------------------------------------
-// the marked-RANSAC chain (sift_planar.hip, sift_epipolar.hip): candidates, seeded RANSAC, refit -- its parts up to the
-// planar launches; its run stands behind the pose stage, which it can take
+// the marked-RANSAC chain (sift_planar.hip, sift_epipolar.hip, sift_pnp.hip): candidates, seeded RANSAC, refit -- its
+// parts up to the planar launches; its run stands behind the pose stage, which it can take
 // ------------------------------------------------------------------------------------------------
-// What tells the homography from the fundamental matrix, as data: every output is copied by its size.
+// What tells the homography, the fundamental matrix and the absolute pose apart, as data: every output is copied by its
+// size.
+enum RansacLaunch { kPlanarLaunch, kEpipolarLaunch, kPnPLaunch };  // planar_launch, epipolar_launch, pnp_launch
 struct RansacModel {
-  size_t elem, head_bytes;      // bytes of a model value -- float (H) or double (F) -- and of the result head
+  size_t elem, head_bytes;      // bytes of a model value -- float (H) or double (F, Rt) -- and of the result head
   int samples, values;          // of a hypothesis: the records drawn, the values kept
+  int reported, min_pts;        // the values of a reported model; the fewest records or candidates that can be fitted
+  int coord_rows;               // coordinate rows per record: x1 y1 x2 y2, or X Y Z x2 y2
   int head_model, head_ransac;  // where the head holds the refined and the winning model, in values (sift_types.h)
-  const void *nothing;          // the nine values reported when there is nothing to fit: the identity, zeros
-  bool epipolar;                // the epipolar kernels, whose block ends in the candidates' own coordinates (ccoord)
+  const void *nothing;          // the model reported when there is nothing to fit: the identity, zeros, [I | 0]
+  bool ccoord;                  // the block ends in the candidates' own coordinates
+  bool needs_support;           // a winner that counts no point is nothing to fit either
+  RansacLaunch launch;          // the four launches behind the marking; kPnPLaunch: its own marking as well
   const char *label;            // check_launch's
 };
 static const double kZeroF[9] = {};
-static const RansacModel kHomography{sizeof(float), kPlanarHeadBytes, 4, 8, kPlanarHeadH, kPlanarHeadR, kIdentH, false,
-                                     "estimate_homography"};
-static const RansacModel kFundamental{sizeof(double), kEpiHeadBytes, 8, 9, kEpiHeadF, kEpiHeadR, kZeroF, true,
-                                      "estimate_fundamental"};
+static const RansacModel kHomography{sizeof(float), kPlanarHeadBytes, 4, 8, 9, 8, 4, kPlanarHeadH, kPlanarHeadR, kIdentH,
+                                     false, false, kPlanarLaunch, "estimate_homography"};
+static const RansacModel kFundamental{sizeof(double), kEpiHeadBytes, 8, 9, 9, 8, 4, kEpiHeadF, kEpiHeadR, kZeroF,
+                                      true, false, kEpipolarLaunch, "estimate_fundamental"};
+static const RansacModel kPnP{sizeof(double), kPnPHeadBytes, 6, 12, 12, 6, 5, kPnPHeadRt, kPnPHeadWin, kIdentRtD,
+                              true, true, kPnPLaunch, "estimate_pnp"};
+
+// The candidate marking over num_pts >= 1 records: coordinates, marks and block counts.  d_cross != NULL: the
+// cross-check against the num_pts2 records of image 2, which carry cusift_match_mutual's fields.
+static void mark_launch(cusift_ctx *ctx, const RansacModel &m, const cusift_point *d_sift, int num_pts, int num_pts2,
+                        int rule, float lo, float hi, float *d_coord, unsigned char *d_marks, int *d_blocks,
+                        const cusift_point *d_cross) {
+  const dim3 grid(idiv_up(num_pts, 256));
+  if (m.launch == kPnPLaunch)  // also wants a finite, non-zero depth, and writes the record's five rows
+    hipLaunchKernelGGL(pnp_mark_kernel, grid, dim3(256), 0, ctx->stream, d_sift, num_pts, num_pts2, rule,
+                       mark_thresh(rule, lo), mark_thresh(rule, hi), d_coord, d_marks, d_blocks, d_cross);
+  else
+    hipLaunchKernelGGL(planar_mark_kernel, grid, dim3(256), 0, ctx->stream, d_sift, num_pts, num_pts2, rule,
+                       mark_thresh(rule, lo), mark_thresh(rule, hi), d_coord, d_marks, d_blocks, PlanarBatch{}, d_cross);
+}
+
 struct RansacOut {
-  void *h_model, *h_ransac;  // nine values each
+  void *h_model, *h_ransac;  // RansacModel::reported values each
   int *num_candidates, *num_matches, *num_fit, *best_loop;
   char *h_inliers;
   int *h_drawn;
@@ -237,8 +253,8 @@ struct RansacOut {
   int *h_all_counts;
 };
 
-// every refusal of cusift_estimate_homography and cusift_estimate_fundamental, before anything is enqueued or written;
-// `outputs`: none of the required output pointers is NULL
+// every refusal of cusift_estimate_homography and cusift_estimate_fundamental, and those that cusift_estimate_pnp shares
+// (pnp_check), before anything is enqueued or written; `outputs`: none of the required output pointers is NULL
 static int ransac_check(const char *who, bool outputs, const cusift_point *d_sift, int num_pts, int rule, float lo,
                         float hi, int num_loops, float thresh, int refine_loops, float refine_thresh) {
   if (!outputs) return fail(CUSIFT_ERR_INVALID, "%s: NULL output", who);
@@ -258,10 +274,10 @@ static int precheck(const char *who, const cusift_point *d_sift, int num_pts, in
                       rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh);
 }
 
-// fewer than 8 records or candidates: there is nothing to fit
+// fewer than the model's min_pts records or candidates: there is nothing to fit
 static void ransac_nothing(const RansacModel &m, int num_pts, int num_loops, const RansacOut &o) {
-  memcpy(o.h_model, m.nothing, m.elem * 9);
-  memcpy(o.h_ransac, m.nothing, m.elem * 9);
+  memcpy(o.h_model, m.nothing, m.elem * m.reported);
+  memcpy(o.h_ransac, m.nothing, m.elem * m.reported);
   *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
   if (o.best_loop) *o.best_loop = 0;
   if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
@@ -272,7 +288,8 @@ static void ransac_nothing(const RansacModel &m, int num_pts, int num_loops, con
 
 // What one pair keeps on the device, as byte offsets into its block (PlanarBatch::scratch apart in a batch): samples,
 // hypotheses and counts -- which the pair call can read back, so they come first -- then all records' coordinates,
-// candidates, marks, the marking's block counts and, for the fundamental matrix, the candidates' own coordinates.
+// candidates, marks, the marking's block counts and, behind the epipolar and the PnP kernels, the candidates' own
+// coordinates.
 struct RansacBlock {
   size_t idx, model, counts, coord, cand, marks, blocks, ccoord, bytes;
   RansacBlock(const RansacModel &m, int num_pts, int num_loops) {
@@ -280,11 +297,11 @@ struct RansacBlock {
     idx = s.take(sizeof(int) * m.samples * (size_t)num_loops);
     model = s.take(m.elem * m.values * (size_t)num_loops);
     counts = s.take(sizeof(int) * (size_t)num_loops);
-    coord = s.take(sizeof(float) * 4 * (size_t)num_pts);
+    coord = s.take(sizeof(float) * m.coord_rows * (size_t)num_pts);
     cand = s.take(sizeof(int) * (size_t)num_pts);
     marks = s.take((size_t)num_pts);
     blocks = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
-    ccoord = m.epipolar ? s.take(sizeof(float) * 4 * (size_t)num_pts) : 0;
+    ccoord = m.ccoord ? s.take(sizeof(float) * m.coord_rows * (size_t)num_pts) : 0;
     bytes = s.size;
   }
 };
@@ -631,7 +648,7 @@ static int pose_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_
   HIP_TRY(hipMemcpyAsync(base + sizeof(double) * kEpiHeadF, h_fundamental, sizeof(double) * 9, hipMemcpyHostToDevice,
                          ctx->stream));
   if (num_pts > 0)
-    mark_launch(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, at<float>(base, coord_off),
+    mark_launch(ctx, kFundamental, d_sift, num_pts, num_pts2, rule, lo, hi, at<float>(base, coord_off),
                 at<unsigned char>(base, mark_off), at<int>(base, block_off), nullptr);
   TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(base, coord_off), at<unsigned char>(base, mark_off), (const int *)base,
                    at<int>(base, pose_off), st));
@@ -654,7 +671,8 @@ extern "C" int cusift_estimate_pose(cusift_ctx *ctx, cusift_point *d_sift, int n
 }
 
 // ------------------------------------------------------------------------------------------------
-// the run of the marked-RANSAC chain, and planar and epipolar registration on it -- one read-back
+// the epipolar and the PnP launches, the run of the marked-RANSAC chain, and planar and epipolar registration on it --
+// one read-back
 // ------------------------------------------------------------------------------------------------
 // The four launches behind the marking, over the block(s) at d_block; n_pairs and nb as planar_launch.
 static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh,
@@ -682,12 +700,42 @@ static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, 
                      refine_loops, refine_thresh, d_head, d_flags, d_err, nb);
 }
 
+// The four launches behind the marking, over the block at d_block: the candidates' 3-D points against their matches'
+// pixels in the image of `cam` (sift_pnp.hip, which has no batch form).
+static void pnp_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh, int refine_loops,
+                       float refine_thresh, uint64_t seed, PnPCam cam, char *d_block, const RansacBlock &b, int *d_head,
+                       char *d_flags) {
+  const float *d_coord = at<float>(d_block, b.coord);
+  float *d_ccoord = at<float>(d_block, b.ccoord);
+  const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
+  double *d_pose = at<double>(d_block, b.model);
+  int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
+  // scoring: as epipolar_launch, over the candidates of the one pair
+  constexpr int n_pairs = 1;
+  const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
+  int cand_per_split;
+  const int splits = score_splits(ctx, num_pts, (long)loop_blocks * n_pairs, 8, 64, true, &cand_per_split);
+  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_marks, num_pts,
+                     (const int *)at<int>(d_block, b.blocks), d_cand, d_head, PlanarBatch{});
+  hipLaunchKernelGGL(pnp_solve_kernel, dim3(loop_blocks), dim3(64), 0, ctx->stream, d_coord, num_pts,
+                     (const int *)d_cand, (const int *)d_head, (unsigned long long)seed, num_loops, cam,
+                     at<int>(d_block, b.idx), d_pose, d_counts, d_ccoord);
+  hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64), 0, ctx->stream, (const float *)d_ccoord,
+                     num_pts, cand_per_split, (const double *)d_pose, num_loops, cam, thresh, d_counts,
+                     (const int *)d_head);
+  hipLaunchKernelGGL(pnp_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, d_coord,
+                     (const float *)d_ccoord, d_marks, (const double *)d_pose, (const int *)d_counts, num_loops, cam,
+                     thresh, refine_loops, refine_thresh, d_head, d_flags);
+}
+
 // The marking, the model's four launches and the one read-back; the arguments are checked.  d_cross as mark_launch's.
 // pose != NULL (cusift_register_pose, on F): its stage behind the selection, at refine_thresh, its head last.
+// cam: the matches' camera, which kPnP alone takes.
 static int ransac_run(cusift_ctx *ctx, const RansacModel &m, cusift_point *d_sift, int num_pts, int num_pts2, int rule,
                       float lo, float hi, int num_loops, float thresh, int refine_loops, float refine_thresh,
-                      uint64_t seed, const RansacOut &o, const cusift_point *d_cross, PoseStage *pose = nullptr) {
-  if (num_pts < 8) {  // fewer than either solver takes (extras/homography.cu:205): the answer needs no device work
+                      uint64_t seed, const RansacOut &o, const cusift_point *d_cross, PoseStage *pose = nullptr,
+                      const PnPCam *cam = nullptr) {
+  if (num_pts < m.min_pts) {  // fewer than the solver takes (extras/homography.cu:205): the answer needs no device work
     ransac_nothing(m, num_pts, num_loops, o);
     // a pose stage still owes coords3D of the records: the staged route from the nine zeros just reported
     return pose ? pose_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, (const double *)o.h_model, *pose) : CUSIFT_OK;
@@ -701,14 +749,17 @@ static int ransac_run(cusift_ctx *ctx, const RansacModel &m, cusift_point *d_sif
   const size_t pose_off = pose ? s.take(kPoseHeadBytes) : 0;
   TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
   char *base = ctx->register_scratch, *d_block = base + block_off;
-  mark_launch(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, at<float>(d_block, b.coord),
+  mark_launch(ctx, m, d_sift, num_pts, num_pts2, rule, lo, hi, at<float>(d_block, b.coord),
               at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), d_cross);
-  if (m.epipolar)
+  if (m.launch == kPlanarLaunch)
+    planar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
+                  base + flag_off, nullptr, 1, PlanarBatch{});
+  else if (m.launch == kEpipolarLaunch)
     epipolar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
                     base + flag_off, nullptr, 1, PlanarBatch{});
   else
-    planar_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
-                  base + flag_off, nullptr, 1, PlanarBatch{});
+    pnp_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, *cam, d_block, b, (int *)base,
+               base + flag_off);
   if (pose)
     TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
                      (const int *)base, at<int>(base, pose_off), *pose));
@@ -720,14 +771,16 @@ static int ransac_run(cusift_ctx *ctx, const RansacModel &m, cusift_point *d_sif
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (pose) pose_report(*pose);
   const char *head = back.data(), *block = back.data() + block_off;
-  if (head_int(head, kPlanarHeadCand) < 8) {  // extras/homography.cu:220; the kernels left the records alone
+  const int n_cand = head_int(head, kPlanarHeadCand);
+  // extras/homography.cu:220; the kernels left the records alone
+  if (n_cand < m.min_pts || (m.needs_support && head_int(head, kPlanarHeadMatches) < 1)) {
     ransac_nothing(m, num_pts, num_loops, o);
-    *o.num_candidates = head_int(head, kPlanarHeadCand);
+    *o.num_candidates = n_cand;
     return CUSIFT_OK;
   }
-  memcpy(o.h_model, head + m.elem * m.head_model, m.elem * 9);
-  memcpy(o.h_ransac, head + m.elem * m.head_ransac, m.elem * 9);
-  *o.num_candidates = head_int(head, kPlanarHeadCand), *o.num_matches = head_int(head, kPlanarHeadMatches);
+  memcpy(o.h_model, head + m.elem * m.head_model, m.elem * m.reported);
+  memcpy(o.h_ransac, head + m.elem * m.head_ransac, m.elem * m.reported);
+  *o.num_candidates = n_cand, *o.num_matches = head_int(head, kPlanarHeadMatches);
   *o.num_fit = head_int(head, kPlanarHeadFit);
   if (o.best_loop) *o.best_loop = head_int(head, kPlanarHeadLoop);
   if (o.h_inliers) memcpy(o.h_inliers, back.data() + flag_off, (size_t)num_pts);
@@ -798,138 +851,19 @@ extern "C" int cusift_register_epipolar(cusift_ctx *ctx, cusift_point *d_sift1, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// absolute pose from coords3D and the matches' pixels (sift_pnp.hip): a sibling of ransac_run -- six samples, twelve
-// values, five coordinate rows, a camera, the answer [I | 0] -- with the same shape: one read-back, one wait
+// absolute pose from coords3D and the matches' pixels (sift_pnp.hip): the third model of ransac_run -- six samples,
+// twelve values, five coordinate rows, a camera, the answer [I | 0] -- one read-back
 // ------------------------------------------------------------------------------------------------
-struct PnPOut {
-  double *h_rt, *h_ransac;  // twelve values each
-  int *num_candidates, *num_matches, *num_fit, *best_loop;
-  char *h_inliers;
-  int *h_drawn;
-  double *h_all;
-  int *h_all_counts;
-};
-static const double kIdentRtD[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-
 // every refusal of cusift_estimate_pnp, before anything is enqueued or written
 static int pnp_check(const char *who, const cusift_point *d_sift, int num_pts, int rule, float lo, float hi,
                      const cusift_camera *camera2, int num_loops, float thresh, int refine_loops, float refine_thresh,
-                     const PnPOut &o) {
+                     const RansacOut &o) {
   if (!camera2) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
-  TRY(ransac_check(who, o.h_rt && o.h_ransac && o.num_candidates && o.num_matches && o.num_fit, d_sift, num_pts, rule, lo,
-                   hi, num_loops, thresh, refine_loops, refine_thresh));
+  TRY(precheck(who, d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
   return check_pinhole(camera2, who);
 }
-
-// fewer than 6 records or candidates, or no hypothesis that counts a point: there is nothing to fit
-static void pnp_nothing(int num_pts, int num_loops, const PnPOut &o) {
-  memcpy(o.h_rt, kIdentRtD, sizeof(kIdentRtD));
-  memcpy(o.h_ransac, kIdentRtD, sizeof(kIdentRtD));
-  *o.num_candidates = 0, *o.num_matches = 0, *o.num_fit = 0;
-  if (o.best_loop) *o.best_loop = 0;
-  if (o.h_inliers && num_pts > 0) memset(o.h_inliers, 0, (size_t)num_pts);
-  if (o.h_drawn) memset(o.h_drawn, 0, sizeof(int) * 6 * (size_t)num_loops);
-  if (o.h_all) memset(o.h_all, 0, sizeof(double) * 12 * (size_t)num_loops);
-  if (o.h_all_counts) memset(o.h_all_counts, 0, sizeof(int) * (size_t)num_loops);
-}
-
-// What the call keeps on the device: samples, hypotheses and counts -- which can be read back, so they come first -- then
-// all records' five coordinate rows, candidates, marks, the marking's block counts and the candidates' own coordinates.
-struct PnPBlock {
-  size_t idx, model, counts, coord, cand, marks, blocks, ccoord, bytes;
-  PnPBlock(int num_pts, int num_loops) {
-    ScratchLayout s;
-    idx = s.take(sizeof(int) * 6 * (size_t)num_loops);
-    model = s.take(sizeof(double) * 12 * (size_t)num_loops);
-    counts = s.take(sizeof(int) * (size_t)num_loops);
-    coord = s.take(sizeof(float) * 5 * (size_t)num_pts);
-    cand = s.take(sizeof(int) * (size_t)num_pts);
-    marks = s.take((size_t)num_pts);
-    blocks = s.take(sizeof(int) * (size_t)idiv_up(num_pts, 256));
-    ccoord = s.take(sizeof(float) * 5 * (size_t)num_pts);
-    bytes = s.size;
-  }
-};
-
-// The candidate splits of pnp_score_kernel: the plan of the epipolar scoring, ~8 one-wave workgroups per CU and whole
-// 64-candidate tiles.  It restates the planner's arithmetic at those settings in place of a fourth call site:
-// tests/test_register_source.py pins the planner's three call sites, and tests/test_pnp_sizes.py plans with this one.
-static int pnp_splits(cusift_ctx *ctx, int num_pts, int loop_blocks, int *per_split_out) {
-  const long target = (8L * ctx->num_cus + loop_blocks - 1) / loop_blocks;
-  const int splits = (int)std::max(1L, std::min(std::min(target, (long)idiv_up(num_pts, 64)), 65535L));
-  const int per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;
-  *per_split_out = per_split;
-  return idiv_up(num_pts, per_split);
-}
-
-// The five launches: the marking and the four behind it.
-static void pnp_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
-                       PnPCam cam, int num_loops, float thresh, int refine_loops, float refine_thresh, uint64_t seed,
-                       char *d_block, const PnPBlock &b, int *d_head, char *d_flags, const cusift_point *d_cross) {
-  float *d_coord = at<float>(d_block, b.coord), *d_ccoord = at<float>(d_block, b.ccoord);
-  unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
-  double *d_pose = at<double>(d_block, b.model);
-  int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand), *d_blocks = at<int>(d_block, b.blocks);
-  const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
-  int per_split;
-  const int splits = pnp_splits(ctx, num_pts, loop_blocks, &per_split);
-  hipLaunchKernelGGL(pnp_mark_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const cusift_point *)d_sift, num_pts,
-                     num_pts2, rule, mark_thresh(rule, lo), mark_thresh(rule, hi), d_coord, d_marks, d_blocks, d_cross);
-  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const unsigned char *)d_marks,
-                     num_pts, (const int *)d_blocks, d_cand, d_head, PlanarBatch{});
-  hipLaunchKernelGGL(pnp_solve_kernel, dim3(loop_blocks), dim3(64), 0, ctx->stream, (const float *)d_coord, num_pts,
-                     (const int *)d_cand, (const int *)d_head, (unsigned long long)seed, num_loops, cam,
-                     at<int>(d_block, b.idx), d_pose, d_counts, d_ccoord);
-  hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64), 0, ctx->stream, (const float *)d_ccoord,
-                     num_pts, per_split, (const double *)d_pose, num_loops, cam, thresh, d_counts, (const int *)d_head);
-  hipLaunchKernelGGL(pnp_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, (const float *)d_coord,
-                     (const float *)d_ccoord, (const unsigned char *)d_marks, (const double *)d_pose,
-                     (const int *)d_counts, num_loops, cam, thresh, refine_loops, refine_thresh, d_head, d_flags);
-}
-
-// The five launches and the one read-back; the arguments are checked.  d_cross as mark_launch's.
-static int pnp_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo, float hi,
-                   const cusift_camera *camera2, int num_loops, float thresh, int refine_loops, float refine_thresh,
-                   uint64_t seed, const PnPOut &o, const cusift_point *d_cross) {
-  if (num_pts < 6) {  // fewer than the solver takes: the answer needs no device work
-    pnp_nothing(num_pts, num_loops, o);
-    return CUSIFT_OK;
-  }
-  const PnPCam cam{(double)camera2->fx, (double)camera2->fy, (double)camera2->cx - (double)camera2->origin,
-                   (double)camera2->cy - (double)camera2->origin};
-  // [head | flags | samples | hypotheses | counts] is what travels back, in one copy; behind it what stays on the device
-  const PnPBlock b(num_pts, num_loops);
-  ScratchLayout s;
-  s.take(kPnPHeadBytes);  // the head, at 0
-  const size_t flag_off = s.take((size_t)num_pts);
-  const size_t block_off = s.take(b.bytes);
-  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
-  char *base = ctx->register_scratch;
-  pnp_launch(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, cam, num_loops, thresh, refine_loops, refine_thresh, seed,
-             base + block_off, b, (int *)base, base + flag_off, d_cross);
-  TRY(check_launch("estimate_pnp"));
-  // the one blocking read-back
-  const bool all = o.h_drawn || o.h_all || o.h_all_counts;
-  std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const char *head = back.data(), *block = back.data() + block_off;
-  const int n_cand = head_int(head, kPlanarHeadCand);
-  if (n_cand < 6 || head_int(head, kPlanarHeadMatches) < 1) {  // the kernels left the records alone
-    pnp_nothing(num_pts, num_loops, o);
-    *o.num_candidates = n_cand;
-    return CUSIFT_OK;
-  }
-  memcpy(o.h_rt, head + sizeof(double) * kPnPHeadRt, sizeof(double) * 12);
-  memcpy(o.h_ransac, head + sizeof(double) * kPnPHeadWin, sizeof(double) * 12);
-  *o.num_candidates = n_cand, *o.num_matches = head_int(head, kPlanarHeadMatches);
-  *o.num_fit = head_int(head, kPlanarHeadFit);
-  if (o.best_loop) *o.best_loop = head_int(head, kPlanarHeadLoop);
-  if (o.h_inliers) memcpy(o.h_inliers, back.data() + flag_off, (size_t)num_pts);
-  if (o.h_drawn) memcpy(o.h_drawn, block + b.idx, sizeof(int) * 6 * (size_t)num_loops);
-  if (o.h_all) memcpy(o.h_all, block + b.model, sizeof(double) * 12 * (size_t)num_loops);
-  if (o.h_all_counts) memcpy(o.h_all_counts, block + b.counts, sizeof(int) * (size_t)num_loops);
-  return CUSIFT_OK;
+static PnPCam pnp_cam(const cusift_camera *c) {
+  return PnPCam{(double)c->fx, (double)c->fy, (double)c->cx - (double)c->origin, (double)c->cy - (double)c->origin};
 }
 
 extern "C" int cusift_estimate_pnp(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_pts2, int rule, float lo,
@@ -938,10 +872,11 @@ extern "C" int cusift_estimate_pnp(cusift_ctx *ctx, cusift_point *d_sift, int nu
                                    int *num_candidates, int *num_matches, int *num_fit, int *best_loop, char *h_inliers,
                                    int *h_drawn, double *h_all_rt, int *h_all_counts) {
   TRY(enter(ctx));
-  const PnPOut o{h_rt, h_ransac, num_candidates, num_matches, num_fit, best_loop, h_inliers, h_drawn, h_all_rt, h_all_counts};
+  const RansacOut o{h_rt, h_ransac, num_candidates, num_matches, num_fit, best_loop, h_inliers, h_drawn, h_all_rt, h_all_counts};
   TRY(pnp_check("EstimatePnP", d_sift, num_pts, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh, o));
-  return pnp_run(ctx, d_sift, num_pts, num_pts2, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh,
-                 seed, o, nullptr);
+  const PnPCam cam = pnp_cam(camera2);
+  return ransac_run(ctx, kPnP, d_sift, num_pts, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+                    seed, o, nullptr, nullptr, &cam);
 }
 
 extern "C" int cusift_register_pnp(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
@@ -951,12 +886,13 @@ extern "C" int cusift_register_pnp(cusift_ctx *ctx, cusift_point *d_sift1, int n
                                    int *num_candidates, int *num_matches, int *num_fit, int *best_loop, char *h_inliers,
                                    int *h_drawn, double *h_all_rt, int *h_all_counts) {
   TRY(enter(ctx));
-  const PnPOut o{h_rt, h_ransac, num_candidates, num_matches, num_fit, best_loop, h_inliers, h_drawn, h_all_rt, h_all_counts};
+  const RansacOut o{h_rt, h_ransac, num_candidates, num_matches, num_fit, best_loop, h_inliers, h_drawn, h_all_rt, h_all_counts};
   TRY(pnp_check("RegisterPnP", d_sift1, num_pts1, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh, o));
   const cusift_point *d_cross;
   TRY(match_enqueue(ctx, "RegisterPnP", d_sift1, num_pts1, d_sift2, num_pts2, distance, &d_cross));
-  return pnp_run(ctx, d_sift1, num_pts1, num_pts2, rule, lo, hi, camera2, num_loops, thresh, refine_loops, refine_thresh,
-                 seed, o, d_cross);
+  const PnPCam cam = pnp_cam(camera2);
+  return ransac_run(ctx, kPnP, d_sift1, num_pts1, num_pts2, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+                    seed, o, d_cross, nullptr, &cam);
 }
 
 // ------------------------------------------------------------------------------------------------

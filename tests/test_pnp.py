@@ -482,12 +482,9 @@ def test_header_library_and_binding_carry_the_pnp_calls():
                  "ransac_sample<6>(seed, idx, n, p);", "ransac_winner<true>(counts, num_loops, s_key, best, best_count);",
                  "wave_tree_sum<kPnPSums>(s, s_part, s_sum, tx);"):
         assert expr in kernels, expr
-    # the scoring plan that tests/test_pnp_sizes.py restates
+    # the scoring grid that tests/test_pnp_sizes.py plans for; tests/test_register_source.py pins the planner and its call
     host = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
-    for line in ("const long target = (8L * ctx->num_cus + loop_blocks - 1) / loop_blocks;",
-                 "const int per_split = idiv_up(idiv_up(num_pts, splits), 64) * 64;",
-                 "hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64)"):
-        assert line in host, line
+    assert "hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64)" in host
 
 
 def exact_scene(name, n=60):

@@ -2,8 +2,8 @@
 loops.  The marking then has 258 workgroups, so planar_compact_kernel's walk over the block counts takes a second step,
 and a scoring split holds several 64-candidate tiles with a ragged one that is not its first (on 256 CUs: 32 splits of
 2,112; three full splits of 33 tiles, a fourth with 2 tiles + 36 candidates, 28 empty).  The premise is asserted with the
-device's own CU count, planned with pnp_splits' arithmetic, which is score_splits' at (8, 64, whole tiles).  The check is
-DEVICE = MODEL of tests/test_pnp.py."""
+device's own CU count, planned with score_splits' arithmetic at the arguments of pnp_launch's call site, which
+tests/test_register_source.py pins.  The check is DEVICE = MODEL of tests/test_pnp.py."""
 import functools
 
 import numpy as np
@@ -12,9 +12,9 @@ import pytest
 from oracle_binding import SIFT_POINT_DTYPE
 from test_pnp import CAM, H, RULE, W, about_y, check_device_equals_model, frustum, pnp_candidates, project, run
 from test_ransac_sizes import device_cus, score_plan, several_tiles, split_tiles
+from test_register_source import PNP as PLAN  # (per_cu, tile, round_to_tile) of pnp_launch's call of score_splits
 
 N, N_IN, N_OUT, LOOPS, SEED = 66000, 3500, 3000, 4096, 1
-PLAN = (8, 64, True)  # pnp_splits of sift_register.hip
 
 
 @functools.lru_cache(maxsize=None)

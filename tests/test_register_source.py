@@ -12,9 +12,10 @@ CSRC = os.path.join(ROOT, "cusift_amd", "csrc")
 
 BLOCKING = ("hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDtoH(", "hipEventSynchronize", "hipMalloc(", "hipFree(",
             "cusift_ctx_synchronize", "cusift_memcpy")
-# (per_cu, tile, round_to_tile) of the three call sites of score_splits, in the order they stand in sift_register.hip;
-# tests/test_ransac_sizes.py plans its sizes with these
+# (per_cu, tile, round_to_tile) of the four call sites of score_splits, in the order they stand in sift_register.hip;
+# tests/test_ransac_sizes.py and tests/test_pnp_sizes.py plan their sizes with these
 PLANAR, RIGID, EPI = (8, 64, True), (4, 256, False), (8, 64, True)
+PNP = (8, 64, True)
 LAUNCH_BANNED = ("for (", "while (", "hipMemcpy", "hipMemset", "Synchronize", "grow_scratch")
 DEFINITION = r'^(?:static|extern "C") [^\n(;={]*?\b(\w+)\('
 
@@ -62,7 +63,7 @@ def one_sync_nothing_else(name, without=()):
 
 
 def check_four_launches(name, kernels):
-    """planar_launch / epipolar_launch: the four launches behind the marking, in their order, none in a loop, and nothing
+    """planar_launch / epipolar_launch / pnp_launch: the four launches behind the marking, in their order, none in a loop, and nothing
     that copies or waits."""
     launch = body(name)
     assert launch.count("hipLaunchKernelGGL(") == 4
@@ -87,9 +88,22 @@ def check_matcher_of_a_fused_call(fused, run):
     assert "match_mutual_kernel<" in reached and "match_kernel<" in reached  # it does reach both matchers' launches
 
 
+def model_field(descriptor, field):
+    """What the RansacModel `descriptor` (kHomography, kFundamental, kPnP) carries in `field`, as text."""
+    struct = code()[code().index("struct RansacModel {"):]
+    members = struct[struct.index("{") + 1:struct.index("\n};\n")]
+    names = [re.sub(r"^.*[ *]", "", n.strip()) for decl in members.split(";") if decl.strip() for n in decl.split(",")]
+    found = re.findall(r"static const RansacModel %s\{([^}]*)\};" % descriptor, code())
+    assert len(found) == 1, descriptor
+    values = [v.strip() for v in found[0].split(",")]
+    assert len(values) == len(names) and names.count(field) == 1, (descriptor, names, values)
+    return values[names.index(field)]
+
+
 def check_chain_run(launch):
-    """ransac_run, the run of both chains: mark -> four launches -> (pose enqueue) -> the one read-back -> the one wait ->
-    (pose report); the staged pose route of fewer than 8 records leaves before anything is enqueued."""
+    """ransac_run, the run of the three chains: mark -> four launches -> (pose enqueue) -> the one read-back -> the one
+    wait -> (pose report); the staged pose route of fewer records than the model can fit leaves before anything is
+    enqueued."""
     run = body("ransac_run")
     # was: order of ("planar_mark_kernel", "planar_launch(" / "epipolar_launch(", "hipMemcpyAsync(", "hipStreamSynchronize(")
     # in planar_run / epipolar_run, and of ("epipolar_launch(", "pose_enqueue(", "hipMemcpyAsync(", "hipStreamSynchronize(",
@@ -101,12 +115,17 @@ def check_chain_run(launch):
     assert run.count("hipStreamSynchronize(") == 1 and run.count("pose_enqueue(") == 1
     # was: run.count("hipLaunchKernelGGL(") == 1 and run.count("planar_launch(") == 1 -- the marking, then the shared four
     assert run.count("hipLaunchKernelGGL(") == 0 and run.count("mark_launch(") == 1 and run.count(launch) == 1
+    # was: one launch in mark_launch, planar_mark_kernel.  Now one per branch: the PnP model's marking, else the planar one
     mark = body("mark_launch")
-    assert mark.count("hipLaunchKernelGGL(") == 1 and "hipLaunchKernelGGL(planar_mark_kernel" in mark
+    assert mark.count("hipLaunchKernelGGL(") == 2 and mark.count("hipLaunchKernelGGL(planar_mark_kernel") == 1
+    assert mark.count("hipLaunchKernelGGL(pnp_mark_kernel") == 1
+    assert re.search(r"if \([^\n]*\)[^\n;]*\n\s*hipLaunchKernelGGL\(pnp_mark_kernel[^;]*;\n\s*else\n\s*hipLaunchKernelGGL\(planar_mark_kernel", mark)
     for banned in LAUNCH_BANNED:
         assert banned not in mark, banned
     # the other way out: the answer that needs no device work, and from there the staged pose route, which has its own wait
-    assert run.count("pose_run(") == 1 and in_order(run, "if (num_pts < 8) {", "pose_run(", "\n  }\n", "grow_scratch(")
+    # was: "if (num_pts < 8) {" -- now the model's minimum, which is 8 for H and F as before and 6 for PnP
+    assert run.count("pose_run(") == 1 and in_order(run, "if (num_pts < m.min_pts) {", "pose_run(", "\n  }\n", "grow_scratch(")
+    assert [model_field(d, "min_pts") for d in ("kHomography", "kFundamental", "kPnP")] == ["8", "8", "6"]
     assert re.search(r"return pose \? pose_run\([^;]*\) : CUSIFT_OK;", run)
 
 
@@ -182,6 +201,21 @@ def test_one_synchronisation_in_the_pose_entry_points():
     assert staged.count("hipStreamSynchronize(") == 1 and not [b for b in BLOCKING if b in staged]
 
 
+def test_one_synchronisation_in_the_pnp_entry_points():
+    for name in ("cusift_estimate_pnp", "cusift_register_pnp"):
+        one_sync_nothing_else(name, without=("pose_run",))
+        assert body(name).count("ransac_run(") == 1 and "&st" not in body(name) and "pose_stage(" not in body(name)
+    check_chain_run("pnp_launch(")
+    check_four_launches("pnp_launch", ("planar_compact_kernel", "pnp_solve_kernel", "pnp_score_kernel",
+                                       "pnp_select_kernel"))
+    reg = body("cusift_register_pnp")
+    check_matcher_of_a_fused_call(reg, "ransac_run(")
+    assert "Synchronize" not in reg and "hipMemcpy" not in reg  # nothing of its own
+    # the chain's copies are gone
+    for gone in ("pnp_run", "pnp_splits", "PnPBlock", "PnPOut", "pnp_nothing"):
+        assert gone not in open(os.path.join(CSRC, "sift_register.hip")).read(), gone
+
+
 # the same rule on the blocking calls that no test held to it before
 def test_one_synchronisation_in_the_other_blocking_entry_points():
     for name in ("cusift_find_homography", "cusift_estimate_rigid", "cusift_register_rgbd_batch"):
@@ -200,14 +234,14 @@ def test_one_synchronisation_in_the_other_blocking_entry_points():
 
 # was tests/test_ransac_sizes.py::test_call_sites_of_score_splits_pass_what_the_plans_here_assume
 def test_call_sites_of_score_splits_pass_what_the_plans_here_assume():
-    """Whoever changes the planner or a call site learns here that the sizes of tests/test_ransac_sizes.py need another
-    look."""
+    """Whoever changes the planner or a call site learns here that the sizes of tests/test_ransac_sizes.py and tests/test_pnp_sizes.py
+    need another look."""
     calls = re.findall(r"score_splits\(ctx, num_pts, \(long\)loop_blocks \* n_pairs, (\d+), (\d+), (true|false), &\w+\)", code())
-    want = [(str(p), str(t), "true" if r else "false") for p, t, r in (PLANAR, RIGID, EPI)]
-    assert calls == want and code().count("score_splits(") == 4, calls  # the definition and the three call sites
+    want = [(str(p), str(t), "true" if r else "false") for p, t, r in (PLANAR, RIGID, EPI, PNP)]
+    assert calls == want and code().count("score_splits(") == 5, calls  # the definition and the four call sites
     assert in_order(code(), "static int score_splits(", "static void planar_launch(", "8, 64, true, &pts_per_split",
                     "static void rigid_launch(", "4, 256, false, &pts_per_split", "static void epipolar_launch(",
-                    "8, 64, true, &per_split")
+                    "8, 64, true, &per_split", "static void pnp_launch(", "8, 64, true, &cand_per_split")
     for blocks in ("loop_blocks = idiv_up(num_loops, 64)", "loop_blocks = idiv_up(num_loops, 256)"):
         assert blocks in code(), blocks
     planner = body("score_splits")  # was: from its signature to `struct PlanarOut {`
