@@ -61,6 +61,7 @@ cpp-tests: $(LIB)
 	$(MAKE) -C $(ROOT)/tests/cpp_epipolar
 	$(MAKE) -C $(ROOT)/tests/cpp_pose
 	$(MAKE) -C $(ROOT)/tests/cpp_pnp
+	$(MAKE) -C $(ROOT)/tests/cpp_sequence_pose
 
 check: cpp-tests
 	$(MAKE) -C $(ROOT)/tests/cpp check

@@ -168,6 +168,49 @@ class BatchExtractor:
         points, counts = self.slots[slot]
         return self.ctx.register_planar_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts, pairs, **opts)
 
+    def _pairs(self, pairs):
+        return [(i, i + 1) for i in range(self.n - 1)] if pairs is None else pairs
+
+    def register_epipolar_sequence(self, pairs=None, slot=0, **opts):
+        """Epipolar registration of the frames of the last extract() into `slot` against each other:
+        cusift_register_epipolar_batch over this extractor's own device records and raw counters -- no count is read back
+        and the records are not written.  pairs: (frame a, frame b) rows; None: (i, i + 1) for every consecutive frame.
+        **opts goes to capi.Context.register_epipolar_batch.  Returns its EpipolarBatchResult: x_b^T F x_a = 0.
+        Blocking."""
+        points, counts = self.slots[slot]
+        return self.ctx.register_epipolar_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
+                                                self._pairs(pairs), **opts)
+
+    def register_pose_sequence(self, camera, camera2=None, pairs=None, slot=0, **opts):
+        """Calibrated two-view poses of the frames of the last extract() into `slot`: cusift_register_pose_batch over this
+        extractor's own device records and raw counters, one pair of cameras for every pair of the list (camera2 None:
+        the same camera).  The records are not written: want_points=True returns each pair's triangulated points.
+        **opts goes to capi.Context.register_pose_batch.  Returns its PoseBatchResult: X_a = R X_b + t with |t| = 1 per
+        pair -- capi.chain_poses does NOT apply to these poses, every pair has a scale of its own.  Blocking."""
+        points, counts = self.slots[slot]
+        return self.ctx.register_pose_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
+                                            self._pairs(pairs), camera, camera2, **opts)
+
+    def register_pnp_sequence(self, camera2, pairs=None, slot=0, d_depth=None, depth_camera=None, **opts):
+        """Absolute poses of the frames of the last extract() into `slot`: cusift_register_pnp_batch over this extractor's
+        own device records and raw counters.  camera2: the capi.Camera of every pair's frame b.  coords3D of the records
+        is read and not written.  d_depth (int16 / uint16 device tensor [n, h, w'], as register_sequence takes it) with
+        depth_camera (None: camera2): one cusift_lift_depth over the whole batch is enqueued on the same stream first --
+        an RGB-D sequence registered by reprojection error, where only frame a of each pair needs depth (register_sequence
+        needs both).  **opts goes to capi.Context.register_pnp_batch.  Returns its PnPBatchResult: X_a = R X_b + t in the
+        unit of coords3D, metric after a lift, so capi.chain_poses(rt) turns the default pair list's result into
+        per-frame poses.  Blocking."""
+        points, counts = self.slots[slot]
+        if d_depth is not None:
+            assert d_depth.is_cuda and d_depth.element_size() == 2 and d_depth.is_contiguous()
+            assert d_depth.dim() == 3 and d_depth.shape[0] == self.n and d_depth.shape[1] == self.h, tuple(d_depth.shape)
+            assert d_depth.shape[2] >= self.w, tuple(d_depth.shape)
+            self.ctx.lift_depth(points.data_ptr(), self.max_pts, d_depth.data_ptr(), self.w, self.h,
+                                camera2 if depth_camera is None else depth_camera, pitch=d_depth.shape[2],
+                                n_images=self.n, d_counters=counts.data_ptr(), image_stride=self.h * d_depth.shape[2])
+        return self.ctx.register_pnp_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
+                                           self._pairs(pairs), camera2, **opts)
+
     def valid_counts(self):
         return torch.clamp(self.counts, max=self.max_pts)
 

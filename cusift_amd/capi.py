@@ -237,6 +237,13 @@ SIGNATURES = {
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cusift_register_epipolar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cusift_register_pose_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64,
+                                        C.POINTER(Camera), C.POINTER(Camera), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "cusift_register_pnp_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, C.POINTER(Camera), _i, _f, _i, _f,
+                                       C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cusift_pack_points": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_compact": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cusift_pack_points_trimmed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -357,6 +364,17 @@ PnPResult = collections.namedtuple("PnPResult", "rt ransac num_candidates num_ma
                                    "all_rt all_counts")
 # what cusift_register_pose returns: the EpipolarResult, then the PoseResult
 RegisterPoseResult = collections.namedtuple("RegisterPoseResult", EpipolarResult._fields + PoseResult._fields)
+# what the pair-list forms return, one entry per pair, as PlanarBatchResult relates to PlanarResult: the models float64
+# [P, 9] (F) or [P, 3, 4] (poses), int32 [P] counts, counts = the records of each pair's first frame (as the device read
+# them), lists of P bool [count] inlier flags and P float32 [count] match errors (NaN where a pair has no fit); the pose
+# form adds rt [P, 3, 4] with |t| = 1, num_front [P], votes [P, 4], sigma [P, 3] and a list of P float32 [count, 3]
+# triangulated points (what register_pose writes into coords3D)
+EpipolarBatchResult = collections.namedtuple("EpipolarBatchResult", "fundamental ransac num_candidates num_matches "
+                                             "num_fit best_loop counts inliers match_error")
+PoseBatchResult = collections.namedtuple("PoseBatchResult", EpipolarBatchResult._fields +
+                                         ("rt", "num_front", "votes", "sigma", "points3d"))
+PnPBatchResult = collections.namedtuple("PnPBatchResult", "rt ransac num_candidates num_matches num_fit best_loop counts "
+                                        "inliers match_error")
 RIGID_KINDS = {"2d": 0, "3d": 1}  # RigidTransformType2D / RigidTransformType3D, extras/rigidTransform.h:16-19
 
 
@@ -928,7 +946,8 @@ class Context:
 
     def set_cross_check(self, on):
         """cusift_ctx_set_cross_check: while on, register_planar, register_epipolar, register_pose, register_rgbd,
-        register_planar_batch and register_rgbd_batch on this context keep mutual matches only -- record i of frame 1
+        register_planar_batch, register_rgbd_batch, register_epipolar_batch, register_pose_batch and register_pnp_batch
+        on this context keep mutual matches only -- record i of frame 1
         takes part only if the column side's best for its match is i (the lowest record on exactly tied best scores).
         The four pair calls then write the match fields of d_sift2 as well and refuse overlapping record ranges.  Nothing
         else changes."""
@@ -1041,6 +1060,75 @@ class Context:
         return PlanarBatchResult(hom, ransac, n_cand, n_match, n_fit, best, counts,
                                  [flags[p, :counts[p]] == 1 for p in range(n_pairs)] if want_inliers else None,
                                  [err[p, :counts[p]].copy() for p in range(n_pairs)] if want_errors else None)
+
+    def _batch(self, call, shape, pairs, max_pts, want_inliers, want_errors):
+        """The outputs that the pair-list forms of F, the pose and PnP share: call(*pointers) makes the library call with
+        the eight shared output pointers.  Returns the nine fields of an EpipolarBatchResult / PnPBatchResult."""
+        n_pairs = len(pairs)
+        model, ransac = np.zeros((n_pairs,) + shape, dtype=np.float64), np.zeros((n_pairs,) + shape, dtype=np.float64)
+        n_cand, n_match, n_fit, best = (np.zeros(n_pairs, dtype=np.int32) for _ in range(4))
+        # the call writes 0 / 1 into the first count entries of a pair's block and nothing behind them
+        flags = np.full((n_pairs, max(max_pts, 1)), -1, dtype=np.int8)
+        err = np.full((n_pairs, max(max_pts, 1)), np.nan, dtype=np.float32) if want_errors else None
+        check(call(model.ctypes.data, ransac.ctypes.data, n_cand.ctypes.data, n_match.ctypes.data, n_fit.ctypes.data,
+                   best.ctypes.data, flags.ctypes.data, err.ctypes.data if want_errors else None))
+        counts = (flags >= 0).sum(axis=1).astype(np.int32) if max_pts > 0 else np.zeros(n_pairs, dtype=np.int32)
+        return (model, ransac, n_cand, n_match, n_fit, best, counts,
+                [flags[p, :counts[p]] == 1 for p in range(n_pairs)] if want_inliers else None,
+                [err[p, :counts[p]].copy() for p in range(n_pairs)] if want_errors else None)
+
+    def register_epipolar_batch(self, d_points, d_counters, n_images, max_pts, pairs, distance=1, rule=None, lo=None,
+                                hi=None, loops=10000, thresh=1.0, refine_loops=5, refine_thresh=1.0, seed=0,
+                                want_inliers=True, want_errors=False):
+        """cusift_register_epipolar_batch: register_epipolar for every pair of `pairs` (int32 [P, 2]) over
+        d_points[n_images][max_pts] + d_counters[n_images] (None: max_pts each) in a fixed number of launches and one
+        synchronisation.  Pair p = (a, b) gives x_b^T F x_a = 0 and draws from seed + p; the records are not written.
+        rule / lo / hi default as in register_planar.  Returns an EpipolarBatchResult."""
+        pairs = pair_list(pairs)
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
+        return EpipolarBatchResult(*self._batch(lambda *out: lib().cusift_register_epipolar_batch(
+            self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data, len(pairs), distance, rule, lo, hi,
+            int(loops), thresh, refine_loops, refine_thresh, _seed64(seed), *out), (9,), pairs, max_pts, want_inliers,
+            want_errors))
+
+    def register_pose_batch(self, d_points, d_counters, n_images, max_pts, pairs, camera, camera2=None, distance=1,
+                            rule=None, lo=None, hi=None, loops=10000, thresh=1.0, refine_loops=5, refine_thresh=1.0,
+                            seed=0, want_inliers=True, want_errors=False, want_points=False):
+        """cusift_register_pose_batch: register_pose for every pair of `pairs`, as register_epipolar_batch and then the
+        pose stage at refine_thresh per pair -- still one synchronisation.  camera: the capi.Camera of every pair's frame
+        a, camera2 of its frame b (None: the same).  The triangulated points do not go into coords3D (the records are not
+        written): want_points returns them.  Returns a PoseBatchResult: X_a = R X_b + t with |t| = 1 PER PAIR, so
+        capi.chain_poses does not apply -- the scale of each pair is its own."""
+        pairs = pair_list(pairs)
+        n_pairs = len(pairs)
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
+        rt, sigma = np.zeros((n_pairs, 3, 4), dtype=np.float64), np.zeros((n_pairs, 3), dtype=np.float64)
+        front, votes = np.zeros(n_pairs, dtype=np.int32), np.zeros((n_pairs, 4), dtype=np.int32)
+        xyz = np.zeros((n_pairs, max(max_pts, 1), 3), dtype=np.float32) if want_points else None
+        epi = self._batch(lambda *out: lib().cusift_register_pose_batch(
+            self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data, n_pairs, distance, rule, lo, hi,
+            int(loops), thresh, refine_loops, refine_thresh, _seed64(seed),
+            C.byref(camera) if camera is not None else None, C.byref(camera2) if camera2 is not None else None,
+            *(out + (rt.ctypes.data, front.ctypes.data, votes.ctypes.data, sigma.ctypes.data,
+                     xyz.ctypes.data if want_points else None))), (9,), pairs, max_pts, want_inliers, want_errors)
+        counts = epi[6]
+        return PoseBatchResult(*(epi + (rt, front, votes, sigma,
+                                        [xyz[p, :counts[p]].copy() for p in range(n_pairs)] if want_points else None)))
+
+    def register_pnp_batch(self, d_points, d_counters, n_images, max_pts, pairs, camera2, distance=1, rule=None, lo=None,
+                           hi=None, loops=10000, thresh=2.0, refine_loops=5, refine_thresh=2.0, seed=0,
+                           want_inliers=True, want_errors=False):
+        """cusift_register_pnp_batch: register_pnp for every pair of `pairs`: coords3D of frame a's records (lift_depth
+        over the batch, or the caller's; read, never written) against their matches' pixels in frame b, whose capi.Camera
+        is camera2 for every pair.  One synchronisation; pair p draws from seed + p.  Returns a PnPBatchResult: X_a = R X_b
+        + t in the unit of coords3D -- metric after a depth lift, so capi.chain_poses composes the default pair list's
+        rt."""
+        pairs = pair_list(pairs)
+        rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
+        return PnPBatchResult(*self._batch(lambda *out: lib().cusift_register_pnp_batch(
+            self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data, len(pairs), distance, rule, lo, hi,
+            C.byref(camera2) if camera2 is not None else None, int(loops), thresh, refine_loops, refine_thresh,
+            _seed64(seed), *out), (3, 4), pairs, max_pts, want_inliers, want_errors))
 
     # ---- drivers ----
     def extract_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):

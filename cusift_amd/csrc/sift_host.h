@@ -95,17 +95,21 @@ __global__ void epipolar_select_kernel(cusift_point *, int, const float *, const
 __global__ void pose_vote_kernel(const float *, const unsigned char *, int, const int *, PoseCams, float, int *,
                                  PlanarBatch);
 __global__ void pose_write_kernel(cusift_point *, const float *, const unsigned char *, int, const int *, PoseCams, float,
-                                  int *, PlanarBatch);
+                                  int *, float *, PlanarBatch);
 __global__ void pnp_mark_kernel(const cusift_point *, int, int, int, float, float, float *, unsigned char *, int *,
                                 const cusift_point *);
 __global__ void pnp_solve_kernel(const float *, int, const int *, const int *, unsigned long long, int, PnPCam, int *,
-                                 double *, int *, float *);
-__global__ void pnp_score_kernel(const float *, int, int, const double *, int, PnPCam, float, int *, const int *);
+                                 double *, int *, float *, PlanarBatch);
+__global__ void pnp_score_kernel(const float *, int, int, const double *, int, PnPCam, float, int *, const int *,
+                                 PlanarBatch);
 __global__ void pnp_select_kernel(cusift_point *, int, const float *, const float *, const unsigned char *, const double *,
-                                  const int *, int, PnPCam, float, int, float, int *, char *);
+                                  const int *, int, PnPCam, float, int, float, int *, char *, float *, PlanarBatch);
 __global__ void sequence_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                      const cusift_match_row *, int, float, float, float *, unsigned char *, int *, int *,
                                      PlanarBatch, const cusift_match_row *);
+__global__ void sequence_pnp_mark_kernel(const cusift_point *, const unsigned int *, int, const int *,
+                                         const cusift_match_row *, int, float, float, float *, unsigned char *, int *,
+                                         int *, PlanarBatch, const cusift_match_row *);
 __global__ void homography_test_kernel(const float *, int, const float *, int, float, int *);
 template <bool k3D>
 __global__ void rigid_solve_kernel(const float *, int, int *, int, int, unsigned long long, float *, int *, const int *,

@@ -111,8 +111,9 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_compact_kernel(const un
   int total;
   const int rank = keep_rank_256(keep, s_wave, total);
   if (keep) cand[base + rank] = i;  // < n: every keep before this one is a distinct record below i
-  // a pair of a batch with fewer than 8 records reports no candidate, as the pair call answers before it counts
-  if (blockIdx.x == gridDim.x - 1 && tx == 0) head[kPlanarHeadCand] = (nb.count && n < 8) ? 0 : base + total;
+  // a pair of a batch with fewer records than its model fits (8 for H and F, 6 for PnP) reports no candidate, as the
+  // pair call answers before it counts
+  if (blockIdx.x == gridDim.x - 1 && tx == 0) head[kPlanarHeadCand] = (nb.count && n < nb.min_pts) ? 0 : base + total;
 }
 
 // a * b rounded toward zero for a, b that hold fp32 values: the product is exact in fp64; round it to nearest, then step

@@ -30,6 +30,11 @@
 // so one lane's Cholesky needs no pivot search -- 6 square roots and 21 divisions where the epipolar refit runs 288
 // Jacobi rotations.  A pivot that is not > 0 (NaN included) keeps the previous pose and ends the refit.  The partial
 // sums are reduced in a fixed order (wave_tree_sum of sift_ransac.h), so every run gives the same bits.
+// A PAIR LIST (cusift_register_pnp_batch).  The solve, scoring and selection kernels have a pair index, blockIdx.z, and
+// PlanarBatch's strides like every kernel of sift_epipolar.hip: pair p's arrays lie the strides further, it draws from
+// seed + p, and its record count is what sequence_pnp_mark_kernel (sift_sequence.hip, in pnp_mark_kernel's place) left
+// in its head; num_pts is then the capacity of a pair.  One pair is gridDim.z == 1 with every stride 0.  A batch's
+// pnp_select_kernel writes match_error to an array of its own: the records are read only.
 // Kernels use no scratch memory and write with vector stores only.
 #include "sift_epipolar.h"
 
@@ -171,11 +176,16 @@ __global__ void __launch_bounds__(kPnPTile) pnp_solve_kernel(const float *__rest
                                                              const int *__restrict__ head, unsigned long long seed,
                                                              int num_loops, PnPCam cam, int *__restrict__ drawn,
                                                              double *__restrict__ pose, int *__restrict__ counts,
-                                                             float *__restrict__ ccoord) {
+                                                             float *__restrict__ ccoord, PlanarBatch nb) {
   __shared__ double s_m[kPnPRows * kPnPCols * kPnPTile];  // the 11 x 12 system, one column of the array per lane
   __shared__ int s_col[kPnPCols * kPnPTile];              // the column permutation of the pivoting
+  coord = pair_ptr(coord, nb.scratch), cand = pair_ptr(cand, nb.scratch);
+  drawn = pair_ptr(drawn, nb.scratch), pose = pair_ptr(pose, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), ccoord = pair_ptr(ccoord, nb.scratch);
+  head = pair_ptr(head, nb.head);
+  seed += blockIdx.z;  // pair p draws from seed + p, 64-bit and wrapping
   const int tx = threadIdx.x;
-  const int n = min(head[kPlanarHeadCand], num_pts);
+  const int n = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
   if (n < 6) return;  // uniform
   // the launch's threads together: candidate k's coordinates to column k (k < n <= num_pts)
   for (int k = blockIdx.x * kPnPTile + tx; k < n; k += gridDim.x * kPnPTile) {
@@ -305,9 +315,11 @@ __global__ void __launch_bounds__(kPnPTile) pnp_solve_kernel(const float *__rest
 __global__ void __launch_bounds__(kPnPTile) pnp_score_kernel(const float *__restrict__ ccoord, int num_pts, int per_split,
                                                              const double *__restrict__ pose, int num_loops, PnPCam cam,
                                                              float thresh, int *__restrict__ counts,
-                                                             const int *__restrict__ head) {
+                                                             const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[5][kPnPTile];
-  const int n_cand = min(head[kPlanarHeadCand], num_pts);
+  ccoord = pair_ptr(ccoord, nb.scratch), pose = pair_ptr(pose, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
+  const int n_cand = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
   if (n_cand < 6) return;  // uniform; nothing was solved: pnp_select_kernel answers alone
   const int tx = threadIdx.x;
   const int loop = blockIdx.x * kPnPTile + tx;
@@ -405,7 +417,8 @@ __device__ __forceinline__ bool pnp_update(const double (&p)[6], const double (&
 
 // head: words kPlanarHeadCand .. kPlanarHeadLoop as the planar head's (planar_compact_kernel writes the first); then as
 // doubles [R | t] refined at kPnPHeadRt and the winner's at kPnPHeadWin.  Fewer than 6 candidates, or a winner that counts
-// nothing: the counts are 0 and the records stay as they are; the host reports the degenerate answer.
+// nothing: the counts are 0 and the records stay as they are; the host reports the degenerate answer.  errors == NULL:
+// match_error goes into the records; otherwise into errors[] (a batch, whose records stay as they are).
 __global__ void __launch_bounds__(kPnPThreads) pnp_select_kernel(cusift_point *__restrict__ pts, int num_pts,
                                                                  const float *__restrict__ coord,
                                                                  const float *__restrict__ ccoord,
@@ -414,18 +427,25 @@ __global__ void __launch_bounds__(kPnPThreads) pnp_select_kernel(cusift_point *_
                                                                  const int *__restrict__ counts, int num_loops,
                                                                  PnPCam cam, float thresh, int refine_loops,
                                                                  float refine_thresh, int *__restrict__ head,
-                                                                 char *__restrict__ flags) {
+                                                                 char *__restrict__ flags, float *__restrict__ errors,
+                                                                 PlanarBatch nb) {
   __shared__ unsigned long long s_key[kPnPThreads];
   __shared__ double s_part[kPnPThreads / 64][kPnPSums];
   __shared__ double s_sum[kPnPSums];
   __shared__ double s_rt[12];
   __shared__ int s_ok;
   __shared__ int s_cnt[kPnPThreads];
+  pts += (size_t)blockIdx.z * nb.records;
+  coord = pair_ptr(coord, nb.scratch), ccoord = pair_ptr(ccoord, nb.scratch);
+  marks = pair_ptr(marks, nb.scratch), pose = pair_ptr(pose, nb.scratch);
+  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
+  flags += (size_t)blockIdx.z * nb.flags;
+  if (errors) errors += (size_t)blockIdx.z * nb.flags;
   const float *__restrict__ kX = ccoord, *__restrict__ kY = ccoord + num_pts, *__restrict__ kZ = ccoord + 2 * (size_t)num_pts;
   const float *__restrict__ kx2 = ccoord + 3 * (size_t)num_pts, *__restrict__ ky2 = ccoord + 4 * (size_t)num_pts;
   const int tx = threadIdx.x;
   double *dhead = (double *)head;
-  const int n = num_pts;
+  const int n = pair_count(head, num_pts, nb);
   const int n_cand = min(head[kPlanarHeadCand], n);
   int best = 0, best_count = 0;
   if (n_cand >= 6) ransac_winner<true>(counts, num_loops, s_key, best, best_count);  // uniform
@@ -495,7 +515,11 @@ __global__ void __launch_bounds__(kPnPThreads) pnp_select_kernel(cusift_point *_
     pnp_inlier(rt, cam, (double)coord[i], (double)coord[(size_t)num_pts + i], (double)coord[2 * (size_t)num_pts + i],
                (double)coord[3 * (size_t)num_pts + i] - cam.px, (double)coord[4 * (size_t)num_pts + i] - cam.py, rt2, &e2,
                &den, abc);
-    pts[i].match_error = abc[2] > 0.0 ? (float)sqrt(e2 / den) : __builtin_nanf("");
+    const float err = abc[2] > 0.0 ? (float)sqrt(e2 / den) : __builtin_nanf("");
+    if (errors)
+      errors[i] = err;
+    else
+      pts[i].match_error = err;
   }
   int fit = 0;
 #pragma unroll 1  // unrolled 16 times the loop's addresses and masks spill scalar registers

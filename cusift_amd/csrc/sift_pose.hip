@@ -14,7 +14,9 @@
 // F comes from the epipolar head (kEpiHeadF): epipolar_select_kernel left it there, or the staged call uploaded it.  The
 // kernels read the SoA coordinates and the mark bytes of the marking kernel, never the 588-byte records, and write three
 // floats per record.  Both have a pair index, blockIdx.z, and PlanarBatch's strides like every kernel of sift_epipolar.hip;
-// the pose heads of a batch are kPoseHeadBytes apart.  No scratch memory, 64 bytes of LDS, vector stores only.
+// the pose heads of a batch are kPoseHeadBytes apart.  cusift_register_pose_batch launches both with one grid layer per
+// pair of its list behind the batched epipolar selection; its triangulated points go to an array, not into the records.
+// No scratch memory, 64 bytes of LDS, vector stores only.
 // COST (profiles/pose.json): 10 us and 11 us at 4,096 and at 32,768 records alike -- the decomposition's chain of fp64
 // divisions and square roots, which every lane walks once per launch; together 2.6 % and 1.5 % of epipolar_select_kernel.
 #include "sift_epipolar.h"
@@ -185,13 +187,17 @@ __global__ void __launch_bounds__(kPoseThreads) pose_vote_kernel(const float *__
 }
 
 // Reads the four votes, writes coords3D of the records [0, n) of pts and -- workgroup 0 -- the rest of the pose head: as
-// doubles [R | t] at kPoseHeadRt and sigma at kPoseHeadSigma, as int num_front at kPoseHeadFront.
+// doubles [R | t] at kPoseHeadRt and sigma at kPoseHeadSigma, as int num_front at kPoseHeadFront.  xyz == NULL: the points
+// go into the records; otherwise into xyz[pair][num_pts][3] (a batch, whose records stay as they are: a frame may be
+// frame 1 of many pairs).
 __global__ void __launch_bounds__(kPoseThreads) pose_write_kernel(cusift_point *__restrict__ pts,
                                                                   const float *__restrict__ coord,
                                                                   const unsigned char *__restrict__ marks, int num_pts,
                                                                   const int *__restrict__ head, PoseCams cams,
-                                                                  float thresh, int *__restrict__ pose, PlanarBatch nb) {
+                                                                  float thresh, int *__restrict__ pose,
+                                                                  float *__restrict__ xyz, PlanarBatch nb) {
   pts += (size_t)blockIdx.z * nb.records;
+  if (xyz) xyz += 3 * (size_t)blockIdx.z * nb.flags;
   coord = pair_ptr(coord, nb.scratch), marks = pair_ptr(marks, nb.scratch);
   head = pair_ptr(head, nb.head), pose = pair_ptr(pose, kPoseHeadBytes);
   const int tx = threadIdx.x;
@@ -226,7 +232,10 @@ __global__ void __launch_bounds__(kPoseThreads) pose_write_kernel(cusift_point *
                       fabsf(fz) < __builtin_inff() && fz > 0.0f;
     X = keep ? fx : 0.0f, Y = keep ? fy : 0.0f, Z = keep ? fz : 0.0f;
   }
-  if (i < n) pts[i].coords3D[0] = X, pts[i].coords3D[1] = Y, pts[i].coords3D[2] = Z;
+  if (i < n) {
+    float *out = xyz ? xyz + 3 * (size_t)i : pts[i].coords3D;
+    out[0] = X, out[1] = Y, out[2] = Z;
+  }
   if (blockIdx.x == 0 && tx == 0) {
     // X1 = R X2 + t: R = R21^T, t = -R21^T t21 with t21 = sign * u3
     double *dpose = (double *)pose;

@@ -620,7 +620,7 @@ static int pose_enqueue(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, cons
   hipLaunchKernelGGL(pose_vote_kernel, grid, dim3(256), 0, ctx->stream, d_coord, d_marks, num_pts, d_head, st.cams,
                      st.thresh, d_pose, PlanarBatch{});
   hipLaunchKernelGGL(pose_write_kernel, grid, dim3(256), 0, ctx->stream, d_sift, d_coord, d_marks, num_pts, d_head,
-                     st.cams, st.thresh, d_pose, PlanarBatch{});
+                     st.cams, st.thresh, d_pose, (float *)nullptr, PlanarBatch{});
   HIP_TRY(hipMemcpyAsync(st.back, d_pose, kPoseHeadBytes, hipMemcpyDeviceToHost, ctx->stream));
   return CUSIFT_OK;
 }
@@ -700,32 +700,33 @@ static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, 
                      refine_loops, refine_thresh, d_head, d_flags, d_err, nb);
 }
 
-// The four launches behind the marking, over the block at d_block: the candidates' 3-D points against their matches'
-// pixels in the image of `cam` (sift_pnp.hip, which has no batch form).
+// The four launches behind the marking, over the block(s) at d_block: the candidates' 3-D points against their matches'
+// pixels in the image of `cam` (sift_pnp.hip); n_pairs and nb as planar_launch.  One pair is the grid
+// hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64), ...) that tests/test_pnp_sizes.py plans
+// for; a pair list adds the layer of the pairs to every grid.
 static void pnp_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh, int refine_loops,
                        float refine_thresh, uint64_t seed, PnPCam cam, char *d_block, const RansacBlock &b, int *d_head,
-                       char *d_flags) {
+                       char *d_flags, float *d_err, int n_pairs, PlanarBatch nb) {
   const float *d_coord = at<float>(d_block, b.coord);
   float *d_ccoord = at<float>(d_block, b.ccoord);
   const unsigned char *d_marks = at<unsigned char>(d_block, b.marks);
   double *d_pose = at<double>(d_block, b.model);
   int *d_counts = at<int>(d_block, b.counts), *d_cand = at<int>(d_block, b.cand);
-  // scoring: as epipolar_launch, over the candidates of the one pair
-  constexpr int n_pairs = 1;
+  // scoring: as epipolar_launch, over the candidates of every pair
   const int blocks = idiv_up(num_pts, 256), loop_blocks = idiv_up(num_loops, 64);
   int cand_per_split;
   const int splits = score_splits(ctx, num_pts, (long)loop_blocks * n_pairs, 8, 64, true, &cand_per_split);
-  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_marks, num_pts,
-                     (const int *)at<int>(d_block, b.blocks), d_cand, d_head, PlanarBatch{});
-  hipLaunchKernelGGL(pnp_solve_kernel, dim3(loop_blocks), dim3(64), 0, ctx->stream, d_coord, num_pts,
+  hipLaunchKernelGGL(planar_compact_kernel, dim3(blocks, 1, n_pairs), dim3(256), 0, ctx->stream, d_marks, num_pts,
+                     (const int *)at<int>(d_block, b.blocks), d_cand, d_head, nb);
+  hipLaunchKernelGGL(pnp_solve_kernel, dim3(loop_blocks, 1, n_pairs), dim3(64), 0, ctx->stream, d_coord, num_pts,
                      (const int *)d_cand, (const int *)d_head, (unsigned long long)seed, num_loops, cam,
-                     at<int>(d_block, b.idx), d_pose, d_counts, d_ccoord);
-  hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64), 0, ctx->stream, (const float *)d_ccoord,
-                     num_pts, cand_per_split, (const double *)d_pose, num_loops, cam, thresh, d_counts,
-                     (const int *)d_head);
-  hipLaunchKernelGGL(pnp_select_kernel, dim3(1), dim3(256), 0, ctx->stream, d_sift, num_pts, d_coord,
+                     at<int>(d_block, b.idx), d_pose, d_counts, d_ccoord, nb);
+  hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits, n_pairs), dim3(64), 0, ctx->stream,
+                     (const float *)d_ccoord, num_pts, cand_per_split, (const double *)d_pose, num_loops, cam, thresh,
+                     d_counts, (const int *)d_head, nb);
+  hipLaunchKernelGGL(pnp_select_kernel, dim3(1, 1, n_pairs), dim3(256), 0, ctx->stream, d_sift, num_pts, d_coord,
                      (const float *)d_ccoord, d_marks, (const double *)d_pose, (const int *)d_counts, num_loops, cam,
-                     thresh, refine_loops, refine_thresh, d_head, d_flags);
+                     thresh, refine_loops, refine_thresh, d_head, d_flags, d_err, nb);
 }
 
 // The marking, the model's four launches and the one read-back; the arguments are checked.  d_cross as mark_launch's.
@@ -759,7 +760,7 @@ static int ransac_run(cusift_ctx *ctx, const RansacModel &m, cusift_point *d_sif
                     base + flag_off, nullptr, 1, PlanarBatch{});
   else
     pnp_launch(ctx, d_sift, num_pts, num_loops, thresh, refine_loops, refine_thresh, seed, *cam, d_block, b, (int *)base,
-               base + flag_off);
+               base + flag_off, nullptr, 1, PlanarBatch{});
   if (pose)
     TRY(pose_enqueue(ctx, d_sift, num_pts, at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
                      (const int *)base, at<int>(base, pose_off), *pose));
@@ -1115,6 +1116,7 @@ extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point 
   cusift_match_row *d_rows_back = ctx->cross_check ? at<cusift_match_row>(base, back_off) : nullptr;
   PlanarBatch nb;
   nb.records = 0, nb.scratch = b.bytes, nb.head = kPlanarHeadBytes, nb.flags = M, nb.count = 1;
+  nb.min_pts = kHomography.min_pts;
   const int *d_pairs = nullptr;
   TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, d_rows_back));
   hipLaunchKernelGGL(sequence_mark_kernel, dim3(idiv_up(max_pts, 256), 1, n_pairs), dim3(256), 0, ctx->stream, d_points,
@@ -1144,4 +1146,198 @@ extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point 
       memcpy(h_match_error + p * M, back.data() + err_off + sizeof(float) * p * M, sizeof(float) * n);
   }
   return CUSIFT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// epipolar, pose and PnP registration of a pair list (sift_sequence.hip, sift_epipolar.hip, sift_pose.hip, sift_pnp.hip):
+// the batch counterpart of ransac_run, told apart by the model -- one read-back
+// ------------------------------------------------------------------------------------------------
+// What a pair-list call returns besides RansacOut's arrays ([P] entries each), and what its model takes: the pose stage's
+// outputs and cameras (pose_cams != NULL: cusift_register_pose_batch), the matches' camera (kPnP)
+struct BatchExtra {
+  float *h_match_error;
+  const PoseCams *pose_cams;
+  PoseOut pose;
+  float *h_points3d;
+  const PnPCam *cam;
+};
+
+// every refusal that the pair-list calls share, before anything is enqueued or written
+static int batch_check(const char *who, const cusift_point *d_points, int n_images, int max_pts, const int *h_pairs,
+                       int n_pairs, int distance, int rule, float lo, float hi, int num_loops, float thresh,
+                       int refine_loops, float refine_thresh, const RansacOut &o) {
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, who));
+  TRY(precheck(who, d_points, n_images > 0 ? max_pts : 0, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh,
+               o));
+  return check_distance(who, distance);
+}
+
+// Pair p's slice of the outputs.
+static RansacOut batch_pair_out(const RansacModel &m, const RansacOut &o, size_t p) {
+  return RansacOut{(char *)o.h_model + m.elem * m.reported * p, (char *)o.h_ransac + m.elem * m.reported * p,
+                   o.num_candidates + p, o.num_matches + p, o.num_fit + p, o.best_loop ? o.best_loop + p : nullptr,
+                   nullptr, nullptr, nullptr, nullptr};
+}
+
+// The matcher, the marking, the model's four launches, the pose stage and the one read-back, every pair of the list in
+// the same launches; the arguments are checked, n_pairs >= 1.
+static int ransac_batch_run(cusift_ctx *ctx, const RansacModel &m, const cusift_point *d_points,
+                            const unsigned int *d_counters, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                            int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                            float refine_thresh, uint64_t seed, const RansacOut &o, const BatchExtra &x) {
+  const size_t P = (size_t)n_pairs, M = (size_t)max_pts;
+  const bool pose = x.pose_cams != nullptr;
+  if (max_pts == 0) {  // every frame is empty, known from the arguments alone
+    for (size_t p = 0; p < P; ++p) {
+      ransac_nothing(m, 0, num_loops, batch_pair_out(m, o, p));
+      if (!pose) continue;
+      memcpy(x.pose.h_rt + 12 * p, kIdentRtD, sizeof(kIdentRtD));
+      x.pose.num_front[p] = 0;
+      if (x.pose.h_votes) memset(x.pose.h_votes + 4 * p, 0, sizeof(int) * 4);
+      if (x.pose.h_sigma) memset(x.pose.h_sigma + 3 * p, 0, sizeof(double) * 3);
+    }
+    return CUSIFT_OK;
+  }
+  // [heads | pose heads | flags | errors | points] is what travels back, in one copy; behind it what stays on the device:
+  // one RansacBlock per pair, then the match rows and -- with the cross-check (cusift_ctx_set_cross_check) -- the
+  // matcher's back rows
+  const RansacBlock b(m, max_pts, num_loops);
+  ScratchLayout s;
+  s.take(m.head_bytes * P);  // the heads, at 0
+  const size_t pose_off = pose ? s.take(kPoseHeadBytes * P) : s.size;
+  const size_t flag_off = s.take(P * M);
+  const size_t err_off = s.take(sizeof(float) * P * M);
+  const size_t xyz_off = pose ? s.take(sizeof(float) * 3 * P * M) : s.size;
+  const size_t block_off = s.take(b.bytes * P);
+  const size_t row_off = s.take(sizeof(cusift_match_row) * P * M);
+  const size_t back_off = ctx->cross_check ? s.take(sizeof(cusift_match_row) * P * M) : 0;
+  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
+  char *base = ctx->register_scratch, *d_block = base + block_off;
+  cusift_match_row *d_rows = at<cusift_match_row>(base, row_off);
+  cusift_match_row *d_rows_back = ctx->cross_check ? at<cusift_match_row>(base, back_off) : nullptr;
+  PlanarBatch nb;
+  nb.records = 0, nb.scratch = b.bytes, nb.head = m.head_bytes, nb.flags = M, nb.count = 1, nb.min_pts = m.min_pts;
+  const int *d_pairs = nullptr;
+  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, d_rows_back));
+  const dim3 mark_grid(idiv_up(max_pts, 256), 1, n_pairs);
+  hipLaunchKernelGGL(m.launch == kPnPLaunch ? sequence_pnp_mark_kernel : sequence_mark_kernel, mark_grid, dim3(256), 0,
+                     ctx->stream, d_points, d_counters, max_pts, d_pairs, (const cusift_match_row *)d_rows, rule,
+                     mark_thresh(rule, lo), mark_thresh(rule, hi), at<float>(d_block, b.coord),
+                     at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), (int *)base, nb,
+                     (const cusift_match_row *)d_rows_back);
+  if (m.launch == kPnPLaunch)
+    pnp_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, *x.cam, d_block, b,
+               (int *)base, base + flag_off, at<float>(base, err_off), n_pairs, nb);
+  else
+    epipolar_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
+                    base + flag_off, at<float>(base, err_off), n_pairs, nb);
+  if (pose) {  // behind the selection, at refine_thresh as in the pair call; the points go to an array of their own
+    HIP_TRY(hipMemsetAsync(base + pose_off, 0, kPoseHeadBytes * P, ctx->stream));
+    hipLaunchKernelGGL(pose_vote_kernel, mark_grid, dim3(256), 0, ctx->stream, (const float *)at<float>(d_block, b.coord),
+                       (const unsigned char *)at<unsigned char>(d_block, b.marks), max_pts, (const int *)base,
+                       *x.pose_cams, refine_thresh, at<int>(base, pose_off), nb);
+    hipLaunchKernelGGL(pose_write_kernel, mark_grid, dim3(256), 0, ctx->stream, (cusift_point *)nullptr,
+                       (const float *)at<float>(d_block, b.coord),
+                       (const unsigned char *)at<unsigned char>(d_block, b.marks), max_pts, (const int *)base,
+                       *x.pose_cams, refine_thresh, at<int>(base, pose_off), at<float>(base, xyz_off), nb);
+  }
+  TRY(check_launch(m.label));
+  // the one blocking read-back
+  size_t back_bytes = pose ? pose_off + kPoseHeadBytes * P : m.head_bytes * P;
+  if (o.h_inliers) back_bytes = flag_off + P * M;
+  if (x.h_match_error) back_bytes = err_off + sizeof(float) * P * M;
+  if (pose && x.h_points3d) back_bytes = xyz_off + sizeof(float) * 3 * P * M;
+  std::vector<char> back(back_bytes);
+  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (size_t p = 0; p < P; ++p) {  // the kernels decided every pair: copies, and the model's answer where nothing was fitted
+    const char *head = back.data() + m.head_bytes * p;
+    const int n_cand = head_int(head, kPlanarHeadCand);
+    const size_t n = (size_t)std::min(std::max(head_int(head, kPlanarHeadCount), 0), max_pts);  // records of frame a
+    const RansacOut one = batch_pair_out(m, o, p);
+    // a winner that counts no point (needs_support) is nothing to fit either, as ransac_run decides after its read-back
+    const bool fitted = n_cand >= m.min_pts && !(m.needs_support && head_int(head, kPlanarHeadMatches) < 1);
+    if (fitted) {
+      memcpy(one.h_model, head + m.elem * m.head_model, m.elem * m.reported);
+      memcpy(one.h_ransac, head + m.elem * m.head_ransac, m.elem * m.reported);
+      *one.num_matches = head_int(head, kPlanarHeadMatches), *one.num_fit = head_int(head, kPlanarHeadFit);
+      if (one.best_loop) *one.best_loop = head_int(head, kPlanarHeadLoop);
+    } else {
+      ransac_nothing(m, 0, num_loops, one);
+    }
+    *one.num_candidates = n_cand;
+    if (o.h_inliers) memcpy(o.h_inliers + p * M, back.data() + flag_off + p * M, n);
+    // a pair without a fit has no error, as the pair call leaves match_error alone then
+    if (x.h_match_error && fitted)
+      memcpy(x.h_match_error + p * M, back.data() + err_off + sizeof(float) * p * M, sizeof(float) * n);
+    if (!pose) continue;
+    const char *ph = back.data() + pose_off + kPoseHeadBytes * p;
+    memcpy(x.pose.h_rt + 12 * p, ph + sizeof(double) * kPoseHeadRt, sizeof(double) * 12);
+    x.pose.num_front[p] = head_int(ph, kPoseHeadFront);
+    if (x.pose.h_votes) memcpy(x.pose.h_votes + 4 * p, ph + sizeof(int) * kPoseHeadVotes, sizeof(int) * 4);
+    if (x.pose.h_sigma) memcpy(x.pose.h_sigma + 3 * p, ph + sizeof(double) * kPoseHeadSigma, sizeof(double) * 3);
+    if (x.h_points3d)
+      memcpy(x.h_points3d + 3 * p * M, back.data() + xyz_off + sizeof(float) * 3 * p * M, sizeof(float) * 3 * n);
+  }
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_register_epipolar_batch(cusift_ctx *ctx, const cusift_point *d_points,
+                                              const unsigned int *d_counters, int n_images, int max_pts,
+                                              const int *h_pairs, int n_pairs, int distance, int rule, float lo, float hi,
+                                              int num_loops, float thresh, int refine_loops, float refine_thresh,
+                                              uint64_t seed, double *h_fundamental, double *h_ransac,
+                                              int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
+                                              char *h_inliers, float *h_match_error) {
+  TRY(enter(ctx));
+  const RansacOut o{h_fundamental, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
+                    h_inliers,     nullptr,  nullptr,          nullptr};
+  TRY(batch_check("RegisterEpipolarBatch", d_points, n_images, max_pts, h_pairs, n_pairs, distance, rule, lo, hi,
+                  num_loops, thresh, refine_loops, refine_thresh, o));
+  if (n_pairs == 0) return CUSIFT_OK;
+  const BatchExtra x{h_match_error, nullptr, PoseOut{}, nullptr, nullptr};
+  return ransac_batch_run(ctx, kFundamental, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, rule, lo, hi,
+                          num_loops, thresh, refine_loops, refine_thresh, seed, o, x);
+}
+
+extern "C" int cusift_register_pose_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                          int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                          int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                          float refine_thresh, uint64_t seed, const cusift_camera *camera1,
+                                          const cusift_camera *camera2, double *h_fundamental, double *h_ransac,
+                                          int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
+                                          char *h_inliers, float *h_match_error, double *h_rt, int *h_num_front,
+                                          int *h_votes, double *h_sigma, float *h_points3d) {
+  TRY(enter(ctx));
+  const RansacOut o{h_fundamental, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
+                    h_inliers,     nullptr,  nullptr,          nullptr};
+  const PoseOut po{h_rt, h_num_front, h_votes, h_sigma};
+  TRY(pose_check("RegisterPoseBatch", camera1, camera2, po));
+  TRY(batch_check("RegisterPoseBatch", d_points, n_images, max_pts, h_pairs, n_pairs, distance, rule, lo, hi, num_loops,
+                  thresh, refine_loops, refine_thresh, o));
+  if (n_pairs == 0) return CUSIFT_OK;
+  const PoseStage st = pose_stage(camera1, camera2, refine_thresh, po);
+  const BatchExtra x{h_match_error, &st.cams, po, h_points3d, nullptr};
+  return ransac_batch_run(ctx, kFundamental, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, rule, lo, hi,
+                          num_loops, thresh, refine_loops, refine_thresh, seed, o, x);
+}
+
+extern "C" int cusift_register_pnp_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                         int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                         int rule, float lo, float hi, const cusift_camera *camera2, int num_loops,
+                                         float thresh, int refine_loops, float refine_thresh, uint64_t seed, double *h_rt,
+                                         double *h_ransac, int *h_num_candidates, int *h_num_matches, int *h_num_fit,
+                                         int *h_best_loop, char *h_inliers, float *h_match_error) {
+  TRY(enter(ctx));
+  const RansacOut o{h_rt, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop, h_inliers, nullptr, nullptr,
+                    nullptr};
+  if (!camera2) return fail(CUSIFT_ERR_INVALID, "RegisterPnPBatch: NULL camera");
+  TRY(batch_check("RegisterPnPBatch", d_points, n_images, max_pts, h_pairs, n_pairs, distance, rule, lo, hi, num_loops,
+                  thresh, refine_loops, refine_thresh, o));
+  TRY(check_pinhole(camera2, "RegisterPnPBatch"));
+  if (n_pairs == 0) return CUSIFT_OK;
+  const PnPCam cam = pnp_cam(camera2);
+  const BatchExtra x{h_match_error, nullptr, PoseOut{}, nullptr, &cam};
+  return ransac_batch_run(ctx, kPnP, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, rule, lo, hi, num_loops,
+                          thresh, refine_loops, refine_thresh, seed, o, x);
 }

@@ -28,8 +28,14 @@
 // = n2.  A pair whose frame 2 is empty has no row (the matcher wrote none): no candidate, nothing read.  The records are
 // never written.
 //
+// THE OTHER MARKINGS.  cusift_register_epipolar_batch and cusift_register_pose_batch launch sequence_mark_kernel as it is:
+// the epipolar model takes the same coordinate rows and the same candidates.  cusift_register_pnp_batch launches
+// sequence_pnp_mark_kernel, the same reading -- match rows, the partner's coords2D, back rows, the record count into the
+// head -- with pnp_mark_kernel's (sift_pnp.hip) five coordinate rows [X | Y | Z | x2 | y2] and its depth condition: three
+// finite coords3D floats in frame 1's record and Z != 0.  Both kernels are one device function, sequence_mark<kPnP>.
+//
 // THE CROSS-CHECK (cusift_ctx_set_cross_check).  Both kernels take rows_back[pair][max_pts], the column side that
-// cusift_match_batch_mutual's kernels leave (NULL = off): record i stays only if back row `match` names i.  The matcher
+// cusift_match_batch_mutual's kernels leave (NULL = off; the markings alike): record i stays only if back row `match` names i.  The matcher
 // writes back rows 0 .. n2 - 1 of a pair with n1 > 0 and n2 > 0 and none otherwise; a back row is read only for a record
 // i < n1 with 0 <= match < n2, inside the n2 > 0 branch, so no unwritten row is ever read.  In a self pair (a, a) every
 // record is its own best in both directions.
@@ -82,14 +88,17 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
   if (tx == 0) sel_count[pair] = base;
 }
 
-// coord [pair][4][max_pts], marks [pair][max_pts], block_counts [pair][ceil(max_pts / 256)] in the pairs' scratch blocks
-// (nb.scratch bytes apart); head[kPlanarHeadCount] of pair p (nb.head bytes apart) = its record count
-__global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
-    const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
-    const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, int rule, float lo, float hi,
-    float *__restrict__ coord, unsigned char *__restrict__ marks, int *__restrict__ block_counts, int *__restrict__ head,
-    PlanarBatch nb, const cusift_match_row *__restrict__ rows_back) {
-  __shared__ int s_wave[kSequenceSelectThreads / 64];
+// The marking of one record of pair blockIdx.z, shared by the two kernels below.  kPnP == false: the coordinate rows are
+// [x1 | y1 | x2 | y2].  kPnP == true: [X | Y | Z | x2 | y2] with (X, Y, Z) = coords3D of frame 1's record, and a
+// candidate also needs pnp_mark_kernel's depth condition -- three finite floats, Z != 0 -- in place of finite x1, y1.
+template <bool kPnP>
+__device__ __forceinline__ void sequence_mark(const cusift_point *__restrict__ points,
+                                              const unsigned int *__restrict__ counters, int max_pts,
+                                              const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows,
+                                              int rule, float lo, float hi, float *__restrict__ coord,
+                                              unsigned char *__restrict__ marks, int *__restrict__ block_counts,
+                                              int *__restrict__ head, PlanarBatch nb,
+                                              const cusift_match_row *__restrict__ rows_back, int *s_wave) {
   const int tx = threadIdx.x;
   const int pair = blockIdx.z;
   const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
@@ -103,6 +112,8 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
   bool cand = false;
   if (i < n1) {
     const float x1 = sift1[i].coords2D[0], y1 = sift1[i].coords2D[1];
+    float X = 0.0f, Y = 0.0f, Z = 0.0f;
+    if (kPnP) X = sift1[i].coords3D[0], Y = sift1[i].coords3D[1], Z = sift1[i].coords3D[2];
     float x2 = 0.0f, y2 = 0.0f;
     unsigned char mk = 0;
     if (n2 > 0) {
@@ -112,7 +123,8 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
       const bool valid = m >= 0 && m < n2;
       const cusift_point *q = sift2 + (valid ? m : 0);  // the partner cusift_match takes the position from
       x2 = q->coords2D[0], y2 = q->coords2D[1];
-      const bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
+      bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
+      if (kPnP) finite = finite && planar_finite(X) && planar_finite(Y) && planar_finite(Z) && Z != 0.0f;
       bool mutual = false;
       if (rows_back) {  // the cross-check: back row m was written (i < n1, m < n2)
         const cusift_match_row *back = rows_back + (size_t)pair * max_pts + (valid ? m : 0);
@@ -121,10 +133,18 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
       mk = planar_marks(rule, score, amb, lo, hi, finite, valid, rows_back != nullptr, mutual);
       cand = mk & 1;
     }
-    coord[i] = x1;
-    coord[i + max_pts] = y1;
-    coord[i + 2 * (size_t)max_pts] = x2;
-    coord[i + 3 * (size_t)max_pts] = y2;
+    if (kPnP) {
+      coord[i] = X;
+      coord[i + max_pts] = Y;
+      coord[i + 2 * (size_t)max_pts] = Z;
+      coord[i + 3 * (size_t)max_pts] = x2;
+      coord[i + 4 * (size_t)max_pts] = y2;
+    } else {
+      coord[i] = x1;
+      coord[i + max_pts] = y1;
+      coord[i + 2 * (size_t)max_pts] = x2;
+      coord[i + 3 * (size_t)max_pts] = y2;
+    }
     marks[i] = mk;
   }
   const int keeps = keep_count_256(cand, s_wave);
@@ -132,6 +152,29 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
     block_counts[blockIdx.x] = keeps;
     if (blockIdx.x == 0) head[kPlanarHeadCount] = n1;
   }
+}
+
+// coord [pair][4][max_pts], marks [pair][max_pts], block_counts [pair][ceil(max_pts / 256)] in the pairs' scratch blocks
+// (nb.scratch bytes apart); head[kPlanarHeadCount] of pair p (nb.head bytes apart) = its record count
+__global__ void __launch_bounds__(kSequenceSelectThreads) sequence_mark_kernel(
+    const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
+    const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, int rule, float lo, float hi,
+    float *__restrict__ coord, unsigned char *__restrict__ marks, int *__restrict__ block_counts, int *__restrict__ head,
+    PlanarBatch nb, const cusift_match_row *__restrict__ rows_back) {
+  __shared__ int s_wave[kSequenceSelectThreads / 64];
+  sequence_mark<false>(points, counters, max_pts, pairs, rows, rule, lo, hi, coord, marks, block_counts, head, nb,
+                       rows_back, s_wave);
+}
+
+// the same for cusift_register_pnp_batch: coord [pair][5][max_pts] = [X | Y | Z | x2 | y2], the depth condition
+__global__ void __launch_bounds__(kSequenceSelectThreads) sequence_pnp_mark_kernel(
+    const cusift_point *__restrict__ points, const unsigned int *__restrict__ counters, int max_pts,
+    const int *__restrict__ pairs, const cusift_match_row *__restrict__ rows, int rule, float lo, float hi,
+    float *__restrict__ coord, unsigned char *__restrict__ marks, int *__restrict__ block_counts, int *__restrict__ head,
+    PlanarBatch nb, const cusift_match_row *__restrict__ rows_back) {
+  __shared__ int s_wave[kSequenceSelectThreads / 64];
+  sequence_mark<true>(points, counters, max_pts, pairs, rows, rule, lo, hi, coord, marks, block_counts, head, nb,
+                      rows_back, s_wave);
 }
 
 }  // namespace cusift

@@ -155,10 +155,12 @@ struct RigidBatch {
 // between their device-only blocks (samples, hypotheses, counts, coordinates, candidates, marks, block counts); head:
 // bytes between their result heads; flags: entries between their inlier flags and between their match errors.
 // count != 0: the kernels' num_pts is the CAPACITY of a pair (the stride of its coordinate rows) and its number of
-// points is word kPlanarHeadCount of its head, written by sequence_mark_kernel (as RigidBatch::count).
+// points is word kPlanarHeadCount of its head, written by the sequence marking (as RigidBatch::count); min_pts is then
+// the fewest records the pair's model fits -- 8 for H and F, 6 for PnP -- below which planar_compact_kernel reports no
+// candidate, as the pair call answers before it counts.
 struct PlanarBatch {
   size_t records, scratch, head, flags;
-  int count;
+  int count, min_pts;
 };
 // A planar result head, in 4-byte words: H[9] (refined) and R[9] (the winner) as float, then as int the candidates, the
 // winner's count, num_fit, the winning loop and -- batched -- the pair's record count.
@@ -181,7 +183,7 @@ struct PoseCams {
 // A PnP result head (sift_pnp.hip): the int words kPlanarHeadCand .. kPlanarHeadLoop where the planar head has them, then,
 // counted in doubles, [R | t] refined and the winner's, twelve each.
 constexpr int kPnPHeadRt = 16, kPnPHeadWin = 32;
-constexpr size_t kPnPHeadBytes = 384;
+constexpr size_t kPnPHeadBytes = 384;                 // between the heads of a batch
 // The intrinsics of the matches' image as the PnP kernels take them: px = cx - origin, py = cy - origin, widened first.
 struct PnPCam {
   double fx, fy, px, py;

@@ -439,8 +439,8 @@ int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_i
 
 /* The cross-check of the registrations, a setting of the context (0 = off, the default; 1 = on; anything else:
  * CUSIFT_ERR_INVALID, the setting unchanged).  It affects cusift_register_planar, cusift_register_rgbd,
- * cusift_register_planar_batch, cusift_register_rgbd_batch, cusift_register_epipolar, cusift_register_pose and
- * cusift_register_pnp and nothing else; with 0 they enqueue the launches and
+ * cusift_register_planar_batch, cusift_register_rgbd_batch, cusift_register_epipolar, cusift_register_pose,
+ * cusift_register_pnp and their pair-list forms (cusift_register_epipolar_batch, _pose_batch, _pnp_batch) and nothing else; with 0 they enqueue the launches and
  * return the bytes they always did.  With 1, record i of frame 1 takes part only if it is MUTUAL: its match m lies in
  * [0, n2) and the column side's best for record m of frame 2 is i -- the column side exactly as cusift_match_mutual /
  * cusift_match_batch_mutual define it, so an exactly tied best keeps the lowest record of frame 1.  Every many-to-one
@@ -583,6 +583,92 @@ int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point *d_points,
                                  int *h_num_fit, int *h_best_loop /* may be NULL */,
                                  char *h_inliers /* [n_pairs][max_pts], may be NULL */,
                                  float *h_match_error /* [n_pairs][max_pts], may be NULL */);
+
+/* ---- the pair-list forms of the fundamental matrix, the calibrated pose and the absolute pose ---------------------- */
+/* cusift_register_epipolar, cusift_register_pose and cusift_register_pnp for every pair of a list, with the contract of
+ * cusift_register_planar_batch: the extractor's batch and a pair list in, one model per pair out, in a number of launches
+ * that does not depend on n_pairs, with no host decision between the stages and no count read back.  The records per
+ * frame are min(d_counters[frame], max_pts), read on the device (d_counters == NULL: max_pts each).  A frame may appear in
+ * any number of pairs, on either side; (a, a) is legal.  What the three calls share:
+ * SEED: pair p draws from seed + p (64-bit, wrapping).
+ * STAGES: cusift_match_batch into rows in the context's scratch; a marking kernel that builds each pair's coordinates and
+ * candidates from its rows, from frame a's records and from coords2D of their partners in frame b (the value cusift_match
+ * puts into match_xpos / match_ypos); then the compaction, the drawing solver, the scoring and the selection + refit of
+ * the pair call with one grid layer per pair.
+ * THE RECORDS ARE NEVER WRITTEN.  match_error of every record of frame a goes to h_match_error ([n_pairs][max_pts], may
+ * be NULL) and the winner's inlier flags to h_inliers ([n_pairs][max_pts], may be NULL): the first count_a entries of
+ * pair p's block, the rest of a block is not written.
+ * EQUALITY: every output of pair p has the bits of the staged route -- pair p's row of cusift_match_batch scattered into a
+ * copy of frame a's records (score, ambiguity, match, match_xpos / match_ypos = the partner's coords2D), then
+ * cusift_estimate_fundamental, cusift_estimate_pose on that F (thresh = refine_thresh), or cusift_estimate_pnp on the
+ * copy, with count_a, count_b and seed + p; h_match_error is the match_error that call writes and h_points3d the coords3D
+ * that cusift_estimate_pose writes.  Where the rows equal what cusift_match writes (cusift_match_batch documents the one
+ * licence to differ: exactly tied best scores) these are the bits of cusift_register_epipolar, cusift_register_pose or
+ * cusift_register_pnp(frame a, frame b, ..., seed + p).
+ * DEGENERATE PAIRS are decided on the device, disturb no other pair and answer what the pair call answers: nine zeros in
+ * both matrices (F), [I | 0], zero votes and zeros in h_points3d (pose), [I | 0] in both poses (PnP).  Every count is 0,
+ * the flags are 0 and the pair's block of h_match_error is not written (the pair call leaves match_error alone).
+ * h_num_candidates[p] = 0 when frame a has fewer records than the model's minimum -- 8 for F and the pose, 6 for PnP --
+ * and the counted number otherwise (0 when frame b is empty: no row exists).  For PnP a winner that counts no point is
+ * nothing to fit either, as in cusift_estimate_pnp: [I | 0], counts 0, h_num_candidates[p] as counted.
+ * CROSS-CHECK: cusift_ctx_set_cross_check is honoured as in cusift_register_planar_batch -- the column side comes from
+ * cusift_match_batch_mutual's back rows in the context's scratch, a record that is not mutual is no candidate, and pair p
+ * has the bits of the pair call with the setting on and seed + p.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of the pair call -- a NULL required output (the
+ * two models and the three counts; for the pose also h_rt, h_num_front and camera1; for PnP camera2), fx or fy 0 or not
+ * finite, cx / cy / origin not finite, num_loops outside [1, 2^24], thresh or refine_thresh not > 0, a NaN lo / hi, an
+ * unknown rule or distance, refine_loops < 0, missing buffers -- and: a pair index outside [0, n_images), n_pairs or
+ * n_images outside [0, 65535], max_pts outside [0, 2^20], a NULL h_pairs with n_pairs > 0.  n_pairs == 0: CUSIFT_OK,
+ * nothing enqueued, nothing written.  max_pts == 0: every pair is degenerate, answered from the arguments alone.  Scratch
+ * lives in the context and grows on demand.
+ * Blocking: ONE stream synchronisation, at the one read-back.
+ *
+ * cusift_register_epipolar_batch: pair p = (a, b) gives x_b^T F x_a = 0, h_fundamental[9 p .. 9 p + 8] (refined) and
+ * h_ransac[9 p .. 9 p + 8] (the winner), as cusift_estimate_fundamental defines them. */
+int cusift_register_epipolar_batch(cusift_ctx *ctx, const cusift_point *d_points,
+                                   const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                                   const int *h_pairs /* [n_pairs][2]: (frame a, frame b) */, int n_pairs, int distance,
+                                   int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                   float refine_thresh, uint64_t seed, double *h_fundamental /* [n_pairs][9] */,
+                                   double *h_ransac /* [n_pairs][9] */, int *h_num_candidates, int *h_num_matches,
+                                   int *h_num_fit, int *h_best_loop /* may be NULL */,
+                                   char *h_inliers /* [n_pairs][max_pts], may be NULL */,
+                                   float *h_match_error /* [n_pairs][max_pts], may be NULL */);
+
+/* cusift_register_epipolar_batch followed, in the same call and before the one read-back, by the pose stage of
+ * cusift_register_pose for every pair: one pair of cameras serves every pair of the list (camera2 == NULL: camera1 for both
+ * views).  h_rt[12 p .. 12 p + 11] = [R | t] of pair p with |t| = 1, h_num_front[p], h_votes ([n_pairs][4], may be NULL)
+ * and h_sigma ([n_pairs][3], may be NULL) as cusift_estimate_pose defines them.  The records are const and a frame may be
+ * frame a of many pairs, so the triangulated points do not go into coords3D: h_points3d ([n_pairs][max_pts][3], may be
+ * NULL) receives the first count_a rows of pair p's block, the values cusift_estimate_pose writes into coords3D. */
+int cusift_register_pose_batch(cusift_ctx *ctx, const cusift_point *d_points,
+                               const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                               const int *h_pairs /* [n_pairs][2]: (frame a, frame b) */, int n_pairs, int distance,
+                               int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                               float refine_thresh, uint64_t seed, const cusift_camera *camera1,
+                               const cusift_camera *camera2 /* may be NULL */, double *h_fundamental /* [n_pairs][9] */,
+                               double *h_ransac /* [n_pairs][9] */, int *h_num_candidates, int *h_num_matches,
+                               int *h_num_fit, int *h_best_loop /* may be NULL */,
+                               char *h_inliers /* [n_pairs][max_pts], may be NULL */,
+                               float *h_match_error /* [n_pairs][max_pts], may be NULL */,
+                               double *h_rt /* [n_pairs][12] */, int *h_num_front, int *h_votes /* may be NULL */,
+                               double *h_sigma /* may be NULL */,
+                               float *h_points3d /* [n_pairs][max_pts][3], may be NULL */);
+
+/* cusift_register_pnp for every pair of a list: coords3D of frame a's records -- from cusift_lift_depth over the batch, or
+ * the caller's -- against the pixels of their matches in frame b, whose camera is camera2 for every pair.  coords3D is
+ * read and never written.  h_rt[12 p .. 12 p + 11] (refined) and h_ransac[12 p .. 12 p + 11] (the winner) map frame b
+ * into frame a, X_a = R X_b + t, in the unit coords3D is in: metric after a depth lift.  Frames of 6 and 7 records are
+ * fitted, as in the pair call. */
+int cusift_register_pnp_batch(cusift_ctx *ctx, const cusift_point *d_points,
+                              const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                              const int *h_pairs /* [n_pairs][2]: (frame a, frame b) */, int n_pairs, int distance,
+                              int rule, float lo, float hi, const cusift_camera *camera2, int num_loops, float thresh,
+                              int refine_loops, float refine_thresh, uint64_t seed, double *h_rt /* [n_pairs][12] */,
+                              double *h_ransac /* [n_pairs][12] */, int *h_num_candidates, int *h_num_matches,
+                              int *h_num_fit, int *h_best_loop /* may be NULL */,
+                              char *h_inliers /* [n_pairs][max_pts], may be NULL */,
+                              float *h_match_error /* [n_pairs][max_pts], may be NULL */);
 
 #ifdef __cplusplus
 }

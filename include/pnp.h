@@ -17,6 +17,7 @@
 
 #include "cuSIFT.h"
 #include "cusift_amd_extras.h"
+#include "epipolar.h"
 
 // The pose over the device records of `data`, which carry match fields and coords3D.  The candidates are those of `rule`
 // (as EstimateFundamental's) with a finite coords3D whose z is not 0; *numMatches of them lie within `thresh` px of the
@@ -51,6 +52,46 @@ inline double RegisterPnP(SiftData &data1, SiftData &data2, const cusift_camera 
                                minScore, maxAmbiguity, camera2, numLoops, thresh, refineLoops, refineThresh, seed, Rt,
                                ransac ? ransac : winner, numCandidates ? numCandidates : &candidates, numMatches, numFit,
                                nullptr, nullptr, nullptr, nullptr, nullptr));
+  return timer.read();
+}
+
+// RegisterPnP for a whole sequence in one call (cusift_register_pnp_batch): pair k = (a, b) of `pairs` gives
+// Rts[12 k .. 12 k + 11] = [R | t] with X_a = R X_b + t in the unit of frame a's coords3D -- metric after a depth lift, so
+// the poses of consecutive pairs compose into a trajectory.  camera2 is the camera of frame b of every pair.  coords3D of
+// the frames' device records is read and not written, and neither is anything else of them.  An empty `pairs` means
+// (i, i + 1) for every consecutive frame; pair k draws from seed + k and has the bits RegisterPnP gives for it with that
+// seed.  matchErrors[k][i]: what RegisterPnP leaves in match_error of record i of frame a (empty for a pair without a
+// fit); inliers[k][i]: the winner's flag.  Returns the elapsed milliseconds.
+inline double RegisterPnPSequence(std::vector<SiftData *> &frames, std::vector<std::pair<int, int> > pairs,
+                                  const cusift_camera *camera2, std::vector<double> &Rts,
+                                  std::vector<int> *numMatches = NULL, std::vector<int> *numFit = NULL,
+                                  int numLoops = 10000, float minScore = 0.0f, float maxAmbiguity = 0.8f,
+                                  float thresh = 2.0f, int refineLoops = 5, float refineThresh = 2.0f, uint64_t seed = 0,
+                                  int distance = 0, int rule = 0, std::vector<double> *ransac = NULL,
+                                  std::vector<std::vector<float> > *matchErrors = NULL,
+                                  std::vector<std::vector<char> > *inliers = NULL,
+                                  std::vector<int> *numCandidates = NULL) {
+  TimerGPU timer;
+  cusift_dropin::SequencePack pack(frames, pairs);
+  const size_t slots = pack.slots(), flat = (size_t)pack.n_pairs * pack.max_pts;
+  std::vector<int> candidates(slots), matches(slots), fit(slots);
+  std::vector<double> rt(12 * slots), win(12 * slots);
+  std::vector<char> h_flags(inliers ? flat : 0);
+  std::vector<float> h_err(matchErrors ? flat : 0);
+  safeCall(cusift_register_pnp_batch(cusift_dropin::ctx(), pack.d_points(), pack.d_counters(), pack.n, pack.max_pts,
+                                     pack.h_pairs.data(), pack.n_pairs, distance, rule, minScore, maxAmbiguity, camera2,
+                                     numLoops, thresh, refineLoops, refineThresh, seed, rt.data(), win.data(),
+                                     candidates.data(), matches.data(), fit.data(), NULL, inliers ? h_flags.data() : NULL,
+                                     matchErrors ? h_err.data() : NULL));
+  Rts.assign(rt.begin(), rt.begin() + 12 * (size_t)pack.n_pairs);
+  if (ransac) ransac->assign(win.begin(), win.begin() + 12 * (size_t)pack.n_pairs);
+  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + pack.n_pairs);
+  if (numFit) numFit->assign(fit.begin(), fit.begin() + pack.n_pairs);
+  if (numCandidates) numCandidates->assign(candidates.begin(), candidates.begin() + pack.n_pairs);
+  std::vector<char> fitted(slots);
+  for (int k = 0; k < pack.n_pairs; k++) fitted[k] = matches[k] >= 1;  // a fit counts at least its own six samples
+  pack.rows(h_flags, 1, NULL, inliers);
+  pack.rows(h_err, 1, &fitted, matchErrors);
   return timer.read();
 }
 

@@ -53,4 +53,43 @@ inline double RegisterPose(SiftData &data1, SiftData &data2, const cusift_camera
   return timer.read();
 }
 
+// RegisterPose for a whole sequence in one call (cusift_register_pose_batch): pair k = (a, b) of `pairs` gives
+// Rts[12 k .. 12 k + 11] = [R | t] with X_a = R X_b + t and |t| = 1 -- PER PAIR: the scale of every pair is its own, so
+// these poses do not compose into a trajectory (RegisterPnPSequence of pnp.h, which is metric, does).  `camera` serves
+// frame a and camera2 frame b of every pair (NULL: the same camera).  An empty `pairs` means (i, i + 1) for every
+// consecutive frame; pair k draws from seed + k and has the bits RegisterPose gives for it with that seed.  The frames
+// are NOT written: points3D[k] holds 3 floats per record of frame a, what RegisterPose writes into coords3D.
+// fundamentals (optional): the refined F of every pair.  Returns the elapsed milliseconds.
+inline double RegisterPoseSequence(std::vector<SiftData *> &frames, std::vector<std::pair<int, int> > pairs,
+                                   const cusift_camera *camera, std::vector<double> &Rts,
+                                   std::vector<int> *numMatches = NULL, std::vector<int> *numFit = NULL,
+                                   std::vector<int> *numFront = NULL, int numLoops = 10000, float minScore = 0.0f,
+                                   float maxAmbiguity = 0.8f, float thresh = 1.0f, int refineLoops = 5,
+                                   float refineThresh = 1.0f, uint64_t seed = 0, int distance = 0, int rule = 0,
+                                   const cusift_camera *camera2 = nullptr, std::vector<double> *fundamentals = NULL,
+                                   std::vector<std::vector<float> > *points3D = NULL,
+                                   std::vector<std::vector<char> > *inliers = NULL) {
+  TimerGPU timer;
+  cusift_dropin::SequencePack pack(frames, pairs);
+  const size_t slots = pack.slots(), flat = (size_t)pack.n_pairs * pack.max_pts;
+  std::vector<int> candidates(slots), matches(slots), fit(slots), front(slots);
+  std::vector<double> fund(9 * slots), win(9 * slots), rt(12 * slots);
+  std::vector<char> h_flags(inliers ? flat : 0);
+  std::vector<float> h_xyz(points3D ? 3 * flat : 0);
+  safeCall(cusift_register_pose_batch(cusift_dropin::ctx(), pack.d_points(), pack.d_counters(), pack.n, pack.max_pts,
+                                      pack.h_pairs.data(), pack.n_pairs, distance, rule, minScore, maxAmbiguity, numLoops,
+                                      thresh, refineLoops, refineThresh, seed, camera, camera2, fund.data(), win.data(),
+                                      candidates.data(), matches.data(), fit.data(), NULL,
+                                      inliers ? h_flags.data() : NULL, NULL, rt.data(), front.data(), NULL, NULL,
+                                      points3D ? h_xyz.data() : NULL));
+  Rts.assign(rt.begin(), rt.begin() + 12 * (size_t)pack.n_pairs);
+  if (fundamentals) fundamentals->assign(fund.begin(), fund.begin() + 9 * (size_t)pack.n_pairs);
+  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + pack.n_pairs);
+  if (numFit) numFit->assign(fit.begin(), fit.begin() + pack.n_pairs);
+  if (numFront) numFront->assign(front.begin(), front.begin() + pack.n_pairs);
+  pack.rows(h_flags, 1, NULL, inliers);
+  pack.rows(h_xyz, 3, NULL, points3D);
+  return timer.read();
+}
+
 #endif  // CUSIFT_AMD_POSE_H
