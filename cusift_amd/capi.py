@@ -1043,29 +1043,18 @@ class Context:
         synchronisation.  Pair p = (a, b) maps frame a onto frame b and draws from seed + p; the records are not written.
         rule / lo / hi default as in register_planar.  Returns a PlanarBatchResult."""
         pairs = pair_list(pairs)
-        n_pairs = len(pairs)
         rule, lo, hi = _rule_defaults(distance, rule, lo, hi)
-        hom, ransac = np.zeros((n_pairs, 9), dtype=np.float32), np.zeros((n_pairs, 9), dtype=np.float32)
-        n_cand, n_match, n_fit, best = (np.zeros(n_pairs, dtype=np.int32) for _ in range(4))
-        # the call writes 0 / 1 into the first count entries of a pair's block and nothing behind them
-        flags = np.full((n_pairs, max(max_pts, 1)), -1, dtype=np.int8)
-        err = np.full((n_pairs, max(max_pts, 1)), np.nan, dtype=np.float32) if want_errors else None
-        check(lib().cusift_register_planar_batch(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
-                                                 n_pairs, distance, rule, lo, hi, int(loops), thresh, refine_loops,
-                                                 refine_thresh, _seed64(seed), hom.ctypes.data,
-                                                 ransac.ctypes.data, n_cand.ctypes.data, n_match.ctypes.data,
-                                                 n_fit.ctypes.data, best.ctypes.data, flags.ctypes.data,
-                                                 err.ctypes.data if want_errors else None))
-        counts = (flags >= 0).sum(axis=1).astype(np.int32) if max_pts > 0 else np.zeros(n_pairs, dtype=np.int32)
-        return PlanarBatchResult(hom, ransac, n_cand, n_match, n_fit, best, counts,
-                                 [flags[p, :counts[p]] == 1 for p in range(n_pairs)] if want_inliers else None,
-                                 [err[p, :counts[p]].copy() for p in range(n_pairs)] if want_errors else None)
+        return PlanarBatchResult(*self._batch(lambda *out: lib().cusift_register_planar_batch(
+            self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data, len(pairs), distance, rule, lo, hi,
+            int(loops), thresh, refine_loops, refine_thresh, _seed64(seed), *out), (9,), pairs, max_pts, want_inliers,
+            want_errors, np.float32))
 
-    def _batch(self, call, shape, pairs, max_pts, want_inliers, want_errors):
-        """The outputs that the pair-list forms of F, the pose and PnP share: call(*pointers) makes the library call with
-        the eight shared output pointers.  Returns the nine fields of an EpipolarBatchResult / PnPBatchResult."""
+    def _batch(self, call, shape, pairs, max_pts, want_inliers, want_errors, dtype=np.float64):
+        """The outputs that the pair-list forms share: call(*pointers) makes the library call with the eight shared
+        output pointers; dtype: of the model's values.  Returns the nine fields of a PlanarBatchResult /
+        EpipolarBatchResult / PnPBatchResult."""
         n_pairs = len(pairs)
-        model, ransac = np.zeros((n_pairs,) + shape, dtype=np.float64), np.zeros((n_pairs,) + shape, dtype=np.float64)
+        model, ransac = np.zeros((n_pairs,) + shape, dtype=dtype), np.zeros((n_pairs,) + shape, dtype=dtype)
         n_cand, n_match, n_fit, best = (np.zeros(n_pairs, dtype=np.int32) for _ in range(4))
         # the call writes 0 / 1 into the first count entries of a pair's block and nothing behind them
         flags = np.full((n_pairs, max(max_pts, 1)), -1, dtype=np.int8)

@@ -2,8 +2,9 @@
 // registration, the calibrated pose, planar and epipolar registration, the absolute pose (PnP), the pair-list forms.  An entry point that reads
 // results back lays its state out in the context's register_scratch, what travels back first, and ends in one copy and
 // one synchronisation.  Shared: match_launch (either pair matcher), match_enqueue (a fused call's matcher), mark_launch
-// (the candidate marking), ransac_run (the chain of the homography, of the fundamental matrix and of the absolute pose,
-// told apart by data).
+// (the candidate marking), pose_launch (the pose stage) and the two runners of the chain of the homography, of the
+// fundamental matrix and of the absolute pose, told apart by data: ransac_run (a pair) and ransac_batch_run (a pair
+// list).  The RGB-D calls run the rigid chain (rigid_launch) behind a selection.
 #include "sift_host.h"
 
 // the refusals that several entry points share; `who` is the entry point's name in the message
@@ -610,27 +611,41 @@ static PoseStage pose_stage(const cusift_camera *camera1, const cusift_camera *c
   return st;
 }
 
-// The pose head zeroed, the two launches, and the head's copy to the host -- adjacent to the caller's one read-back, in
-// front of its one synchronisation.  d_head: the epipolar head with F at kEpiHeadF.  num_pts == 0: one workgroup, which
-// writes the head.
+// The pose heads zeroed and the two launches, n_pairs and nb as planar_launch.  d_head: the epipolar head(s) with F at
+// kEpiHeadF.  d_xyz != NULL: the points go there, not into coords3D.  num_pts == 0: one workgroup, which writes the head.
+static int pose_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, const float *d_coord,
+                       const unsigned char *d_marks, const int *d_head, const PoseCams &cams, float thresh, int *d_pose,
+                       float *d_xyz, int n_pairs, PlanarBatch nb) {
+  const dim3 grid(std::max(idiv_up(num_pts, 256), 1), 1, n_pairs);
+  HIP_TRY(hipMemsetAsync(d_pose, 0, kPoseHeadBytes * (size_t)n_pairs, ctx->stream));
+  hipLaunchKernelGGL(pose_vote_kernel, grid, dim3(256), 0, ctx->stream, d_coord, d_marks, num_pts, d_head, cams, thresh,
+                     d_pose, nb);
+  hipLaunchKernelGGL(pose_write_kernel, grid, dim3(256), 0, ctx->stream, d_sift, d_coord, d_marks, num_pts, d_head, cams,
+                     thresh, d_pose, d_xyz, nb);
+  return CUSIFT_OK;
+}
+
+// The pair call's stage: pose_launch and the head's copy to the host -- adjacent to the caller's one read-back, in front
+// of its one synchronisation.
 static int pose_enqueue(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, const float *d_coord,
                         const unsigned char *d_marks, const int *d_head, int *d_pose, PoseStage &st) {
-  const dim3 grid(std::max(idiv_up(num_pts, 256), 1));
-  HIP_TRY(hipMemsetAsync(d_pose, 0, kPoseHeadBytes, ctx->stream));
-  hipLaunchKernelGGL(pose_vote_kernel, grid, dim3(256), 0, ctx->stream, d_coord, d_marks, num_pts, d_head, st.cams,
-                     st.thresh, d_pose, PlanarBatch{});
-  hipLaunchKernelGGL(pose_write_kernel, grid, dim3(256), 0, ctx->stream, d_sift, d_coord, d_marks, num_pts, d_head,
-                     st.cams, st.thresh, d_pose, (float *)nullptr, PlanarBatch{});
+  TRY(pose_launch(ctx, d_sift, num_pts, d_coord, d_marks, d_head, st.cams, st.thresh, d_pose, nullptr, 1, PlanarBatch{}));
   HIP_TRY(hipMemcpyAsync(st.back, d_pose, kPoseHeadBytes, hipMemcpyDeviceToHost, ctx->stream));
   return CUSIFT_OK;
 }
 
-// after the synchronisation: the pose head into the caller's outputs
-static void pose_report(const PoseStage &st) {
-  memcpy(st.out.h_rt, st.back + sizeof(double) * kPoseHeadRt, sizeof(double) * 12);
-  *st.out.num_front = head_int(st.back, kPoseHeadFront);
-  if (st.out.h_votes) memcpy(st.out.h_votes, st.back + sizeof(int) * kPoseHeadVotes, sizeof(int) * 4);
-  if (st.out.h_sigma) memcpy(st.out.h_sigma, st.back + sizeof(double) * kPoseHeadSigma, sizeof(double) * 3);
+// after the synchronisation: a pose head that was read back into entry p of the caller's outputs (a pair call: 0)
+static void pose_report(const char *head, const PoseOut &o, size_t p = 0) {
+  memcpy(o.h_rt + 12 * p, head + sizeof(double) * kPoseHeadRt, sizeof(double) * 12);
+  o.num_front[p] = head_int(head, kPoseHeadFront);
+  if (o.h_votes) memcpy(o.h_votes + 4 * p, head + sizeof(int) * kPoseHeadVotes, sizeof(int) * 4);
+  if (o.h_sigma) memcpy(o.h_sigma + 3 * p, head + sizeof(double) * kPoseHeadSigma, sizeof(double) * 3);
+}
+static void pose_nothing(const PoseOut &o, size_t p) {  // no frames to look at: [I | 0], nothing in front, no votes
+  memcpy(o.h_rt + 12 * p, kIdentRtD, sizeof(kIdentRtD));
+  o.num_front[p] = 0;
+  if (o.h_votes) memset(o.h_votes + 4 * p, 0, sizeof(int) * 4);
+  if (o.h_sigma) memset(o.h_sigma + 3 * p, 0, sizeof(double) * 3);
 }
 
 // The staged route: F from the host, the marking, the pose stage; the arguments are checked.
@@ -654,7 +669,7 @@ static int pose_run(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_
                    at<int>(base, pose_off), st));
   TRY(check_launch("estimate_pose"));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  pose_report(st);
+  pose_report(st.back, st.out);
   return CUSIFT_OK;
 }
 
@@ -701,9 +716,7 @@ static void epipolar_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, 
 }
 
 // The four launches behind the marking, over the block(s) at d_block: the candidates' 3-D points against their matches'
-// pixels in the image of `cam` (sift_pnp.hip); n_pairs and nb as planar_launch.  One pair is the grid
-// hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64), ...) that tests/test_pnp_sizes.py plans
-// for; a pair list adds the layer of the pairs to every grid.
+// pixels in the image of `cam` (sift_pnp.hip); n_pairs and nb as planar_launch.
 static void pnp_launch(cusift_ctx *ctx, cusift_point *d_sift, int num_pts, int num_loops, float thresh, int refine_loops,
                        float refine_thresh, uint64_t seed, PnPCam cam, char *d_block, const RansacBlock &b, int *d_head,
                        char *d_flags, float *d_err, int n_pairs, PlanarBatch nb) {
@@ -770,7 +783,7 @@ static int ransac_run(cusift_ctx *ctx, const RansacModel &m, cusift_point *d_sif
   std::vector<char> back(all ? block_off + b.coord : (o.h_inliers ? block_off : flag_off));
   HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (pose) pose_report(*pose);
+  if (pose) pose_report(pose->back, pose->out);
   const char *head = back.data(), *block = back.data() + block_off;
   const int n_cand = head_int(head, kPlanarHeadCand);
   // extras/homography.cu:220; the kernels left the records alone
@@ -1075,82 +1088,8 @@ extern "C" int cusift_register_pose(cusift_ctx *ctx, cusift_point *d_sift1, int 
 }
 
 // ------------------------------------------------------------------------------------------------
-// planar registration of a pair list (sift_sequence.hip, sift_planar.hip) -- one read-back
-// ------------------------------------------------------------------------------------------------
-extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
-                                            int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
-                                            int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
-                                            float refine_thresh, uint64_t seed, float *h_homography, float *h_ransac,
-                                            int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
-                                            char *h_inliers, float *h_match_error) {
-  TRY(enter(ctx));
-  const RansacOut o{h_homography, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
-                    h_inliers,    nullptr,  nullptr,          nullptr};
-  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "RegisterPlanarBatch"));
-  TRY(precheck("RegisterPlanarBatch", d_points, n_images > 0 ? max_pts : 0, rule, lo, hi, num_loops, thresh,
-               refine_loops, refine_thresh, o));
-  TRY(check_distance("RegisterPlanarBatch", distance));
-  if (n_pairs == 0) return CUSIFT_OK;
-  const size_t P = (size_t)n_pairs, M = (size_t)max_pts;
-  if (max_pts == 0) {  // every frame is empty, known from the arguments alone
-    for (size_t p = 0; p < P; ++p) {
-      const RansacOut one{h_homography + 9 * p, h_ransac + 9 * p, h_num_candidates + p, h_num_matches + p,
-                          h_num_fit + p, h_best_loop ? h_best_loop + p : nullptr, nullptr, nullptr, nullptr, nullptr};
-      ransac_nothing(kHomography, 0, num_loops, one);
-    }
-    return CUSIFT_OK;
-  }
-  // [heads | flags | errors] is what travels back, in one copy; behind it what stays on the device: one RansacBlock per
-  // pair, then the match rows and -- with the cross-check (cusift_ctx_set_cross_check) -- the matcher's back rows
-  const RansacBlock b(kHomography, max_pts, num_loops);
-  ScratchLayout s;
-  s.take(kPlanarHeadBytes * P);  // the heads, at 0
-  const size_t flag_off = s.take(P * M);
-  const size_t err_off = s.take(sizeof(float) * P * M);
-  const size_t block_off = s.take(b.bytes * P);
-  const size_t row_off = s.take(sizeof(cusift_match_row) * P * M);
-  const size_t back_off = ctx->cross_check ? s.take(sizeof(cusift_match_row) * P * M) : 0;
-  TRY(grow_scratch(ctx, ctx->register_scratch, ctx->register_scratch_bytes, s.size, "", false));
-  char *base = ctx->register_scratch, *d_block = base + block_off;
-  cusift_match_row *d_rows = at<cusift_match_row>(base, row_off);
-  cusift_match_row *d_rows_back = ctx->cross_check ? at<cusift_match_row>(base, back_off) : nullptr;
-  PlanarBatch nb;
-  nb.records = 0, nb.scratch = b.bytes, nb.head = kPlanarHeadBytes, nb.flags = M, nb.count = 1;
-  nb.min_pts = kHomography.min_pts;
-  const int *d_pairs = nullptr;
-  TRY(match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, d_rows_back));
-  hipLaunchKernelGGL(sequence_mark_kernel, dim3(idiv_up(max_pts, 256), 1, n_pairs), dim3(256), 0, ctx->stream, d_points,
-                     d_counters, max_pts, d_pairs, (const cusift_match_row *)d_rows, rule, mark_thresh(rule, lo),
-                     mark_thresh(rule, hi), at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
-                     at<int>(d_block, b.blocks), (int *)base, nb, (const cusift_match_row *)d_rows_back);
-  planar_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
-                base + flag_off, at<float>(base, err_off), n_pairs, nb);
-  TRY(check_launch("register_planar_batch"));
-  // the one blocking read-back
-  std::vector<char> back(h_match_error ? err_off + sizeof(float) * P * M
-                                       : (h_inliers ? flag_off + P * M : kPlanarHeadBytes * P));
-  HIP_TRY(hipMemcpyAsync(back.data(), base, back.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  for (size_t p = 0; p < P; ++p) {  // the kernels decided every pair, the degenerate ones included: copies only
-    const char *head = back.data() + kPlanarHeadBytes * p;
-    const int n_cand = head_int(head, kPlanarHeadCand);
-    const size_t n = (size_t)std::min(std::max(head_int(head, kPlanarHeadCount), 0), max_pts);  // records of frame 1
-    memcpy(h_homography + 9 * p, head + sizeof(float) * kPlanarHeadH, sizeof(float) * 9);
-    memcpy(h_ransac + 9 * p, head + sizeof(float) * kPlanarHeadR, sizeof(float) * 9);
-    h_num_candidates[p] = n_cand, h_num_matches[p] = head_int(head, kPlanarHeadMatches);
-    h_num_fit[p] = head_int(head, kPlanarHeadFit);
-    if (h_best_loop) h_best_loop[p] = head_int(head, kPlanarHeadLoop);
-    if (h_inliers) memcpy(h_inliers + p * M, back.data() + flag_off + p * M, n);
-    // a pair without a fit has no error, as the pair call leaves match_error alone then
-    if (h_match_error && n_cand >= 8)
-      memcpy(h_match_error + p * M, back.data() + err_off + sizeof(float) * p * M, sizeof(float) * n);
-  }
-  return CUSIFT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// epipolar, pose and PnP registration of a pair list (sift_sequence.hip, sift_epipolar.hip, sift_pose.hip, sift_pnp.hip):
-// the batch counterpart of ransac_run, told apart by the model -- one read-back
+// planar, epipolar, pose and PnP registration of a pair list (sift_sequence.hip, sift_planar.hip, sift_epipolar.hip,
+// sift_pose.hip, sift_pnp.hip): the batch counterpart of ransac_run, told apart by the model -- one read-back
 // ------------------------------------------------------------------------------------------------
 // What a pair-list call returns besides RansacOut's arrays ([P] entries each), and what its model takes: the pose stage's
 // outputs and cameras (pose_cams != NULL: cusift_register_pose_batch), the matches' camera (kPnP)
@@ -1190,11 +1129,7 @@ static int ransac_batch_run(cusift_ctx *ctx, const RansacModel &m, const cusift_
   if (max_pts == 0) {  // every frame is empty, known from the arguments alone
     for (size_t p = 0; p < P; ++p) {
       ransac_nothing(m, 0, num_loops, batch_pair_out(m, o, p));
-      if (!pose) continue;
-      memcpy(x.pose.h_rt + 12 * p, kIdentRtD, sizeof(kIdentRtD));
-      x.pose.num_front[p] = 0;
-      if (x.pose.h_votes) memset(x.pose.h_votes + 4 * p, 0, sizeof(int) * 4);
-      if (x.pose.h_sigma) memset(x.pose.h_sigma + 3 * p, 0, sizeof(double) * 3);
+      if (pose) pose_nothing(x.pose, p);
     }
     return CUSIFT_OK;
   }
@@ -1225,22 +1160,19 @@ static int ransac_batch_run(cusift_ctx *ctx, const RansacModel &m, const cusift_
                      mark_thresh(rule, lo), mark_thresh(rule, hi), at<float>(d_block, b.coord),
                      at<unsigned char>(d_block, b.marks), at<int>(d_block, b.blocks), (int *)base, nb,
                      (const cusift_match_row *)d_rows_back);
-  if (m.launch == kPnPLaunch)
-    pnp_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, *x.cam, d_block, b,
-               (int *)base, base + flag_off, at<float>(base, err_off), n_pairs, nb);
-  else
+  if (m.launch == kPlanarLaunch)
+    planar_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (float *)base,
+                  base + flag_off, at<float>(base, err_off), n_pairs, nb);
+  else if (m.launch == kEpipolarLaunch)
     epipolar_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, d_block, b, (int *)base,
                     base + flag_off, at<float>(base, err_off), n_pairs, nb);
-  if (pose) {  // behind the selection, at refine_thresh as in the pair call; the points go to an array of their own
-    HIP_TRY(hipMemsetAsync(base + pose_off, 0, kPoseHeadBytes * P, ctx->stream));
-    hipLaunchKernelGGL(pose_vote_kernel, mark_grid, dim3(256), 0, ctx->stream, (const float *)at<float>(d_block, b.coord),
-                       (const unsigned char *)at<unsigned char>(d_block, b.marks), max_pts, (const int *)base,
-                       *x.pose_cams, refine_thresh, at<int>(base, pose_off), nb);
-    hipLaunchKernelGGL(pose_write_kernel, mark_grid, dim3(256), 0, ctx->stream, (cusift_point *)nullptr,
-                       (const float *)at<float>(d_block, b.coord),
-                       (const unsigned char *)at<unsigned char>(d_block, b.marks), max_pts, (const int *)base,
-                       *x.pose_cams, refine_thresh, at<int>(base, pose_off), at<float>(base, xyz_off), nb);
-  }
+  else
+    pnp_launch(ctx, nullptr, max_pts, num_loops, thresh, refine_loops, refine_thresh, seed, *x.cam, d_block, b,
+               (int *)base, base + flag_off, at<float>(base, err_off), n_pairs, nb);
+  if (pose)  // behind the selection, at refine_thresh as in the pair call; the points go to an array of their own
+    TRY(pose_launch(ctx, nullptr, max_pts, at<float>(d_block, b.coord), at<unsigned char>(d_block, b.marks),
+                    (const int *)base, *x.pose_cams, refine_thresh, at<int>(base, pose_off), at<float>(base, xyz_off),
+                    n_pairs, nb));
   TRY(check_launch(m.label));
   // the one blocking read-back
   size_t back_bytes = pose ? pose_off + kPoseHeadBytes * P : m.head_bytes * P;
@@ -1271,15 +1203,28 @@ static int ransac_batch_run(cusift_ctx *ctx, const RansacModel &m, const cusift_
     if (x.h_match_error && fitted)
       memcpy(x.h_match_error + p * M, back.data() + err_off + sizeof(float) * p * M, sizeof(float) * n);
     if (!pose) continue;
-    const char *ph = back.data() + pose_off + kPoseHeadBytes * p;
-    memcpy(x.pose.h_rt + 12 * p, ph + sizeof(double) * kPoseHeadRt, sizeof(double) * 12);
-    x.pose.num_front[p] = head_int(ph, kPoseHeadFront);
-    if (x.pose.h_votes) memcpy(x.pose.h_votes + 4 * p, ph + sizeof(int) * kPoseHeadVotes, sizeof(int) * 4);
-    if (x.pose.h_sigma) memcpy(x.pose.h_sigma + 3 * p, ph + sizeof(double) * kPoseHeadSigma, sizeof(double) * 3);
+    pose_report(back.data() + pose_off + kPoseHeadBytes * p, x.pose, p);
     if (x.h_points3d)
       memcpy(x.h_points3d + 3 * p * M, back.data() + xyz_off + sizeof(float) * 3 * p * M, sizeof(float) * 3 * n);
   }
   return CUSIFT_OK;
+}
+
+extern "C" int cusift_register_planar_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                            int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                            int rule, float lo, float hi, int num_loops, float thresh, int refine_loops,
+                                            float refine_thresh, uint64_t seed, float *h_homography, float *h_ransac,
+                                            int *h_num_candidates, int *h_num_matches, int *h_num_fit, int *h_best_loop,
+                                            char *h_inliers, float *h_match_error) {
+  TRY(enter(ctx));
+  const RansacOut o{h_homography, h_ransac, h_num_candidates, h_num_matches, h_num_fit, h_best_loop,
+                    h_inliers,    nullptr,  nullptr,          nullptr};
+  TRY(batch_check("RegisterPlanarBatch", d_points, n_images, max_pts, h_pairs, n_pairs, distance, rule, lo, hi, num_loops,
+                  thresh, refine_loops, refine_thresh, o));
+  if (n_pairs == 0) return CUSIFT_OK;
+  const BatchExtra x{h_match_error, nullptr, PoseOut{}, nullptr, nullptr};
+  return ransac_batch_run(ctx, kHomography, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, rule, lo, hi,
+                          num_loops, thresh, refine_loops, refine_thresh, seed, o, x);
 }
 
 extern "C" int cusift_register_epipolar_batch(cusift_ctx *ctx, const cusift_point *d_points,

@@ -496,6 +496,54 @@ def test_batch_refusals_leave_everything_untouched(ctx, frames):
         np.array_equal(u, v) for u, v in zip(c2, ints))
 
 
+def optional_outputs_three_ways(call, n_pairs, max_pts, shape, dtype):
+    """call(eight output pointers) -> status, made three times: h_inliers and h_match_error both NULL, only h_inliers
+    NULL, both given -- the three sizes of the pair-list runner's read-back.  The two models and the four count arrays
+    are byte-equal in all three; what is not asked for is not written.  Returns the third call's (models and counts,
+    flags, errors)."""
+    got = []
+    for want_flags, want_err in ((False, False), (False, True), (True, True)):
+        models = [np.full((n_pairs,) + shape, 9.0, dtype) for _ in range(2)]
+        ints = [np.full(n_pairs, -7, np.int32) for _ in range(4)]
+        fl = np.full((n_pairs, max_pts), -1, np.int8)
+        err = np.full((n_pairs, max_pts), np.nan, np.float32)
+        assert call(*([a.ctypes.data for a in models + ints] + [fl.ctypes.data if want_flags else None,
+                                                                err.ctypes.data if want_err else None])) == 0
+        assert want_flags or (fl == -1).all()
+        assert want_err or np.isnan(err).all()
+        got.append((models + ints, fl, err))
+    for other in got[:2]:
+        for u, v in zip(other[0], got[2][0]):
+            assert u.tobytes() == v.tobytes()
+    assert got[1][2].tobytes() == got[2][2].tobytes()  # the errors do not depend on the flags being asked for
+    return got[2]
+
+
+@pytest.mark.gpu
+def test_optional_outputs_left_out_change_nothing_else(ctx, frames):
+    """The read-back branches that capi.Context.register_planar_batch never reaches (it always passes a flags array), on
+    the degenerate list: raw calls with neither flags nor errors, with errors only, with both.  Models and counts
+    byte-equal; the third call's flags and errors are the wrapper's."""
+    from cusift_amd import capi
+
+    seed, n_pairs = 9, len(DEGENERATE)
+    pts, cnt = frames.upload(ctx)
+    outs, fl, err = optional_outputs_three_ways(
+        lambda *out: capi.lib().cusift_register_planar_batch(ctx.handle, pts.ptr, cnt.ptr, N_FRAMES, MAX_PTS,
+                                                             DEGENERATE.ctypes.data, n_pairs, 1, 1, 999.0, 0.8, LOOPS,
+                                                             5.0, 5, 3.0, seed, *out),
+        n_pairs, MAX_PTS, (9,), np.float32)
+    res, _ = register_batch(ctx, frames, seed, pairs=DEGENERATE)
+    for u, v in zip(outs, res[:6]):
+        assert u.tobytes() == np.asarray(v).tobytes()
+    for p in range(n_pairs):
+        n = int((fl[p] >= 0).sum())
+        assert n == res.counts[p] and (fl[p, :n] >= 0).all(), p
+        assert np.array_equal(fl[p, :n] == 1, res.inliers[p]), p
+        assert err[p, :n].tobytes() == res.match_error[p].tobytes() and np.isnan(err[p, n:]).all(), p
+    assert np.isnan(err[list(DEGENERATE_AT)]).all() and not np.isnan(err[0, :frames.n[0]]).all()
+
+
 @pytest.mark.gpu
 def test_register_planar_sequence_end_to_end(ctx, oracle, gray1):
     """gray1.pgm and three frames warped by cumulative mild homographies, extracted by BatchExtractor and registered

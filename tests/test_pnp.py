@@ -483,8 +483,10 @@ def test_header_library_and_binding_carry_the_pnp_calls():
                  "wave_tree_sum<kPnPSums>(s, s_part, s_sum, tx);"):
         assert expr in kernels, expr
     # the scoring grid that tests/test_pnp_sizes.py plans for; tests/test_register_source.py pins the planner and its call
+    # (one grid layer per pair); the launch itself, not a comment about it
     host = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()
-    assert "hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits), dim3(64)" in host
+    host = "\n".join(line.split("//")[0] for line in host.splitlines())
+    assert "hipLaunchKernelGGL(pnp_score_kernel, dim3(loop_blocks, splits, n_pairs), dim3(64)" in host
 
 
 def exact_scene(name, n=60):

@@ -22,7 +22,7 @@ from oracle_binding import SIFT_POINT_DTYPE
 from test_epipolar_batch import (MAX_PTS, N_FRAMES, LOOPS, SEEDS, Frames, fill_extractor, same_results, scatter,
                                  the_frames)
 from test_planar import upload
-from test_planar_batch import RULES, match_rows
+from test_planar_batch import RULES, match_rows, optional_outputs_three_ways
 from test_pnp import (CAM, H, IDENT, REFINE_LOOPS, REFINE_THRESH, ROT_BOUND, THRESH, TRANS_BOUND, W, cam_of, camera,
                       coords5, match_error, pnp_candidates, pnp_inliers, refit, rot_err)
 from test_rgbd_batch import MASK64, SENTINEL, tie_rows
@@ -336,6 +336,34 @@ def test_refusals_leave_everything_untouched(ctx, frames):
                                                 ptr(c2[0]), ptr(c2[1]), ptr(c2[2]), None, None, None) == 0
     assert m2.tobytes() == rt.tobytes() and r2.tobytes() == ran.tobytes() and all(
         np.array_equal(u, v) for u, v in zip(c2, ints))
+
+
+@pytest.mark.gpu
+def test_optional_outputs_left_out_change_nothing_else(ctx, frames):
+    """tests/test_planar_batch.py's check of the read-back branches below the wrapper's, on the model whose winner may
+    lack support: raw calls with neither flags nor errors, with errors only, with both, over the whole list.  Models and
+    counts byte-equal; the third call's flags and errors are the wrapper's."""
+    from cusift_amd import capi
+
+    seed, n_pairs = 9, len(PAIRS)
+    pts, cnt = frames.upload(ctx)
+    rule = RULES[1]
+    outs, fl, err = optional_outputs_three_ways(
+        lambda *out: capi.lib().cusift_register_pnp_batch(ctx.handle, pts.ptr, cnt.ptr, N_FRAMES, MAX_PTS,
+                                                          PAIRS.ctypes.data, n_pairs, 1, rule["rule"], rule["lo"],
+                                                          rule["hi"], C.byref(camera(CAM)), LOOPS, THRESH, REFINE_LOOPS,
+                                                          REFINE_THRESH, seed, *out),
+        n_pairs, MAX_PTS, (3, 4), np.float64)
+    res, _ = pnp_batch(ctx, frames, seed)
+    for u, v in zip(outs, res[:6]):
+        assert u.tobytes() == np.asarray(v).tobytes()
+    for p in range(n_pairs):
+        n = int((fl[p] >= 0).sum())
+        assert n == res.counts[p] and (fl[p, :n] >= 0).all(), p
+        assert np.array_equal(fl[p, :n] == 1, res.inliers[p]), p
+        assert err[p, :n].tobytes() == res.match_error[p].tobytes() and np.isnan(err[p, n:]).all(), p
+    assert np.isnan(err[list(DEGENERATE_AT)]).all() and not np.isnan(err[0, :frames.n[0]]).all()
+    assert res.num_candidates[13] >= 6 and res.num_matches[13] == 0  # the winner without support is among them
 
 
 @pytest.mark.gpu

@@ -100,6 +100,58 @@ def model_field(descriptor, field):
     return values[names.index(field)]
 
 
+LAUNCHES = ("planar_launch(", "epipolar_launch(", "pnp_launch(")
+
+
+def check_dispatch(run, launch):
+    """The model's four launches in a runner: `launch` once, under its branch of the three-way choice by m.launch.  Each
+    launch function is named three times in the file: its definition and one call in either runner."""
+    assert run.count(launch) == 1 and [run.count(f) for f in LAUNCHES] == [1, 1, 1]
+    assert in_order(run, "if (m.launch == kPlanarLaunch)", "planar_launch(", "else if (m.launch == kEpipolarLaunch)",
+                    "epipolar_launch(", "\n  else\n", "pnp_launch(")
+    assert [code().count(f) for f in LAUNCHES] == [3, 3, 3]
+
+
+def check_pose_launch():
+    """pose_launch, the pose stage of a pair and of a pair list: the head(s) zeroed, the vote, the write; the grid carries
+    the pairs, nothing loops over them, nothing copies or waits."""
+    stage = body("pose_launch")
+    assert in_order(stage, "hipMemsetAsync(", "hipLaunchKernelGGL(pose_vote_kernel", "hipLaunchKernelGGL(pose_write_kernel")
+    assert stage.count("hipLaunchKernelGGL(") == 2 and stage.count("hipMemsetAsync(") == 1
+    assert "kPoseHeadBytes * (size_t)n_pairs" in stage
+    assert "const dim3 grid(std::max(idiv_up(num_pts, 256), 1), 1, n_pairs);" in stage
+    for banned in ("for (", "while (", "hipMemcpy", "Synchronize", "grow_scratch"):
+        assert banned not in stage, banned
+    for name in ("pose_vote_kernel", "pose_write_kernel"):
+        assert code().count("hipLaunchKernelGGL(" + name) == 1, name  # no second copy of the stage
+    assert code().count("pose_launch(") == 3  # the definition, pose_enqueue, ransac_batch_run
+
+
+def check_batch_call(name, launch, pose=False):
+    """A pair-list call: one hipStreamSynchronize on its path and nothing else that blocks; nothing of its own in the
+    entry point; in ransac_batch_run one read-back, the order matcher -> marking -> model launches -> (pose stage) ->
+    read-back -> wait, one marking launch statement and no launch in a loop over the pairs."""
+    one_sync_nothing_else(name)
+    entry = body(name)
+    assert "Synchronize" not in entry and "hipMemcpy" not in entry and "hipLaunchKernelGGL(" not in entry
+    assert entry.count("ransac_batch_run(") == 1 and entry.count("batch_check(") == 1
+    assert in_order(entry, "batch_check(", "if (n_pairs == 0) return CUSIFT_OK;", "ransac_batch_run(")
+    assert ("pose_stage(" in entry) == pose and ("&st.cams" in entry) == pose
+    run = body("ransac_batch_run")
+    assert run.count("hipStreamSynchronize(") == 1 and not [b for b in BLOCKING if b in run]
+    assert in_order(run, "match_batch_launch(", "sequence_mark_kernel", launch, "pose_launch(", "hipMemcpyAsync(",
+                    "hipStreamSynchronize(", "pose_report(")
+    check_dispatch(run, launch)
+    assert run.count("hipMemcpyAsync(") == 1  # one read-back; the pair list is uploaded by the matcher's launcher
+    # the marking here, compact / solve / score / select in the model's launch function, the pose stage's two in pose_launch
+    assert run.count("hipLaunchKernelGGL(") == 1 and run.count("pose_launch(") == 1
+    assert "hipLaunchKernelGGL(m.launch == kPnPLaunch ? sequence_pnp_mark_kernel : sequence_mark_kernel" in run
+    assert re.search(r"if \(pose\)\s*\n\s*TRY\(pose_launch\(", run)
+    launches = run[run.index("match_batch_launch("):run.index("hipMemcpyAsync(")]
+    assert "for (" not in launches and "while (" not in launches
+    return entry
+
+
 def check_chain_run(launch):
     """ransac_run, the run of the three chains: mark -> four launches -> (pose enqueue) -> the one read-back -> the one
     wait -> (pose report); the staged pose route of fewer records than the model can fit leaves before anything is
@@ -115,6 +167,7 @@ def check_chain_run(launch):
     assert run.count("hipStreamSynchronize(") == 1 and run.count("pose_enqueue(") == 1
     # was: run.count("hipLaunchKernelGGL(") == 1 and run.count("planar_launch(") == 1 -- the marking, then the shared four
     assert run.count("hipLaunchKernelGGL(") == 0 and run.count("mark_launch(") == 1 and run.count(launch) == 1
+    check_dispatch(run, launch)
     # was: one launch in mark_launch, planar_mark_kernel.  Now one per branch: the PnP model's marking, else the planar one
     mark = body("mark_launch")
     assert mark.count("hipLaunchKernelGGL(") == 2 and mark.count("hipLaunchKernelGGL(planar_mark_kernel") == 1
@@ -142,19 +195,29 @@ def test_one_synchronisation_in_the_planar_entry_points():
 
 # was tests/test_planar_batch.py::test_one_synchronisation_in_the_batch_entry_point
 def test_one_synchronisation_in_the_batch_entry_point():
-    # was: one hipStreamSynchronize( and no blocking call in the entry point's own text; now on its whole path
-    one_sync_nothing_else("cusift_register_planar_batch")
-    entry = body("cusift_register_planar_batch")
-    assert entry.count("hipStreamSynchronize(") == 1 and not [b for b in BLOCKING if b in entry]
-    assert in_order(entry, "match_batch_launch(", "sequence_mark_kernel", "planar_launch(", "hipMemcpyAsync(",
-                    "hipStreamSynchronize(")
-    assert entry.count("hipMemcpyAsync(") == 1  # one read-back; the pair list is uploaded by the matcher's launcher
-    # five launches -- the marking here, compact / solve / score / select in planar_launch -- none in a loop over the pairs
-    assert entry.count("hipLaunchKernelGGL(") == 1 and entry.count("planar_launch(") == 1
-    assert "hipLaunchKernelGGL(sequence_mark_kernel" in entry
+    # was: one hipStreamSynchronize( and no blocking call, the order match_batch_launch( -> sequence_mark_kernel ->
+    # planar_launch( -> hipMemcpyAsync( -> hipStreamSynchronize(, one hipMemcpyAsync(, one hipLaunchKernelGGL( (the
+    # marking) and no loop in front of the read-back, all in the entry point's own text.  The body is ransac_batch_run
+    # now: the same on the call's path and on the runner (check_batch_call)
+    entry = check_batch_call("cusift_register_planar_batch", "planar_launch(")
+    assert "ransac_batch_run(ctx, kHomography," in entry
+    assert model_field("kHomography", "launch") == "kPlanarLaunch"
     check_planar_launch()
-    launches = entry[entry.index("match_batch_launch("):entry.index("hipMemcpyAsync(")]
-    assert "for (" not in launches and "while (" not in launches
+    # five launches on the path -- the marking, compact / solve / score / select -- and no pose stage
+    p = path("cusift_register_planar_batch", without=("epipolar_launch", "pnp_launch", "pose_launch", "match_batch_launch"))
+    assert p.count("hipLaunchKernelGGL(") == 5
+
+
+def test_one_synchronisation_in_the_other_pair_list_entry_points():
+    """The rule of the planar pair-list call on its three siblings, which no test held to it."""
+    for name, model, launch, pose in (("cusift_register_epipolar_batch", "kFundamental", "epipolar_launch(", False),
+                                      ("cusift_register_pose_batch", "kFundamental", "epipolar_launch(", True),
+                                      ("cusift_register_pnp_batch", "kPnP", "pnp_launch(", False)):
+        entry = check_batch_call(name, launch, pose)
+        assert "ransac_batch_run(ctx, %s," % model in entry
+    assert model_field("kFundamental", "launch") == "kEpipolarLaunch" and model_field("kPnP", "launch") == "kPnPLaunch"
+    check_pose_launch()
+    assert code().count("ransac_batch_run(") == 5  # the definition and the four calls
 
 
 # was tests/test_epipolar.py::test_one_synchronisation_in_the_epipolar_entry_points
@@ -183,12 +246,18 @@ def test_one_synchronisation_in_the_pose_entry_points():
     # was: order of ("planar_mark_kernel", "pose_enqueue(", "hipStreamSynchronize(", "pose_report(") in pose_run
     assert in_order(run, "mark_launch(", "pose_enqueue(", "hipStreamSynchronize(", "pose_report(")
     assert run.count("hipMemcpyAsync(") == 1 and run.count("hipStreamSynchronize(") == 1  # F goes up; the head's copy is the stage's
+    # was: order of (hipMemsetAsync(, pose_vote_kernel, pose_write_kernel, hipMemcpyAsync() and two launches in
+    # pose_enqueue; the first three stand in pose_launch now, which the pair-list runner shares
     enq = body("pose_enqueue")
-    assert in_order(enq, "hipMemsetAsync(", "hipLaunchKernelGGL(pose_vote_kernel", "hipLaunchKernelGGL(pose_write_kernel",
-                    "hipMemcpyAsync(")
-    assert enq.count("hipLaunchKernelGGL(") == 2 and enq.count("hipMemcpyAsync(") == 1
+    assert in_order(enq, "pose_launch(", "hipMemcpyAsync(")
+    assert enq.count("pose_launch(") == 1 and enq.count("hipMemcpyAsync(") == 1 and "hipLaunchKernelGGL(" not in enq
+    assert "nullptr, 1, PlanarBatch{})" in enq  # one pair, into the records
     for banned in ("for (", "while (", "Synchronize", "grow_scratch"):
         assert banned not in enq, banned
+    check_pose_launch()
+    # one pose_report serves the pair calls and the runner's loop, on the head it is handed
+    assert body("pose_report").startswith("static void pose_report(const char *head, const PoseOut &o, size_t p = 0)")
+    assert code().count("pose_report(") == 4 and code().count("kPoseHeadRt") == 1
     # the fused call: the epipolar run with the stage behind its launches, in front of its one read-back and wait
     fused = body("cusift_register_pose")
     assert "Synchronize" not in fused and "hipMemcpy" not in fused and not [b for b in BLOCKING if b in fused]
