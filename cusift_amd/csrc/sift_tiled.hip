@@ -132,7 +132,8 @@ struct cusift_tiled {
   float *bands[kMaxOctaves] = {nullptr};
   float *full = nullptr;  // the whole collapse octave, on the root
   unsigned int *d_small = nullptr;  // [0] first (fstPts), [1] flags
-  bool per_octave = false;          // $CUSIFT_TILED_PER_OCTAVE (read at creation): the tiled octaves one at a time
+  // CUSIFT_POLICY_TILED_PER_OCTAVE of the context (cusift_ctx_get_policy, read at creation): the tiled octaves one at a time
+  bool per_octave = false;
   bool loaded = false;
   ~cusift_tiled() {
     (void)hipSetDevice(device);

@@ -98,18 +98,27 @@ class StripPlan:
 class StripExtractor:
     """One rank of the strip-tiled extraction (needs a GPU): output buffers + a capi.Tiled.  `comm`: a capi.Comm for
     the distributed form (run_distributed) -- the extractor then runs on the communicator's context, so kernels and
-    exchanges share one stream; None for run_virtual / world 1 (the context borrows torch's current stream)."""
+    exchanges share one stream; None for run_virtual / world 1 (the context borrows torch's current stream).
+    `ctx`: a capi.Context of the caller's on the same device, used instead of a new one and never closed by close() --
+    the way to set a policy (capi.POLICY_TILED_PER_OCTAVE) before capi.Tiled reads it at creation.  Not together with
+    `comm`: a communicator already supplies the context (set the policy on that one before creating the communicator)."""
 
-    def __init__(self, rank, world, W, H, params, device=None, halo=HALO, comm=None, strict=True):
+    def __init__(self, rank, world, W, H, params, device=None, halo=HALO, comm=None, strict=True, ctx=None):
         if not torch.cuda.is_available():
             raise capi.CusiftError("StripExtractor needs a GPU (no CPU fallback)")
+        if ctx is not None and comm is not None:
+            raise ValueError("StripExtractor: pass ctx= or comm=, not both (the communicator supplies the context)")
         self.rank, self.world, self.strict = rank, world, strict
         self.params = params
         self.plan = StripPlan(W, H, world, params.num_octaves, halo)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if ctx is not None and ctx.device != self.device.index:
+            raise ValueError("StripExtractor: ctx is on device %r, the extractor on %r" % (ctx.device, self.device.index))
         with torch.cuda.device(self.device):
             if comm is not None:
                 self.ctx, self.owns_ctx = comm.ctx, False
+            elif ctx is not None:
+                self.ctx, self.owns_ctx = ctx, False
             else:
                 self.ctx = capi.Context(self.device.index, stream=torch.cuda.current_stream().cuda_stream)
                 self.owns_ctx = True

@@ -57,6 +57,7 @@ def test_strips_equal_whole_image(ctx, W, H, P, n_oct, blur, thresh, collapse):
     np.testing.assert_array_equal(got["coords2D"], want["coords2D"])
     np.testing.assert_array_equal(got["scale"], want["scale"])
     np.testing.assert_array_equal(got["sharpness"], want["sharpness"])
+    np.testing.assert_array_equal(got["edgeness"], want["edgeness"])
     np.testing.assert_array_equal(got["orientation"], want["orientation"])
     np.testing.assert_array_equal(got["data"], want["data"])
     for e in exts:
