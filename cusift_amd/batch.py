@@ -98,6 +98,20 @@ class BatchExtractor:
 
         return packer
 
+    def _pairs(self, pairs):
+        return [(i, i + 1) for i in range(self.n - 1)] if pairs is None else pairs
+
+    def _pair_counts(self, counts, i, j):
+        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
+        return int(n_i), int(n_j)
+
+    def _depth_layout(self, d_depth):
+        """Checks a depth tensor [n, h, w'] of 16-bit samples; returns (pitch, image_stride) in samples."""
+        assert d_depth.is_cuda and d_depth.element_size() == 2 and d_depth.is_contiguous()
+        assert d_depth.dim() == 3 and d_depth.shape[0] == self.n and d_depth.shape[1] == self.h, tuple(d_depth.shape)
+        assert d_depth.shape[2] >= self.w, tuple(d_depth.shape)
+        return d_depth.shape[2], self.h * d_depth.shape[2]
+
     def register_sequence(self, d_depth, camera, pairs=None, slot=0, **ransac):
         """Registers the frames of the last extract() into `slot` against each other: cusift_register_rgbd_batch over
         this extractor's own device records and raw counters -- no count is read back, the frame counts never reach
@@ -106,15 +120,11 @@ class BatchExtractor:
         frame.  **ransac goes to capi.Context.register_rgbd_batch (loops, thresh2, kind, seed, distance, score_threshold,
         ambiguity_threshold).  Returns its tuple: (rt [P, 3, 4], num_matches [P], num_inliers [P], pairs list, flags
         list); capi.chain_poses(rt) turns the default pair list's result into per-frame poses.  Blocking."""
-        assert d_depth.is_cuda and d_depth.element_size() == 2 and d_depth.is_contiguous()
-        assert d_depth.dim() == 3 and d_depth.shape[0] == self.n and d_depth.shape[1] == self.h, tuple(d_depth.shape)
-        assert d_depth.shape[2] >= self.w, tuple(d_depth.shape)
-        if pairs is None:
-            pairs = [(i, i + 1) for i in range(self.n - 1)]
+        pitch, image_stride = self._depth_layout(d_depth)
         points, counts = self.slots[slot]
         return self.ctx.register_rgbd_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
-                                            d_depth.data_ptr(), self.w, self.h, camera, pairs,
-                                            pitch=d_depth.shape[2], image_stride=self.h * d_depth.shape[2], **ransac)
+                                            d_depth.data_ptr(), self.w, self.h, camera, self._pairs(pairs),
+                                            pitch=pitch, image_stride=image_stride, **ransac)
 
     def register_planar(self, i, j, slot=0, **opts):
         """Planar registration of frames i and j of the last extract() into `slot`: cusift_register_planar over this
@@ -122,8 +132,8 @@ class BatchExtractor:
         one call.  **opts goes to capi.Context.register_planar (distance, rule, lo, hi, loops, thresh, refine_loops,
         refine_thresh, seed, want_all).  Returns its PlanarResult: homography maps frame i onto frame j.  Blocking."""
         points, counts = self.slots[slot]
-        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
-        return self.ctx.register_planar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_planar(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, **opts)
 
     def register_epipolar(self, i, j, slot=0, **opts):
         """Epipolar registration of frames i and j of the last extract() into `slot`: cusift_register_epipolar over this
@@ -131,8 +141,8 @@ class BatchExtractor:
         one call.  **opts goes to capi.Context.register_epipolar (distance, rule, lo, hi, loops, thresh, refine_loops,
         refine_thresh, seed, want_all).  Returns its EpipolarResult: x_j^T F x_i = 0.  Blocking."""
         points, counts = self.slots[slot]
-        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
-        return self.ctx.register_epipolar(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), **opts)
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_epipolar(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, **opts)
 
     def register_pose(self, i, j, camera, camera2=None, slot=0, **opts):
         """Calibrated two-view pose of frames i and j of the last extract() into `slot`: cusift_register_pose over this
@@ -140,9 +150,8 @@ class BatchExtractor:
         capi.Camera of frame i, camera2 of frame j (None: the same).  The two counts are read with one call.  **opts goes
         to capi.Context.register_pose.  Returns its RegisterPoseResult: X_i = R X_j + t with |t| = 1.  Blocking."""
         points, counts = self.slots[slot]
-        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
-        return self.ctx.register_pose(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), camera, camera2,
-                                      **opts)
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_pose(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, camera, camera2, **opts)
 
     def register_pnp(self, i, j, camera2, slot=0, **opts):
         """Absolute pose of frame j of the last extract() into `slot` from frame i's coords3D (as lift_depth or an earlier
@@ -151,8 +160,8 @@ class BatchExtractor:
         read with one call.  **opts goes to capi.Context.register_pnp.  Returns its PnPResult: X_i = R X_j + t, t in the
         unit of frame i's coords3D.  Blocking."""
         points, counts = self.slots[slot]
-        n_i, n_j = torch.clamp(counts[[i, j]], max=self.max_pts).tolist()  # the one read-back of the counts
-        return self.ctx.register_pnp(points[i].data_ptr(), int(n_i), points[j].data_ptr(), int(n_j), camera2, **opts)
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_pnp(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, camera2, **opts)
 
     def register_planar_sequence(self, pairs=None, slot=0, **opts):
         """Planar registration of the frames of the last extract() into `slot` against each other:
@@ -163,13 +172,9 @@ class BatchExtractor:
         want_inliers, want_errors).  Returns its PlanarBatchResult: homography[p] maps frame a onto frame b;
         capi.chain_homographies(homography) turns the default pair list's result into per-frame maps into frame 0.
         Blocking."""
-        if pairs is None:
-            pairs = [(i, i + 1) for i in range(self.n - 1)]
         points, counts = self.slots[slot]
-        return self.ctx.register_planar_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts, pairs, **opts)
-
-    def _pairs(self, pairs):
-        return [(i, i + 1) for i in range(self.n - 1)] if pairs is None else pairs
+        return self.ctx.register_planar_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
+                                              self._pairs(pairs), **opts)
 
     def register_epipolar_sequence(self, pairs=None, slot=0, **opts):
         """Epipolar registration of the frames of the last extract() into `slot` against each other:
@@ -202,12 +207,10 @@ class BatchExtractor:
         per-frame poses.  Blocking."""
         points, counts = self.slots[slot]
         if d_depth is not None:
-            assert d_depth.is_cuda and d_depth.element_size() == 2 and d_depth.is_contiguous()
-            assert d_depth.dim() == 3 and d_depth.shape[0] == self.n and d_depth.shape[1] == self.h, tuple(d_depth.shape)
-            assert d_depth.shape[2] >= self.w, tuple(d_depth.shape)
+            pitch, image_stride = self._depth_layout(d_depth)
             self.ctx.lift_depth(points.data_ptr(), self.max_pts, d_depth.data_ptr(), self.w, self.h,
-                                camera2 if depth_camera is None else depth_camera, pitch=d_depth.shape[2],
-                                n_images=self.n, d_counters=counts.data_ptr(), image_stride=self.h * d_depth.shape[2])
+                                camera2 if depth_camera is None else depth_camera, pitch=pitch, n_images=self.n,
+                                d_counters=counts.data_ptr(), image_stride=image_stride)
         return self.ctx.register_pnp_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
                                            self._pairs(pairs), camera2, **opts)
 

@@ -23,6 +23,7 @@
 
 #include "cuSIFT.h"
 #include "cusift_amd_extras.h"
+#include "sequence.h"
 
 // Returns the elapsed milliseconds like the reference.  homography: 9 floats (row-major 3x3, h[8] = 1);
 // *numMatches: inliers of the winning hypothesis among ALL numPts points of `data`.
@@ -208,55 +209,15 @@ inline double RegisterPlanarSequence(std::vector<SiftData *> &frames, std::vecto
                                      std::vector<std::vector<float> > *matchErrors = NULL,
                                      std::vector<std::vector<char> > *inliers = NULL) {
   TimerGPU timer;
-  cusift_ctx *ctx = cusift_dropin::ctx();
   numLoops = iDivUp(numLoops, 16) * 16;  // extras/homography.cu:200
-  const int n = (int)frames.size();
-  if (pairs.empty())
-    for (int i = 0; i + 1 < n; i++) pairs.push_back(std::make_pair(i, i + 1));
-  const int n_pairs = (int)pairs.size();
-  int max_pts = 1;
-  std::vector<unsigned int> counts((size_t)(n > 0 ? n : 1), 0u);
-  for (int i = 0; i < n; i++) {
-    counts[i] = frames[i]->d_data != nullptr && frames[i]->numPts > 0 ? (unsigned int)frames[i]->numPts : 0u;
-    if ((int)counts[i] > max_pts) max_pts = (int)counts[i];
-  }
-  struct block {
-    void *ptr = nullptr;
-    explicit block(size_t bytes) { safeCall(cusift_malloc(&ptr, bytes > 0 ? bytes : 1)); }
-    ~block() { cusift_free(ptr); }
-    block(const block &) = delete;
-    block &operator=(const block &) = delete;
-  };
-  block points(sizeof(SiftPoint) * (size_t)n * (size_t)max_pts), counters(sizeof(unsigned int) * counts.size());
-  safeCall(cusift_memcpy_h2d(ctx, counters.ptr, counts.data(), sizeof(unsigned int) * counts.size()));
-  for (int i = 0; i < n; i++)
-    if (counts[i] > 0)
-      safeCall(cusift_memcpy_d2d(ctx, static_cast<SiftPoint *>(points.ptr) + (size_t)i * max_pts, frames[i]->d_data,
-                                 sizeof(SiftPoint) * (size_t)counts[i]));
-  const size_t slots = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  std::vector<int> h_pairs(2 * slots), candidates(slots), matches(slots), fit(slots);
-  for (int k = 0; k < n_pairs; k++) h_pairs[2 * (size_t)k] = pairs[k].first, h_pairs[2 * (size_t)k + 1] = pairs[k].second;
-  std::vector<float> hom(9 * slots), win(9 * slots);
-  std::vector<char> h_flags(inliers ? (size_t)n_pairs * max_pts : 0);
-  std::vector<float> h_err(matchErrors ? (size_t)n_pairs * max_pts : 0);
-  safeCall(cusift_register_planar_batch(ctx, static_cast<const cusift_point *>(points.ptr),
-                                        static_cast<const unsigned int *>(counters.ptr), n, max_pts, h_pairs.data(),
-                                        n_pairs, distance, rule, minScore, maxAmbiguity, numLoops, thresh, refineLoops,
-                                        refineThresh, seed, hom.data(), win.data(), candidates.data(), matches.data(),
-                                        fit.data(), NULL, inliers ? h_flags.data() : NULL,
-                                        matchErrors ? h_err.data() : NULL));
-  homographies.assign(hom.begin(), hom.begin() + 9 * (size_t)n_pairs);
-  if (ransac) ransac->assign(win.begin(), win.begin() + 9 * (size_t)n_pairs);
-  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + n_pairs);
-  if (numFit) numFit->assign(fit.begin(), fit.begin() + n_pairs);
-  if (inliers) inliers->assign((size_t)n_pairs, std::vector<char>());
-  if (matchErrors) matchErrors->assign((size_t)n_pairs, std::vector<float>());
-  for (int k = 0; k < n_pairs; k++) {
-    const size_t first = (size_t)k * max_pts, count = counts[pairs[k].first];
-    if (inliers) (*inliers)[k].assign(h_flags.begin() + first, h_flags.begin() + first + count);
-    if (matchErrors && candidates[k] >= 8)
-      (*matchErrors)[k].assign(h_err.begin() + first, h_err.begin() + first + count);
-  }
+  cusift_dropin::SequencePack pack(frames, pairs);
+  cusift_dropin::SequenceOutputs<float> out(pack, 9, inliers != NULL, matchErrors != NULL);
+  safeCall(cusift_register_planar_batch(cusift_dropin::ctx(), pack.d_points(), pack.d_counters(), pack.n, pack.max_pts,
+                                        pack.h_pairs.data(), pack.n_pairs, distance, rule, minScore, maxAmbiguity,
+                                        numLoops, thresh, refineLoops, refineThresh, seed, out.model.data(),
+                                        out.winner.data(), out.candidates.data(), out.matches.data(), out.fit.data(),
+                                        NULL, out.flags(), out.errors()));
+  out.finish(&homographies, ransac, numMatches, numFit, out.candidates, 8, matchErrors, inliers);
   return timer.read();
 }
 

@@ -18,6 +18,7 @@
 #include "cuSIFT.h"
 #include "cusift_amd_extras.h"
 #include "epipolar.h"
+#include "sequence.h"
 
 // The pose over the device records of `data`, which carry match fields and coords3D.  The candidates are those of `rule`
 // (as EstimateFundamental's) with a finite coords3D whose z is not 0; *numMatches of them lie within `thresh` px of the
@@ -73,25 +74,15 @@ inline double RegisterPnPSequence(std::vector<SiftData *> &frames, std::vector<s
                                   std::vector<int> *numCandidates = NULL) {
   TimerGPU timer;
   cusift_dropin::SequencePack pack(frames, pairs);
-  const size_t slots = pack.slots(), flat = (size_t)pack.n_pairs * pack.max_pts;
-  std::vector<int> candidates(slots), matches(slots), fit(slots);
-  std::vector<double> rt(12 * slots), win(12 * slots);
-  std::vector<char> h_flags(inliers ? flat : 0);
-  std::vector<float> h_err(matchErrors ? flat : 0);
+  cusift_dropin::SequenceOutputs<double> out(pack, 12, inliers != NULL, matchErrors != NULL);
   safeCall(cusift_register_pnp_batch(cusift_dropin::ctx(), pack.d_points(), pack.d_counters(), pack.n, pack.max_pts,
                                      pack.h_pairs.data(), pack.n_pairs, distance, rule, minScore, maxAmbiguity, camera2,
-                                     numLoops, thresh, refineLoops, refineThresh, seed, rt.data(), win.data(),
-                                     candidates.data(), matches.data(), fit.data(), NULL, inliers ? h_flags.data() : NULL,
-                                     matchErrors ? h_err.data() : NULL));
-  Rts.assign(rt.begin(), rt.begin() + 12 * (size_t)pack.n_pairs);
-  if (ransac) ransac->assign(win.begin(), win.begin() + 12 * (size_t)pack.n_pairs);
-  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + pack.n_pairs);
-  if (numFit) numFit->assign(fit.begin(), fit.begin() + pack.n_pairs);
-  if (numCandidates) numCandidates->assign(candidates.begin(), candidates.begin() + pack.n_pairs);
-  std::vector<char> fitted(slots);
-  for (int k = 0; k < pack.n_pairs; k++) fitted[k] = matches[k] >= 1;  // a fit counts at least its own six samples
-  pack.rows(h_flags, 1, NULL, inliers);
-  pack.rows(h_err, 1, &fitted, matchErrors);
+                                     numLoops, thresh, refineLoops, refineThresh, seed, out.model.data(), out.winner.data(),
+                                     out.candidates.data(), out.matches.data(), out.fit.data(), NULL, out.flags(),
+                                     out.errors()));
+  // a fit counts at least its own six samples
+  out.finish(&Rts, ransac, numMatches, numFit, out.matches, 1, matchErrors, inliers);
+  if (numCandidates) numCandidates->assign(out.candidates.begin(), out.candidates.begin() + pack.n_pairs);
   return timer.read();
 }
 

@@ -16,6 +16,7 @@
 #include "cuSIFT.h"
 #include "cusift_amd_extras.h"
 #include "epipolar.h"
+#include "sequence.h"
 
 // The pose from a fundamental matrix F (9 doubles as EstimateFundamental returns them) over the device records of
 // `data`, which carry match fields.  The fit set is the candidates of `rule` (as EstimateFundamental's) within `thresh`
@@ -71,23 +72,19 @@ inline double RegisterPoseSequence(std::vector<SiftData *> &frames, std::vector<
                                    std::vector<std::vector<char> > *inliers = NULL) {
   TimerGPU timer;
   cusift_dropin::SequencePack pack(frames, pairs);
-  const size_t slots = pack.slots(), flat = (size_t)pack.n_pairs * pack.max_pts;
-  std::vector<int> candidates(slots), matches(slots), fit(slots), front(slots);
-  std::vector<double> fund(9 * slots), win(9 * slots), rt(12 * slots);
-  std::vector<char> h_flags(inliers ? flat : 0);
-  std::vector<float> h_xyz(points3D ? 3 * flat : 0);
+  cusift_dropin::SequenceOutputs<double> out(pack, 9, inliers != NULL, false);  // F's outputs; the pose's own on top
+  std::vector<int> front(pack.slots());
+  std::vector<double> rt(12 * pack.slots());
+  std::vector<float> h_xyz(points3D ? 3 * pack.flat() : 0);
   safeCall(cusift_register_pose_batch(cusift_dropin::ctx(), pack.d_points(), pack.d_counters(), pack.n, pack.max_pts,
                                       pack.h_pairs.data(), pack.n_pairs, distance, rule, minScore, maxAmbiguity, numLoops,
-                                      thresh, refineLoops, refineThresh, seed, camera, camera2, fund.data(), win.data(),
-                                      candidates.data(), matches.data(), fit.data(), NULL,
-                                      inliers ? h_flags.data() : NULL, NULL, rt.data(), front.data(), NULL, NULL,
+                                      thresh, refineLoops, refineThresh, seed, camera, camera2, out.model.data(),
+                                      out.winner.data(), out.candidates.data(), out.matches.data(), out.fit.data(), NULL,
+                                      out.flags(), NULL, rt.data(), front.data(), NULL, NULL,
                                       points3D ? h_xyz.data() : NULL));
+  out.finish(fundamentals, NULL, numMatches, numFit, out.candidates, 8, NULL, inliers);
   Rts.assign(rt.begin(), rt.begin() + 12 * (size_t)pack.n_pairs);
-  if (fundamentals) fundamentals->assign(fund.begin(), fund.begin() + 9 * (size_t)pack.n_pairs);
-  if (numMatches) numMatches->assign(matches.begin(), matches.begin() + pack.n_pairs);
-  if (numFit) numFit->assign(fit.begin(), fit.begin() + pack.n_pairs);
   if (numFront) numFront->assign(front.begin(), front.begin() + pack.n_pairs);
-  pack.rows(h_flags, 1, NULL, inliers);
   pack.rows(h_xyz, 3, NULL, points3D);
   return timer.read();
 }

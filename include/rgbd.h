@@ -21,21 +21,14 @@
 #include "cusift_amd_extras.h"
 #include "matching.h"
 #include "rigidTransform.h"
+#include "sequence.h"
 
 namespace cusift_dropin {
 // a 16-bit depth image on the device, dense rows; freed when it goes out of scope
-struct device_depth {
-  void *ptr = nullptr;
-  device_depth(const unsigned short *h_depth, int w, int h) {
-    const size_t bytes = sizeof(unsigned short) * (size_t)w * (size_t)h;
-    safeCall(cusift_malloc(&ptr, bytes));
-    safeCall(cusift_memcpy_h2d(ctx(), ptr, h_depth, bytes));
+struct device_depth : device_block {
+  device_depth(const unsigned short *h_depth, int w, int h) : device_block(sizeof(unsigned short) * (size_t)w * (size_t)h) {
+    safeCall(cusift_memcpy_h2d(ctx(), ptr, h_depth, sizeof(unsigned short) * (size_t)w * (size_t)h));
   }
-  ~device_depth() {
-    if (ptr) cusift_free(ptr);
-  }
-  device_depth(const device_depth &) = delete;
-  device_depth &operator=(const device_depth &) = delete;
   const uint16_t *get() const { return static_cast<const uint16_t *>(ptr); }
 };
 }  // namespace cusift_dropin
@@ -107,50 +100,25 @@ inline void RegisterRGBDSequence(std::vector<SiftData *> &frames, const std::vec
                                  std::vector<std::vector<std::pair<int, int> > > *selected = NULL,
                                  std::vector<std::vector<char> > *inliers = NULL) {
   cusift_ctx *ctx = cusift_dropin::ctx();
-  const int n = (int)frames.size();
-  if (pairs.empty())
-    for (int i = 0; i + 1 < n; i++) pairs.push_back(std::make_pair(i, i + 1));
-  const int n_pairs = (int)pairs.size();
-  int max_pts = 1;
-  std::vector<unsigned int> counts((size_t)(n > 0 ? n : 1), 0u);
-  for (int i = 0; i < n; i++) {
-    counts[i] = frames[i]->d_data != nullptr && frames[i]->numPts > 0 ? (unsigned int)frames[i]->numPts : 0u;
-    if ((int)counts[i] > max_pts) max_pts = (int)counts[i];
-  }
-  struct block {
-    void *ptr = nullptr;
-    explicit block(size_t bytes) { safeCall(cusift_malloc(&ptr, bytes > 0 ? bytes : 1)); }
-    ~block() { cusift_free(ptr); }
-    block(const block &) = delete;
-    block &operator=(const block &) = delete;
-  };
+  cusift_dropin::SequencePack pack(frames, pairs);  // a copy: the lift and the matcher write it, not the frames
+  const int n_pairs = pack.n_pairs, max_pts = pack.max_pts;
   const size_t image = (size_t)w * (size_t)h;
-  block points(sizeof(SiftPoint) * (size_t)n * (size_t)max_pts), counters(sizeof(unsigned int) * counts.size());
-  block depth(sizeof(unsigned short) * image * (size_t)n);
-  safeCall(cusift_memcpy_h2d(ctx, counters.ptr, counts.data(), sizeof(unsigned int) * counts.size()));
-  for (int i = 0; i < n; i++) {
-    if (counts[i] > 0)
-      safeCall(cusift_memcpy_d2d(ctx, static_cast<SiftPoint *>(points.ptr) + (size_t)i * max_pts, frames[i]->d_data,
-                                 sizeof(SiftPoint) * (size_t)counts[i]));
+  cusift_dropin::device_block depth(sizeof(unsigned short) * image * (size_t)pack.n);
+  for (int i = 0; i < pack.n; i++)
     safeCall(cusift_memcpy_h2d(ctx, static_cast<unsigned short *>(depth.ptr) + (size_t)i * image, h_depths[i],
                                sizeof(unsigned short) * image));
-  }
-  std::vector<int> h_pairs(2 * (size_t)(n_pairs > 0 ? n_pairs : 1)), matches((size_t)(n_pairs > 0 ? n_pairs : 1)),
-      found(matches.size());
-  for (int k = 0; k < n_pairs; k++) h_pairs[2 * (size_t)k] = pairs[k].first, h_pairs[2 * (size_t)k + 1] = pairs[k].second;
-  std::vector<int> h_sel(selected ? 2 * (size_t)n_pairs * max_pts : 0);
-  std::vector<char> h_flags(inliers ? (size_t)n_pairs * max_pts : 0);
-  Rt.assign(12 * (size_t)n_pairs, 0.0f);
-  std::vector<float> rt(12 * matches.size());
-  safeCall(cusift_register_rgbd_batch(ctx, static_cast<cusift_point *>(points.ptr),
-                                      static_cast<const unsigned int *>(counters.ptr), n, max_pts,
-                                      static_cast<const uint16_t *>(depth.ptr), w, h, w, image, &camera, h_pairs.data(),
-                                      n_pairs, distance == MatchSiftDistanceL2 ? 1 : 0, scoreThreshold,
-                                      ambiguityThreshold, numLoops, thresh * thresh,
+  std::vector<int> matches(pack.slots()), found(pack.slots());
+  std::vector<int> h_sel(selected ? 2 * pack.flat() : 0);
+  std::vector<char> h_flags(inliers ? pack.flat() : 0);
+  std::vector<float> rt(12 * pack.slots());
+  safeCall(cusift_register_rgbd_batch(ctx, pack.d_points(), pack.d_counters(), pack.n, max_pts,
+                                      static_cast<const uint16_t *>(depth.ptr), w, h, w, image, &camera,
+                                      pack.h_pairs.data(), n_pairs, distance == MatchSiftDistanceL2 ? 1 : 0,
+                                      scoreThreshold, ambiguityThreshold, numLoops, thresh * thresh,
                                       type == RigidTransformType3D ? 1 : 0, seed ? seed : (uint64_t)std::time(0),
                                       rt.data(), matches.data(), found.data(), selected ? h_sel.data() : NULL,
                                       inliers ? h_flags.data() : NULL));
-  for (size_t i = 0; i < Rt.size(); i++) Rt[i] = rt[i];
+  Rt.assign(rt.begin(), rt.begin() + 12 * (size_t)n_pairs);
   if (numInliers) numInliers->assign(found.begin(), found.begin() + n_pairs);
   if (numMatches) numMatches->assign(matches.begin(), matches.begin() + n_pairs);
   if (selected) {

@@ -3,6 +3,8 @@
 // Three frames: frame 0 with random points, frames 1 and 2 its images under two planted homographies with gross
 // outliers; record i of frame 0 has the descriptor of its partner in both, so the matcher pairs them with a dot product
 // of 1 and no two best scores tie.  The pair list repeats a first member, reverses a pair and holds a self pair.
+// Frame 3 is a default-constructed SiftData, no records and no buffers: the pairs (0, 3), (3, 0) and (3, 3) give what
+// RegisterPlanar gives for them -- the identity, no inliers, flags for frame a's records and no match_error row.
 // Checked, per pair k: homography, winning hypothesis, numMatches, numFit, match_error of every record and the inlier
 // flags have the bits RegisterPlanar gives on fresh copies of the two frames with seed + k; the frames handed to
 // RegisterPlanarSequence keep every byte; the refined homography of the planted pairs lies within 0.5 px (corners) of
@@ -93,6 +95,7 @@ int main() {
     }
     auto upload = [&](SiftData &d, const std::vector<SiftPoint> &src) {
       const int n = (int)src.size();
+      if (n == 0) return;  // as constructed: d_data == nullptr, numPts == 0
       InitSiftData(d, n, true, true);
       std::memcpy(d.h_data, src.data(), sizeof(SiftPoint) * n);
       d.numPts = n;
@@ -101,10 +104,11 @@ int main() {
 
     const uint64_t seed = 11;
     const int loops = 1000;
-    std::vector<std::pair<int, int> > pairs = {{0, 1}, {0, 2}, {1, 0}, {0, 1}, {2, 2}};
-    std::vector<SiftData> frames(3);
+    std::vector<std::pair<int, int> > pairs = {{0, 1}, {0, 2}, {1, 0}, {0, 1}, {2, 2}, {0, 3}, {3, 0}, {3, 3}};
+    f.resize(4);  // frame 3: no records
+    std::vector<SiftData> frames(4);
     std::vector<SiftData *> ptrs;
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < 4; i++) {
       upload(frames[i], f[i]);
       ptrs.push_back(&frames[i]);
     }
@@ -133,8 +137,15 @@ int main() {
       EXPECT(std::memcmp(H1, &hom[9 * k], sizeof(H1)) == 0, "pair %zu: homography differs", k);
       EXPECT(std::memcmp(R1, &win[9 * k], sizeof(R1)) == 0, "pair %zu: winner differs", k);
       EXPECT(m1 == matches[k] && fit1 == fit[k], "pair %zu: counts %d %d, pair call %d %d", k, matches[k], fit[k], m1, fit1);
-      EXPECT((int)errors[k].size() == na && (int)flags[k].size() == na, "pair %zu: %zu errors, %zu flags for %d records", k,
-             errors[k].size(), flags[k].size(), na);
+      EXPECT((int)flags[k].size() == na, "pair %zu: %zu flags for %d records", k, flags[k].size(), na);
+      if (f[a].empty() || f[b].empty()) {  // nothing to match: no fit, so no match_error row
+        const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        EXPECT(std::memcmp(ident, &hom[9 * k], sizeof(ident)) == 0 && matches[k] == 0 && fit[k] == 0 && errors[k].empty() &&
+                   flags[k] == std::vector<char>((size_t)na, 0),
+               "pair %zu: %d inliers, %d fit, %zu errors with an empty frame", k, matches[k], fit[k], errors[k].size());
+        continue;
+      }
+      EXPECT((int)errors[k].size() == na, "pair %zu: %zu errors for %d records", k, errors[k].size(), na);
       int same = 0, marked = 0;
       for (int i = 0; i < na && (int)errors[k].size() == na; i++)
         same += std::memcmp(&d1.h_data[i].match_error, &errors[k][i], sizeof(float)) == 0;
@@ -148,11 +159,14 @@ int main() {
         EXPECT(matches[k] >= (int)(0.9 * 0.6 * nOther[k]), "pair %zu: %d inliers", k, matches[k]);
       }
     }
-    // the default pair list is the walk (i, i + 1); an empty sequence is no error
-    std::vector<std::pair<int, int> > none;
-    std::vector<float> walk;
+    // the default pair list is the walk (i, i + 1), byte for byte; an empty sequence is no error
+    std::vector<std::pair<int, int> > none, steps = {{0, 1}, {1, 2}, {2, 3}};
+    std::vector<float> walk, stepped;
     RegisterPlanarSequence(ptrs, none, walk, NULL, NULL, loops, lo, hi, 5.0f, 5, 3.0f, seed);
-    EXPECT(walk.size() == 18 && std::memcmp(walk.data(), hom.data(), 9 * sizeof(float)) == 0, "default pairs");
+    RegisterPlanarSequence(ptrs, steps, stepped, NULL, NULL, loops, lo, hi, 5.0f, 5, 3.0f, seed);
+    EXPECT(walk.size() == 27 && std::memcmp(walk.data(), hom.data(), 9 * sizeof(float)) == 0, "default pairs");
+    EXPECT(walk.size() == stepped.size() && std::memcmp(walk.data(), stepped.data(), sizeof(float) * walk.size()) == 0,
+           "the default pairs differ from the explicit walk");
     std::vector<SiftData *> nobody;
     RegisterPlanarSequence(nobody, none, walk);
     EXPECT(walk.empty(), "an empty sequence gave %zu floats", walk.size());

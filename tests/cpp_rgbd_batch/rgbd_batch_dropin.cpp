@@ -1,7 +1,9 @@
 // The reference walks its sequences frame by frame (main.cpp: compareMatchingWithMATLAB, i -> i + 1).  This program
 // registers a short sequence made of the reference's own pair -- frames 1, 2, 1 -- in ONE RegisterRGBDSequence call with
 // the pair list (0,1) (1,2) (0,2) (1,1), and checks it against RegisterRGBD called pair by pair with the same seeds:
-// pair k of the sequence call draws from seed + k, so every Rt must come out with the same bits.
+// pair k of the sequence call draws from seed + k, so every Rt must come out with the same bits.  A fourth frame has a
+// depth image and no records (a default-constructed SiftData): the pairs (0,3) and (3,1) give the identity, no matches
+// and empty rows, as RegisterRGBD does.  An empty pair list is the walk (i, i + 1); no frames give empty outputs.
 //
 //   rgbd_batch_dropin sift1.bin sift2.bin depth1.u16 depth2.u16 intrinsics.txt
 // depth*.u16: 640 x 480 raw little-endian 16-bit samples as stored in the reference's PNGs (the Python test writes them
@@ -62,16 +64,17 @@ int main(int argc, char **argv) {
   cam.fx = (float)K[0], cam.fy = (float)K[4], cam.cx = (float)K[2], cam.cy = (float)K[5];
   cam.origin = 1.0f, cam.units_per_metre = 1000.0f, cam.encoding = 1;
 
-  SiftData f0, f1, f2;
+  SiftData f0, f1, f2, f3;  // f3 as constructed: d_data == nullptr, numPts == 0
   EXPECT(ReadVLFeatSiftData(f0, argv[1]) > 0 && ReadVLFeatSiftData(f1, argv[2]) > 0 && ReadVLFeatSiftData(f2, argv[1]) > 0,
          "cannot read the VLFeat dumps");
   std::vector<SiftData *> frames;
-  frames.push_back(&f0), frames.push_back(&f1), frames.push_back(&f2);
+  frames.push_back(&f0), frames.push_back(&f1), frames.push_back(&f2), frames.push_back(&f3);
   std::vector<const unsigned short *> depths;
   depths.push_back(depth1.data()), depths.push_back(depth2.data()), depths.push_back(depth1.data());
+  depths.push_back(depth2.data());  // every frame's depth is uploaded, also that of the frame without records
   std::vector<std::pair<int, int> > pairs;
   pairs.push_back(std::make_pair(0, 1)), pairs.push_back(std::make_pair(1, 2)), pairs.push_back(std::make_pair(0, 2));
-  pairs.push_back(std::make_pair(1, 1));
+  pairs.push_back(std::make_pair(1, 1)), pairs.push_back(std::make_pair(0, 3)), pairs.push_back(std::make_pair(3, 1));
 
   // ---- the whole list in one call (first: it leaves the frames' own records untouched) ----
   std::vector<float> Rt;
@@ -88,8 +91,8 @@ int main(int argc, char **argv) {
   // ---- pair by pair, on fresh copies of the records, pair k with seed + k ----
   for (size_t k = 0; k < pairs.size(); k++) {
     SiftData a, b;
-    ReadVLFeatSiftData(a, argv[pairs[k].first == 1 ? 2 : 1]);
-    ReadVLFeatSiftData(b, argv[pairs[k].second == 1 ? 2 : 1]);
+    if (pairs[k].first != 3) ReadVLFeatSiftData(a, argv[pairs[k].first == 1 ? 2 : 1]);
+    if (pairs[k].second != 3) ReadVLFeatSiftData(b, argv[pairs[k].second == 1 ? 2 : 1]);
     float one[12];
     int in = -1, nm = -1;
     std::vector<std::pair<int, int> > sel;
@@ -105,8 +108,33 @@ int main(int argc, char **argv) {
            nm, numMatches[k]);
     EXPECT(sel == selected[k], "pair %zu: other selected matches", k);
     EXPECT(flags == inliers[k], "pair %zu: other inlier flags", k);
+    if (pairs[k].first == 3 || pairs[k].second == 3) {
+      const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+      EXPECT(std::memcmp(ident, Rt.data() + 12 * k, sizeof(ident)) == 0 && numMatches[k] == 0 && numInliers[k] == 0 &&
+                 selected[k].empty() && inliers[k].empty(),
+             "pair %zu: %d matches, %d inliers, %zu selected with an empty frame", k, numMatches[k], numInliers[k],
+             selected[k].size());
+    }
     std::printf("pair (%d, %d): matches %d, inliers %d\n", pairs[k].first, pairs[k].second, numMatches[k], numInliers[k]);
   }
+  // an empty pair list is the walk (i, i + 1), byte for byte; a sequence without frames gives empty outputs and no error
+  std::vector<std::pair<int, int> > none, steps;
+  for (int i = 0; i + 1 < 4; i++) steps.push_back(std::make_pair(i, i + 1));
+  std::vector<float> walk, stepped;
+  std::vector<int> walkIn, walkM, steppedIn, steppedM;
+  RegisterRGBDSequence(frames, depths, W, H, cam, none, walk, &walkIn, &walkM, 1024, 0.05f, RigidTransformType3D,
+                       MatchSiftDistanceL2, 1000.0f, 0.6f, kSeed);
+  RegisterRGBDSequence(frames, depths, W, H, cam, steps, stepped, &steppedIn, &steppedM, 1024, 0.05f, RigidTransformType3D,
+                       MatchSiftDistanceL2, 1000.0f, 0.6f, kSeed);
+  EXPECT(walk.size() == 36 && walk.size() == stepped.size() &&
+             std::memcmp(walk.data(), stepped.data(), sizeof(float) * walk.size()) == 0 && walkIn == steppedIn && walkM == steppedM,
+         "the default pairs differ from the explicit walk");
+  EXPECT(walk.size() >= 12 && std::memcmp(walk.data(), Rt.data(), 12 * sizeof(float)) == 0, "the walk's pair (0, 1)");
+  std::vector<SiftData *> nobody;
+  std::vector<const unsigned short *> noDepths;
+  RegisterRGBDSequence(nobody, noDepths, W, H, cam, none, walk, &walkIn, &walkM, 1024, 0.05f, RigidTransformType3D,
+                       MatchSiftDistanceL2, 1000.0f, 0.6f, kSeed);
+  EXPECT(walk.empty() && walkIn.empty() && walkM.empty(), "an empty sequence gave %zu floats", walk.size());
   std::printf(failures ? "FAILED (%d)\n" : "PASSED\n", failures);
   return failures ? 1 : 0;
 }
