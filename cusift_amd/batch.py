@@ -144,6 +144,29 @@ class BatchExtractor:
         n_i, n_j = self._pair_counts(counts, i, j)
         return self.ctx.register_epipolar(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, **opts)
 
+    def match_guided(self, i, j, model, m, radius, slot=0, distance=1):
+        """Guided match of frames i and j of the last extract() into `slot`: cusift_match_guided over this extractor's
+        device records (frame i's match fields are written) -- frame j's records that fail `model` ("homography": x_j ~ m
+        x_i; "epipolar": x_j^T m x_i = 0) by more than `radius` pixels cannot be a record's match.  The two counts are
+        read with one call.  Asynchronous on the extractor's stream."""
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        self.ctx.match_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, model, m, radius, distance)
+
+    def register_planar_guided(self, i, j, radius=None, slot=0, **opts):
+        """register_planar(i, j) with a second, guided matching pass: capi.Context.register_planar_guided over this
+        extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.  Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_planar_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, radius, **opts)
+
+    def register_epipolar_guided(self, i, j, radius=None, slot=0, **opts):
+        """register_epipolar(i, j) with a second, guided matching pass: capi.Context.register_epipolar_guided over this
+        extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.  Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_epipolar_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, radius, **opts)
+
     def register_pose(self, i, j, camera, camera2=None, slot=0, **opts):
         """Calibrated two-view pose of frames i and j of the last extract() into `slot`: cusift_register_pose over this
         extractor's device records (frame i's match fields, match_error and coords3D are written).  camera: the

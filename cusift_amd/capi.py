@@ -204,6 +204,7 @@ SIGNATURES = {
     "cusift_describe_band": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _i, _i, _vp]),
     "cusift_match": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "cusift_match_mutual": (_i, [_vp, _vp, _i, _vp, _i, _i]),
+    "cusift_match_guided": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _f]),
     "cusift_memcpy2d_d2h": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
     "cusift_find_homography": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, C.POINTER(_i), _vp, _vp]),
     "cusift_estimate_homography": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp, C.POINTER(_i),
@@ -233,6 +234,7 @@ SIGNATURES = {
                                   C.c_uint64, _vp, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
     "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cusift_match_batch_mutual": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "cusift_match_batch_guided": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _vp]),
     "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
@@ -477,6 +479,19 @@ def check_select_strongest_args(d_heads, n_lists, n_images, capacity, d_counts, 
         raise ValueError("select_strongest: %d lists x %d images x %d heads are too many" % (n_lists, n_images, capacity))
 
 
+GUIDE_MODELS = {"homography": 0, "epipolar": 1}  # CUSIFT_GUIDE_HOMOGRAPHY / CUSIFT_GUIDE_EPIPOLAR
+
+
+def guide_models(model, m, n_models=None):
+    """(model as the C ABI's int, the matrices as contiguous float64 [n, 9]) of a guided match: `model` is
+    "homography" / "epipolar" or 0 / 1 (anything else is handed through for the library to refuse), `m` one 3 x 3 or
+    9-vector -- or n_models of them -- of any float type (register_planar's float32 H is widened)."""
+    m = np.ascontiguousarray(m, dtype=np.float64).reshape(-1, 9)
+    if len(m) != (1 if n_models is None else n_models):
+        raise ValueError("guided match: %d models for %d pairs" % (len(m), 1 if n_models is None else n_models))
+    return GUIDE_MODELS.get(model, model), m
+
+
 def pair_list(pairs):
     """A pair list as the C ABI takes it: contiguous int32 [P, 2] of (frame 1, frame 2)."""
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -534,6 +549,7 @@ class Context:
         else:
             check(lib().cusift_ctx_create_borrowed(C.byref(self._h), device, C.c_void_p(int(stream))))
         self.device = device
+        self.cross_check = False  # what set_cross_check last set: the guided chains refuse to run while it is on
 
     @property
     def handle(self):
@@ -759,6 +775,16 @@ class Context:
         written: overlapping ranges are refused.  Asynchronous."""
         check(lib().cusift_match_mutual(self.handle, d_sift1, n1, d_sift2, n2, distance))
 
+    def match_guided(self, d_sift1, n1, d_sift2, n2, model, m, radius, distance=1):
+        """cusift_match_guided: match() where a record of d_sift2 whose coords2D fail the geometric test against a row's
+        coords2D cannot be that row's best or second best.  model "homography" (0): m = H with x2 ~ H x1, the test is
+        |x2 - H x1| < radius; "epipolar" (1): m = F with x2^T F x1 = 0, the test is the distance of x2 from the line
+        F x1 < radius.  m: 3 x 3 or 9 values, widened to float64.  A row that nothing passes ends with match = -1.
+        Asynchronous; m is read before the call returns."""
+        model, m = (GUIDE_MODELS.get(model, model), None) if m is None else guide_models(model, m)
+        check(lib().cusift_match_guided(self.handle, d_sift1, n1, d_sift2, n2, distance, model,
+                                        None if m is None else m.ctypes.data, radius))
+
     def find_homography(self, d_sift, num_pts, rand_pts, thresh=5.0, want_all=False):
         """cusift_find_homography: rand_pts is an int32 array [4, num_loops] of sample indices into d_sift.
         Returns (H[9], num_matches) or, with want_all, (H, num_matches, all_homographies[8, L], all_counts[L])."""
@@ -841,6 +867,36 @@ class Context:
         return self._ransac(self._F, lambda *out: lib().cusift_register_epipolar(
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
             _seed64(seed), *out), n1, max(loops, 0), want_all)
+
+    def _guided_chain(self, register, estimate, model, thresh, d_sift1, n1, d_sift2, n2, radius, opts):
+        """register -> match_guided under the refined model -> estimate over the rewritten records, same options."""
+        if self.cross_check:
+            raise CusiftError("guided registration: turn the cross-check off first (set_cross_check(False)) -- the "
+                              "guided matcher has no column side")
+        first = register(d_sift1, n1, d_sift2, n2, **opts)
+        distance = opts.get("distance", 1)
+        rule, lo, hi = _rule_defaults(distance, opts.get("rule"), opts.get("lo"), opts.get("hi"))
+        self.match_guided(d_sift1, n1, d_sift2, n2, model, first[0], opts.get("thresh", thresh) if radius is None else radius,
+                          distance)
+        again = {k: v for k, v in opts.items() if k != "distance"}
+        again.update(rule=rule, lo=lo, hi=hi)
+        return first, estimate(d_sift1, n1, n2, **again)
+
+    def register_planar_guided(self, d_sift1, n1, d_sift2, n2, radius=None, **opts):
+        """The second matching pass of a planar registration: register_planar(**opts), then match_guided under the refined
+        homography it returned (radius None: that call's thresh), then estimate_homography over the rewritten records of
+        d_sift1 with num_pts2 = n2 and the same options and seed.  Matches that the ratio test of the first pass threw
+        away because a look-alike scored as well come back when the look-alike lies elsewhere.  Returns (first pass,
+        guided pass), two PlanarResults.  CusiftError while the cross-check is on.  Blocking, twice."""
+        return self._guided_chain(self.register_planar, self.estimate_homography, "homography", 5.0, d_sift1, n1, d_sift2,
+                                  n2, radius, opts)
+
+    def register_epipolar_guided(self, d_sift1, n1, d_sift2, n2, radius=None, **opts):
+        """register_planar_guided for two views of a general scene: register_epipolar(**opts), match_guided under the
+        refined fundamental matrix (radius None: that call's thresh, pixels from the epipolar line), estimate_fundamental
+        over the rewritten records.  Returns (first pass, guided pass), two EpipolarResults."""
+        return self._guided_chain(self.register_epipolar, self.estimate_fundamental, "epipolar", 1.0, d_sift1, n1, d_sift2,
+                                  n2, radius, opts)
 
     @staticmethod
     def _pose(call):
@@ -952,6 +1008,7 @@ class Context:
         The four pair calls then write the match fields of d_sift2 as well and refuse overlapping record ranges.  Nothing
         else changes."""
         check(lib().cusift_ctx_set_cross_check(self.handle, check_cross_check(on)))
+        self.cross_check = bool(on)
 
     def select_strongest(self, d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
         """cusift_select_strongest: the selection alone, on lists of 64-byte record heads.  d_heads [n_lists, n_images,
@@ -1009,6 +1066,16 @@ class Context:
         pairs = pair_list(pairs)
         check(lib().cusift_match_batch_mutual(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
                                               len(pairs), distance, d_rows, d_rows_back))
+
+    def match_batch_guided(self, d_points, d_counters, n_images, max_pts, pairs, model, m, radius, d_rows, distance=1):
+        """cusift_match_batch_guided: match_batch() with match_guided()'s rule, pair p under m[p] (float [P, 3, 3] or
+        [P, 9], widened to float64; one kind of `model` and one radius for the list).  Asynchronous; m is read before the
+        call returns."""
+        pairs = pair_list(pairs)
+        model, m = (GUIDE_MODELS.get(model, model), None) if m is None else guide_models(model, m, len(pairs))
+        check(lib().cusift_match_batch_guided(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
+                                              len(pairs), distance, model, None if m is None else m.ctypes.data, radius,
+                                              d_rows))
 
     def register_rgbd_batch(self, d_points, d_counters, n_images, max_pts, d_depth, w, h, camera, pairs, pitch=None,
                             image_stride=None, distance=1, score_threshold=999.0, ambiguity_threshold=1.0, loops=1024,

@@ -1,11 +1,16 @@
 // match_tile.inc -- the body shared by match_kernel and match_batch_kernel (sift_match.hip): one workgroup's 64 rows
 // (descriptors p1_base .. p1_base + 15 of this wave) against the columns [col_begin, col_end) of sift2.  Included inside
-// a kernel that has in scope: kL2, kInit, sB, lane, wv, r, g, p1_base, sift1, n1, sift2, col_begin, col_end, cols.  On
-// exit lane r == 0 of every 16-lane group g holds best[q], second[q], bidx[q] of rows p1_base + 4 g + q (q = 0..3).
+// a kernel that has in scope: kL2, kInit, sB, lane, wv, r, g, p1_base, sift1, n1, sift2, col_begin, col_end, cols and
+// guide.  On exit lane r == 0 of every 16-lane group g holds best[q], second[q], bidx[q] of rows p1_base + 4 g + q
+// (q = 0..3).
 // One text, so that a (row, column) dot product is the same k-ordered MFMA chain whichever kernel computes it.
 // `cols` is the column side (sift_match.hip): NoColumnSide in the one-directional kernels, whose three calls below are
 // empty inline functions -- no barrier, no LDS, no register (tools/kernel_regs.py: 96 VGPRs, 16,896 B as before);
 // ColumnSide in the mutual kernels.
+// `guide` is the geometric predicate of the guided kernels (sift_match.hip): NoGuide everywhere else, again nothing but
+// empty inline functions; GuideH / GuideF keep the per-row terms of this lane's rows 4g + q in registers (rows()), stage
+// coords2D of a tile's 32 columns into floats 128..129 of the columns' LDS rows (fetch() / store(), the descriptors'
+// range-checked buffer resource, no new LDS) and turn a (row, column) that fails the test into kInit in the update.
   // A fragments: lane (r, g) holds elements 16u + 4g + j of descriptor p1_base + r (u = 0..7, j = 0..3)
   float a[8][4];
   {
@@ -25,6 +30,7 @@
     best[q] = second[q] = kInit;
     bidx[q] = -1;
   }
+  guide.rows(sift1, n1, p1_base, lane);
 
   // staging: thread t moves four 16-byte chunks per tile; chunk c = t + 256 i -> descriptor c >> 5, floats 4 (c & 31).
   // Raw buffer loads from a descriptor based at this split's first column: the lane offset is computed once, the tile
@@ -39,6 +45,7 @@
     const int soff = __builtin_amdgcn_readfirstlane((c0 - col_begin) * kRec);
 #pragma unroll
     for (int i = 0; i < 4; ++i) stage[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc2, voff, soff + 8 * i * kRec, 0);
+    guide.fetch(rsrc2, soff);
   };
   if (col_begin < col_end) fetch(col_begin);
   const float *brow = sB + r * kBStride + 4 * g;
@@ -49,9 +56,12 @@
       const int c = threadIdx.x + 256 * i;
       *reinterpret_cast<u4 *>(sB + (c >> 5) * kBStride + 4 * (c & 31)) = stage[i];
     }
+    guide.store(sB);
     __syncthreads();
     if (c0 + kMatchTileCols < col_end) fetch(c0 + kMatchTileCols);  // in flight while this tile is multiplied
     if (c0 > col_begin) cols.drain(c0 - kMatchTileCols, col_begin, col_end, lane, wv);  // the previous tile's columns
+    // this lane's two columns' coordinates, read in front of the MFMAs so that the update does not wait for LDS
+    const auto xy2a = guide.column(sB, r), xy2b = guide.column(sB, 16 + r);
 
     // two independent 16x16 accumulators (columns c0 + r and c0 + 16 + r), each a k-ordered chain; the B fragments
     // of step u + 1 are read from LDS before the MFMAs of step u are issued
@@ -83,12 +93,14 @@
       for (int t = 0; t < 2; ++t) {
         const int p2 = c0 + 16 * t + r;
         const bool live = full || p2 < col_end;
+        const auto xy2 = t ? xy2b : xy2a;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float dot = t ? acc1[q] : acc0[q];
           // ComputeL2Distance :71-72, 2 - 2*dot (2*dot is exact, so the fused form has the same bits)
           float val = kL2 ? (dot > -1.0f ? __builtin_fmaf(-2.0f, dot, 2.0f) : kMatchFltMax) : dot;
-          val = live ? val : kInit;
+          // `live` stays in the condition: a column past col_end reads as zeros, and (0, 0) can pass a guide
+          val = (live && guide.pass(q, xy2)) ? val : kInit;
           top2_update<kL2>(best[q], second[q], bidx[q], val, p2);
         }
       }

@@ -74,6 +74,14 @@ __global__ void match_batch_mutual_kernel(const cusift_point *, const unsigned i
                                           MatchPartial *, int, cusift_match_row *, MatchPartial *, cusift_match_row *);
 __global__ void match_batch_mutual_merge_kernel(const unsigned int *, int, const int *, int, const MatchPartial *, int,
                                                 cusift_match_row *);
+struct GuideH;  // the geometric predicates of the guided matchers (sift_match.hip)
+struct GuideF;
+template <bool kL2, class Guide>
+__global__ void match_guided_kernel(cusift_point *, int, const cusift_point *, int, int, MatchPartial *, int, GuideModel,
+                                    float);
+template <bool kL2, class Guide>
+__global__ void match_batch_guided_kernel(const cusift_point *, const unsigned int *, int, const int *, int,
+                                          MatchPartial *, int, cusift_match_row *, const GuideModel *, float);
 __global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                        const cusift_match_row *, float, float, int, int *, float *, int *,
                                        const cusift_match_row *);

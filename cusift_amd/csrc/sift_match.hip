@@ -84,6 +84,24 @@ struct NoColumnSide {
   __device__ __forceinline__ void finish(A...) const {}
 };
 
+// The geometric predicate of a tile as match_tile.inc sees it: rows() before the column loop, fetch() / store() beside
+// the descriptors' staging, column() and pass() in the update.  NoGuide is every unguided kernel's: empty inline
+// functions and a test that is always true.  GuideH / GuideF (cusift_match_guided) are defined with their kernels below.
+struct NoGuide {
+  struct Column {};
+  template <class... A>
+  __device__ __forceinline__ void rows(A...) const {}
+  template <class... A>
+  __device__ __forceinline__ void fetch(A...) const {}
+  template <class... A>
+  __device__ __forceinline__ void store(A...) const {}
+  template <class... A>
+  __device__ __forceinline__ Column column(A...) const {
+    return Column{};
+  }
+  __device__ __forceinline__ bool pass(int, Column) const { return true; }
+};
+
 // One workgroup = 64 descriptors of image 1 (16 per wave) x one contiguous range of image 2's columns
 // (blockIdx.y = column split; the host picks the number of splits so that the grid fills 256 CUs even for a few
 // thousand keypoints).  With one split the kernel writes the final fields; otherwise the (best, second, index)
@@ -102,6 +120,7 @@ __global__ void __launch_bounds__(256) match_kernel(cusift_point *__restrict__ s
   const int col_end = min(col_begin + cols_per_split, n2);  // padded columns (:57) can never win: skip them
   constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;       // also what a masked column scores: it changes nothing
   const NoColumnSide cols;
+  const NoGuide guide;
 
 #include "match_tile.inc"
   if (r == 0) {
@@ -182,6 +201,7 @@ __global__ void __launch_bounds__(256) match_batch_kernel(const cusift_point *__
   const int col_end = min(col_begin + cols_per_split, n2);
   constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
   const NoColumnSide cols;
+  const NoGuide guide;
 
 #include "match_tile.inc"
   if (r == 0) {
@@ -338,6 +358,7 @@ __global__ void __launch_bounds__(256) match_mutual_kernel(cusift_point *sift1, 
     }
   };
   const ColumnSide<kL2, decltype(col_out)> cols{sColBest, sColSecond, sColIdx, n1, col_out};
+  const NoGuide guide;
 
 #include "match_tile.inc"
   if (r == 0) {
@@ -418,6 +439,7 @@ __global__ void __launch_bounds__(256) match_batch_mutual_kernel(const cusift_po
     }
   };
   const ColumnSide<kL2, decltype(col_out)> cols{sColBest, sColSecond, sColIdx, n1, col_out};
+  const NoGuide guide;
 
 #include "match_tile.inc"
   if (r == 0) {
@@ -467,5 +489,187 @@ __global__ void __launch_bounds__(256) match_batch_mutual_merge_kernel(const uns
   }
   write_match_row(rows_back + (size_t)pair * max_pts + j, m.best, m.second, m.idx, l2);
 }
+
+// ---- nearest neighbours under a known H or F (cusift_match_guided, cusift_match_batch_guided) ------------------------
+// match_kernel with one more rule: a column whose coords2D fail the geometric test against the row's coords2D scores
+// kInit for that row, which changes nothing in the scan.  The definition, expression by expression, is in
+// include/cusift_amd_extras.h; per row it is fp64 and evaluated once, before the column loop -- lane (r, g) computes row
+// 4g + (r & 3) of its wave and the four lanes of a quad exchange, so every lane ends with the terms of its rows 4g + q in
+// registers -- and per (row, column) it is a handful of fp32 operations in the update, beside the MFMAs of the other
+// waves.  The columns' coordinates ride in the four spare floats of the LDS rows (kBStride 132, 128 used): the first 32
+// threads load them through the descriptors' buffer resource, so a column past col_end reads (0, 0) -- and is still
+// masked by `live`, because (0, 0) can pass.
+struct GuideColumns {
+  struct Column {
+    float x, y;
+  };
+  const double *m;  // the model, row-major
+  float r2;         // radius * radius
+  u2 staged;        // threads 0..31: coords2D of column c0 + threadIdx.x of the tile in flight
+
+  __device__ __forceinline__ void fetch(__amdgpu_buffer_rsrc_t rsrc2, int soff) {
+    if (threadIdx.x < kMatchTileCols)
+      staged = __builtin_amdgcn_raw_buffer_load_b64(
+          rsrc2, (int)threadIdx.x * (int)sizeof(cusift_point) + (int)offsetof(cusift_point, coords2D), soff, 0);
+  }
+  __device__ __forceinline__ void store(float *sB) const {
+    if (threadIdx.x < kMatchTileCols) *reinterpret_cast<u2 *>(sB + threadIdx.x * kBStride + 128) = staged;
+  }
+  __device__ __forceinline__ Column column(const float *sB, int j) const {
+    const f2 v = *reinterpret_cast<const f2 *>(sB + j * kBStride + 128);
+    return Column{v[0], v[1]};
+  }
+  // coords2D of the row this lane evaluates, and what the quad's lane q evaluated
+  __device__ __forceinline__ const float *row_xy(const cusift_point *__restrict__ sift1, int n1, int p1_base,
+                                                 int lane) const {
+    return sift1[min(p1_base + 4 * (lane >> 4) + (lane & 3), n1 - 1)].coords2D;
+  }
+  static __device__ __forceinline__ float from_quad(float v, int lane, int q) { return __shfl(v, (lane & ~3) | q); }
+};
+
+// x2 ~ H x1: the row's image (px, py), then |x2 - p|^2 < r2.  W == 0 gives an infinity or a NaN: no pass.
+struct GuideH : GuideColumns {
+  float px[4], py[4];
+  __device__ __forceinline__ void rows(const cusift_point *__restrict__ sift1, int n1, int p1_base, int lane) {
+    const float *xy = row_xy(sift1, n1, p1_base, lane);
+    const double x1 = xy[0], y1 = xy[1];
+    const double X = (m[0] * x1 + m[1] * y1) + m[2];
+    const double Y = (m[3] * x1 + m[4] * y1) + m[5];
+    const double W = (m[6] * x1 + m[7] * y1) + m[8];
+    const float x = (float)(X / W), y = (float)(Y / W);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      px[q] = from_quad(x, lane, q);
+      py[q] = from_quad(y, lane, q);
+    }
+  }
+  __device__ __forceinline__ bool pass(int q, Column c) const {
+    const float dx = c.x - px[q], dy = c.y - py[q];
+    return dx * dx + dy * dy < r2;
+  }
+};
+
+// x2^T F x1 = 0: the row's epipolar line scaled to a unit normal (a, b, c), then (a x2 + b y2 + c)^2 < r2.  A line whose
+// normal has length 0 or that is not finite is three NaNs: no pass for the whole row.
+struct GuideF : GuideColumns {
+  float a[4], b[4], c[4];
+  __device__ __forceinline__ void rows(const cusift_point *__restrict__ sift1, int n1, int p1_base, int lane) {
+    const float *xy = row_xy(sift1, n1, p1_base, lane);
+    const double x1 = xy[0], y1 = xy[1];
+    const double l0 = (m[0] * x1 + m[1] * y1) + m[2];
+    const double l1 = (m[3] * x1 + m[4] * y1) + m[5];
+    const double l2 = (m[6] * x1 + m[7] * y1) + m[8];
+    const double n = sqrt(l0 * l0 + l1 * l1);
+    const double kInf = __builtin_huge_val();
+    const bool line = n > 0.0 && n < kInf && fabs(l2) < kInf;
+    const float kNaN = __builtin_nanf("");
+    const float la = line ? (float)(l0 / n) : kNaN, lb = line ? (float)(l1 / n) : kNaN, lc = line ? (float)(l2 / n) : kNaN;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      a[q] = from_quad(la, lane, q);
+      b[q] = from_quad(lb, lane, q);
+      c[q] = from_quad(lc, lane, q);
+    }
+  }
+  __device__ __forceinline__ bool pass(int q, Column p) const {
+    const float d = (a[q] * p.x + b[q] * p.y) + c[q];
+    return d * d < r2;
+  }
+};
+
+template <bool kL2, class Guide>
+__global__ void __launch_bounds__(256) match_guided_kernel(cusift_point *__restrict__ sift1, int n1,
+                                                          const cusift_point *__restrict__ sift2, int n2,
+                                                          int cols_per_split, MatchPartial *__restrict__ partials,
+                                                          int n1_pad, GuideModel model, float r2) {
+  __shared__ float sB[kMatchTileCols * kBStride];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  const int col_begin = blockIdx.y * cols_per_split;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+  const NoColumnSide cols;
+  Guide guide;
+  guide.m = model.m;
+  guide.r2 = r2;
+
+#include "match_tile.inc"
+  if (r == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p1 = p1_base + 4 * g + q;
+      if (p1 >= n1) continue;
+      if (partials) {
+        MatchPartial mp;
+        mp.best = best[q];
+        mp.second = second[q];
+        mp.idx = bidx[q];
+        partials[(size_t)blockIdx.y * n1_pad + p1] = mp;
+      } else {
+        write_match(sift1 + p1, sift2, n2, best[q], second[q], bidx[q], kL2);
+      }
+    }
+  }
+}
+
+// match_batch_kernel with pair blockIdx.z's model from models[pair] (a device copy of the caller's array)
+template <bool kL2, class Guide>
+__global__ void __launch_bounds__(256) match_batch_guided_kernel(const cusift_point *__restrict__ points,
+                                                                const unsigned int *__restrict__ counters,
+                                                                int max_pts, const int *__restrict__ pairs,
+                                                                int cols_per_split, MatchPartial *__restrict__ partials,
+                                                                int n1_pad, cusift_match_row *__restrict__ rows,
+                                                                const GuideModel *__restrict__ models, float r2) {
+  __shared__ float sB[kMatchTileCols * kBStride];
+  const int pair = blockIdx.z;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const int col_begin = blockIdx.y * cols_per_split;
+  if ((int)blockIdx.x * kMatchRowsPerBlock >= n1 || col_begin >= n2) return;  // uniform: no rows or no columns
+  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
+  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
+  const NoColumnSide cols;
+  Guide guide;
+  guide.m = models[pair].m;
+  guide.r2 = r2;
+
+#include "match_tile.inc"
+  if (r == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p1 = p1_base + 4 * g + q;
+      if (p1 >= n1) continue;
+      if (partials) {
+        MatchPartial mp;
+        mp.best = best[q];
+        mp.second = second[q];
+        mp.idx = bidx[q];
+        partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = mp;
+      } else {
+        write_match_row(rows + (size_t)pair * max_pts + p1, best[q], second[q], bidx[q], kL2);
+      }
+    }
+  }
+}
+
+#define CUSIFT_GUIDED_KERNELS(kL2, Guide)                                                                               \
+  template __global__ void match_guided_kernel<kL2, Guide>(cusift_point *, int, const cusift_point *, int, int,          \
+                                                           MatchPartial *, int, GuideModel, float);                      \
+  template __global__ void match_batch_guided_kernel<kL2, Guide>(const cusift_point *, const unsigned int *, int,        \
+                                                                 const int *, int, MatchPartial *, int,                  \
+                                                                 cusift_match_row *, const GuideModel *, float);
+CUSIFT_GUIDED_KERNELS(false, GuideH)
+CUSIFT_GUIDED_KERNELS(true, GuideH)
+CUSIFT_GUIDED_KERNELS(false, GuideF)
+CUSIFT_GUIDED_KERNELS(true, GuideF)
+#undef CUSIFT_GUIDED_KERNELS
 
 }  // namespace cusift

@@ -65,11 +65,27 @@ static int match_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int n_p
   return CUSIFT_OK;
 }
 
+// The geometry of a guided match (cusift_match_guided, cusift_match_batch_guided), checked: which test, the squared radius
+// and the models as the caller's host array -- one of the pair call, one per pair of the pair-list call.
+struct GuideCall {
+  int model;
+  float r2;
+  const double *h_models;
+};
+// every refusal the guided calls add to their unguided counterparts'
+static int check_guide(const char *who, int model, const double *h_models, float radius) {
+  if (model != CUSIFT_GUIDE_HOMOGRAPHY && model != CUSIFT_GUIDE_EPIPOLAR)
+    return fail(CUSIFT_ERR_INVALID, "%s: model must be 0 (homography) or 1 (epipolar), got %d", who, model);
+  if (!h_models) return fail(CUSIFT_ERR_INVALID, "%s: NULL model", who);
+  return radius > 0.0f ? CUSIFT_OK : fail(CUSIFT_ERR_INVALID, "%s: radius must be > 0", who);
+}
+
 // The matcher of one pair: one launch, plus the row-side merge when the columns are split.  d_back != NULL
 // (cusift_match_mutual): image 2's records again, to receive the column side -- folded from the same accumulators
-// (sift_match.hip), merged when there are several row blocks.  Both counts >= 1, the arguments are checked.
+// (sift_match.hip), merged when there are several row blocks.  guide != NULL (cusift_match_guided, never with d_back):
+// the guided kernel, its model a kernel argument.  Both counts >= 1, the arguments are checked.
 static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
-                        int distance, cusift_point *d_back) {
+                        int distance, cusift_point *d_back, const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits, cols_per_split;
   TRY(match_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
@@ -90,7 +106,15 @@ static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, co
     hipLaunchKernelGGL(distance ? match_mutual_kernel<true> : match_mutual_kernel<false>, grid, dim3(256), 0,
                        ctx->stream, d_sift1, num_pts1, d_back, num_pts2, cols_per_split, partials, n1_pad,
                        col_partials);
-  else
+  else if (guide) {
+    GuideModel model;
+    memcpy(model.m, guide->h_models, sizeof(model.m));
+    const auto kernel = guide->model == CUSIFT_GUIDE_EPIPOLAR
+                            ? (distance ? match_guided_kernel<true, GuideF> : match_guided_kernel<false, GuideF>)
+                            : (distance ? match_guided_kernel<true, GuideH> : match_guided_kernel<false, GuideH>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2, cols_per_split,
+                       partials, n1_pad, model, guide->r2);
+  } else
     hipLaunchKernelGGL(distance ? match_kernel<true> : match_kernel<false>, grid, dim3(256), 0, ctx->stream, d_sift1,
                        num_pts1, d_sift2, num_pts2, cols_per_split, partials, n1_pad);
   if (splits > 1)
@@ -100,7 +124,7 @@ static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, co
     hipLaunchKernelGGL(match_mutual_merge_kernel, dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_back,
                        num_pts2, (const cusift_point *)d_sift1, num_pts1, distance, (const MatchPartial *)col_partials,
                        row_blocks);
-  return check_launch(d_back ? "match_mutual" : "match");
+  return check_launch(d_back ? "match_mutual" : guide ? "match_guided" : "match");
 }
 
 extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
@@ -110,6 +134,18 @@ extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1
   if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: missing data");
   TRY(check_distance("MatchSiftData", distance));
   return match_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, nullptr);
+}
+
+// cusift_match where a column that fails the geometric test against a row scores the initial value for that row.
+extern "C" int cusift_match_guided(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                   int num_pts2, int distance, int model, const double h_model[9], float radius) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchGuided: missing data");
+  TRY(check_distance("MatchGuided", distance));
+  TRY(check_guide("MatchGuided", model, h_model, radius));
+  const GuideCall guide{model, radius * radius, h_model};
+  return match_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, nullptr, &guide);
 }
 
 // Both directions from one pass over the scores.  Both record sets are written, so their ranges must not overlap.
@@ -928,7 +964,8 @@ static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int ma
 // *d_pairs_out: the list on the device, for the stages behind it.  n_pairs >= 1, max_pts >= 1, the list is checked.
 static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
                               const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
-                              const int **d_pairs_out, cusift_match_row *d_rows_back = nullptr) {
+                              const int **d_pairs_out, cusift_match_row *d_rows_back = nullptr,
+                              const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(max_pts, 64);
   int splits, cols_per_split;
   TRY(match_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
@@ -937,7 +974,9 @@ static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, con
   const size_t part_b = align_up_sz(splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0, 256);
   // the column side (cusift_match_batch_mutual): [pair][row block][max_pts] partials when there is more than one row block
   const size_t col_b = d_rows_back && row_blocks > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * row_blocks * max_pts : 0;
-  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b + col_b, "", false));
+  // the models of a guided call (cusift_match_batch_guided, never with d_rows_back): [pair], behind the partials
+  const size_t model_b = guide ? sizeof(GuideModel) * (size_t)n_pairs : 0;
+  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b + col_b + model_b, "", false));
   int *d_pairs = (int *)ctx->pairs_scratch;
   MatchPartial *partials = splits > 1 ? (MatchPartial *)(ctx->pairs_scratch + list_b) : nullptr;
   MatchPartial *col_partials = col_b ? (MatchPartial *)(ctx->pairs_scratch + list_b + part_b) : nullptr;
@@ -947,7 +986,16 @@ static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, con
     hipLaunchKernelGGL(distance ? match_batch_mutual_kernel<true> : match_batch_mutual_kernel<false>, grid, dim3(256),
                        0, ctx->stream, d_points, d_counters, max_pts, d_pairs, cols_per_split, partials, n1_pad, d_rows,
                        col_partials, d_rows_back);
-  else
+  else if (guide) {
+    GuideModel *d_models = (GuideModel *)(ctx->pairs_scratch + list_b + part_b + col_b);
+    HIP_TRY(hipMemcpyAsync(d_models, guide->h_models, model_b, hipMemcpyHostToDevice, ctx->stream));
+    const auto kernel =
+        guide->model == CUSIFT_GUIDE_EPIPOLAR
+            ? (distance ? match_batch_guided_kernel<true, GuideF> : match_batch_guided_kernel<false, GuideF>)
+            : (distance ? match_batch_guided_kernel<true, GuideH> : match_batch_guided_kernel<false, GuideH>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, (const int *)d_pairs,
+                       cols_per_split, partials, n1_pad, d_rows, (const GuideModel *)d_models, guide->r2);
+  } else
     hipLaunchKernelGGL(distance ? match_batch_kernel<true> : match_batch_kernel<false>, grid, dim3(256), 0, ctx->stream,
                        d_points, d_counters, max_pts, d_pairs, cols_per_split, partials, n1_pad, d_rows);
   if (splits > 1)
@@ -971,6 +1019,22 @@ extern "C" int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points,
   if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatch: missing data");
   const int *d_pairs = nullptr;
   return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs);
+}
+
+// cusift_match_batch under one model per pair (sift_match.hip: match_batch_guided_kernel)
+extern "C" int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                         int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                         int model, const double *h_models, float radius, cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  TRY(check_distance("MatchBatchGuided", distance));
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "MatchBatchGuided"));
+  TRY(check_guide("MatchBatchGuided", model, h_models, radius));
+  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatchGuided: missing data");
+  const GuideCall guide{model, radius * radius, h_models};
+  const int *d_pairs = nullptr;
+  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, nullptr,
+                            &guide);
 }
 
 // cusift_match_batch with the column side of every pair in d_rows_back (sift_match.hip: match_batch_mutual_kernel)

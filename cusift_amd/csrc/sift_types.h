@@ -144,6 +144,12 @@ struct MatchPartial {
   int idx;
 };
 
+// the model of a guided match (cusift_match_guided): H or F, row-major; a kernel argument of the pair call, an array in
+// context scratch -- one per pair -- of the pair-list call
+struct GuideModel {
+  double m[9];
+};
+
 // elements between consecutive pairs of a batched RANSAC (blockIdx.z of the rigid_* kernels); all 0 for one pair
 struct RigidBatch {
   size_t coord, indices, rt, counts, head, flags;

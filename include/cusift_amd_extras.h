@@ -43,6 +43,41 @@ int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cus
  * -- both are written; match a set against a copy of itself.  Asynchronous on the context's stream. */
 int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, cusift_point *d_sift2, int num_pts2,
                         int distance);
+/* Guided matching: nearest neighbours under a model that is already known -- the second matching pass of a registration.
+ * On repeated structure the best and the second-best descriptor are near-equal, `ambiguity` is close to 1 and the ratio
+ * test discards the match; once H or F is known the look-alike usually lies far from where the model puts the partner.
+ * THE RESULT is cusift_match's with one more rule: a column j that fails the geometric test below against row i scores
+ * the initial value for that row -- 999 for distance 1, -1 for distance 0 -- which changes nothing in the strict-compare
+ * scan.  The scan, the tree over the lanes, the column splits (CUSIFT_POLICY_MATCH_SPLITS included), the merge and the
+ * five fields written are cusift_match's, from the same text.
+ * A ROW FOR WHICH NO COLUMN PASSES receives score = the initial value, match = -1, the ambiguity that two initial values
+ * give (999 / (999 + 1e-6), or 2 / (2 + 1e-6)) and match_xpos / match_ypos of record 0, as cusift_match answers for a row
+ * that no column can win.  The candidate marking of the estimate / register calls rejects match = -1 whenever num_pts2 >=
+ * 0 is given.
+ * A ROW WITH EXACTLY ONE PASSING COLUMN has second = the initial value and therefore a tiny ambiguity.  That is intended
+ * -- it is the only compatible partner; the caller's score threshold is what guards against a bad descriptor distance.
+ * THE TEST uses x1 = coords2D of row i and x2 = coords2D of column j, floats, and is pinned to these expressions (the
+ * build uses -ffp-contract=off), so that a restatement in float64 / float32 gives the same bit.
+ * CUSIFT_GUIDE_HOMOGRAPHY: M = H row-major, x2 ~ H x1, the direction of cusift_register_planar's output (widen its floats).
+ *   per row, fp64 (x1, y1 widened):   X = (H0*x1 + H1*y1) + H2;  Y = (H3*x1 + H4*y1) + H5;  W = (H6*x1 + H7*y1) + H8;
+ *                                     px = (float)(X / W);  py = (float)(Y / W)
+ *   per pair, fp32:                   dx = x2 - px;  dy = y2 - py;  pass <=> dx*dx + dy*dy < r2,  r2 = radius * radius
+ *   A NaN anywhere is no pass; so is W == 0, which gives an infinity or a NaN.
+ * CUSIFT_GUIDE_EPIPOLAR: M = F row-major with x2^T F x1 = 0, the convention of cusift_estimate_fundamental.
+ *   per row, fp64:   l0, l1, l2 exactly as in the Sampson test above;  n = sqrt(l0*l0 + l1*l1);
+ *                    a = (float)(l0 / n);  b = (float)(l1 / n);  c = (float)(l2 / n)
+ *   per pair, fp32:  d = (a*x2 + b*y2) + c;  pass <=> d*d < r2
+ *   A row whose line is not usable -- unless n > 0, n < infinity and |l2| < infinity -- has a = b = c = NaN: no column
+ *   passes.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): everything cusift_match refuses, an unknown model, a NULL
+ * h_model, radius not > 0 (NaN included).  +infinity is a legal radius (every finite test passes).  A model that is not
+ * finite is no error: it passes nothing.  A count <= 0 on either side: CUSIFT_OK, nothing enqueued, as cusift_match.
+ * h_model is read before the call returns.  Asynchronous on the context's stream; writes what cusift_match writes and
+ * nothing else. */
+#define CUSIFT_GUIDE_HOMOGRAPHY 0
+#define CUSIFT_GUIDE_EPIPOLAR 1
+int cusift_match_guided(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
+                        int distance, int model, const double h_model[9], float radius);
 /* cudaMemcpy2D device->host (extras/matching.cu:311-315 copies the 5 match fields of every record); blocking. */
 int cusift_memcpy2d_d2h(cusift_ctx *ctx, void *h_dst, size_t dst_pitch, const void *d_src, size_t src_pitch,
                         size_t width_bytes, size_t rows);
@@ -517,6 +552,18 @@ int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsi
 int cusift_match_batch_mutual(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
                               int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
                               cusift_match_row *d_rows, cusift_match_row *d_rows_back);
+
+/* cusift_match_batch under one model per pair (cusift_match_guided over a pair list): pair p's rows are what
+ * cusift_match_batch writes for it with cusift_match_guided's rule added, under the model h_models[9 p .. 9 p + 8] -- all
+ * pairs the same kind of `model` and the same radius.  h_models is host memory and is read before the call returns, as
+ * h_pairs is; the device copy lives in the context's scratch.  Rows, counts and launches as cusift_match_batch; the
+ * records are not written.
+ * CUSIFT_ERR_INVALID (nothing enqueued): every case of cusift_match_batch, an unknown model, a NULL h_models, radius not
+ * > 0 (NaN included). */
+int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
+                              int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
+                              int model, const double *h_models /* [n_pairs][9] */, float radius,
+                              cusift_match_row *d_rows);
 
 /* cusift_register_rgbd for every pair of a list, device-resident from the extractor's batch + depth images to one
  * [R | t] per pair: ONE cusift_lift_depth over all frames (frame k's depth image at d_depth + k * image_stride_elems),

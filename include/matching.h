@@ -59,6 +59,47 @@ inline std::vector<SiftMatch *> MatchSiftData(SiftData &data1, SiftData &data2,
   return matches;
 }
 
+// MatchSiftData under a model that is already known (not in the reference): cusift_match_guided() instead of
+// cusift_match() -- a record of data2 whose coords2D fail the test against a record of data1 cannot be its match.  model:
+// CUSIFT_GUIDE_HOMOGRAPHY (M = H, x2 ~ H x1, within `radius` pixels of H x1) or CUSIFT_GUIDE_EPIPOLAR (M = F, x2^T F x1 =
+// 0, within `radius` pixels of the line F x1); M is row-major.  A record that nothing passes has match == -1 and is not
+// returned.  Everything else is MatchSiftData's.
+inline std::vector<SiftMatch *> MatchSiftDataGuided(SiftData &data1, SiftData &data2, int model, const double M[9],
+                                                    float radius, MatchSiftDistance distance = MatchSiftDistanceL2,
+                                                    float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                                    MatchType type = MatchType2D) {
+  std::vector<SiftMatch *> matches;
+  if (!data1.numPts || !data2.numPts) return matches;
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match_guided(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
+                               reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
+                               distance == MatchSiftDistanceL2 ? 1 : 0, model, M, radius));
+  if (data1.h_data != nullptr)  // the 5 match fields of every record, extras/matching.cu:311-315
+    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
+                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
+  else
+    safeCall(cusift_ctx_synchronize(ctx));
+  if (data1.h_data == nullptr) return matches;
+  const float thresh2 = scoreThreshold * scoreThreshold;
+  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
+  for (int i = 0; i < data1.numPts; i++) {
+    SiftPoint &p = data1.h_data[i];
+    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
+    if (p.match < 0 || p.match >= data2.numPts || data2.h_data == nullptr) continue;
+    if (type == MatchType2D || (p.coords3D[2] != 0 && data2.h_data[p.match].coords3D[2] != 0)) {
+      SiftMatch *m = new SiftMatch();
+      m->pt1 = &p;
+      m->pt2 = &data2.h_data[p.match];
+      m->score = p.score;
+      m->ambiguity = p.ambiguity;
+      m->error = 0.0f;
+      matches.push_back(m);
+    }
+  }
+  return matches;
+}
+
 // MatchSiftData with the cross-check (not in the reference): one cusift_match_mutual() fills the match fields of BOTH
 // sets -- data1's as MatchSiftData does, data2's with its best and second best in data1 (the lowest record on exactly
 // tied best scores) -- and a pair (i, j) is returned only if it passes MatchSiftData's filter and record j's match is i.
