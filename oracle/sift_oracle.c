@@ -482,7 +482,10 @@ void oracle_extract_descriptors(const float *img, int w, int h, int pitch, oracl
         int veri = (y + 2) / 4 - 1;
         float verf = (y - 1.5f) / 4.0f - veri;
         float iverf = 1.0f - verf;
-        int angi = (int)angf;
+        /* cuSIFT_D.cu:222 `int angi = angf;`: the device's conversion turns a NaN (a non-finite tap) into 0, so the NaN
+         * shares land in the cell's bins 0 and 1 and the whole descriptor is NaN after the normalisation.  In C the
+         * conversion of a NaN is undefined (x86 gives INT_MIN, and desc_add would drop the sample). */
+        int angi = angf == angf ? (int)angf : 0;
         int angp = (angi < 7 ? angi + 1 : 0);
         angf -= angi;
         float iangf = 1.0f - angf;

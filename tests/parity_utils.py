@@ -8,6 +8,51 @@ def canonical_order(pts):
     return pts[key]
 
 
+HEAD_FIELDS = ("subsampling", "coords2D", "scale", "sharpness", "edgeness", "orientation")
+QUIET_NAN = np.uint32(0x7FC00000)
+
+
+def record_keys(pts, fields):
+    """[n, k] uint32: the bits of the given float32 fields of every record, every NaN replaced by one quiet NaN."""
+    vals = np.concatenate([np.asarray(pts[f], dtype=np.float32).reshape(len(pts), -1) for f in fields], axis=1)
+    keys = vals.view(np.uint32).copy()
+    keys[np.isnan(vals)] = QUIET_NAN
+    return keys
+
+
+def same_records(want, got, fields=HEAD_FIELDS, label="", desc_tol=None):
+    """Two record sets hold the same records, for sets that may hold non-finite coordinates (canonical_order has no
+    defined order for NaN keys, so a field-by-field comparison after it can fail on correct output).
+
+    Every record becomes a key of the bit patterns of `fields`; the two MULTISETS of keys must be equal -- every record,
+    no exempt fraction.  Infinities and signed zeros are compared exactly, as bits; only NaN bits are normalised (all
+    NaNs count as one quiet NaN: `inf - inf` yields the default NaN of the machine that computed it, and its sign and
+    payload differ between x86 and gfx950).  With `desc_tol` the descriptors are then compared record by record through
+    the same keys: NaN-holding rows in the same places, every finite row within `desc_tol` (L2).  Records whose keys are
+    equal were computed from equal inputs, so which of them meets which does not matter.
+    Returns the largest descriptor distance (0.0 without descriptors)."""
+    assert len(want) == len(got), (label, "count", len(want), len(got))
+    if len(want) == 0:
+        return 0.0
+    kw, kg = record_keys(want, fields), record_keys(got, fields)
+    ow, og = np.lexsort(kw.T[::-1]), np.lexsort(kg.T[::-1])
+    kw, kg = kw[ow], kg[og]
+    if not np.array_equal(kw, kg):
+        bad = np.flatnonzero((kw != kg).any(axis=1))
+        raise AssertionError("%s: %d of %d sorted record keys differ (fields %s); first: want %s, got %s" % (
+            label, len(bad), len(kw), "/".join(fields), kw[bad[0]].view(np.float32), kg[bad[0]].view(np.float32)))
+    if desc_tol is None:
+        return 0.0
+    a, b = want["data"][ow], got["data"][og]
+    fin = np.isfinite(a).all(axis=1)
+    np.testing.assert_array_equal(np.isfinite(b).all(axis=1), fin, err_msg="%s: non-finite descriptor rows" % label)
+    if not fin.any():
+        return 0.0
+    l2 = np.linalg.norm(a[fin].astype(np.float64) - b[fin].astype(np.float64), axis=1)
+    assert l2.max() < desc_tol, (label, "descriptor L2", float(l2.max()), int((l2 >= desc_tol).sum()), len(l2))
+    return float(l2.max())
+
+
 def ang_diff(a, b):
     d = np.abs(a - b) % 360.0
     return np.minimum(d, 360.0 - d)
