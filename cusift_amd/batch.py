@@ -153,6 +153,36 @@ class BatchExtractor:
         n_i, n_j = self._pair_counts(counts, i, j)
         self.ctx.match_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, model, m, radius, distance)
 
+    def quantize(self, slot=0):
+        """8-bit descriptors of the last extract() into `slot`: cusift_quantize_descriptors over this extractor's device
+        records and raw counters.  Returns (uint8 [n, max_pts, 128], int32 [n, max_pts, 2]) device tensors, allocated once
+        per slot: the bytes are the OpenCV / VLFeat / COLMAP convention (512 v clipped to 255) -- what a caller hands to
+        them -- and the ints are (sum q, sum q^2), which match8() needs.  Rows past a frame's count keep what they held.
+        Asynchronous on the extractor's stream."""
+        if not hasattr(self, "_desc8"):
+            self._desc8 = {}
+        if slot not in self._desc8:
+            with torch.cuda.device(self.device):
+                self._desc8[slot] = (torch.zeros((self.n, self.max_pts, 128), dtype=torch.uint8, device=self.device),
+                                     torch.zeros((self.n, self.max_pts, 2), dtype=torch.int32, device=self.device))
+        q, sums = self._desc8[slot]
+        points, counts = self.slots[slot]
+        self.ctx.quantize_descriptors(points.data_ptr(), self.max_pts, q.data_ptr(), sums.data_ptr(), n_images=self.n,
+                                      d_counters=counts.data_ptr())
+        return q, sums
+
+    def match8(self, i, j, slot=0, distance=1):
+        """8-bit match of frames i and j of `slot` on the tensors of the last quantize(slot): cusift_match8 writes frame
+        i's five match fields (exact integer scores scaled by 2^-18; int8 matrix pipe).  The two counts are read with one
+        call.  Asynchronous on the extractor's stream."""
+        if slot not in getattr(self, "_desc8", {}):
+            raise capi.CusiftError("match8: call quantize(slot=%d) first" % slot)
+        q, sums = self._desc8[slot]
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        self.ctx.match8(points[i].data_ptr(), n_i, q[i].data_ptr(), sums[i].data_ptr(), points[j].data_ptr(), n_j,
+                        q[j].data_ptr(), sums[j].data_ptr(), distance)
+
     def register_planar_guided(self, i, j, radius=None, slot=0, **opts):
         """register_planar(i, j) with a second, guided matching pass: capi.Context.register_planar_guided over this
         extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.  Blocking."""

@@ -235,6 +235,10 @@ SIGNATURES = {
     "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cusift_match_batch_mutual": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "cusift_match_batch_guided": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _vp]),
+    "cusift_quantize_descriptors": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "cusift_desc8_sums": (_i, [_vp, _vp, _i, _vp]),
+    "cusift_match8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
+    "cusift_match8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
@@ -1076,6 +1080,30 @@ class Context:
         check(lib().cusift_match_batch_guided(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
                                               len(pairs), distance, model, None if m is None else m.ctypes.data, radius,
                                               d_rows))
+
+    # ---- 8-bit descriptors ----
+    def quantize_descriptors(self, d_points, max_pts, d_q, d_sums, n_images=1, d_counters=None):
+        """cusift_quantize_descriptors: d_points[n_images][max_pts] (+ d_counters, None: max_pts each) to the byte table
+        d_q uint8 [n_images][max_pts][128] (16-byte aligned: the OpenCV / VLFeat / COLMAP convention, 512 v clipped to
+        255) and d_sums int32 [n_images][max_pts][2] = (sum q, sum q^2).  Rows past a count are not written.
+        Asynchronous."""
+        check(lib().cusift_quantize_descriptors(self.handle, d_points, d_counters, n_images, max_pts, d_q, d_sums))
+
+    def desc8_sums(self, d_q, n, d_sums):
+        """cusift_desc8_sums: d_sums int32 [n][2] of n byte descriptors d_q uint8 [n][128] that came from elsewhere."""
+        check(lib().cusift_desc8_sums(self.handle, d_q, n, d_sums))
+
+    def match8(self, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance=1):
+        """cusift_match8: match() on two byte tables (int8 matrix pipe, exact integer scores scaled by 2^-18): writes the
+        same five fields of d_sift1[0 .. n1); d_sift2 is read for coords2D of the match only.  Asynchronous."""
+        check(lib().cusift_match8(self.handle, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance))
+
+    def match8_batch(self, d_q, d_sums, d_counters, n_images, max_pts, pairs, d_rows, distance=1):
+        """cusift_match8_batch: match_batch() on the tables quantize_descriptors() wrote for a batch, match8()'s model;
+        d_rows[P][max_pts] of MatchRow (device pointer).  Asynchronous."""
+        pairs = pair_list(pairs)
+        check(lib().cusift_match8_batch(self.handle, d_q, d_sums, d_counters, n_images, max_pts, pairs.ctypes.data,
+                                        len(pairs), distance, d_rows))
 
     def register_rgbd_batch(self, d_points, d_counters, n_images, max_pts, d_depth, w, h, camera, pairs, pitch=None,
                             image_stride=None, distance=1, score_threshold=999.0, ambiguity_threshold=1.0, loops=1024,

@@ -6,6 +6,7 @@
 //   sift_register.hip the registration host layer: matcher, FindHomography, rigid RANSAC, RGB-D registration, the
 //                     calibrated pose, planar and epipolar registration on one chain, the absolute pose, the pair-list forms
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
+//   sift_match8.hip   8-bit descriptors: the quantiser, the int8-MFMA matcher, their entry points (a unit of its own)
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 // The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,

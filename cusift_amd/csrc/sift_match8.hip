@@ -1,0 +1,515 @@
+// sift_match8.hip -- 8-bit descriptors: the quantiser, the two sums of a byte descriptor, and the brute-force matcher on
+// the int8 matrix pipe (v_mfma_i32_16x16x64_i8), for a pair and for a pair list.  The definitions, expression by
+// expression, are in include/cusift_amd_extras.h (cusift_quantize_descriptors, cusift_desc8_sums, cusift_match8,
+// cusift_match8_batch); this text is how they are computed.
+//
+// Tables: q[n][128] unsigned bytes, dense and 16-byte aligned; sums[n][2] = (sum q, sum q^2) as int.
+//
+// THE MATCHER.  The int8 MFMA is signed, so both operands are q - 128 (XOR 0x80 on the packed words: the rows once, into
+// registers; the columns on their way into LDS).  With a = q1 - 128, b = q2 - 128 and S' = sum a b, which is what the
+// accumulators hold:
+//     sum a^2 = sum q1^2 - 256 sum q1 + 2^21 = R(row), sum b^2 = C(column) likewise,
+//     D = sum (q1 - q2)^2 = R + C - 2 S'            (the shift cancels in the difference)
+//     S = sum q1 q2       = S' + 128 (sum q1 + sum q2) - 2^21    (128 (sum a + sum b) + 128^3, all-255: 8,323,200).
+// A row's order over the columns does not depend on the row's own term, so the scan of a row runs on
+//     key' = C - 2 S'              (L2)        key' = -128 sum q2 - S'      (dot product: the smallest -S)
+// -- one integer operation per score, the column's term read from LDS beside its bytes -- and the row's term is added once,
+// behind the scan: key = key' + R, or key' - 128 sum q1 + 2^21.  |key'| < 2^23 for every real column.  A column past the
+// split's end carries the term 2^30 instead: it can never be best while a real column exists (a split has one), and a
+// `second` at or above 2^29 means "no second column", which the write-out turns into cusift_match's initial value.
+// The update per score is min, med3, one compare and one select: best = min(best, v); second = med3(best_old, second, v)
+// (best_old <= second always, so that is the second smallest of the three); idx = v < best_old ? column : idx.  A lane
+// meets its columns in ascending order and compares strictly, so it keeps the lowest column of equal keys; every merge
+// (the tree over the 16 lanes of a row, the fold of the column splits) orders (key, column) pairs, so the lowest column
+// wins there too and `second` is the second smallest key of the multiset: the result does not depend on scan order, tile
+// or split count, and there are no atomics.
+//
+// Shape: a workgroup is 4 waves x 64 rows (a wave keeps its 64 rows' 128 bytes as four A fragments, 32 registers) against
+// one contiguous range of columns (blockIdx.y); the columns pass through LDS in tiles of 64 (two buffers, one barrier per
+// tile; the next tile's global loads are in flight in registers while this one is multiplied).  Per B fragment -- 16
+// columns x 128 bytes, two ds_read_b128 -- a wave issues 8 MFMAs (4 row groups x 2 k halves) and updates 16 scores per
+// lane.  The k order inside a fragment is whatever 16 consecutive bytes per lane give: A and B load the same byte
+// positions (bytes 64 m + 16 g .. + 15 of their row / column in lane (r, g), MFMA m), which is all a dot product needs.
+// C/D: col = lane & 15, row = 4 (lane >> 4) + reg.
+#include "sift_host.h"
+
+#include "sift_device.h"
+
+namespace cusift {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kM8RowsPerWave = 64;                    // four 16-row A fragments
+constexpr int kM8RowsPerBlock = 4 * kM8RowsPerWave;   // 256
+constexpr int kM8TileCols = 64;                       // columns per LDS tile
+constexpr int kM8Stride = 144;                        // bytes per LDS column: 128 + the column's term + pad; 36 dwords,
+                                                      // = 4 mod 32 like the fp32 matcher's rows: ds_read_b128 without conflicts
+constexpr int kM8Masked = 1 << 30;                    // the term of a column past the split's end
+constexpr int kM8None = 1 << 29;                      // a key at or above this is no column
+constexpr int kM8Init = 0x7fffffff;
+constexpr float kM8FltMax = 999.0f;                   // cusift_match's initial values
+constexpr float kM8Scale = 1.0f / 262144.0f;          // 2^-18: (q / 512)^2
+
+// per-(column split, row) result: final keys (D, or -S), kM8Init where there is none
+struct Match8Partial {
+  int best, second, idx, pad;
+};
+
+__device__ __forceinline__ int med3i(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
+
+// (best, second, idx) of two disjoint column sets -> of their union: (key, column) pairs in order, second smallest key
+__device__ __forceinline__ void m8_merge(int &best, int &second, int &idx, int ob, int os, int oi) {
+  const bool take = ob < best || (ob == best && (unsigned)oi < (unsigned)idx);  // idx -1 (no column) loses to any column
+  second = min(max(best, ob), min(second, os));
+  best = min(best, ob);
+  idx = take ? oi : idx;
+}
+
+// what a row's term adds behind the scan
+template <bool kL2>
+__device__ __forceinline__ int m8_row_term(int sum, int sq) {
+  return kL2 ? sq - 256 * sum + (1 << 21) : (1 << 21) - 128 * sum;
+}
+template <bool kL2>
+__device__ __forceinline__ int m8_col_term(int sum, int sq) {
+  return kL2 ? sq - 256 * sum + (1 << 21) : -128 * sum;
+}
+
+// final keys -> the three values cusift_match's tail works on
+template <bool kL2>
+__device__ __forceinline__ void m8_floats(int best, int second, float &fb, float &fs) {
+  fb = kL2 ? (float)best * kM8Scale : (float)(-best) * kM8Scale;
+  fs = second >= kM8None ? (kL2 ? kM8FltMax : -1.0f) : (kL2 ? (float)second * kM8Scale : (float)(-second) * kM8Scale);
+}
+
+// match_ambiguity of sift_match.hip, the reference's two expressions: the 1e-6 is a double
+__device__ __forceinline__ float m8_ambiguity(float best, float second, bool l2) {
+  return l2 ? (float)(best / (second + 1e-6)) : (float)((1 - best) / (1 - second + 1e-6));
+}
+
+template <bool kL2>
+__device__ __forceinline__ void m8_write_point(cusift_point *pt, const cusift_point *__restrict__ sift2, int n2, int best,
+                                               int second, int idx) {
+  float fb, fs;
+  m8_floats<kL2>(best, second, fb, fs);
+  pt->score = fb;
+  pt->ambiguity = m8_ambiguity(fb, fs, kL2);
+  pt->match = idx;
+  const int m = (idx >= 0 && idx < n2) ? idx : 0;  // as write_match
+  pt->match_xpos = sift2[m].coords2D[0];
+  pt->match_ypos = sift2[m].coords2D[1];
+}
+
+template <bool kL2>
+__device__ __forceinline__ void m8_write_row(cusift_match_row *__restrict__ row, int best, int second, int idx) {
+  float fb, fs;
+  m8_floats<kL2>(best, second, fb, fs);
+  f4 v;
+  v[0] = fb;
+  v[1] = m8_ambiguity(fb, fs, kL2);
+  v[2] = __int_as_float(idx);
+  v[3] = 0.0f;  // reserved
+  *reinterpret_cast<f4 *>(row) = v;
+}
+
+// One workgroup's 256 rows [blockIdx.x * 256 ..) of (q1, sums1, n1) against the columns [col_begin, col_end) of
+// (q2, sums2); col_begin < col_end and blockIdx.x * 256 < n1.  out(row, best, second, idx) receives every row < n1 once,
+// with final keys.
+template <bool kL2, class Out>
+__device__ __forceinline__ void m8_block(const unsigned char *__restrict__ q1, const int *__restrict__ sums1, int n1,
+                                         const unsigned char *__restrict__ q2, const int *__restrict__ sums2,
+                                         int col_begin, int col_end, unsigned char *sB, Out out) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kM8RowsPerBlock + wv * kM8RowsPerWave;
+
+  // A fragments: lane (r, g) holds bytes 64 m + 16 g .. + 15 of row p1_base + 16 i + r (i = 0..3, m = 0..1), minus 128.
+  // A row past n1 is a copy of the last one; it is never written.
+  i32x4 a[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned char *row = q1 + (size_t)min(p1_base + 16 * i + r, n1 - 1) * 128 + 16 * g;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const u4 v = *reinterpret_cast<const u4 *>(row + 64 * m);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[i][m][j] = (int)(v[j] ^ 0x80808080u);
+    }
+  }
+  // running top-2 of rows 16 i + 4 g + j over the columns this lane sees (r mod 16), on key'
+  int best[4][4], second[4][4], bidx[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      best[i][j] = second[i][j] = kM8Init;
+      bidx[i][j] = -1;
+    }
+
+  // staging: thread t moves two 16-byte chunks per tile; chunk c = t + 256 k -> column c >> 3, bytes 16 (c & 7).  Raw
+  // buffer loads from a descriptor based at the split's first column: a column past col_end reads as 0 and is masked by
+  // its term.  Threads 0..63 also fetch the sums of column c0 + t and turn them into the column's term.
+  const int n_cols = col_end - col_begin;
+  const __amdgpu_buffer_rsrc_t rsrc2 =
+      __builtin_amdgcn_make_buffer_rsrc((void *)(q2 + (size_t)col_begin * 128), 0, n_cols * 128, kBufFlags);
+  const int voff = (int)(threadIdx.x >> 3) * 128 + 16 * (int)(threadIdx.x & 7);
+  u4 stage[2];
+  int stage_term = kM8Masked;
+  auto fetch = [&](int c0) {
+    const int soff = __builtin_amdgcn_readfirstlane((c0 - col_begin) * 128);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) stage[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc2, voff, soff + 32 * k * 128, 0);
+    if (threadIdx.x < kM8TileCols) {
+      const int c = c0 + (int)threadIdx.x;
+      stage_term = kM8Masked;
+      if (c < col_end) {
+        const int2 s = *reinterpret_cast<const int2 *>(sums2 + 2 * (size_t)c);
+        stage_term = m8_col_term<kL2>(s.x, s.y);
+      }
+    }
+  };
+  fetch(col_begin);
+  int par = 0;
+  for (int c0 = col_begin; c0 < col_end; c0 += kM8TileCols, par ^= 1) {
+    // buffer `par` was last read two tiles ago, in front of the previous tile's barrier
+    unsigned char *buf = sB + par * (kM8TileCols * kM8Stride);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = threadIdx.x + 256 * k;
+      u4 v = stage[k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] ^= 0x80808080u;
+      *reinterpret_cast<u4 *>(buf + (c >> 3) * kM8Stride + 16 * (c & 7)) = v;
+    }
+    if (threadIdx.x < kM8TileCols) *reinterpret_cast<int *>(buf + threadIdx.x * kM8Stride + 128) = stage_term;
+    __syncthreads();
+    if (c0 + kM8TileCols < col_end) fetch(c0 + kM8TileCols);  // in flight while this tile is multiplied
+
+    const unsigned char *bcol = buf + r * kM8Stride + 16 * g;
+#pragma unroll
+    for (int t = 0; t < kM8TileCols / 16; ++t) {
+      const i32x4 b0 = *reinterpret_cast<const i32x4 *>(bcol + 16 * t * kM8Stride);
+      const i32x4 b1 = *reinterpret_cast<const i32x4 *>(bcol + 16 * t * kM8Stride + 64);
+      const int term = *reinterpret_cast<const int *>(buf + (16 * t + r) * kM8Stride + 128);
+      const int p2 = c0 + 16 * t + r;
+      i32x4 acc[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        acc[i] = i32x4{0, 0, 0, 0};
+        acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i][0], b0, acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i][1], b1, acc[i], 0, 0, 0);
+      }
+      // acc[i][j] = S' of row 16 i + 4 g + j and column p2
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int v = kL2 ? term - 2 * acc[i][j] : term - acc[i][j];
+          const int old = best[i][j];
+          best[i][j] = min(old, v);
+          second[i][j] = med3i(old, second[i][j], v);
+          bidx[i][j] = v < old ? p2 : bidx[i][j];
+        }
+    }
+  }
+  // the tree over the 16 lanes of a row; lane r == 0 of group g ends with rows 16 i + 4 g + j
+#pragma unroll
+  for (int len = 8; len > 0; len >>= 1)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int ob = __shfl_down(best[i][j], len, 16);
+        const int os = __shfl_down(second[i][j], len, 16);
+        const int oi = __shfl_down(bidx[i][j], len, 16);
+        if (r < len) m8_merge(best[i][j], second[i][j], bidx[i][j], ob, os, oi);
+      }
+  if (r == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int p1 = p1_base + 16 * i + 4 * g + j;
+        if (p1 >= n1) continue;
+        const int2 s = *reinterpret_cast<const int2 *>(sums1 + 2 * (size_t)p1);
+        const int rt = m8_row_term<kL2>(s.x, s.y);
+        // a real column's key' is below 2^23 in magnitude; "none" stays none
+        out(p1, best[i][j] + rt, second[i][j] >= kM8None ? kM8Init : second[i][j] + rt, bidx[i][j]);
+      }
+  }
+}
+
+// One pair.  grid (row blocks, column splits).  partials == NULL (one split): the five fields are final; otherwise
+// partials[split][n1_pad] and match8_merge_kernel folds them.
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_kernel(cusift_point *__restrict__ sift1, int n1,
+                                                    const unsigned char *__restrict__ q1, const int *__restrict__ sums1,
+                                                    const cusift_point *__restrict__ sift2, int n2,
+                                                    const unsigned char *__restrict__ q2, const int *__restrict__ sums2,
+                                                    int cols_per_split, Match8Partial *__restrict__ partials, int n1_pad) {
+  __shared__ __attribute__((aligned(16))) unsigned char sB[2 * kM8TileCols * kM8Stride];
+  const int col_begin = blockIdx.y * cols_per_split;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  if (col_begin >= col_end) return;  // uniform; the host sizes the splits so that this never happens
+  m8_block<kL2>(q1, sums1, n1, q2, sums2, col_begin, col_end, sB, [&](int p1, int b, int s, int i) {
+    if (partials)
+      partials[(size_t)blockIdx.y * n1_pad + p1] = Match8Partial{b, s, i, 0};
+    else
+      m8_write_point<kL2>(sift1 + p1, sift2, n2, b, s, i);
+  });
+}
+template __global__ void match8_kernel<false>(cusift_point *, int, const unsigned char *, const int *, const cusift_point *,
+                                              int, const unsigned char *, const int *, int, Match8Partial *, int);
+template __global__ void match8_kernel<true>(cusift_point *, int, const unsigned char *, const int *, const cusift_point *,
+                                             int, const unsigned char *, const int *, int, Match8Partial *, int);
+
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_merge_kernel(cusift_point *__restrict__ sift1, int n1,
+                                                          const cusift_point *__restrict__ sift2, int n2,
+                                                          const Match8Partial *__restrict__ partials, int n1_pad,
+                                                          int n_splits) {
+  const int p1 = blockIdx.x * 256 + threadIdx.x;
+  if (p1 >= n1) return;
+  Match8Partial m = partials[p1];
+  for (int s = 1; s < n_splits; ++s) {
+    const Match8Partial o = partials[(size_t)s * n1_pad + p1];
+    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
+  }
+  m8_write_point<kL2>(sift1 + p1, sift2, n2, m.best, m.second, m.idx);
+}
+
+// The pair list: blockIdx.z picks the pair, the counts come from device memory (clamped to max_pts), the grid is sized
+// from max_pts.  A workgroup without rows or without columns returns before it loads a byte.
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_batch_kernel(const unsigned char *__restrict__ q, const int *__restrict__ sums,
+                                                          const unsigned int *__restrict__ counters, int max_pts,
+                                                          const int *__restrict__ pairs, int cols_per_split,
+                                                          Match8Partial *__restrict__ partials, int n1_pad,
+                                                          cusift_match_row *__restrict__ rows) {
+  __shared__ __attribute__((aligned(16))) unsigned char sB[2 * kM8TileCols * kM8Stride];
+  const int pair = blockIdx.z;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const int col_begin = blockIdx.y * cols_per_split;
+  if ((int)blockIdx.x * kM8RowsPerBlock >= n1 || col_begin >= n2) return;  // uniform
+  const int col_end = min(col_begin + cols_per_split, n2);
+  m8_block<kL2>(q + (size_t)f1 * max_pts * 128, sums + (size_t)f1 * max_pts * 2, n1, q + (size_t)f2 * max_pts * 128,
+                sums + (size_t)f2 * max_pts * 2, col_begin, col_end, sB, [&](int p1, int b, int s, int i) {
+                  if (partials)
+                    partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = Match8Partial{b, s, i, 0};
+                  else
+                    m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, b, s, i);
+                });
+}
+template __global__ void match8_batch_kernel<false>(const unsigned char *, const int *, const unsigned int *, int,
+                                                    const int *, int, Match8Partial *, int, cusift_match_row *);
+template __global__ void match8_batch_kernel<true>(const unsigned char *, const int *, const unsigned int *, int,
+                                                   const int *, int, Match8Partial *, int, cusift_match_row *);
+
+// match8_merge_kernel per pair (blockIdx.y): folds the splits that had columns
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_batch_merge_kernel(const unsigned int *__restrict__ counters, int max_pts,
+                                                                const int *__restrict__ pairs, int cols_per_split,
+                                                                const Match8Partial *__restrict__ partials, int n1_pad,
+                                                                int n_splits, cusift_match_row *__restrict__ rows) {
+  const int pair = blockIdx.y;
+  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const int p1 = blockIdx.x * 256 + threadIdx.x;
+  if (p1 >= n1 || n2 <= 0) return;
+  const int live = min(n_splits, (n2 + cols_per_split - 1) / cols_per_split);  // the others wrote nothing
+  const Match8Partial *__restrict__ mine = partials + (size_t)pair * n_splits * n1_pad + p1;
+  Match8Partial m = mine[0];
+  for (int s = 1; s < live; ++s) {
+    const Match8Partial o = mine[(size_t)s * n1_pad];
+    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
+  }
+  m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, m.best, m.second, m.idx);
+}
+
+// ---- the quantiser --------------------------------------------------------------------------------------------------------
+// 32 lanes per record: lane l reads floats 4 l .. 4 l + 3 (16 bytes; the 588-byte records are only 4-byte aligned),
+// writes one packed word -- a record's 128 bytes are one 128-byte line -- and the 32 lanes' sums meet by
+// shuffles inside the half wave.  8 records per workgroup; grid (record blocks, images).
+typedef float f4u8 __attribute__((ext_vector_type(4), aligned(4)));
+
+__device__ __forceinline__ int quantize_one(float v) {
+  const float t = 512.0f * v;  // exact
+  const float u = t + 0.5f;    // one rounding
+  return (v > 0.0f) ? (u < 255.0f ? (int)u : 255) : 0;
+}
+
+__global__ void __launch_bounds__(256) quantize_kernel(const cusift_point *__restrict__ points,
+                                                      const unsigned int *__restrict__ counters, int max_pts,
+                                                      unsigned char *__restrict__ q, int *__restrict__ sums) {
+  const int img = blockIdx.y;
+  const int n = frame_count(counters, img, max_pts);
+  const int rec = blockIdx.x * 8 + (int)(threadIdx.x >> 5);
+  const int l = threadIdx.x & 31;
+  if (rec >= n) return;  // uniform over the record's 32 lanes: the shuffles below stay inside them
+  const size_t at = (size_t)img * max_pts + rec;
+  const f4u8 v = *reinterpret_cast<const f4u8 *>(points[at].data + 4 * l);
+  unsigned int word = 0;
+  int s = 0, s2 = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int b = quantize_one(v[j]);
+    word |= (unsigned int)b << (8 * j);
+    s += b;
+    s2 += b * b;
+  }
+  reinterpret_cast<unsigned int *>(q + at * 128)[l] = word;
+#pragma unroll
+  for (int d = 16; d > 0; d >>= 1) {
+    s += __shfl_xor(s, d, 32);
+    s2 += __shfl_xor(s2, d, 32);
+  }
+  if (l == 0) *reinterpret_cast<int2 *>(sums + 2 * at) = int2{s, s2};
+}
+
+// 8 lanes per record, 16 bytes each
+__global__ void __launch_bounds__(256) desc8_sums_kernel(const unsigned char *__restrict__ q, int n, int *__restrict__ sums) {
+  const int rec = blockIdx.x * 32 + (int)(threadIdx.x >> 3);
+  const int l = threadIdx.x & 7;
+  if (rec >= n) return;  // uniform over the record's 8 lanes
+  const u4 v = *reinterpret_cast<const u4 *>(q + (size_t)rec * 128 + 16 * l);
+  int s = 0, s2 = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int b = (int)((v[j] >> (8 * k)) & 0xffu);
+      s += b;
+      s2 += b * b;
+    }
+#pragma unroll
+  for (int d = 4; d > 0; d >>= 1) {
+    s += __shfl_xor(s, d, 8);
+    s2 += __shfl_xor(s2, d, 8);
+  }
+  if (l == 0) *reinterpret_cast<int2 *>(sums + 2 * (size_t)rec) = int2{s, s2};
+}
+
+}  // namespace cusift
+
+// ------------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------------
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The column splits of the 8-bit matchers over n_pairs pairs: aim at >= 2 workgroups per CU (a workgroup is 256 rows,
+// four times the fp32 matcher's), keep >= 4 LDS tiles (256 columns) per split.  CUSIFT_POLICY_MATCH_SPLITS = k > 0: k
+// splits, at most one per tile.  A split is a whole number of tiles and spans less than 2^31 bytes of the table.
+static int match8_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int n_pairs, int *splits_out,
+                             int *cols_per_split_out) {
+  const long blocks = (long)idiv_up(num_pts1, kM8RowsPerBlock) * n_pairs;
+  int splits = (int)std::max(1L, std::min((2L * ctx->num_cus + blocks - 1) / blocks,
+                                          (long)idiv_up(num_pts2, 4 * kM8TileCols)));
+  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, kM8TileCols));
+  splits = std::min(splits, 65535);
+  constexpr int kMaxColsPerSplit = (int)((0x7fffffffu / 128u) / kM8TileCols * kM8TileCols);
+  splits = std::max(splits, idiv_up(num_pts2, kMaxColsPerSplit));
+  if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "Match8: too many descriptors in set 2 (%d)", num_pts2);
+  const int cols_per_split = idiv_up(idiv_up(num_pts2, splits), kM8TileCols) * kM8TileCols;
+  *splits_out = idiv_up(num_pts2, cols_per_split);
+  *cols_per_split_out = cols_per_split;
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_quantize_descriptors(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                           int n_images, int max_pts, unsigned char *d_q, int *d_sums) {
+  TRY(enter(ctx));
+  if (n_images < 0 || n_images > 65535 || max_pts < 0 || max_pts > (1 << 24))
+    return fail(CUSIFT_ERR_INVALID, "QuantizeDescriptors: n_images %d outside [0, 65535] or max_pts %d outside [0, 2^24]",
+                n_images, max_pts);
+  if (n_images == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_points || !d_q || !d_sums) return fail(CUSIFT_ERR_INVALID, "QuantizeDescriptors: missing data");
+  if (!aligned16(d_q)) return fail(CUSIFT_ERR_INVALID, "QuantizeDescriptors: d_q must be 16-byte aligned");
+  if (((uintptr_t)d_sums & 7) != 0) return fail(CUSIFT_ERR_INVALID, "QuantizeDescriptors: d_sums must be 8-byte aligned");
+  hipLaunchKernelGGL(quantize_kernel, dim3(idiv_up(max_pts, 8), n_images), dim3(256), 0, ctx->stream, d_points, d_counters,
+                     max_pts, d_q, d_sums);
+  return check_launch("quantize_descriptors");
+}
+
+extern "C" int cusift_desc8_sums(cusift_ctx *ctx, const unsigned char *d_q, int n, int *d_sums) {
+  TRY(enter(ctx));
+  if (n <= 0) return CUSIFT_OK;
+  if (!d_q || !d_sums) return fail(CUSIFT_ERR_INVALID, "Desc8Sums: missing data");
+  if (!aligned16(d_q)) return fail(CUSIFT_ERR_INVALID, "Desc8Sums: d_q must be 16-byte aligned");
+  if (((uintptr_t)d_sums & 7) != 0) return fail(CUSIFT_ERR_INVALID, "Desc8Sums: d_sums must be 8-byte aligned");
+  hipLaunchKernelGGL(desc8_sums_kernel, dim3(idiv_up(n, 32)), dim3(256), 0, ctx->stream, d_q, n, d_sums);
+  return check_launch("desc8_sums");
+}
+
+static int check_tables8(const char *who, const unsigned char *d_q, const int *d_sums) {
+  if (!d_q || !d_sums) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
+  if (!aligned16(d_q)) return fail(CUSIFT_ERR_INVALID, "%s: a descriptor table must be 16-byte aligned", who);
+  if (((uintptr_t)d_sums & 7) != 0) return fail(CUSIFT_ERR_INVALID, "%s: a sums table must be 8-byte aligned", who);
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
+                             const int *d_sums1, const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2,
+                             const int *d_sums2, int distance) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "Match8: missing data");
+  TRY(check_tables8("Match8", d_q1, d_sums1));
+  TRY(check_tables8("Match8", d_q2, d_sums2));
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8: distance must be 0 or 1");
+  const int row_blocks = idiv_up(num_pts1, kM8RowsPerBlock);
+  int splits, cols_per_split;
+  TRY(match8_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
+  const int n1_pad = row_blocks * kM8RowsPerBlock;
+  Match8Partial *partials = nullptr;
+  if (splits > 1) {
+    const size_t bytes = sizeof(Match8Partial) * (size_t)splits * n1_pad;
+    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
+    partials = reinterpret_cast<Match8Partial *>(ctx->match_scratch);
+  }
+  hipLaunchKernelGGL(distance ? match8_kernel<true> : match8_kernel<false>, dim3(row_blocks, splits), dim3(256), 0,
+                     ctx->stream, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, cols_per_split,
+                     partials, n1_pad);
+  if (splits > 1)
+    hipLaunchKernelGGL(distance ? match8_merge_kernel<true> : match8_merge_kernel<false>, dim3(idiv_up(num_pts1, 256)),
+                       dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2,
+                       (const Match8Partial *)partials, n1_pad, splits);
+  return check_launch("match8");
+}
+
+extern "C" int cusift_match8_batch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
+                                   const unsigned int *d_counters, int n_images, int max_pts, const int *h_pairs,
+                                   int n_pairs, int distance, cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8Batch: distance must be 0 or 1");
+  if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "Match8Batch: n_pairs %d outside [0, 65535]", n_pairs);
+  if (n_images < 0 || n_images > 65535)
+    return fail(CUSIFT_ERR_INVALID, "Match8Batch: n_images %d outside [0, 65535]", n_images);
+  if (max_pts < 0 || max_pts > (1 << 20))
+    return fail(CUSIFT_ERR_INVALID, "Match8Batch: max_pts %d outside [0, 2^20]", max_pts);
+  if (n_pairs > 0 && !h_pairs) return fail(CUSIFT_ERR_INVALID, "Match8Batch: NULL pair list");
+  for (int p = 0; p < 2 * n_pairs; ++p)
+    if (h_pairs[p] < 0 || h_pairs[p] >= n_images)
+      return fail(CUSIFT_ERR_INVALID, "Match8Batch: pair %d names frame %d outside [0, %d)", p / 2, h_pairs[p], n_images);
+  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_rows) return fail(CUSIFT_ERR_INVALID, "Match8Batch: missing data");
+  TRY(check_tables8("Match8Batch", d_q, d_sums));
+  const int row_blocks = idiv_up(max_pts, kM8RowsPerBlock);
+  int splits, cols_per_split;
+  TRY(match8_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
+  const int n1_pad = row_blocks * kM8RowsPerBlock;
+  const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
+  const size_t part_b = splits > 1 ? sizeof(Match8Partial) * (size_t)n_pairs * splits * n1_pad : 0;
+  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b, "", false));
+  int *d_pairs = (int *)ctx->pairs_scratch;
+  Match8Partial *partials = splits > 1 ? (Match8Partial *)(ctx->pairs_scratch + list_b) : nullptr;
+  HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(distance ? match8_batch_kernel<true> : match8_batch_kernel<false>,
+                     dim3(row_blocks, splits, n_pairs), dim3(256), 0, ctx->stream, d_q, d_sums, d_counters, max_pts,
+                     (const int *)d_pairs, cols_per_split, partials, n1_pad, d_rows);
+  if (splits > 1)
+    hipLaunchKernelGGL(distance ? match8_batch_merge_kernel<true> : match8_batch_merge_kernel<false>,
+                       dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream, d_counters, max_pts,
+                       (const int *)d_pairs, cols_per_split, (const Match8Partial *)partials, n1_pad, splits, d_rows);
+  return check_launch("match8_batch");
+}

@@ -3,7 +3,7 @@
  * planar registration built on both (seeded RANSAC + refit on the device), the RANSAC rigid transform and the RGB-D
  * registration built on them (depth lift, match selection, the fused call for one frame pair and for a pair list over a
  * batch of frames), the epipolar registration, the calibrated pose behind it and the absolute pose
- * from 3-D/2-D matches (PnP).
+ * from 3-D/2-D matches (PnP), the 8-bit descriptors (quantiser, int8 matcher).
  * Part of the C ABI of libcusift_amd.so; conventions and the map of the four headers: cusift_amd.h.
  */
 #ifndef CUSIFT_AMD_EXTRAS_H
@@ -564,6 +564,58 @@ int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_points, con
                               int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
                               int model, const double *h_models /* [n_pairs][9] */, float radius,
                               cusift_match_row *d_rows);
+
+/* ---- 8-bit descriptors: quantised on the device, matched on the int8 matrix pipe ------------------------------------
+ * The byte descriptor is what OpenCV, VLFeat and COLMAP store and exchange: 128 unsigned bytes per keypoint, 512 v clipped
+ * to 255 ("8-bit descriptors").  A TABLE here is unsigned char [n][128], dense (record i at byte 128 i)
+ * and 16-byte aligned, with int sums[n][2] = (sum of q, sum of q * q) over the record's 128 bytes beside it, 8-byte
+ * aligned.  Integer scores are exact: every output below is pinned bit for bit by a few lines of integer arithmetic.
+ *
+ * cusift_quantize_descriptors: d_points[n_images][max_pts] + d_counters[n_images] as cusift_extract_batch leaves them
+ * (d_counters == NULL: max_pts records each, as cusift_lift_depth; counts are clamped to max_pts on the device) ->
+ * d_q[n_images][max_pts][128] and d_sums[n_images][max_pts][2].  Per element v = data[k], in fp32, pinned to these
+ * expressions (the build uses -ffp-contract=off):
+ *     t = 512.0f * v                                   (exact)
+ *     u = t + 0.5f                                     (one rounding)
+ *     q = (v > 0) ? (u < 255.0f ? (int)u : 255) : 0    ((int) truncates)
+ * so NaN, zeros and negatives give 0, +infinity and anything at or above 255/512 give 255.  Rows past a frame's count
+ * are not written.  One launch, no read-back, asynchronous on the context's stream; the records are not written.
+ * CUSIFT_ERR_INVALID (nothing enqueued): n_images outside [0, 65535], max_pts outside [0, 2^24], missing buffers, a d_q
+ * that is not 16-byte aligned, a d_sums that is not 8-byte aligned.  n_images == 0 or max_pts == 0: CUSIFT_OK. */
+int cusift_quantize_descriptors(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
+                                int n_images, int max_pts, unsigned char *d_q, int *d_sums);
+/* The same two sums for n byte descriptors that came from somewhere else (a COLMAP or OpenCV database): d_sums[i] =
+ * (sum q, sum q * q) of d_q[i][0..128).  n <= 0: CUSIFT_OK, nothing enqueued.  Refusals as above. */
+int cusift_desc8_sums(cusift_ctx *ctx, const unsigned char *d_q, int n, int *d_sums);
+/* cusift_match on two tables: writes score, ambiguity, match, match_xpos, match_ypos of d_sift1[0 .. num_pts1) and nothing
+ * else; d_sift2 is read only for coords2D of the match (of record 0 when match is outside [0, num_pts2), as cusift_match).
+ * The descriptors of the records themselves are not read: row i is d_q1[i], column j is d_q2[j].
+ * SCORES, all integers: S = sum_k q1[k] * q2[k];  for distance 1 the key of column j is D = sum q1^2 + sum q2^2 - 2 S (the
+ * two sums from the sums tables) and its score is (float)D * 2^-18; for distance 0 the key is -S and the score is
+ * (float)S * 2^-18.  Both integers stay below 2^24 (128 * 255^2 = 8,323,200), so the floats are exact.
+ * MODEL: match = the LOWEST column with the smallest key; score = that column's score; second = the score of the second
+ * smallest key of the multiset of all columns' keys, so a tie for best gives second == best; with a single column second
+ * is cusift_match's initial value, 999 for distance 1 and -1 for distance 0.  ambiguity, cusift_match's two expressions
+ * unchanged (the 1e-6 is a double): distance 1: (float)(best / (second + 1e-6)); distance 0: (float)((1 - best) / (1 -
+ * second + 1e-6)).
+ * The model does not depend on scan order, tile or split count: the same input gives the same bytes under every
+ * CUSIFT_POLICY_MATCH_SPLITS (honoured: k > 0 asks for k column splits, at most one per 64 columns), there are no atomics,
+ * and every merge breaks ties on the lower column -- with integer keys exact ties are ordinary.
+ * QUANTISED DESCRIPTORS ARE NOT UNIT VECTORS (sum (q / 512)^2 is near 1, not 1), so for distance 0 `1 - best` can be
+ * slightly negative and the ambiguity with it; the formula is the reference's, verbatim.  Distance 1 is the mode to use.
+ * A count <= 0 on either side: CUSIFT_OK, nothing enqueued.  CUSIFT_ERR_INVALID (nothing enqueued): a NULL pointer, a
+ * table that is not 16-byte aligned, a sums table that is not 8-byte aligned, a distance other than 0 or 1.  Asynchronous
+ * on the context's stream; per-split scratch (16 bytes per split and row) lives in the context. */
+int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1, const int *d_sums1,
+                  const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2, const int *d_sums2, int distance);
+/* cusift_match8 over a pair list, on the tables cusift_quantize_descriptors writes for a batch: the contract of
+ * cusift_match_batch (pairs, counts read on the device and clamped to max_pts, the grid sized from max_pts, rows past
+ * frame 1's count not written, no row for a pair whose frame 2 is empty, (a, a) legal, the same refusals) with
+ * cusift_match8's model: d_rows[p * max_pts + i] = score, ambiguity and match exactly as cusift_match8 writes them for
+ * the tables of pair p's two frames.  Also refused: misaligned tables. */
+int cusift_match8_batch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
+                        const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                        const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance, cusift_match_row *d_rows);
 
 /* cusift_register_rgbd for every pair of a list, device-resident from the extractor's batch + depth images to one
  * [R | t] per pair: ONE cusift_lift_depth over all frames (frame k's depth image at d_depth + k * image_stride_elems),

@@ -143,6 +143,96 @@ inline std::vector<SiftMatch *> MatchSiftDataMutual(SiftData &data1, SiftData &d
   return matches;
 }
 
+// ---- 8-bit descriptors (not in the reference; cusift_quantize_descriptors, cusift_match8) ------------------------------
+// The byte descriptors of a SiftData: record i's 128 bytes at h_data / d_data + 128 i -- 512 v clipped to 255, the
+// convention of OpenCV, VLFeat and COLMAP -- and d_sums[2 i], d_sums[2 i + 1] = sum q, sum q^2 on the device.  Copying is
+// disabled, as for SiftData.
+struct SiftDescriptors8 {
+  int numPts = 0;                   // descriptors held
+  int maxPts = 0;                   // descriptors allocated
+  unsigned char *h_data = nullptr;  // [maxPts][128], or nullptr: no host copy wanted
+  unsigned char *d_data = nullptr;  // [maxPts][128], 16-byte aligned
+  int *d_sums = nullptr;            // [maxPts][2]
+  SiftDescriptors8() = default;
+  SiftDescriptors8(const SiftDescriptors8 &) = delete;
+  SiftDescriptors8 &operator=(const SiftDescriptors8 &) = delete;
+  ~SiftDescriptors8() { release(); }
+  void release() {
+    if (d_data) cusift_free(d_data);
+    if (d_sums) cusift_free(d_sums);
+    cusift_dropin::host_free(h_data);
+    h_data = d_data = nullptr;
+    d_sums = nullptr;
+    numPts = maxPts = 0;
+  }
+};
+
+inline void InitSiftDescriptors8(SiftDescriptors8 &desc, int num = 1024, bool host = false) {
+  desc.release();
+  if (num <= 0) return;
+  void *p = nullptr;
+  safeCall(cusift_malloc(&p, (size_t)128 * (size_t)num));
+  desc.d_data = static_cast<unsigned char *>(p);
+  safeCall(cusift_malloc(&p, sizeof(int) * 2 * (size_t)num));
+  desc.d_sums = static_cast<int *>(p);
+  if (host) desc.h_data = static_cast<unsigned char *>(cusift_dropin::host_alloc((size_t)128 * (size_t)num));
+  desc.maxPts = num;
+}
+inline void FreeSiftDescriptors8(SiftDescriptors8 &desc) { desc.release(); }
+
+// Quantises the descriptors of data's device records into desc (grown when it holds fewer than data.numPts, keeping
+// whether it has a host copy) and copies the bytes to desc.h_data when that is not null (blocking then; otherwise
+// asynchronous on the calling thread's context).
+inline void QuantizeSiftData(SiftData &data, SiftDescriptors8 &desc) {
+  if (desc.maxPts < data.numPts) InitSiftDescriptors8(desc, data.numPts, desc.h_data != nullptr);
+  desc.numPts = data.numPts;
+  if (!data.numPts || data.d_data == nullptr) return;
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_quantize_descriptors(ctx, reinterpret_cast<const cusift_point *>(data.d_data), nullptr, 1, data.numPts,
+                                       desc.d_data, desc.d_sums));
+  if (desc.h_data != nullptr) safeCall(cusift_memcpy_d2h(ctx, desc.h_data, desc.d_data, (size_t)128 * (size_t)data.numPts));
+}
+
+// MatchSiftData on the byte descriptors (cusift_match8: int8 matrix pipe, exact integer scores scaled by 2^-18 to
+// MatchSiftData's range): the same filter, the same return type.  desc1 / desc2 hold the descriptors of data1 / data2
+// (QuantizeSiftData, or bytes from elsewhere with cusift_desc8_sums); the float descriptors of the records are not read.
+inline std::vector<SiftMatch *> MatchSiftData8(SiftData &data1, SiftDescriptors8 &desc1, SiftData &data2,
+                                               SiftDescriptors8 &desc2, MatchSiftDistance distance = MatchSiftDistanceL2,
+                                               float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                               MatchType type = MatchType2D) {
+  std::vector<SiftMatch *> matches;
+  if (!data1.numPts || !data2.numPts) return matches;
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
+  if (desc1.numPts != data1.numPts || desc2.numPts != data2.numPts) return matches;  // not the descriptors of these sets
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match8(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts, desc1.d_data, desc1.d_sums,
+                         reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts, desc2.d_data, desc2.d_sums,
+                         distance == MatchSiftDistanceL2 ? 1 : 0));
+  if (data1.h_data != nullptr)  // the 5 match fields of every record, as MatchSiftData
+    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
+                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
+  else
+    safeCall(cusift_ctx_synchronize(ctx));
+  if (data1.h_data == nullptr) return matches;
+  const float thresh2 = scoreThreshold * scoreThreshold;
+  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
+  for (int i = 0; i < data1.numPts; i++) {
+    SiftPoint &p = data1.h_data[i];
+    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
+    if (p.match < 0 || p.match >= data2.numPts || data2.h_data == nullptr) continue;
+    if (type == MatchType2D || (p.coords3D[2] != 0 && data2.h_data[p.match].coords3D[2] != 0)) {
+      SiftMatch *m = new SiftMatch();
+      m->pt1 = &p;
+      m->pt2 = &data2.h_data[p.match];
+      m->score = p.score;
+      m->ambiguity = p.ambiguity;
+      m->error = 0.0f;
+      matches.push_back(m);
+    }
+  }
+  return matches;
+}
+
 // The cross-check inside the registrations (not in the reference; cusift_ctx_set_cross_check): while on, RegisterPlanar,
 // RegisterRGBD and their ...Sequence forms (homography.h, rgbd.h) feed their RANSAC mutual matches only -- record i of
 // the first set must be the best of its own match, the lowest record on exactly tied best scores.  Acts on the calling
