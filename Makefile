@@ -63,6 +63,7 @@ cpp-tests: $(LIB)
 	$(MAKE) -C $(ROOT)/tests/cpp_pnp
 	$(MAKE) -C $(ROOT)/tests/cpp_sequence_pose
 	$(MAKE) -C $(ROOT)/tests/cpp_match8
+	$(MAKE) -C $(ROOT)/tests/cpp_match8_mutual
 
 check: cpp-tests
 	$(MAKE) -C $(ROOT)/tests/cpp check

@@ -20,10 +20,12 @@ class BatchExtractor:
     selected on the device before anything is described; counts are then the kept counts.
     cross_check = True: register_planar, register_epipolar, register_pose, register_planar_sequence and register_sequence feed their
     RANSAC mutual matches only (cusift_ctx_set_cross_check on this extractor's context).
+    match_bits = 8: the same calls quantise their records and match the bytes on the int8 matrix pipe
+    (cusift_ctx_set_match_bits on this extractor's context); 32, the default, matches the float descriptors.
     """
 
     def __init__(self, n_images, w, h, params=None, device=None, pitch=None, n_slots=1, keep_strongest=0,
-                 cross_check=False, **param_overrides):
+                 cross_check=False, match_bits=32, **param_overrides):
         if not torch.cuda.is_available():
             raise capi.CusiftError("BatchExtractor needs a GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -33,6 +35,7 @@ class BatchExtractor:
         self.max_pts = self.params.max_pts
         self.keep_strongest = capi.check_keep_strongest(keep_strongest, self.max_pts)
         self.cross_check = bool(capi.check_cross_check(cross_check))
+        self.match_bits = capi.check_match_bits(match_bits)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream()
             self.ctx = capi.Context(self.device.index, stream=self.stream.cuda_stream)
@@ -40,6 +43,8 @@ class BatchExtractor:
                 self.ctx.set_keep_strongest(self.keep_strongest)
             if self.cross_check:
                 self.ctx.set_cross_check(True)
+            if self.match_bits != 32:
+                self.ctx.set_match_bits(self.match_bits)
             self.ctx.reserve(self.n, self.w, self.h, self.params)
             # n_slots > 1: output ring, so that a consumer (D2H copy, all-gatherv on another stream) can still
             # read step i's SiftData while step i+1 is being extracted
@@ -182,6 +187,18 @@ class BatchExtractor:
         n_i, n_j = self._pair_counts(counts, i, j)
         self.ctx.match8(points[i].data_ptr(), n_i, q[i].data_ptr(), sums[i].data_ptr(), points[j].data_ptr(), n_j,
                         q[j].data_ptr(), sums[j].data_ptr(), distance)
+
+    def match8_mutual(self, i, j, slot=0, distance=1):
+        """match8(i, j) and match8(j, i) from one pass, on the tensors of the last quantize(slot): cusift_match8_mutual
+        writes the five match fields of both frames' records.  i == j is refused (both sets are written).  Asynchronous
+        on the extractor's stream."""
+        if slot not in getattr(self, "_desc8", {}):
+            raise capi.CusiftError("match8_mutual: call quantize(slot=%d) first" % slot)
+        q, sums = self._desc8[slot]
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        self.ctx.match8_mutual(points[i].data_ptr(), n_i, q[i].data_ptr(), sums[i].data_ptr(), points[j].data_ptr(), n_j,
+                               q[j].data_ptr(), sums[j].data_ptr(), distance)
 
     def register_planar_guided(self, i, j, radius=None, slot=0, **opts):
         """register_planar(i, j) with a second, guided matching pass: capi.Context.register_planar_guided over this

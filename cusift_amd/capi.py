@@ -166,6 +166,7 @@ SIGNATURES = {
     "cusift_ctx_set_policy": (_i, [_vp, _i, _i]),
     "cusift_ctx_set_keep_strongest": (_i, [_vp, _i]),
     "cusift_ctx_set_cross_check": (_i, [_vp, _i]),
+    "cusift_ctx_set_match_bits": (_i, [_vp, _i]),
     "cusift_ctx_get_policy": (_i, [_vp, _i, C.POINTER(C.c_int)]),
     "cusift_ctx_arena_bytes": (_sz, [_vp]),
     "cusift_ctx_forks": (C.c_ulong, [_vp]),
@@ -239,6 +240,8 @@ SIGNATURES = {
     "cusift_desc8_sums": (_i, [_vp, _vp, _i, _vp]),
     "cusift_match8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     "cusift_match8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "cusift_match8_mutual": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
+    "cusift_match8_batch_mutual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
@@ -457,6 +460,14 @@ def check_cross_check(on):
     return int(on)
 
 
+def check_match_bits(bits):
+    """What Context.set_match_bits checks before it calls the library (needs no device): returns 32 or 8.  ValueError
+    for anything but the integers 32 and 8."""
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or bits not in (32, 8):
+        raise ValueError("match_bits: 32 or 8, got %r" % (bits,))
+    return int(bits)
+
+
 def check_keep_strongest(k, max_pts=None):
     """What Context.set_keep_strongest checks before it calls the library (needs no device): returns K as an int.
     ValueError for K < 0, a K that is no integer, or (max_pts given) K > max_pts, which the next extraction would refuse."""
@@ -554,6 +565,7 @@ class Context:
             check(lib().cusift_ctx_create_borrowed(C.byref(self._h), device, C.c_void_p(int(stream))))
         self.device = device
         self.cross_check = False  # what set_cross_check last set: the guided chains refuse to run while it is on
+        self.match_bits = 32  # what set_match_bits last set: the guided chains refuse to run while it is 8
 
     @property
     def handle(self):
@@ -877,6 +889,9 @@ class Context:
         if self.cross_check:
             raise CusiftError("guided registration: turn the cross-check off first (set_cross_check(False)) -- the "
                               "guided matcher has no column side")
+        if self.match_bits == 8:
+            raise CusiftError("guided registration: set the match bits back to 32 first (set_match_bits(32)) -- there "
+                              "is no 8-bit guided matcher")
         first = register(d_sift1, n1, d_sift2, n2, **opts)
         distance = opts.get("distance", 1)
         rule, lo, hi = _rule_defaults(distance, opts.get("rule"), opts.get("lo"), opts.get("hi"))
@@ -1014,6 +1029,14 @@ class Context:
         check(lib().cusift_ctx_set_cross_check(self.handle, check_cross_check(on)))
         self.cross_check = bool(on)
 
+    def set_match_bits(self, bits):
+        """cusift_ctx_set_match_bits: 32 (default) or 8.  While 8, the calls set_cross_check affects quantise their
+        records into scratch of the context and match the bytes on the int8 matrix pipe (match8 / match8_mutual and the
+        batch forms) -- bit for bit the staged route quantize_descriptors + match8 + estimate_*.  Nothing else reads it;
+        the guided chains refuse to run while it is 8."""
+        check(lib().cusift_ctx_set_match_bits(self.handle, check_match_bits(bits)))
+        self.match_bits = int(bits)
+
     def select_strongest(self, d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
         """cusift_select_strongest: the selection alone, on lists of 64-byte record heads.  d_heads [n_lists, n_images,
         capacity, 64 B], d_counts uint32 [n_lists, n_images] (in: held, out: kept) and d_kept uint32 [n_images] are
@@ -1097,6 +1120,18 @@ class Context:
         """cusift_match8: match() on two byte tables (int8 matrix pipe, exact integer scores scaled by 2^-18): writes the
         same five fields of d_sift1[0 .. n1); d_sift2 is read for coords2D of the match only.  Asynchronous."""
         check(lib().cusift_match8(self.handle, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance))
+
+    def match8_mutual(self, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance=1):
+        """cusift_match8_mutual: match8() in both directions from one pass: d_sift1 gets match8(1, 2)'s bytes, d_sift2
+        gets match8(2, 1)'s.  Overlapping record ranges are refused.  Asynchronous."""
+        check(lib().cusift_match8_mutual(self.handle, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance))
+
+    def match8_batch_mutual(self, d_q, d_sums, d_counters, n_images, max_pts, pairs, d_rows, d_rows_back, distance=1):
+        """cusift_match8_batch_mutual: match8_batch() plus d_rows_back[P][max_pts], the column side of every pair (what
+        match8_batch would write for the swapped pair).  Asynchronous."""
+        pairs = pair_list(pairs)
+        check(lib().cusift_match8_batch_mutual(self.handle, d_q, d_sums, d_counters, n_images, max_pts,
+                                               pairs.ctypes.data, len(pairs), distance, d_rows, d_rows_back))
 
     def match8_batch(self, d_q, d_sums, d_counters, n_images, max_pts, pairs, d_rows, distance=1):
         """cusift_match8_batch: match_batch() on the tables quantize_descriptors() wrote for a batch, match8()'s model;

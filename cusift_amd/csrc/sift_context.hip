@@ -283,6 +283,7 @@ extern "C" int cusift_ctx_destroy(cusift_ctx *ctx) {
   if (ctx->pairs_scratch) (void)hipFree(ctx->pairs_scratch);
   if (ctx->match_scratch) (void)hipFree(ctx->match_scratch);
   if (ctx->match_col_scratch) (void)hipFree(ctx->match_col_scratch);
+  if (ctx->q8_scratch) (void)hipFree(ctx->q8_scratch);
   if (ctx->d_counter1) (void)hipFree(ctx->d_counter1);
   if (ctx->d_queue) (void)hipFree(ctx->d_queue);
   if (ctx->h_counter1) (void)hipHostFree(ctx->h_counter1);
@@ -375,6 +376,13 @@ extern "C" int cusift_ctx_set_cross_check(cusift_ctx *ctx, int on) {
   if (!ctx) return fail(CUSIFT_ERR_INVALID, "ctx is NULL");
   if (on != 0 && on != 1) return fail(CUSIFT_ERR_INVALID, "cross_check: 0 (off) or 1 (on), got %d", on);
   ctx->cross_check = on;
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_ctx_set_match_bits(cusift_ctx *ctx, int bits) {
+  if (!ctx) return fail(CUSIFT_ERR_INVALID, "ctx is NULL");
+  if (bits != 32 && bits != 8) return fail(CUSIFT_ERR_INVALID, "match_bits: 32 (fp32) or 8 (bytes), got %d", bits);
+  ctx->match_bits = bits;
   return CUSIFT_OK;
 }
 

@@ -234,6 +234,9 @@ struct cusift_ctx {
   // per-split partials (live together with register_scratch in the last two)
   char *pairs_scratch = nullptr;
   size_t pairs_scratch_bytes = 0;
+  // the byte tables and sums the registrations quantise into while cusift_ctx_set_match_bits is 8 (sift_match8.hip)
+  char *q8_scratch = nullptr;
+  size_t q8_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;
@@ -251,6 +254,7 @@ struct cusift_ctx {
   bool recording = false;  // inside cusift_graph_create's capture
   int keep_strongest = 0;  // cusift_ctx_set_keep_strongest: K > 0, every extraction keeps the K strongest keypoints per image
   int cross_check = 0;     // cusift_ctx_set_cross_check: 1, the six cusift_register_* calls keep mutual matches only
+  int match_bits = 32;     // cusift_ctx_set_match_bits: 8, the registrations quantise and match on the int8 matrix pipe
   unsigned long forks = 0;  // extractions that took the side stream
   // the lists' counters in the arena that the last extraction's join_counts_kernel left zero (stream order): the next
   // extraction that uses exactly them skips its memset.  Anything else that writes the arena resets this.
@@ -379,6 +383,12 @@ static int grow_scratch(cusift_ctx *ctx, T *&ptr, size_t &have, size_t bytes, co
 int enter(cusift_ctx *ctx);
 int check_launch(const char *what);
 int ensure_arena(cusift_ctx *ctx, size_t bytes);
+// sift_match8.hip, for the registrations' matcher fronts (sift_register.hip)
+int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
+                        int distance, cusift_point *d_back);
+int match8_batch_enqueue(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int n_images,
+                         int max_pts, const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
+                         cusift_match_row *d_rows_back, const int **d_pairs_out);
 int ensure_side_stream(cusift_ctx *ctx);
 size_t bands_arena_bytes(int n_bands, int max_pts);
 void scale_down_taps(ScaleDownTaps &T, float variance);

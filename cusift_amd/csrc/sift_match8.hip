@@ -1,7 +1,8 @@
 // sift_match8.hip -- 8-bit descriptors: the quantiser, the two sums of a byte descriptor, and the brute-force matcher on
 // the int8 matrix pipe (v_mfma_i32_16x16x64_i8), for a pair and for a pair list.  The definitions, expression by
 // expression, are in include/cusift_amd_extras.h (cusift_quantize_descriptors, cusift_desc8_sums, cusift_match8,
-// cusift_match8_batch); this text is how they are computed.
+// cusift_match8_batch, cusift_match8_mutual, cusift_match8_batch_mutual); this text is how they are computed.  At the end:
+// the registrations' matcher fronts while cusift_ctx_set_match_bits is 8.
 //
 // Tables: q[n][128] unsigned bytes, dense and 16-byte aligned; sums[n][2] = (sum q, sum q^2) as int.
 //
@@ -112,13 +113,65 @@ __device__ __forceinline__ void m8_write_row(cusift_match_row *__restrict__ row,
   *reinterpret_cast<f4 *>(row) = v;
 }
 
+// ---- the column side (cusift_match8_mutual, cusift_match8_batch_mutual) -------------------------------------------------
+// For every column the best and second best ROW, from the accumulators the row side already holds.  In the C/D layout lane
+// (r, g) has, per B fragment, the 16 scores of one column against rows 16 i + 4 g + j of its wave.  The column's order over
+// the rows does not depend on the column's own term, so the scan runs on
+//     key'' = R - 2 S'   (L2)          key'' = -128 sum q1 - S'   (dot product)
+// with the ROW's term (m8_col_term of the row's sums: the row is the "column" of the swapped call), and the column's term
+// (m8_row_term of its sums) is added once, behind the scan: the same integers as the row side, D or -S.  A row past n1
+// carries kM8ColMasked instead.  |key''| < 2^23 for a real row, so kM8ColBias - key'' lies in (2^24, 2^26) for a real row
+// and below 2^24 for a padding row, and a wave sees 64 rows: (bias - key'') << 6 | (63 - local row) is one unsigned word
+// whose DESCENDING order is that of (key, row) ascending.  Its maximum is the best key with the lowest row, the second
+// largest word carries the second smallest key of the multiset, and 0 is "nothing yet".  The 16 row terms are kept
+// negated, pre-shifted, with the row in their low bits; the accumulator enters shifted by 7 (2 S', L2) or 6, which
+// leaves the low 6 bits alone.  Per score: one shift-add, one max, one med3.  Then two cross-lane
+// steps fold the four g groups of a column, lanes g == 0 leave (best word, second word) in LDS -- [tile parity][wave][64]
+// -- and behind the NEXT tile's barrier 16 lanes of every wave fold the four waves of a column as (key, row) pairs with the
+// block's row numbers (m8_merge: the words' local rows do not order rows of different waves) and hand the final keys to
+// out.  A buffer is written again two tiles later, behind a barrier that every wave reaches only after its drain.
+constexpr int kM8ColBias = 1 << 25;
+constexpr int kM8ColMasked = (1 << 25) - (1 << 23);  // bias - masked - 2 S' stays in [2^22, 2^24)
+constexpr int kM8ColNone = 1 << 24;                  // key'' = bias - (word >> 6) above this is no row
+
+struct M8NoCols {
+  static constexpr bool kOn = false;
+};
+template <class ColOut>
+struct M8Cols {
+  static constexpr bool kOn = true;
+  uint2 *buf;  // [2][4][kM8TileCols]
+  ColOut out;  // out(column, best, second, row): final keys, kM8Init where there is no second
+};
+
+__device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) { return max(min(a, b), min(max(a, b), c)); }
+
+// the columns [c_prev, c_prev + 64) of the tile whose words lie in buffer `par`
+template <bool kL2, class Cols>
+__device__ __forceinline__ void m8_cols_drain(const Cols &cols, const int *__restrict__ sums2, int c_prev, int col_end,
+                                              int par, int lane, int wv) {
+  const int j = 16 * wv + lane, col = c_prev + j;
+  if (lane < 16 && col < col_end) {
+    int best = kM8Init, second = kM8Init, idx = -1;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const uint2 e = cols.buf[(par * 4 + w) * kM8TileCols + j];
+      m8_merge(best, second, idx, kM8ColBias - (int)(e.x >> 6), kM8ColBias - (int)(e.y >> 6),
+               (int)blockIdx.x * kM8RowsPerBlock + w * kM8RowsPerWave + 63 - (int)(e.x & 63u));
+    }
+    const int2 s = *reinterpret_cast<const int2 *>(sums2 + 2 * (size_t)col);
+    const int ct = m8_row_term<kL2>(s.x, s.y);
+    cols.out(col, best + ct, second > kM8ColNone ? kM8Init : second + ct, idx);
+  }
+}
+
 // One workgroup's 256 rows [blockIdx.x * 256 ..) of (q1, sums1, n1) against the columns [col_begin, col_end) of
 // (q2, sums2); col_begin < col_end and blockIdx.x * 256 < n1.  out(row, best, second, idx) receives every row < n1 once,
-// with final keys.
-template <bool kL2, class Out>
+// with final keys.  Cols = M8Cols: the column side as well, over this workgroup's rows.
+template <bool kL2, class Out, class Cols = M8NoCols>
 __device__ __forceinline__ void m8_block(const unsigned char *__restrict__ q1, const int *__restrict__ sums1, int n1,
                                          const unsigned char *__restrict__ q2, const int *__restrict__ sums2,
-                                         int col_begin, int col_end, unsigned char *sB, Out out) {
+                                         int col_begin, int col_end, unsigned char *sB, Out out, Cols cols = Cols{}) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
@@ -146,6 +199,22 @@ __device__ __forceinline__ void m8_block(const unsigned char *__restrict__ q1, c
       best[i][j] = second[i][j] = kM8Init;
       bidx[i][j] = -1;
     }
+  // column side: the terms of rows 16 i + 4 g + j, biased, shifted, the local row below them
+  unsigned cterm[4][4];
+  if constexpr (Cols::kOn) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int local = 16 * i + 4 * g + j;
+        int term = kM8ColMasked;
+        if (p1_base + local < n1) {
+          const int2 s = *reinterpret_cast<const int2 *>(sums1 + 2 * (size_t)(p1_base + local));
+          term = m8_col_term<kL2>(s.x, s.y);
+        }
+        cterm[i][j] = ((unsigned)(kM8ColBias - term) << 6) | (unsigned)(63 - local);
+      }
+  }
 
   // staging: thread t moves two 16-byte chunks per tile; chunk c = t + 256 k -> column c >> 3, bytes 16 (c & 7).  Raw
   // buffer loads from a descriptor based at the split's first column: a column past col_end reads as 0 and is masked by
@@ -185,6 +254,8 @@ __device__ __forceinline__ void m8_block(const unsigned char *__restrict__ q1, c
     if (threadIdx.x < kM8TileCols) *reinterpret_cast<int *>(buf + threadIdx.x * kM8Stride + 128) = stage_term;
     __syncthreads();
     if (c0 + kM8TileCols < col_end) fetch(c0 + kM8TileCols);  // in flight while this tile is multiplied
+    if constexpr (Cols::kOn)
+      if (c0 > col_begin) m8_cols_drain<kL2>(cols, sums2, c0 - kM8TileCols, col_end, par ^ 1, lane, wv);
 
     const unsigned char *bcol = buf + r * kM8Stride + 16 * g;
 #pragma unroll
@@ -211,7 +282,32 @@ __device__ __forceinline__ void m8_block(const unsigned char *__restrict__ q1, c
           second[i][j] = med3i(old, second[i][j], v);
           bidx[i][j] = v < old ? p2 : bidx[i][j];
         }
+      if constexpr (Cols::kOn) {
+        unsigned cb = 0u, cs = 0u;  // cs <= cb
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const unsigned w = ((unsigned)acc[i][j] << (kL2 ? 7 : 6)) + cterm[i][j];
+            const unsigned old = cb;
+            cb = max(old, w);
+            cs = umed3(old, cs, w);  // the second largest of the three
+          }
+#pragma unroll
+        for (int d = 16; d <= 32; d <<= 1) {  // the four g groups of column p2
+          const unsigned ob = __shfl_xor(cb, d);
+          const unsigned os = __shfl_xor(cs, d);
+          cs = max(min(cb, ob), max(cs, os));
+          cb = max(cb, ob);
+        }
+        if (g == 0) cols.buf[(par * 4 + wv) * kM8TileCols + 16 * t + r] = uint2{cb, cs};
+      }
     }
+  }
+  if constexpr (Cols::kOn) {  // the last tile's columns
+    __syncthreads();
+    m8_cols_drain<kL2>(cols, sums2, col_begin + (col_end - col_begin - 1) / kM8TileCols * kM8TileCols, col_end, par ^ 1, lane,
+                       wv);
   }
   // the tree over the 16 lanes of a row; lane r == 0 of group g ends with rows 16 i + 4 g + j
 #pragma unroll
@@ -325,6 +421,124 @@ __global__ void __launch_bounds__(256) match8_batch_merge_kernel(const unsigned 
     m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
   }
   m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, m.best, m.second, m.idx);
+}
+
+// ---- both directions from one pass ---------------------------------------------------------------------------------------
+// match8_kernel with the column side: set 2's five fields, or -- with more than one row block -- col_partials[row block][n2]
+// for match8_mutual_merge_kernel.  Column splits partition the columns, so every (row block, column) is written once.
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_mutual_kernel(cusift_point *sift1, int n1, const unsigned char *__restrict__ q1,
+                                                           const int *__restrict__ sums1, cusift_point *sift2, int n2,
+                                                           const unsigned char *__restrict__ q2,
+                                                           const int *__restrict__ sums2, int cols_per_split,
+                                                           Match8Partial *__restrict__ partials, int n1_pad,
+                                                           Match8Partial *__restrict__ col_partials) {
+  __shared__ __attribute__((aligned(16))) unsigned char sB[2 * kM8TileCols * kM8Stride];
+  __shared__ uint2 sCols[2 * 4 * kM8TileCols];
+  const int col_begin = blockIdx.y * cols_per_split;
+  const int col_end = min(col_begin + cols_per_split, n2);
+  if (col_begin >= col_end) return;  // uniform; the host sizes the splits so that this never happens
+  auto col_out = [&](int col, int b, int s, int i) {
+    if (col_partials)
+      col_partials[(size_t)blockIdx.x * n2 + col] = Match8Partial{b, s, i, 0};
+    else
+      m8_write_point<kL2>(sift2 + col, sift1, n1, b, s, i);
+  };
+  m8_block<kL2>(
+      q1, sums1, n1, q2, sums2, col_begin, col_end, sB,
+      [&](int p1, int b, int s, int i) {
+        if (partials)
+          partials[(size_t)blockIdx.y * n1_pad + p1] = Match8Partial{b, s, i, 0};
+        else
+          m8_write_point<kL2>(sift1 + p1, sift2, n2, b, s, i);
+      },
+      M8Cols<decltype(col_out)>{sCols, col_out});
+}
+template __global__ void match8_mutual_kernel<false>(cusift_point *, int, const unsigned char *, const int *, cusift_point *,
+                                                     int, const unsigned char *, const int *, int, Match8Partial *, int,
+                                                     Match8Partial *);
+template __global__ void match8_mutual_kernel<true>(cusift_point *, int, const unsigned char *, const int *, cusift_point *,
+                                                    int, const unsigned char *, const int *, int, Match8Partial *, int,
+                                                    Match8Partial *);
+
+// folds the row blocks of one column
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_mutual_merge_kernel(cusift_point *__restrict__ sift2, int n2,
+                                                                 const cusift_point *__restrict__ sift1, int n1,
+                                                                 const Match8Partial *__restrict__ col_partials,
+                                                                 int row_blocks) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n2) return;
+  Match8Partial m = col_partials[j];
+  for (int b = 1; b < row_blocks; ++b) {
+    const Match8Partial o = col_partials[(size_t)b * n2 + j];
+    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
+  }
+  m8_write_point<kL2>(sift2 + j, sift1, n1, m.best, m.second, m.idx);
+}
+
+// match8_batch_kernel with the column side in rows_back[pair][max_pts]; col_partials[pair][row block][max_pts], NULL when
+// max_pts fits one row block.
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_batch_mutual_kernel(const unsigned char *__restrict__ q,
+                                                                 const int *__restrict__ sums,
+                                                                 const unsigned int *__restrict__ counters, int max_pts,
+                                                                 const int *__restrict__ pairs, int cols_per_split,
+                                                                 Match8Partial *__restrict__ partials, int n1_pad,
+                                                                 cusift_match_row *__restrict__ rows,
+                                                                 Match8Partial *__restrict__ col_partials,
+                                                                 cusift_match_row *__restrict__ rows_back) {
+  __shared__ __attribute__((aligned(16))) unsigned char sB[2 * kM8TileCols * kM8Stride];
+  __shared__ uint2 sCols[2 * 4 * kM8TileCols];
+  const int pair = blockIdx.z;
+  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
+  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
+  const int col_begin = blockIdx.y * cols_per_split;
+  if ((int)blockIdx.x * kM8RowsPerBlock >= n1 || col_begin >= n2) return;  // uniform
+  const int col_end = min(col_begin + cols_per_split, n2);
+  auto col_out = [&](int col, int b, int s, int i) {
+    if (col_partials)
+      col_partials[((size_t)pair * gridDim.x + blockIdx.x) * max_pts + col] = Match8Partial{b, s, i, 0};
+    else
+      m8_write_row<kL2>(rows_back + (size_t)pair * max_pts + col, b, s, i);
+  };
+  m8_block<kL2>(
+      q + (size_t)f1 * max_pts * 128, sums + (size_t)f1 * max_pts * 2, n1, q + (size_t)f2 * max_pts * 128,
+      sums + (size_t)f2 * max_pts * 2, col_begin, col_end, sB,
+      [&](int p1, int b, int s, int i) {
+        if (partials)
+          partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = Match8Partial{b, s, i, 0};
+        else
+          m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, b, s, i);
+      },
+      M8Cols<decltype(col_out)>{sCols, col_out});
+}
+template __global__ void match8_batch_mutual_kernel<false>(const unsigned char *, const int *, const unsigned int *, int,
+                                                           const int *, int, Match8Partial *, int, cusift_match_row *,
+                                                           Match8Partial *, cusift_match_row *);
+template __global__ void match8_batch_mutual_kernel<true>(const unsigned char *, const int *, const unsigned int *, int,
+                                                          const int *, int, Match8Partial *, int, cusift_match_row *,
+                                                          Match8Partial *, cusift_match_row *);
+
+// match8_mutual_merge_kernel per pair (blockIdx.y): folds the row blocks that had rows
+template <bool kL2>
+__global__ void __launch_bounds__(256) match8_batch_mutual_merge_kernel(const unsigned int *__restrict__ counters,
+                                                                       int max_pts, const int *__restrict__ pairs,
+                                                                       const Match8Partial *__restrict__ col_partials,
+                                                                       int row_blocks,
+                                                                       cusift_match_row *__restrict__ rows_back) {
+  const int pair = blockIdx.y;
+  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n2 || n1 <= 0) return;
+  const int live = min(row_blocks, (n1 + kM8RowsPerBlock - 1) / kM8RowsPerBlock);  // the others wrote nothing
+  const Match8Partial *__restrict__ mine = col_partials + (size_t)pair * row_blocks * max_pts + j;
+  Match8Partial m = mine[0];
+  for (int b = 1; b < live; ++b) {
+    const Match8Partial o = mine[(size_t)b * max_pts];
+    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
+  }
+  m8_write_row<kL2>(rows_back + (size_t)pair * max_pts + j, m.best, m.second, m.idx);
 }
 
 // ---- the quantiser --------------------------------------------------------------------------------------------------------
@@ -448,6 +662,47 @@ static int check_tables8(const char *who, const unsigned char *d_q, const int *d
   return CUSIFT_OK;
 }
 
+
+// The matcher of one pair: one launch, plus the row-side merge when the columns are split.  d_back != NULL
+// (cusift_match8_mutual): image 2's records again, to receive the column side, merged when there are several row blocks.
+// Both counts >= 1, the arguments are checked.
+static int match8_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
+                         const int *d_sums1, const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2,
+                         const int *d_sums2, int distance, cusift_point *d_back) {
+  const int row_blocks = idiv_up(num_pts1, kM8RowsPerBlock);
+  int splits, cols_per_split;
+  TRY(match8_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
+  const int n1_pad = row_blocks * kM8RowsPerBlock;
+  Match8Partial *partials = nullptr, *col_partials = nullptr;
+  if (splits > 1) {
+    const size_t bytes = sizeof(Match8Partial) * (size_t)splits * n1_pad;
+    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
+    partials = reinterpret_cast<Match8Partial *>(ctx->match_scratch);
+  }
+  if (d_back && row_blocks > 1) {
+    const size_t bytes = sizeof(Match8Partial) * (size_t)row_blocks * num_pts2;
+    TRY(grow_scratch(ctx, ctx->match_col_scratch, ctx->match_col_scratch_bytes, bytes, "", false));
+    col_partials = reinterpret_cast<Match8Partial *>(ctx->match_col_scratch);
+  }
+  if (d_back)
+    hipLaunchKernelGGL(distance ? match8_mutual_kernel<true> : match8_mutual_kernel<false>, dim3(row_blocks, splits),
+                       dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_q1, d_sums1, d_back, num_pts2, d_q2, d_sums2,
+                       cols_per_split, partials, n1_pad, col_partials);
+  else
+    hipLaunchKernelGGL(distance ? match8_kernel<true> : match8_kernel<false>, dim3(row_blocks, splits), dim3(256), 0,
+                       ctx->stream, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, cols_per_split,
+                       partials, n1_pad);
+  if (splits > 1)
+    hipLaunchKernelGGL(distance ? match8_merge_kernel<true> : match8_merge_kernel<false>, dim3(idiv_up(num_pts1, 256)),
+                       dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2,
+                       (const Match8Partial *)partials, n1_pad, splits);
+  if (col_partials)
+    hipLaunchKernelGGL(distance ? match8_mutual_merge_kernel<true> : match8_mutual_merge_kernel<false>,
+                       dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_back, num_pts2,
+                       (const cusift_point *)d_sift1, num_pts1, (const Match8Partial *)col_partials, row_blocks);
+  return check_launch(d_back ? "match8_mutual" : "match8");
+}
+
 extern "C" int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
                              const int *d_sums1, const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2,
                              const int *d_sums2, int distance) {
@@ -457,59 +712,142 @@ extern "C" int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts
   TRY(check_tables8("Match8", d_q1, d_sums1));
   TRY(check_tables8("Match8", d_q2, d_sums2));
   if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8: distance must be 0 or 1");
-  const int row_blocks = idiv_up(num_pts1, kM8RowsPerBlock);
-  int splits, cols_per_split;
-  TRY(match8_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
-  const int n1_pad = row_blocks * kM8RowsPerBlock;
-  Match8Partial *partials = nullptr;
-  if (splits > 1) {
-    const size_t bytes = sizeof(Match8Partial) * (size_t)splits * n1_pad;
-    TRY(grow_scratch(ctx, ctx->match_scratch, ctx->match_scratch_bytes, bytes, "", true));
-    partials = reinterpret_cast<Match8Partial *>(ctx->match_scratch);
-  }
-  hipLaunchKernelGGL(distance ? match8_kernel<true> : match8_kernel<false>, dim3(row_blocks, splits), dim3(256), 0,
-                     ctx->stream, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, cols_per_split,
-                     partials, n1_pad);
-  if (splits > 1)
-    hipLaunchKernelGGL(distance ? match8_merge_kernel<true> : match8_merge_kernel<false>, dim3(idiv_up(num_pts1, 256)),
-                       dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2,
-                       (const Match8Partial *)partials, n1_pad, splits);
-  return check_launch("match8");
+  return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, nullptr);
 }
 
-extern "C" int cusift_match8_batch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
-                                   const unsigned int *d_counters, int n_images, int max_pts, const int *h_pairs,
-                                   int n_pairs, int distance, cusift_match_row *d_rows) {
+// Both directions from one pass over the scores.  Both record sets are written, so their ranges must not overlap.
+extern "C" int cusift_match8_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
+                                    const int *d_sums1, cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2,
+                                    const int *d_sums2, int distance) {
   TRY(enter(ctx));
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8Batch: distance must be 0 or 1");
-  if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "Match8Batch: n_pairs %d outside [0, 65535]", n_pairs);
-  if (n_images < 0 || n_images > 65535)
-    return fail(CUSIFT_ERR_INVALID, "Match8Batch: n_images %d outside [0, 65535]", n_images);
-  if (max_pts < 0 || max_pts > (1 << 20))
-    return fail(CUSIFT_ERR_INVALID, "Match8Batch: max_pts %d outside [0, 2^20]", max_pts);
-  if (n_pairs > 0 && !h_pairs) return fail(CUSIFT_ERR_INVALID, "Match8Batch: NULL pair list");
-  for (int p = 0; p < 2 * n_pairs; ++p)
-    if (h_pairs[p] < 0 || h_pairs[p] >= n_images)
-      return fail(CUSIFT_ERR_INVALID, "Match8Batch: pair %d names frame %d outside [0, %d)", p / 2, h_pairs[p], n_images);
-  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
-  if (!d_rows) return fail(CUSIFT_ERR_INVALID, "Match8Batch: missing data");
-  TRY(check_tables8("Match8Batch", d_q, d_sums));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // nothing to match, on either side
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "Match8Mutual: missing data");
+  TRY(check_tables8("Match8Mutual", d_q1, d_sums1));
+  TRY(check_tables8("Match8Mutual", d_q2, d_sums2));
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8Mutual: distance must be 0 or 1");
+  const uintptr_t a = (uintptr_t)d_sift1, b = (uintptr_t)d_sift2;
+  if (a < b + sizeof(cusift_point) * (size_t)num_pts2 && b < a + sizeof(cusift_point) * (size_t)num_pts1)
+    return fail(CUSIFT_ERR_INVALID, "Match8Mutual: the two record ranges overlap (both are written; match a copy)");
+  return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, d_sift2);
+}
+
+// Uploads the pair list and enqueues the matcher of every pair: one launch, plus a merge when the columns are split and
+// -- with d_rows_back, the column side -- one more when max_pts spans several row blocks.  *d_pairs_out: the list on the
+// device.  n_pairs >= 1, max_pts >= 1, the arguments are checked.
+int match8_batch_launch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums, const unsigned int *d_counters,
+                        int max_pts, const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
+                        cusift_match_row *d_rows_back, const int **d_pairs_out) {
   const int row_blocks = idiv_up(max_pts, kM8RowsPerBlock);
   int splits, cols_per_split;
   TRY(match8_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
   const int n1_pad = row_blocks * kM8RowsPerBlock;
   const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
   const size_t part_b = splits > 1 ? sizeof(Match8Partial) * (size_t)n_pairs * splits * n1_pad : 0;
-  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b, "", false));
+  const size_t col_b = d_rows_back && row_blocks > 1 ? sizeof(Match8Partial) * (size_t)n_pairs * row_blocks * max_pts : 0;
+  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b + col_b, "", false));
   int *d_pairs = (int *)ctx->pairs_scratch;
   Match8Partial *partials = splits > 1 ? (Match8Partial *)(ctx->pairs_scratch + list_b) : nullptr;
+  Match8Partial *col_partials = col_b ? (Match8Partial *)(ctx->pairs_scratch + list_b + part_b) : nullptr;
   HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(distance ? match8_batch_kernel<true> : match8_batch_kernel<false>,
-                     dim3(row_blocks, splits, n_pairs), dim3(256), 0, ctx->stream, d_q, d_sums, d_counters, max_pts,
-                     (const int *)d_pairs, cols_per_split, partials, n1_pad, d_rows);
+  const dim3 grid(row_blocks, splits, n_pairs);
+  if (d_rows_back)
+    hipLaunchKernelGGL(distance ? match8_batch_mutual_kernel<true> : match8_batch_mutual_kernel<false>, grid, dim3(256), 0,
+                       ctx->stream, d_q, d_sums, d_counters, max_pts, (const int *)d_pairs, cols_per_split, partials,
+                       n1_pad, d_rows, col_partials, d_rows_back);
+  else
+    hipLaunchKernelGGL(distance ? match8_batch_kernel<true> : match8_batch_kernel<false>, grid, dim3(256), 0, ctx->stream,
+                       d_q, d_sums, d_counters, max_pts, (const int *)d_pairs, cols_per_split, partials, n1_pad, d_rows);
   if (splits > 1)
     hipLaunchKernelGGL(distance ? match8_batch_merge_kernel<true> : match8_batch_merge_kernel<false>,
                        dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream, d_counters, max_pts,
                        (const int *)d_pairs, cols_per_split, (const Match8Partial *)partials, n1_pad, splits, d_rows);
-  return check_launch("match8_batch");
+  if (col_partials)
+    hipLaunchKernelGGL(distance ? match8_batch_mutual_merge_kernel<true> : match8_batch_mutual_merge_kernel<false>,
+                       dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream, d_counters, max_pts,
+                       (const int *)d_pairs, (const Match8Partial *)col_partials, row_blocks, d_rows_back);
+  if (d_pairs_out) *d_pairs_out = d_pairs;
+  return check_launch(d_rows_back ? "match8_batch_mutual" : "match8_batch");
+}
+
+// every refusal of the 8-bit pair-list calls; *nothing: a list or a capacity of zero
+static int check_batch8(const char *who, const unsigned char *d_q, const int *d_sums, int n_images, int max_pts,
+                        const int *h_pairs, int n_pairs, int distance, const cusift_match_row *d_rows, bool *nothing) {
+  *nothing = true;
+  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "%s: distance must be 0 or 1", who);
+  if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_pairs %d outside [0, 65535]", who, n_pairs);
+  if (n_images < 0 || n_images > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_images %d outside [0, 65535]", who, n_images);
+  if (max_pts < 0 || max_pts > (1 << 20)) return fail(CUSIFT_ERR_INVALID, "%s: max_pts %d outside [0, 2^20]", who, max_pts);
+  if (n_pairs > 0 && !h_pairs) return fail(CUSIFT_ERR_INVALID, "%s: NULL pair list", who);
+  for (int p = 0; p < 2 * n_pairs; ++p)
+    if (h_pairs[p] < 0 || h_pairs[p] >= n_images)
+      return fail(CUSIFT_ERR_INVALID, "%s: pair %d names frame %d outside [0, %d)", who, p / 2, h_pairs[p], n_images);
+  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_rows) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
+  TRY(check_tables8(who, d_q, d_sums));
+  *nothing = false;
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_match8_batch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
+                                   const unsigned int *d_counters, int n_images, int max_pts, const int *h_pairs,
+                                   int n_pairs, int distance, cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  bool nothing;
+  TRY(check_batch8("Match8Batch", d_q, d_sums, n_images, max_pts, h_pairs, n_pairs, distance, d_rows, &nothing));
+  if (nothing) return CUSIFT_OK;
+  return match8_batch_launch(ctx, d_q, d_sums, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, nullptr, nullptr);
+}
+
+extern "C" int cusift_match8_batch_mutual(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
+                                          const unsigned int *d_counters, int n_images, int max_pts, const int *h_pairs,
+                                          int n_pairs, int distance, cusift_match_row *d_rows,
+                                          cusift_match_row *d_rows_back) {
+  TRY(enter(ctx));
+  bool nothing;
+  if (!d_rows_back) return fail(CUSIFT_ERR_INVALID, "Match8BatchMutual: NULL d_rows_back");
+  TRY(check_batch8("Match8BatchMutual", d_q, d_sums, n_images, max_pts, h_pairs, n_pairs, distance, d_rows, &nothing));
+  if (nothing) return CUSIFT_OK;
+  if (d_rows_back == d_rows) return fail(CUSIFT_ERR_INVALID, "Match8BatchMutual: d_rows_back must be distinct from d_rows");
+  return match8_batch_launch(ctx, d_q, d_sums, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, d_rows_back,
+                             nullptr);
+}
+
+// ---- the registrations' matcher front while cusift_ctx_set_match_bits is 8 (sift_register.hip) ---------------------------
+// The byte tables live in the context: q [n][128] on a 256-byte boundary, the sums behind them on another.
+static int tables8_scratch(cusift_ctx *ctx, size_t n, unsigned char **q, int **sums) {
+  const size_t q_b = align_up_sz(128 * n, 256);
+  TRY(grow_scratch(ctx, ctx->q8_scratch, ctx->q8_scratch_bytes, q_b + align_up_sz(8 * n, 256), "", false));
+  *q = reinterpret_cast<unsigned char *>(ctx->q8_scratch);
+  *sums = reinterpret_cast<int *>(ctx->q8_scratch + q_b);
+  return CUSIFT_OK;
+}
+
+// cusift_quantize_descriptors of both record sets, then cusift_match8 -- d_back != NULL: cusift_match8_mutual.  Counts
+// >= 1, the arguments are checked.
+int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
+                        int distance, cusift_point *d_back) {
+  unsigned char *q;
+  int *sums;
+  const size_t n1_slots = align_up_sz((size_t)num_pts1, 32);  // keeps table 2 and its sums aligned
+  TRY(tables8_scratch(ctx, n1_slots + (size_t)num_pts2, &q, &sums));
+  unsigned char *q2 = q + 128 * n1_slots;
+  int *sums2 = sums + 2 * n1_slots;
+  hipLaunchKernelGGL(quantize_kernel, dim3(idiv_up(num_pts1, 8), 1), dim3(256), 0, ctx->stream,
+                     (const cusift_point *)d_sift1, (const unsigned int *)nullptr, num_pts1, q, sums);
+  hipLaunchKernelGGL(quantize_kernel, dim3(idiv_up(num_pts2, 8), 1), dim3(256), 0, ctx->stream, d_sift2,
+                     (const unsigned int *)nullptr, num_pts2, q2, sums2);
+  return match8_launch(ctx, d_sift1, num_pts1, q, sums, d_sift2, num_pts2, q2, sums2, distance, d_back);
+}
+
+// cusift_quantize_descriptors of the whole batch, then cusift_match8_batch -- d_rows_back != NULL: _batch_mutual.
+int match8_batch_enqueue(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int n_images,
+                         int max_pts, const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
+                         cusift_match_row *d_rows_back, const int **d_pairs_out) {
+  unsigned char *q;
+  int *sums;
+  TRY(tables8_scratch(ctx, (size_t)n_images * max_pts, &q, &sums));
+  hipLaunchKernelGGL(quantize_kernel, dim3(idiv_up(max_pts, 8), n_images), dim3(256), 0, ctx->stream, d_points, d_counters,
+                     max_pts, q, sums);
+  return match8_batch_launch(ctx, q, sums, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, d_rows_back,
+                             d_pairs_out);
 }

@@ -168,6 +168,13 @@ static int match_enqueue(cusift_ctx *ctx, const char *who, cusift_point *d_sift1
   TRY(check_distance(who, distance));
   if (num_pts2 < 0 || (num_pts2 > 0 && !d_sift2)) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
   *d_cross = ctx->cross_check ? d_sift2 : nullptr;
+  if (ctx->match_bits == 8) {  // cusift_ctx_set_match_bits: quantise both sets into the context, match the bytes
+    if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match8: nothing to match
+    if (!d_sift1) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
+    if (ctx->cross_check) TRY(check_disjoint(who, d_sift1, num_pts1, d_sift2, num_pts2));
+    return match8_pair_enqueue(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance,
+                               ctx->cross_check ? const_cast<cusift_point *>(d_sift2) : nullptr);
+  }
   if (ctx->cross_check)
     return cusift_match_mutual(ctx, d_sift1, num_pts1, const_cast<cusift_point *>(d_sift2), num_pts2, distance);
   return cusift_match(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance);
@@ -962,10 +969,10 @@ static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int ma
 
 // Uploads the pair list and enqueues the matcher of every pair: one launch, plus the merge when the columns are split.
 // *d_pairs_out: the list on the device, for the stages behind it.  n_pairs >= 1, max_pts >= 1, the list is checked.
-static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
-                              const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
-                              const int **d_pairs_out, cusift_match_row *d_rows_back = nullptr,
-                              const GuideCall *guide = nullptr) {
+static int match_batch_launch32(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                int max_pts, const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
+                                const int **d_pairs_out, cusift_match_row *d_rows_back = nullptr,
+                                const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(max_pts, 64);
   int splits, cols_per_split;
   TRY(match_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
@@ -1009,6 +1016,21 @@ static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, con
   return check_launch("match_batch");
 }
 
+// The matcher of the pair-list registrations: match_batch_launch32, or -- cusift_ctx_set_match_bits 8 -- ONE quantiser
+// launch over the frames the list names (0 .. the highest), honouring the counters, then the batched 8-bit matcher: the
+// same rows.
+static int match_batch_launch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int max_pts,
+                              const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
+                              const int **d_pairs_out, cusift_match_row *d_rows_back) {
+  if (ctx->match_bits != 8)
+    return match_batch_launch32(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, d_pairs_out,
+                              d_rows_back);
+  int n_frames = 0;
+  for (int p = 0; p < 2 * n_pairs; ++p) n_frames = std::max(n_frames, h_pairs[p] + 1);
+  return match8_batch_enqueue(ctx, d_points, d_counters, n_frames, max_pts, h_pairs, n_pairs, distance, d_rows,
+                              d_rows_back, d_pairs_out);
+}
+
 extern "C" int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
                                   int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
                                   cusift_match_row *d_rows) {
@@ -1018,7 +1040,7 @@ extern "C" int cusift_match_batch(cusift_ctx *ctx, const cusift_point *d_points,
   if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
   if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatch: missing data");
   const int *d_pairs = nullptr;
-  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs);
+  return match_batch_launch32(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs);
 }
 
 // cusift_match_batch under one model per pair (sift_match.hip: match_batch_guided_kernel)
@@ -1033,7 +1055,7 @@ extern "C" int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_
   if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatchGuided: missing data");
   const GuideCall guide{model, radius * radius, h_models};
   const int *d_pairs = nullptr;
-  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, nullptr,
+  return match_batch_launch32(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, nullptr,
                             &guide);
 }
 
@@ -1048,7 +1070,7 @@ extern "C" int cusift_match_batch_mutual(cusift_ctx *ctx, const cusift_point *d_
   if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
   if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatchMutual: missing data");
   const int *d_pairs = nullptr;
-  return match_batch_launch(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs,
+  return match_batch_launch32(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs,
                             d_rows_back);
 }
 

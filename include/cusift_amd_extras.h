@@ -491,6 +491,25 @@ int cusift_select_strongest(cusift_ctx *ctx, void *d_heads, int n_lists, int n_i
  * (63 consecutive pairs) at max_pts 32768, 0.8 GB at 8192 -- plus 16 bytes x n_pairs x max_pts of back rows. */
 int cusift_ctx_set_cross_check(cusift_ctx *ctx, int on);
 
+/* The descriptors the registrations match on, a setting of the context: 32 (the default, the float descriptors) or 8
+ * (bytes, on the int8 matrix pipe); anything else: CUSIFT_ERR_INVALID, the setting unchanged.  It affects the calls
+ * cusift_ctx_set_cross_check affects and nothing else: cusift_match, cusift_match_mutual, cusift_match_guided, the
+ * cusift_match8* calls, cusift_find_homography and cusift_estimate_* do not read it.  With 32 every call enqueues exactly
+ * what it always did.  With 8:
+ *   - a pair call quantises both record sets into scratch the context owns (two quantiser launches; tables 16-byte, sums
+ *     8-byte aligned; grown on demand as the other scratch blocks are) and enqueues cusift_match8 -- with the cross-check
+ *     on, cusift_match8_mutual -- in place of cusift_match / cusift_match_mutual;
+ *   - a pair-list call quantises the batch once (ONE launch over the frames the list names, honouring d_counters) and
+ *     enqueues cusift_match8_batch -- with the cross-check on, cusift_match8_batch_mutual -- which writes the same
+ *     cusift_match_row rows.  Everything behind the matcher (marking, selection, RANSAC, refit, read-back) is unchanged.
+ * CONTRACT.  With 8 and the cross-check off a registration returns, bit for bit, what this sequence returns with the same
+ * seed: cusift_quantize_descriptors on both sets, cusift_match8, and the staged cusift_estimate_* (for RGB-D:
+ * cusift_select_matches + cusift_estimate_rigid).  With the cross-check on it is cusift_match8_mutual plus the mutual
+ * condition of cusift_ctx_set_cross_check, and d_sift2's match fields are written as cusift_match8_mutual writes them.
+ * Pair p of a batch has the bits of the pair call at seed + p.  Still one synchronisation and no count read back, and the
+ * number of launches does not depend on the pair list. */
+int cusift_ctx_set_match_bits(cusift_ctx *ctx, int bits);
+
 /* Frame-to-frame registration of an RGB-D pair, device-resident from SiftData + depth to [R | t]: cusift_lift_depth
  * of both frames (one width x height image each, rows pitch_elems apart), cusift_match(distance), the 3-D selection
  * above and the RANSAC + refit of cusift_estimate_rigid over the selected pairs, drawn from `seed` -- sampling, tie
@@ -616,6 +635,36 @@ int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const un
 int cusift_match8_batch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
                         const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
                         const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance, cusift_match_row *d_rows);
+/* cusift_match8 with both directions from one pass over the integer scores.  Set 1 (d_sift1) receives exactly the bytes
+ * cusift_match8 writes.  Set 2 receives the same five fields for each of its records j, over the records of set 1 -- THE
+ * COLUMN SIDE, expression by expression:
+ *     key(i, j) = the same exact integer as on the row side: D = sum_k (q1[i][k] - q2[j][k])^2 for distance 1, -S for 0;
+ *     match     = the LOWEST row i with the smallest key(., j);
+ *     score     = (float)D * 2^-18, or (float)S * 2^-18, of that row;
+ *     second    = the score of the second smallest key of the multiset {key(i, j) : i}, so a tied best gives second ==
+ *                 best; with num_pts1 == 1 it is cusift_match's initial value, 999 for distance 1 and -1 for distance 0;
+ *     ambiguity = cusift_match8's two expressions on (score, second), unchanged;
+ *     match_xpos, match_ypos = coords2D of d_sift1[match].
+ * The keys are symmetric integers, so THE FIELDS OF SET 2 AFTER cusift_match8_mutual(A, B) EQUAL, BYTE FOR BYTE, THE
+ * FIELDS OF SET 1 AFTER cusift_match8(B, A), and set 1's equal cusift_match8(A, B)'s.  Every merge orders (key, row)
+ * pairs: the same bytes on every run, for every grid and under every CUSIFT_POLICY_MATCH_SPLITS; there are no atomics.
+ * A count <= 0 on either side: CUSIFT_OK, nothing enqueued, nothing written.  CUSIFT_ERR_INVALID (nothing enqueued): every
+ * case of cusift_match8, and record ranges that overlap (both are written), as cusift_match_mutual.  Scratch in the
+ * context: cusift_match8's, plus -- with more than 256 records in set 1 -- column partials of
+ * 16 B x ceil(num_pts1 / 256) x num_pts2, folded by one more launch. */
+int cusift_match8_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1, const int *d_sums1,
+                         cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2, const int *d_sums2, int distance);
+/* cusift_match8_batch with the column side: d_rows is exactly what cusift_match8_batch writes; d_rows_back[p * max_pts +
+ * j] = score, ambiguity and match (an index into frame 1) of record j of pair p's frame 2 by the column side above, over
+ * the tables of pair p's two frames.  Rows past frame 2's count are not written, and a pair with an empty frame writes no
+ * row on either side.  (a, a) is legal; the launch count does not depend on the list.  d_rows_back: device memory,
+ * [n_pairs][max_pts], 16-byte aligned, distinct from d_rows.  CUSIFT_ERR_INVALID (nothing enqueued): every case of
+ * cusift_match8_batch, a NULL d_rows_back, d_rows_back == d_rows.  Scratch in the context: cusift_match8_batch's, plus
+ * -- with max_pts > 256 -- column partials of 16 B x n_pairs x ceil(max_pts / 256) x max_pts. */
+int cusift_match8_batch_mutual(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums,
+                               const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                               const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance, cusift_match_row *d_rows,
+                               cusift_match_row *d_rows_back);
 
 /* cusift_register_rgbd for every pair of a list, device-resident from the extractor's batch + depth images to one
  * [R | t] per pair: ONE cusift_lift_depth over all frames (frame k's depth image at d_depth + k * image_stride_elems),

@@ -233,11 +233,62 @@ inline std::vector<SiftMatch *> MatchSiftData8(SiftData &data1, SiftDescriptors8
   return matches;
 }
 
+// MatchSiftData8 with the cross-check (cusift_match8_mutual: both directions from one pass over the integer scores): the
+// match fields of BOTH sets are written -- data2's are what MatchSiftData8(data2, desc2, data1, desc1) would write into it,
+// byte for byte -- and a pair (i, j) is returned only if it passes MatchSiftData's filter and record j's match is i.
+// MatchSiftDataMutual's filter and return type; both SiftData need host AND device buffers; the sets must be distinct.
+inline std::vector<SiftMatch *> MatchSiftData8Mutual(SiftData &data1, SiftDescriptors8 &desc1, SiftData &data2,
+                                                     SiftDescriptors8 &desc2,
+                                                     MatchSiftDistance distance = MatchSiftDistanceL2,
+                                                     float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                                     MatchType type = MatchType2D) {
+  std::vector<SiftMatch *> matches;
+  if (!data1.numPts || !data2.numPts) return matches;
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
+  if (desc1.numPts != data1.numPts || desc2.numPts != data2.numPts) return matches;  // not the descriptors of these sets
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match8_mutual(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts, desc1.d_data,
+                                desc1.d_sums, reinterpret_cast<cusift_point *>(data2.d_data), data2.numPts, desc2.d_data,
+                                desc2.d_sums, distance == MatchSiftDistanceL2 ? 1 : 0));
+  if (data1.h_data == nullptr || data2.h_data == nullptr) {
+    safeCall(cusift_ctx_synchronize(ctx));
+    return matches;
+  }
+  safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score, sizeof(SiftPoint),
+                               5 * sizeof(float), (size_t)data1.numPts));
+  safeCall(cusift_memcpy2d_d2h(ctx, &data2.h_data[0].score, sizeof(SiftPoint), &data2.d_data[0].score, sizeof(SiftPoint),
+                               5 * sizeof(float), (size_t)data2.numPts));
+  const float thresh2 = scoreThreshold * scoreThreshold;
+  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
+  for (int i = 0; i < data1.numPts; i++) {
+    SiftPoint &p = data1.h_data[i];
+    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
+    if (p.match < 0 || p.match >= data2.numPts) continue;
+    SiftPoint &q = data2.h_data[p.match];
+    if (type == MatchType3D && !(p.coords3D[2] != 0 && q.coords3D[2] != 0)) continue;
+    if (q.match != i) continue;  // the cross-check
+    SiftMatch *m = new SiftMatch();
+    m->pt1 = &p;
+    m->pt2 = &q;
+    m->score = p.score;
+    m->ambiguity = p.ambiguity;
+    m->error = 0.0f;
+    matches.push_back(m);
+  }
+  return matches;
+}
+
 // The cross-check inside the registrations (not in the reference; cusift_ctx_set_cross_check): while on, RegisterPlanar,
 // RegisterRGBD and their ...Sequence forms (homography.h, rgbd.h) feed their RANSAC mutual matches only -- record i of
 // the first set must be the best of its own match, the lowest record on exactly tied best scores.  Acts on the calling
 // thread's implicit context, the one those calls use.  RegisterPlanar then writes the match fields of data2's device
 // records too.  MatchSiftData, MatchSiftDataMutual, FindHomography and EstimateRigidTransform do not change.
 inline void SetCrossCheck(bool on) { safeCall(cusift_ctx_set_cross_check(cusift_dropin::ctx(), on ? 1 : 0)); }
+
+// The descriptors the registrations match on (not in the reference; cusift_ctx_set_match_bits): 32, the default, or 8 --
+// RegisterPlanar, RegisterRGBD and the other calls SetCrossCheck affects then quantise their records into scratch of the
+// calling thread's implicit context and match the bytes on the int8 matrix pipe, bit for bit what QuantizeSiftData +
+// MatchSiftData8 + the staged estimate give.  Anything else throws; nothing else reads the setting.
+inline void SetMatchBits(int bits) { safeCall(cusift_ctx_set_match_bits(cusift_dropin::ctx(), bits)); }
 
 #endif  // CUSIFT_AMD_MATCHING_H
