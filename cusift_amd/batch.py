@@ -69,6 +69,26 @@ class BatchExtractor:
                                self.params, self.points.data_ptr(), self.counts.data_ptr())
         return self.points, self.counts
 
+    def describe(self, d_imgs, points=None, counts=None, slot=0, keep_orientation=False, octave_from_scale=False):
+        """cusift_describe_batch: orientation + descriptor of the records as they stand, in place -- by default the
+        slot's own tensors (what extract() left there, or what the caller wrote into them: coords2D and scale in image
+        pixels).  points: uint8 [n, max_pts, 588] device tensor; counts: int32 [n] device tensor of its own, or None with
+        `points` given: every image has max_pts records.  Only enqueues work; returns (points, counts)."""
+        assert d_imgs.is_cuda and d_imgs.dtype == torch.float32 and d_imgs.is_contiguous()
+        assert tuple(d_imgs.shape) == (self.n, self.h, self.pitch), tuple(d_imgs.shape)
+        if points is None:
+            points, own_counts = self.slots[slot]
+            counts = own_counts if counts is None else counts
+        assert points.is_cuda and points.dtype == torch.uint8 and points.is_contiguous()
+        assert tuple(points.shape) == (self.n, self.max_pts, capi.SIFT_POINT_BYTES), tuple(points.shape)
+        if counts is not None:
+            assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.n
+        flags = (capi.DESCRIBE_KEEP_ORIENTATION if keep_orientation else 0) | \
+                (capi.DESCRIBE_OCTAVE_FROM_SCALE if octave_from_scale else 0)
+        self.ctx.describe_batch(d_imgs.data_ptr(), self.n, self.w, self.h, self.pitch, self.h * self.pitch, self.params,
+                                points.data_ptr(), counts.data_ptr() if counts is not None else None, flags)
+        return points, counts
+
     def make_packer(self, stream=None):
         """A `packer(points, counts, max_pts)` for cusift_amd.dist.allgather_siftdata that runs cusift_pack_points on
         `stream` (a torch.cuda.Stream; default: this extractor's stream) through a context of its own that borrows

@@ -16,6 +16,8 @@ CUSIFT_OK = 0
 NUM_STAGES = 8
 STAGE_NAMES = ("scale_down", "laplace_multi", "find_points_multi", "compute_orientations",
                "extract_descriptors", "total", "detect_multi", "describe_all")
+# flags of cusift_describe_batch
+DESCRIBE_KEEP_ORIENTATION, DESCRIBE_OCTAVE_FROM_SCALE = 1, 2
 
 # SiftPoint, cuSIFT.h:10-30 (588 B, no padding)
 SIFT_POINT_DTYPE = np.dtype(
@@ -261,6 +263,7 @@ SIGNATURES = {
     "cusift_expand_points_host": (_i, [_vp, _sz, _vp]),
     "cusift_sort_points_host": (_i, [_vp, _i]),
     "cusift_extract_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp]),
+    "cusift_describe_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp, C.c_uint]),
     "cusift_graph_create": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp]),
     "cusift_graph_launch": (_i, [_vp]),
     "cusift_graph_nodes": (_i, [_vp]),
@@ -1253,6 +1256,48 @@ class Context:
     def extract_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):
         check(lib().cusift_extract_batch(self.handle, d_imgs, n_images, w, h, pitch, image_stride, C.byref(params),
                                          d_points, d_counters))
+
+    def describe_batch(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters=None, flags=0):
+        """cusift_describe_batch: orientation + descriptor of the caller's records, in place (asynchronous).  Image i has
+        min(d_counters[i], max_pts) records, max_pts with d_counters=None; flags: DESCRIBE_KEEP_ORIENTATION,
+        DESCRIBE_OCTAVE_FROM_SCALE."""
+        check(lib().cusift_describe_batch(self.handle, d_imgs, n_images, w, h, pitch, image_stride, C.byref(params),
+                                          d_points, d_counters, int(flags)))
+
+    def describe(self, image, keypoints, keep_orientation=None, **params):
+        """SIFT descriptors at the caller's keypoints (blocking, host arrays): `image` float [h, w], `keypoints` [n, 3]
+        (x, y, scale) or [n, 4] (+ orientation in degrees) in image pixels.  Four columns keep the given orientations
+        unless keep_orientation=False; the octave of each keypoint comes from its scale.  Returns n records
+        (SIFT_POINT_DTYPE) in the caller's order; a keypoint that is not finite, or whose scale is not positive, comes
+        back with a zero descriptor and subsampling 0.  **params: default_params' fields (num_octaves, root_sift,
+        upsample, ...)."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        kp = np.asarray(keypoints, dtype=np.float32)
+        if img.ndim != 2 or kp.ndim != 2 or kp.shape[1] not in (3, 4):
+            raise ValueError("describe: image [h, w] and keypoints [n, 3] or [n, 4], got %r and %r" % (img.shape, kp.shape))
+        if keep_orientation is None:
+            keep_orientation = kp.shape[1] == 4
+        if keep_orientation and kp.shape[1] != 4:
+            raise ValueError("describe: keep_orientation needs a fourth column of orientations")
+        n = len(kp)
+        recs = np.zeros(n, dtype=SIFT_POINT_DTYPE)
+        recs["coords2D"] = kp[:, :2]
+        recs["scale"] = kp[:, 2]
+        if kp.shape[1] == 4:
+            recs["orientation"] = kp[:, 3]
+        if n == 0:
+            return recs
+        h, w = img.shape
+        prm = default_params(**dict(params, max_pts=n))
+        d_img, d_pts = DeviceBuffer.from_numpy(self, img), DeviceBuffer.from_numpy(self, recs)
+        try:
+            self.describe_batch(d_img.ptr, 1, w, h, w, h * w, prm, d_pts.ptr, None,
+                                DESCRIBE_KEEP_ORIENTATION if keep_orientation else 0)
+            self.synchronize()
+            return d_pts.to_numpy(SIFT_POINT_DTYPE, (n,))
+        finally:
+            d_img.free()
+            d_pts.free()
 
     def record_graph(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters):
         """cusift_graph_create: extract_batch for fixed buffers, recorded once as a hipGraph (see ExtractGraph)."""

@@ -9,6 +9,7 @@
 //   sift_match8.hip   8-bit descriptors: the quantiser, the int8-MFMA matcher, their entry points (a unit of its own)
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
+//   sift_describe.hip cusift_describe_batch: the pyramid and describe_given_kernel for caller-supplied keypoints
 // The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,
 // reductions, ordered compaction, pair strides).
 #pragma once
@@ -58,6 +59,8 @@ __global__ void describe_all_kernel(OctaveTable, cusift_point *, int, unsigned i
 __global__ void join_counts_kernel(unsigned int *, SegmentTable, unsigned int *, int, int, unsigned int *, int);
 __global__ void describe_bands_kernel(OctaveTable, BandWindows, cusift_point *, int, SegmentTable, const unsigned int *,
                                       float, float, int, unsigned int *);
+__global__ void describe_given_kernel(OctaveTable, cusift_point *, int, const unsigned int *, int, float, float, int,
+                                      unsigned int);
 __global__ void rootsift_kernel(cusift_point *, int);
 template <bool kL2>
 __global__ void match_kernel(cusift_point *, int, const cusift_point *, int, int, MatchPartial *, int);

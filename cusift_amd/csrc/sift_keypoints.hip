@@ -1374,6 +1374,131 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 }
 
 // ------------------------------------------------------------------------------------------------
+// Orientation + descriptor of keypoints the CALLER supplies (cusift_describe_batch, sift_describe.hip): records in
+// input-image pixels, in the caller's order, described in place.  Its own front -- validity test, octave rule, octave
+// units: include/cusift_amd_extras.h pins all three expression by expression -- then the device functions of the kernels above
+// on the extraction's pyramid, so a record that came from an extraction gets its bits back.  A plain walk like
+// describe_bands_kernel's: none of describe_all_kernel's queue and prefetch.
+//   walk    gridDim.y == 1: the flattened (image, record) pairs, grid-stride, over a prefix table of the clamped
+//           counts (n_images <= kMaxFlatImages) -- images with few records leave nobody idle; otherwise blockIdx.y is
+//           the image.  counters == NULL: every image has max_pts records.
+//   writes  data, subsampling and -- unless the orientation is kept -- orientation; nothing else of a record, and
+//           nothing beyond an image's count.
+// ------------------------------------------------------------------------------------------------
+constexpr float kDescribeLow = 0.93303299f;  // 2^-0.1: the lowest scale / subsampling the detector's refinement assigns
+__device__ __forceinline__ bool finite_bits(float v) { return (sm_bits(v) & 0x7f800000u) != 0x7f800000u; }
+
+// one valid keypoint through one sampler: `ori` is the kept orientation, or replaced by the orientation stage's
+template <typename TEX>
+__device__ __forceinline__ void describe_given_one(KpShared &S, const TEX &tex, const DescLaneConsts &C, float px,
+                                                   float py, float kscale, bool keep, float &ori, int lane, float &b0,
+                                                   float &b1) {
+  if (!keep) ori = kp_orientation(S, tex, px, py, kscale, lane);  // wave-uniform
+  kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
+}
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) describe_given_kernel(
+    OctaveTable T, cusift_point *__restrict__ points, int max_pts, const unsigned int *__restrict__ counters,
+    int n_images, float q, float inv_q, int root_sift, unsigned int flags) {
+  __shared__ KpShared S;
+  __shared__ unsigned int s_prefix[kMaxFlatImages + 1];
+  const int lane = threadIdx.x;
+  const bool flat = gridDim.y == 1;  // wave-uniform; the host flattens up to kMaxFlatImages images
+  const bool keep = (flags & CUSIFT_DESCRIBE_KEEP_ORIENTATION) != 0u;
+  const bool from_scale = (flags & CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE) != 0u;
+  auto count_of = [&](int i) {
+    const unsigned int c = counters ? counters[i] : (unsigned int)max_pts;
+    return c < (unsigned int)max_pts ? c : (unsigned int)max_pts;
+  };
+  unsigned int total;
+  int im;
+  if (flat) {
+    for (int i = lane; i < n_images; i += 64) s_prefix[i + 1] = count_of(i);
+    wave_sync();
+    running_sums_in_place(s_prefix, n_images, lane);
+    wave_sync();
+    total = s_prefix[n_images];
+    im = 0;
+  } else {
+    im = blockIdx.y;
+    total = count_of(im);
+  }
+  total = (unsigned int)__builtin_amdgcn_readfirstlane((int)total);
+  const DescLaneConsts C = desc_lane_consts(lane, q, inv_q);
+
+  for (unsigned int g = blockIdx.x; g < total; g += gridDim.x) {  // wave-uniform
+    unsigned int idx = g;
+    if (flat) {
+      while (__builtin_amdgcn_readfirstlane((int)s_prefix[im + 1]) <= g) ++im;  // ends: g < total = s_prefix[n_images]
+      idx = g - (unsigned int)__builtin_amdgcn_readfirstlane((int)s_prefix[im]);
+    }
+    cusift_point *pt = points + (long)im * max_pts + idx;
+    const float x = uniform(pt->coords2D[0]), y = uniform(pt->coords2D[1]), scale = uniform(pt->scale);
+    const float rec_sub = uniform(pt->subsampling);
+    float ori = keep ? uniform(pt->orientation) : 0.0f;
+    // validity: both coordinates and the scale finite, the scale positive
+    if (!(finite_bits(x) && finite_bits(y) && finite_bits(scale) && scale > 0.0f)) {
+      pt->data[lane] = 0.0f;
+      pt->data[lane + 64] = 0.0f;
+      if (lane == 0) pt->subsampling = 0.0f;
+      continue;
+    }
+    // octave: the recorded one -- the record's subsampling has exactly the bits of some sub[o] (the first such o) --
+    // or, from the scale, the largest o with scale >= kLow * sub[o], 0 if there is none
+    int o = -1;
+    if (!from_scale) {
+      for (int i = T.n_oct - 1; i >= 0; --i)
+        if (sm_bits(rec_sub) == sm_bits(T.sub[i])) o = i;
+    }
+    if (o < 0) {
+      o = 0;
+      for (int i = 1; i < T.n_oct; ++i)
+        if (scale >= kDescribeLow * T.sub[i]) o = i;
+    }
+    const float sub = T.sub[o];
+    const float px = x / sub, py = y / sub, kscale = scale / sub;  // octave units
+    const float *img = T.base[o] + (long)im * T.stride[o];
+    const int w = T.w[o], h = T.h[o], pitch = T.pitch[o];
+    const RowWindow rw{0, h};
+    // one patch for both stages, as describe_all_kernel's.  A kept orientation whose sine and cosine may not be finite
+    // (sm_sincosf answers NaN from |x| = 1e9) takes the global sampler, whose clamps hold for any tap position.
+    const float reach = fmaxf(7.5f * (12.0f / 16.0f * kscale) * 1.41422f + 1.0f + 0.01f, 6.0f);
+    PatchGeom pg;
+    int pw, ph;
+    const bool use_patch = patch_for_reach(px, py, reach, pg, pw, ph) && fabsf(ori) < 1e9f;
+    if (use_patch) stage_patch(img, w, h, pitch, rw, S.patch, pg, pw, ph, lane);
+    wave_sync();
+    float b0, b1;
+    if (use_patch) {
+      if (q > 0.0f)
+        describe_given_one(S, PatchSampler<kDescPatch, true>{S.patch, pg.x0, pg.y0, q, inv_q}, C, px, py, kscale, keep, ori,
+                           lane, b0, b1);
+      else
+        describe_given_one(S, PatchSampler<kDescPatch, false>{S.patch, pg.x0, pg.y0, q, inv_q}, C, px, py, kscale, keep, ori,
+                           lane, b0, b1);
+    } else {
+      describe_given_one(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, C, px, py, kscale, keep, ori, lane, b0, b1);
+    }
+    // finish_descriptor's RootSIFT step and descriptor stores; of the head only orientation and subsampling
+    const int e0 = desc_elem(lane);
+    if (root_sift) {
+      float *v = S.fin();
+      v[e0] = b0;
+      v[e0 + 4] = b1;
+      wave_sync();
+      rootsift_lanes(v, e0, e0 + 4, b0, b1);
+    }
+    pt->data[e0] = b0;
+    pt->data[e0 + 4] = b1;
+    if (lane == 0) {
+      if (!keep) pt->orientation = ori;
+      pt->subsampling = sub;
+    }
+    wave_sync();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // ConvertSiftToRootSift: reference cuSIFT_D.cu:299-317 (sequential L1 sum, sqrt(max(0,v)/sum)).
 // One wave per point; the 128-term sum is kept sequential to match the reference order (rootsift_lanes).
 // ------------------------------------------------------------------------------------------------

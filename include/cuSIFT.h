@@ -3,7 +3,8 @@
 // A program written against the reference's cuSIFT.h / cuImage.h / cutils.h (the live `SiftData` class API of
 // test/detector.cpp:41-49, or the legacy InitSiftData / ExtractSift / FreeSiftData trio of main.cpp:99-103,
 // 324-349) compiles against this one header and links libcusift_amd.so.  Everything here is a thin
-// inline shim over the C ABI in cusift_amd.h: no HIP headers, no CUDA types.
+// inline shim over the C ABI in cusift_amd.h (SiftData::Describe: cusift_describe_batch of cusift_amd_extras.h): no HIP
+// headers, no CUDA types.
 //
 // Differences from the reference, on purpose:
 //   * the methods that took a cudaTextureObject_t (cuSIFT.h:68-71) are internal helpers of the reference
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "cusift_amd.h"
+#include "cusift_amd_extras.h"  // cusift_describe_batch (SiftData::Describe)
 
 // ---- cutils.h:15-18 -------------------------------------------------------------------------------
 inline int iDivUp(int a, int b) { return (a % b != 0) ? (a / b + 1) : (a / b); }
@@ -412,6 +414,26 @@ class SiftData {
     report(CUSIFT_REPORT_READ(timer));
   }
 
+  // New (not in the reference, which describes only what it detects): orientation + descriptor of the numPts records
+  // in d_data as they stand -- an earlier Extract's, or keypoints put there by AddSiftData (debug.h): coords2D and scale
+  // in image pixels -- in place and in their order, over cusift_describe_batch with this object's numOctaves, scaleUp
+  // and rootSift.  flags: CUSIFT_DESCRIBE_KEEP_ORIENTATION (the records' orientations are used as they are, 0 = upright),
+  // CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE (ignore the records' subsampling).  Blocking; refreshes h_data when there is one.
+  void Describe(cuImage &img, unsigned flags = 0, float subsampling = 1.0f) {
+    require_device("DescribeSift");
+    if (img.d_data == nullptr) {
+      std::printf("DescribeSift: missing data\n");
+      return;
+    }
+    if (numPts <= 0) return;
+    cusift_params p = params(subsampling);
+    p.max_pts = numPts;  // one image, every record of it
+    safeCall(cusift_describe_batch(cusift_dropin::ctx(), img.d_data, 1, img.width, img.height, img.pitch,
+                                   (size_t)img.pitch * img.height, &p, as_c(d_data), nullptr, flags));
+    safeCall(cusift_ctx_synchronize(cusift_dropin::ctx()));
+    Synchronize();
+  }
+
   // cuSIFT.cu:383-395 (always returns 0.0 like every launch wrapper of the reference)
   double ConvertSiftToRootSift() {
     if (d_data && numPts > 0) {
@@ -509,6 +531,11 @@ inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double
 inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double initBlur, float thresh,
                         float lowestScale = 0.0f, float subsampling = 1.0f, bool scaleUp = false) {
   ExtractSift(siftData, img, numOctaves, initBlur, thresh, lowestScale, subsampling, scaleUp, 0);
+}
+// New: SiftData::Describe in the legacy style -- descriptors for the records siftData already holds on the device.
+inline void DescribeSift(SiftData &siftData, cuImage &img, int numOctaves, float subsampling = 1.0f, unsigned flags = 0) {
+  siftData.numOctaves = numOctaves;
+  siftData.Describe(img, flags, subsampling);
 }
 // The reference's ExtractRootSift is commented out ("TODO: bring rootsift back", cuSIFT.cu:122-134: ExtractSift,
 // then ConvertSiftToRootSift, then Synchronize; its argument list lost thresh/lowestScale).  Same result in one

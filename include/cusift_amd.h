@@ -8,7 +8,7 @@
  * (SiftPoint / SiftData / cuImage / ExtractSift ...) on top of exactly these functions; Python binds
  * them with ctypes (cusift_amd/capi.py).  See INTEGRATION.md.
  *
- * Map of the C ABI (114 entry points in four headers; cusift_amd_all.h includes them all):
+ * Map of the C ABI (115 entry points in four headers; cusift_amd_all.h includes them all):
  *   cusift_amd.h (THIS FILE, 48): the drop-in boundary -- everything include/cuSIFT.h is built on (process / device,
  *     context, device memory helpers, cusift_extract / _extract_host / _scale_down / _scale_up / _rootsift / _sort_points_host,
  *     cusift_event_* for TimerGPU), the batch driver a throughput caller needs (cusift_extract_batch, cusift_graph_*,
@@ -20,7 +20,8 @@
  *   cusift_amd_multigpu.h: SiftData on the wire (pack / trimmed / compact records), the communicator over RCCL, the
  *     all-gatherv of SiftData, halo exchange, the strip tiling of one large image over the ranks and its band kernels.
  *   cusift_amd_extras.h: the next rows of SURVEY 8f -- cusift_match, cusift_find_homography,
- *                        cusift_estimate_homography, cusift_register_planar, cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd, cusift_select_strongest.
+ *                        cusift_estimate_homography, cusift_register_planar, cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd, cusift_select_strongest,
+ *                        and cusift_describe_batch (orientation + descriptor at the caller's keypoints).
  *
  * Conventions
  *  - every function returns CUSIFT_OK (0) or a negative cusift_status; cusift_last_error() gives text.

@@ -818,6 +818,38 @@ int cusift_register_pnp_batch(cusift_ctx *ctx, const cusift_point *d_points,
                               char *h_inliers /* [n_pairs][max_pts], may be NULL */,
                               float *h_match_error /* [n_pairs][max_pts], may be NULL */);
 
+/* ---- descriptors at caller-supplied keypoints -------------------------------------------- */
+/* Orientation + descriptor of keypoints the CALLER supplies -- a tracker's predictions, reprojected map points, a dense
+ * grid, another detector's output, an earlier extraction's records -- in place, in the caller's order (OpenCV's
+ * compute() / useProvidedKeypoints, VLFeat's 'frames').  New: the reference describes only what it detects.
+ * Asynchronous on the context's stream: no host read-back, no allocation once the arena is sized.
+ * d_points: n_images * p->max_pts records; image i has min(d_counters[i], max_pts) of them, max_pts with d_counters ==
+ * NULL; nothing beyond that count is touched.  coords2D and scale are in input-image pixels, as extraction writes them.
+ * Of `p` only num_octaves, subsampling, max_pts, tex_frac_bits, root_sift and upsample are read; keep_strongest,
+ * cross-check and match-bits do not affect the call.
+ *   pyramid   octave images o = 0 .. num_octaves - 1 in the context's arena, the extraction's bit for bit: sub[0] =
+ *             p->subsampling (0.5f * p->subsampling with upsample = 1, octave 0 then being the cusift_scale_up
+ *             enlargement), sub[o] = sub[o - 1] * 2.0f, image o + 1 = cusift_scale_down(variance 0.5) of image o.
+ *   skipped   a record with a coordinate or the scale not finite, or !(scale > 0): no image is read, data becomes 128
+ *             zeros, subsampling 0, orientation stays.  Everything finite is legal -- positions outside the image, any
+ *             scale: the samplers clamp, as for the stage calls.
+ *   octave    recorded: CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE is not set and the record's subsampling has exactly the bits
+ *             of some sub[o] -- that o (the first such).  Otherwise (subsampling 0, NaN, anything else) from the scale,
+ *             in fp32: the largest o with   scale >= 0.93303299f * sub[o]   (one product, one comparison), 0 if there
+ *             is none.  0.93303299f = 2^-0.1 is the lowest scale / subsampling the detector's refinement assigns, so an
+ *             octave's range [0.93303299f sub[o], 0.93303299f sub[o + 1]) is the one the detector emits.
+ *   units     px = x / sub[o], py = y / sub[o], kscale = scale / sub[o], three fp32 divisions (exact for a power of two).
+ *   written   orientation (degrees) -- unless CUSIFT_DESCRIBE_KEEP_ORIENTATION, which uses the record's value as it is
+ *             (0 = upright SIFT); data[128] (RootSIFT with p->root_sift); subsampling = sub[o].  Every other byte of the
+ *             record, coords2D and scale included, keeps the caller's bits.
+ * The same device functions as the extraction on the same images: records of cusift_extract_batch come back byte for
+ * byte.  CUSIFT_ERR_INVALID, nothing enqueued: the geometry cusift_extract_batch refuses, unknown flag bits, NULL
+ * images or points with something to do.  n_images == 0 or max_pts == 0: CUSIFT_OK, nothing done. */
+enum { CUSIFT_DESCRIBE_KEEP_ORIENTATION = 1, CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE = 2 };
+int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n_images, int w, int h, int pitch,
+                          size_t image_stride, const cusift_params *p, cusift_point *d_points,
+                          const unsigned int *d_counters /* or NULL */, unsigned int flags);
+
 #ifdef __cplusplus
 }
 #endif
