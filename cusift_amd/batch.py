@@ -9,6 +9,27 @@ import torch
 from . import capi
 
 
+class Tracks:
+    """What BatchExtractor.build_tracks leaves on the device (cusift_build_tracks): track int32 [n, max_pts] (the track of
+    every record, -1: none), offsets int32 [N // 2 + 1] and obs int32 [N] (the nodes frame * max_pts + record of track t
+    at obs[offsets[t] : offsets[t + 1]], ascending), stats int32 [8] (tracks, observations, accepted rows, components
+    dropped for a shared frame, dropped for min_views only), and what they were built from: the pair list, the matcher's
+    rows / rows_back int32 [P, max_pts, 4] (MatchRow) and keep uint8 [P, max_pts] or None."""
+
+    def __init__(self, n_images, max_pts, pairs, track, offsets, obs, stats, rows, rows_back, keep):
+        self.n_images, self.max_pts, self.pairs = n_images, max_pts, pairs
+        self.track, self.offsets, self.obs, self.stats = track, offsets, obs, stats
+        self.rows, self.rows_back, self.keep = rows, rows_back, keep
+
+    def to_host(self):
+        """Blocking: (T, [[(frame, record), ...] per track])."""
+        n_tracks = int(self.stats[0].item())
+        offsets = self.offsets[: n_tracks + 1].cpu().numpy()
+        obs = self.obs[: int(offsets[-1])].cpu().numpy()
+        return n_tracks, [[(int(v) // self.max_pts, int(v) % self.max_pts) for v in obs[offsets[t]:offsets[t + 1]]]
+                          for t in range(n_tracks)]
+
+
 class BatchExtractor:
     """Extracts SiftData for a batch of equally sized, HBM-resident float32 images.
 
@@ -303,6 +324,69 @@ class BatchExtractor:
                                 d_counters=counts.data_ptr(), image_stride=image_stride)
         return self.ctx.register_pnp_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
                                            self._pairs(pairs), camera2, **opts)
+
+    def build_tracks(self, pairs=None, slot=0, mutual=True, inliers=None, rule=1, lo=None, hi=None, min_views=2,
+                     distance=1, match_bits=None):
+        """Feature tracks of the frames of the last extract() into `slot`: the pair-list matcher (match_batch_mutual, or
+        match_batch with mutual=False; the 8-bit matchers on quantize(slot)'s tables when match_bits, by default this
+        extractor's, is 8) and cusift_build_tracks behind it on the same stream.  pairs: (frame a, frame b) rows; None:
+        (i, i + 1) for every consecutive frame.  inliers: [P, max_pts] flags, or one array per pair as a
+        PlanarBatchResult's `inliers` -- only rows flagged there can be edges.  rule / lo / hi: the match filter of the
+        registrations (capi.Context.build_tracks).  Returns a Tracks of device tensors; nothing is read back."""
+        pairs = capi.pair_list(self._pairs(pairs))
+        bits = self.match_bits if match_bits is None else capi.check_match_bits(match_bits)
+        points, counts = self.slots[slot]
+        n_pairs, n_nodes = len(pairs), self.n * self.max_pts
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            rows = torch.zeros((n_pairs, self.max_pts, 4), dtype=torch.int32, device=self.device)
+            rows_back = torch.zeros_like(rows) if mutual else None
+            keep = None
+            if inliers is not None:
+                flags = np.zeros((n_pairs, self.max_pts), dtype=np.uint8)
+                for p, row in enumerate(inliers):
+                    row = np.asarray(row).reshape(-1)
+                    flags[p, : len(row)] = row != 0
+                keep = torch.from_numpy(flags).to(self.device)
+            track = torch.empty((self.n, self.max_pts), dtype=torch.int32, device=self.device)
+            offsets = torch.zeros((n_nodes // 2 + 1,), dtype=torch.int32, device=self.device)
+            obs = torch.zeros((max(n_nodes, 1),), dtype=torch.int32, device=self.device)
+            stats = torch.zeros((8,), dtype=torch.int32, device=self.device)
+            back = rows_back.data_ptr() if mutual else None
+            if bits == 8:
+                q, sums = self.quantize(slot)
+                if mutual:
+                    self.ctx.match8_batch_mutual(q.data_ptr(), sums.data_ptr(), counts.data_ptr(), self.n, self.max_pts,
+                                                 pairs, rows.data_ptr(), back, distance)
+                else:
+                    self.ctx.match8_batch(q.data_ptr(), sums.data_ptr(), counts.data_ptr(), self.n, self.max_pts, pairs,
+                                          rows.data_ptr(), distance)
+            elif mutual:
+                self.ctx.match_batch_mutual(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts, pairs,
+                                            rows.data_ptr(), back, distance)
+            else:
+                self.ctx.match_batch(points.data_ptr(), counts.data_ptr(), self.n, self.max_pts, pairs, rows.data_ptr(),
+                                     distance)
+            self.ctx.build_tracks(counts.data_ptr(), self.n, self.max_pts, pairs, rows.data_ptr(), track.data_ptr(),
+                                  offsets.data_ptr(), obs.data_ptr(), stats.data_ptr(), d_rows_back=back,
+                                  d_keep=keep.data_ptr() if keep is not None else None, rule=rule, lo=lo, hi=hi,
+                                  min_views=min_views)
+        return Tracks(self.n, self.max_pts, pairs, track, offsets, obs, stats, rows, rows_back, keep)
+
+    def triangulate_tracks(self, tracks, poses, camera, min_pivot=1e-12, slot=0):
+        """The 3-D point of every track of build_tracks() from all its views: cusift_triangulate_tracks over the records
+        of `slot`.  poses: capi.chain_poses' [n, 4, 4] or [n, 3, 4], camera to world; camera: one capi.Camera for all
+        frames.  Returns device tensors points3d float64 [cap, 4] = (X, Y, Z, largest reprojection error in pixels) and
+        front int32 [cap] with cap = n * max_pts // 2; rows at and past the track count stay zero, and so does a
+        degenerate track (min_pivot: capi.Context.triangulate_tracks).  Nothing is read back."""
+        points, _ = self.slots[slot]
+        cap = tracks.offsets.numel() - 1
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            points3d = torch.zeros((cap, 4), dtype=torch.float64, device=self.device)
+            front = torch.zeros((cap,), dtype=torch.int32, device=self.device)
+            self.ctx.triangulate_tracks(points.data_ptr(), self.n, self.max_pts, tracks.offsets.data_ptr(),
+                                        tracks.obs.data_ptr(), tracks.stats.data_ptr(), cap, poses, camera,
+                                        points3d.data_ptr(), front.data_ptr(), min_pivot=min_pivot)
+        return points3d, front
 
     def valid_counts(self):
         return torch.clamp(self.counts, max=self.max_pts)

@@ -264,6 +264,9 @@ SIGNATURES = {
     "cusift_sort_points_host": (_i, [_vp, _i]),
     "cusift_extract_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp]),
     "cusift_describe_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp, C.c_uint]),
+    "cusift_build_tracks": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "cusift_triangulate_tracks": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(Camera), C.c_double, _vp,
+                                       _vp]),
     "cusift_graph_create": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp]),
     "cusift_graph_launch": (_i, [_vp]),
     "cusift_graph_nodes": (_i, [_vp]),
@@ -534,6 +537,17 @@ def chain_poses(rts, pairs=None):
         step[:3, :] = rt
         poses[i + 1] = poses[i] @ step
     return poses
+
+
+def track_poses(poses, n_images):
+    """Per-frame poses as cusift_triangulate_tracks takes them: contiguous float64 [n_images, 12], the row-major
+    [R | t] of every frame -- from chain_poses' [n, 4, 4] (its top three rows) or from [n, 3, 4]."""
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.ndim == 3 and poses.shape[1:] == (4, 4):
+        poses = poses[:, :3, :]
+    if poses.size != 12 * n_images:
+        raise ValueError("triangulate_tracks: %d pose entries for %d frames" % (poses.size, n_images))
+    return np.ascontiguousarray(poses).reshape(n_images, 12)
 
 
 def chain_homographies(h, pairs=None):
@@ -1263,6 +1277,33 @@ class Context:
         DESCRIBE_OCTAVE_FROM_SCALE."""
         check(lib().cusift_describe_batch(self.handle, d_imgs, n_images, w, h, pitch, image_stride, C.byref(params),
                                           d_points, d_counters, int(flags)))
+
+    # ---- feature tracks of a sequence ----
+    def build_tracks(self, d_counters, n_images, max_pts, pairs, d_rows, d_track, d_offsets, d_obs, d_stats,
+                     d_rows_back=None, d_keep=None, rule=1, lo=None, hi=None, min_views=2):
+        """cusift_build_tracks: the connected components of the match graph that `pairs` (int32 [P, 2]) and d_rows[P]
+        [max_pts] of MatchRow span over the records of a batch, as tracks.  A row is an edge when it passes `rule`
+        (0: score > lo && ambiguity < hi; 1: score < lo^2 && ambiguity < hi^2), d_keep (uint8 [P][max_pts], None: all) and
+        the cross-check against d_rows_back (None: off); a component is a track when it has min_views nodes and no two
+        in one frame.  Device outputs: d_track int32 [n_images][max_pts], d_offsets int32 [N // 2 + 1], d_obs int32 [N],
+        d_stats uint32 [8] with N = n_images * max_pts.  lo / hi default as in register_planar.  Asynchronous, nothing is
+        read back."""
+        pairs = pair_list(pairs)
+        rule, lo, hi = _rule_defaults(1, rule, lo, hi)
+        check(lib().cusift_build_tracks(self.handle, d_counters, n_images, max_pts, pairs.ctypes.data, len(pairs), d_rows,
+                                        d_rows_back, d_keep, rule, lo, hi, min_views, d_track, d_offsets, d_obs, d_stats))
+
+    def triangulate_tracks(self, d_points, n_images, max_pts, d_offsets, d_obs, d_stats, max_tracks, poses, camera,
+                           d_points3d, d_front, min_pivot=1e-12):
+        """cusift_triangulate_tracks: the point nearest to all pixel rays of every track (fp64), d_points3d float64
+        [max_tracks][4] = (X, Y, Z, largest reprojection error in pixels) and d_front int32 [max_tracks] = members in
+        front of their camera; four zeros and 0 for a degenerate track (a pivot not > min_pivot: pass 1 - cos(angle) for a
+        two-view parallax limit).  poses: [n_images, 4, 4] (chain_poses) or [n_images, 3, 4], camera to world; camera: one
+        Camera for all frames.  Asynchronous; poses is read before the call returns."""
+        poses = track_poses(poses, n_images)
+        check(lib().cusift_triangulate_tracks(self.handle, d_points, n_images, max_pts, d_offsets, d_obs, d_stats,
+                                              max_tracks, poses.ctypes.data, C.byref(camera), min_pivot, d_points3d,
+                                              d_front))
 
     def describe(self, image, keypoints, keep_orientation=None, **params):
         """SIFT descriptors at the caller's keypoints (blocking, host arrays): `image` float [h, w], `keypoints` [n, 3]

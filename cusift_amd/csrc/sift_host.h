@@ -10,6 +10,7 @@
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 //   sift_describe.hip cusift_describe_batch: the pyramid and describe_given_kernel for caller-supplied keypoints
+//   sift_tracks.hip   cusift_build_tracks, cusift_triangulate_tracks: their kernels and entry points (a unit of its own)
 // The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,
 // reductions, ordered compaction, pair strides).
 #pragma once
@@ -240,6 +241,9 @@ struct cusift_ctx {
   // the byte tables and sums the registrations quantise into while cusift_ctx_set_match_bits is 8 (sift_match8.hip)
   char *q8_scratch = nullptr;
   size_t q8_scratch_bytes = 0;
+  // cusift_build_tracks (pair list, union-find, hash sets, scans) and cusift_triangulate_tracks (the poses): sift_tracks.hip
+  char *tracks_scratch = nullptr;
+  size_t tracks_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;
@@ -386,6 +390,8 @@ static int grow_scratch(cusift_ctx *ctx, T *&ptr, size_t &have, size_t bytes, co
 int enter(cusift_ctx *ctx);
 int check_launch(const char *what);
 int ensure_arena(cusift_ctx *ctx, size_t bytes);
+// sift_register.hip: what every pair-list call refuses of its batch shape and its list (sift_tracks.hip shares it)
+int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int max_pts, const char *who);
 // sift_match8.hip, for the registrations' matcher fronts (sift_register.hip)
 int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
                         int distance, cusift_point *d_back);

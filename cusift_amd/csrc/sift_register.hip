@@ -955,7 +955,7 @@ extern "C" int cusift_register_pnp(cusift_ctx *ctx, cusift_point *d_sift1, int n
 // ------------------------------------------------------------------------------------------------
 // the same over a batch of frames and a pair list (sift_sequence.hip)
 // ------------------------------------------------------------------------------------------------
-static int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int max_pts, const char *who) {
+int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int max_pts, const char *who) {
   if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_pairs %d outside [0, 65535]", who, n_pairs);
   if (n_images < 0 || n_images > 65535)
     return fail(CUSIFT_ERR_INVALID, "%s: n_images %d outside [0, 65535]", who, n_images);

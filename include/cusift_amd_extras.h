@@ -850,6 +850,85 @@ int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n_images, in
                           size_t image_stride, const cusift_params *p, cusift_point *d_points,
                           const unsigned int *d_counters /* or NULL */, unsigned int flags);
 
+/* ---- feature tracks of a sequence: match-graph components and their triangulation (sift_tracks.hip) --------------- */
+/* From the rows of a pair-list matcher to TRACKS, the observations (frame, record) of one scene point across the
+ * sequence: what OpenMVG's TracksBuilder, COLMAP's correspondence graph and every bundle adjuster take as input.  New:
+ * the reference returns matches per pair.  Everything stays on the device.
+ * NODES: v = f * max_pts + i is live when i < count_f = min(d_counters[f], max_pts) (d_counters == NULL: max_pts each);
+ * N = n_images * max_pts <= 2^31 - 1.
+ * EDGES: for pair p = (a, b) of h_pairs and a live record i of frame a, with row = d_rows[p * max_pts + i] and m =
+ * row.match, the edge (a, i) -- (b, m) exists iff ALL of
+ *     a != b;   0 <= m < count_b;
+ *     the row passes `rule`, the CANDIDATES predicates of cusift_estimate_homography:  0: score > lo && ambiguity < hi;
+ *       1: score < lo^2 && ambiguity < hi^2 (the squares in fp32).  A NaN fails; rule 0 with lo = -inf and hi = +inf
+ *       switches the test off;
+ *     d_keep == NULL or d_keep[p * max_pts + i] != 0   (where the h_inliers of a cusift_register_*_batch call go back in);
+ *     d_rows_back == NULL or d_rows_back[p * max_pts + m].match == i   (the cross-check of cusift_select_mutual).
+ * Rows past count_a are never read, and a pair with count_a == 0 or count_b == 0 contributes nothing whatever bytes its
+ * rows hold (the matchers leave them unwritten).  A frame may be in any number of pairs, on either side; repeated pairs,
+ * and both (a, b) and (b, a), are legal.  Rows of cusift_match8_batch* are the same struct.
+ * TRACKS: a connected component of the live nodes under the edges is a track iff it has at least min_views (>= 2) nodes
+ * AND no two of its nodes lie in one frame.  A component with two records of one frame is dropped whole (OpenMVG's rule:
+ * one wrong match must not glue two scene points together).  Tracks are numbered 0 .. T-1 in ascending order of their
+ * smallest node.
+ * OUTPUTS, device memory:
+ *     d_track[v]      track of node v or -1; all N entries are written, dead slots included
+ *     d_offsets[0..T] and d_obs[0 .. d_offsets[T]): the nodes of track t in ascending node order -- one per frame, frames
+ *                     ascending -- at d_obs[d_offsets[t] .. d_offsets[t + 1]).  The caller provides N / 2 + 1 entries of
+ *                     d_offsets and N of d_obs; entries past the ones named are not written
+ *     d_stats[8]      [0] T; [1] observations = d_offsets[T]; [2] accepted (p, i) rows, duplicates counted each time;
+ *                     [3] components dropped for a shared frame; [4] components of >= 2 nodes dropped only for
+ *                     min_views; [5..7] 0
+ * Asynchronous on the context's stream: no synchronisation, no read-back, and a number of launches that depends on
+ * neither the data nor n_pairs (a lock-free union-find, ordered scans; sift_tracks.hip).  Scratch lives in the context
+ * and grows on demand.  h_pairs is read before the call returns.  The same input gives the same bytes in every output.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): what cusift_match_batch refuses of n_images, max_pts, h_pairs
+ * and n_pairs; N > 2^31 - 1; a NULL d_rows with n_pairs > 0; a NULL output; an unknown rule; a NaN lo or hi; min_views <
+ * 2; d_rows_back == d_rows.  n_pairs == 0 or max_pts == 0: CUSIFT_OK, every d_track entry -1, d_offsets[0] = 0, d_stats
+ * zeros. */
+int cusift_build_tracks(cusift_ctx *ctx, const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                        const int *h_pairs /* [n_pairs][2] */, int n_pairs,
+                        const cusift_match_row *d_rows /* [n_pairs][max_pts] */,
+                        const cusift_match_row *d_rows_back /* [n_pairs][max_pts] or NULL */,
+                        const unsigned char *d_keep /* [n_pairs][max_pts] or NULL */,
+                        int rule, float lo, float hi, int min_views,
+                        int *d_track /* [n_images][max_pts] */, int *d_offsets, int *d_obs,
+                        unsigned int *d_stats /* [8] */);
+
+/* The 3-D point of every track from ALL its views: the midpoint triangulation, the point nearest to all pixel rays, from a
+ * 3 x 3 positive definite system.  h_poses[f] is the row-major [R | t] of frame f, camera to world, X_world = R X_f + t:
+ * the top three rows of chain_poses' matrices -- with metric poses the points share one scale, which the per-pair points
+ * of cusift_register_pose* (|t| = 1 per pair) do not.  One cusift_camera serves all frames; only fx, fy, cx, cy and
+ * origin are used, px = cx - origin, py = cy - origin, the floats widened first.  The track count is read on the device
+ * from d_stats[0] and clamped to max_tracks; the grid is sized from max_tracks.  ALL FP64, every expression evaluated in
+ * the order written (the build uses -ffp-contract=off), the members of a track in d_obs order, the sums from 0:
+ *     x, y = coords2D of the record, widened;   d = ((x - px) / fx, (y - py) / fy, 1)
+ *     w[i] = (R[i][0]*d0 + R[i][1]*d1) + R[i][2];          n = (w0*w0 + w1*w1) + w2*w2
+ *     M[i][j] = (i == j ? 1 : 0) - (w[i]*w[j]) / n
+ *     A[i][j] += M[i][j];      g[i] += (M[i][0]*t0 + M[i][1]*t1) + M[i][2]*t2
+ *     q00 = A00;  l00 = sqrt(q00);  l10 = A10 / l00;  l20 = A20 / l00
+ *     q11 = A11 - l10*l10;  l11 = sqrt(q11);  l21 = (A21 - l20*l10) / l11
+ *     q22 = A22 - (l20*l20 + l21*l21);  l22 = sqrt(q22)
+ *     y0 = g0 / l00;  y1 = (g1 - l10*y0) / l11;  y2 = (g2 - (l20*y0 + l21*y1)) / l22
+ *     X2 = y2 / l22;  X1 = (y1 - l21*X2) / l11;  X0 = (y0 - (l10*X1 + l20*X2)) / l00
+ *     per member:  e = X - t;  c[j] = (R[0][j]*e0 + R[1][j]*e1) + R[2][j]*e2;  in front iff c2 > 0
+ *                  u = fx*(c0/c2) + px;  v = fy*(c1/c2) + py;  err2 = (u - x)*(u - x) + (v - y)*(v - y)
+ *                  worst = err2 > worst ? err2 : worst          (from 0; a NaN never enters)
+ * DEGENERATE: any of q00, q11, q22 not > min_pivot, or X not finite -- four zeros and d_front = 0.  Two identical rays
+ * give q22 = 1.1e-16, positive, so 0 lets them through; 1e-12 is about a thousand times the rounding noise of a ten-view
+ * sum (10 * 2^-53).  A caller who wants a parallax limit passes more: for two views, 1 - cos(angle between the rays).
+ * Every other track: d_points3d[t] = (X0, X1, X2, sqrt(worst)) -- the point in world coordinates and its largest
+ * reprojection error in pixels -- and d_front[t] = the number of members in front of their camera.  Rows at or past the
+ * track count are not written.  d_points is read, never written.  Asynchronous, no synchronisation; h_poses is read
+ * before the call returns, as h_models is.
+ * CUSIFT_ERR_INVALID (nothing enqueued): a NULL pointer; a pose entry that is not finite; fx or fy zero or not finite;
+ * cx, cy or origin not finite; min_pivot negative or NaN; max_tracks < 0; n_images outside [0, 65535], max_pts outside
+ * [0, 2^20], N > 2^31 - 1. */
+int cusift_triangulate_tracks(cusift_ctx *ctx, const cusift_point *d_points, int n_images, int max_pts,
+                              const int *d_offsets, const int *d_obs, const unsigned int *d_stats, int max_tracks,
+                              const double *h_poses /* [n_images][12] */, const cusift_camera *camera,
+                              double min_pivot, double *d_points3d /* [max_tracks][4] */, int *d_front /* [max_tracks] */);
+
 #ifdef __cplusplus
 }
 #endif
