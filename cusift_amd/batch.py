@@ -30,6 +30,24 @@ class Tracks:
                           for t in range(n_tracks)]
 
 
+class BundleResult:
+    """What BatchExtractor.bundle_adjust leaves on the device (cusift_bundle_adjust), all float64: poses [n, 12] (row-
+    major [R | t], camera to world), points3d [cap, 4] = (X, Y, Z, largest reprojection error in pixels; an unused
+    track keeps its input row), history [iterations, 4] = (cost, trial cost, lambda, 1 accepted / 0 rejected / 2 not
+    run), summary [8] = (entry cost, final cost, accepted steps, iterations run, used tracks, used observations, free
+    frames, final lambda)."""
+
+    def __init__(self, poses, points3d, history, summary):
+        self.poses, self.points3d, self.history, self.summary = poses, points3d, history, summary
+
+    def to_host(self):
+        """Blocking: (poses [n, 4, 4] as chain_poses returns them, points3d, history, summary) as numpy arrays."""
+        rt = self.poses.cpu().numpy().reshape(-1, 3, 4)
+        poses = np.tile(np.eye(4), (len(rt), 1, 1))
+        poses[:, :3, :] = rt
+        return poses, self.points3d.cpu().numpy(), self.history.cpu().numpy(), self.summary.cpu().numpy()
+
+
 class BatchExtractor:
     """Extracts SiftData for a batch of equally sized, HBM-resident float32 images.
 
@@ -387,6 +405,28 @@ class BatchExtractor:
                                         tracks.obs.data_ptr(), tracks.stats.data_ptr(), cap, poses, camera,
                                         points3d.data_ptr(), front.data_ptr(), min_pivot=min_pivot)
         return points3d, front
+
+    def bundle_adjust(self, tracks, poses, camera, points3d, fixed=None, slot=0, **params):
+        """Refines the poses and the points of triangulate_tracks() together: cusift_bundle_adjust over the records of
+        `slot`, Schur-complement Levenberg-Marquardt with every decision on the device.  poses: capi.chain_poses'
+        [n, 4, 4] or [n, 3, 4], camera to world; points3d: triangulate_tracks' tensor (read, not written: the result
+        has its own copy); fixed: flags of the frames that must not move (None: frame 0); params: the fields of
+        capi.BundleParams (iterations, lam, lambda_min, lambda_max, huber, max_error, min_decrease).  Returns a
+        BundleResult of device tensors; nothing is read back."""
+        points, _ = self.slots[slot]
+        cap = tracks.offsets.numel() - 1
+        par = capi.BundleParams(**params)
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            out = points3d.to(dtype=torch.float64, copy=True).contiguous()
+            if out.numel() != 4 * cap:
+                raise ValueError("bundle_adjust: points3d has %d entries, the tracks take [%d, 4]" % (out.numel(), cap))
+            d_poses = torch.zeros((self.n, 12), dtype=torch.float64, device=self.device)
+            history = torch.zeros((par.iterations, 4), dtype=torch.float64, device=self.device)
+            summary = torch.zeros((8,), dtype=torch.float64, device=self.device)
+            self.ctx.bundle_adjust(points.data_ptr(), self.n, self.max_pts, tracks.offsets.data_ptr(),
+                                   tracks.obs.data_ptr(), tracks.stats.data_ptr(), cap, poses, camera, out.data_ptr(),
+                                   d_poses.data_ptr(), history.data_ptr(), summary.data_ptr(), fixed=fixed, params=par)
+        return BundleResult(d_poses, out, history, summary)
 
     def valid_counts(self):
         return torch.clamp(self.counts, max=self.max_pts)

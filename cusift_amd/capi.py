@@ -99,6 +99,31 @@ class Camera(C.Structure):
         super().__init__(fx, fy, cx, cy, origin, units_per_metre, encoding)
 
 
+class BundleParams(C.Structure):
+    """cusift_bundle_params (include/cusift_amd_extras.h): the Levenberg-Marquardt settings of cusift_bundle_adjust.
+    Fields left out take cusift_bundle_default_params' values (iterations 10, lambda 1e-3, lambda_min 1e-9, lambda_max
+    1e6, huber 0 = squared error, max_error 0 = no entry gate, min_decrease 1e-12)."""
+
+    _fields_ = [
+        ("iterations", C.c_int),
+        ("lambda_", C.c_double),
+        ("lambda_min", C.c_double),
+        ("lambda_max", C.c_double),
+        ("huber", C.c_double),
+        ("max_error", C.c_double),
+        ("min_decrease", C.c_double),
+    ]
+
+    def __init__(self, **fields):
+        super().__init__()
+        lib().cusift_bundle_default_params(C.byref(self))
+        for k, v in fields.items():
+            k = "lambda_" if k in ("lambda", "lam") else k
+            if k not in [name for name, _ in self._fields_]:
+                raise TypeError("unknown bundle parameter %r" % k)
+            setattr(self, k, v)
+
+
 class CusiftError(RuntimeError):
     pass
 
@@ -267,6 +292,9 @@ SIGNATURES = {
     "cusift_build_tracks": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "cusift_triangulate_tracks": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(Camera), C.c_double, _vp,
                                        _vp]),
+    "cusift_bundle_default_params": (None, [C.POINTER(BundleParams)]),
+    "cusift_bundle_adjust": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, C.POINTER(Camera),
+                                  C.POINTER(BundleParams), _vp, _vp, _vp, _vp]),
     "cusift_graph_create": (_i, [_vp, C.POINTER(_vp), _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp]),
     "cusift_graph_launch": (_i, [_vp]),
     "cusift_graph_nodes": (_i, [_vp]),
@@ -1304,6 +1332,32 @@ class Context:
         check(lib().cusift_triangulate_tracks(self.handle, d_points, n_images, max_pts, d_offsets, d_obs, d_stats,
                                               max_tracks, poses.ctypes.data, C.byref(camera), min_pivot, d_points3d,
                                               d_front))
+
+    def bundle_adjust(self, d_points, n_images, max_pts, d_offsets, d_obs, d_stats, max_tracks, poses, camera,
+                      d_points3d, d_poses, d_history, d_summary, fixed=None, params=None, **fields):
+        """cusift_bundle_adjust: Schur-complement Levenberg-Marquardt over the poses and the track points (fp64, on the
+        device, decisions included).  poses: [n_images, 4, 4] (chain_poses) or [n_images, 3, 4], camera to world; fixed:
+        per-frame flags of the frames that must not move (None: frame 0); params: a BundleParams, or its fields as
+        keywords (iterations, lam, lambda_min, lambda_max, huber, max_error, min_decrease).  d_points3d float64
+        [max_tracks][4] is read (triangulate_tracks' rows) and written; d_poses float64 [n_images][12], d_history
+        float64 [iterations][4] = (cost, trial cost, lambda, 1 accepted / 0 rejected / 2 not run) and d_summary
+        float64 [8] = (entry cost, final cost, accepted, run, used tracks, used observations, free frames, lambda) are
+        written.  Asynchronous; poses and fixed are read before the call returns.  Returns the BundleParams used."""
+        poses = track_poses(poses, n_images)
+        if params is None:
+            params = BundleParams(**fields)
+        elif fields:
+            raise TypeError("bundle_adjust: params and keyword fields together")
+        h_fixed = None
+        if fixed is not None:
+            fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8).reshape(-1)
+            if fixed.size != n_images:
+                raise ValueError("bundle_adjust: %d fixed flags for %d frames" % (fixed.size, n_images))
+            h_fixed = fixed.ctypes.data
+        check(lib().cusift_bundle_adjust(self.handle, d_points, n_images, max_pts, d_offsets, d_obs, d_stats, max_tracks,
+                                         poses.ctypes.data, h_fixed, C.byref(camera), C.byref(params), d_points3d,
+                                         d_poses, d_history, d_summary))
+        return params
 
     def describe(self, image, keypoints, keep_orientation=None, **params):
         """SIFT descriptors at the caller's keypoints (blocking, host arrays): `image` float [h, w], `keypoints` [n, 3]

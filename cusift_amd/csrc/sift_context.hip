@@ -285,6 +285,7 @@ extern "C" int cusift_ctx_destroy(cusift_ctx *ctx) {
   if (ctx->match_col_scratch) (void)hipFree(ctx->match_col_scratch);
   if (ctx->q8_scratch) (void)hipFree(ctx->q8_scratch);
   if (ctx->tracks_scratch) (void)hipFree(ctx->tracks_scratch);
+  if (ctx->bundle_scratch) (void)hipFree(ctx->bundle_scratch);
   if (ctx->d_counter1) (void)hipFree(ctx->d_counter1);
   if (ctx->d_queue) (void)hipFree(ctx->d_queue);
   if (ctx->h_counter1) (void)hipHostFree(ctx->h_counter1);

@@ -11,6 +11,7 @@
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 //   sift_describe.hip cusift_describe_batch: the pyramid and describe_given_kernel for caller-supplied keypoints
 //   sift_tracks.hip   cusift_build_tracks, cusift_triangulate_tracks: their kernels and entry points (a unit of its own)
+//   sift_bundle.hip   cusift_bundle_adjust: its kernels and entry point (a unit of its own)
 // The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,
 // reductions, ordered compaction, pair strides).
 #pragma once
@@ -244,6 +245,9 @@ struct cusift_ctx {
   // cusift_build_tracks (pair list, union-find, hash sets, scans) and cusift_triangulate_tracks (the poses): sift_tracks.hip
   char *tracks_scratch = nullptr;
   size_t tracks_scratch_bytes = 0;
+  // cusift_bundle_adjust (the state, both pose and point buffers, node -> track, the reduced system): sift_bundle.hip
+  char *bundle_scratch = nullptr;
+  size_t bundle_scratch_bytes = 0;
   // staging buffer for 8-bit uploads (cusift_image_u8_h2d)
   unsigned char *u8_stage = nullptr;
   size_t u8_stage_bytes = 0;

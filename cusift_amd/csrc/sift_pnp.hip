@@ -394,15 +394,8 @@ __device__ __forceinline__ bool pnp_step(const double *s_sum, double (&p)[6]) {
 
 // R <- R exp([w]x)^T, t <- t - R d: the left increment (w, d) of X2 = R21 X1 + t21 in the returned direction.
 __device__ __forceinline__ bool pnp_update(const double (&p)[6], const double (&rt)[12], double (&out)[12]) {
-  const double w0 = p[0], w1 = p[1], w2 = p[2];
-  const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-  const double th = sqrt(th2);
-  const bool tiny = th2 < 1e-20;
-  const double A = tiny ? 1.0 : sin(th) / th, B = tiny ? 0.5 : (1.0 - cos(th)) / th2;
   double E[3][3];
-  E[0][0] = 1.0 - B * (w1 * w1 + w2 * w2), E[0][1] = B * (w0 * w1) - A * w2, E[0][2] = B * (w0 * w2) + A * w1;
-  E[1][0] = B * (w0 * w1) + A * w2, E[1][1] = 1.0 - B * (w0 * w0 + w2 * w2), E[1][2] = B * (w1 * w2) - A * w0;
-  E[2][0] = B * (w0 * w2) - A * w1, E[2][1] = B * (w1 * w2) + A * w0, E[2][2] = 1.0 - B * (w0 * w0 + w1 * w1);
+  rodrigues_exp(p[0], p[1], p[2], E);
   bool ok = true;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {

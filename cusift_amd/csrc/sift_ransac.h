@@ -180,4 +180,17 @@ __device__ __forceinline__ void write_selected(int *__restrict__ pairs, float *_
   c[3] = b[0], c[4] = b[1], c[5] = b[2];
 }
 
+// Exp(w) of a rotation vector, Rodrigues' formula in fp64: E = I + A [w]x + B [w]x^2, A = sin(th) / th, B = (1 - cos(th))
+// / th^2, the limits 1 and 1/2 below th^2 = 1e-20.  The PnP refit (sift_pnp.hip) and the bundle adjuster's pose update
+// (sift_bundle.hip) both take their increment through this one expression.
+__device__ __forceinline__ void rodrigues_exp(double w0, double w1, double w2, double (&E)[3][3]) {
+  const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
+  const double th = sqrt(th2);
+  const bool tiny = th2 < 1e-20;
+  const double A = tiny ? 1.0 : sin(th) / th, B = tiny ? 0.5 : (1.0 - cos(th)) / th2;
+  E[0][0] = 1.0 - B * (w1 * w1 + w2 * w2), E[0][1] = B * (w0 * w1) - A * w2, E[0][2] = B * (w0 * w2) + A * w1;
+  E[1][0] = B * (w0 * w1) + A * w2, E[1][1] = 1.0 - B * (w0 * w0 + w2 * w2), E[1][2] = B * (w1 * w2) - A * w0;
+  E[2][0] = B * (w0 * w2) - A * w1, E[2][1] = B * (w1 * w2) + A * w0, E[2][2] = 1.0 - B * (w0 * w0 + w1 * w1);
+}
+
 }  // namespace cusift

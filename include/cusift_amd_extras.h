@@ -929,6 +929,106 @@ int cusift_triangulate_tracks(cusift_ctx *ctx, const cusift_point *d_points, int
                               const double *h_poses /* [n_images][12] */, const cusift_camera *camera,
                               double min_pivot, double *d_points3d /* [max_tracks][4] */, int *d_front /* [max_tracks] */);
 
+/* ---- bundle adjustment: the poses and the track points refined together (sift_bundle.hip) ------------------------- */
+/* Minimises  sum over the USED observations of  rho(|pi(R_f^T (X_t - t_f)) - pixel|^2)  over the poses of the frames that
+ * move and the points of the used tracks, by Schur-complement Levenberg-Marquardt, on the device.  New: the reference
+ * stops at one model per pair.  The conventions are cusift_triangulate_tracks', unchanged: h_poses[f] = row-major
+ * [R | t], camera to world; one camera for all frames, px = cx - origin, py = cy - origin, the floats widened; the track
+ * count T = min(d_stats[0], max_tracks) is read on the device; d_points is read, never written.  rho is the identity
+ * (huber == 0) or Huber's function at `huber` pixels, applied as IRLS weights taken at the current accepted iterate.
+ * ALL FP64, every expression in the order written (-ffp-contract=off), "from 0" sums start at +0.0.
+ * ONE OBSERVATION of track t in frame f, pixel (x, y) = coords2D widened, pose P = [R | t], point X:
+ *     e = X - t;  c[j] = (R[0][j]*e0 + R[1][j]*e1) + R[2][j]*e2;  q0 = c0/c2;  q1 = c1/c2
+ *     r0 = (fx*q0 + px) - x;  r1 = (fy*q1 + py) - y;  err2 = r0*r0 + r1*r1
+ *     rho = err2  if huber == 0 or err2 <= huber*huber,  else (2*huber)*sqrt(err2) - huber*huber
+ *     w   = 1     under the same condition,              else huber / sqrt(err2)
+ * USED, decided once, at entry, under h_poses and the input d_points3d.  A track is unused if its input row is four
+ * zeros (triangulation's degenerate mark), if a member is not a node of the batch, or if a member's x or y is not
+ * finite.  Otherwise an observation is used iff c2 > 0 && err2 < inf && (max_error == 0 || sqrt(err2) <= max_error),
+ * and the track is used iff at least two of its observations are; an unused track has no used observation.  Unused
+ * tracks keep their input row bit for bit.
+ * HELD: frame f is held iff h_fixed[f] != 0 (h_fixed == NULL: frame 0 only) or it has no used observation.  Its camera
+ * Jacobian is taken as zero, its diagonal block of the reduced system is the identity, its output pose is its input pose
+ * bit for bit.  With frame 0 alone held the scale is left to the damping; fix a second frame to pin it.
+ * PARAMETRISATION: R <- R Exp(w) with the Rodrigues expression of the PnP refit (E = I + A [w]x + B [w]x^2, A = sin(th)
+ * / th, B = (1 - cos(th)) / th^2, 1 and 1/2 below th^2 = 1e-20; R'[i][j] = (R[i][0]*E[0][j] + R[i][1]*E[1][j]) +
+ * R[i][2]*E[2][j]), t <- t + dt, X <- X + dX; the camera unknowns are ordered (w, dt).  JACOBIANS of (r0, r1):
+ *     a0 = fx/c2;  a1 = fy/c2;  b0 = 0 - a0*q0;  b1 = 0 - a1*q1
+ *     JX[0][k] = a0*R[k][0] + b0*R[k][2];   JX[1][k] = a1*R[k][1] + b1*R[k][2]                       (k = 0..2)
+ *     Jc[0][0..2] = (0 - b0*c1,  b0*c0 - a0*c2,  a0*c1);   Jc[1][0..2] = (a1*c2 - b1*c1,  b1*c0,  0 - a1*c0)
+ *     Jc[r][3 + k] = 0 - JX[r][k]
+ *     W[a][k] = w*(Jc[0][a]*JX[0][k] + Jc[1][a]*JX[1][k])                      (6 x 3, never stored: recomputed)
+ * ONE ITERATION at the current poses, points and lambda:
+ *   per used track, over its used members in d_obs order, from 0:
+ *     V[i][j] += w*(JX[0][i]*JX[0][j] + JX[1][i]*JX[1][j])   (i >= j);     gt[i] += w*(JX[0][i]*r0 + JX[1][i]*r1)
+ *     v_ii = V_ii + lambda*V_ii;  v10, v20, v21 = V's;  c00 = v11*v22 - v21*v21;  c10 = v21*v20 - v10*v22
+ *     c20 = v10*v21 - v11*v20;  det = (v00*c00 + v10*c10) + v20*c20;  c11 = v00*v22 - v20*v20
+ *     c21 = v10*v20 - v00*v21;  c22 = v00*v11 - v10*v10;   Vi[i][j] = Vi[j][i] = c_ij / det
+ *     the track's pivots FAIL unless v00 > 0 && c22 > 0 && 0 < det < inf
+ *   per used observation:  Y[a][k] = (W[a][0]*Vi[0][k] + W[a][1]*Vi[1][k]) + W[a][2]*Vi[2][k]
+ *   per free frame f, over its records (FRAME ORDER, below), from 0:
+ *     U[a][b] += w*(Jc[0][a]*Jc[0][b] + Jc[1][a]*Jc[1][b]);    gf[a] += w*(Jc[0][a]*r0 + Jc[1][a]*r1)
+ *     ef[a] += (Y[a][0]*gt0 + Y[a][1]*gt1) + Y[a][2]*gt2
+ *   per pair of free frames f <= g, over the records of frame f whose track has a used observation in g, FRAME ORDER:
+ *     E[a][b] += (Y_f[a][0]*W_g[b][0] + Y_f[a][1]*W_g[b][1]) + Y_f[a][2]*W_g[b][2]
+ *   the reduced system, dense, of size M = 6 n_images:   S[6f+a][6f+b] = (a == b ? U[a][a] + lambda*U[a][a] : U[a][b])
+ *     - E_ff[a][b];   S[6g+b][6f+a] = 0 - E_fg[a][b]  (f < g);   rhs[6f+a] = ef[a] - gf[a];   a held frame: identity
+ *     block, zero rows and columns, rhs 0.  Only the lower triangle of S is used.
+ *   Cholesky, column j = 0 .. M-1:  acc_i = S[i][j], then acc_i -= L[i][k]*L[j][k] for k = 0 .. j-1 ascending (i >= j);
+ *     L[j][j] = sqrt(acc_j);  L[i][j] = acc_i / L[j][j].  The pivot FAILS unless 0 < acc_j < inf.
+ *     L y = rhs:  for j ascending  y_j = b_j / L[j][j],  then b_i -= L[i][j]*y_j for i > j;
+ *     L^T d = y:  for j descending  d_j = y_j / L[j][j],  then y_i -= L[j][i]*d_j for i < j.
+ *   trial poses of the free frames from d[6f .. 6f+5] as above.  Trial points, per used track, members in d_obs order:
+ *     z[k] = ((((W[0][k]*d0 + W[1][k]*d1) + W[2][k]*d2) + W[3][k]*d3) + W[4][k]*d4) + W[5][k]*d5   (d of the member's frame)
+ *     s[k] = gt[k], then s[k] += z[k];   X'[i] = X[i] + (0 - ((Vi[i][0]*s0 + Vi[i][1]*s1) + Vi[i][2]*s2))
+ *   the cost of a track = sum of rho over its used members in d_obs order from 0; +inf if its pivots failed, if a used
+ *     observation lands at c2 <= 0 (or NaN), or if the sum is not < inf.  The COST = the sum over the used tracks in
+ *     FRAME ORDER by track number; the trial cost is +inf too if a pivot of S failed.
+ * FRAME ORDER: 256 partial sums, partial k takes index k, k + 256, k + 512, ... ascending, from 0 (the index is the
+ * record of the frame, or the track number; what is not used adds nothing); then partial[k] += partial[k + h] for
+ * h = 128, 64, .. 1, and partial[0] is the sum.  No floating-point atomics anywhere: the same input gives the same bytes
+ * in every output on every run.
+ * THE DECISION, on the device: the trial is accepted iff trial cost < cost.  Accepted: the trial becomes the iterate,
+ * lambda = max(lambda / 10, lambda_min), and the solver stops if (cost - trial) / cost <= min_decrease.  Rejected:
+ * lambda = 10 lambda, and the solver stops if lambda > lambda_max.  Without a used track it is stopped at entry.  After
+ * a stop the remaining enqueued iterations do nothing.
+ * OUTPUTS, device memory:
+ *     d_points3d[t]  (X, Y, Z, sqrt of the largest err2 over the track's used observations, from 0) of a used track under
+ *                    the final poses; other rows, and rows at or past T, are not written
+ *     d_poses        all n_images poses, [R | t] row-major
+ *     d_history[k]   (cost before, trial cost, lambda used, flag): 1 accepted, 0 rejected; an iteration that did not run:
+ *                    (cost, cost, lambda, 2)
+ *     d_summary[8]   entry cost, final cost, accepted steps, iterations run, used tracks, used observations, free frames,
+ *                    final lambda
+ * Asynchronous on the context's stream: no synchronisation, no read-back, 5 launches before the first iteration
+ * (copies included), 6 per iteration and 1 behind the last, whatever the data holds.  Scratch lives in the context and
+ * grows on demand: a word per node, some 200 bytes per track, and S (8 M^2 bytes, 18.9 MB at 256 frames).  h_poses and
+ * h_fixed are read before the call returns.
+ * CUSIFT_ERR_INVALID (nothing enqueued): everything cusift_triangulate_tracks refuses; a NULL params or output;
+ * n_images > 256 (the reduced system is dense; beyond it takes an iterative solver); iterations outside [1, 100];
+ * lambda, lambda_min or lambda_max not positive and finite; huber, max_error or min_decrease negative or not finite.
+ * max_tracks == 0 (or a batch without nodes): CUSIFT_OK, d_poses = h_poses, d_summary zeros, d_history rows
+ * (0, 0, lambda, 2). */
+typedef struct cusift_bundle_params {
+  int    iterations;    /* Levenberg-Marquardt iterations ENQUEUED, 1 .. 100 */
+  double lambda;        /* initial damping, > 0                      (default 1e-3) */
+  double lambda_min;    /* floor after an accepted step              (default 1e-9) */
+  double lambda_max;    /* above it the solver stops                 (default 1e6)  */
+  double huber;         /* pixels; 0 = plain squared error */
+  double max_error;     /* pixels; entry gate per observation; 0 = off */
+  double min_decrease;  /* relative; stop after an accepted step that gains less (default 1e-12) */
+} cusift_bundle_params;
+void cusift_bundle_default_params(cusift_bundle_params *p); /* the defaults above, iterations 10 */
+
+int cusift_bundle_adjust(cusift_ctx *ctx, const cusift_point *d_points, int n_images, int max_pts,
+                         const int *d_offsets, const int *d_obs, const unsigned int *d_stats, int max_tracks,
+                         const double *h_poses /* [n_images][12] */,
+                         const unsigned char *h_fixed /* [n_images] or NULL: frame 0 only */,
+                         const cusift_camera *camera, const cusift_bundle_params *params,
+                         double *d_points3d /* [max_tracks][4], IN and OUT */,
+                         double *d_poses /* [n_images][12], OUT */,
+                         double *d_history /* [iterations][4], OUT */, double *d_summary /* [8], OUT */);
+
 #ifdef __cplusplus
 }
 #endif

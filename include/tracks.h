@@ -8,6 +8,8 @@
 // of their first observation.  Only the track count, the offsets and the observations travel back.
 // TriangulateTracks gives every track its 3-D point from all its views under per-frame poses [R | t] (camera to world,
 // 12 doubles a frame) and one camera.
+// BundleAdjust refines those poses and points together (cusift_bundle_adjust: Schur-complement Levenberg-Marquardt on
+// the device) and returns them in place.
 #ifndef CUSIFT_AMD_TRACKS_H
 #define CUSIFT_AMD_TRACKS_H
 
@@ -104,6 +106,61 @@ inline std::vector<double> TriangulateTracks(std::vector<SiftData *> &frames, co
     if (n_tracks > 0) safeCall(cusift_memcpy_d2h(c, front->data(), in_front.ptr, sizeof(int) * n_tracks));
   }
   return out;
+}
+
+// Bundle adjustment of what TriangulateTracks returned: `poses` (12 doubles a frame) and `points` (4 doubles a track)
+// go in and come back refined -- a track that is not used (four zeros, a coordinate that is not finite, fewer than two
+// observations in front of their cameras and inside params->max_error) keeps its row, a frame that is held its pose.
+// params: NULL for cusift_bundle_default_params.  fixed (optional): a flag per frame that must not move; NULL holds
+// frame 0 only, which leaves the scale to the damping -- fix a second frame to pin it.  history (optional): 4 doubles
+// per enqueued iteration (cost, trial cost, lambda, 1 accepted / 0 rejected / 2 not run).  Returns the 8 doubles of the
+// summary: entry cost, final cost, accepted steps, iterations run, used tracks, used observations, free frames,
+// final lambda; empty if poses or points are too short.
+inline std::vector<double> BundleAdjust(std::vector<SiftData *> &frames, const SiftTracks &tracks,
+                                        std::vector<double> &poses, const cusift_camera &camera,
+                                        std::vector<double> &points, const cusift_bundle_params *params = NULL,
+                                        const std::vector<char> *fixed = NULL, std::vector<double> *history = NULL) {
+  cusift_ctx *c = cusift_dropin::ctx();
+  std::vector<std::pair<int, int> > none;
+  cusift_dropin::SequencePack pack(frames, none);
+  const size_t n_tracks = tracks.size(), n_frames = frames.size();
+  if (poses.size() < 12 * n_frames || points.size() < 4 * n_tracks) return std::vector<double>();
+  if (fixed && fixed->size() < n_frames) return std::vector<double>();
+  cusift_bundle_params par;
+  if (params) par = *params;
+  else cusift_bundle_default_params(&par);
+  std::vector<int> h_offsets(1, 0), h_obs;
+  for (size_t t = 0; t < n_tracks; t++) {
+    for (size_t e = 0; e < tracks[t].size(); e++) h_obs.push_back(tracks[t][e].first * pack.max_pts + tracks[t][e].second);
+    h_offsets.push_back((int)h_obs.size());
+  }
+  unsigned int h_stats[8] = {(unsigned int)n_tracks, (unsigned int)h_obs.size(), 0, 0, 0, 0, 0, 0};
+  const size_t n_hist = 4 * (size_t)(par.iterations > 0 ? par.iterations : 1);
+  cusift_dropin::device_block offsets(sizeof(int) * h_offsets.size()), obs(sizeof(int) * h_obs.size());
+  cusift_dropin::device_block counters(sizeof(h_stats)), d_points(sizeof(double) * 4 * n_tracks);
+  cusift_dropin::device_block d_poses(sizeof(double) * 12 * n_frames), d_history(sizeof(double) * n_hist);
+  cusift_dropin::device_block d_summary(sizeof(double) * 8);
+  safeCall(cusift_memcpy_h2d(c, offsets.ptr, h_offsets.data(), sizeof(int) * h_offsets.size()));
+  if (!h_obs.empty()) safeCall(cusift_memcpy_h2d(c, obs.ptr, h_obs.data(), sizeof(int) * h_obs.size()));
+  safeCall(cusift_memcpy_h2d(c, counters.ptr, h_stats, sizeof(h_stats)));
+  if (n_tracks > 0) safeCall(cusift_memcpy_h2d(c, d_points.ptr, points.data(), sizeof(double) * 4 * n_tracks));
+  std::vector<unsigned char> flags(n_frames > 0 ? n_frames : 1, 0);
+  for (size_t f = 0; fixed && f < n_frames; f++) flags[f] = (*fixed)[f] != 0;
+  safeCall(cusift_bundle_adjust(c, pack.d_points(), pack.n, pack.max_pts, static_cast<const int *>(offsets.ptr),
+                                static_cast<const int *>(obs.ptr), static_cast<const unsigned int *>(counters.ptr),
+                                (int)n_tracks, poses.data(), fixed ? flags.data() : NULL, &camera, &par,
+                                static_cast<double *>(d_points.ptr), static_cast<double *>(d_poses.ptr),
+                                static_cast<double *>(d_history.ptr), static_cast<double *>(d_summary.ptr)));
+  std::vector<double> summary(8);
+  safeCall(cusift_memcpy_d2h(c, summary.data(), d_summary.ptr, sizeof(double) * 8));
+  if (n_frames > 0) safeCall(cusift_memcpy_d2h(c, poses.data(), d_poses.ptr, sizeof(double) * 12 * n_frames));
+  if (n_tracks > 0) safeCall(cusift_memcpy_d2h(c, points.data(), d_points.ptr, sizeof(double) * 4 * n_tracks));
+  if (history) {
+    history->assign(n_hist, 0.0);
+    safeCall(cusift_memcpy_d2h(c, history->data(), d_history.ptr, sizeof(double) * n_hist));
+    history->resize(4 * (size_t)par.iterations);
+  }
+  return summary;
 }
 
 #endif  // CUSIFT_AMD_TRACKS_H

@@ -1,0 +1,226 @@
+"""cusift_bundle_adjust (cusift_amd/csrc/sift_bundle.hip) against tests/bundle_model.py's restatement in numpy, through
+capi.Context.bundle_adjust: Scene A (800 tracks, seven frames, every strided loop turning twice) from the default start,
+from a far start that is rejected first, with Huber weights and the entry gate over every kind of unused track, with all
+frames and with frames {0, 3} fixed; Scene B for the factorisation at 198 and 390 unknowns; the refusals; the edges.
+
+The bar for fp64 against a numpy restatement is the project's: 1e-9 * max(1, |value|) on every pose entry, point row and
+cost.  Flags are compared on the iterations where the model's own relative cost change exceeds 1e-6 -- below that the
+decision can rest on rounding -- and the iteration counts stop before the tail where the model's own decisions are
+rounding noise (tests/test_bundle_model.py prints the histories)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import bundle_model as bm
+from bundle_model import FILL
+
+pytestmark = pytest.mark.gpu
+BAR = 1e-9
+
+
+def fixed_mask(n, frames):
+    m = np.zeros(n, bool)
+    m[list(frames)] = True
+    return m
+
+
+# name -> (scene, keywords of the call); the iteration counts: tests/test_bundle_model.py and the histories printed there
+CASES = {
+    "default": (lambda: bm.scene_a(), dict(iterations=5)),
+    "far": (lambda: bm.scene_a_far(), dict(iterations=13, lam=1e-9)),
+    "huber_gate": (lambda: bm.scene_a_gated()[0], dict(iterations=5, huber=1.0, max_error=20.0)),
+    "all_fixed": (lambda: bm.scene_a(), dict(iterations=2, fixed=fixed_mask(7, range(7)))),
+    "fixed_0_3": (lambda: bm.scene_a(), dict(iterations=4, fixed=fixed_mask(7, (0, 3)))),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def model_of(name):
+    make, kw = CASES[name]
+    return bm.run_model(make(), **kw)
+
+
+def deviation(got, want):
+    want = np.asarray(want, dtype=np.float64)
+    both_inf = np.isinf(want) & (got == want)
+    with np.errstate(invalid="ignore"):
+        d = np.abs(got - want) / np.maximum(1.0, np.abs(want))
+    return float(np.where(both_inf, 0.0, d).max()) if d.size else 0.0
+
+
+def compare(out, model, sc, iterations, n_tracks=None, rows_in=None):
+    """Every output of a device run against the model's; returns the largest deviation.  rows_in: what d_points3d held
+    before the call where that is more than the scene's rows and FILL behind them."""
+    T = len(sc["offsets"]) - 1 if n_tracks is None else n_tracks
+    h, mh = out["history"][:iterations], model["history"]
+    worst = max(deviation(out["poses"], model["poses"]), deviation(out["points3d"][:T], model["points3d"]),
+                deviation(h[:, :3], mh[:, :3]), deviation(out["summary"][[0, 1, 7]], model["summary"][[0, 1, 7]]))
+    assert worst <= BAR, worst
+    with np.errstate(invalid="ignore", divide="ignore"):
+        decided = ~(np.abs(mh[:, 0] - mh[:, 1]) / mh[:, 0] <= 1e-6) | (mh[:, 3] == 2)
+    np.testing.assert_array_equal(h[decided, 3], mh[decided, 3])
+    np.testing.assert_array_equal(out["summary"][2:7], model["summary"][2:7])
+    # unused tracks and held frames: the input bytes
+    unused = ~model["used"]
+    assert out["points3d"][:T][unused].tobytes() == np.ascontiguousarray(sc["points"][:T][unused]).tobytes()
+    held = model["held"]
+    assert out["poses"][held].tobytes() == np.ascontiguousarray(sc["poses"][held]).tobytes()
+    # nothing past the track count, nothing past the enqueued iterations
+    if rows_in is None:
+        assert (out["points3d"][len(sc["offsets"]) - 1:] == FILL).all()
+    assert out["points3d"][T:].tobytes() == (out["points3d"] if rows_in is None else rows_in)[T:].tobytes()
+    assert (out["history"][iterations:] == FILL).all()
+    return worst, int(decided.sum())
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_scene_a_equals_the_model(ctx, name):
+    make, kw = CASES[name]
+    sc, model = make(), model_of(name)
+    dev = bm.DeviceBundle(ctx, sc)
+    try:
+        out = dev.run(**kw)
+        worst, decided = compare(out, model, sc, kw["iterations"])
+        print("bundle_adjust %s against the numpy model: largest deviation %.3g (bar 1e-9), %d of %d flags decided above "
+              "1e-6, final cost %.6g" % (name, worst, decided, kw["iterations"], out["summary"][1]))
+        assert dev.records_back().tobytes() == dev.recs.tobytes()  # d_points is read, never written
+        again = dev.run(**kw)
+        for k in ("points3d", "poses", "history", "summary"):
+            assert again[k].tobytes() == out[k].tobytes(), k  # the same bytes on every run
+        if name == "far":
+            assert out["history"][0, 3] == 0 and np.isinf(out["history"][0, 1])
+        if name in ("default", "far"):
+            assert out["summary"][1] <= bm.planted_cost(sc)
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("n_tracks,n_cams", [(120, 33), (60, 65)])
+def test_scene_b_factorisation_sizes(ctx, n_tracks, n_cams):
+    """33 frames: 561 Schur blocks, 198 unknowns; 65 frames: 390 unknowns.  33 and 65 passes of six columns, and
+    neither 198 nor 390 is a multiple of the eight the factorisation's and the back-substitution's loops step by."""
+    sc = bm.planted_scene(n_tracks, n_cams, 8, 0, 3, 0.01, 0.02)
+    assert set(np.diff(sc["offsets"]).tolist()) == set(range(2, 9))
+    model = bm.run_model(sc, iterations=2)
+    assert model["summary"][6] == n_cams - 1 and model["summary"][2] >= 1
+    dev = bm.DeviceBundle(ctx, sc)
+    try:
+        out = dev.run(iterations=2)
+        worst, _ = compare(out, model, sc, 2)
+        print("bundle_adjust %d frames x %d tracks: largest deviation %.3g (bar 1e-9)" % (n_cams, n_tracks, worst))
+    finally:
+        dev.close()
+
+
+def test_refusals(ctx):
+    from cusift_amd import capi
+
+    sc = bm.scene_a()
+    dev = bm.DeviceBundle(ctx, sc)
+    try:
+        host = [dev.points_in(), np.full((sc["n"], 12), FILL), np.full((100, 4), FILL), np.full(8, FILL)]
+        for p, a in zip(dev.outs, host):
+            ctx.h2d(p, a)
+        ctx.synchronize()
+        fx, fy, cx, cy = sc["cam"]
+        flat = np.ascontiguousarray(sc["poses"].reshape(sc["n"], 12))
+        many = np.tile(flat[:1], (257, 1))
+        bad = [flat.copy() for _ in range(2)]
+        bad[0][3, 7], bad[1][6, 0] = np.nan, np.inf
+        d_recs, d_offsets, d_obs, d_stats = dev.ptrs
+        d_x, d_poses, d_hist, d_sum = dev.outs
+        good = dict(recs=d_recs, n=sc["n"], max_pts=sc["max_pts"], offsets=d_offsets, obs=d_obs, stats=d_stats,
+                    cap=dev.cap, poses=flat.ctypes.data, fixed=None, cam=capi.Camera(fx, fy, cx, cy), par={}, x=d_x,
+                    out=d_poses, hist=d_hist, summ=d_sum)
+        cases = [dict(recs=None), dict(offsets=None), dict(obs=None), dict(stats=None), dict(poses=None), dict(cam=None),
+                 dict(par=None), dict(x=None), dict(out=None), dict(hist=None), dict(summ=None),
+                 dict(poses=bad[0].ctypes.data), dict(poses=bad[1].ctypes.data),
+                 dict(cam=capi.Camera(0.0, fy, cx, cy)), dict(cam=capi.Camera(fx, np.inf, cx, cy)),
+                 dict(cam=capi.Camera(fx, fy, np.nan, cy)), dict(cam=capi.Camera(fx, fy, cx, np.inf)),
+                 dict(cam=capi.Camera(fx, fy, cx, cy, origin=np.nan)), dict(cap=-1), dict(n=4096, max_pts=1 << 20),
+                 dict(n=-1), dict(n=65536), dict(max_pts=-1), dict(max_pts=(1 << 20) + 1),
+                 dict(n=257, max_pts=4, poses=many.ctypes.data),
+                 dict(par=dict(iterations=0)), dict(par=dict(iterations=101)), dict(par=dict(lam=0.0)),
+                 dict(par=dict(lam=np.nan)), dict(par=dict(lam=np.inf)), dict(par=dict(lambda_min=0.0)),
+                 dict(par=dict(lambda_min=np.nan)), dict(par=dict(lambda_max=-1.0)), dict(par=dict(lambda_max=np.nan)),
+                 dict(par=dict(huber=-1.0)), dict(par=dict(huber=np.nan)), dict(par=dict(max_error=-1.0)),
+                 dict(par=dict(max_error=np.nan)), dict(par=dict(min_decrease=-1e-30)),
+                 dict(par=dict(min_decrease=np.nan))]
+        for case in cases:
+            a = dict(good, **case)
+            par = None if a["par"] is None else capi.BundleParams(**a["par"])
+            rc = capi.lib().cusift_bundle_adjust(ctx.handle, a["recs"], a["n"], a["max_pts"], a["offsets"], a["obs"],
+                                                 a["stats"], a["cap"], a["poses"], a["fixed"],
+                                                 C.byref(a["cam"]) if a["cam"] is not None else None,
+                                                 C.byref(par) if par is not None else None, a["x"], a["out"], a["hist"],
+                                                 a["summ"])
+            assert rc == -1, (case, rc)  # CUSIFT_ERR_INVALID
+        ctx.synchronize()
+        for p, a in zip(dev.outs, host):
+            back = np.empty_like(a)
+            ctx.d2h(back, p)
+            assert back.tobytes() == a.tobytes()  # nothing was enqueued
+        # 256 frames are not refused (one record each, no track: every frame held, the poses come back)
+        par = capi.BundleParams(iterations=1)
+        d_many = ctx.malloc(8 * 12 * 256)
+        try:
+            rc = capi.lib().cusift_bundle_adjust(ctx.handle, d_recs, 256, 4, d_offsets, d_obs, d_stats, 0,
+                                                 many.ctypes.data, None, C.byref(good["cam"]), C.byref(par), d_x, d_many,
+                                                 d_hist, d_sum)
+            assert rc == 0
+            ctx.synchronize()
+            back = np.empty((256, 12))
+            ctx.d2h(back, d_many)
+            assert back.tobytes() == many[:256].tobytes()
+        finally:
+            ctx.free(d_many)
+    finally:
+        dev.close()
+
+
+def test_edges(ctx):
+    sc = bm.scene_a()
+    dev = bm.DeviceBundle(ctx, sc)
+    try:
+        # max_tracks below the track count clamps it: the first 300 tracks are the problem
+        model = bm.run_model(sc, iterations=3, n_tracks=300)
+        out = dev.run(max_tracks=300, iterations=3)
+        compare(out, model, sc, 3, n_tracks=300, rows_in=dev.points_in())  # rows 300 .. 799 keep the scene's rows
+        assert out["summary"][4] == 300
+        # max_tracks == 0: the poses copied, zeros in the summary, no iteration run
+        out = dev.run(max_tracks=0, iterations=3, lam=0.5)
+        assert out["poses"].tobytes() == np.ascontiguousarray(sc["poses"]).tobytes()
+        assert (out["summary"] == 0).all()
+        np.testing.assert_array_equal(out["history"][:3], [[0, 0, 0.5, 2]] * 3)
+        assert (out["history"][3:] == FILL).all() and out["points3d"].tobytes() == dev.points_in().tobytes()
+    finally:
+        dev.close()
+    # d_stats[0] == 0 with room for tracks: nothing is used, every frame is held, stopped at entry
+    dev = bm.DeviceBundle(ctx, sc, n_tracks=0)
+    try:
+        out = dev.run(iterations=2)
+        assert out["poses"].tobytes() == np.ascontiguousarray(sc["poses"]).tobytes()
+        np.testing.assert_array_equal(out["summary"], [0, 0, 0, 0, 0, 0, 0, 1e-3])
+        np.testing.assert_array_equal(out["history"][:2], [[0, 0, 1e-3, 2]] * 2)
+        assert out["points3d"].tobytes() == dev.points_in().tobytes()
+        model = bm.run_model(sc, iterations=2, n_tracks=0)
+        np.testing.assert_array_equal(model["summary"], out["summary"])
+    finally:
+        dev.close()
+    # one frame: it is frame 0, held; the tracks' observations in it are fewer than two each, so nothing is used
+    one = dict(sc, n=1, poses=sc["poses"][:1], xy=sc["xy"][:1])
+    offsets, obs = [0], []
+    for t in range(20):
+        obs.append(t)
+        offsets.append(len(obs))
+    one["offsets"], one["obs"], one["points"] = np.asarray(offsets, np.int32), np.asarray(obs, np.int32), sc["points"][:20]
+    dev = bm.DeviceBundle(ctx, one)
+    try:
+        out = dev.run(iterations=2)
+        model = bm.run_model(one, iterations=2)
+        compare(out, model, one, 2)
+        assert out["summary"][4] == 0 and out["summary"][6] == 0 and (out["history"][:2, 3] == 2).all()
+    finally:
+        dev.close()
