@@ -100,7 +100,10 @@ def _member_sum(terms, first, length):
 def bundle_model(xy, max_pts, offsets, obs, poses, fx, fy, cx, cy, points3d, origin=0.0, fixed=None, n_tracks=None,
                  **params):
     """xy float32 [n, max_pts, 2]; poses [n, 3, 4] camera to world; points3d [>= T, 4] (the input rows).  Returns a dict:
-    poses [n, 3, 4], points3d [T, 4], history [iterations, 4], summary [8], used (bool per track)."""
+    poses [n, 3, 4], points3d [T, 4], history [iterations, 4], summary [8], used (bool per track), used_obs, held, and
+    two diagnostics: causes, one record per iteration that ran -- sfail (a Cholesky pivot failed), vfail (used tracks
+    whose 3 x 3 pivot test failed), behind (used observations with c2 <= 0 at the trial), pivot (column, value, S[j][j]
+    of the first failed Cholesky pivot or None) -- and, with keep_system=True, systems: (S, rhs, step) per iteration."""
     p = dict(DEFAULTS, **params)
     iterations, lam = int(p["iterations"]), f64(p["lam"])
     poses = np.array(poses, dtype=f64).reshape(-1, 3, 4)
@@ -160,6 +163,7 @@ def bundle_model(xy, max_pts, offsets, obs, poses, fx, fy, cx, cy, points3d, ori
 
         cost = total_cost(poses, X) if T else f64(0.0)
         entry_cost, accepted, ran, stopped = cost, 0, 0, not used_track.any()  # no used track: stopped at entry
+        causes, systems = [], []  # diagnostics for the tests: why a trial was infinite; the reduced systems on request
         for k in range(iterations):
             if stopped:
                 history[k] = (cost, cost, lam, 2.0)
@@ -241,12 +245,14 @@ def bundle_model(xy, max_pts, offsets, obs, poses, fx, fy, cx, cy, points3d, ori
                         S[6 * gg:6 * gg + 6, 6 * f:6 * f + 6] = (0.0 - Efg).T
                 rhs[6 * f:6 * f + 6] = ef - gf
             # ---- Cholesky, column by column, every sum from k = 0 ascending; then L y = rhs and L^T x = y
-            L, sfail = np.zeros((M, M)), False
+            L, sfail, pivot = np.zeros((M, M)), False, None
             for j in range(M):
                 acc = S[j:, j].copy()
                 for kk in range(j):
                     acc = acc - L[j:, kk] * L[j, kk]
                 if not (acc[0] > 0.0 and acc[0] < np.inf):
+                    if not sfail:
+                        pivot = (j, float(acc[0]), float(S[j, j]))
                     sfail = True
                 d = np.sqrt(acc[0])
                 L[j, j] = d
@@ -284,6 +290,11 @@ def bundle_model(xy, max_pts, offsets, obs, poses, fx, fy, cx, cy, points3d, ori
             trial = total_cost(trial_poses, trial_X, vfail)
             if sfail or not (trial < np.inf):
                 trial = f64(np.inf)
+            c_trial = pr.residuals(trial_poses, trial_X, un, ut)[0]
+            causes.append(dict(sfail=bool(sfail), vfail=int(vfail.sum()), behind=int((c_trial[:, 2] <= 0.0).sum()),
+                               pivot=pivot))
+            if p.get("keep_system"):
+                systems.append((S, rhs, yv.copy()))
             # ---- the decision
             if trial < cost:
                 gain = (cost - trial) / cost
@@ -310,7 +321,8 @@ def bundle_model(xy, max_pts, offsets, obs, poses, fx, fy, cx, cy, points3d, ori
             out[used_track, :3] = X[used_track]
             out[used_track, 3] = np.sqrt(worst[used_track])
         summary[:] = (entry_cost, cost, accepted, ran, used_track.sum(), ok.sum(), (~held).sum(), lam)
-    return dict(poses=poses, points3d=out, history=history, summary=summary, used=used_track, used_obs=ok, held=held)
+    return dict(poses=poses, points3d=out, history=history, summary=summary, used=used_track, used_obs=ok, held=held,
+                causes=causes, systems=systems)
 
 
 def perturbed(poses, rot_sigma, trans_sigma, frames, seed=5):
@@ -392,6 +404,30 @@ def scene_a_gated():
     flat[sc["obs"][who["cut3"]]] += (50.0, 0.0)
     flat[sc["obs"][who["cut2"]]] += (0.0, -50.0)
     return sc, who
+
+
+@functools.lru_cache(maxsize=None)
+def scene_small():
+    """The scene of the stop tests: 60 tracks of 2 .. 5 views over five cameras, max_pts 68.  The model's history from
+    the default start: 5526.1 -> 5.3675 -> 9.871e-3 -> 1.1405e-5 -> 1.3366e-8 at lambda = 1e-3 .. 1e-6.  Shared:
+    treat it as read-only."""
+    return planted_scene(60, 5, 5, 0, 3, 0.01, 0.02)
+
+
+FAR_TRACK, FAR_SCALE = 4, 1e170  # a two-view track (frames 3 and 4) that stays in front of both cameras when moved out
+
+
+@functools.lru_cache(maxsize=None)
+def scene_small_far_point():
+    """scene_small() with track FAR_TRACK's entry point FAR_SCALE times as far from the origin: still in front of its
+    two cameras and with finite pixel errors, so the track is used, but its JX is of the order fx / 1e170 and every
+    product of two of them is below the smallest subnormal: V_t is exactly zero, v00 > 0 fails, V_t^-1 = 0 / 0.
+    Returns (scene, the track's frames)."""
+    base = scene_small()
+    sc = dict(base, points=base["points"].copy())
+    sc["points"][FAR_TRACK, :3] *= FAR_SCALE
+    s = slice(base["offsets"][FAR_TRACK], base["offsets"][FAR_TRACK + 1])
+    return sc, tuple((base["obs"][s] // base["max_pts"]).tolist())
 
 
 def planted_cost(sc, **params):

@@ -1,7 +1,12 @@
 """cusift_bundle_adjust (cusift_amd/csrc/sift_bundle.hip) against tests/bundle_model.py's restatement in numpy, through
 capi.Context.bundle_adjust: Scene A (800 tracks, seven frames, every strided loop turning twice) from the default start,
 from a far start that is rejected first, with Huber weights and the entry gate over every kind of unused track, with all
-frames and with frames {0, 3} fixed; Scene B for the factorisation at 198 and 390 unknowns; the refusals; the edges.
+frames, with frames {0, 3} and with no frame fixed; Scene B for the factorisation at 198 and 390 unknowns (1020 to 1536:
+tests/test_bundle_sizes.py); the exits of the state machine -- the min_decrease and lambda_max stops, the lambda_min
+clamp, a failed track pivot without and with a failed Cholesky pivot; the refusals; the edges.
+
+Measured on an MI355X, largest deviation of the cases added with the stops: fixed_none 7.65e-13, min_decrease 2.79e-14,
+lambda_min 8.99e-14; lambda_max, track_pivot and cholesky_pivot 0 (nothing is accepted: every output is an entry value).
 
 The bar for fp64 against a numpy restatement is the project's: 1e-9 * max(1, |value|) on every pose entry, point row and
 cost.  Flags are compared on the iterations where the model's own relative cost change exceeds 1e-6 -- below that the
@@ -33,6 +38,8 @@ CASES = {
     "huber_gate": (lambda: bm.scene_a_gated()[0], dict(iterations=5, huber=1.0, max_error=20.0)),
     "all_fixed": (lambda: bm.scene_a(), dict(iterations=2, fixed=fixed_mask(7, range(7)))),
     "fixed_0_3": (lambda: bm.scene_a(), dict(iterations=4, fixed=fixed_mask(7, (0, 3)))),
+    # h_fixed given and all zero: no frame fixed by the caller (NULL would hold frame 0), frame 6 held as unobserved
+    "fixed_none": (lambda: bm.scene_a(), dict(iterations=4, fixed=fixed_mask(7, ()))),
 }
 
 
@@ -79,6 +86,10 @@ def compare(out, model, sc, iterations, n_tracks=None, rows_in=None):
 def test_scene_a_equals_the_model(ctx, name):
     make, kw = CASES[name]
     sc, model = make(), model_of(name)
+    if name == "fixed_none":  # on the model: the gauge is free, and the steps are still accepted by large margins
+        assert model["held"].tolist() == [False] * 6 + [True] and model["summary"][6] == 6
+        assert (model["history"][:, 3] == 1).all() and (model["history"][:, 1] < 0.1 * model["history"][:, 0]).all()
+        assert not any(c["sfail"] or c["vfail"] or c["behind"] for c in model["causes"])
     dev = bm.DeviceBundle(ctx, sc)
     try:
         out = dev.run(**kw)
@@ -110,6 +121,130 @@ def test_scene_b_factorisation_sizes(ctx, n_tracks, n_cams):
         out = dev.run(iterations=2)
         worst, _ = compare(out, model, sc, 2)
         print("bundle_adjust %d frames x %d tracks: largest deviation %.3g (bar 1e-9)" % (n_cams, n_tracks, worst))
+    finally:
+        dev.close()
+
+
+def far_point_fixed():
+    """The frames of the far point's track and frame 0 held: the track's 0 / 0 never enters the reduced system."""
+    return fixed_mask(5, (0,) + bm.scene_small_far_point()[1])
+
+
+# The exits of the Levenberg-Marquardt state machine; tests/test_bundle_model.py states each from the definition.
+# name -> (scene, keywords of the call; a callable is called for its value when the case runs)
+STOPS = {
+    # the first gain is 0.99903 <= 0.9995: accepted, then stopped (the margin, 4e-4, is far above rounding)
+    "min_decrease": (lambda: bm.scene_small(), dict(iterations=4, min_decrease=0.9995)),
+    # the first trial throws points behind cameras; 10 * 1e-9 exceeds lambda_max
+    "lambda_max": (lambda: bm.scene_a_far(), dict(iterations=3, lam=1e-9, lambda_max=5e-9)),
+    # three accepted steps: lambda 1e-3 -> max(1e-4, 5e-4) -> 5e-4
+    "lambda_min": (lambda: bm.scene_small(), dict(iterations=3, lambda_min=5e-4)),
+    # V_t exactly zero for one used track whose frames are held: vfail alone, three rejections up to lambda_max
+    "track_pivot": (lambda: bm.scene_small_far_point()[0], dict(iterations=5, lambda_max=0.5, fixed=far_point_fixed)),
+    # the same track with its frames free: its 0 / 0 reaches S, the Cholesky pivot of column 18 is NaN -- vfail AND sfail
+    "cholesky_pivot": (lambda: bm.scene_small_far_point()[0], dict(iterations=5, lambda_max=0.5)),
+}
+
+
+def stop_case(name):
+    make, kw = STOPS[name]
+    return make(), {k: v() if callable(v) else v for k, v in kw.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def stop_model(name):
+    sc, kw = stop_case(name)
+    return bm.run_model(sc, **kw)
+
+
+def worst_entry_error(sc, model):
+    """Column 3 of the rows a run that never accepts writes: each used track's largest reprojection error at entry, in
+    plain numpy (no pinned order; the maximum and the square root are exact to an ulp or two)."""
+    nodes = sc["obs"].astype(np.int64)
+    tracks = np.repeat(np.arange(len(sc["offsets"]) - 1), np.diff(sc["offsets"]))
+    fx, fy, cx, cy = (np.float64(np.float32(v)) for v in sc["cam"])
+    P = sc["poses"][nodes // sc["max_pts"]]
+    c = np.einsum("nji,nj->ni", P[:, :, :3], sc["points"][tracks, :3] - P[:, :, 3])
+    uv = np.stack([fx * c[:, 0] / c[:, 2] + cx, fy * c[:, 1] / c[:, 2] + cy], axis=1)
+    err = np.linalg.norm(uv - sc["xy"].reshape(-1, 2)[nodes].astype(np.float64), axis=1)
+    worst = np.zeros(len(sc["offsets"]) - 1)
+    np.maximum.at(worst, tracks[model["used_obs"]], err[model["used_obs"]])
+    return worst
+
+
+@pytest.mark.parametrize("name", list(STOPS))
+def test_stops_and_failed_pivots(ctx, name):
+    """Each case first asserts on the model that it takes the branch it is named for, then compares the device.
+
+    cholesky_pivot: sfail is reached together with vfail only.  S is positive definite for every lambda > 0 in exact
+    arithmetic, so a pivot fails by a margin only through a value that is not finite; NaN pixels and poses are refused
+    or unused at entry, an overflow in U_f is an overflow in V_t of the same observation, and V_t^-1 enters S only
+    through the tracks, so what poisons S has failed its track first.  For the same reason no case has a failed
+    iteration followed by an accepted one (which would pin bundle_decide_kernel's reset of sfail): a rejection changes
+    lambda alone, lambda enters as 1 + lambda, and a failure that ten times lambda cures is one of rounding (lambda
+    below 1e-16) or of subnormal products -- nothing a test may rest on."""
+    (sc, kw), model = stop_case(name), stop_model(name)
+    n_it = kw["iterations"]
+    h, s, causes = model["history"], model["summary"], model["causes"]
+    entry_x, entry_p = np.ascontiguousarray(sc["points"][:, :3]), np.ascontiguousarray(sc["poses"])
+    # ---- the model takes the branch
+    if name == "min_decrease":
+        gain = (h[0, 0] - h[0, 1]) / h[0, 0]
+        assert h[0, 3] == 1 and 0.9985 < gain < 0.9995 - 1e-4
+        assert s[2] == 1 and s[3] == 1 and s[7] == 1e-4
+    elif name == "lambda_max":
+        assert len(causes) == 1 and causes[0]["behind"] > 0 and not causes[0]["sfail"] and causes[0]["vfail"] == 0
+        assert h[0, 3] == 0 and np.isinf(h[0, 1])
+        np.testing.assert_array_equal(s, [h[0, 0], h[0, 0], 0, 1, 800, 3308, 5, 1e-8])
+    elif name == "lambda_min":
+        assert (h[:, 3] == 1).all() and ((h[:, 0] - h[:, 1]) / h[:, 0] > 0.5).all() and s[3] == 3
+    else:
+        assert model["used"][bm.FAR_TRACK] and s[4] == 60  # finite input, and the track is used
+        assert len(causes) == 3 and all(c["vfail"] == 1 and c["behind"] == 0 for c in causes)
+        if name == "track_pivot":
+            assert not any(c["sfail"] for c in causes) and s[6] == 2
+        else:
+            assert all(c["sfail"] and np.isnan(c["pivot"][1]) for c in causes) and s[6] == 4
+        assert np.isfinite(s[0]) and np.isinf(h[:3, 1]).all() and (h[:3, 3] == 0).all()
+        np.testing.assert_array_equal(h[:, 2], [1e-3, 1e-2, 1e-1, 1.0, 1.0])
+        assert s[2] == 0 and s[3] == 3 and s[7] == 1.0
+    dev = bm.DeviceBundle(ctx, sc)
+    try:
+        out = dev.run(**kw)
+        print("bundle_adjust stop %s: history\n%s\nsummary %s" % (name, out["history"][:n_it], out["summary"]))
+        worst, decided = compare(out, model, sc, n_it)
+        print("bundle_adjust stop %s against the numpy model: largest deviation %.3g (bar 1e-9), %d of %d flags decided"
+              % (name, worst, decided, n_it))
+        assert decided == n_it
+        oh, os_ = out["history"], out["summary"]
+        T = len(sc["offsets"]) - 1
+        if name == "min_decrease":
+            # rows 1 .. 3: (cost, cost, lambda, 2) of the accepted step; the outputs are that step's, not the entry's
+            np.testing.assert_array_equal(oh[1:4], [[oh[0, 1], oh[0, 1], 1e-4, 2.0]] * 3)
+            assert os_[2] == 1 and os_[3] == 1 and os_[1] == oh[0, 1] and os_[7] == 1e-4
+            assert (out["poses"][1:] != entry_p[1:]).any(axis=(1, 2)).all()
+            assert (out["points3d"][:T, :3] != entry_x).any(axis=1).all()
+        elif name == "lambda_min":
+            assert (oh[1:3, 2] == 5e-4).all() and os_[7] == 5e-4  # exactly
+        else:
+            # never accepted: the poses and the points are the input bytes, column 3 the worst error at entry
+            assert out["poses"].tobytes() == entry_p.tobytes()
+            assert np.ascontiguousarray(out["points3d"][:T, :3]).tobytes() == entry_x.tobytes()
+            want = worst_entry_error(sc, model)
+            # pixel coordinates are of the order 1e3, an ulp there is 2e-13: 1e-10 px is a few hundred ulps
+            assert np.abs(out["points3d"][:T, 3] - want)[model["used"]].max() <= 1e-10
+            ran = 1 if name == "lambda_max" else 3
+            assert (oh[:ran, 3] == 0).all() and np.isinf(oh[:ran, 1]).all() and (oh[:ran, 0] == os_[0]).all()
+            np.testing.assert_array_equal(oh[1:ran, 2], 10.0 * oh[:ran - 1, 2])  # tenfold a row
+            np.testing.assert_array_equal(oh[ran:n_it], [[os_[0], os_[0], 10.0 * oh[ran - 1, 2], 2.0]] * (n_it - ran))
+            np.testing.assert_array_equal(os_[1:4], [os_[0], 0, ran])
+            assert os_[7] == 10.0 * oh[ran - 1, 2] > kw["lambda_max"]
+            if name == "lambda_max":
+                np.testing.assert_array_equal(os_[2:], [0, 1, 800, 3308, 5, 1e-8])
+        assert dev.records_back().tobytes() == dev.recs.tobytes()
+        again = dev.run(**kw)
+        for k in ("points3d", "poses", "history", "summary"):
+            assert again[k].tobytes() == out[k].tobytes(), k  # the same bytes on every run
     finally:
         dev.close()
 

@@ -208,6 +208,154 @@ def test_two_fixed_frames_pin_the_scale():
     assert r["summary"][1] < r["summary"][0] and (np.diff(r["history"][:, 0]) <= 0).all()
 
 
+def check_state_machine(r, lam, lambda_min, lambda_max, min_decrease):
+    """The rows of a history against the contract's transitions, walked from the definition: row k + 1 starts at
+    max(lambda_k / 10, lambda_min) and the trial cost after an accepted row, at 10 lambda_k and the same cost after a
+    rejected one; the run stops after an accepted row whose gain is at most min_decrease or a rejected one whose next
+    lambda exceeds lambda_max, and every later row is (cost, cost, lambda, 2).  Returns the number of rows that ran."""
+    h, s = r["history"], r["summary"]
+    cost, stopped, ran, accepted = s[0], s[4] == 0, 0, 0
+    for row in h:
+        if stopped:
+            assert row.tolist() == [cost, cost, lam, 2.0]
+            continue
+        ran += 1
+        assert row[0] == cost and row[2] == lam and row[3] in (0.0, 1.0)
+        assert (row[3] == 1.0) == (row[1] < row[0])
+        if row[3] == 1.0:
+            accepted += 1
+            stopped = (cost - row[1]) / cost <= min_decrease
+            cost, lam = row[1], max(lam / 10.0, lambda_min)
+        else:
+            lam = 10.0 * lam
+            stopped = lam > lambda_max
+    assert s[1] == cost and s[2] == accepted and s[7] == lam
+    assert s[3] == ran == (h[:, 3] != 2).sum() == len(r["causes"])
+    return ran
+
+
+def test_every_history_follows_the_state_machine():
+    """The runs the other tests make, and the stops of tests/test_bundle.py, under check_state_machine."""
+    d = bm.DEFAULTS
+    runs = [(bm.run_model(scene(), iterations=ITERS_DEFAULT), {}),
+            (bm.run_model(scene(far=True), iterations=ITERS_FAR, lam=1e-9), dict(lam=1e-9)),
+            (bm.run_model(bm.scene_small(), iterations=4, min_decrease=0.9995), dict(min_decrease=0.9995)),
+            (bm.run_model(bm.scene_small(), iterations=3, lambda_min=5e-4), dict(lambda_min=5e-4)),
+            (bm.run_model(scene(far=True), iterations=3, lam=1e-9, lambda_max=5e-9), dict(lam=1e-9, lambda_max=5e-9))]
+    for r, kw in runs:
+        p = dict(d, **kw)
+        check_state_machine(r, p["lam"], p["lambda_min"], p["lambda_max"], p["min_decrease"])
+
+
+def test_min_decrease_stops_after_the_accepted_step():
+    sc = bm.scene_small()
+    free = bm.run_model(sc, iterations=1)
+    r = bm.run_model(sc, iterations=4, min_decrease=0.9995)
+    h = r["history"]
+    print("small scene: first gain %.6f against min_decrease 0.9995" % ((h[0, 0] - h[0, 1]) / h[0, 0]))
+    assert check_state_machine(r, 1e-3, 1e-9, 1e6, 0.9995) == 1
+    assert abs((h[0, 0] - h[0, 1]) / h[0, 0] - 0.99903) < 1e-5  # 4e-4 under the threshold: no rounding decides this
+    # the outputs are those of the one accepted step, not the entry state: the same as one iteration without the stop
+    for k in ("poses", "points3d"):
+        assert r[k].tobytes() == free[k].tobytes()
+    assert (r["poses"][1:] != sc["poses"][1:]).any(axis=(1, 2)).all()
+    assert h[1:].tolist() == [[h[0, 1], h[0, 1], 1e-4, 2.0]] * 3 and r["summary"][2] == r["summary"][3] == 1
+
+
+def test_lambda_max_stops_after_the_rejected_step():
+    sc = scene(far=True)
+    r = bm.run_model(sc, iterations=3, lam=1e-9, lambda_max=5e-9)
+    assert check_state_machine(r, 1e-9, 1e-9, 5e-9, 1e-12) == 1
+    cause = r["causes"][0]
+    assert cause["behind"] > 0 and cause["vfail"] == 0 and not cause["sfail"]  # points behind cameras, nothing else
+    entry = r["summary"][0]
+    assert np.isinf(r["history"][0, 1]) and r["summary"].tolist() == [entry, entry, 0, 1, 800, 3308, 5, 1e-8]
+    assert r["history"][1:].tolist() == [[entry, entry, 1e-8, 2.0]] * 2
+    # nothing was accepted: the input poses and points, and in column 3 each track's worst error at entry
+    assert r["poses"].tobytes() == sc["poses"].tobytes()
+    assert r["points3d"][:, :3].tobytes() == sc["points"][:, :3].tobytes()
+    _, err, tracks = project(sc, sc["poses"], sc["points"][:, :3])
+    worst = np.zeros(800)
+    np.maximum.at(worst, tracks, err)
+    assert np.abs(r["points3d"][:, 3] - worst).max() <= 1e-10
+    # entry cost: the squared errors of all 3308 observations
+    assert abs(entry / (err * err).sum() - 1.0) < 1e-12
+
+
+def test_lambda_min_clamps_the_damping():
+    r = bm.run_model(bm.scene_small(), iterations=3, lambda_min=5e-4)
+    assert check_state_machine(r, 1e-3, 5e-4, 1e6, 1e-12) == 3
+    assert r["history"][:, 2].tolist() == [1e-3, 5e-4, 5e-4] and r["summary"][7] == 5e-4
+    assert (r["history"][:, 3] == 1).all()
+    # without the clamp the second row would run at 1e-4
+    assert bm.run_model(bm.scene_small(), iterations=2)["history"][1, 2] == 1e-4
+
+
+def test_no_fixed_frame_leaves_the_gauge_to_the_damping():
+    """fixed given and all zero: only the frame nothing observes is held; NULL would hold frame 0 as well."""
+    sc = scene()
+    r = bm.run_model(sc, iterations=4, fixed=np.zeros(7, bool))
+    assert r["held"].tolist() == [False] * 6 + [True] and r["summary"][6] == 6
+    assert check_state_machine(r, 1e-3, 1e-9, 1e6, 1e-12) == 4
+    assert (r["history"][:, 1] < 0.1 * r["history"][:, 0]).all()  # accepted by large margins
+    assert (r["poses"][0] != sc["poses"][0]).any() and r["poses"][6].tobytes() == sc["poses"][6].tobytes()
+    assert not any(c["sfail"] or c["vfail"] or c["behind"] for c in r["causes"])
+
+
+@pytest.mark.parametrize("frames_held", [True, False])
+def test_a_point_far_out_fails_its_track_pivot(frames_held):
+    """Track FAR_TRACK at 1e170 times its distance: used at entry, V_t exactly zero.  With its frames held the reduced
+    system never sees it (vfail alone); with them free its 0 / 0 makes a Cholesky pivot NaN as well."""
+    base = bm.scene_small()
+    sc, frames = bm.scene_small_far_point()
+    assert len(frames) == 2 and np.isfinite(sc["points"]).all()
+    fixed = None
+    if frames_held:
+        fixed = np.zeros(5, bool)
+        fixed[[0] + list(frames)] = True
+    r = bm.run_model(sc, iterations=5, lambda_max=0.5, fixed=fixed)
+    assert check_state_machine(r, 1e-3, 1e-9, 0.5, 1e-12) == 3
+    # from the definition: the track is in front of both cameras with a finite error, and a product of two of its JX
+    # entries (at most (|fx| + |fy|) / c2 each) is below the smallest subnormal by orders of magnitude
+    c2, err, tracks = project(sc, sc["poses"], sc["points"][:, :3])
+    mine = tracks == bm.FAR_TRACK
+    assert (c2[mine] > 1e169).all() and np.isfinite(err[mine]).all() and r["used"][bm.FAR_TRACK]
+    fx, fy, cx, cy = sc["cam"]
+    pix = sc["xy"].reshape(-1, 2)[sc["obs"][mine]].astype(np.float64)
+    q_max = ((np.abs(pix - (cx, cy)).max() + err[mine].max()) / min(fx, fy))  # |q| <= (|pixel - centre| + error) / f
+    jx_max = (fx + fy) * (1.0 + q_max) / c2[mine].min()
+    print("far point: c2 >= %.3g, |q| <= %.3g, |JX| <= %.3g: a product is below 1e%.1f" % (c2[mine].min(), q_max, jx_max,
+                                                                                         2.0 * np.log10(jx_max)))
+    assert 2.0 * np.log10(jx_max) < np.log10(5e-324) - 5.0  # five orders below the smallest subnormal: exactly 0
+    assert r["summary"][4] == 60 and r["summary"][6] == (2 if frames_held else 4)
+    for c in r["causes"]:
+        assert c["vfail"] == 1 and c["behind"] == 0 and c["sfail"] == (not frames_held)
+        if not frames_held:
+            assert np.isnan(c["pivot"][1])  # not a sign that rounding could turn
+    assert np.isinf(r["history"][:3, 1]).all() and r["history"][:, 2].tolist() == [1e-3, 1e-2, 1e-1, 1.0, 1.0]
+    assert r["poses"].tobytes() == sc["poses"].tobytes()
+    assert r["points3d"][:, :3].tobytes() == sc["points"][:, :3].tobytes()
+    worst = np.zeros(60)
+    np.maximum.at(worst, tracks, err)
+    assert np.abs(r["points3d"][:, 3] - worst).max() <= 1e-10  # column 3: the worst error at entry
+    # the scene without the far point is an ordinary one: its first step is accepted
+    assert bm.run_model(base, iterations=1)["history"][0, 3] == 1
+
+
+def test_the_size_scenes_keep_their_conditions():
+    """tests/test_bundle_sizes.py's conditions at 170, 171 and 256 frames, without a GPU (the model: about 20 s)."""
+    import test_bundle_sizes as sizes
+
+    assert sorted(6 * v[0] for v in sizes.SIZES.values()) == [1020, 1026, 1026, 1536]
+    for name, (n_cams, _, _, _, held) in sizes.SIZES.items():
+        sc, model = sizes.check_size_conditions(name)
+        per_frame = np.bincount(sc["obs"][model["used_obs"]] // sc["max_pts"], minlength=n_cams)
+        print("%s: frame %d held, %d .. %d observations a frame, history %s" % (name, held, per_frame.min(),
+                                                                              per_frame.max(),
+                                                                              model["history"][:, :2].tolist()))
+        assert per_frame.min() >= 2 and model["held"].sum() == 1
+
+
 def test_strided_tree_sum_is_the_stated_order():
     rng = np.random.default_rng(0)
     v = rng.normal(size=700) * 10.0 ** rng.integers(-8, 8, size=700)
