@@ -57,6 +57,9 @@ class BatchExtractor:
         counts  int32  [n]                 raw counters; valid points = min(count, max_pts)
     keep_strongest = K > 0: every image keeps its K strongest keypoints (cusift_ctx_set_keep_strongest; K <= max_pts),
     selected on the device before anything is described; counts are then the kept counts.
+    second_orientation = ratio > 0 (0.8 is the reference's constant): every image's records are followed by a duplicate of
+    each keypoint whose orientation histogram has a second peak above ratio x the first, at that orientation
+    (cusift_ctx_set_second_orientation); counts include them, up to max_pts.
     cross_check = True: register_planar, register_epipolar, register_pose, register_planar_sequence and register_sequence feed their
     RANSAC mutual matches only (cusift_ctx_set_cross_check on this extractor's context).
     match_bits = 8: the same calls quantise their records and match the bytes on the int8 matrix pipe
@@ -64,7 +67,7 @@ class BatchExtractor:
     """
 
     def __init__(self, n_images, w, h, params=None, device=None, pitch=None, n_slots=1, keep_strongest=0,
-                 cross_check=False, match_bits=32, **param_overrides):
+                 cross_check=False, match_bits=32, second_orientation=0.0, **param_overrides):
         if not torch.cuda.is_available():
             raise capi.CusiftError("BatchExtractor needs a GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -73,6 +76,7 @@ class BatchExtractor:
         self.params = params if params is not None else capi.default_params(**param_overrides)
         self.max_pts = self.params.max_pts
         self.keep_strongest = capi.check_keep_strongest(keep_strongest, self.max_pts)
+        self.second_orientation = capi.check_second_orientation(second_orientation)
         self.cross_check = bool(capi.check_cross_check(cross_check))
         self.match_bits = capi.check_match_bits(match_bits)
         with torch.cuda.device(self.device):
@@ -80,6 +84,8 @@ class BatchExtractor:
             self.ctx = capi.Context(self.device.index, stream=self.stream.cuda_stream)
             if self.keep_strongest:
                 self.ctx.set_keep_strongest(self.keep_strongest)
+            if self.second_orientation:
+                self.ctx.set_second_orientation(self.second_orientation)
             if self.cross_check:
                 self.ctx.set_cross_check(True)
             if self.match_bits != 32:
@@ -126,6 +132,26 @@ class BatchExtractor:
                 (capi.DESCRIBE_OCTAVE_FROM_SCALE if octave_from_scale else 0)
         self.ctx.describe_batch(d_imgs.data_ptr(), self.n, self.w, self.h, self.pitch, self.h * self.pitch, self.params,
                                 points.data_ptr(), counts.data_ptr() if counts is not None else None, flags)
+        return points, counts
+
+    def second_orientations(self, d_imgs, points=None, counts=None, slot=0, ratio=0.8, octave_from_scale=False):
+        """cusift_second_orientations_batch: appends the second-peak duplicates behind the records as they stand -- by
+        default the slot's own tensors (what extract() or describe() left there).  points: uint8 [n, max_pts, 588] device
+        tensor; counts: int32 [n] device tensor, read and updated (required with `points` given).  Only enqueues work;
+        returns (points, counts)."""
+        assert d_imgs.is_cuda and d_imgs.dtype == torch.float32 and d_imgs.is_contiguous()
+        assert tuple(d_imgs.shape) == (self.n, self.h, self.pitch), tuple(d_imgs.shape)
+        if points is None:
+            points, own_counts = self.slots[slot]
+            counts = own_counts if counts is None else counts
+        if counts is None:
+            raise ValueError("second_orientations: counts is read and written, None given")
+        assert points.is_cuda and points.dtype == torch.uint8 and points.is_contiguous()
+        assert tuple(points.shape) == (self.n, self.max_pts, capi.SIFT_POINT_BYTES), tuple(points.shape)
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.n
+        self.ctx.second_orientations(d_imgs.data_ptr(), self.n, self.w, self.h, self.pitch, self.h * self.pitch,
+                                     self.params, points.data_ptr(), counts.data_ptr(), ratio,
+                                     capi.DESCRIBE_OCTAVE_FROM_SCALE if octave_from_scale else 0)
         return points, counts
 
     def make_packer(self, stream=None):

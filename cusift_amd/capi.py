@@ -192,6 +192,7 @@ SIGNATURES = {
     "cusift_pipe_destroy": (_i, [_vp]),
     "cusift_ctx_set_policy": (_i, [_vp, _i, _i]),
     "cusift_ctx_set_keep_strongest": (_i, [_vp, _i]),
+    "cusift_ctx_set_second_orientation": (_i, [_vp, C.c_float]),
     "cusift_ctx_set_cross_check": (_i, [_vp, _i]),
     "cusift_ctx_set_match_bits": (_i, [_vp, _i]),
     "cusift_ctx_get_policy": (_i, [_vp, _i, C.POINTER(C.c_int)]),
@@ -289,6 +290,7 @@ SIGNATURES = {
     "cusift_sort_points_host": (_i, [_vp, _i]),
     "cusift_extract_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp]),
     "cusift_describe_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp, C.c_uint]),
+    "cusift_second_orientations_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _sz, _PP, _vp, _vp, C.c_float, C.c_uint]),
     "cusift_build_tracks": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "cusift_triangulate_tracks": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(Camera), C.c_double, _vp,
                                        _vp]),
@@ -512,6 +514,21 @@ def check_keep_strongest(k, max_pts=None):
     if max_pts is not None and k > max_pts:
         raise ValueError("keep_strongest: K = %d exceeds max_pts = %d" % (k, max_pts))
     return int(k)
+
+
+def check_second_orientation(ratio, allow_off=True):
+    """What Context.set_second_orientation (and, with allow_off=False, Context.second_orientations) checks before it calls
+    the library (needs no device): returns the ratio as a float.  ValueError for a ratio that is no real number, is
+    negative, above 1 or not a number -- and for 0, which turns the setting off, where the stage call is meant."""
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float, np.integer, np.floating)):
+        raise ValueError("second_orientation: the ratio must be a number, got %r" % (ratio,))
+    r = float(np.float32(ratio))
+    if r == 0.0 and allow_off:
+        return 0.0
+    if not (0.0 < r <= 1.0):  # a NaN fails both comparisons
+        raise ValueError("second_orientation: the ratio must %slie in (0, 1], got %r"
+                         % ("be 0 (off) or " if allow_off else "", ratio))
+    return r
 
 
 def check_select_strongest_args(d_heads, n_lists, n_images, capacity, d_counts, keep, d_kept):
@@ -1064,6 +1081,14 @@ class Context:
         k = check_keep_strongest(k)
         check(lib().cusift_ctx_set_keep_strongest(self.handle, k))
 
+    def set_second_orientation(self, ratio):
+        """cusift_ctx_set_second_orientation: every later extraction on this context (and every graph recorded from now
+        on) appends, behind each image's records, a duplicate of every keypoint whose orientation histogram has a second
+        peak above `ratio` of the first, described at that orientation (second_orientations is the stage).  0 turns it
+        off; 0.8 is the reference's constant."""
+        ratio = check_second_orientation(ratio)
+        check(lib().cusift_ctx_set_second_orientation(self.handle, ratio))
+
     def set_cross_check(self, on):
         """cusift_ctx_set_cross_check: while on, register_planar, register_epipolar, register_pose, register_rgbd,
         register_planar_batch, register_rgbd_batch, register_epipolar_batch, register_pose_batch and register_pnp_batch
@@ -1305,6 +1330,19 @@ class Context:
         DESCRIBE_OCTAVE_FROM_SCALE."""
         check(lib().cusift_describe_batch(self.handle, d_imgs, n_images, w, h, pitch, image_stride, C.byref(params),
                                           d_points, d_counters, int(flags)))
+
+    def second_orientations(self, d_imgs, n_images, w, h, pitch, image_stride, params, d_points, d_counters, ratio=0.8,
+                            flags=0):
+        """cusift_second_orientations_batch: behind image i's min(d_counters[i], max_pts) records, a duplicate of every
+        record whose orientation histogram has a second peak above `ratio` of the first -- the parent's bytes with that
+        peak's orientation and the descriptor at it -- in ascending parent index, cut at max_pts; d_counters (uint32 [n],
+        required) is updated.  The records must have been described on this image (extract_batch, describe_batch);
+        flags: DESCRIBE_OCTAVE_FROM_SCALE.  Asynchronous."""
+        ratio = check_second_orientation(ratio, allow_off=False)
+        if not d_counters:
+            raise ValueError("second_orientations: the counters are read and written, None given")
+        check(lib().cusift_second_orientations_batch(self.handle, d_imgs, n_images, w, h, pitch, image_stride,
+                                                     C.byref(params), d_points, d_counters, ratio, int(flags)))
 
     # ---- feature tracks of a sequence ----
     def build_tracks(self, d_counters, n_images, max_pts, pairs, d_rows, d_track, d_offsets, d_obs, d_stats,

@@ -5,16 +5,20 @@
 // which chooses every record's octave itself.  The contract is include/cusift_amd_extras.h's.
 #include "sift_host.h"
 
-extern "C" int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n_images, int w, int h, int pitch,
-                                     size_t image_stride, const cusift_params *prm, cusift_point *d_points,
-                                     const unsigned int *d_counters, unsigned int flags) {
-  TRY(enter(ctx));
-  if (!prm) return fail(CUSIFT_ERR_INVALID, "params is NULL");
-  if (flags & ~(unsigned int)(CUSIFT_DESCRIBE_KEEP_ORIENTATION | CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE))
-    return fail(CUSIFT_ERR_INVALID, "describe: unknown flag bits 0x%x", flags);
+// The pyramid set-up that cusift_describe_batch and cusift_second_orientations_batch (sift_second.hip) share: refuses
+// the geometry cusift_extract_batch refuses, lays the octave images out in the arena with `extra_bytes` of the caller's
+// scratch behind them (*extra; everything that may allocate or query the device happens before anything is enqueued),
+// and enqueues the extraction's own pyramid launches.  `nothing`: n_images == 0 or max_pts == 0, no error, nothing done.
+int describe_pyramid(cusift_ctx *ctx, const char *who, const float *d_imgs, int n_images, int w, int h, int pitch,
+                     size_t image_stride, const cusift_params *prm, const cusift_point *d_points, size_t extra_bytes,
+                     OctaveTable &T, char **extra, bool &nothing) {
+  nothing = false;
   if (n_images < 0 || prm->max_pts < 0)
-    return fail(CUSIFT_ERR_INVALID, "describe: n_images = %d and max_pts = %d must not be negative", n_images, prm->max_pts);
-  if (n_images == 0 || prm->max_pts == 0) return CUSIFT_OK;  // nothing to do is no error
+    return fail(CUSIFT_ERR_INVALID, "%s: n_images = %d and max_pts = %d must not be negative", who, n_images, prm->max_pts);
+  if (n_images == 0 || prm->max_pts == 0) {  // nothing to do is no error
+    nothing = true;
+    return CUSIFT_OK;
+  }
   // the geometry cusift_extract_batch refuses (resolve_plan, sift_driver.hip)
   if (w < 1 || h < 1 || pitch < w)
     return fail(CUSIFT_ERR_INVALID, "bad geometry n=%d w=%d h=%d pitch=%d", n_images, w, h, pitch);
@@ -22,11 +26,10 @@ extern "C" int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n
   if (n_images > 1 && image_stride < (size_t)h * pitch) return fail(CUSIFT_ERR_INVALID, "image_stride too small");
   if (prm->upsample && (w > (1 << 27) || h > 4 * 65535))
     return fail(CUSIFT_ERR_INVALID, "upsample: %dx%d is too large to enlarge", w, h);
-  if (!d_imgs || !d_points) return fail(CUSIFT_ERR_INVALID, "describe: missing data");
+  if (!d_imgs || !d_points) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
 
   // the octave images of the extraction (resolve_plan): octave 0 is the caller's image or its enlargement, every
   // further one half of the one before, at a pitch of whole 128 floats, one behind the other in the arena
-  OctaveTable T;
   memset(&T, 0, sizeof(T));
   size_t off[kMaxOctaves] = {0};
   const bool up = prm->upsample != 0;
@@ -51,7 +54,7 @@ extern "C" int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n
     T.n_oct = o + 1;
   }
   // everything that may allocate or query the device, before anything is enqueued
-  TRY(ensure_arena(ctx, total));
+  TRY(ensure_arena(ctx, total + extra_bytes));
   if (ctx->describe_grid == 0) {  // the resident blocks of describe_all_kernel (same LDS, same 4 waves per SIMD): cached
     int per_cu = 0, cus = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, describe_all_kernel, 64, 0));
@@ -68,6 +71,21 @@ extern "C" int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n
   for (int o = 1; o < T.n_oct; ++o)
     TRY(cusift_scale_down(ctx, const_cast<float *>(T.base[o]), T.pitch[o], (size_t)T.stride[o], T.base[o - 1], T.w[o - 1],
                           T.h[o - 1], T.pitch[o - 1], (size_t)T.stride[o - 1], n_images, 0.5f));  // cuSIFT.cu:185
+  if (extra) *extra = ctx->arena + total;
+  return CUSIFT_OK;
+}
+
+extern "C" int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n_images, int w, int h, int pitch,
+                                     size_t image_stride, const cusift_params *prm, cusift_point *d_points,
+                                     const unsigned int *d_counters, unsigned int flags) {
+  TRY(enter(ctx));
+  if (!prm) return fail(CUSIFT_ERR_INVALID, "params is NULL");
+  if (flags & ~(unsigned int)(CUSIFT_DESCRIBE_KEEP_ORIENTATION | CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE))
+    return fail(CUSIFT_ERR_INVALID, "describe: unknown flag bits 0x%x", flags);
+  OctaveTable T;
+  bool nothing = false;
+  TRY(describe_pyramid(ctx, "describe", d_imgs, n_images, w, h, pitch, image_stride, prm, d_points, 0, T, nullptr, nothing));
+  if (nothing) return CUSIFT_OK;
 
   float q, inv_q;
   frac_consts(prm->tex_frac_bits, q, inv_q);

@@ -187,6 +187,15 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
     return fail(CUSIFT_ERR_INVALID, "keep_strongest: needs the keypoint lists, which CUSIFT_POLICY_GENERIC_KERNELS rules out");
   if (pl.keep && n_images > kMaxFlatImages)
     return fail(CUSIFT_ERR_INVALID, "keep_strongest: at most %d images per call, got %d", kMaxFlatImages, n_images);
+  // Second-peak orientations (cusift_ctx_set_second_orientation; sift_second.hip): the stage runs behind
+  // describe_all_kernel, on the pyramid that launch has read, so such a call takes the flat path -- or is refused.
+  pl.second = ctx->second_orientation;
+  if (pl.second != 0.0f && !prm->fused_detect)
+    return fail(CUSIFT_ERR_INVALID, "second_orientation: needs the one description launch of fused_detect = 1");
+  if (pl.second != 0.0f && ctx->knobs.force_generic)
+    return fail(CUSIFT_ERR_INVALID, "second_orientation: needs the one description launch, which CUSIFT_POLICY_GENERIC_KERNELS rules out");
+  if (pl.second != 0.0f && n_images > kMaxFlatImages)
+    return fail(CUSIFT_ERR_INVALID, "second_orientation: at most %d images per call, got %d", kMaxFlatImages, n_images);
   int n = std::max(1, std::min(prm->num_octaves, kMaxOctaves));
   pl.upsample = prm->upsample != 0;
   if (pl.upsample) {
@@ -244,6 +253,10 @@ static int resolve_plan(Plan &pl, const cusift_ctx *ctx, const cusift_params *pr
   if (pl.keep) {
     pl.select_off = off;
     off = align_up_sz(off + select_scratch_bytes(pl.n_oct, n_images, prm->max_pts), 256);
+  }
+  if (pl.second != 0.0f) {
+    pl.second_off = off;
+    off = align_up_sz(off + second_scratch_bytes(n_images, prm->max_pts), 256);
   }
   pl.total = off;
   resolve_launches(pl, ctx, prm, true);
@@ -441,11 +454,18 @@ extern "C" int cusift_extract_batch(cusift_ctx *ctx, const float *d_imgs, int n_
   } else {
     HIP_TRY(hipMemsetAsync(queue, 0, kQueueShards * 128, ctx->stream));
   }
-  StageTimer t(ctx, CUSIFT_STAGE_DESCRIBE_ALL);
-  hipLaunchKernelGGL(describe_all_kernel, grid, dim3(64), 0, ctx->stream, T, d_points, prm->max_pts, d_counters,
-                     n_images, q, inv_q, prm->root_sift, queue, G,
-                     pl.self_join ? (const unsigned int *)nullptr : (const unsigned int *)seg_end);
-  return check_launch("describe_all");
+  {
+    StageTimer t(ctx, CUSIFT_STAGE_DESCRIBE_ALL);
+    hipLaunchKernelGGL(describe_all_kernel, grid, dim3(64), 0, ctx->stream, T, d_points, prm->max_pts, d_counters,
+                       n_images, q, inv_q, prm->root_sift, queue, G,
+                       pl.self_join ? (const unsigned int *)nullptr : (const unsigned int *)seg_end);
+    TRY(check_launch("describe_all"));
+  }
+  // second_orientation: the records are complete; the stage duplicates behind them, on the pyramid just read
+  if (pl.second != 0.0f)
+    TRY(second_orientations_impl(ctx, T, d_points, prm->max_pts, d_counters, n_images, prm, pl.second, 0u,
+                                 ctx->arena + pl.second_off));
+  return CUSIFT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 //   sift_describe.hip cusift_describe_batch: the pyramid and describe_given_kernel for caller-supplied keypoints
+//   sift_second.hip   second-peak orientations: the scan kernel, the stage's launches, cusift_second_orientations_batch
+//                     (its wave-per-record kernels: sift_second.inc, in sift_keypoints.hip's unit)
 //   sift_tracks.hip   cusift_build_tracks, cusift_triangulate_tracks: their kernels and entry points (a unit of its own)
 //   sift_bundle.hip   cusift_bundle_adjust: its kernels and entry point (a unit of its own)
 // The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,
@@ -63,6 +65,10 @@ __global__ void describe_bands_kernel(OctaveTable, BandWindows, cusift_point *, 
                                       float, float, int, unsigned int *);
 __global__ void describe_given_kernel(OctaveTable, cusift_point *, int, const unsigned int *, int, float, float, int,
                                       unsigned int);
+__global__ void second_peak_kernel(OctaveTable, const cusift_point *, int, const unsigned int *, int, float, float, float,
+                                   unsigned int, float *);
+__global__ void second_describe_kernel(OctaveTable, cusift_point *, int, const unsigned int *, const unsigned int *,
+                                       const unsigned int *, const float *, int, float, float, int, unsigned int);
 __global__ void rootsift_kernel(cusift_point *, int);
 template <bool kL2>
 __global__ void match_kernel(cusift_point *, int, const cusift_point *, int, int, MatchPartial *, int);
@@ -264,6 +270,8 @@ struct cusift_ctx {
   bool side_probed = false;  // `side` passed the concurrency probe (policy value 2 accepts no other)
   bool recording = false;  // inside cusift_graph_create's capture
   int keep_strongest = 0;  // cusift_ctx_set_keep_strongest: K > 0, every extraction keeps the K strongest keypoints per image
+  float second_orientation = 0.0f;  // cusift_ctx_set_second_orientation: ratio > 0, every extraction duplicates the keypoints
+                                    // whose orientation histogram has a second peak above ratio x the first
   int cross_check = 0;     // cusift_ctx_set_cross_check: 1, the six cusift_register_* calls keep mutual matches only
   int match_bits = 32;     // cusift_ctx_set_match_bits: 8, the registrations quantise and match on the int8 matrix pipe
   unsigned long forks = 0;  // extractions that took the side stream
@@ -343,6 +351,9 @@ struct Plan {
   // keep_strongest = K > 0: the selection's scratch (sift_select.hip) behind the lists; it runs after the last detection
   int keep = 0;
   size_t select_off = 0;
+  // second_orientation = ratio > 0: the stage's scratch (sift_second.hip) behind that; it runs after describe_all_kernel
+  float second = 0.0f;
+  size_t second_off = 0;
   bool fork = false;     // the layout has octave 0's list for the side stream (stays set when no side stream is found)
   size_t dog_bytes = 0;  // DoG planes of the largest kTwoStage octave (0: none)
   // the launch sequence
@@ -418,6 +429,15 @@ int detect_multi_impl(cusift_ctx *ctx, const MultiOctave *octaves, int n_octaves
 size_t select_scratch_bytes(int n_lists, int n_images, int capacity);
 int select_strongest_impl(cusift_ctx *ctx, const SegmentTable &G, int n_images, int capacity, int keep, char *scratch,
                           unsigned int *d_kept);
+// sift_describe.hip: the pyramid of cusift_describe_batch, with `extra_bytes` of the arena behind it
+int describe_pyramid(cusift_ctx *ctx, const char *who, const float *d_imgs, int n_images, int w, int h, int pitch,
+                     size_t image_stride, const cusift_params *prm, const cusift_point *d_points, size_t extra_bytes,
+                     OctaveTable &T, char **extra, bool &nothing);
+// sift_second.hip: the second-peak stage on records that were described on the pyramid T
+size_t second_scratch_bytes(int n_images, int max_pts);
+int second_orientations_impl(cusift_ctx *ctx, const OctaveTable &T, cusift_point *d_points, int max_pts,
+                             unsigned int *d_counters, int n_images, const cusift_params *prm, float ratio,
+                             unsigned int flags, char *scratch);
 int descriptors_impl(cusift_ctx *ctx, const float *d_img, int w, int h, int pitch, size_t img_stride,
                      cusift_point *d_points, int max_pts, const unsigned int *d_first, const unsigned int *d_counters,
                      float subsampling, int tex_frac_bits, int n_images, RowWindow rw, int root_sift = 0,

@@ -8,3 +8,5 @@ int cusift_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2,
 
 // The context's cusift_ctx_set_keep_strongest setting (0: off), for the units that see cusift_ctx as an opaque type.
 int cusift_keep_strongest_of(const cusift_ctx *ctx);
+// The context's cusift_ctx_set_second_orientation setting (0: off), likewise.
+float cusift_second_orientation_of(const cusift_ctx *ctx);

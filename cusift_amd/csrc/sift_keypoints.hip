@@ -474,9 +474,31 @@ __device__ __forceinline__ OriPrep kp_orientation_prep(SH &S, const TEX &tex, fl
   return OriPrep{lattice, w00, w10, w01, w11, e_c};
 }
 
-template <typename SH, typename TEX>
+// The second peak of the smoothed histogram (second-peak orientations: sift_second.inc), from kp_orientation's registers:
+// lanes b and b + 32 hold smoothed value `sm` and peak value `pk` of bin b, `mv` is the largest peak and i1 the first bin
+// that attains it (-1: no positive peak).  The reference's scan (cuSIFT_D.cu:359-375, as oracle_compute_orientations
+// restates it) leaves in maxval2 the largest peak of the bins other than i1 and in i2 the first of them that attains it,
+// -1 when none of them is positive.  The orientation is that of its dormant lines 381-383, the first peak's formula
+// around i2.  Returned to every lane when i2 >= 0 and, in fp32, maxval2 > ratio * maxval1 (one product, one strict
+// compare) -- a NaN otherwise.
+__device__ __forceinline__ float second_peak_orientation(float sm, float pk, float mv, int i1, float ratio, int tx) {
+  const bool other = (tx & 31) != i1;
+  const float mv2 = max_of_lanes_0_31(other ? pk : 0.0f);
+  const unsigned long long hit = __ballot(tx < 32 && other && pk == mv2 && mv2 > 0.0f);
+  const int i2 = hit ? (int)__builtin_ctzll(hit) : -1;
+  const int smi = __builtin_bit_cast(int, sm);
+  const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(smi, (i2 + 1) & 31));
+  const float v2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(smi, (i2 + 31) & 31));
+  const float peak = i2 + 0.5f * (v1 - v2) / (2.0f * mv2 - v1 - v2);
+  const float ori = 11.25f * (peak < 0.0f ? peak + 32.0f : peak);
+  return (i2 >= 0 && mv2 > ratio * mv) ? ori : __builtin_nanf("");
+}
+
+// kSecond (sift_second.inc; false everywhere else, and then nothing below differs): returns second_peak_orientation()
+// of the same histogram instead -- the orientation of the second peak where it passes `ratio`, a NaN where it does not.
+template <bool kSecond = false, typename SH, typename TEX>
 __device__ __forceinline__ float kp_orientation(SH &S, const TEX &tex, const OriPrep &P, float kx, float ky, float scale,
-                                                int tx) {
+                                                int tx, float ratio = 0.0f) {
   const float xp = kx - 5.0f;
   const float yp = ky - 5.0f;
   const bool lattice = P.lattice;
@@ -611,6 +633,7 @@ __device__ __forceinline__ float kp_orientation(SH &S, const TEX &tex, const Ori
   const unsigned long long hit = __ballot(tx < 32 && pk == mv && mv > 0.0f);
   const int i1 = hit ? (int)__builtin_ctzll(hit) : -1;
   const int smi = __builtin_bit_cast(int, sm);
+  if constexpr (kSecond) return second_peak_orientation(sm, pk, mv, i1, ratio, tx);
   const float val1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(smi, (i1 + 1) & 31));
   const float val2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(smi, (i1 + 31) & 31));
   const float peak = i1 + 0.5f * (val1 - val2) / (2.0f * mv - val1 - val2);
@@ -1710,5 +1733,8 @@ __global__ void __launch_bounds__(256) math_eval_kernel(int op, const float *__r
     }
   }
 }
+
+// second-peak orientations: the peak kernel and the kernel that describes the duplicates
+#include "sift_second.inc"
 
 }  // namespace cusift

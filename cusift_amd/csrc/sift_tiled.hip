@@ -181,6 +181,9 @@ extern "C" int cusift_tiled_plan(int W, int H, int world, int num_octaves, int h
 // (the strongest K of a strip are not the strip's share of the image's strongest K)
 static const char kTiledKeepStrongest[] =
     "tiled: the context keeps the strongest keypoints per image (cusift_ctx_set_keep_strongest), which is not tiled; set it to 0";
+// (a strip's histogram near its border is not the image's: the duplicates would depend on the tiling)
+static const char kTiledSecondOrientation[] =
+    "tiled: the context duplicates second-peak orientations (cusift_ctx_set_second_orientation), which is not tiled; set it to 0";
 extern "C" int cusift_tiled_create(cusift_tiled **out, cusift_ctx *ctx, cusift_comm *comm, int rank, int world, int W,
                                    int H, const cusift_params *prm, int halo_rows) {
   if (!out) return cusift_fail(CUSIFT_ERR_INVALID, "out is NULL");
@@ -190,6 +193,7 @@ extern "C" int cusift_tiled_create(cusift_tiled **out, cusift_ctx *ctx, cusift_c
   if (prm->max_pts < 1) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: max_pts must be >= 1");
   if (prm->upsample) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: upsample = 1 (octave -1) is not tiled; enlarge the strips' image first");
   if (cusift_keep_strongest_of(ctx)) return cusift_fail(CUSIFT_ERR_INVALID, kTiledKeepStrongest);
+  if (cusift_second_orientation_of(ctx) != 0.0f) return cusift_fail(CUSIFT_ERR_INVALID, kTiledSecondOrientation);
   if (comm) {
     int cr = -1, cw = -1;
     TRY(cusift_comm_rank(comm, &cr, &cw));
@@ -410,6 +414,7 @@ extern "C" int cusift_tiled_process(cusift_tiled *t, cusift_point *d_points, uns
   TRY(tiled_enter(t));
   if (!d_points || !d_counter) return cusift_fail(CUSIFT_ERR_INVALID, "tiled: missing output");
   if (cusift_keep_strongest_of(t->ctx)) return cusift_fail(CUSIFT_ERR_INVALID, kTiledKeepStrongest);
+  if (cusift_second_orientation_of(t->ctx) != 0.0f) return cusift_fail(CUSIFT_ERR_INVALID, kTiledSecondOrientation);
   const StripPlan &pl = t->pl;
   const cusift_params &p = t->prm;
   HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned int), t->stream));  // cuSIFT.cu:69

@@ -360,12 +360,18 @@ class SiftData {
   // x, scale -- cusift_ctx_set_keep_strongest), selected on the device before anything is described.  0 (default): all,
   // up to maxPts.  At most maxPts.  Handed to the calling thread's context on every Extract.  Trailing field, default 0.
   int keepStrongest;
+  // new: second-peak orientations -- every keypoint whose orientation histogram has a second peak above
+  // secondOrientation x the first is followed, behind the image's records, by a duplicate at that orientation with its own
+  // descriptor (cusift_ctx_set_second_orientation; the duplication the reference leaves compiled out, cuSIFT_D.cu:380).
+  // 0 (default): off; 0.8f is the reference's constant.  Handed to the calling thread's context on every Extract.
+  // Trailing field, default 0.
+  float secondOrientation;
 
   // cuSIFT.cu:13-32
   explicit SiftData(int maxPts_ = 1024, bool host = false, bool dev = false)
       : numPts(0), maxPts(0), h_data(nullptr), d_data(nullptr), numOctaves(5), numScales(5), initBlur(0.0),
         initSubsampling(1.0f), peakThresh(0.1f), edgeThresh(10.0f), lowestScale(0.0f), rootSift(false), scaleUp(false),
-        keepStrongest(0) {
+        keepStrongest(0), secondOrientation(0.0f) {
     allocate(maxPts_, host, dev);
   }
   ~SiftData() { release(); }
@@ -395,6 +401,7 @@ class SiftData {
     require_device("Extract");
     cusift_params p = params(subsampling);
     safeCall(cusift_ctx_set_keep_strongest(cusift_dropin::ctx(), keepStrongest));
+    safeCall(cusift_ctx_set_second_orientation(cusift_dropin::ctx(), secondOrientation));
     safeCall(cusift_extract_host(cusift_dropin::ctx(), im, width, height, &p, as_c(d_data), as_c(h_data), &numPts));
     report(CUSIFT_REPORT_READ(timer));
   }
@@ -409,6 +416,7 @@ class SiftData {
     }
     cusift_params p = params(subsampling);
     safeCall(cusift_ctx_set_keep_strongest(cusift_dropin::ctx(), keepStrongest));
+    safeCall(cusift_ctx_set_second_orientation(cusift_dropin::ctx(), secondOrientation));
     safeCall(cusift_extract(cusift_dropin::ctx(), img.d_data, img.width, img.height, img.pitch, &p, as_c(d_data),
                             as_c(h_data), &numPts));
     report(CUSIFT_REPORT_READ(timer));
@@ -431,6 +439,30 @@ class SiftData {
     safeCall(cusift_describe_batch(cusift_dropin::ctx(), img.d_data, 1, img.width, img.height, img.pitch,
                                    (size_t)img.pitch * img.height, &p, as_c(d_data), nullptr, flags));
     safeCall(cusift_ctx_synchronize(cusift_dropin::ctx()));
+    Synchronize();
+  }
+
+  // New: the second-peak stage on the numPts records in d_data as they stand (an Extract's, or Describe's) -- appends
+  // the duplicates behind them, up to maxPts, over cusift_second_orientations_batch with this object's numOctaves,
+  // scaleUp and rootSift, and updates numPts.  flags: CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE.  Blocking; refreshes h_data.
+  void SecondOrientations(cuImage &img, float ratio = 0.8f, unsigned flags = 0, float subsampling = 1.0f) {
+    require_device("SecondOrientationsSift");
+    if (img.d_data == nullptr) {
+      std::printf("SecondOrientationsSift: missing data\n");
+      return;
+    }
+    if (numPts <= 0) return;
+    cusift_params p = params(subsampling);
+    void *d_count = nullptr;
+    unsigned int count = (unsigned int)numPts;
+    safeCall(cusift_malloc(&d_count, sizeof(count)));
+    safeCall(cusift_memcpy_h2d(cusift_dropin::ctx(), d_count, &count, sizeof(count)));
+    safeCall(cusift_second_orientations_batch(cusift_dropin::ctx(), img.d_data, 1, img.width, img.height, img.pitch,
+                                              (size_t)img.pitch * img.height, &p, as_c(d_data),
+                                              static_cast<unsigned int *>(d_count), ratio, flags));
+    safeCall(cusift_memcpy_d2h(cusift_dropin::ctx(), &count, d_count, sizeof(count)));
+    safeCall(cusift_free(d_count));
+    numPts = (int)count;
     Synchronize();
   }
 
@@ -536,6 +568,12 @@ inline void ExtractSift(SiftData &siftData, cuImage &img, int numOctaves, double
 inline void DescribeSift(SiftData &siftData, cuImage &img, int numOctaves, float subsampling = 1.0f, unsigned flags = 0) {
   siftData.numOctaves = numOctaves;
   siftData.Describe(img, flags, subsampling);
+}
+// New: SiftData::SecondOrientations in the legacy style -- the second-peak duplicates of the records siftData holds.
+inline void SecondOrientationsSift(SiftData &siftData, cuImage &img, int numOctaves, float ratio = 0.8f,
+                                   float subsampling = 1.0f, unsigned flags = 0) {
+  siftData.numOctaves = numOctaves;
+  siftData.SecondOrientations(img, ratio, flags, subsampling);
 }
 // The reference's ExtractRootSift is commented out ("TODO: bring rootsift back", cuSIFT.cu:122-134: ExtractSift,
 // then ConvertSiftToRootSift, then Synchronize; its argument list lost thresh/lowestScale).  Same result in one

@@ -21,7 +21,8 @@
  *     all-gatherv of SiftData, halo exchange, the strip tiling of one large image over the ranks and its band kernels.
  *   cusift_amd_extras.h: the next rows of SURVEY 8f -- cusift_match, cusift_find_homography,
  *                        cusift_estimate_homography, cusift_register_planar, cusift_estimate_rigid, cusift_lift_depth, cusift_select_matches, cusift_register_rgbd, cusift_select_strongest,
- *                        and cusift_describe_batch (orientation + descriptor at the caller's keypoints).
+ *                        cusift_describe_batch (orientation + descriptor at the caller's keypoints) and
+ *                        cusift_second_orientations_batch / cusift_ctx_set_second_orientation (second-peak orientations).
  *
  * Conventions
  *  - every function returns CUSIFT_OK (0) or a negative cusift_status; cusift_last_error() gives text.
@@ -196,6 +197,8 @@ int cusift_ctx_get_policy(cusift_ctx *ctx, int key, int *value);
  * not take (a caller's odd pitch) -- or when k > max_pts.  k < 0 is refused here.  cusift_tiled_* refuses a context with
  * k > 0; cusift_pipe_* creates its own contexts and does not select. */
 int cusift_ctx_set_keep_strongest(cusift_ctx *ctx, int k);
+/* (cusift_ctx_set_second_orientation, the other sticky extraction setting -- a second record for a keypoint whose
+ * orientation histogram has a second peak -- is declared with its stage in cusift_amd_extras.h.) */
 /* An event on a context's stream: record, then the GPU time between two of them (blocks until `stop` has happened).
  * What the reference's TimerGPU does with cudaEvents (cutils.h:94-114); include/cuSIFT.h builds TimerGPU on these. */
 typedef struct cusift_event cusift_event;

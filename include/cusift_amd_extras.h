@@ -850,6 +850,58 @@ int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n_images, in
                           size_t image_stride, const cusift_params *p, cusift_point *d_points,
                           const unsigned int *d_counters /* or NULL */, unsigned int flags);
 
+/* ---- second-peak orientations ----------------------------------------------------------- */
+/* A second record for every keypoint whose orientation histogram has a second peak above `ratio` of the first, as
+ * Lowe's, OpenCV's, VLFeat's and SiftGPU's extraction emit one.  The reference computes both peaks and leaves the
+ * duplication compiled out (ComputeOrientations_D, cuSIFT_D.cu:380 `&& false`); this is that rule, at most ONE duplicate
+ * per keypoint.  A stage on any records: an extraction's (cusift_ctx_set_second_orientation, below, runs it
+ * behind every extraction) or a caller's after cusift_describe_batch.  Asynchronous on the context's stream: three
+ * launches behind the pyramid's whatever the records hold, no host read-back, no allocation once the arena is sized.
+ * d_points: n_images * p->max_pts records; image i has n = min(d_counters[i], max_pts) of them.  Pyramid, `skipped`
+ * validity, octave and units are cusift_describe_batch's, CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE (the only flag) included;
+ * of `p` the same fields are read.
+ *   parent    record j < n gets a duplicate iff it is valid (coordinates and scale finite, scale > 0) and, with hist[32]
+ *             the smoothed histogram of the orientation stage -- on the record's octave image in octave units, the same
+ *             texture model, sums in the oracle's order: the same bits -- and pk[b] = hist[b] where hist[b] > hist[b - 1]
+ *             && hist[b] >= hist[b + 1] (indices mod 32), else 0:
+ *               maxval1 = max(0, max_b pk[b]),   i1 = the first b with pk[b] == maxval1 > 0, -1 if there is none;
+ *               maxval2 = max(0, max_{b != i1} pk[b]),   i2 = the first b != i1 with pk[b] == maxval2 > 0, -1 if none
+ *             (what the reference's one pass over the 32 peaks, cuSIFT_D.cu:359-375, leaves in these four), it holds
+ *               i2 >= 0   &&   maxval2 > ratio * maxval1          in fp32: one product, one strict comparison,
+ *             and the orientation below is a number (a histogram with infinite entries may give a NaN: no duplicate).
+ *             The record's own orientation field is neither read nor checked.
+ *   second    orientation2 = 11.25f * (pk2 < 0 ? pk2 + 32 : pk2),   pk2 = i2 + 0.5f * (v1 - v2) / (2.0f * maxval2 - v1 - v2),
+ *             v1 = hist[(i2 + 1) & 31], v2 = hist[(i2 + 31) & 31]: the first peak's interpolation around i2.
+ *   placed    with m the number of parents of image i: duplicate k (k = 0, 1, ... in ascending parent index) goes to
+ *             slot n + k as long as n + k < max_pts; d_counters[i] = min(n + m, max_pts) (a raw counter above max_pts
+ *             comes back as max_pts).  Records [0, n) keep every byte; nothing at or beyond the new count is touched.
+ *             No append race: the same input gives the same bytes on every run.
+ *   holds     the parent's record byte for byte, except: orientation = orientation2; data[128] = the descriptor at
+ *             orientation2 from the extraction's own descriptor device function (RootSIFT with p->root_sift);
+ *             subsampling = sub[o] of the octave the rule above chose -- the parent's own bits whenever the parent was
+ *             described on this pyramid.
+ * CUSIFT_ERR_INVALID, nothing enqueued: what cusift_describe_batch refuses, a ratio outside (0, 1] or not a number,
+ * d_counters == NULL, any other flag bit.  n_images == 0 or max_pts == 0: CUSIFT_OK, nothing done. */
+int cusift_second_orientations_batch(cusift_ctx *ctx, const float *d_imgs, int n_images, int w, int h, int pitch,
+                                     size_t image_stride, const cusift_params *p, cusift_point *d_points,
+                                     unsigned int *d_counters /* in-out, not NULL */, float ratio, unsigned int flags);
+
+/* The stage above behind every extraction of a context (new here; the reference computes the peak and leaves the duplication compiled out,
+ * cuSIFT_D.cu:380): a keypoint whose orientation histogram has a second peak above `ratio` of the first gets a second
+ * record at that orientation.  Sticky per context; ratio = 0 (the default) turns it off and extraction is bit for bit
+ * and launch for launch what it was; 0.8f is the reference's constant.  With 0 < ratio <= 1 every cusift_extract /
+ * _extract_host / _extract_batch on this context, and every cusift_graph recorded while it is set, runs the stage of
+ * cusift_second_orientations_batch (above: the contract, expression by expression) right behind the
+ * description, on the pyramid that launch has just read: three more launches on the context's stream, the same number
+ * whatever the images hold, no host read-back.  Image i then holds its n records, every byte as with ratio = 0, and
+ * behind them the duplicates in ascending parent index, cut where max_pts ends; d_counters[i] = min(n + duplicates,
+ * max_pts).  With cusift_ctx_set_keep_strongest(k) the selection runs first, only kept records duplicate, and an image
+ * holds up to min(2 k, max_pts) records.  The stage needs the one description launch over all octaves: the call is
+ * refused with CUSIFT_ERR_INVALID, nothing enqueued, with fused_detect = 0, CUSIFT_POLICY_GENERIC_KERNELS or more than
+ * 256 images per call.  A ratio that is negative, above 1 or not a number is refused here.  cusift_tiled_* refuses a
+ * context with ratio > 0; cusift_pipe_* creates its own contexts and does not duplicate. */
+int cusift_ctx_set_second_orientation(cusift_ctx *ctx, float ratio);
+
 /* ---- feature tracks of a sequence: match-graph components and their triangulation (sift_tracks.hip) --------------- */
 /* From the rows of a pair-list matcher to TRACKS, the observations (frame, record) of one scene point across the
  * sequence: what OpenMVG's TracksBuilder, COLMAP's correspondence graph and every bundle adjuster take as input.  New:
