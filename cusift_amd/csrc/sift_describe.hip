@@ -89,13 +89,8 @@ extern "C" int cusift_describe_batch(cusift_ctx *ctx, const float *d_imgs, int n
 
   float q, inv_q;
   frac_consts(prm->tex_frac_bits, q, inv_q);
-  // as many workgroups as are resident at once, at most one per record; beyond kMaxFlatImages one row of them per image
-  const bool flat = n_images <= kMaxFlatImages;
-  const long cap = flat ? (long)n_images * prm->max_pts : (long)prm->max_pts;
-  const long resident = flat ? (long)ctx->describe_grid : std::max(1L, (long)ctx->describe_grid / n_images);
-  dim3 grid((unsigned int)std::max(1L, std::min(cap, resident)), flat ? 1u : (unsigned int)n_images);
   StageTimer t(ctx, CUSIFT_STAGE_DESCRIBE_ALL);
-  hipLaunchKernelGGL(describe_given_kernel, grid, dim3(64), 0, ctx->stream, T, d_points, prm->max_pts, d_counters,
-                     n_images, q, inv_q, prm->root_sift, flags);
+  hipLaunchKernelGGL(describe_given_kernel, describe_walk_grid(ctx, n_images, prm->max_pts), dim3(64), 0, ctx->stream, T,
+                     d_points, prm->max_pts, d_counters, n_images, q, inv_q, prm->root_sift, flags);
   return check_launch("describe_given");
 }

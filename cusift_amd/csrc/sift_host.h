@@ -9,9 +9,11 @@
 //   sift_match8.hip   8-bit descriptors: the quantiser, the int8-MFMA matcher, their entry points (a unit of its own)
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
-//   sift_describe.hip cusift_describe_batch: the pyramid and describe_given_kernel for caller-supplied keypoints
+//   sift_describe.hip cusift_describe_batch: the pyramid (describe_pyramid) and describe_given_kernel for caller-supplied
+//                     keypoints
 //   sift_second.hip   second-peak orientations: the scan kernel, the stage's launches, cusift_second_orientations_batch
-//                     (its wave-per-record kernels: sift_second.inc, in sift_keypoints.hip's unit)
+//                     (its wave-per-record kernels: sift_second.inc, in sift_keypoints.hip's unit, on the frame that unit's
+//                     description kernels share; all three are launched on describe_walk_grid, below)
 //   sift_tracks.hip   cusift_build_tracks, cusift_triangulate_tracks: their kernels and entry points (a unit of its own)
 //   sift_bundle.hip   cusift_bundle_adjust: its kernels and entry point (a unit of its own)
 // The device units share sift_device.h (all of them) and sift_ransac.h (the eight registration units: sampling, winner,
@@ -433,6 +435,15 @@ int select_strongest_impl(cusift_ctx *ctx, const SegmentTable &G, int n_images, 
 int describe_pyramid(cusift_ctx *ctx, const char *who, const float *d_imgs, int n_images, int w, int h, int pitch,
                      size_t image_stride, const cusift_params *prm, const cusift_point *d_points, size_t extra_bytes,
                      OctaveTable &T, char **extra, bool &nothing);
+// The grid of the kernels that walk records with RecordWalk (sift_keypoints.hip: describe_given_kernel, the second-peak
+// kernels): as many workgroups as are resident at once (ctx->describe_grid, sized by describe_pyramid), at most one per
+// record slot; up to kMaxFlatImages images are walked flat (grid.y == 1), beyond that one row of workgroups per image.
+static inline dim3 describe_walk_grid(const cusift_ctx *ctx, int n_images, int max_pts) {
+  const bool flat = n_images <= kMaxFlatImages;
+  const long cap = flat ? (long)n_images * max_pts : (long)max_pts;
+  const long resident = flat ? (long)ctx->describe_grid : std::max(1L, (long)ctx->describe_grid / n_images);
+  return dim3((unsigned int)std::max(1L, std::min(cap, resident)), flat ? 1u : (unsigned int)n_images);
+}
 // sift_second.hip: the second-peak stage on records that were described on the pyramid T
 size_t second_scratch_bytes(int n_images, int max_pts);
 int second_orientations_impl(cusift_ctx *ctx, const OctaveTable &T, cusift_point *d_points, int max_pts,

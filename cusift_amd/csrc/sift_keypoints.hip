@@ -923,6 +923,155 @@ __device__ __forceinline__ bool patch_for_reach(float px, float py, float reach,
 }
 
 // ------------------------------------------------------------------------------------------------
+// The frame the description kernels share -- the two stage kernels, describe_all_kernel, describe_bands_kernel,
+// describe_given_kernel and the two second-peak kernels (sift_second.inc): which image a keypoint samples, how far,
+// through which sampler, which record an item is and how a descriptor leaves.  One copy of each, so "same octave, same
+// patch, same sampler => same bits" between the kernels is what the code says.
+// ------------------------------------------------------------------------------------------------
+// The image a keypoint samples: one image of one octave, or (row window) a band of it.
+struct OctaveView {
+  const float *img;
+  int w, h, pitch;
+  RowWindow rw;
+};
+__device__ __forceinline__ OctaveView octave_view(const OctaveTable &T, int o, int im) {
+  return OctaveView{T.base[o] + (long)im * T.stride[o], T.w[o], T.h[o], T.pitch[o], RowWindow{0, T.h[o]}};
+}
+__device__ __forceinline__ OctaveView band_view(const OctaveTable &T, const BandWindows &BW, int o) {
+  return OctaveView{T.base[o], T.w[o], T.h[o], T.pitch[o], RowWindow{BW.row0[o], BW.hg[o]}};
+}
+
+// Calls f(tex) with the one sampler that applies (wave-uniform): the LDS patch at `pg` with the quantised or the exact
+// texture model, or global memory.  f is a generic lambda: its body is instantiated once per sampler type (PatchSampler).
+template <int kStride, typename F>
+__device__ __forceinline__ void with_sampler(bool use_patch, const float *patch, const PatchGeom &pg, const OctaveView &V,
+                                             float q, float inv_q, F &&f) {
+  if (use_patch) {
+    if (q > 0.0f)
+      f(PatchSampler<kStride, true>{patch, pg.x0, pg.y0, q, inv_q});
+    else
+      f(PatchSampler<kStride, false>{patch, pg.x0, pg.y0, q, inv_q});
+  } else {
+    f(GlobalSampler{V.img, V.w, V.h, V.pitch, V.rw, q, inv_q});
+  }
+}
+
+// One patch for both stages: orientation taps reach 6 px, descriptor taps 7.5*spacing*(|cos|+|sin|) + 1 at most
+// (|cos| + |sin| <= sqrt 2).
+__device__ __forceinline__ float both_stage_reach(float kscale) {
+  return fmaxf(7.5f * (12.0f / 16.0f * kscale) * 1.41422f + 1.0f + 0.01f, 6.0f);
+}
+
+// The octave of a record the extraction wrote: subsampling = sub0 * 2^octave, exp0 = the exponent field of T.sub[0].
+__device__ __forceinline__ int octave_exponent(float sub) { return (__float_as_int(sub) >> 23) & 0xff; }
+__device__ __forceinline__ int octave_from_subsampling_exponent(const OctaveTable &T, float sub, int exp0) {
+  return clampi(octave_exponent(sub) - exp0, 0, T.n_oct - 1);
+}
+
+// cusift_describe_batch's front (include/cusift_amd_extras.h pins both expression by expression; the second-peak stage
+// repeats it).  Validity: both coordinates and the scale finite, the scale positive.  Octave: the recorded one -- the
+// record's subsampling has exactly the bits of some sub[o] (the first such o) -- or, from the scale, the largest o with
+// scale >= kDescribeLow * sub[o], 0 if there is none.
+constexpr float kDescribeLow = 0.93303299f;  // 2^-0.1: the lowest scale / subsampling the detector's refinement assigns
+__device__ __forceinline__ bool finite_bits(float v) { return (sm_bits(v) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ bool valid_keypoint(float x, float y, float scale) {
+  return finite_bits(x) && finite_bits(y) && finite_bits(scale) && scale > 0.0f;
+}
+__device__ __forceinline__ int describe_octave_of(const OctaveTable &T, float rec_sub, float scale, bool from_scale) {
+  int o = -1;
+  if (!from_scale) {
+    for (int i = T.n_oct - 1; i >= 0; --i)
+      if (sm_bits(rec_sub) == sm_bits(T.sub[i])) o = i;
+  }
+  if (o < 0) {
+    o = 0;
+    for (int i = 1; i < T.n_oct; ++i)
+      if (scale >= kDescribeLow * T.sub[i]) o = i;
+  }
+  return o;
+}
+
+// Band of a strip-tiled image: does the keypoint's sampling footprint (orientation window +-6 px, descriptor grid
+// +-7.5*spacing*(|cos|+|sin|), +-1 px taps, bilinear 2x2) leave the band where the band does not end at the image
+// border?  There the clamp would replace the neighbour's rows (cusift_describe_band); the kernels count such keypoints.
+__device__ __forceinline__ bool band_footprint_cut(RowWindow rw, int h, float py, float kscale, float ori) {
+  float sn, cs;
+  sm_sincosf(2.0f * 3.1415f / 360.0f * ori, &sn, &cs);
+  const float r = fmaxf(7.5f * (12.0f / 16.0f * kscale) * (fabsf(sn) + fabsf(cs)), 6.0f) + 2.5f;
+  return (rw.row0 > 0 && !(py - r >= (float)rw.row0)) || (rw.row0 + h < rw.hg && !(py + r <= (float)(rw.row0 + h - 1)));
+}
+
+// RootSIFT epilogue (wave-uniform flag) + the descriptor's stores, lane l its elements desc_elem(l) and + 4
+__device__ __forceinline__ void store_descriptor(KpShared &S, cusift_point *pt, float b0, float b1, int lane,
+                                                 int root_sift) {
+  const int e0 = desc_elem(lane);  // kp_descriptor's element of this lane (and e0 + 4)
+  if (root_sift) {
+    float *v = S.fin();
+    v[e0] = b0;
+    v[e0 + 4] = b1;
+    wave_sync();
+    rootsift_lanes(v, e0, e0 + 4, b0, b1);
+  }
+  pt->data[e0] = b0;
+  pt->data[e0 + 4] = b1;
+}
+
+// s_prefix[1 .. n] hold per-image counts: turns them into running sums (s_prefix[0] = 0) with a wave scan, 64 images per
+// pass.  (Lane 0 alone, one LDS read-modify-write after the other, took ~8,000 cycles for 64 images -- once per wave, 1 %
+// of describe_all_kernel's launch in the phase stamps.)  The caller syncs before and after.
+__device__ __forceinline__ void running_sums_in_place(unsigned int *s_prefix, int n_images, int lane) {
+  unsigned int carry = 0;
+  for (int base = 0; base < n_images; base += 64) {  // wave-uniform
+    const int i = base + lane;
+    unsigned int x = i < n_images ? s_prefix[i + 1] : 0u;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned int y = (unsigned int)__shfl_up((int)x, d);
+      if (lane >= d) x += y;
+    }
+    if (i < n_images) s_prefix[i + 1] = carry + x;
+    carry += (unsigned int)__builtin_amdgcn_readlane((int)x, 63);
+  }
+  if (lane == 0) s_prefix[0] = 0;
+}
+
+// The record walk of describe_given_kernel and the second-peak kernels: item g < total of a workgroup's grid-stride loop
+// is record locate(g) of image `im`.  gridDim.y == 1 (describe_walk_grid, sift_host.h, flattens up to kMaxFlatImages
+// images): the items are the flattened (image, record) pairs over a prefix table of the images' counts clamped at `cap`
+// -- images with few records leave nobody idle; otherwise blockIdx.y is the image.  count_of(i) is image i's count as
+// the kernel reads it.  A workgroup sees increasing items, so `im` only moves forward.  Everything here is wave-uniform.
+struct RecordWalk {
+  const unsigned int *s_prefix;  // [n_images + 1], the kernel's LDS
+  bool flat;
+  int im;
+  unsigned int total;
+  template <typename F>
+  __device__ __forceinline__ RecordWalk(unsigned int *prefix, unsigned int cap, int n_images, int lane, F &&count_of)
+      : s_prefix(prefix), flat(gridDim.y == 1), im(0) {
+    auto clamped = [&](int i) {
+      const unsigned int c = count_of(i);
+      return c < cap ? c : cap;
+    };
+    if (flat) {
+      for (int i = lane; i < n_images; i += 64) prefix[i + 1] = clamped(i);
+      wave_sync();
+      running_sums_in_place(prefix, n_images, lane);
+      wave_sync();
+      total = prefix[n_images];
+    } else {
+      im = blockIdx.y;
+      total = clamped(im);
+    }
+    total = (unsigned int)__builtin_amdgcn_readfirstlane((int)total);
+  }
+  __device__ __forceinline__ unsigned int locate(unsigned int g) {
+    if (!flat) return g;
+    while (__builtin_amdgcn_readfirstlane((int)s_prefix[im + 1]) <= g) ++im;  // ends: g < total = s_prefix[n_images]
+    return g - (unsigned int)__builtin_amdgcn_readfirstlane((int)s_prefix[im]);
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
 // ComputeOrientations (stage entry point; persistent grid over [first, min(count,max_pts)) of each image)
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) orientations_kernel(const float *__restrict__ img, int w, int h, int pitch,
@@ -944,37 +1093,20 @@ __global__ void __launch_bounds__(64) orientations_kernel(const float *__restric
     const float kx = uniform(pt->coords2D[0]), ky = uniform(pt->coords2D[1]);
     // every tap lies in [k-6, k+6]; its 2x2 footprint starts at floor(k-6.5) .. floor(k+5.5): a 16x16 patch
     const bool use_patch = (fabsf(kx) < 1e5f) && (fabsf(ky) < 1e5f);
+    const PatchGeom g{(int)floorf(kx - 6.5f) - 1, (int)floorf(ky - 6.5f) - 1, 16};
+    if (use_patch) stage_patch(img, w, h, pitch, rw, S.patch, g, 16, 16, tx);
     float ori;
-    if (use_patch) {
-      const PatchGeom g{(int)floorf(kx - 6.5f) - 1, (int)floorf(ky - 6.5f) - 1, 16};
-      stage_patch(img, w, h, pitch, rw, S.patch, g, 16, 16, tx);
-      if (q > 0.0f)
-        ori = kp_orientation(S, PatchSampler<16, true>{S.patch, g.x0, g.y0, q, inv_q}, kx, ky, scale, tx);
-      else
-        ori = kp_orientation(S, PatchSampler<16, false>{S.patch, g.x0, g.y0, q, inv_q}, kx, ky, scale, tx);
-    } else {
-      ori = kp_orientation(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, kx, ky, scale, tx);
-    }
+    with_sampler<16>(use_patch, S.patch, g, OctaveView{img, w, h, pitch, rw}, q, inv_q,
+                     [&](const auto &tex) { ori = kp_orientation(S, tex, kx, ky, scale, tx); });
     if (tx == 0) pt->orientation = ori;
     wave_sync();
   }
 }
 
-// RootSIFT epilogue (wave-uniform flag) + the record stores of ExtractSiftDescriptors_D, cuSIFT_D.cu:288-296
+// store_descriptor + the record stores of ExtractSiftDescriptors_D, cuSIFT_D.cu:288-296
 __device__ __forceinline__ void finish_descriptor(KpShared &S, cusift_point *pt, float b0, float b1, float px,
                                                   float py, float kscale, float sub, int lane, int root_sift) {
-  const int e0 = desc_elem(lane);  // kp_descriptor's element of this lane (and e0 + 4)
-  if (root_sift) {
-    float *v = S.fin();
-    v[e0] = b0;
-    v[e0 + 4] = b1;
-    wave_sync();
-    rootsift_lanes(v, e0, e0 + 4, b0, b1);
-  }
-  {
-    pt->data[e0] = b0;
-    pt->data[e0 + 4] = b1;
-  }
+  store_descriptor(S, pt, b0, b1, lane, root_sift);
   if (lane == 0) {
     pt->coords2D[0] = px * sub;
     pt->coords2D[1] = py * sub;
@@ -1004,57 +1136,23 @@ __global__ void __launch_bounds__(64) descriptors_kernel(const float *__restrict
     cusift_point *pt = points + bx;
     const float px = uniform(pt->coords2D[0]), py = uniform(pt->coords2D[1]);
     const float kscale = uniform(pt->scale), ori = uniform(pt->orientation);
-    if (flags) {
-      // Band of a strip-tiled image: count the keypoints whose sampling footprint (orientation window +-6 px,
-      // descriptor grid +-7.5*spacing*(|cos|+|sin|), +-1 px taps, bilinear 2x2) leaves the band where the band does
-      // not end at the image border -- there the clamp would replace the neighbour's rows (cusift_describe_band).
-      float sn, cs;
-      sm_sincosf(2.0f * 3.1415f / 360.0f * ori, &sn, &cs);
-      const float r = fmaxf(7.5f * (12.0f / 16.0f * kscale) * (fabsf(sn) + fabsf(cs)), 6.0f) + 2.5f;
-      const bool cut = (rw.row0 > 0 && !(py - r >= (float)rw.row0)) ||
-                       (rw.row0 + h < rw.hg && !(py + r <= (float)(rw.row0 + h - 1)));
-      if (cut && lane == 0) atomicAdd(flags, 1u);
-    }
+    if (flags && band_footprint_cut(rw, h, py, kscale, ori) && lane == 0) atomicAdd(flags, 1u);
     // every tap is within `reach` of the keypoint: 7.5*spacing*(|cos|+|sin|) for the grid + 1 for the tap
     const float reach = 7.5f * (12.0f / 16.0f * kscale) * 1.41422f + 1.0f + 0.01f;  // |cos| + |sin| <= sqrt 2
     PatchGeom g;
     int pw, ph;
     const bool use_patch = patch_for_reach(px, py, reach, g, pw, ph);
-    float b0, b1;
     if (use_patch) {
       stage_patch(img, w, h, pitch, rw, S.patch, g, pw, ph, lane);
       wave_sync();
-      if (q > 0.0f)
-        kp_descriptor(S, PatchSampler<kDescPatch, true>{S.patch, g.x0, g.y0, q, inv_q}, C, px, py, kscale, ori, lane,
-                      b0, b1);
-      else
-        kp_descriptor(S, PatchSampler<kDescPatch, false>{S.patch, g.x0, g.y0, q, inv_q}, C, px, py, kscale, ori, lane,
-                      b0, b1);
-    } else {
-      kp_descriptor(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, C, px, py, kscale, ori, lane, b0, b1);
     }
+    float b0, b1;
+    with_sampler<kDescPatch>(use_patch, S.patch, g, OctaveView{img, w, h, pitch, rw}, q, inv_q, [&](const auto &tex) {
+      kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
+    });
     finish_descriptor(S, pt, b0, b1, px, py, kscale, subsampling, lane, root_sift);
     wave_sync();
   }
-}
-
-// s_prefix[1 .. n] hold per-image counts: turns them into running sums (s_prefix[0] = 0) with a wave scan, 64 images per
-// pass.  (Lane 0 alone, one LDS read-modify-write after the other, took ~8,000 cycles for 64 images -- once per wave, 1 %
-// of describe_all_kernel's launch in the phase stamps.)  The caller syncs before and after.
-__device__ __forceinline__ void running_sums_in_place(unsigned int *s_prefix, int n_images, int lane) {
-  unsigned int carry = 0;
-  for (int base = 0; base < n_images; base += 64) {  // wave-uniform
-    const int i = base + lane;
-    unsigned int x = i < n_images ? s_prefix[i + 1] : 0u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned int y = (unsigned int)__shfl_up((int)x, d);
-      if (lane >= d) x += y;
-    }
-    if (i < n_images) s_prefix[i + 1] = carry + x;
-    carry += (unsigned int)__builtin_amdgcn_readlane((int)x, 63);
-  }
-  if (lane == 0) s_prefix[0] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1064,20 +1162,6 @@ __device__ __forceinline__ void running_sums_in_place(unsigned int *s_prefix, in
 // -- so images with more keypoints do not leave the rest of the grid idle, one patch load serves both stages,
 // and 2 x octaves launches become one.  Same device functions as the two stage kernels => same results.
 // ------------------------------------------------------------------------------------------------
-// One keypoint, both stages, handing the orientation back (describe_bands_kernel's footprint check wants it);
-// describe_all_kernel makes the same calls itself, with its work-queue steps between them.
-template <typename TEX>
-__device__ __forceinline__ float describe_keypoint_ori(KpShared &S, const TEX &tex, const DescLaneConsts &C,
-                                                       cusift_point *pt, float px, float py, float kscale, float sub,
-                                                       int lane, int root_sift) {
-  const float ori = kp_orientation(S, tex, px, py, kscale, lane);
-  float b0, b1;
-  kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
-  if (lane == 0) pt->orientation = ori;
-  finish_descriptor(S, pt, b0, b1, px, py, kscale, sub, lane, root_sift);
-  return ori;
-}
-
 // 4 waves per SIMD (<= 128 VGPRs) is what this kernel needs: its LDS read-modify-write chains and dependent taps are
 // latency that only other waves hide (forced to 3 / 2 waves the launch takes 1.25x / 1.8x as long)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) describe_all_kernel(OctaveTable T, cusift_point *__restrict__ points, int max_pts,
@@ -1113,7 +1197,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   wave_sync();
   const unsigned int total = s_prefix[n_images];
   const DescLaneConsts C = desc_lane_consts(lane, q, inv_q);
-  const int exp0 = (__float_as_int(T.sub[0]) >> 23) & 0xff;
+  const int exp0 = octave_exponent(T.sub[0]);
 
   // Items are handed out dynamically: the first one is the workgroup's index, every further one comes from a global
   // cursor (*queue, zeroed before the launch) that is advanced when the previous item STARTS, so the atomic's
@@ -1213,21 +1297,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
                    : [off] "v"(0u), [one] "v"(1u), [base] "s"(cursor)
                    : "memory");
     }
-    int o = ((__float_as_int(sub) >> 23) & 0xff) - exp0;  // subsampling = sub0 * 2^octave
-    o = clampi(o, 0, T.n_oct - 1);
-    const float *img = T.base[o] + (long)im_cur * T.stride[o];
-    const int w = T.w[o], h = T.h[o], pitch = T.pitch[o];
-    const RowWindow rw{0, h};
-    // one patch for both stages: orientation taps reach 6 px, descriptor taps 7.5*spacing*sqrt(2)+1 at most
-    const float reach = fmaxf(7.5f * (12.0f / 16.0f * kscale) * 1.41422f + 1.0f + 0.01f, 6.0f);
+    const OctaveView V = octave_view(T, octave_from_subsampling_exponent(T, sub, exp0), im_cur);
     PatchGeom pg;
     int pw, ph;
-    const bool use_patch = patch_for_reach(px, py, reach, pg, pw, ph);
+    const bool use_patch = patch_for_reach(px, py, both_stage_reach(kscale), pg, pw, ph);
     // The patch's loads are issued and NOT waited for: what the orientation stage derives from the keypoint's fields
-    // alone (Gaussian table, lattice test and weights: ~70 instructions) runs while they are in flight.
+    // alone (Gaussian table, lattice test and weights: ~70 instructions) runs while they are in flight.  (The one
+    // sampler dispatch written out: it sits between the loads and their wait.)
     OriPrep prep;
     if (use_patch) {
-      stage_patch<false>(img, w, h, pitch, rw, S.patch, pg, pw, ph, lane);
+      stage_patch<false>(V.img, V.w, V.h, V.pitch, V.rw, S.patch, pg, pw, ph, lane);
       STAMP(S, 0);
       if (q > 0.0f)
         prep = kp_orientation_prep(S, PatchSampler<kDescPatch, true>{S.patch, pg.x0, pg.y0, q, inv_q}, px, py, kscale, lane);
@@ -1236,7 +1315,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
       STAMP(S, 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch is in LDS
     } else {
-      prep = kp_orientation_prep(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, px, py, kscale, lane);
+      prep = kp_orientation_prep(S, GlobalSampler{V.img, V.w, V.h, V.pitch, V.rw, q, inv_q}, px, py, kscale, lane);
     }
     wave_sync();
     STAMP(S, 2);
@@ -1250,14 +1329,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
     if (g < total) pt_next = locate_begin(g);  // issues the load of its image's segment ends
     STAMP(S, 3);
     float ori;
-    if (use_patch) {
-      if (q > 0.0f)
-        ori = kp_orientation(S, PatchSampler<kDescPatch, true>{S.patch, pg.x0, pg.y0, q, inv_q}, prep, px, py, kscale, lane);
-      else
-        ori = kp_orientation(S, PatchSampler<kDescPatch, false>{S.patch, pg.x0, pg.y0, q, inv_q}, prep, px, py, kscale, lane);
-    } else {
-      ori = kp_orientation(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, prep, px, py, kscale, lane);
-    }
+    with_sampler<kDescPatch>(use_patch, S.patch, pg, V, q, inv_q,
+                             [&](const auto &tex) { ori = kp_orientation(S, tex, prep, px, py, kscale, lane); });
     // Between the stages: where the next item's head waits, and the load of that head -- its round trip hides behind
     // the descriptor stage, as the segment ends' did behind the orientation stage.
     const cusift_point *src_next = nullptr;
@@ -1268,14 +1341,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
     }
     STAMP(S, 14);
     float b0, b1;
-    if (use_patch) {
-      if (q > 0.0f)
-        kp_descriptor(S, PatchSampler<kDescPatch, true>{S.patch, pg.x0, pg.y0, q, inv_q}, C, px, py, kscale, ori, lane, b0, b1);
-      else
-        kp_descriptor(S, PatchSampler<kDescPatch, false>{S.patch, pg.x0, pg.y0, q, inv_q}, C, px, py, kscale, ori, lane, b0, b1);
-    } else {
-      kp_descriptor(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, C, px, py, kscale, ori, lane, b0, b1);
-    }
+    with_sampler<kDescPatch>(use_patch, S.patch, pg, V, q, inv_q, [&](const auto &tex) {
+      kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
+    });
     // The next head has arrived long ago; waiting for it HERE, before this keypoint's stores are issued, is free -- at
     // the top of the loop the same wait also waited for those stores' acknowledgements (the compiler's vmcnt(0) for the
     // head's first use: ~1-2 us of write round trip exposed per keypoint).
@@ -1336,8 +1404,8 @@ __global__ void __launch_bounds__(256) join_counts_kernel(unsigned int *__restri
 // band form of describe_all_kernel.  Segment 0 of G is the caller's list as it stands -- keypoints of coarser octaves,
 // already described, left alone -- and segments 1.. are the bands' staging lists, coarsest first; a keypoint's head is
 // read there, its record written at its place in list order.  A rank has a few thousand keypoints: a plain
-// grid-stride walk, none of describe_all_kernel's queue and prefetch.  `flags`: the footprint check of
-// descriptors_kernel (a keypoint whose samples leave the band where the band does not end at the image border).
+// grid-stride walk, none of describe_all_kernel's queue and prefetch.  `flags`: counts the keypoints of
+// band_footprint_cut (samples that leave the band where it does not end at the image border), as descriptors_kernel.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) describe_bands_kernel(
     OctaveTable T, BandWindows BW, cusift_point *__restrict__ points, int max_pts, SegmentTable G,
@@ -1346,7 +1414,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   const int lane = threadIdx.x;
   const unsigned int total = seg_end[G.n_seg - 1];
   const DescLaneConsts C = desc_lane_consts(lane, q, inv_q);
-  const int exp0 = (__float_as_int(T.sub[0]) >> 23) & 0xff;
+  const int exp0 = octave_exponent(T.sub[0]);
   for (unsigned int k = seg_end[0] + blockIdx.x; k < total; k += gridDim.x) {  // wave-uniform
     int r = 1;
     unsigned int first = seg_end[0];
@@ -1362,62 +1430,55 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
       pt->edgeness = edge;
       pt->subsampling = sub;
     }
-    int o = ((__float_as_int(sub) >> 23) & 0xff) - exp0;  // subsampling = sub0 * 2^octave
-    o = clampi(o, 0, T.n_oct - 1);
-    const float *img = T.base[o];
-    const int w = T.w[o], h = T.h[o], pitch = T.pitch[o];
-    const RowWindow rw{BW.row0[o], BW.hg[o]};
-    const float reach = fmaxf(7.5f * (12.0f / 16.0f * kscale) * 1.41422f + 1.0f + 0.01f, 6.0f);
+    const OctaveView V = band_view(T, BW, octave_from_subsampling_exponent(T, sub, exp0));
     PatchGeom pg;
     int pw, ph;
-    const bool use_patch = patch_for_reach(px, py, reach, pg, pw, ph);
-    if (use_patch) stage_patch(img, w, h, pitch, rw, S.patch, pg, pw, ph, lane);
+    const bool use_patch = patch_for_reach(px, py, both_stage_reach(kscale), pg, pw, ph);
+    if (use_patch) stage_patch(V.img, V.w, V.h, V.pitch, V.rw, S.patch, pg, pw, ph, lane);
     wave_sync();
     float ori;
-    if (use_patch) {
-      if (q > 0.0f)
-        ori = describe_keypoint_ori(S, PatchSampler<kDescPatch, true>{S.patch, pg.x0, pg.y0, q, inv_q}, C, pt, px, py, kscale,
-                                sub, lane, root_sift);
-      else
-        ori = describe_keypoint_ori(S, PatchSampler<kDescPatch, false>{S.patch, pg.x0, pg.y0, q, inv_q}, C, pt, px, py, kscale,
-                                sub, lane, root_sift);
-    } else {
-      ori = describe_keypoint_ori(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, C, pt, px, py, kscale, sub, lane, root_sift);
-    }
-    if (flags) {  // as in descriptors_kernel
-      float sn, cs;
-      sm_sincosf(2.0f * 3.1415f / 360.0f * ori, &sn, &cs);
-      const float rr = fmaxf(7.5f * (12.0f / 16.0f * kscale) * (fabsf(sn) + fabsf(cs)), 6.0f) + 2.5f;
-      const bool cut = (rw.row0 > 0 && !(py - rr >= (float)rw.row0)) ||
-                       (rw.row0 + h < rw.hg && !(py + rr <= (float)(rw.row0 + h - 1)));
-      if (cut && lane == 0) atomicAdd(flags, 1u);
-    }
+    with_sampler<kDescPatch>(use_patch, S.patch, pg, V, q, inv_q, [&](const auto &tex) {  // both stages, as describe_all_kernel
+      ori = kp_orientation(S, tex, px, py, kscale, lane);
+      float b0, b1;
+      kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
+      if (lane == 0) pt->orientation = ori;
+      finish_descriptor(S, pt, b0, b1, px, py, kscale, sub, lane, root_sift);
+    });
+    if (flags && band_footprint_cut(V.rw, V.h, py, kscale, ori) && lane == 0) atomicAdd(flags, 1u);
     wave_sync();
   }
 }
 
 // ------------------------------------------------------------------------------------------------
 // Orientation + descriptor of keypoints the CALLER supplies (cusift_describe_batch, sift_describe.hip): records in
-// input-image pixels, in the caller's order, described in place.  Its own front -- validity test, octave rule, octave
-// units: include/cusift_amd_extras.h pins all three expression by expression -- then the device functions of the kernels above
-// on the extraction's pyramid, so a record that came from an extraction gets its bits back.  A plain walk like
-// describe_bands_kernel's: none of describe_all_kernel's queue and prefetch.
-//   walk    gridDim.y == 1: the flattened (image, record) pairs, grid-stride, over a prefix table of the clamped
-//           counts (n_images <= kMaxFlatImages) -- images with few records leave nobody idle; otherwise blockIdx.y is
-//           the image.  counters == NULL: every image has max_pts records.
+// input-image pixels, in the caller's order, described in place.  Its own front -- valid_keypoint, describe_octave_of,
+// octave units: include/cusift_amd_extras.h pins all three expression by expression -- then the device functions of the
+// kernels above on the extraction's pyramid, so a record that came from an extraction gets its bits back.  A plain walk
+// (RecordWalk; counters == NULL: every image has max_pts records): none of describe_all_kernel's queue and prefetch.
 //   writes  data, subsampling and -- unless the orientation is kept -- orientation; nothing else of a record, and
 //           nothing beyond an image's count.
 // ------------------------------------------------------------------------------------------------
-constexpr float kDescribeLow = 0.93303299f;  // 2^-0.1: the lowest scale / subsampling the detector's refinement assigns
-__device__ __forceinline__ bool finite_bits(float v) { return (sm_bits(v) & 0x7f800000u) != 0x7f800000u; }
-
-// one valid keypoint through one sampler: `ori` is the kept orientation, or replaced by the orientation stage's
-template <typename TEX>
-__device__ __forceinline__ void describe_given_one(KpShared &S, const TEX &tex, const DescLaneConsts &C, float px,
-                                                   float py, float kscale, bool keep, float &ori, int lane, float &b0,
-                                                   float &b1) {
-  if (!keep) ori = kp_orientation(S, tex, px, py, kscale, lane);  // wave-uniform
-  kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
+// One valid record's sampling set-up on octave o = describe_octave_of(), shared with the second-peak kernels
+// (sift_second.inc): the record in octave units, the patch of both stages staged and waited for.  A kept orientation
+// whose sine and cosine may not be finite (sm_sincosf answers NaN from |x| = 1e9) takes the global sampler, whose
+// clamps hold for any tap position.
+struct GivenKeypoint {
+  OctaveView V;
+  float sub, px, py, kscale;
+  PatchGeom pg;
+  bool use_patch;
+};
+__device__ __forceinline__ GivenKeypoint stage_given(KpShared &S, const OctaveTable &T, int o, int im, float x, float y,
+                                                     float scale, float ori, int lane) {
+  GivenKeypoint K;
+  K.sub = T.sub[o];
+  K.px = x / K.sub, K.py = y / K.sub, K.kscale = scale / K.sub;  // octave units
+  K.V = octave_view(T, o, im);
+  int pw, ph;
+  K.use_patch = patch_for_reach(K.px, K.py, both_stage_reach(K.kscale), K.pg, pw, ph) && fabsf(ori) < 1e9f;
+  if (K.use_patch) stage_patch(K.V.img, K.V.w, K.V.h, K.V.pitch, K.V.rw, S.patch, K.pg, pw, ph, lane);
+  wave_sync();
+  return K;
 }
 
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) describe_given_kernel(
@@ -1426,93 +1487,33 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   __shared__ KpShared S;
   __shared__ unsigned int s_prefix[kMaxFlatImages + 1];
   const int lane = threadIdx.x;
-  const bool flat = gridDim.y == 1;  // wave-uniform; the host flattens up to kMaxFlatImages images
   const bool keep = (flags & CUSIFT_DESCRIBE_KEEP_ORIENTATION) != 0u;
   const bool from_scale = (flags & CUSIFT_DESCRIBE_OCTAVE_FROM_SCALE) != 0u;
-  auto count_of = [&](int i) {
-    const unsigned int c = counters ? counters[i] : (unsigned int)max_pts;
-    return c < (unsigned int)max_pts ? c : (unsigned int)max_pts;
-  };
-  unsigned int total;
-  int im;
-  if (flat) {
-    for (int i = lane; i < n_images; i += 64) s_prefix[i + 1] = count_of(i);
-    wave_sync();
-    running_sums_in_place(s_prefix, n_images, lane);
-    wave_sync();
-    total = s_prefix[n_images];
-    im = 0;
-  } else {
-    im = blockIdx.y;
-    total = count_of(im);
-  }
-  total = (unsigned int)__builtin_amdgcn_readfirstlane((int)total);
+  RecordWalk walk(s_prefix, (unsigned int)max_pts, n_images, lane,  // counters == NULL: every image has max_pts records
+                  [&](int i) { return counters ? counters[i] : (unsigned int)max_pts; });
   const DescLaneConsts C = desc_lane_consts(lane, q, inv_q);
 
-  for (unsigned int g = blockIdx.x; g < total; g += gridDim.x) {  // wave-uniform
-    unsigned int idx = g;
-    if (flat) {
-      while (__builtin_amdgcn_readfirstlane((int)s_prefix[im + 1]) <= g) ++im;  // ends: g < total = s_prefix[n_images]
-      idx = g - (unsigned int)__builtin_amdgcn_readfirstlane((int)s_prefix[im]);
-    }
-    cusift_point *pt = points + (long)im * max_pts + idx;
+  for (unsigned int g = blockIdx.x; g < walk.total; g += gridDim.x) {  // wave-uniform
+    const unsigned int idx = walk.locate(g);
+    cusift_point *pt = points + (long)walk.im * max_pts + idx;
     const float x = uniform(pt->coords2D[0]), y = uniform(pt->coords2D[1]), scale = uniform(pt->scale);
     const float rec_sub = uniform(pt->subsampling);
     float ori = keep ? uniform(pt->orientation) : 0.0f;
-    // validity: both coordinates and the scale finite, the scale positive
-    if (!(finite_bits(x) && finite_bits(y) && finite_bits(scale) && scale > 0.0f)) {
+    if (!valid_keypoint(x, y, scale)) {
       pt->data[lane] = 0.0f;
       pt->data[lane + 64] = 0.0f;
       if (lane == 0) pt->subsampling = 0.0f;
       continue;
     }
-    // octave: the recorded one -- the record's subsampling has exactly the bits of some sub[o] (the first such o) --
-    // or, from the scale, the largest o with scale >= kLow * sub[o], 0 if there is none
-    int o = -1;
-    if (!from_scale) {
-      for (int i = T.n_oct - 1; i >= 0; --i)
-        if (sm_bits(rec_sub) == sm_bits(T.sub[i])) o = i;
-    }
-    if (o < 0) {
-      o = 0;
-      for (int i = 1; i < T.n_oct; ++i)
-        if (scale >= kDescribeLow * T.sub[i]) o = i;
-    }
-    const float sub = T.sub[o];
-    const float px = x / sub, py = y / sub, kscale = scale / sub;  // octave units
-    const float *img = T.base[o] + (long)im * T.stride[o];
-    const int w = T.w[o], h = T.h[o], pitch = T.pitch[o];
-    const RowWindow rw{0, h};
-    // one patch for both stages, as describe_all_kernel's.  A kept orientation whose sine and cosine may not be finite
-    // (sm_sincosf answers NaN from |x| = 1e9) takes the global sampler, whose clamps hold for any tap position.
-    const float reach = fmaxf(7.5f * (12.0f / 16.0f * kscale) * 1.41422f + 1.0f + 0.01f, 6.0f);
-    PatchGeom pg;
-    int pw, ph;
-    const bool use_patch = patch_for_reach(px, py, reach, pg, pw, ph) && fabsf(ori) < 1e9f;
-    if (use_patch) stage_patch(img, w, h, pitch, rw, S.patch, pg, pw, ph, lane);
-    wave_sync();
+    const int o = describe_octave_of(T, rec_sub, scale, from_scale);
+    const GivenKeypoint K = stage_given(S, T, o, walk.im, x, y, scale, ori, lane);
+    const float sub = K.sub, px = K.px, py = K.py, kscale = K.kscale;
     float b0, b1;
-    if (use_patch) {
-      if (q > 0.0f)
-        describe_given_one(S, PatchSampler<kDescPatch, true>{S.patch, pg.x0, pg.y0, q, inv_q}, C, px, py, kscale, keep, ori,
-                           lane, b0, b1);
-      else
-        describe_given_one(S, PatchSampler<kDescPatch, false>{S.patch, pg.x0, pg.y0, q, inv_q}, C, px, py, kscale, keep, ori,
-                           lane, b0, b1);
-    } else {
-      describe_given_one(S, GlobalSampler{img, w, h, pitch, rw, q, inv_q}, C, px, py, kscale, keep, ori, lane, b0, b1);
-    }
-    // finish_descriptor's RootSIFT step and descriptor stores; of the head only orientation and subsampling
-    const int e0 = desc_elem(lane);
-    if (root_sift) {
-      float *v = S.fin();
-      v[e0] = b0;
-      v[e0 + 4] = b1;
-      wave_sync();
-      rootsift_lanes(v, e0, e0 + 4, b0, b1);
-    }
-    pt->data[e0] = b0;
-    pt->data[e0 + 4] = b1;
+    with_sampler<kDescPatch>(K.use_patch, S.patch, K.pg, K.V, q, inv_q, [&](const auto &tex) {
+      if (!keep) ori = kp_orientation(S, tex, px, py, kscale, lane);  // wave-uniform
+      kp_descriptor(S, tex, C, px, py, kscale, ori, lane, b0, b1);
+    });
+    store_descriptor(S, pt, b0, b1, lane, root_sift);  // of the head only orientation and subsampling
     if (lane == 0) {
       if (!keep) pt->orientation = ori;
       pt->subsampling = sub;

@@ -65,11 +65,7 @@ int second_orientations_impl(cusift_ctx *ctx, const OctaveTable &T, cusift_point
   unsigned int *dup_count = reinterpret_cast<unsigned int *>(scratch + 2 * words);
   float q, inv_q;
   frac_consts(prm->tex_frac_bits, q, inv_q);
-  // describe_given_kernel's grid: as many workgroups as are resident at once, at most one per record slot
-  const bool flat = n_images <= kMaxFlatImages;
-  const long cap = flat ? (long)n_images * max_pts : (long)max_pts;
-  const long resident = flat ? (long)ctx->describe_grid : std::max(1L, (long)ctx->describe_grid / n_images);
-  const dim3 grid((unsigned int)std::max(1L, std::min(cap, resident)), flat ? 1u : (unsigned int)n_images);
+  const dim3 grid = describe_walk_grid(ctx, n_images, max_pts);
   hipLaunchKernelGGL(second_peak_kernel, grid, dim3(64), 0, ctx->stream, T, (const cusift_point *)d_points, max_pts,
                      (const unsigned int *)d_counters, n_images, q, inv_q, ratio, flags, marks);
   TRY(check_launch("second_peak"));

@@ -588,7 +588,7 @@ BANDS = ((0, 32), (24, 56), (48, 80))
 
 
 def band_radius(oracle, scale, ori):
-    """descriptors_kernel's footprint radius, restated: fmaxf(7.5 (12/16 scale) (|sin| + |cos|), 6) + 2.5 at
+    """band_footprint_cut()'s radius (sift_keypoints.hip), restated: fmaxf(7.5 (12/16 scale) (|sin| + |cos|), 6) + 2.5 at
     theta = 2 * 3.1415 / 360 * orientation, with the kernels' own sincosf (sift_math.h, which the oracle compiles too)."""
     theta = (F(2.0) * F(3.1415) / F(360.0) * np.asarray(ori, dtype=np.float32)).astype(np.float32)
     sn, cs = oracle.math_eval("sincos", theta)

@@ -179,7 +179,7 @@ def test_every_border_of_every_tiled_octave_has_keypoints_on_both_sides(oracle, 
 
 @pytest.mark.parametrize("name,seed", [("two", None), ("three", None), ("three", THREE_B), ("narrow", None)])
 def test_footprints_stay_inside_the_halo_by_the_restated_reach(oracle, name, seed):
-    """The flag condition of descriptors_kernel (sift_keypoints.hip:990-992) and describe_bands_kernel (:1367-1369):
+    """The flag condition of descriptors_kernel and describe_bands_kernel, band_footprint_cut() of sift_keypoints.hip:
 
         r = fmaxf(7.5f * (12.0f / 16.0f * kscale) * (|sin| + |cos|), 6.0f) + 2.5f
         cut = (row0 > 0 && !(py - r >= row0)) || (row0 + h < hg && !(py + r <= row0 + h - 1))
