@@ -7,6 +7,8 @@
 //                     calibrated pose, planar and epipolar registration on one chain, the absolute pose, the pair-list forms
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_match8.hip   8-bit descriptors: the quantiser, the int8-MFMA matcher, their entry points (a unit of its own)
+//   sift_match_common.h  device code of both matchers (sift_match.hip, sift_match8.hip): write-out, pair-list frame,
+//                     fold of the partials, the "partial or final" sink
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
 //                     recorded graph, the single-image entry points, cusift_ctx_reserve
 //   sift_describe.hip cusift_describe_batch: the pyramid (describe_pyramid) and describe_given_kernel for caller-supplied
@@ -407,8 +409,44 @@ static int grow_scratch(cusift_ctx *ctx, T *&ptr, size_t &have, size_t bytes, co
 int enter(cusift_ctx *ctx);
 int check_launch(const char *what);
 int ensure_arena(cusift_ctx *ctx, size_t bytes);
-// sift_register.hip: what every pair-list call refuses of its batch shape and its list (sift_tracks.hip shares it)
+// sift_register.hip: what every pair-list call refuses of its batch shape and its list (sift_tracks.hip shares it), and
+// two refusals of the matchers (sift_match8.hip shares them): the distance, and record ranges that a mutual matcher
+// writes both of
 int check_pair_list(const int *h_pairs, int n_pairs, int n_images, int max_pts, const char *who);
+int check_distance(const char *who, int distance);
+int check_disjoint(const char *who, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2);
+
+// The shape of a brute-force matcher as its split plan sees it.
+struct MatcherShape {
+  int rows_per_block;  // rows of set 1 per workgroup
+  int tile_cols;       // columns of set 2 per LDS tile
+  int wgs_per_cu;      // workgroups per CU the grid aims at
+  int col_bytes;       // bytes per column behind a split's buffer resource (32-bit byte offsets)
+  const char *who;     // in the error text
+};
+constexpr MatcherShape kMatcher32{64, 32, 4, (int)sizeof(cusift_point), "MatchSiftData"};  // sift_match.hip
+constexpr MatcherShape kMatcher8{256, 64, 2, 128, "Match8"};                                // sift_match8.hip
+
+// The column splits of a matcher over n_pairs pairs (a batch: sized from max_pts, the counts stay on the device): aim at
+// >= wgs_per_cu workgroups per CU over all pairs, keep >= 4 LDS tiles per split.  CUSIFT_POLICY_MATCH_SPLITS = k > 0: k
+// splits, at most one per tile.  A split is a whole number of tiles and spans less than 2^31 bytes (3.65 M of the
+// 588-byte records) -- more columns than that force further splits (never a batch: max_pts <= 2^20).
+static inline int matcher_split_plan(const cusift_ctx *ctx, const MatcherShape &shape, int num_pts1, int num_pts2,
+                                     int n_pairs, int *splits_out, int *cols_per_split_out) {
+  const int tile = shape.tile_cols;
+  const long blocks = (long)idiv_up(num_pts1, shape.rows_per_block) * n_pairs;
+  int splits = (int)std::max(1L, std::min(((long)shape.wgs_per_cu * ctx->num_cus + blocks - 1) / blocks,
+                                          (long)idiv_up(num_pts2, 4 * tile)));
+  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, tile));
+  splits = std::min(splits, 65535);
+  const int max_cols_per_split = (int)((0x7fffffffu / (unsigned int)shape.col_bytes) / tile * tile);
+  splits = std::max(splits, idiv_up(num_pts2, max_cols_per_split));
+  if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "%s: too many records in set 2 (%d)", shape.who, num_pts2);
+  const int cols_per_split = idiv_up(idiv_up(num_pts2, splits), tile) * tile;
+  *splits_out = idiv_up(num_pts2, cols_per_split);
+  *cols_per_split_out = cols_per_split;
+  return CUSIFT_OK;
+}
 // sift_match8.hip, for the registrations' matcher fronts (sift_register.hip)
 int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
                         int distance, cusift_point *d_back);

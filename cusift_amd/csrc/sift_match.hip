@@ -16,8 +16,11 @@
 // Numerics: the reference sums pt1[k]*pt2[k] starting at k = (p2 mod 16) and wrapping; the MFMA chain visits k in
 // the order 16u+j, 16u+4+j, 16u+8+j, 16u+12+j (u = 0..7, j = 0..3).  Scores agree to ~1e-7; indices agree except
 // for exact-score near-ties (tests bound both).
-#include "sift_device.h"
-
+//
+// Every main kernel is match_block (below) between its frame and its sinks: one text, so that a (row, column) dot
+// product is the same chain whichever kernel computes it.  The write-out, the pair-list frame, the fold of the merge
+// kernels and the "partial or final" sink are sift_match_common.h's, shared with the 8-bit matcher.
+#include "sift_match_common.h"
 
 namespace cusift {
 
@@ -42,21 +45,19 @@ __device__ __forceinline__ void top2_scan(float &best, float &second, int &idx, 
   }
 }
 
-// the 1e-6 is a double constant in the reference (extras/matching.cu:143,222): evaluate in double, store float
-__device__ __forceinline__ float match_ambiguity(float best, float second, bool l2) {
-  return l2 ? (float)(best / (second + 1e-6)) : (float)((1 - best) / (1 - second + 1e-6));
+// The triple (ob, os, oi) of the columns (or rows) that lie above this triple's, merged into it: the step of the tree
+// over the lanes and of every fold over splits, waves and row blocks.  The comparisons are strict, so an exactly tied
+// best keeps the lower index.
+__device__ __forceinline__ void top2_merge(float &best, float &second, int &idx, float ob, float os, int oi, bool l2) {
+  top2_scan(best, second, idx, ob, oi, l2);
+  if (beats(os, second, l2)) second = os;
 }
-
-// the tail of FindMinCorr/FindMaxCorr (extras/matching.cu:140-150,220-229): the five fields MatchSiftData fills
-__device__ __forceinline__ void write_match(cusift_point *pt, const cusift_point *__restrict__ sift2, int n2,
-                                            float best, float second, int idx, bool l2) {
-  pt->score = best;
-  pt->ambiguity = match_ambiguity(best, second, l2);
-  pt->match = idx;
-  const int m = (idx >= 0 && idx < n2) ? idx : 0;  // the reference reads sift2[-1] here
-  pt->match_xpos = sift2[m].coords2D[0];
-  pt->match_ypos = sift2[m].coords2D[1];
-}
+struct Top2Merge {  // as fold_partials' merge step
+  bool l2;
+  __device__ __forceinline__ void operator()(MatchPartial &m, const MatchPartial &o) const {
+    top2_merge(m.best, m.second, m.idx, o.best, o.second, o.idx, l2);
+  }
+};
 
 // 16-byte loads from the 588-byte records: descriptors are only 4-byte aligned
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -72,7 +73,20 @@ __device__ __forceinline__ void top2_update(float &best, float &second, int &idx
   best = win ? val : best;
 }
 
-// The column side of a tile as match_tile.inc sees it: tile() once a tile's scores are in the accumulators, drain() for
+// The two sinks of the main kernels (partial_or, sift_match_common.h): the triple of record i of `dst` against the
+// records `other`, and of row i of a pair's row array.
+template <bool kL2>
+__device__ __forceinline__ auto point_sink(MatchPartial *partials, size_t slab, cusift_point *dst,
+                                           const cusift_point *other, int n_other) {
+  return partial_or(partials, slab,
+                    [=](int i, float b, float s, int idx) { write_match(dst + i, other, n_other, b, s, idx, kL2); });
+}
+template <bool kL2>
+__device__ __forceinline__ auto row_sink(MatchPartial *partials, size_t slab, cusift_match_row *rows) {
+  return partial_or(partials, slab, [=](int i, float b, float s, int idx) { write_match_row(rows + i, b, s, idx, kL2); });
+}
+
+// The column side of a tile as match_block sees it: tile() once a tile's scores are in the accumulators, drain() for
 // the previous tile behind the next tile's barriers, finish() behind the loop.  NoColumnSide is the one-directional
 // kernels': every call is an empty inline function.  ColumnSide (cusift_match_mutual) is defined with its kernels below.
 struct NoColumnSide {
@@ -84,7 +98,7 @@ struct NoColumnSide {
   __device__ __forceinline__ void finish(A...) const {}
 };
 
-// The geometric predicate of a tile as match_tile.inc sees it: rows() before the column loop, fetch() / store() beside
+// The geometric predicate of a tile as match_block sees it: rows() before the column loop, fetch() / store() beside
 // the descriptors' staging, column() and pass() in the update.  NoGuide is every unguided kernel's: empty inline
 // functions and a test that is always true.  GuideH / GuideF (cusift_match_guided) are defined with their kernels below.
 struct NoGuide {
@@ -102,6 +116,143 @@ struct NoGuide {
   __device__ __forceinline__ bool pass(int, Column) const { return true; }
 };
 
+// One workgroup's 64 rows [blockIdx.x * 64 ..) of (sift1, n1) -- descriptors p1_base .. p1_base + 15 in each wave --
+// against the columns [col_begin, col_end) of sift2, through the LDS tile sB.  out(row, best, second, idx) receives every
+// row < n1 once.
+// `cols` is the column side: NoColumnSide in the one-directional kernels, whose three calls below are empty inline
+// functions -- no barrier, no LDS, no register (tools/kernel_regs.py: 96 VGPRs, 16,896 B); ColumnSide in the mutual
+// kernels.
+// `guide` is the geometric predicate of the guided kernels: NoGuide everywhere else, again nothing but empty inline
+// functions; GuideH / GuideF keep the per-row terms of this lane's rows 4g + q in registers (rows()), stage coords2D of
+// a tile's 32 columns into floats 128..129 of the columns' LDS rows (fetch() / store(), the descriptors' range-checked
+// buffer resource, no new LDS) and turn a (row, column) that fails the test into kInit in the update.
+template <bool kL2, class Cols, class Guide, class Out>
+__device__ __forceinline__ void match_block(const cusift_point *sift1, int n1, const cusift_point *sift2, int col_begin,
+                                            int col_end, float *sB, const Cols cols, Guide guide, const Out out) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;  // also what a masked column scores: it changes nothing
+
+  // A fragments: lane (r, g) holds elements 16u + 4g + j of descriptor p1_base + r (u = 0..7, j = 0..3)
+  float a[8][4];
+  {
+    const float *d1 = sift1[min(p1_base + r, n1 - 1)].data;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const f4u v = *reinterpret_cast<const f4u *>(d1 + 16 * u + 4 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[u][j] = v[j];
+    }
+  }
+  // running top-2 of rows 4g + q for the columns this lane sees (p2 = r mod 16): reference thread tx = r
+  float best[4], second[4];
+  int bidx[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    best[q] = second[q] = kInit;
+    bidx[q] = -1;
+  }
+  guide.rows(sift1, n1, p1_base, lane);
+
+  // staging: thread t moves four 16-byte chunks per tile; chunk c = t + 256 i -> descriptor c >> 5, floats 4 (c & 31).
+  // Raw buffer loads from a descriptor based at this split's first column: the lane offset is computed once, the tile
+  // and the chunk row advance in the scalar offset, and columns past col_end read as 0 (their scores are masked below;
+  // padded columns, extras/matching.cu:57, can never win: they are skipped).
+  const __amdgpu_buffer_rsrc_t rsrc2 = __builtin_amdgcn_make_buffer_rsrc(
+      (void *)(sift2 + col_begin), 0, (int)((col_end > col_begin ? col_end - col_begin : 0) * sizeof(cusift_point)),
+      kBufFlags);
+  constexpr int kRec = (int)sizeof(cusift_point);
+  const int voff = (int)(threadIdx.x >> 5) * kRec + (int)offsetof(cusift_point, data) + 16 * (int)(threadIdx.x & 31);
+  u4 stage[4];
+  auto fetch = [&](int c0) {
+    const int soff = __builtin_amdgcn_readfirstlane((c0 - col_begin) * kRec);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) stage[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc2, voff, soff + 8 * i * kRec, 0);
+    guide.fetch(rsrc2, soff);
+  };
+  if (col_begin < col_end) fetch(col_begin);
+  const float *brow = sB + r * kBStride + 4 * g;
+  for (int c0 = col_begin; c0 < col_end; c0 += kMatchTileCols) {
+    __syncthreads();  // the previous tile has been consumed
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = threadIdx.x + 256 * i;
+      *reinterpret_cast<u4 *>(sB + (c >> 5) * kBStride + 4 * (c & 31)) = stage[i];
+    }
+    guide.store(sB);
+    __syncthreads();
+    if (c0 + kMatchTileCols < col_end) fetch(c0 + kMatchTileCols);  // in flight while this tile is multiplied
+    if (c0 > col_begin) cols.drain(c0 - kMatchTileCols, col_begin, col_end, lane, wv);  // the previous tile's columns
+    // this lane's two columns' coordinates, read in front of the MFMAs so that the update does not wait for LDS
+    const auto xy2a = guide.column(sB, r), xy2b = guide.column(sB, 16 + r);
+
+    // two independent 16x16 accumulators (columns c0 + r and c0 + 16 + r), each a k-ordered chain; the B fragments
+    // of step u + 1 are read from LDS before the MFMAs of step u are issued
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    __builtin_amdgcn_s_setprio(1);  // a wave with MFMAs to issue goes before its SIMD's waves that are in the update
+    f4 b0 = *reinterpret_cast<const f4 *>(brow);
+    f4 b1 = *reinterpret_cast<const f4 *>(brow + 16 * kBStride);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      f4 n0 = b0, n1v = b1;
+      if (u < 7) {
+        n0 = *reinterpret_cast<const f4 *>(brow + 16 * (u + 1));
+        n1v = *reinterpret_cast<const f4 *>(brow + 16 * kBStride + 16 * (u + 1));
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b0[j], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b1[j], acc1, 0, 0, 0);
+      }
+      b0 = n0;
+      b1 = n1v;
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // acc[q] = <descriptor p1_base + 4g + q, descriptor p2>.  (Deferring this update into the next tile's MFMA gaps
+    // -- one score per step u -- was built and measured: no change, 110-112 TFLOP/s at 16k either way.)
+    {
+      const bool full = c0 + kMatchTileCols <= col_end;  // wave-uniform: only a split's last tile can be partial
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int p2 = c0 + 16 * t + r;
+        const bool live = full || p2 < col_end;
+        const auto xy2 = t ? xy2b : xy2a;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float dot = t ? acc1[q] : acc0[q];
+          // ComputeL2Distance :71-72, 2 - 2*dot (2*dot is exact, so the fused form has the same bits)
+          float val = kL2 ? (dot > -1.0f ? __builtin_fmaf(-2.0f, dot, 2.0f) : kMatchFltMax) : dot;
+          // `live` stays in the condition: a column past col_end reads as zeros, and (0, 0) can pass a guide
+          val = (live && guide.pass(q, xy2)) ? val : kInit;
+          top2_update<kL2>(best[q], second[q], bidx[q], val, p2);
+        }
+      }
+    }
+    cols.tile(c0, col_begin, acc0, acc1, p1_base, lane, wv);
+  }
+  cols.finish(col_begin, col_end, lane, wv);
+  // tree over tx = r (extras/matching.cu:122-138,201-218): lane r < len takes lane r + len; ties keep the lower r
+#pragma unroll
+  for (int len = 8; len > 0; len >>= 1) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float ob = __shfl_down(best[q], len, 16);
+      const float os = __shfl_down(second[q], len, 16);
+      const int oi = __shfl_down(bidx[q], len, 16);
+      if (r < len) top2_merge(best[q], second[q], bidx[q], ob, os, oi, kL2);
+    }
+  }
+  if (r == 0) {  // lane r == 0 of every 16-lane group g holds rows p1_base + 4 g + q
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int p1 = p1_base + 4 * g + q;
+      if (p1 < n1) out(p1, best[q], second[q], bidx[q]);
+    }
+  }
+}
+
 // One workgroup = 64 descriptors of image 1 (16 per wave) x one contiguous range of image 2's columns
 // (blockIdx.y = column split; the host picks the number of splits so that the grid fills 256 CUs even for a few
 // thousand keypoints).  With one split the kernel writes the final fields; otherwise the (best, second, index)
@@ -112,33 +263,9 @@ __global__ void __launch_bounds__(256) match_kernel(cusift_point *__restrict__ s
                                                    int cols_per_split, MatchPartial *__restrict__ partials,
                                                    int n1_pad) {
   __shared__ float sB[kMatchTileCols * kBStride];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
   const int col_begin = blockIdx.y * cols_per_split;
-  const int col_end = min(col_begin + cols_per_split, n2);  // padded columns (:57) can never win: skip them
-  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;       // also what a masked column scores: it changes nothing
-  const NoColumnSide cols;
-  const NoGuide guide;
-
-#include "match_tile.inc"
-  if (r == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p1 = p1_base + 4 * g + q;
-      if (p1 >= n1) continue;
-      if (partials) {
-        MatchPartial mp;
-        mp.best = best[q];
-        mp.second = second[q];
-        mp.idx = bidx[q];
-        partials[(size_t)blockIdx.y * n1_pad + p1] = mp;
-      } else {
-        write_match(sift1 + p1, sift2, n2, best[q], second[q], bidx[q], kL2);
-      }
-    }
-  }
+  match_block<kL2>(sift1, n1, sift2, col_begin, min(col_begin + cols_per_split, n2), sB, NoColumnSide{}, NoGuide{},
+                   point_sink<kL2>(partials, (size_t)blockIdx.y * n1_pad, sift1, sift2, n2));
 }
 
 template __global__ void match_kernel<false>(cusift_point *, int, const cusift_point *, int, int, MatchPartial *, int);
@@ -152,33 +279,14 @@ __global__ void __launch_bounds__(256) match_merge_kernel(cusift_point *__restri
   const bool l2 = l2_mode != 0;
   const int p1 = blockIdx.x * 256 + threadIdx.x;
   if (p1 >= n1) return;
-  MatchPartial m = partials[p1];
-  for (int s = 1; s < n_splits; ++s) {
-    const MatchPartial o = partials[(size_t)s * n1_pad + p1];
-    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
-    if (beats(o.second, m.second, l2)) m.second = o.second;
-  }
+  const MatchPartial m = fold_partials(partials + p1, n1_pad, n_splits, Top2Merge{l2});
   write_match(sift1 + p1, sift2, n2, m.best, m.second, m.idx, l2);
 }
 
 // ---- the same matcher over a pair list (cusift_match_batch) -----------------------------------------------------------
-// points[n_images][max_pts] + counters[n_images] as cusift_extract_batch leaves them; pairs[p] = (frame 1, frame 2).
-// A workgroup is (row block, column split, pair): blockIdx.z picks the pair, the two record counts come from device
-// memory (clamped to max_pts like rgbd_lift_kernel's), and a workgroup without rows or without columns returns before
-// it loads a record.  The grid is sized from max_pts because the host does not know the counts.  Results go to
-// rows[pair][max_pts] (score, ambiguity, match: write_match's arithmetic), never into the records, so that a frame can
-// be the first member of any number of pairs.  Rows past frame 1's count are not written; a pair whose frame 2 is empty
-// writes no row at all.
-__device__ __forceinline__ void write_match_row(cusift_match_row *__restrict__ row, float best, float second, int idx,
-                                                bool l2) {
-  f4 v;
-  v[0] = best;
-  v[1] = match_ambiguity(best, second, l2);
-  v[2] = __int_as_float(idx);
-  v[3] = 0.0f;  // reserved
-  *reinterpret_cast<f4 *>(row) = v;
-}
-
+// A workgroup is (row block, column split, pair) of PairFrame (sift_match_common.h); one without rows or without columns
+// returns before it loads a record.  Results go to rows[pair][max_pts], never into the records.  Rows past frame 1's
+// count are not written; a pair whose frame 2 is empty writes no row at all.
 // partials[pair][split][n1_pad]; NULL with one split: the rows are final
 template <bool kL2>
 __global__ void __launch_bounds__(256) match_batch_kernel(const cusift_point *__restrict__ points,
@@ -187,39 +295,12 @@ __global__ void __launch_bounds__(256) match_batch_kernel(const cusift_point *__
                                                          MatchPartial *__restrict__ partials, int n1_pad,
                                                          cusift_match_row *__restrict__ rows) {
   __shared__ float sB[kMatchTileCols * kBStride];
-  const int pair = blockIdx.z;
-  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
-  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
-  const int col_begin = blockIdx.y * cols_per_split;
-  if ((int)blockIdx.x * kMatchRowsPerBlock >= n1 || col_begin >= n2) return;  // uniform: no rows or no columns
-  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
-  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
-  const int col_end = min(col_begin + cols_per_split, n2);
-  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
-  const NoColumnSide cols;
-  const NoGuide guide;
-
-#include "match_tile.inc"
-  if (r == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p1 = p1_base + 4 * g + q;
-      if (p1 >= n1) continue;
-      if (partials) {
-        MatchPartial mp;
-        mp.best = best[q];
-        mp.second = second[q];
-        mp.idx = bidx[q];
-        partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = mp;
-      } else {
-        write_match_row(rows + (size_t)pair * max_pts + p1, best[q], second[q], bidx[q], kL2);
-      }
-    }
-  }
+  const PairFrame fr(counters, pairs, max_pts, cols_per_split, kMatchRowsPerBlock);
+  if (fr.empty) return;
+  match_block<kL2>(points + (size_t)fr.f1 * max_pts, fr.n1, points + (size_t)fr.f2 * max_pts, fr.col_begin, fr.col_end,
+                   sB, NoColumnSide{}, NoGuide{},
+                   row_sink<kL2>(partials, ((size_t)fr.pair * gridDim.y + blockIdx.y) * n1_pad,
+                                 rows + (size_t)fr.pair * max_pts));
 }
 
 template __global__ void match_batch_kernel<false>(const cusift_point *, const unsigned int *, int, const int *, int,
@@ -234,24 +315,18 @@ __global__ void __launch_bounds__(256) match_batch_merge_kernel(const unsigned i
                                                                const MatchPartial *__restrict__ partials, int n1_pad,
                                                                int n_splits, cusift_match_row *__restrict__ rows) {
   const bool l2 = l2_mode != 0;
-  const int pair = blockIdx.y;
-  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const PairCounts pc(blockIdx.y, counters, pairs, max_pts);
   const int p1 = blockIdx.x * 256 + threadIdx.x;
-  if (p1 >= n1 || n2 <= 0) return;
-  const int live = min(n_splits, (n2 + cols_per_split - 1) / cols_per_split);  // the others wrote nothing
-  const MatchPartial *__restrict__ mine = partials + (size_t)pair * n_splits * n1_pad + p1;
-  MatchPartial m = mine[0];
-  for (int s = 1; s < live; ++s) {
-    const MatchPartial o = mine[(size_t)s * n1_pad];
-    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
-    if (beats(o.second, m.second, l2)) m.second = o.second;
-  }
-  write_match_row(rows + (size_t)pair * max_pts + p1, m.best, m.second, m.idx, l2);
+  if (p1 >= pc.n1 || pc.n2 <= 0) return;
+  const int live = min(n_splits, (pc.n2 + cols_per_split - 1) / cols_per_split);  // the others wrote nothing
+  const MatchPartial m =
+      fold_partials(partials + (size_t)pc.pair * n_splits * n1_pad + p1, n1_pad, live, Top2Merge{l2});
+  write_match_row(rows + (size_t)pc.pair * max_pts + p1, m.best, m.second, m.idx, l2);
 }
 
 // ---- both directions from one pass (cusift_match_mutual, cusift_match_batch_mutual) -----------------------------------
 // The row side is match_kernel's, from the same text.  The column side -- for every descriptor of image 2 the best and
-// second best of image 1 -- is reduced from the same accumulators (match_tile.inc's `cols`) and is defined by
+// second best of image 1 -- is reduced from the same accumulators (match_block's `cols`) and is defined by
 // a plain model: top2_scan over the rows 0 .. n1 - 1 in ascending order from (kInit, kInit, -1).  Best and second of that
 // scan do not depend on the order in which partial scans are merged, the index does: every merge takes the lower rows
 // first and compares strictly, so an exactly tied best keeps the LOWEST row, whatever the grid.  Column splits
@@ -263,13 +338,14 @@ __global__ void __launch_bounds__(256) match_batch_merge_kernel(const unsigned i
 // -- and leaves 32 triples in LDS (two buffers, by tile parity); behind the next tile's barriers eight lanes of every
 // wave fold the four waves of a column and hand it to `out`.  A buffer is written again two tiles later, behind a
 // barrier that every wave reaches only after its drain.
-typedef float ColFloats[4][kMatchTileCols];  // [wave][column of the tile]
-typedef int ColInts[4][kMatchTileCols];
+struct ColumnTriples {  // [tile parity][wave][column of the tile]
+  float best[2][4][kMatchTileCols], second[2][4][kMatchTileCols];
+  int idx[2][4][kMatchTileCols];
+};
 
 template <bool kL2, class Out>
 struct ColumnSide {
-  ColFloats *best, *second;  // [2]: tile parity
-  ColInts *idx;
+  ColumnTriples *s;
   int n1;
   Out out;  // out(column, best, second, idx): the column's result over this workgroup's 64 rows
   static constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
@@ -296,13 +372,12 @@ struct ColumnSide {
         const float ob = __shfl_down(cb, d);
         const float os = __shfl_down(cs, d);
         const int oi = __shfl_down(ci, d);
-        top2_scan(cb, cs, ci, ob, oi, kL2);
-        if (beats(os, cs, kL2)) cs = os;
+        top2_merge(cb, cs, ci, ob, os, oi, kL2);
       }
       if (g == 0) {
-        best[par][wv][16 * t + r] = cb;
-        second[par][wv][16 * t + r] = cs;
-        idx[par][wv][16 * t + r] = ci;
+        s->best[par][wv][16 * t + r] = cb;
+        s->second[par][wv][16 * t + r] = cs;
+        s->idx[par][wv][16 * t + r] = ci;
       }
     }
   }
@@ -312,14 +387,10 @@ struct ColumnSide {
     const int j = 8 * wv + lane, col = c_prev + j;
     if (lane < 8 && col < col_end) {
       const int par = ((c_prev - col_begin) / kMatchTileCols) & 1;
-      float cb = best[par][0][j], cs = second[par][0][j];
-      int ci = idx[par][0][j];
+      float cb = s->best[par][0][j], cs = s->second[par][0][j];
+      int ci = s->idx[par][0][j];
 #pragma unroll
-      for (int w = 1; w < 4; ++w) {
-        top2_scan(cb, cs, ci, best[par][w][j], idx[par][w][j], kL2);
-        const float os = second[par][w][j];
-        if (beats(os, cs, kL2)) cs = os;
-      }
+      for (int w = 1; w < 4; ++w) top2_merge(cb, cs, ci, s->best[par][w][j], s->second[par][w][j], s->idx[par][w][j], kL2);
       out(col, cb, cs, ci);
     }
   }
@@ -331,52 +402,22 @@ struct ColumnSide {
     drain(col_begin + (col_end - col_begin - 1) / kMatchTileCols * kMatchTileCols, col_begin, col_end, lane, wv);
   }
 };
+template <bool kL2, class Out>
+__device__ __forceinline__ ColumnSide<kL2, Out> column_side(ColumnTriples *s, int n1, Out out) {
+  return ColumnSide<kL2, Out>{s, n1, out};
+}
 
 template <bool kL2>
 __global__ void __launch_bounds__(256) match_mutual_kernel(cusift_point *sift1, int n1, cusift_point *sift2, int n2,
                                                           int cols_per_split, MatchPartial *__restrict__ partials,
                                                           int n1_pad, MatchPartial *__restrict__ col_partials) {
   __shared__ float sB[kMatchTileCols * kBStride];
-  __shared__ ColFloats sColBest[2], sColSecond[2];
-  __shared__ ColInts sColIdx[2];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
+  __shared__ ColumnTriples sCols;
   const int col_begin = blockIdx.y * cols_per_split;
-  const int col_end = min(col_begin + cols_per_split, n2);
-  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
-  auto col_out = [&](int col, float cb, float cs, int ci) {
-    if (col_partials) {
-      MatchPartial mp;
-      mp.best = cb;
-      mp.second = cs;
-      mp.idx = ci;
-      col_partials[(size_t)blockIdx.x * n2 + col] = mp;
-    } else {
-      write_match(sift2 + col, sift1, n1, cb, cs, ci, kL2);
-    }
-  };
-  const ColumnSide<kL2, decltype(col_out)> cols{sColBest, sColSecond, sColIdx, n1, col_out};
-  const NoGuide guide;
-
-#include "match_tile.inc"
-  if (r == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p1 = p1_base + 4 * g + q;
-      if (p1 >= n1) continue;
-      if (partials) {
-        MatchPartial mp;
-        mp.best = best[q];
-        mp.second = second[q];
-        mp.idx = bidx[q];
-        partials[(size_t)blockIdx.y * n1_pad + p1] = mp;
-      } else {
-        write_match(sift1 + p1, sift2, n2, best[q], second[q], bidx[q], kL2);
-      }
-    }
-  }
+  match_block<kL2>(
+      sift1, n1, sift2, col_begin, min(col_begin + cols_per_split, n2), sB,
+      column_side<kL2>(&sCols, n1, point_sink<kL2>(col_partials, (size_t)blockIdx.x * n2, sift2, sift1, n1)), NoGuide{},
+      point_sink<kL2>(partials, (size_t)blockIdx.y * n1_pad, sift1, sift2, n2));
 }
 
 template __global__ void match_mutual_kernel<false>(cusift_point *, int, cusift_point *, int, int, MatchPartial *, int,
@@ -392,12 +433,7 @@ __global__ void __launch_bounds__(256) match_mutual_merge_kernel(cusift_point *s
   const bool l2 = l2_mode != 0;
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n2) return;
-  MatchPartial m = col_partials[j];
-  for (int b = 1; b < row_blocks; ++b) {
-    const MatchPartial o = col_partials[(size_t)b * n2 + j];
-    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
-    if (beats(o.second, m.second, l2)) m.second = o.second;
-  }
+  const MatchPartial m = fold_partials(col_partials + j, n2, row_blocks, Top2Merge{l2});
   write_match(sift2 + j, sift1, n1, m.best, m.second, m.idx, l2);
 }
 
@@ -412,52 +448,16 @@ __global__ void __launch_bounds__(256) match_batch_mutual_kernel(const cusift_po
                                                                 MatchPartial *__restrict__ col_partials,
                                                                 cusift_match_row *__restrict__ rows_back) {
   __shared__ float sB[kMatchTileCols * kBStride];
-  __shared__ ColFloats sColBest[2], sColSecond[2];
-  __shared__ ColInts sColIdx[2];
-  const int pair = blockIdx.z;
-  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
-  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
-  const int col_begin = blockIdx.y * cols_per_split;
-  if ((int)blockIdx.x * kMatchRowsPerBlock >= n1 || col_begin >= n2) return;  // uniform: no rows or no columns
-  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
-  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
-  const int col_end = min(col_begin + cols_per_split, n2);
-  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
-  auto col_out = [&](int col, float cb, float cs, int ci) {
-    if (col_partials) {
-      MatchPartial mp;
-      mp.best = cb;
-      mp.second = cs;
-      mp.idx = ci;
-      col_partials[((size_t)pair * gridDim.x + blockIdx.x) * max_pts + col] = mp;
-    } else {
-      write_match_row(rows_back + (size_t)pair * max_pts + col, cb, cs, ci, kL2);
-    }
-  };
-  const ColumnSide<kL2, decltype(col_out)> cols{sColBest, sColSecond, sColIdx, n1, col_out};
-  const NoGuide guide;
-
-#include "match_tile.inc"
-  if (r == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p1 = p1_base + 4 * g + q;
-      if (p1 >= n1) continue;
-      if (partials) {
-        MatchPartial mp;
-        mp.best = best[q];
-        mp.second = second[q];
-        mp.idx = bidx[q];
-        partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = mp;
-      } else {
-        write_match_row(rows + (size_t)pair * max_pts + p1, best[q], second[q], bidx[q], kL2);
-      }
-    }
-  }
+  __shared__ ColumnTriples sCols;
+  const PairFrame fr(counters, pairs, max_pts, cols_per_split, kMatchRowsPerBlock);
+  if (fr.empty) return;
+  match_block<kL2>(
+      points + (size_t)fr.f1 * max_pts, fr.n1, points + (size_t)fr.f2 * max_pts, fr.col_begin, fr.col_end, sB,
+      column_side<kL2>(&sCols, fr.n1,
+                       row_sink<kL2>(col_partials, ((size_t)fr.pair * gridDim.x + blockIdx.x) * max_pts,
+                                     rows_back + (size_t)fr.pair * max_pts)),
+      NoGuide{},
+      row_sink<kL2>(partials, ((size_t)fr.pair * gridDim.y + blockIdx.y) * n1_pad, rows + (size_t)fr.pair * max_pts));
 }
 
 template __global__ void match_batch_mutual_kernel<false>(const cusift_point *, const unsigned int *, int, const int *,
@@ -475,19 +475,13 @@ __global__ void __launch_bounds__(256) match_batch_mutual_merge_kernel(const uns
                                                                       int row_blocks,
                                                                       cusift_match_row *__restrict__ rows_back) {
   const bool l2 = l2_mode != 0;
-  const int pair = blockIdx.y;
-  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const PairCounts pc(blockIdx.y, counters, pairs, max_pts);
   const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n2 || n1 <= 0) return;
-  const int live = min(row_blocks, (n1 + kMatchRowsPerBlock - 1) / kMatchRowsPerBlock);  // the others wrote nothing
-  const MatchPartial *__restrict__ mine = col_partials + (size_t)pair * row_blocks * max_pts + j;
-  MatchPartial m = mine[0];
-  for (int b = 1; b < live; ++b) {
-    const MatchPartial o = mine[(size_t)b * max_pts];
-    top2_scan(m.best, m.second, m.idx, o.best, o.idx, l2);
-    if (beats(o.second, m.second, l2)) m.second = o.second;
-  }
-  write_match_row(rows_back + (size_t)pair * max_pts + j, m.best, m.second, m.idx, l2);
+  if (j >= pc.n2 || pc.n1 <= 0) return;
+  const int live = min(row_blocks, (pc.n1 + kMatchRowsPerBlock - 1) / kMatchRowsPerBlock);  // the others wrote nothing
+  const MatchPartial m =
+      fold_partials(col_partials + (size_t)pc.pair * row_blocks * max_pts + j, max_pts, live, Top2Merge{l2});
+  write_match_row(rows_back + (size_t)pc.pair * max_pts + j, m.best, m.second, m.idx, l2);
 }
 
 // ---- nearest neighbours under a known H or F (cusift_match_guided, cusift_match_batch_guided) ------------------------
@@ -583,35 +577,12 @@ __global__ void __launch_bounds__(256) match_guided_kernel(cusift_point *__restr
                                                           int cols_per_split, MatchPartial *__restrict__ partials,
                                                           int n1_pad, GuideModel model, float r2) {
   __shared__ float sB[kMatchTileCols * kBStride];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
   const int col_begin = blockIdx.y * cols_per_split;
-  const int col_end = min(col_begin + cols_per_split, n2);
-  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
-  const NoColumnSide cols;
   Guide guide;
   guide.m = model.m;
   guide.r2 = r2;
-
-#include "match_tile.inc"
-  if (r == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p1 = p1_base + 4 * g + q;
-      if (p1 >= n1) continue;
-      if (partials) {
-        MatchPartial mp;
-        mp.best = best[q];
-        mp.second = second[q];
-        mp.idx = bidx[q];
-        partials[(size_t)blockIdx.y * n1_pad + p1] = mp;
-      } else {
-        write_match(sift1 + p1, sift2, n2, best[q], second[q], bidx[q], kL2);
-      }
-    }
-  }
+  match_block<kL2>(sift1, n1, sift2, col_begin, min(col_begin + cols_per_split, n2), sB, NoColumnSide{}, guide,
+                   point_sink<kL2>(partials, (size_t)blockIdx.y * n1_pad, sift1, sift2, n2));
 }
 
 // match_batch_kernel with pair blockIdx.z's model from models[pair] (a device copy of the caller's array)
@@ -623,41 +594,15 @@ __global__ void __launch_bounds__(256) match_batch_guided_kernel(const cusift_po
                                                                 int n1_pad, cusift_match_row *__restrict__ rows,
                                                                 const GuideModel *__restrict__ models, float r2) {
   __shared__ float sB[kMatchTileCols * kBStride];
-  const int pair = blockIdx.z;
-  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
-  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
-  const int col_begin = blockIdx.y * cols_per_split;
-  if ((int)blockIdx.x * kMatchRowsPerBlock >= n1 || col_begin >= n2) return;  // uniform: no rows or no columns
-  const cusift_point *__restrict__ sift1 = points + (size_t)f1 * max_pts;
-  const cusift_point *__restrict__ sift2 = points + (size_t)f2 * max_pts;
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kMatchRowsPerBlock + wv * 16;
-  const int col_end = min(col_begin + cols_per_split, n2);
-  constexpr float kInit = kL2 ? kMatchFltMax : -1.0f;
-  const NoColumnSide cols;
+  const PairFrame fr(counters, pairs, max_pts, cols_per_split, kMatchRowsPerBlock);
+  if (fr.empty) return;
   Guide guide;
-  guide.m = models[pair].m;
+  guide.m = models[fr.pair].m;
   guide.r2 = r2;
-
-#include "match_tile.inc"
-  if (r == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p1 = p1_base + 4 * g + q;
-      if (p1 >= n1) continue;
-      if (partials) {
-        MatchPartial mp;
-        mp.best = best[q];
-        mp.second = second[q];
-        mp.idx = bidx[q];
-        partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = mp;
-      } else {
-        write_match_row(rows + (size_t)pair * max_pts + p1, best[q], second[q], bidx[q], kL2);
-      }
-    }
-  }
+  match_block<kL2>(points + (size_t)fr.f1 * max_pts, fr.n1, points + (size_t)fr.f2 * max_pts, fr.col_begin, fr.col_end,
+                   sB, NoColumnSide{}, guide,
+                   row_sink<kL2>(partials, ((size_t)fr.pair * gridDim.y + blockIdx.y) * n1_pad,
+                                 rows + (size_t)fr.pair * max_pts));
 }
 
 #define CUSIFT_GUIDED_KERNELS(kL2, Guide)                                                                               \

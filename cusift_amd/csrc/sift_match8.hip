@@ -34,7 +34,7 @@
 // C/D: col = lane & 15, row = 4 (lane >> 4) + reg.
 #include "sift_host.h"
 
-#include "sift_device.h"
+#include "sift_match_common.h"
 
 namespace cusift {
 
@@ -65,6 +65,11 @@ __device__ __forceinline__ void m8_merge(int &best, int &second, int &idx, int o
   best = min(best, ob);
   idx = take ? oi : idx;
 }
+struct M8Merge {  // as fold_partials' merge step
+  __device__ __forceinline__ void operator()(Match8Partial &m, const Match8Partial &o) const {
+    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
+  }
+};
 
 // what a row's term adds behind the scan
 template <bool kL2>
@@ -83,34 +88,32 @@ __device__ __forceinline__ void m8_floats(int best, int second, float &fb, float
   fs = second >= kM8None ? (kL2 ? kM8FltMax : -1.0f) : (kL2 ? (float)second * kM8Scale : (float)(-second) * kM8Scale);
 }
 
-// match_ambiguity of sift_match.hip, the reference's two expressions: the 1e-6 is a double
-__device__ __forceinline__ float m8_ambiguity(float best, float second, bool l2) {
-  return l2 ? (float)(best / (second + 1e-6)) : (float)((1 - best) / (1 - second + 1e-6));
-}
-
+// cusift_match's tail on them (sift_match_common.h): the five fields of a record, or a row of a pair's row array
 template <bool kL2>
 __device__ __forceinline__ void m8_write_point(cusift_point *pt, const cusift_point *__restrict__ sift2, int n2, int best,
                                                int second, int idx) {
   float fb, fs;
   m8_floats<kL2>(best, second, fb, fs);
-  pt->score = fb;
-  pt->ambiguity = m8_ambiguity(fb, fs, kL2);
-  pt->match = idx;
-  const int m = (idx >= 0 && idx < n2) ? idx : 0;  // as write_match
-  pt->match_xpos = sift2[m].coords2D[0];
-  pt->match_ypos = sift2[m].coords2D[1];
+  write_match(pt, sift2, n2, fb, fs, idx, kL2);
 }
-
 template <bool kL2>
 __device__ __forceinline__ void m8_write_row(cusift_match_row *__restrict__ row, int best, int second, int idx) {
   float fb, fs;
   m8_floats<kL2>(best, second, fb, fs);
-  f4 v;
-  v[0] = fb;
-  v[1] = m8_ambiguity(fb, fs, kL2);
-  v[2] = __int_as_float(idx);
-  v[3] = 0.0f;  // reserved
-  *reinterpret_cast<f4 *>(row) = v;
+  write_match_row(row, fb, fs, idx, kL2);
+}
+
+// The two sinks of the main kernels (partial_or, sift_match_common.h): the keys of record i of `dst` against the records
+// `other`, and of row i of a pair's row array.
+template <bool kL2>
+__device__ __forceinline__ auto m8_point_sink(Match8Partial *partials, size_t slab, cusift_point *dst,
+                                              const cusift_point *other, int n_other) {
+  return partial_or(partials, slab,
+                    [=](int i, int b, int s, int idx) { m8_write_point<kL2>(dst + i, other, n_other, b, s, idx); });
+}
+template <bool kL2>
+__device__ __forceinline__ auto m8_row_sink(Match8Partial *partials, size_t slab, cusift_match_row *rows) {
+  return partial_or(partials, slab, [=](int i, int b, int s, int idx) { m8_write_row<kL2>(rows + i, b, s, idx); });
 }
 
 // ---- the column side (cusift_match8_mutual, cusift_match8_batch_mutual) -------------------------------------------------
@@ -348,12 +351,8 @@ __global__ void __launch_bounds__(256) match8_kernel(cusift_point *__restrict__ 
   const int col_begin = blockIdx.y * cols_per_split;
   const int col_end = min(col_begin + cols_per_split, n2);
   if (col_begin >= col_end) return;  // uniform; the host sizes the splits so that this never happens
-  m8_block<kL2>(q1, sums1, n1, q2, sums2, col_begin, col_end, sB, [&](int p1, int b, int s, int i) {
-    if (partials)
-      partials[(size_t)blockIdx.y * n1_pad + p1] = Match8Partial{b, s, i, 0};
-    else
-      m8_write_point<kL2>(sift1 + p1, sift2, n2, b, s, i);
-  });
+  m8_block<kL2>(q1, sums1, n1, q2, sums2, col_begin, col_end, sB,
+                m8_point_sink<kL2>(partials, (size_t)blockIdx.y * n1_pad, sift1, sift2, n2));
 }
 template __global__ void match8_kernel<false>(cusift_point *, int, const unsigned char *, const int *, const cusift_point *,
                                               int, const unsigned char *, const int *, int, Match8Partial *, int);
@@ -367,16 +366,12 @@ __global__ void __launch_bounds__(256) match8_merge_kernel(cusift_point *__restr
                                                           int n_splits) {
   const int p1 = blockIdx.x * 256 + threadIdx.x;
   if (p1 >= n1) return;
-  Match8Partial m = partials[p1];
-  for (int s = 1; s < n_splits; ++s) {
-    const Match8Partial o = partials[(size_t)s * n1_pad + p1];
-    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
-  }
+  const Match8Partial m = fold_partials(partials + p1, n1_pad, n_splits, M8Merge{});
   m8_write_point<kL2>(sift1 + p1, sift2, n2, m.best, m.second, m.idx);
 }
 
-// The pair list: blockIdx.z picks the pair, the counts come from device memory (clamped to max_pts), the grid is sized
-// from max_pts.  A workgroup without rows or without columns returns before it loads a byte.
+// The pair list: a workgroup is (row block, column split, pair) of PairFrame (sift_match_common.h); one without rows or
+// without columns returns before it loads a byte.
 template <bool kL2>
 __global__ void __launch_bounds__(256) match8_batch_kernel(const unsigned char *__restrict__ q, const int *__restrict__ sums,
                                                           const unsigned int *__restrict__ counters, int max_pts,
@@ -384,19 +379,12 @@ __global__ void __launch_bounds__(256) match8_batch_kernel(const unsigned char *
                                                           Match8Partial *__restrict__ partials, int n1_pad,
                                                           cusift_match_row *__restrict__ rows) {
   __shared__ __attribute__((aligned(16))) unsigned char sB[2 * kM8TileCols * kM8Stride];
-  const int pair = blockIdx.z;
-  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
-  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
-  const int col_begin = blockIdx.y * cols_per_split;
-  if ((int)blockIdx.x * kM8RowsPerBlock >= n1 || col_begin >= n2) return;  // uniform
-  const int col_end = min(col_begin + cols_per_split, n2);
-  m8_block<kL2>(q + (size_t)f1 * max_pts * 128, sums + (size_t)f1 * max_pts * 2, n1, q + (size_t)f2 * max_pts * 128,
-                sums + (size_t)f2 * max_pts * 2, col_begin, col_end, sB, [&](int p1, int b, int s, int i) {
-                  if (partials)
-                    partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = Match8Partial{b, s, i, 0};
-                  else
-                    m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, b, s, i);
-                });
+  const PairFrame fr(counters, pairs, max_pts, cols_per_split, kM8RowsPerBlock);
+  if (fr.empty) return;
+  m8_block<kL2>(q + (size_t)fr.f1 * max_pts * 128, sums + (size_t)fr.f1 * max_pts * 2, fr.n1,
+                q + (size_t)fr.f2 * max_pts * 128, sums + (size_t)fr.f2 * max_pts * 2, fr.col_begin, fr.col_end, sB,
+                m8_row_sink<kL2>(partials, ((size_t)fr.pair * gridDim.y + blockIdx.y) * n1_pad,
+                                 rows + (size_t)fr.pair * max_pts));
 }
 template __global__ void match8_batch_kernel<false>(const unsigned char *, const int *, const unsigned int *, int,
                                                     const int *, int, Match8Partial *, int, cusift_match_row *);
@@ -409,18 +397,12 @@ __global__ void __launch_bounds__(256) match8_batch_merge_kernel(const unsigned 
                                                                 const int *__restrict__ pairs, int cols_per_split,
                                                                 const Match8Partial *__restrict__ partials, int n1_pad,
                                                                 int n_splits, cusift_match_row *__restrict__ rows) {
-  const int pair = blockIdx.y;
-  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const PairCounts pc(blockIdx.y, counters, pairs, max_pts);
   const int p1 = blockIdx.x * 256 + threadIdx.x;
-  if (p1 >= n1 || n2 <= 0) return;
-  const int live = min(n_splits, (n2 + cols_per_split - 1) / cols_per_split);  // the others wrote nothing
-  const Match8Partial *__restrict__ mine = partials + (size_t)pair * n_splits * n1_pad + p1;
-  Match8Partial m = mine[0];
-  for (int s = 1; s < live; ++s) {
-    const Match8Partial o = mine[(size_t)s * n1_pad];
-    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
-  }
-  m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, m.best, m.second, m.idx);
+  if (p1 >= pc.n1 || pc.n2 <= 0) return;
+  const int live = min(n_splits, (pc.n2 + cols_per_split - 1) / cols_per_split);  // the others wrote nothing
+  const Match8Partial m = fold_partials(partials + (size_t)pc.pair * n_splits * n1_pad + p1, n1_pad, live, M8Merge{});
+  m8_write_row<kL2>(rows + (size_t)pc.pair * max_pts + p1, m.best, m.second, m.idx);
 }
 
 // ---- both directions from one pass ---------------------------------------------------------------------------------------
@@ -438,21 +420,10 @@ __global__ void __launch_bounds__(256) match8_mutual_kernel(cusift_point *sift1,
   const int col_begin = blockIdx.y * cols_per_split;
   const int col_end = min(col_begin + cols_per_split, n2);
   if (col_begin >= col_end) return;  // uniform; the host sizes the splits so that this never happens
-  auto col_out = [&](int col, int b, int s, int i) {
-    if (col_partials)
-      col_partials[(size_t)blockIdx.x * n2 + col] = Match8Partial{b, s, i, 0};
-    else
-      m8_write_point<kL2>(sift2 + col, sift1, n1, b, s, i);
-  };
-  m8_block<kL2>(
-      q1, sums1, n1, q2, sums2, col_begin, col_end, sB,
-      [&](int p1, int b, int s, int i) {
-        if (partials)
-          partials[(size_t)blockIdx.y * n1_pad + p1] = Match8Partial{b, s, i, 0};
-        else
-          m8_write_point<kL2>(sift1 + p1, sift2, n2, b, s, i);
-      },
-      M8Cols<decltype(col_out)>{sCols, col_out});
+  const auto col_out = m8_point_sink<kL2>(col_partials, (size_t)blockIdx.x * n2, sift2, sift1, n1);
+  m8_block<kL2>(q1, sums1, n1, q2, sums2, col_begin, col_end, sB,
+                m8_point_sink<kL2>(partials, (size_t)blockIdx.y * n1_pad, sift1, sift2, n2),
+                M8Cols<decltype(col_out)>{sCols, col_out});
 }
 template __global__ void match8_mutual_kernel<false>(cusift_point *, int, const unsigned char *, const int *, cusift_point *,
                                                      int, const unsigned char *, const int *, int, Match8Partial *, int,
@@ -469,11 +440,7 @@ __global__ void __launch_bounds__(256) match8_mutual_merge_kernel(cusift_point *
                                                                  int row_blocks) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n2) return;
-  Match8Partial m = col_partials[j];
-  for (int b = 1; b < row_blocks; ++b) {
-    const Match8Partial o = col_partials[(size_t)b * n2 + j];
-    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
-  }
+  const Match8Partial m = fold_partials(col_partials + j, n2, row_blocks, M8Merge{});
   m8_write_point<kL2>(sift2 + j, sift1, n1, m.best, m.second, m.idx);
 }
 
@@ -490,28 +457,15 @@ __global__ void __launch_bounds__(256) match8_batch_mutual_kernel(const unsigned
                                                                  cusift_match_row *__restrict__ rows_back) {
   __shared__ __attribute__((aligned(16))) unsigned char sB[2 * kM8TileCols * kM8Stride];
   __shared__ uint2 sCols[2 * 4 * kM8TileCols];
-  const int pair = blockIdx.z;
-  const int f1 = pairs[2 * pair], f2 = pairs[2 * pair + 1];
-  const int n1 = frame_count(counters, f1, max_pts), n2 = frame_count(counters, f2, max_pts);
-  const int col_begin = blockIdx.y * cols_per_split;
-  if ((int)blockIdx.x * kM8RowsPerBlock >= n1 || col_begin >= n2) return;  // uniform
-  const int col_end = min(col_begin + cols_per_split, n2);
-  auto col_out = [&](int col, int b, int s, int i) {
-    if (col_partials)
-      col_partials[((size_t)pair * gridDim.x + blockIdx.x) * max_pts + col] = Match8Partial{b, s, i, 0};
-    else
-      m8_write_row<kL2>(rows_back + (size_t)pair * max_pts + col, b, s, i);
-  };
-  m8_block<kL2>(
-      q + (size_t)f1 * max_pts * 128, sums + (size_t)f1 * max_pts * 2, n1, q + (size_t)f2 * max_pts * 128,
-      sums + (size_t)f2 * max_pts * 2, col_begin, col_end, sB,
-      [&](int p1, int b, int s, int i) {
-        if (partials)
-          partials[((size_t)pair * gridDim.y + blockIdx.y) * n1_pad + p1] = Match8Partial{b, s, i, 0};
-        else
-          m8_write_row<kL2>(rows + (size_t)pair * max_pts + p1, b, s, i);
-      },
-      M8Cols<decltype(col_out)>{sCols, col_out});
+  const PairFrame fr(counters, pairs, max_pts, cols_per_split, kM8RowsPerBlock);
+  if (fr.empty) return;
+  const auto col_out = m8_row_sink<kL2>(col_partials, ((size_t)fr.pair * gridDim.x + blockIdx.x) * max_pts,
+                                        rows_back + (size_t)fr.pair * max_pts);
+  m8_block<kL2>(q + (size_t)fr.f1 * max_pts * 128, sums + (size_t)fr.f1 * max_pts * 2, fr.n1,
+                q + (size_t)fr.f2 * max_pts * 128, sums + (size_t)fr.f2 * max_pts * 2, fr.col_begin, fr.col_end, sB,
+                m8_row_sink<kL2>(partials, ((size_t)fr.pair * gridDim.y + blockIdx.y) * n1_pad,
+                                 rows + (size_t)fr.pair * max_pts),
+                M8Cols<decltype(col_out)>{sCols, col_out});
 }
 template __global__ void match8_batch_mutual_kernel<false>(const unsigned char *, const int *, const unsigned int *, int,
                                                            const int *, int, Match8Partial *, int, cusift_match_row *,
@@ -527,18 +481,13 @@ __global__ void __launch_bounds__(256) match8_batch_mutual_merge_kernel(const un
                                                                        const Match8Partial *__restrict__ col_partials,
                                                                        int row_blocks,
                                                                        cusift_match_row *__restrict__ rows_back) {
-  const int pair = blockIdx.y;
-  const int n1 = frame_count(counters, pairs[2 * pair], max_pts), n2 = frame_count(counters, pairs[2 * pair + 1], max_pts);
+  const PairCounts pc(blockIdx.y, counters, pairs, max_pts);
   const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n2 || n1 <= 0) return;
-  const int live = min(row_blocks, (n1 + kM8RowsPerBlock - 1) / kM8RowsPerBlock);  // the others wrote nothing
-  const Match8Partial *__restrict__ mine = col_partials + (size_t)pair * row_blocks * max_pts + j;
-  Match8Partial m = mine[0];
-  for (int b = 1; b < live; ++b) {
-    const Match8Partial o = mine[(size_t)b * max_pts];
-    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
-  }
-  m8_write_row<kL2>(rows_back + (size_t)pair * max_pts + j, m.best, m.second, m.idx);
+  if (j >= pc.n2 || pc.n1 <= 0) return;
+  const int live = min(row_blocks, (pc.n1 + kM8RowsPerBlock - 1) / kM8RowsPerBlock);  // the others wrote nothing
+  const Match8Partial m =
+      fold_partials(col_partials + (size_t)pc.pair * row_blocks * max_pts + j, max_pts, live, M8Merge{});
+  m8_write_row<kL2>(rows_back + (size_t)pc.pair * max_pts + j, m.best, m.second, m.idx);
 }
 
 // ---- the quantiser --------------------------------------------------------------------------------------------------------
@@ -611,24 +560,8 @@ __global__ void __launch_bounds__(256) desc8_sums_kernel(const unsigned char *__
 // ------------------------------------------------------------------------------------------------
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-// The column splits of the 8-bit matchers over n_pairs pairs: aim at >= 2 workgroups per CU (a workgroup is 256 rows,
-// four times the fp32 matcher's), keep >= 4 LDS tiles (256 columns) per split.  CUSIFT_POLICY_MATCH_SPLITS = k > 0: k
-// splits, at most one per tile.  A split is a whole number of tiles and spans less than 2^31 bytes of the table.
-static int match8_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int n_pairs, int *splits_out,
-                             int *cols_per_split_out) {
-  const long blocks = (long)idiv_up(num_pts1, kM8RowsPerBlock) * n_pairs;
-  int splits = (int)std::max(1L, std::min((2L * ctx->num_cus + blocks - 1) / blocks,
-                                          (long)idiv_up(num_pts2, 4 * kM8TileCols)));
-  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, kM8TileCols));
-  splits = std::min(splits, 65535);
-  constexpr int kMaxColsPerSplit = (int)((0x7fffffffu / 128u) / kM8TileCols * kM8TileCols);
-  splits = std::max(splits, idiv_up(num_pts2, kMaxColsPerSplit));
-  if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "Match8: too many descriptors in set 2 (%d)", num_pts2);
-  const int cols_per_split = idiv_up(idiv_up(num_pts2, splits), kM8TileCols) * kM8TileCols;
-  *splits_out = idiv_up(num_pts2, cols_per_split);
-  *cols_per_split_out = cols_per_split;
-  return CUSIFT_OK;
-}
+static_assert(kMatcher8.rows_per_block == kM8RowsPerBlock && kMatcher8.tile_cols == kM8TileCols,
+              "the split plan's shape (sift_host.h) is the kernels'");
 
 extern "C" int cusift_quantize_descriptors(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
                                            int n_images, int max_pts, unsigned char *d_q, int *d_sums) {
@@ -671,7 +604,7 @@ static int match8_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, c
                          const int *d_sums2, int distance, cusift_point *d_back) {
   const int row_blocks = idiv_up(num_pts1, kM8RowsPerBlock);
   int splits, cols_per_split;
-  TRY(match8_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
+  TRY(matcher_split_plan(ctx, kMatcher8, num_pts1, num_pts2, 1, &splits, &cols_per_split));
   const int n1_pad = row_blocks * kM8RowsPerBlock;
   Match8Partial *partials = nullptr, *col_partials = nullptr;
   if (splits > 1) {
@@ -711,7 +644,7 @@ extern "C" int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts
   if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "Match8: missing data");
   TRY(check_tables8("Match8", d_q1, d_sums1));
   TRY(check_tables8("Match8", d_q2, d_sums2));
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8: distance must be 0 or 1");
+  TRY(check_distance("Match8", distance));
   return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, nullptr);
 }
 
@@ -724,10 +657,8 @@ extern "C" int cusift_match8_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int 
   if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "Match8Mutual: missing data");
   TRY(check_tables8("Match8Mutual", d_q1, d_sums1));
   TRY(check_tables8("Match8Mutual", d_q2, d_sums2));
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "Match8Mutual: distance must be 0 or 1");
-  const uintptr_t a = (uintptr_t)d_sift1, b = (uintptr_t)d_sift2;
-  if (a < b + sizeof(cusift_point) * (size_t)num_pts2 && b < a + sizeof(cusift_point) * (size_t)num_pts1)
-    return fail(CUSIFT_ERR_INVALID, "Match8Mutual: the two record ranges overlap (both are written; match a copy)");
+  TRY(check_distance("Match8Mutual", distance));
+  TRY(check_disjoint("Match8Mutual", d_sift1, num_pts1, d_sift2, num_pts2));
   return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, d_sift2);
 }
 
@@ -739,7 +670,7 @@ int match8_batch_launch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_
                         cusift_match_row *d_rows_back, const int **d_pairs_out) {
   const int row_blocks = idiv_up(max_pts, kM8RowsPerBlock);
   int splits, cols_per_split;
-  TRY(match8_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
+  TRY(matcher_split_plan(ctx, kMatcher8, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
   const int n1_pad = row_blocks * kM8RowsPerBlock;
   const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
   const size_t part_b = splits > 1 ? sizeof(Match8Partial) * (size_t)n_pairs * splits * n1_pad : 0;
@@ -773,14 +704,8 @@ int match8_batch_launch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_
 static int check_batch8(const char *who, const unsigned char *d_q, const int *d_sums, int n_images, int max_pts,
                         const int *h_pairs, int n_pairs, int distance, const cusift_match_row *d_rows, bool *nothing) {
   *nothing = true;
-  if (distance != 0 && distance != 1) return fail(CUSIFT_ERR_INVALID, "%s: distance must be 0 or 1", who);
-  if (n_pairs < 0 || n_pairs > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_pairs %d outside [0, 65535]", who, n_pairs);
-  if (n_images < 0 || n_images > 65535) return fail(CUSIFT_ERR_INVALID, "%s: n_images %d outside [0, 65535]", who, n_images);
-  if (max_pts < 0 || max_pts > (1 << 20)) return fail(CUSIFT_ERR_INVALID, "%s: max_pts %d outside [0, 2^20]", who, max_pts);
-  if (n_pairs > 0 && !h_pairs) return fail(CUSIFT_ERR_INVALID, "%s: NULL pair list", who);
-  for (int p = 0; p < 2 * n_pairs; ++p)
-    if (h_pairs[p] < 0 || h_pairs[p] >= n_images)
-      return fail(CUSIFT_ERR_INVALID, "%s: pair %d names frame %d outside [0, %d)", who, p / 2, h_pairs[p], n_images);
+  TRY(check_distance(who, distance));
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, who));
   if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
   if (!d_rows) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
   TRY(check_tables8(who, d_q, d_sums));

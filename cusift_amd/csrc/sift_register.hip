@@ -8,7 +8,7 @@
 #include "sift_host.h"
 
 // the refusals that several entry points share; `who` is the entry point's name in the message
-static int check_distance(const char *who, int distance) {
+int check_distance(const char *who, int distance) {
   return distance == 0 || distance == 1 ? CUSIFT_OK : fail(CUSIFT_ERR_INVALID, "%s: distance must be 0 or 1", who);
 }
 static int check_dims(const char *who, const char *name, int type) {
@@ -25,8 +25,7 @@ static int check_not_nan(const char *who, float a, float b) {
   return std::isnan(a) || std::isnan(b) ? fail(CUSIFT_ERR_INVALID, "%s: a threshold is NaN", who) : CUSIFT_OK;
 }
 // the mutual matcher writes both record sets: their ranges must not overlap
-static int check_disjoint(const char *who, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
-                          int num_pts2) {
+int check_disjoint(const char *who, const cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2) {
   const uintptr_t a = (uintptr_t)d_sift1, b = (uintptr_t)d_sift2;
   if (a < b + sizeof(cusift_point) * (size_t)num_pts2 && b < a + sizeof(cusift_point) * (size_t)num_pts1)
     return fail(CUSIFT_ERR_INVALID, "%s: the two record ranges overlap (both are written; match a copy)", who);
@@ -46,25 +45,6 @@ static const double kIdentRtD[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
 // ------------------------------------------------------------------------------------------------
 // matcher
 // ------------------------------------------------------------------------------------------------
-// The column splits of the matchers, over n_pairs pairs (a batch: sized from max_pts, the counts stay on the device):
-// aim at >= 4 workgroups per CU over all pairs, keep >= 4 LDS tiles (128 columns) per split.
-static int match_split_plan(cusift_ctx *ctx, int num_pts1, int num_pts2, int n_pairs, int *splits_out,
-                            int *cols_per_split_out) {
-  const long blocks = (long)idiv_up(num_pts1, 64) * n_pairs;
-  int splits = (int)std::max(1L, std::min((4L * ctx->num_cus + blocks - 1) / blocks, (long)idiv_up(num_pts2, 128)));
-  if (ctx->knobs.match_splits > 0) splits = std::min(ctx->knobs.match_splits, idiv_up(num_pts2, 32));
-  splits = std::min(splits, 65535);
-  // the kernel addresses a split's columns through a buffer resource with 32-bit byte offsets: a split may span at most
-  // 2^31 / 588 records (3.65 M) -- more points than that force further splits (never a batch: max_pts <= 2^20)
-  constexpr int kMaxColsPerSplit = (int)((0x7fffffffu / sizeof(cusift_point)) / 32 * 32);
-  splits = std::max(splits, idiv_up(num_pts2, kMaxColsPerSplit));
-  if (splits > 65535) return fail(CUSIFT_ERR_INVALID, "MatchSiftData: too many points in image 2 (%d)", num_pts2);
-  const int cols_per_split = idiv_up(idiv_up(num_pts2, splits), 32) * 32;
-  *splits_out = idiv_up(num_pts2, cols_per_split);
-  *cols_per_split_out = cols_per_split;
-  return CUSIFT_OK;
-}
-
 // The geometry of a guided match (cusift_match_guided, cusift_match_batch_guided), checked: which test, the squared radius
 // and the models as the caller's host array -- one of the pair call, one per pair of the pair-list call.
 struct GuideCall {
@@ -88,7 +68,7 @@ static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, co
                         int distance, cusift_point *d_back, const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(num_pts1, 64);
   int splits, cols_per_split;
-  TRY(match_split_plan(ctx, num_pts1, num_pts2, 1, &splits, &cols_per_split));
+  TRY(matcher_split_plan(ctx, kMatcher32, num_pts1, num_pts2, 1, &splits, &cols_per_split));
   const int n1_pad = row_blocks * 64;
   MatchPartial *partials = nullptr, *col_partials = nullptr;
   if (splits > 1) {
@@ -975,7 +955,7 @@ static int match_batch_launch32(cusift_ctx *ctx, const cusift_point *d_points, c
                                 const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(max_pts, 64);
   int splits, cols_per_split;
-  TRY(match_split_plan(ctx, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
+  TRY(matcher_split_plan(ctx, kMatcher32, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
   const int n1_pad = row_blocks * 64;
   const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
   const size_t part_b = align_up_sz(splits > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * splits * n1_pad : 0, 256);

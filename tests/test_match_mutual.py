@@ -1,5 +1,5 @@
 """Mutual nearest neighbours from one pass: cusift_match_mutual, cusift_select_mutual, cusift_match_batch_mutual
-(cusift_amd/csrc/sift_match.hip, match_tile.inc with a ColumnSide), held to zero tolerance like the matcher.
+(cusift_amd/csrc/sift_match.hip, match_block with a ColumnSide), held to zero tolerance like the matcher.
 
 The row side must be byte for byte what cusift_match writes under the same split setting.  The column side is defined by
 `column_model`: FindMinCorr / FindMaxCorr's update run over the rows 0, 1, ..., n1 - 1 in ascending order from
