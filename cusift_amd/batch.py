@@ -318,6 +318,24 @@ class BatchExtractor:
         n_i, n_j = self._pair_counts(counts, i, j)
         return self.ctx.register_pnp(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, camera2, **opts)
 
+    def match_projected(self, i, j, rt, camera2, radius, slot=0, distance=1):
+        """Match by projection of frames i and j of the last extract() into `slot`: cusift_match_projected over this
+        extractor's device records (frame i's match fields are written, its coords3D read) -- a record of frame j counts
+        for a record of frame i only within `radius` pixels of where rt (X_i = R X_j + t) and camera2, the capi.Camera of
+        frame j, put that record's coords3D.  The two counts are read with one call.  Asynchronous on the extractor's
+        stream."""
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        self.ctx.match_projected(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, rt, camera2, radius, distance)
+
+    def register_pnp_guided(self, i, j, camera2, radius=None, slot=0, **opts):
+        """register_pnp(i, j, camera2) with a second matching pass by projection: capi.Context.register_pnp_guided over
+        this extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.
+        Blocking."""
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return self.ctx.register_pnp_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, camera2, radius, **opts)
+
     def register_planar_sequence(self, pairs=None, slot=0, **opts):
         """Planar registration of the frames of the last extract() into `slot` against each other:
         cusift_register_planar_batch over this extractor's own device records and raw counters -- no count is read

@@ -234,6 +234,7 @@ SIGNATURES = {
     "cusift_match": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "cusift_match_mutual": (_i, [_vp, _vp, _i, _vp, _i, _i]),
     "cusift_match_guided": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _f]),
+    "cusift_match_projected": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, C.POINTER(Camera), _f]),
     "cusift_memcpy2d_d2h": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
     "cusift_find_homography": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, C.POINTER(_i), _vp, _vp]),
     "cusift_estimate_homography": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp, _vp, C.POINTER(_i),
@@ -264,6 +265,7 @@ SIGNATURES = {
     "cusift_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cusift_match_batch_mutual": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "cusift_match_batch_guided": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _vp]),
+    "cusift_match_batch_projected": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.POINTER(Camera), _f, _vp]),
     "cusift_quantize_descriptors": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "cusift_desc8_sums": (_i, [_vp, _vp, _i, _vp]),
     "cusift_match8": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
@@ -556,6 +558,15 @@ def guide_models(model, m, n_models=None):
     if len(m) != (1 if n_models is None else n_models):
         raise ValueError("guided match: %d models for %d pairs" % (len(m), 1 if n_models is None else n_models))
     return GUIDE_MODELS.get(model, model), m
+
+
+def pose_models(rt, n_models=None):
+    """The poses of a projected match as contiguous float64 [n, 12]: one 3 x 4 or 12-vector [R | t] -- or n_models of
+    them -- of any float type."""
+    rt = np.ascontiguousarray(rt, dtype=np.float64).reshape(-1, 12)
+    if len(rt) != (1 if n_models is None else n_models):
+        raise ValueError("projected match: %d poses for %d pairs" % (len(rt), 1 if n_models is None else n_models))
+    return rt
 
 
 def pair_list(pairs):
@@ -863,6 +874,17 @@ class Context:
         check(lib().cusift_match_guided(self.handle, d_sift1, n1, d_sift2, n2, distance, model,
                                         None if m is None else m.ctypes.data, radius))
 
+    def match_projected(self, d_sift1, n1, d_sift2, n2, rt, camera2, radius, distance=1):
+        """cusift_match_projected: match() where a record of d_sift2 counts for a row only within `radius` pixels of where
+        the pose puts the row's coords3D in the image of `camera2` (capi.Camera).  rt: [R | t], 3 x 4 or 12 values, X1 = R
+        X2 + t as estimate_pnp / register_pnp return it, widened to float64.  A row without depth (Z == 0), behind camera
+        2 or that nothing passes ends with match = -1.  coords3D is read, never written.  Asynchronous; rt and camera2
+        are read before the call returns."""
+        rt = None if rt is None else pose_models(rt)
+        check(lib().cusift_match_projected(self.handle, d_sift1, n1, d_sift2, n2, distance,
+                                           None if rt is None else rt.ctypes.data,
+                                           C.byref(camera2) if camera2 is not None else None, radius))
+
     def find_homography(self, d_sift, num_pts, rand_pts, thresh=5.0, want_all=False):
         """cusift_find_homography: rand_pts is an int32 array [4, num_loops] of sample indices into d_sift.
         Returns (H[9], num_matches) or, with want_all, (H, num_matches, all_homographies[8, L], all_counts[L])."""
@@ -946,8 +968,10 @@ class Context:
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi, loops, thresh, refine_loops, refine_thresh,
             _seed64(seed), *out), n1, max(loops, 0), want_all)
 
-    def _guided_chain(self, register, estimate, model, thresh, d_sift1, n1, d_sift2, n2, radius, opts):
-        """register -> match_guided under the refined model -> estimate over the rewritten records, same options."""
+    def _guided_chain(self, register, estimate, guided, thresh, d_sift1, n1, d_sift2, n2, radius, opts):
+        """register -> the guided matcher under the refined model -> estimate over the rewritten records, same options.
+        guided(d_sift1, n1, d_sift2, n2, refined model, radius, distance) is match_guided under H or F, or
+        match_projected under [R | t]."""
         if self.cross_check:
             raise CusiftError("guided registration: turn the cross-check off first (set_cross_check(False)) -- the "
                               "guided matcher has no column side")
@@ -957,8 +981,7 @@ class Context:
         first = register(d_sift1, n1, d_sift2, n2, **opts)
         distance = opts.get("distance", 1)
         rule, lo, hi = _rule_defaults(distance, opts.get("rule"), opts.get("lo"), opts.get("hi"))
-        self.match_guided(d_sift1, n1, d_sift2, n2, model, first[0], opts.get("thresh", thresh) if radius is None else radius,
-                          distance)
+        guided(d_sift1, n1, d_sift2, n2, first[0], opts.get("thresh", thresh) if radius is None else radius, distance)
         again = {k: v for k, v in opts.items() if k != "distance"}
         again.update(rule=rule, lo=lo, hi=hi)
         return first, estimate(d_sift1, n1, n2, **again)
@@ -969,15 +992,19 @@ class Context:
         d_sift1 with num_pts2 = n2 and the same options and seed.  Matches that the ratio test of the first pass threw
         away because a look-alike scored as well come back when the look-alike lies elsewhere.  Returns (first pass,
         guided pass), two PlanarResults.  CusiftError while the cross-check is on.  Blocking, twice."""
-        return self._guided_chain(self.register_planar, self.estimate_homography, "homography", 5.0, d_sift1, n1, d_sift2,
-                                  n2, radius, opts)
+        return self._guided_chain(self.register_planar, self.estimate_homography, self._guided_by("homography"), 5.0,
+                                  d_sift1, n1, d_sift2, n2, radius, opts)
 
     def register_epipolar_guided(self, d_sift1, n1, d_sift2, n2, radius=None, **opts):
         """register_planar_guided for two views of a general scene: register_epipolar(**opts), match_guided under the
         refined fundamental matrix (radius None: that call's thresh, pixels from the epipolar line), estimate_fundamental
         over the rewritten records.  Returns (first pass, guided pass), two EpipolarResults."""
-        return self._guided_chain(self.register_epipolar, self.estimate_fundamental, "epipolar", 1.0, d_sift1, n1, d_sift2,
-                                  n2, radius, opts)
+        return self._guided_chain(self.register_epipolar, self.estimate_fundamental, self._guided_by("epipolar"), 1.0,
+                                  d_sift1, n1, d_sift2, n2, radius, opts)
+
+    def _guided_by(self, model):
+        """match_guided under one kind of model, in _guided_chain's argument order"""
+        return lambda d1, n1, d2, n2, m, radius, distance: self.match_guided(d1, n1, d2, n2, model, m, radius, distance)
 
     @staticmethod
     def _pose(call):
@@ -1039,6 +1066,17 @@ class Context:
             self.handle, d_sift1, n1, d_sift2, n2, distance, rule, lo, hi,
             C.byref(camera2) if camera2 is not None else None, loops, thresh, refine_loops, refine_thresh, _seed64(seed),
             *out), n1, max(loops, 0), want_all)
+
+    def register_pnp_guided(self, d_sift1, n1, d_sift2, n2, camera2, radius=None, **opts):
+        """register_planar_guided for a pose from 3-D/2-D matches: register_pnp(camera2, **opts), match_projected under
+        the refined [R | t] (radius None: that call's thresh, pixels from the projection of coords3D), estimate_pnp over
+        the rewritten records with num_pts2 = n2 and the same options and seed.  Returns (first pass, guided pass), two
+        PnPResults.  CusiftError while the cross-check is on or the match bits are 8.  Blocking, twice."""
+        return self._guided_chain(
+            lambda d1, m1, d2, m2, **o: self.register_pnp(d1, m1, d2, m2, camera2, **o),
+            lambda d1, m1, m2, **o: self.estimate_pnp(d1, m1, camera2, m2, **o),
+            lambda d1, m1, d2, m2, rt, r, distance: self.match_projected(d1, m1, d2, m2, rt, camera2, r, distance),
+            2.0, d_sift1, n1, d_sift2, n2, radius, opts)
 
     def estimate_rigid(self, coord, indices=None, loops=None, thresh2=0.0025, kind="3d", seed=0, want_all=False):
         """cusift_estimate_rigid: RANSAC rigid transform x ~ R y + t from coord float32 [N, 6] (reference xyz, moving
@@ -1173,6 +1211,17 @@ class Context:
         check(lib().cusift_match_batch_guided(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
                                               len(pairs), distance, model, None if m is None else m.ctypes.data, radius,
                                               d_rows))
+
+    def match_batch_projected(self, d_points, d_counters, n_images, max_pts, pairs, rts, camera2, radius, d_rows,
+                              distance=1):
+        """cusift_match_batch_projected: match_batch() with match_projected()'s rule, pair p under rts[p] (float [P, 3, 4]
+        or [P, 12], widened to float64; one camera2 and one radius for the list).  Asynchronous; rts and camera2 are read
+        before the call returns."""
+        pairs = pair_list(pairs)
+        rts = None if rts is None else pose_models(rts, len(pairs))
+        check(lib().cusift_match_batch_projected(self.handle, d_points, d_counters, n_images, max_pts, pairs.ctypes.data,
+                                                 len(pairs), distance, None if rts is None else rts.ctypes.data,
+                                                 C.byref(camera2) if camera2 is not None else None, radius, d_rows))
 
     # ---- 8-bit descriptors ----
     def quantize_descriptors(self, d_points, max_pts, d_q, d_sums, n_images=1, d_counters=None):

@@ -98,6 +98,12 @@ __global__ void match_guided_kernel(cusift_point *, int, const cusift_point *, i
 template <bool kL2, class Guide>
 __global__ void match_batch_guided_kernel(const cusift_point *, const unsigned int *, int, const int *, int,
                                           MatchPartial *, int, cusift_match_row *, const GuideModel *, float);
+template <bool kL2>  // the matcher under a pose and coords3D (sift_match_project.hip)
+__global__ void match_projected_kernel(cusift_point *, int, const cusift_point *, int, int, MatchPartial *, int,
+                                       ProjectModel, float);
+template <bool kL2>
+__global__ void match_batch_projected_kernel(const cusift_point *, const unsigned int *, int, const int *, int,
+                                             MatchPartial *, int, cusift_match_row *, const ProjectModel *, float);
 __global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                        const cusift_match_row *, float, float, int, int *, float *, int *,
                                        const cusift_match_row *);
@@ -249,6 +255,8 @@ struct cusift_ctx {
   // per-split partials (live together with register_scratch in the last two)
   char *pairs_scratch = nullptr;
   size_t pairs_scratch_bytes = 0;
+  // cusift_match_batch_projected: the pairs' models as the upload reads them (the caller's poses beside the one camera)
+  std::vector<ProjectModel> project_models;
   // the byte tables and sums the registrations quantise into while cusift_ctx_set_match_bits is 8 (sift_match8.hip)
   char *q8_scratch = nullptr;
   size_t q8_scratch_bytes = 0;

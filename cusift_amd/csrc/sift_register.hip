@@ -47,11 +47,20 @@ static const double kIdentRtD[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
 // ------------------------------------------------------------------------------------------------
 // The geometry of a guided match (cusift_match_guided, cusift_match_batch_guided), checked: which test, the squared radius
 // and the models as the caller's host array -- one of the pair call, one per pair of the pair-list call.
+// camera != NULL (cusift_match_projected, cusift_match_batch_projected): the test is the projection of coords3D, h_models
+// holds [R | t], twelve doubles a pair, and `model` is not read.
 struct GuideCall {
   int model;
   float r2;
   const double *h_models;
+  const PnPCam *camera = nullptr;
 };
+static ProjectModel project_model(const double *h_rt, const PnPCam &cam) {
+  ProjectModel pm;
+  memcpy(pm.rt, h_rt, sizeof(pm.rt));
+  pm.fx = cam.fx, pm.fy = cam.fy, pm.px = cam.px, pm.py = cam.py;
+  return pm;
+}
 // every refusal the guided calls add to their unguided counterparts'
 static int check_guide(const char *who, int model, const double *h_models, float radius) {
   if (model != CUSIFT_GUIDE_HOMOGRAPHY && model != CUSIFT_GUIDE_EPIPOLAR)
@@ -86,6 +95,10 @@ static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, co
     hipLaunchKernelGGL(distance ? match_mutual_kernel<true> : match_mutual_kernel<false>, grid, dim3(256), 0,
                        ctx->stream, d_sift1, num_pts1, d_back, num_pts2, cols_per_split, partials, n1_pad,
                        col_partials);
+  else if (guide && guide->camera)
+    hipLaunchKernelGGL(distance ? match_projected_kernel<true> : match_projected_kernel<false>, grid, dim3(256), 0,
+                       ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2, cols_per_split, partials, n1_pad,
+                       project_model(guide->h_models, *guide->camera), guide->r2);
   else if (guide) {
     GuideModel model;
     memcpy(model.m, guide->h_models, sizeof(model.m));
@@ -104,7 +117,7 @@ static int match_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, co
     hipLaunchKernelGGL(match_mutual_merge_kernel, dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_back,
                        num_pts2, (const cusift_point *)d_sift1, num_pts1, distance, (const MatchPartial *)col_partials,
                        row_blocks);
-  return check_launch(d_back ? "match_mutual" : guide ? "match_guided" : "match");
+  return check_launch(d_back ? "match_mutual" : guide ? (guide->camera ? "match_projected" : "match_guided") : "match");
 }
 
 extern "C" int cusift_match(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
@@ -962,7 +975,8 @@ static int match_batch_launch32(cusift_ctx *ctx, const cusift_point *d_points, c
   // the column side (cusift_match_batch_mutual): [pair][row block][max_pts] partials when there is more than one row block
   const size_t col_b = d_rows_back && row_blocks > 1 ? sizeof(MatchPartial) * (size_t)n_pairs * row_blocks * max_pts : 0;
   // the models of a guided call (cusift_match_batch_guided, never with d_rows_back): [pair], behind the partials
-  const size_t model_b = guide ? sizeof(GuideModel) * (size_t)n_pairs : 0;
+  // (cusift_match_batch_projected: ProjectModel [pair] in the same place; col_b is 0 for both, so it is 256-byte aligned)
+  const size_t model_b = guide ? (guide->camera ? sizeof(ProjectModel) : sizeof(GuideModel)) * (size_t)n_pairs : 0;
   TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b + col_b + model_b, "", false));
   int *d_pairs = (int *)ctx->pairs_scratch;
   MatchPartial *partials = splits > 1 ? (MatchPartial *)(ctx->pairs_scratch + list_b) : nullptr;
@@ -973,7 +987,15 @@ static int match_batch_launch32(cusift_ctx *ctx, const cusift_point *d_points, c
     hipLaunchKernelGGL(distance ? match_batch_mutual_kernel<true> : match_batch_mutual_kernel<false>, grid, dim3(256),
                        0, ctx->stream, d_points, d_counters, max_pts, d_pairs, cols_per_split, partials, n1_pad, d_rows,
                        col_partials, d_rows_back);
-  else if (guide) {
+  else if (guide && guide->camera) {
+    ProjectModel *d_models = (ProjectModel *)(ctx->pairs_scratch + list_b + part_b + col_b);
+    ctx->project_models.resize(n_pairs);  // stays allocated behind this call, whenever the upload reads it
+    for (int p = 0; p < n_pairs; ++p) ctx->project_models[p] = project_model(guide->h_models + 12 * (size_t)p, *guide->camera);
+    HIP_TRY(hipMemcpyAsync(d_models, ctx->project_models.data(), model_b, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(distance ? match_batch_projected_kernel<true> : match_batch_projected_kernel<false>, grid,
+                       dim3(256), 0, ctx->stream, d_points, d_counters, max_pts, (const int *)d_pairs, cols_per_split,
+                       partials, n1_pad, d_rows, (const ProjectModel *)d_models, guide->r2);
+  } else if (guide) {
     GuideModel *d_models = (GuideModel *)(ctx->pairs_scratch + list_b + part_b + col_b);
     HIP_TRY(hipMemcpyAsync(d_models, guide->h_models, model_b, hipMemcpyHostToDevice, ctx->stream));
     const auto kernel =
@@ -1034,6 +1056,45 @@ extern "C" int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_
   if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
   if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatchGuided: missing data");
   const GuideCall guide{model, radius * radius, h_models};
+  const int *d_pairs = nullptr;
+  return match_batch_launch32(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, nullptr,
+                            &guide);
+}
+
+// Matching by projection (sift_match_project.hip): cusift_match / cusift_match_batch where a record of image 2 counts for
+// a row only within `radius` pixels of where the pose puts the row's coords3D.  Every refusal the two calls add:
+static int check_project(const char *who, const double *h_rts, const cusift_camera *camera2, float radius) {
+  if (!h_rts) return fail(CUSIFT_ERR_INVALID, "%s: NULL pose", who);
+  if (!camera2) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
+  TRY(check_pinhole(camera2, who));
+  return radius > 0.0f ? CUSIFT_OK : fail(CUSIFT_ERR_INVALID, "%s: radius must be > 0", who);
+}
+
+extern "C" int cusift_match_projected(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                      int num_pts2, int distance, const double h_rt[12], const cusift_camera *camera2,
+                                      float radius) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "MatchProjected: missing data");
+  TRY(check_distance("MatchProjected", distance));
+  TRY(check_project("MatchProjected", h_rt, camera2, radius));
+  const PnPCam cam = pnp_cam(camera2);
+  const GuideCall guide{0, radius * radius, h_rt, &cam};
+  return match_launch(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, nullptr, &guide);
+}
+
+extern "C" int cusift_match_batch_projected(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters,
+                                            int n_images, int max_pts, const int *h_pairs, int n_pairs, int distance,
+                                            const double *h_rts, const cusift_camera *camera2, float radius,
+                                            cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  TRY(check_distance("MatchBatchProjected", distance));
+  TRY(check_pair_list(h_pairs, n_pairs, n_images, max_pts, "MatchBatchProjected"));
+  TRY(check_project("MatchBatchProjected", h_rts, camera2, radius));
+  if (n_pairs == 0 || max_pts == 0) return CUSIFT_OK;
+  if (!d_points || !d_rows) return fail(CUSIFT_ERR_INVALID, "MatchBatchProjected: missing data");
+  const PnPCam cam = pnp_cam(camera2);
+  const GuideCall guide{0, radius * radius, h_rts, &cam};
   const int *d_pairs = nullptr;
   return match_batch_launch32(ctx, d_points, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, &d_pairs, nullptr,
                             &guide);

@@ -150,6 +150,14 @@ struct GuideModel {
   double m[9];
 };
 
+// the model of a projected match (cusift_match_projected): [R | t] row-major with X1 = R X2 + t, and camera 2's
+// intrinsics with px = cx - origin, py = cy - origin; a kernel argument of the pair call, an array in context scratch --
+// one per pair -- of the pair-list call
+struct ProjectModel {
+  double rt[12];
+  double fx, fy, px, py;
+};
+
 // elements between consecutive pairs of a batched RANSAC (blockIdx.z of the rigid_* kernels); all 0 for one pair
 struct RigidBatch {
   size_t coord, indices, rt, counts, head, flags;

@@ -78,6 +78,36 @@ int cusift_match_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, cu
 #define CUSIFT_GUIDE_EPIPOLAR 1
 int cusift_match_guided(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
                         int distance, int model, const double h_model[9], float radius);
+/* Matching by projection: nearest neighbours under a known pose -- the guided pass behind cusift_register_pnp, and the
+ * search a tracker runs per frame (ORB-SLAM's SearchByProjection, COLMAP's guided matching after image registration).
+ * The records of d_sift1 carry map points in coords3D (cusift_lift_depth, cusift_register_pose); a pose of camera 2,
+ * predicted or just estimated, says where each lands in image 2, and only the records of d_sift2 that lie there count.
+ * THE RESULT is cusift_match's with one more rule, exactly as cusift_match_guided states it: a column j that fails the
+ * test below against row i scores the initial value for that row.  A row that no column passes receives match = -1, the
+ * initial score, the ambiguity of two initial values and match_xpos / match_ypos of record 0; a row with exactly one
+ * passing column has a tiny ambiguity.  The scan, the tree, the column splits (CUSIFT_POLICY_MATCH_SPLITS included), the
+ * merge and the five fields written are cusift_match's, from the same text.
+ * CONVENTIONS are cusift_estimate_pnp's: X1 = (X, Y, Z) = coords3D of row i, widened to double; h_rt = [R | t] row-major
+ * with X1 = R X2 + t; fx, fy, px = cx - origin, py = cy - origin of camera2, each widened first; (x2, y2) = coords2D of
+ * column j.  THE TEST is pinned to these expressions (the build uses -ffp-contract=off):
+ *   per row, fp64:   dx = X - rt[3];  dy = Y - rt[7];  dz = Z - rt[11]
+ *                    a = (rt[0]*dx + rt[4]*dy) + rt[8]*dz;  b = (rt[1]*dx + rt[5]*dy) + rt[9]*dz;
+ *                    c = (rt[2]*dx + rt[6]*dy) + rt[10]*dz                  (the a, b, c of the PnP inlier test)
+ *                    usable <=> Z != 0 && c > 0
+ *                    qx = (float)((fx*a)/c + px);  qy = (float)((fy*b)/c + py)       -- both NaN when not usable
+ *   per pair, fp32:  ex = x2 - qx;  ey = y2 - qy;  pass <=> ex*ex + ey*ey < r2,  r2 = radius * radius
+ * A NaN anywhere is no pass.  A row with no depth (Z == 0, the "no depth" mark of cusift_lift_depth), a row behind camera
+ * 2 or on its principal plane, and a row with a coordinate that is not finite pass nothing.  +infinity is a legal radius.
+ * A pose that is not finite is no error: it passes nothing.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): everything cusift_match refuses; a NULL h_rt or camera2; fx or
+ * fy zero or not finite, cx, cy or origin not finite (the checks of cusift_estimate_pnp); radius not > 0 (NaN included).
+ * A count <= 0 on either side: CUSIFT_OK, nothing enqueued, as cusift_match.  h_rt and camera2 are read before the call
+ * returns.  Asynchronous on the context's stream, no synchronisation; writes what cusift_match writes and nothing else:
+ * coords3D is read, never written. */
+struct cusift_camera; /* defined below, with the RGB-D calls */
+int cusift_match_projected(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                           int num_pts2, int distance, const double h_rt[12], const struct cusift_camera *camera2,
+                           float radius);
 /* cudaMemcpy2D device->host (extras/matching.cu:311-315 copies the 5 match fields of every record); blocking. */
 int cusift_memcpy2d_d2h(cusift_ctx *ctx, void *h_dst, size_t dst_pitch, const void *d_src, size_t src_pitch,
                         size_t width_bytes, size_t rows);
@@ -583,6 +613,18 @@ int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_points, con
                               int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
                               int model, const double *h_models /* [n_pairs][9] */, float radius,
                               cusift_match_row *d_rows);
+
+/* cusift_match_batch under one pose per pair (cusift_match_projected over a pair list): pair p's rows are what
+ * cusift_match_batch writes for it with cusift_match_projected's rule added, under the pose h_rts[12 p .. 12 p + 11] --
+ * X1 = R X2 + t with frame 1 = the pair's first member, whose coords3D are read -- all pairs under the same camera2 and
+ * the same radius.  h_rts and camera2 are host memory and are read before the call returns, as h_pairs is; the device
+ * copy lives in the context's scratch.  Rows, counts and launches as cusift_match_batch; the records are not written.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of cusift_match_batch, a NULL h_rts or camera2, fx
+ * or fy zero or not finite, cx, cy or origin not finite, radius not > 0 (NaN included). */
+int cusift_match_batch_projected(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters /* or NULL */,
+                                 int n_images, int max_pts, const int *h_pairs /* [n_pairs][2] */, int n_pairs,
+                                 int distance, const double *h_rts /* [n_pairs][12] */, const cusift_camera *camera2,
+                                 float radius, cusift_match_row *d_rows);
 
 /* ---- 8-bit descriptors: quantised on the device, matched on the int8 matrix pipe ------------------------------------
  * The byte descriptor is what OpenCV, VLFeat and COLMAP store and exchange: 128 unsigned bytes per keypoint, 512 v clipped

@@ -18,6 +18,7 @@
 #include "cuSIFT.h"
 #include "cusift_amd_extras.h"
 #include "epipolar.h"
+#include "matching.h"
 #include "sequence.h"
 
 // The pose over the device records of `data`, which carry match fields and coords3D.  The candidates are those of `rule`
@@ -54,6 +55,49 @@ inline double RegisterPnP(SiftData &data1, SiftData &data2, const cusift_camera 
                                ransac ? ransac : winner, numCandidates ? numCandidates : &candidates, numMatches, numFit,
                                nullptr, nullptr, nullptr, nullptr, nullptr));
   return timer.read();
+}
+
+// MatchSiftData under a pose that is already known (not in the reference): cusift_match_projected() instead of
+// cusift_match() -- the second matching pass behind RegisterPnP, or a tracker's search under a predicted pose.  A record
+// of data2 can be the match of a record of data1 only within `radius` pixels of where Rt (12 doubles, [R | t] with X1 = R
+// X2 + t, as RegisterPnP returns it) and camera2 put that record's coords3D.  A record without depth (coords3D z == 0),
+// behind camera 2 or that nothing passes has match == -1 and is not returned.  Everything else is MatchSiftData's, as in
+// MatchSiftDataGuided (matching.h).
+inline std::vector<SiftMatch *> MatchSiftDataProjected(SiftData &data1, SiftData &data2, const double Rt[12],
+                                                       const cusift_camera *camera2, float radius,
+                                                       MatchSiftDistance distance = MatchSiftDistanceL2,
+                                                       float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                                       MatchType type = MatchType2D) {
+  std::vector<SiftMatch *> matches;
+  if (!data1.numPts || !data2.numPts) return matches;
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match_projected(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
+                                  reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
+                                  distance == MatchSiftDistanceL2 ? 1 : 0, Rt, camera2, radius));
+  if (data1.h_data != nullptr)  // the 5 match fields of every record, extras/matching.cu:311-315
+    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
+                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
+  else
+    safeCall(cusift_ctx_synchronize(ctx));
+  if (data1.h_data == nullptr) return matches;
+  const float thresh2 = scoreThreshold * scoreThreshold;
+  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
+  for (int i = 0; i < data1.numPts; i++) {
+    SiftPoint &p = data1.h_data[i];
+    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
+    if (p.match < 0 || p.match >= data2.numPts || data2.h_data == nullptr) continue;
+    if (type == MatchType2D || (p.coords3D[2] != 0 && data2.h_data[p.match].coords3D[2] != 0)) {
+      SiftMatch *m = new SiftMatch();
+      m->pt1 = &p;
+      m->pt2 = &data2.h_data[p.match];
+      m->score = p.score;
+      m->ambiguity = p.ambiguity;
+      m->error = 0.0f;
+      matches.push_back(m);
+    }
+  }
+  return matches;
 }
 
 // RegisterPnP for a whole sequence in one call (cusift_register_pnp_batch): pair k = (a, b) of `pairs` gives
