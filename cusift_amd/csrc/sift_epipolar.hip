@@ -5,13 +5,11 @@
 //
 //   planar_mark_kernel      (sift_planar.hip, unchanged) candidate?  SoA coordinates [x1 | y1 | x2 | y2] of all records
 //   planar_compact_kernel   (sift_planar.hip, unchanged) the candidates' record indices in ascending order, their number
-//   epipolar_solve_kernel   one hypothesis per lane: its eight samples drawn from the candidate list, Hartley
-//                           normalisation, the null vector of the 8 x 9 system, rank 2, denormalisation, unit norm and
-//                           sign.  The launch's threads together also gather the candidates' coordinates into a compacted
-//                           SoA, which is all the scoring and the refit read
-//   epipolar_score_kernel   one hypothesis per lane, its 9 coefficients and its count in registers; 64-candidate tiles in
-//                           LDS as SoA rows of doubles, every lane reads the same candidate (a broadcast); grid (loops /
-//                           64, candidate splits); the splits' partial counts meet in one integer atomic add per lane
+//   epipolar_solve_kernel   one hypothesis per lane: draw_and_gather (sift_ransac_chain.h: the candidates' coordinates
+//                           compacted, eight samples drawn from the candidate list), Hartley normalisation, the
+//                           null_vector of the 8 x 9 system, rank 2, denormalisation, unit norm and sign
+//   epipolar_score_kernel   ransac_score (sift_ransac_chain.h) over the candidates with epipolar_inlier; grid (loops /
+//                           64, candidate splits)
 //   epipolar_select_kernel  one workgroup: the winner (ransac_winner<true>: among equals the first), its
 //                           inlier flags, the refit rounds (normalised 9 x 9 sums over the current inliers, cyclic Jacobi,
 //                           rank 2), then match_error of every record and the number of candidates that fit
@@ -21,10 +19,8 @@
 // path does: the epipolar constraint is one-dimensional, so a rejected match lies within a pixel of a random epipolar
 // line far more often than within a pixel of a homography's image of its point.  The scoring's cost follows n_cand.
 //
-// THE NULL VECTOR of the 8 x 9 system is found by Gaussian elimination with complete pivoting (rows and columns) and
-// back substitution from x[8] = 1: exact rank 8 has a one-dimensional null space, no squaring of the condition number as
-// a 9 x 9 normal matrix would bring, about 500 flops.  The system lives in LDS, one column per lane, because the pivot
-// search indexes it dynamically; everything else is in registers with static indices.  The refit's 9 x 9 matrix is a sum
+// THE NULL VECTOR of the 8 x 9 system is null_vector's (sift_ransac_chain.h): Gaussian elimination with complete
+// pivoting in LDS, about 500 flops; everything else is in registers with static indices.  The refit's 9 x 9 matrix is a sum
 // over many points: there the eigenvector of the smallest eigenvalue is taken by cyclic Jacobi, kEpiSweeps9 sweeps over
 // the 36 pairs in row-major order, whatever the data.  RANK 2: F' = F (I - v v^T) with v the eigenvector of the smallest
 // eigenvalue of F^T F (3 x 3 cyclic Jacobi, kEpiSweeps3 sweeps) -- the nearest rank-2 matrix in the Frobenius norm.
@@ -35,11 +31,13 @@
 // 819 us and 1,580 us.  The select kernel carries the call: every refit round ends in one lane's Jacobi (288 rotations,
 // each two divisions and two square roots in fp64, 126 doubles of state that overflow into AGPRs) while 255 lanes wait.
 #include "sift_epipolar.h"
+#include "sift_ransac_chain.h"
 
 namespace cusift {
 
 constexpr int kEpiThreads = 256;  // select
 constexpr int kEpiTile = 64;      // hypotheses per workgroup of the solve and scoring kernels, candidates per LDS tile
+static_assert(kEpiTile == kRansacTile && kEpiThreads == kRansacThreads, "the shared bodies' geometry");
 constexpr int kEpiSums = 45;      // the upper triangle of the 9 x 9 normal matrix
 
 // Column of v that belongs to the smallest a[j][j]; among equals the first.
@@ -126,32 +124,15 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_solve_kernel(const float *_
                                                                   float *__restrict__ ccoord, PlanarBatch nb) {
   __shared__ double s_m[72 * kEpiTile];  // the 8 x 9 system, one column of the array per lane
   __shared__ int s_col[9 * kEpiTile];    // the column permutation of the pivoting
-  coord = pair_ptr(coord, nb.scratch), cand = pair_ptr(cand, nb.scratch);
-  drawn = pair_ptr(drawn, nb.scratch), fund = pair_ptr(fund, nb.scratch);
-  counts = pair_ptr(counts, nb.scratch), ccoord = pair_ptr(ccoord, nb.scratch);
-  head = pair_ptr(head, nb.head);
-  const int tx = threadIdx.x;
-  const int n = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
-  if (n < 8) return;  // uniform
-  // the launch's threads together: candidate k's coordinates to column k (k < n <= num_pts)
-  for (int k = blockIdx.x * kEpiTile + tx; k < n; k += gridDim.x * kEpiTile) {
-    const int r = clampi(cand[k], 0, num_pts - 1);  // memory safety only: the list holds record indices
-#pragma unroll
-    for (int c = 0; c < 4; ++c) ccoord[(size_t)c * num_pts + k] = coord[(size_t)c * num_pts + r];
-  }
-  const int idx = blockIdx.x * kEpiTile + tx;
-  if (idx >= num_loops) return;  // no barrier below: every thread touches only its own LDS column
-  int p[8];  // positions in the candidate list
-  ransac_sample<8>(seed + blockIdx.z, idx, n, p);
+  int idx, rec[8];
+  if (!draw_and_gather<8, 4>(coord, num_pts, cand, head, seed, num_loops, drawn, fund, counts, ccoord, nb, idx, rec)) return;
   double x1[8], y1[8], x2[8], y2[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const int r = clampi(cand[p[i]], 0, num_pts - 1);
-    drawn[(size_t)i * num_loops + idx] = r;
+    const int r = rec[i];
     x1[i] = (double)coord[r], y1[i] = (double)coord[(size_t)num_pts + r];
     x2[i] = (double)coord[2 * (size_t)num_pts + r], y2[i] = (double)coord[3 * (size_t)num_pts + r];
   }
-  counts[idx] = 0;
   // Hartley: centroid to 0, mean distance sqrt(2), per image
   EpiNorm n1, n2;
   {
@@ -168,8 +149,7 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_solve_kernel(const float *_
     }
     n1.s = sqrt(2.0) / (d1 / 8.0), n2.s = sqrt(2.0) / (d2 / 8.0);
   }
-#define M(i, j) s_m[((i) * 9 + (j)) * kEpiTile + tx]
-#define COL(j) s_col[(j) * kEpiTile + tx]
+  const LaneSystem<9> M{s_m, (int)threadIdx.x};
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const double u1 = (x1[i] - n1.cx) * n1.s, v1 = (y1[i] - n1.cy) * n1.s;
@@ -178,98 +158,35 @@ __global__ void __launch_bounds__(kEpiTile) epipolar_solve_kernel(const float *_
     M(i, 3) = v2 * u1, M(i, 4) = v2 * v1, M(i, 5) = v2;
     M(i, 6) = u1, M(i, 7) = v1, M(i, 8) = 1.0;
   }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) COL(j) = j;
-  // Gaussian elimination with complete pivoting.  A pivot of 0 or NaN divides into something not finite, which
-  // epipolar_finish turns into nine zeros.
-#pragma unroll 1
-  for (int k = 0; k < 8; ++k) {
-    double big = -1.0;
-    int pi = k, pj = k;
-    for (int i = k; i < 8; ++i)
-      for (int j = k; j < 9; ++j) {
-        const double t = fabs(M(i, j));
-        const bool more = t > big;
-        big = more ? t : big;
-        pi = more ? i : pi;
-        pj = more ? j : pj;
-      }
-    for (int j = k; j < 9; ++j) {  // rows k and pi, from column k on (in front of it the rows are done with)
-      const double a = M(k, j), b = M(pi, j);
-      M(k, j) = b, M(pi, j) = a;
-    }
-    for (int i = 0; i < 8; ++i) {  // columns k and pj, in every row: the rows above belong to the triangle
-      const double a = M(i, k), b = M(i, pj);
-      M(i, k) = b, M(i, pj) = a;
-    }
-    const int ck = COL(k), cj = COL(pj);
-    COL(k) = cj, COL(pj) = ck;
-    const double piv = M(k, k);
-    for (int i = k + 1; i < 8; ++i) {
-      const double f = M(i, k) / piv;
-      for (int j = k + 1; j < 9; ++j) M(i, j) -= f * M(k, j);
-    }
-  }
-  // back substitution from x[8] = 1 (static indices), then back through the column permutation by way of row 0 of the
-  // system, which nothing reads any more once x is complete
-  double x[9];
-  x[8] = 1.0;
-#pragma unroll
-  for (int k = 7; k >= 0; --k) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = k + 1; j < 9; ++j) s += M(k, j) * x[j];
-    x[k] = -s / M(k, k);
-  }
-  int col[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) col[j] = clampi(COL(j), 0, 8);
-#pragma unroll
-  for (int j = 0; j < 9; ++j) M(0, col[j]) = x[j];
   double fh[9], F[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) fh[j] = M(0, j);
-#undef M
-#undef COL
+  null_vector<8, 9>(M, s_col, fh);
   epipolar_finish(fh, n1, n2, F);
 #pragma unroll
   for (int i = 0; i < 9; ++i) fund[(size_t)i * num_loops + idx] = F[i];
 }
 
-// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the candidates [y * per_split, (y + 1) * per_split) -- the splits
-// are sized from the capacity num_pts, and one that lies past the candidates adds nothing.  counts were zeroed by the
-// solve kernel.
+// ransac_score's model (sift_ransac_chain.h): 9 doubles per hypothesis, counted over the candidates.
+struct EpipolarScore {
+  static constexpr int kValues = 9, kRows = 4, kMin = 8, kUnroll = 4;
+  static constexpr bool kCandidates = true;
+  typedef double value_t;
+  double t2;
+  __device__ __forceinline__ void stage(double (*s_pt)[kEpiTile], const float *__restrict__ coord, int num_pts, int tile,
+                                        int tx) const {
+    stage_rows<4>(s_pt, coord, num_pts, tile, tx);
+  }
+  __device__ __forceinline__ bool inlier(const double (&F)[9], const double (*p)[kEpiTile], int j) const {
+    return epipolar_inlier(F, p[0][j], p[1][j], p[2][j], p[3][j], t2);
+  }
+};
+
 __global__ void __launch_bounds__(kEpiTile) epipolar_score_kernel(const float *__restrict__ ccoord, int num_pts,
                                                                   int per_split, const double *__restrict__ fund,
                                                                   int num_loops, float thresh, int *__restrict__ counts,
                                                                   const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[4][kEpiTile];
-  ccoord = pair_ptr(ccoord, nb.scratch), fund = pair_ptr(fund, nb.scratch);
-  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
-  const int n_cand = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
-  if (n_cand < 8) return;  // uniform; nothing was solved: epipolar_select_kernel answers alone
-  const int tx = threadIdx.x;
-  const int loop = blockIdx.x * kEpiTile + tx;
-  const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
-  double F[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) F[i] = fund[(size_t)i * num_loops + src];
-  const double t2 = (double)thresh * (double)thresh;
-  const int begin = blockIdx.y * per_split;
-  const int end = min(n_cand, begin + per_split);
-  int cnt = 0;
-  for (int tile = begin; tile < end; tile += kEpiTile) {
-    const int n = min(kEpiTile, end - tile);
-    __syncthreads();
-    if (tx < n) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s_pt[c][tx] = (double)ccoord[(size_t)c * num_pts + tile + tx];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int j = 0; j < n; ++j) cnt += epipolar_inlier(F, s_pt[0][j], s_pt[1][j], s_pt[2][j], s_pt[3][j], t2) ? 1 : 0;
-  }
-  if (loop < num_loops && cnt) atomicAdd(&counts[loop], cnt);
+  ransac_score(EpipolarScore{(double)thresh * (double)thresh}, ccoord, num_pts, per_split, fund, num_loops, counts, head,
+               nb, s_pt);
 }
 
 // head: words kPlanarHeadCand .. kPlanarHeadCount as the planar head's (planar_compact_kernel writes the first); then as

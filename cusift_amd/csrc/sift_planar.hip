@@ -5,13 +5,12 @@
 //
 //   planar_mark_kernel      per record: candidate? member of the refit set?  SoA coordinates [x1 | y1 | x2 | y2] of ALL
 //                           records (TestHomographies counts over all of them); candidates per 256-record workgroup
+//                           (pair_mark of sift_ransac_chain.h, the body the PnP chain's marking shares)
 //   planar_compact_kernel   the candidates' record indices in ASCENDING order and their number.  No atomics: the
 //                           workgroups before this one are summed, the own keeps are ranked by keep_rank_256
 //   homography_solve_kernel (sift_homography.hip) drawing its own four samples per hypothesis from the candidate list
-//   planar_score_kernel     TestHomographies: one hypothesis per lane, its 8 coefficients (as doubles) and its count in
-//                           registers; 64-point tiles in LDS as SoA rows of doubles, every lane reads the same point (a
-//                           broadcast); grid (loops / 64, point splits); the splits' partial counts meet in one integer
-//                           atomic add per lane (order-free)
+//   planar_score_kernel     TestHomographies: ransac_score (sift_ransac_chain.h, the scoring body of all three models)
+//                           over all records with planar_inlier; grid (loops / 64, point splits)
 //   planar_select_kernel    one workgroup: the winner (the most inliers and, among equals, the FIRST, :249-254:
 //                           ransac_winner<true>), its inlier flags, ImproveHomography's rounds of weighted normal
 //                           equations, then match_error of every record and the number of records with err < limit
@@ -45,17 +44,16 @@
 // A normal matrix that is not positive definite (NaN included) keeps the previous A, as cholesky_solve8 of
 // include/homography.h does.
 // Kernels use no scratch memory and write with vector stores only.
-#include "sift_ransac.h"
+#include "sift_ransac_chain.h"
 
 namespace cusift {
 
 constexpr int kPlanarThreads = 256;  // mark / compact / select
 constexpr int kPlanarTile = 64;      // hypotheses per workgroup of the scoring kernel, points per LDS tile
+static_assert(kPlanarTile == kRansacTile && kPlanarThreads == kRansacThreads, "the shared bodies' geometry");
 constexpr int kPlanarSums = 29;
 
-// coord [4][num_pts], fitset [num_pts], block_counts [ceil(num_pts / 256)].  pts2 != NULL (cusift_ctx_set_cross_check): the
-// num_pts2 records of image 2 with cusift_match_mutual's fields; a record that is not its partner's match is neither a
-// candidate nor in the refit set, under either rule.
+// coord [4][num_pts], marks [num_pts], block_counts [ceil(num_pts / 256)]: pair_mark<false> (sift_ransac_chain.h).
 __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusift_point *__restrict__ pts, int num_pts,
                                                                      int num_pts2, int rule, float lo, float hi,
                                                                      float *__restrict__ coord,
@@ -63,32 +61,7 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_mark_kernel(const cusif
                                                                      int *__restrict__ block_counts, PlanarBatch nb,
                                                                      const cusift_point *__restrict__ pts2) {
   __shared__ int s_wave[kPlanarThreads / 64];
-  pts += (size_t)blockIdx.z * nb.records;
-  coord = pair_ptr(coord, nb.scratch), marks = pair_ptr(marks, nb.scratch);
-  block_counts = pair_ptr(block_counts, nb.scratch);
-  const int tx = threadIdx.x;
-  const int i = blockIdx.x * kPlanarThreads + tx;
-  bool cand = false;
-  if (i < num_pts) {
-    const cusift_point *p = pts + i;
-    const float x1 = p->coords2D[0], y1 = p->coords2D[1], x2 = p->match_xpos, y2 = p->match_ypos;
-    const float score = p->score, amb = p->ambiguity;
-    const int m = p->match;
-    coord[i] = x1;
-    coord[i + num_pts] = y1;
-    coord[i + 2 * (size_t)num_pts] = x2;
-    coord[i + 3 * (size_t)num_pts] = y2;
-    const bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
-    const bool inside = m >= 0 && m < num_pts2;
-    // the cross-check: the partner's own match (cusift_match_mutual's column side) must name record i
-    const bool mutual = pts2 && inside && pts2[m].match == i;
-    const unsigned char mk =
-        planar_marks(rule, score, amb, lo, hi, finite, num_pts2 < 0 || inside, pts2 != nullptr, mutual);
-    marks[i] = mk;
-    cand = mk & 1;
-  }
-  const int keeps = keep_count_256(cand, s_wave);
-  if (tx == 0) block_counts[blockIdx.x] = keeps;
+  pair_mark<false>(pts, num_pts, num_pts2, rule, lo, hi, coord, marks, block_counts, nb, pts2, s_wave);
 }
 
 // cand[k] = record index of the k-th candidate; the last workgroup writes their number into head[kPlanarHeadCand].
@@ -139,81 +112,29 @@ __device__ __forceinline__ bool planar_inlier(const double (&a)[8], float a2, fl
   return err2 < planar_mul_rz(thresh2, (double)planar_mul_rz(dd, dd));
 }
 
-// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the points [y * pts_per_split, (y + 1) * pts_per_split) -- of a
-// batch the splits are sized from the capacity, and one that lies past its pair's count adds nothing.
-// counts were zeroed by the solve kernel.
+// ransac_score's model (sift_ransac_chain.h): 8 floats per hypothesis, counted over ALL records as TestHomographies
+// does; the threshold arrives squared in fp32 from the host.
+struct PlanarScore {
+  static constexpr int kValues = 8, kRows = 4, kMin = 8, kUnroll = 2;
+  static constexpr bool kCandidates = false;
+  typedef float value_t;
+  double t2;
+  __device__ __forceinline__ void stage(double (*s_pt)[kPlanarTile], const float *__restrict__ coord, int num_pts, int tile,
+                                        int tx) const {
+    stage_rows<4>(s_pt, coord, num_pts, tile, tx);
+  }
+  __device__ __forceinline__ bool inlier(const double (&a)[8], const double (*p)[kPlanarTile], int j) const {
+    return planar_inlier(a, (float)a[2], (float)a[5], p[0][j], p[1][j], p[2][j], p[3][j], t2);
+  }
+};
+
 __global__ void __launch_bounds__(kPlanarTile) planar_score_kernel(const float *__restrict__ coord, int num_pts,
                                                                    int pts_per_split, const float *__restrict__ homo,
                                                                    int num_loops, float thresh2,
                                                                    int *__restrict__ counts,
                                                                    const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[4][kPlanarTile];
-  coord = pair_ptr(coord, nb.scratch), homo = pair_ptr(homo, nb.scratch);
-  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
-  if (head[kPlanarHeadCand] < 8) return;  // uniform; nothing was solved: planar_select_kernel answers alone
-  const int tx = threadIdx.x;
-  const int loop = blockIdx.x * kPlanarTile + tx;
-  const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
-  double a[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = (double)homo[(size_t)i * num_loops + src];
-  const float a2 = (float)a[2], a5 = (float)a[5];
-  const double t2 = (double)thresh2;
-  const int begin = blockIdx.y * pts_per_split;
-  const int end = min(pair_count(head, num_pts, nb), begin + pts_per_split);
-  int cnt = 0;
-  for (int tile = begin; tile < end; tile += kPlanarTile) {
-    const int n = min(kPlanarTile, end - tile);
-    __syncthreads();
-    if (tx < n) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s_pt[c][tx] = (double)coord[(size_t)c * num_pts + tile + tx];
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int j = 0; j < n; ++j)
-      cnt += planar_inlier(a, a2, a5, s_pt[0][j], s_pt[1][j], s_pt[2][j], s_pt[3][j], t2) ? 1 : 0;
-  }
-  if (loop < num_loops && cnt) atomicAdd(&counts[loop], cnt);
-}
-
-// cholesky_solve8 of include/homography.h on M (lower triangle read), fully unrolled so that every index is static;
-// false (a untouched) if M is not positive definite.
-__device__ __forceinline__ bool planar_cholesky8(const double (&M)[8][8], const double (&x)[8], double (&a)[8]) {
-  double L[8][8];
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      double s = M[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
-      if (i == j) {
-        ok = ok && (s > 0.0);
-        L[i][i] = sqrt(s);
-      } else {
-        L[i][j] = s / L[j][j];
-      }
-    }
-  double y[8], r[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    double s = x[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
-    y[i] = s / L[i][i];
-  }
-#pragma unroll
-  for (int i = 7; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 8; ++k) s -= L[k][i] * r[k];
-    r[i] = s / L[i][i];
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = ok ? r[i] : a[i];
-  return ok;
+  ransac_score(PlanarScore{(double)thresh2}, coord, num_pts, pts_per_split, homo, num_loops, counts, head, nb, s_pt);
 }
 
 // The reprojection error of ImproveHomography, include/homography.h:116-120 and :134-137 (the same expressions).
@@ -307,11 +228,9 @@ __global__ void __launch_bounds__(kPlanarThreads) planar_select_kernel(cusift_po
                               {t[7], t[9], t[11], t[13], t[15], t[17], t[19], t[20]}};
       const double X[8] = {t[21], t[22], t[23], t[24], t[25], t[26], t[27], t[28]};
       double r[8];
+      const bool ok = cholesky_lower<8>(M, X, r);  // cholesky_solve8 of include/homography.h
 #pragma unroll
-      for (int i = 0; i < 8; ++i) r[i] = A[i];
-      planar_cholesky8(M, X, r);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s_a[i] = r[i];
+      for (int i = 0; i < 8; ++i) s_a[i] = ok ? r[i] : A[i];
     }
     __syncthreads();
 #pragma unroll

@@ -4,17 +4,15 @@
 // (cusift_estimate_pnp), and all of it is fp64.  cusift_estimate_pnp / cusift_register_pnp enqueue, on the context's
 // stream, with no host round trip in between:
 //
-//   pnp_mark_kernel         planar_marks() plus the depth condition (three finite coords3D floats, coords3D[2] != 0); SoA
-//                           coordinates [X | Y | Z | x2 | y2] of all records; marks and per-block counts as
-//                           planar_compact_kernel reads them
+//   pnp_mark_kernel         pair_mark (sift_ransac_chain.h) with the depth condition (three finite coords3D floats,
+//                           coords3D[2] != 0); SoA coordinates [X | Y | Z | x2 | y2] of all records; marks and per-block
+//                           counts as planar_compact_kernel reads them
 //   planar_compact_kernel   (sift_planar.hip, unchanged) the candidates' record indices in ascending order, their number
-//   pnp_solve_kernel        one hypothesis per lane: its six samples drawn from the candidate list, the normalised
-//                           11 x 12 DLT system, its null vector, denormalisation, the nearest rotation, scale, [R | t].
-//                           The launch's threads together also gather the candidates' coordinates into a compacted SoA,
-//                           which is all the scoring and the refit read
-//   pnp_score_kernel        one hypothesis per lane, its twelve doubles and its count in registers; 64-candidate tiles in
-//                           LDS as SoA rows of doubles, every lane reads the same candidate (a broadcast); grid (loops /
-//                           64, candidate splits); the splits' partial counts meet in one integer atomic add per lane
+//   pnp_solve_kernel        one hypothesis per lane: draw_and_gather (sift_ransac_chain.h: the candidates' coordinates
+//                           compacted, six samples drawn from the candidate list), the normalised 11 x 12 DLT system, its
+//                           null_vector, denormalisation, the nearest rotation, scale, [R | t]
+//   pnp_score_kernel        ransac_score (sift_ransac_chain.h) over the candidates with pnp_inlier; grid (loops / 64,
+//                           candidate splits)
 //   pnp_select_kernel       one workgroup: the winner (ransac_winner<true>: among equals the first), its inlier flags, the
 //                           Gauss-Newton rounds (27 sums and the set's size over the current inliers, a 6 x 6 Cholesky
 //                           solve on one lane, Rodrigues), then match_error of every record and the candidates that fit
@@ -22,10 +20,9 @@
 // THE POSE is kept in one form everywhere -- hypotheses, winner, refit, outputs: twelve doubles, row-major [R | t] with
 // X1 = R X2 + t, the RGB-D calls' direction.  pnp_inlier() is the one test that the scoring, the flags, the refit's
 // membership, num_fit and match_error share, so a host can recount every integer of a call from the doubles it returns.
-// THE NULL VECTOR of the 11 x 12 system is found as epipolar_solve_kernel finds its own: Gaussian elimination with
-// complete pivoting in LDS, one column of the array per lane (the pivot search indexes it dynamically; consecutive lanes
-// are consecutive doubles, so every access is conflict-free), back substitution from x[11] = 1 with static indices.  132
-// doubles and 12 ints per lane: 70,656 bytes of static LDS per one-wave workgroup, two workgroups per CU.
+// THE NULL VECTOR of the 11 x 12 system is null_vector's (sift_ransac_chain.h), the elimination epipolar_solve_kernel
+// runs on its 8 x 9 system.  132 doubles and 12 ints per lane: 70,656 bytes of static LDS per one-wave workgroup, two
+// workgroups per CU.
 // THE REFIT's normal matrix is a sum of 2 x 6 Jacobian outer products: positive definite unless the set is degenerate,
 // so one lane's Cholesky needs no pivot search -- 6 square roots and 21 divisions where the epipolar refit runs 288
 // Jacobi rotations.  A pivot that is not > 0 (NaN included) keeps the previous pose and ends the refit.  The partial
@@ -37,19 +34,15 @@
 // pnp_select_kernel writes match_error to an array of its own: the records are read only.
 // Kernels use no scratch memory and write with vector stores only.
 #include "sift_epipolar.h"
+#include "sift_ransac_chain.h"
 
 namespace cusift {
 
 constexpr int kPnPThreads = 256;  // mark / select
 constexpr int kPnPTile = 64;      // hypotheses per workgroup of the solve and scoring kernels, candidates per LDS tile
+static_assert(kPnPTile == kRansacTile && kPnPThreads == kRansacThreads, "the shared bodies' geometry");
 constexpr int kPnPRows = 11, kPnPCols = 12;
 constexpr int kPnPSums = 28;      // 21 of J^T J, 6 of J^T r, the size of the set
-
-__device__ __forceinline__ bool pnp_finite(double x) { return fabs(x) < __builtin_inf(); }  // a NaN fails
-
-__device__ __forceinline__ double pnp_pick(int i, double a0, double a1, double a2) {
-  return i == 0 ? a0 : (i == 1 ? a1 : a2);
-}
 
 // The inlier test, in exactly the expressions of include/cusift_amd_extras.h: no division, no root.  xs = x2 - px and
 // ys = y2 - py.  *e2 and *den leave for match_error.  A NaN fails; a point that is not in front of the camera fails.
@@ -81,15 +74,15 @@ __device__ __forceinline__ bool pnp_finish(const double (&p)[12], double (&rt)[1
   // the eigenpairs in descending order, the first among equals
   const double l0 = g[0][0], l1 = g[1][1], l2 = g[2][2];
   int i1 = 0;
-  i1 = l1 > pnp_pick(i1, l0, l1, l2) ? 1 : i1;
-  i1 = l2 > pnp_pick(i1, l0, l1, l2) ? 2 : i1;
+  i1 = l1 > pick3(i1, l0, l1, l2) ? 1 : i1;
+  i1 = l2 > pick3(i1, l0, l1, l2) ? 2 : i1;
   const int ia = i1 == 0 ? 1 : 0, ib = i1 == 2 ? 1 : 2;  // the other two, ascending
-  const int i2 = pnp_pick(ib, l0, l1, l2) > pnp_pick(ia, l0, l1, l2) ? ib : ia;
-  const double lam1 = pnp_pick(i1, l0, l1, l2), lam2 = pnp_pick(i2, l0, l1, l2);
+  const int i2 = pick3(ib, l0, l1, l2) > pick3(ia, l0, l1, l2) ? ib : ia;
+  const double lam1 = pick3(i1, l0, l1, l2), lam2 = pick3(i2, l0, l1, l2);
   const double s1 = sqrt(lam1 > 0.0 ? lam1 : 0.0), s2 = sqrt(lam2 > 0.0 ? lam2 : 0.0);
   double v1[3], v2[3], v3[3], u1[3], u2[3], u3[3], w[3], mv3[3];
 #pragma unroll
-  for (int r = 0; r < 3; ++r) v1[r] = pnp_pick(i1, v[r][0], v[r][1], v[r][2]), v2[r] = pnp_pick(i2, v[r][0], v[r][1], v[r][2]);
+  for (int r = 0; r < 3; ++r) v1[r] = pick3(i1, v[r][0], v[r][1], v[r][2]), v2[r] = pick3(i2, v[r][0], v[r][1], v[r][2]);
   v3[0] = v1[1] * v2[2] - v1[2] * v2[1];
   v3[1] = v1[2] * v2[0] - v1[0] * v2[2];
   v3[2] = v1[0] * v2[1] - v1[1] * v2[0];
@@ -127,14 +120,14 @@ __device__ __forceinline__ bool pnp_finish(const double (&p)[12], double (&rt)[1
     out[4 * r + 3] = -((R21[r] * t21[0] + R21[3 + r] * t21[1]) + R21[6 + r] * t21[2]);
   }
 #pragma unroll
-  for (int i = 0; i < 12; ++i) ok = ok && pnp_finite(out[i]);
+  for (int i = 0; i < 12; ++i) ok = ok && finite_d(out[i]);
 #pragma unroll
   for (int i = 0; i < 12; ++i) rt[i] = ok ? out[i] : 0.0;
   return ok;
 }
 
-// coord [5][num_pts], block_counts [ceil(num_pts / 256)].  pts2 != NULL (cusift_ctx_set_cross_check): as
-// planar_mark_kernel's.
+// coord [5][num_pts] = [X | Y | Z | x2 | y2], marks, block_counts: pair_mark<true> (sift_ransac_chain.h), planar_mark_kernel's
+// body plus the depth condition.
 __global__ void __launch_bounds__(kPnPThreads) pnp_mark_kernel(const cusift_point *__restrict__ pts, int num_pts,
                                                                int num_pts2, int rule, float lo, float hi,
                                                                float *__restrict__ coord,
@@ -142,31 +135,7 @@ __global__ void __launch_bounds__(kPnPThreads) pnp_mark_kernel(const cusift_poin
                                                                int *__restrict__ block_counts,
                                                                const cusift_point *__restrict__ pts2) {
   __shared__ int s_wave[kPnPThreads / 64];
-  const int tx = threadIdx.x;
-  const int i = blockIdx.x * kPnPThreads + tx;
-  bool cand = false;
-  if (i < num_pts) {
-    const cusift_point *p = pts + i;
-    const float x1 = p->coords2D[0], y1 = p->coords2D[1], x2 = p->match_xpos, y2 = p->match_ypos;
-    const float X = p->coords3D[0], Y = p->coords3D[1], Z = p->coords3D[2];
-    const float score = p->score, amb = p->ambiguity;
-    const int m = p->match;
-    coord[i] = X;
-    coord[i + num_pts] = Y;
-    coord[i + 2 * (size_t)num_pts] = Z;
-    coord[i + 3 * (size_t)num_pts] = x2;
-    coord[i + 4 * (size_t)num_pts] = y2;
-    const bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
-    const bool depth = planar_finite(X) && planar_finite(Y) && planar_finite(Z) && Z != 0.0f;
-    const bool inside = m >= 0 && m < num_pts2;
-    const bool mutual = pts2 && inside && pts2[m].match == i;
-    const unsigned char mk =
-        planar_marks(rule, score, amb, lo, hi, finite && depth, num_pts2 < 0 || inside, pts2 != nullptr, mutual);
-    marks[i] = mk;
-    cand = mk & 1;
-  }
-  const int keeps = keep_count_256(cand, s_wave);
-  if (tx == 0) block_counts[blockIdx.x] = keeps;
+  pair_mark<true>(pts, num_pts, num_pts2, rule, lo, hi, coord, marks, block_counts, PlanarBatch{}, pts2, s_wave);
 }
 
 // drawn [6][num_loops] (record indices), pose [12][num_loops], counts [num_loops] (zeroed here for the scoring kernel),
@@ -179,34 +148,16 @@ __global__ void __launch_bounds__(kPnPTile) pnp_solve_kernel(const float *__rest
                                                              float *__restrict__ ccoord, PlanarBatch nb) {
   __shared__ double s_m[kPnPRows * kPnPCols * kPnPTile];  // the 11 x 12 system, one column of the array per lane
   __shared__ int s_col[kPnPCols * kPnPTile];              // the column permutation of the pivoting
-  coord = pair_ptr(coord, nb.scratch), cand = pair_ptr(cand, nb.scratch);
-  drawn = pair_ptr(drawn, nb.scratch), pose = pair_ptr(pose, nb.scratch);
-  counts = pair_ptr(counts, nb.scratch), ccoord = pair_ptr(ccoord, nb.scratch);
-  head = pair_ptr(head, nb.head);
-  seed += blockIdx.z;  // pair p draws from seed + p, 64-bit and wrapping
-  const int tx = threadIdx.x;
-  const int n = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
-  if (n < 6) return;  // uniform
-  // the launch's threads together: candidate k's coordinates to column k (k < n <= num_pts)
-  for (int k = blockIdx.x * kPnPTile + tx; k < n; k += gridDim.x * kPnPTile) {
-    const int r = clampi(cand[k], 0, num_pts - 1);  // memory safety only: the list holds record indices
-#pragma unroll
-    for (int c = 0; c < 5; ++c) ccoord[(size_t)c * num_pts + k] = coord[(size_t)c * num_pts + r];
-  }
-  const int idx = blockIdx.x * kPnPTile + tx;
-  if (idx >= num_loops) return;  // no barrier below: every thread touches only its own LDS column
-  int p[6];  // positions in the candidate list
-  ransac_sample<6>(seed, idx, n, p);
+  int idx, rec[6];
+  if (!draw_and_gather<6, 5>(coord, num_pts, cand, head, seed, num_loops, drawn, pose, counts, ccoord, nb, idx, rec)) return;
   double X[6], Y[6], Z[6], u[6], v[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    const int r = clampi(cand[p[i]], 0, num_pts - 1);
-    drawn[(size_t)i * num_loops + idx] = r;
+    const int r = rec[i];
     X[i] = (double)coord[r], Y[i] = (double)coord[(size_t)num_pts + r], Z[i] = (double)coord[2 * (size_t)num_pts + r];
     u[i] = ((double)coord[3 * (size_t)num_pts + r] - cam.px) / cam.fx;
     v[i] = ((double)coord[4 * (size_t)num_pts + r] - cam.py) / cam.fy;
   }
-  counts[idx] = 0;
   // the 3-D samples: centroid to 0, mean distance sqrt(3)
   double cx, cy, cz, s;
   {
@@ -222,8 +173,7 @@ __global__ void __launch_bounds__(kPnPTile) pnp_solve_kernel(const float *__rest
     }
     s = sqrt(3.0) / (d / 6.0);
   }
-#define M(i, j) s_m[((i) * kPnPCols + (j)) * kPnPTile + tx]
-#define COL(j) s_col[(j) * kPnPTile + tx]
+  const LaneSystem<kPnPCols> M{s_m, (int)threadIdx.x};
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     const double xn = (X[i] - cx) * s, yn = (Y[i] - cy) * s, zn = (Z[i] - cz) * s;
@@ -237,59 +187,8 @@ __global__ void __launch_bounds__(kPnPTile) pnp_solve_kernel(const float *__rest
       M(2 * i + 1, 11) = -v[i];
     }
   }
-#pragma unroll
-  for (int j = 0; j < kPnPCols; ++j) COL(j) = j;
-  // Gaussian elimination with complete pivoting.  A pivot of 0 or NaN divides into something not finite, which
-  // pnp_finish turns into twelve zeros.
-#pragma unroll 1
-  for (int k = 0; k < kPnPRows; ++k) {
-    double big = -1.0;
-    int pi = k, pj = k;
-    for (int i = k; i < kPnPRows; ++i)
-      for (int j = k; j < kPnPCols; ++j) {
-        const double t = fabs(M(i, j));
-        const bool more = t > big;
-        big = more ? t : big;
-        pi = more ? i : pi;
-        pj = more ? j : pj;
-      }
-    for (int j = k; j < kPnPCols; ++j) {  // rows k and pi, from column k on (in front of it the rows are done with)
-      const double a = M(k, j), b = M(pi, j);
-      M(k, j) = b, M(pi, j) = a;
-    }
-    for (int i = 0; i < kPnPRows; ++i) {  // columns k and pj, in every row: the rows above belong to the triangle
-      const double a = M(i, k), b = M(i, pj);
-      M(i, k) = b, M(i, pj) = a;
-    }
-    const int ck = COL(k), cj = COL(pj);
-    COL(k) = cj, COL(pj) = ck;
-    const double piv = M(k, k);
-    for (int i = k + 1; i < kPnPRows; ++i) {
-      const double f = M(i, k) / piv;
-      for (int j = k + 1; j < kPnPCols; ++j) M(i, j) -= f * M(k, j);
-    }
-  }
-  // back substitution from x[11] = 1 (static indices), then back through the column permutation by way of row 0 of the
-  // system, which nothing reads any more once x is complete
-  double x[kPnPCols];
-  x[kPnPCols - 1] = 1.0;
-#pragma unroll
-  for (int k = kPnPRows - 1; k >= 0; --k) {
-    double acc = 0.0;
-#pragma unroll
-    for (int j = k + 1; j < kPnPCols; ++j) acc += M(k, j) * x[j];
-    x[k] = -acc / M(k, k);
-  }
-  int col[kPnPCols];
-#pragma unroll
-  for (int j = 0; j < kPnPCols; ++j) col[j] = clampi(COL(j), 0, kPnPCols - 1);
-#pragma unroll
-  for (int j = 0; j < kPnPCols; ++j) M(0, col[j]) = x[j];
   double ph[12];
-#pragma unroll
-  for (int j = 0; j < kPnPCols; ++j) ph[j] = M(0, j);
-#undef M
-#undef COL
+  null_vector<kPnPRows, kPnPCols>(M, s_col, ph);
   // denormalise: P = P^ T with T = [s I | -s c; 0 0 0 1]
   const double tx3 = -(s * cx), ty3 = -(s * cy), tz3 = -(s * cz);
   double P[12];
@@ -309,86 +208,48 @@ __global__ void __launch_bounds__(kPnPTile) pnp_solve_kernel(const float *__rest
   for (int i = 0; i < 12; ++i) pose[(size_t)i * num_loops + idx] = rt[i];
 }
 
-// blockIdx.x: 64 hypotheses (one per lane); blockIdx.y: the candidates [y * per_split, (y + 1) * per_split) -- the splits
-// are sized from the capacity num_pts, and one that lies past the candidates adds nothing.  counts were zeroed by the
-// solve kernel.
+// ransac_score's model (sift_ransac_chain.h): 12 doubles per hypothesis, counted over the candidates; the pixel rows are
+// staged with the principal point taken off, as pnp_inlier wants them.
+struct PnPScore {
+  static constexpr int kValues = 12, kRows = 5, kMin = 6, kUnroll = 4;
+  static constexpr bool kCandidates = true;
+  typedef double value_t;
+  PnPCam cam;
+  double t2;
+  __device__ __forceinline__ void stage(double (*s_pt)[kPnPTile], const float *__restrict__ ccoord, int num_pts, int tile,
+                                        int tx) const {
+    stage_rows<3>(s_pt, ccoord, num_pts, tile, tx);
+    s_pt[3][tx] = (double)ccoord[3 * (size_t)num_pts + tile + tx] - cam.px;
+    s_pt[4][tx] = (double)ccoord[4 * (size_t)num_pts + tile + tx] - cam.py;
+  }
+  __device__ __forceinline__ bool inlier(const double (&rt)[12], const double (*p)[kPnPTile], int j) const {
+    return pnp_inlier(rt, cam, p[0][j], p[1][j], p[2][j], p[3][j], p[4][j], t2);
+  }
+};
+
 __global__ void __launch_bounds__(kPnPTile) pnp_score_kernel(const float *__restrict__ ccoord, int num_pts, int per_split,
                                                              const double *__restrict__ pose, int num_loops, PnPCam cam,
                                                              float thresh, int *__restrict__ counts,
                                                              const int *__restrict__ head, PlanarBatch nb) {
   __shared__ double s_pt[5][kPnPTile];
-  ccoord = pair_ptr(ccoord, nb.scratch), pose = pair_ptr(pose, nb.scratch);
-  counts = pair_ptr(counts, nb.scratch), head = pair_ptr(head, nb.head);
-  const int n_cand = min(head[kPlanarHeadCand], pair_count(head, num_pts, nb));
-  if (n_cand < 6) return;  // uniform; nothing was solved: pnp_select_kernel answers alone
-  const int tx = threadIdx.x;
-  const int loop = blockIdx.x * kPnPTile + tx;
-  const int src = loop < num_loops ? loop : num_loops - 1;  // lanes past the end score a copy and drop the result
-  double rt[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) rt[i] = pose[(size_t)i * num_loops + src];
-  const double t2 = (double)thresh * (double)thresh;
-  const int begin = blockIdx.y * per_split;
-  const int end = min(n_cand, begin + per_split);
-  int cnt = 0;
-  for (int tile = begin; tile < end; tile += kPnPTile) {
-    const int n = min(kPnPTile, end - tile);
-    __syncthreads();
-    if (tx < n) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) s_pt[c][tx] = (double)ccoord[(size_t)c * num_pts + tile + tx];
-      s_pt[3][tx] = (double)ccoord[3 * (size_t)num_pts + tile + tx] - cam.px;
-      s_pt[4][tx] = (double)ccoord[4 * (size_t)num_pts + tile + tx] - cam.py;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int j = 0; j < n; ++j)
-      cnt += pnp_inlier(rt, cam, s_pt[0][j], s_pt[1][j], s_pt[2][j], s_pt[3][j], s_pt[4][j], t2) ? 1 : 0;
-  }
-  if (loop < num_loops && cnt) atomicAdd(&counts[loop], cnt);
+  ransac_score(PnPScore{cam, (double)thresh * (double)thresh}, ccoord, num_pts, per_split, pose, num_loops, counts, head, nb,
+               s_pt);
 }
 
-// Solves the 6 x 6 system A p = -g from the 27 sums (A's upper triangle row by row, then g) by Cholesky, static indices.
+// Solves the 6 x 6 system A p = -g from the 27 sums (A's upper triangle row by row, then g) by cholesky_lower.
 // false: a pivot is not > 0 (NaN included) or the step is not finite.
 __device__ __forceinline__ bool pnp_step(const double *s_sum, double (&p)[6]) {
-  double L[6][6], y[6];
+  double A[6][6], g[6];
   int q = 0;
 #pragma unroll
   for (int i = 0; i < 6; ++i)
 #pragma unroll
-    for (int j = i; j < 6; ++j) L[j][i] = s_sum[q++];  // the lower triangle holds A
-  bool ok = true;
+    for (int j = i; j < 6; ++j) A[j][i] = s_sum[q++];  // the lower triangle holds A
 #pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = L[j][j];
+  for (int i = 0; i < 6; ++i) g[i] = -s_sum[21 + i];
+  bool ok = cholesky_lower<6>(A, g, p);
 #pragma unroll
-    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-    ok = ok && d > 0.0;
-    const double r = sqrt(d);
-    L[j][j] = r;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double a = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) a -= L[i][k] * L[j][k];
-      L[i][j] = a / r;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {  // L y = -g
-    double a = -s_sum[21 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) a -= L[i][k] * y[k];
-    y[i] = a / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {  // L^T p = y
-    double a = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) a -= L[k][i] * p[k];
-    p[i] = a / L[i][i];
-    ok = ok && pnp_finite(p[i]);
-  }
+  for (int i = 0; i < 6; ++i) ok = ok && finite_d(p[i]);
   return ok;
 }
 
@@ -404,7 +265,7 @@ __device__ __forceinline__ bool pnp_update(const double (&p)[6], const double (&
     out[4 * i + 3] = rt[4 * i + 3] - ((out[4 * i] * p[3] + out[4 * i + 1] * p[4]) + out[4 * i + 2] * p[5]);
   }
 #pragma unroll
-  for (int i = 0; i < 12; ++i) ok = ok && pnp_finite(out[i]);
+  for (int i = 0; i < 12; ++i) ok = ok && finite_d(out[i]);
   return ok;
 }
 

@@ -25,12 +25,6 @@ namespace cusift {
 
 constexpr int kPoseThreads = 256;
 
-__device__ __forceinline__ bool pose_finite(double x) { return fabs(x) < __builtin_inf(); }  // a NaN fails
-
-__device__ __forceinline__ double pose_pick(int i, double a0, double a1, double a2) {
-  return i == 0 ? a0 : (i == 1 ? a1 : a2);
-}
-
 // The decomposition of E = K2^T (F K1): R[0] = U W V^T, R[1] = U W^T V^T (row-major R21), t = u3, the singular values.
 // The four candidates are (R[0], +t), (R[0], -t), (R[1], +t), (R[1], -t).  ok == false: a degenerate answer.
 struct PoseFrame {
@@ -41,7 +35,7 @@ struct PoseFrame {
 __device__ __forceinline__ void pose_decompose(const double (&F)[9], const PoseCams &k, PoseFrame &p) {
   bool any = false, fin = true;
 #pragma unroll
-  for (int i = 0; i < 9; ++i) any = any || F[i] != 0.0, fin = fin && pose_finite(F[i]);
+  for (int i = 0; i < 9; ++i) any = any || F[i] != 0.0, fin = fin && finite_d(F[i]);
   // A = F K1, E = K2^T A
   double A[3][3], E[3][3];
 #pragma unroll
@@ -65,17 +59,17 @@ __device__ __forceinline__ void pose_decompose(const double (&F)[9], const PoseC
   epipolar_jacobi<3>(g, v, kEpiSweeps3);
   const double l0 = g[0][0], l1 = g[1][1], l2 = g[2][2];
   int i1 = 0;
-  i1 = l1 > pose_pick(i1, l0, l1, l2) ? 1 : i1;
-  i1 = l2 > pose_pick(i1, l0, l1, l2) ? 2 : i1;
+  i1 = l1 > pick3(i1, l0, l1, l2) ? 1 : i1;
+  i1 = l2 > pick3(i1, l0, l1, l2) ? 2 : i1;
   const int ia = i1 == 0 ? 1 : 0, ib = i1 == 2 ? 1 : 2;  // the other two, ascending
-  const int i2 = pose_pick(ib, l0, l1, l2) > pose_pick(ia, l0, l1, l2) ? ib : ia;
+  const int i2 = pick3(ib, l0, l1, l2) > pick3(ia, l0, l1, l2) ? ib : ia;
   const int i3 = 3 - i1 - i2;
-  const double lam[3] = {pose_pick(i1, l0, l1, l2), pose_pick(i2, l0, l1, l2), pose_pick(i3, l0, l1, l2)};
+  const double lam[3] = {pick3(i1, l0, l1, l2), pick3(i2, l0, l1, l2), pick3(i3, l0, l1, l2)};
 #pragma unroll
   for (int i = 0; i < 3; ++i) p.sigma[i] = sqrt(lam[i] > 0.0 ? lam[i] : 0.0);
   double v1[3], v2[3], v3[3], u1[3], u2[3], u3[3];
 #pragma unroll
-  for (int r = 0; r < 3; ++r) v1[r] = pose_pick(i1, v[r][0], v[r][1], v[r][2]), v2[r] = pose_pick(i2, v[r][0], v[r][1], v[r][2]);
+  for (int r = 0; r < 3; ++r) v1[r] = pick3(i1, v[r][0], v[r][1], v[r][2]), v2[r] = pick3(i2, v[r][0], v[r][1], v[r][2]);
   v3[0] = v1[1] * v2[2] - v1[2] * v2[1];
   v3[1] = v1[2] * v2[0] - v1[0] * v2[2];
   v3[2] = v1[0] * v2[1] - v1[1] * v2[0];
@@ -99,7 +93,7 @@ __device__ __forceinline__ void pose_decompose(const double (&F)[9], const PoseC
 #pragma unroll
   for (int r = 0; r < 3; ++r) ev3[r] = (E[r][0] * v3[0] + E[r][1] * v3[1]) + E[r][2] * v3[2];
   const double s3 = fabs((u3[0] * ev3[0] + u3[1] * ev3[1]) + u3[2] * ev3[2]);
-  p.sigma[2] = pose_finite(s3) ? s3 : p.sigma[2];
+  p.sigma[2] = finite_d(s3) ? s3 : p.sigma[2];
   bool out = true;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -107,10 +101,10 @@ __device__ __forceinline__ void pose_decompose(const double (&F)[9], const PoseC
     for (int j = 0; j < 3; ++j) {
       p.R[0][3 * i + j] = (u2[i] * v1[j] - u1[i] * v2[j]) + u3[i] * v3[j];
       p.R[1][3 * i + j] = (u1[i] * v2[j] - u2[i] * v1[j]) + u3[i] * v3[j];
-      out = out && pose_finite(p.R[0][3 * i + j]) && pose_finite(p.R[1][3 * i + j]);
+      out = out && finite_d(p.R[0][3 * i + j]) && finite_d(p.R[1][3 * i + j]);
     }
     p.t[i] = u3[i];
-    out = out && pose_finite(u3[i]) && pose_finite(p.sigma[i]);
+    out = out && finite_d(u3[i]) && finite_d(p.sigma[i]);
   }
   p.ok = any && fin && p.sigma[1] > 0.0 && out;
 }

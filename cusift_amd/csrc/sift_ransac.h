@@ -21,6 +21,13 @@ namespace cusift {
 constexpr int kRansacThreads = 256;  // the workgroup of every *_256 helper and of ransac_winner: four waves
 constexpr int kRansacRedraws = 64;
 
+__device__ __forceinline__ bool finite_d(double x) { return fabs(x) < __builtin_inf(); }  // a NaN fails
+
+// a_i for a run-time i in {0, 1, 2}: selects, so the three stay in registers
+__device__ __forceinline__ double pick3(int i, double a0, double a1, double a2) {
+  return i == 0 ? a0 : (i == 1 ? a1 : a2);
+}
+
 __device__ __forceinline__ unsigned long long ransac_mix(unsigned long long z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

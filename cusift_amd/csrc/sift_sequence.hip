@@ -40,7 +40,7 @@
 // i < n1 with 0 <= match < n2, inside the n2 > 0 branch, so no unwritten row is ever read.  In a self pair (a, a) every
 // record is its own best in both directions.
 // No scratch memory, vector stores only.
-#include "sift_ransac.h"
+#include "sift_ransac_chain.h"
 
 namespace cusift {
 
@@ -88,9 +88,10 @@ __global__ void __launch_bounds__(kSequenceSelectThreads) sequence_select_kernel
   if (tx == 0) sel_count[pair] = base;
 }
 
-// The marking of one record of pair blockIdx.z, shared by the two kernels below.  kPnP == false: the coordinate rows are
-// [x1 | y1 | x2 | y2].  kPnP == true: [X | Y | Z | x2 | y2] with (X, Y, Z) = coords3D of frame 1's record, and a
-// candidate also needs pnp_mark_kernel's depth condition -- three finite floats, Z != 0 -- in place of finite x1, y1.
+// The marking of one record of pair blockIdx.z, shared by the two kernels below: what pair_mark (sift_ransac_chain.h)
+// reads from a record's match fields comes from the pair's match rows here; the predicate (mark_record) and the
+// coordinate rows (write_coord_rows) are the same.  kPnP: [X | Y | Z | x2 | y2] with (X, Y, Z) = coords3D of frame 1's
+// record, and the depth condition.
 template <bool kPnP>
 __device__ __forceinline__ void sequence_mark(const cusift_point *__restrict__ points,
                                               const unsigned int *__restrict__ counters, int max_pts,
@@ -123,28 +124,15 @@ __device__ __forceinline__ void sequence_mark(const cusift_point *__restrict__ p
       const bool valid = m >= 0 && m < n2;
       const cusift_point *q = sift2 + (valid ? m : 0);  // the partner cusift_match takes the position from
       x2 = q->coords2D[0], y2 = q->coords2D[1];
-      bool finite = planar_finite(x1) && planar_finite(y1) && planar_finite(x2) && planar_finite(y2);
-      if (kPnP) finite = finite && planar_finite(X) && planar_finite(Y) && planar_finite(Z) && Z != 0.0f;
       bool mutual = false;
       if (rows_back) {  // the cross-check: back row m was written (i < n1, m < n2)
         const cusift_match_row *back = rows_back + (size_t)pair * max_pts + (valid ? m : 0);
         mutual = valid && __float_as_int((*reinterpret_cast<const f4 *>(back))[2]) == i;
       }
-      mk = planar_marks(rule, score, amb, lo, hi, finite, valid, rows_back != nullptr, mutual);
+      mk = mark_record<kPnP>(rule, score, amb, lo, hi, x1, y1, x2, y2, X, Y, Z, valid, rows_back != nullptr, mutual);
       cand = mk & 1;
     }
-    if (kPnP) {
-      coord[i] = X;
-      coord[i + max_pts] = Y;
-      coord[i + 2 * (size_t)max_pts] = Z;
-      coord[i + 3 * (size_t)max_pts] = x2;
-      coord[i + 4 * (size_t)max_pts] = y2;
-    } else {
-      coord[i] = x1;
-      coord[i + max_pts] = y1;
-      coord[i + 2 * (size_t)max_pts] = x2;
-      coord[i + 3 * (size_t)max_pts] = y2;
-    }
+    write_coord_rows<kPnP>(coord, max_pts, i, x1, y1, x2, y2, X, Y, Z);
     marks[i] = mk;
   }
   const int keeps = keep_count_256(cand, s_wave);

@@ -479,9 +479,12 @@ def test_header_library_and_binding_carry_the_pnp_calls():
                  "R21[3 * i + j] = (u1[i] * v1[j] + u2[i] * v2[j]) + u3[i] * v3[j];",
                  "const double ju[6] = {g2 * b, g0 * c - g2 * a, -(g0 * b), g0, 0.0, g2};",
                  "const double jv[6] = {h2 * b - h1 * c, -(h2 * a), h1 * a, 0.0, h1, h2};",
-                 "ransac_sample<6>(seed, idx, n, p);", "ransac_winner<true>(counts, num_loops, s_key, best, best_count);",
+                 "draw_and_gather<6, 5>(", "ransac_winner<true>(counts, num_loops, s_key, best, best_count);",
                  "wave_tree_sum<kPnPSums>(s, s_part, s_sum, tx);"):
         assert expr in kernels, expr
+    # the six samples are drawn in the solve front that the PnP and the epipolar chain share
+    chain = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_ransac_chain.h")).read()
+    assert "ransac_sample<N>(seed, idx, n, p);" in chain and "template <int N, int kRows>" in chain
     # the scoring grid that tests/test_pnp_sizes.py plans for; tests/test_register_source.py pins the planner and its call
     # (one grid layer per pair); the launch itself, not a comment about it
     host = open(os.path.join(ROOT, "cusift_amd", "csrc", "sift_register.hip")).read()

@@ -324,12 +324,21 @@ def test_call_sites_of_score_splits_pass_what_the_plans_here_assume():
     for src, const in (("sift_epipolar.hip", "constexpr int kEpiTile = 64;"), ("sift_rigid.hip", "constexpr int kRigidTile = 256;"),
                        ("sift_rigid.hip", "constexpr int kRigidThreads = 256;"), ("sift_planar.hip", "constexpr int kPlanarTile = 64;"),
                        ("sift_planar.hip", "constexpr int kPlanarThreads = 256;"), ("sift_rgbd.hip", "constexpr int kSelectThreads = 256;"),
-                       ("sift_pose.hip", "constexpr int kPoseThreads = 256;")):
+                       ("sift_pose.hip", "constexpr int kPoseThreads = 256;"),
+                       ("sift_pnp.hip", "constexpr int kPnPTile = 64;"),
+                       ("sift_ransac_chain.h", "constexpr int kRansacTile = 64;"),
+                       # each unit's tile is the one of the scoring body it shares
+                       ("sift_epipolar.hip", "static_assert(kEpiTile == kRansacTile &&"),
+                       ("sift_planar.hip", "static_assert(kPlanarTile == kRansacTile &&"),
+                       ("sift_pnp.hip", "static_assert(kPnPTile == kRansacTile &&")):
         assert const in open(os.path.join(CSRC, src)).read(), const
-    # the walks test_ransac_sizes.py is about stand as its plans restate them
-    for src, walk in (("sift_epipolar.hip", "for (int tile = begin; tile < end; tile += kEpiTile) {"),
+    # the walks test_ransac_sizes.py is about stand as its plans restate them: one for the planar, epipolar and PnP
+    # scoring kernels (ransac_score), which each unit's kernel calls
+    for src, walk in (("sift_ransac_chain.h", "for (int tile = begin; tile < end; tile += kRansacTile) {"),
+                      ("sift_epipolar.hip", "ransac_score(EpipolarScore{"),
+                      ("sift_planar.hip", "ransac_score(PlanarScore{"),
+                      ("sift_pnp.hip", "ransac_score(PnPScore{"),
                       ("sift_rigid.hip", "for (int tile = begin; tile < end; tile += kRigidTile) {"),
-                      ("sift_planar.hip", "for (int tile = begin; tile < end; tile += kPlanarTile) {"),
                       ("sift_planar.hip", "for (int b = tx; b < (int)blockIdx.x; b += kPlanarThreads) before += block_counts[b];"),
                       ("sift_rgbd.hip", "for (int b = tx; b < (int)blockIdx.x; b += kSelectThreads) before += block_counts[b];")):
         assert walk in open(os.path.join(CSRC, src)).read(), walk
