@@ -438,7 +438,20 @@ def planted_cost(sc, **params):
 
 
 def run_model(sc, **kw):
+    """The model on a scene dictionary; the scene's "origin" (absent: 0) is the camera's, unless the call names one."""
+    kw.setdefault("origin", sc.get("origin", 0.0))
     return bundle_model(sc["xy"], sc["max_pts"], sc["offsets"], sc["obs"], sc["poses"], *sc["cam"], sc["points"], **kw)
+
+
+def with_origin(sc, origin):
+    """The scene seen through a camera whose cx / cy count from `origin`: the pixels moved by -origin (rounded to float32
+    again: they are this scene's pixels, not exact copies), the entry points triangulated with that camera.  The
+    geometry is the scene's; only a reader that drops or flips the origin sees another one."""
+    from tracks_model import triangulate_model
+
+    xy = (sc["xy"].astype(f64) - origin).astype(np.float32)
+    points, _ = triangulate_model(xy, sc["max_pts"], sc["offsets"], sc["obs"], sc["poses"], *sc["cam"], origin=origin)
+    return dict(sc, xy=xy, points=points, origin=origin)
 
 
 FILL = -7.0  # what device_bundle puts into every output entry before the call
@@ -498,7 +511,7 @@ class DeviceBundle:
     def camera(self):
         from cusift_amd import capi
 
-        return capi.Camera(*self.sc["cam"])
+        return capi.Camera(*self.sc["cam"], origin=self.sc.get("origin", 0.0))
 
     def records_back(self):
         back = np.empty_like(self.recs)

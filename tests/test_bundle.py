@@ -8,6 +8,14 @@ clamp, a failed track pivot without and with a failed Cholesky pivot; the refusa
 Measured on an MI355X, largest deviation of the cases added with the stops: fixed_none 7.65e-13, min_decrease 2.79e-14,
 lambda_min 8.99e-14; lambda_max, track_pivot and cholesky_pivot 0 (nothing is accepted: every output is an entry value).
 
+The pixel origin (px = cx - origin): Scene A's default case through a camera (cx + 1, cy + 1, origin 1) must give the
+bytes of (cx, cy, origin 0), and the small scene on pixels generated for origin 0.5 (bundle_model.with_origin) must equal
+the model called with 0.5 -- measured 1.76e-13 --, which tests/test_bundle_model.py shows to end 4e-3 in the poses away
+from the model with the origin dropped.  Tried once in a scratch build that was never committed, `cx + origin` in
+cusift_bundle_adjust: both origin tests fail (deviations 0.29 and 0.084 from the model), and so does
+tests/test_bundle_batch.py on the bytes of its origin-1 call; every other case of this file and of
+tests/test_bundle_sizes.py stays green (origin 0 throughout).
+
 The bar for fp64 against a numpy restatement is the project's: 1e-9 * max(1, |value|) on every pose entry, point row and
 cost.  Flags are compared on the iterations where the model's own relative cost change exceeds 1e-6 -- below that the
 decision can rest on rounding -- and the iteration counts stop before the tail where the model's own decisions are
@@ -104,6 +112,51 @@ def test_scene_a_equals_the_model(ctx, name):
             assert out["history"][0, 3] == 0 and np.isinf(out["history"][0, 1])
         if name in ("default", "far"):
             assert out["summary"][1] <= bm.planted_cost(sc)
+    finally:
+        dev.close()
+
+
+def test_origin_one_is_origin_zero_to_the_byte(ctx):
+    """px = cx - origin: Scene A's 320 and 240 plus 1 are exact in float32, so a camera (cx + 1, cy + 1, origin 1) is the
+    camera (cx, cy, origin 0) and every output byte of the default case must be the same."""
+    sc, kw = bm.scene_a(), CASES["default"][1]
+    fx, fy, cx, cy = sc["cam"]
+    assert np.float32(cx + 1.0) - np.float32(1.0) == np.float32(cx) and np.float32(cy + 1.0) - np.float32(1.0) == np.float32(cy)
+    one = dict(sc, cam=(fx, fy, cx + 1.0, cy + 1.0), origin=1.0)
+    outs = []
+    for s in (sc, one):
+        dev = bm.DeviceBundle(ctx, s)
+        try:
+            assert dev.camera().origin == s.get("origin", 0.0) and dev.camera().cx == s["cam"][2]
+            outs.append(dev.run(**kw))
+        finally:
+            dev.close()
+    compare(outs[1], model_of("default"), sc, kw["iterations"])
+    assert outs[0]["summary"][2] >= 1  # steps were accepted: the outputs are no entry values
+    for k in ("points3d", "poses", "history", "summary"):
+        assert outs[1][k].tobytes() == outs[0][k].tobytes(), k
+
+
+ORIGIN_KW = dict(iterations=3)
+
+
+def test_origin_half_equals_the_model(ctx):
+    """The stop tests' scene on pixels generated for origin 0.5, against the model called with 0.5.  The model with the
+    origin dropped or flipped is far away (asserted here and, without a GPU, in tests/test_bundle_model.py)."""
+    sc = bm.with_origin(bm.scene_small(), 0.5)
+    model = bm.run_model(sc, **ORIGIN_KW)
+    assert (model["history"][:, 3] == 1).all() and model["summary"][4] == 60
+    for origin in (0.0, -0.5):
+        other = bm.run_model(sc, origin=origin, **ORIGIN_KW)
+        assert deviation(other["poses"], model["poses"]) > 1e4 * BAR and deviation(other["summary"][:2], model["summary"][:2]) > 1e4 * BAR
+    dev = bm.DeviceBundle(ctx, sc)
+    try:
+        assert dev.camera().origin == 0.5
+        out = dev.run(**ORIGIN_KW)
+        worst, decided = compare(out, model, sc, ORIGIN_KW["iterations"])
+        print("bundle_adjust, origin 0.5, against the numpy model: largest deviation %.3g (bar 1e-9), %d of %d flags "
+              "decided" % (worst, decided, ORIGIN_KW["iterations"]))
+        assert decided == ORIGIN_KW["iterations"]
     finally:
         dev.close()
 

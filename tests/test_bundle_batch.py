@@ -62,6 +62,16 @@ def test_bundle_adjust_behind_tracks_and_triangulation():
         # to_host's poses go straight back in: the cost of the result is the final cost, and nothing is left to accept
         again = ex.bundle_adjust(tracks, poses, cam, res.points3d, iterations=1, huber=2.0)
         assert abs(again.summary[0].item() / summary[1] - 1.0) < 1e-9
+        # the camera is handed through: (cx + 1, cy + 1) counted from origin 1 is the same camera (320 and 240 are
+        # exact in float32), so both calls give the bytes they gave
+        cam1 = capi.Camera(fx, fy, cx + 1.0, cy + 1.0, origin=1.0)
+        points3d_1, front_1 = ex.triangulate_tracks(tracks, start, cam1)
+        res_1 = ex.bundle_adjust(tracks, start, cam1, points3d_1, iterations=6, huber=2.0)
+        torch.cuda.synchronize()
+        assert points3d_1.cpu().numpy().tobytes() == points3d.cpu().numpy().tobytes()
+        for mine, theirs in ((res_1.points3d, res.points3d), (res_1.poses, res.poses), (res_1.history, res.history),
+                             (res_1.summary, res.summary)):
+            assert mine.cpu().numpy().tobytes() == theirs.cpu().numpy().tobytes()
         # the same call through Context.bundle_adjust on the same pointers: the same bytes
         cap = tracks.offsets.numel() - 1
         with torch.cuda.device(ex.device), torch.cuda.stream(ex.stream):

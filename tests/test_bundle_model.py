@@ -369,3 +369,28 @@ def test_strided_tree_sum_is_the_stated_order():
         h //= 2
     assert bm.strided_tree_sum(v) == part[0]
     assert bm.strided_tree_sum(np.zeros((0, 3))).tolist() == [0.0, 0.0, 0.0]
+
+
+def test_the_origin_is_visible_to_the_model():
+    """px = cx - origin.  Origin 1 with (cx + 1, cy + 1) is origin 0 with (cx, cy) to the bit (320 and 240 are exact in
+    float32).  On pixels generated for origin 0.5 (bm.with_origin) the model called with 0.5 sees the small scene's
+    geometry; with the origin dropped or flipped it ends far from it -- far more than the 1e-9 of the device test
+    (tests/test_bundle.py::test_origin_half_equals_the_model), so that test can tell `cx + origin` from `cx - origin`."""
+    base = bm.scene_small()
+    fx, fy, cx, cy = base["cam"]
+    zero = bm.run_model(base, iterations=3)
+    one = bm.run_model(dict(base, cam=(fx, fy, cx + 1.0, cy + 1.0), origin=1.0), iterations=3)
+    for k in ("poses", "points3d", "history", "summary"):
+        assert one[k].tobytes() == zero[k].tobytes(), k
+    sc = bm.with_origin(base, 0.5)
+    assert sc["origin"] == 0.5 and np.abs(sc["xy"][:5, :60] - (base["xy"][:5, :60] - 0.5)).max() < 1e-4
+    half = bm.run_model(sc, iterations=3)
+    assert check_state_machine(half, 1e-3, 1e-9, 1e6, 1e-12) == 3 and (half["history"][:, 3] == 1).all()
+    # the scene's own run, to the float32 rounding of the moved pixels
+    assert np.abs(half["poses"] - zero["poses"]).max() < 1e-4 and abs(half["summary"][0] / zero["summary"][0] - 1.0) < 1e-3
+    for what, origin in (("dropped", 0.0), ("flipped", -0.5)):
+        other = bm.run_model(sc, origin=origin, iterations=3)
+        d_pose = np.abs(other["poses"] - half["poses"]).max()
+        d_cost = abs(other["summary"][0] - half["summary"][0]) / half["summary"][0]
+        print("origin %s: poses move by %.3g, entry cost by %.3g of itself (bar 1e-9)" % (what, d_pose, d_cost))
+        assert d_pose > 1e-5 and d_cost > 1e-5

@@ -1,7 +1,15 @@
 """cusift_triangulate_tracks (cusift_amd/csrc/sift_tracks.hip) against tests/tracks_model.py's restatement in numpy: the
 six-camera scene with 300 tracks of 2 to 6 views, a track of two identical rays, a track behind one of its cameras, a
 record that is not finite, rows past the track count, and the refusals.  The bar for fp64 against a numpy restatement is
-the one of tests/test_pose.py and tests/test_pnp.py: 1e-9 * max(1, |value|)."""
+the one of tests/test_pose.py and tests/test_pnp.py: 1e-9 * max(1, |value|).
+
+The pixel origin (px = cx - origin): origin 1 with (cx + 1, cy + 1) must give the bytes of origin 0 with (cx, cy) -- 320
+and 240 are exact in float32 --, and origin 0.5 on pixels generated for it must equal the model called with 0.5, which
+the CPU test shows to be 0.004 to 0.1 per track away from the model with the origin dropped (0.008 to 0.2 with its sign
+flipped).  Measured on an MI355X: largest deviation 0 for origin 0.5, as for origin 0.  Tried once in a scratch build
+that was never committed, `cx + origin` in cusift_triangulate_tracks: test_origin_one_is_origin_zero_to_the_byte fails
+on the bytes, test_origin_half_equals_the_model with a deviation of 3.16, and tests/test_bundle_batch.py on the bytes of
+its origin-1 call; everything else of this file stays green (origin 0 throughout)."""
 import ctypes as C
 
 import numpy as np
@@ -126,6 +134,93 @@ def test_points_equal_the_model(ctx):
         assert np.array_equal((out[:N_TRACKS] == 0).all(axis=1), dropped)
         assert (np.abs(out[:N_TRACKS] - strict) <= 1e-9 * np.maximum(1.0, np.abs(strict))).all()
         np.testing.assert_array_equal(front[:N_TRACKS], strict_front)
+    finally:
+        dev.close()
+
+
+def half_origin_scene():
+    """scene() as a camera sees it whose cx / cy count from 0.5: every pixel moved by -0.5 (rounded to float32 again)."""
+    poses, recs, offsets, obs, cam = scene()
+    recs = recs.copy()
+    recs["coords2D"] = (recs["coords2D"].astype(np.float64) - 0.5).astype(np.float32)
+    return poses, recs, offsets, obs, cam
+
+
+def test_the_origin_is_visible_to_the_model():
+    """px = cx - origin: origin 1 with (cx + 1, cy + 1) is origin 0 with (cx, cy) to the bit; on pixels generated for
+    origin 0.5 a dropped or flipped origin moves the points by far more than the bar of the device test."""
+    poses, recs, offsets, obs, (fx, fy, cx, cy) = scene()
+    assert np.float32(cx + 1.0) - np.float32(1.0) == np.float32(cx) and np.float32(cy + 1.0) - np.float32(1.0) == np.float32(cy)
+    zero = triangulate_model(recs["coords2D"], MAX_PTS, offsets, obs, poses, fx, fy, cx, cy)
+    one = triangulate_model(recs["coords2D"], MAX_PTS, offsets, obs, poses, fx, fy, cx + 1.0, cy + 1.0, origin=1.0)
+    assert one[0].tobytes() == zero[0].tobytes() and one[1].tobytes() == zero[1].tobytes()
+    poses, recs, offsets, obs, _ = half_origin_scene()
+    half, front = triangulate_model(recs["coords2D"], MAX_PTS, offsets, obs, poses, fx, fy, cx, cy, origin=0.5)
+    # the same geometry: the points of scene(), to the float32 rounding of the moved pixels
+    assert np.abs(half[:297, :3] - zero[0][:297, :3]).max() < 1e-3 and (front == zero[1]).all()
+    for what, origin in (("dropped", 0.0), ("flipped", -0.5)):
+        other, _ = triangulate_model(recs["coords2D"], MAX_PTS, offsets, obs, poses, fx, fy, cx, cy, origin=origin)
+        moved = (np.abs(other[:297] - half[:297]) / np.maximum(1.0, np.abs(half[:297]))).max(axis=1)
+        print("origin %s: the points move by %.3g .. %.3g (bar 1e-9)" % (what, moved.min(), moved.max()))
+        assert moved.min() > 1e-5  # ten thousand times the bar, on every track
+
+
+@pytest.mark.gpu
+def test_origin_one_is_origin_zero_to_the_byte(ctx):
+    from cusift_amd import capi
+
+    poses, recs, offsets, obs, (fx, fy, cx, cy) = scene()
+    dev = Device(ctx, recs, offsets, obs, N_TRACKS, N_TRACKS)
+    try:
+        d_recs, d_offsets, d_obs, d_stats, d_out, d_front = dev.ptrs
+        got = []
+        for cam in (capi.Camera(fx, fy, cx, cy), capi.Camera(fx, fy, cx + 1.0, cy + 1.0, origin=1.0)):
+            ctx.h2d(d_out, np.full((N_TRACKS, 4), FILL))
+            ctx.h2d(d_front, np.full(N_TRACKS, int(FILL), np.int32))
+            ctx.triangulate_tracks(d_recs, N_CAMS + 1, MAX_PTS, d_offsets, d_obs, d_stats, N_TRACKS, poses, cam, d_out,
+                                   d_front)
+            got.append(dev.read())
+        assert (got[0][0][:297] != 0).any(axis=1).all() and (got[0][0] != FILL).all()
+        assert got[1][0].tobytes() == got[0][0].tobytes() and got[1][1].tobytes() == got[0][1].tobytes()
+    finally:
+        dev.close()
+
+
+@pytest.mark.gpu
+def test_origin_half_equals_the_model(ctx):
+    from cusift_amd import capi
+
+    poses, recs, offsets, obs, (fx, fy, cx, cy) = half_origin_scene()
+    want, want_front = triangulate_model(recs["coords2D"], MAX_PTS, offsets, obs, poses, fx, fy, cx, cy, origin=0.5)
+    dev = Device(ctx, recs, offsets, obs, N_TRACKS, N_TRACKS)
+    try:
+        d_recs, d_offsets, d_obs, d_stats, d_out, d_front = dev.ptrs
+        ctx.triangulate_tracks(d_recs, N_CAMS + 1, MAX_PTS, d_offsets, d_obs, d_stats, N_TRACKS, poses,
+                               capi.Camera(fx, fy, cx, cy, origin=0.5), d_out, d_front)
+        out, front = dev.read()
+        dev_err = np.abs(out - want) / np.maximum(1.0, np.abs(want))
+        print("triangulate_tracks, origin 0.5, against the numpy model: largest deviation %.3g (bar 1e-9)" % dev_err.max())
+        assert dev_err.max() <= 1e-9
+        np.testing.assert_array_equal(front, want_front)
+    finally:
+        dev.close()
+
+
+@pytest.mark.gpu
+def test_no_tracks_and_no_frames_write_nothing(ctx):
+    """max_tracks = 0 and n_images = 0: CUSIFT_OK, nothing enqueued."""
+    from cusift_amd import capi
+
+    poses, recs, offsets, obs, (fx, fy, cx, cy) = scene()
+    cam = capi.Camera(fx, fy, cx, cy)
+    dev = Device(ctx, recs, offsets, obs, N_TRACKS, N_TRACKS)
+    try:
+        d_recs, d_offsets, d_obs, d_stats, d_out, d_front = dev.ptrs
+        ctx.triangulate_tracks(d_recs, N_CAMS + 1, MAX_PTS, d_offsets, d_obs, d_stats, 0, poses, cam, d_out, d_front)
+        ctx.triangulate_tracks(d_recs, 0, MAX_PTS, d_offsets, d_obs, d_stats, N_TRACKS, poses[:0], cam, d_out, d_front)
+        ctx.triangulate_tracks(d_recs, 0, 0, d_offsets, d_obs, d_stats, N_TRACKS, poses[:0], cam, d_out, d_front)
+        out, front = dev.read()
+        assert (out == FILL).all() and (front == int(FILL)).all()
     finally:
         dev.close()
 
