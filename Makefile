@@ -17,7 +17,7 @@ ROOT    := $(abspath $(dir $(lastword $(MAKEFILE_LIST))))
 CSRC    := $(ROOT)/cusift_amd/csrc
 OBJROOT := $(ROOT)/build/obj
 
-SOURCES := sift_context sift_stages sift_register sift_driver sift_describe sift_second sift_stencils sift_keypoints sift_match sift_match_project sift_match8 sift_frontend \
+SOURCES := sift_context sift_stages sift_register sift_driver sift_describe sift_second sift_stencils sift_keypoints sift_match sift_match_project sift_match8 sift_match8_guided sift_frontend \
            sift_homography sift_planar sift_epipolar sift_pose sift_pnp sift_rigid sift_rgbd sift_sequence sift_select sift_tracks sift_bundle sift_comm sift_tiled sift_pipe
 HEADERS := $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc) $(wildcard $(ROOT)/include/cusift_amd*.h)
 
@@ -64,6 +64,7 @@ cpp-tests: $(LIB)
 	$(MAKE) -C $(ROOT)/tests/cpp_sequence_pose
 	$(MAKE) -C $(ROOT)/tests/cpp_match8
 	$(MAKE) -C $(ROOT)/tests/cpp_match8_mutual
+	$(MAKE) -C $(ROOT)/tests/cpp_match8_guided
 	$(MAKE) -C $(ROOT)/tests/cpp_describe
 	$(MAKE) -C $(ROOT)/tests/cpp_second_orientation
 	$(MAKE) -C $(ROOT)/tests/cpp_tracks

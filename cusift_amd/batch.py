@@ -285,16 +285,41 @@ class BatchExtractor:
         self.ctx.match8_mutual(points[i].data_ptr(), n_i, q[i].data_ptr(), sums[i].data_ptr(), points[j].data_ptr(), n_j,
                                q[j].data_ptr(), sums[j].data_ptr(), distance)
 
+    def _tables8(self, who, i, j, slot):
+        """(records i, count, table, sums, records j, count, table, sums) of the last quantize(slot), as the 8-bit pair
+        calls take them"""
+        if slot not in getattr(self, "_desc8", {}):
+            raise capi.CusiftError("%s: call quantize(slot=%d) first" % (who, slot))
+        q, sums = self._desc8[slot]
+        points, counts = self.slots[slot]
+        n_i, n_j = self._pair_counts(counts, i, j)
+        return (points[i].data_ptr(), n_i, q[i].data_ptr(), sums[i].data_ptr(), points[j].data_ptr(), n_j, q[j].data_ptr(),
+                sums[j].data_ptr())
+
+    def match8_guided(self, i, j, model, m, radius, slot=0, distance=1):
+        """match_guided(i, j, model, m, radius) on the tensors of the last quantize(slot): cusift_match8_guided writes frame
+        i's five match fields from the bytes, the test reads the records' coords2D.  Asynchronous on the extractor's
+        stream."""
+        self.ctx.match8_guided(*self._tables8("match8_guided", i, j, slot), model, m, radius, distance)
+
+    def match8_projected(self, i, j, rt, camera2, radius, slot=0, distance=1):
+        """match_projected(i, j, rt, camera2, radius) on the tensors of the last quantize(slot): cusift_match8_projected
+        writes frame i's five match fields from the bytes, the test reads frame i's coords3D and frame j's coords2D.
+        Asynchronous on the extractor's stream."""
+        self.ctx.match8_projected(*self._tables8("match8_projected", i, j, slot), rt, camera2, radius, distance)
+
     def register_planar_guided(self, i, j, radius=None, slot=0, **opts):
         """register_planar(i, j) with a second, guided matching pass: capi.Context.register_planar_guided over this
-        extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.  Blocking."""
+        extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on; with
+        match_bits = 8 it runs with match8=True among the options (the second pass on bytes too).  Blocking."""
         points, counts = self.slots[slot]
         n_i, n_j = self._pair_counts(counts, i, j)
         return self.ctx.register_planar_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, radius, **opts)
 
     def register_epipolar_guided(self, i, j, radius=None, slot=0, **opts):
         """register_epipolar(i, j) with a second, guided matching pass: capi.Context.register_epipolar_guided over this
-        extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.  Blocking."""
+        extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on; with
+        match_bits = 8 it runs with match8=True among the options (the second pass on bytes too).  Blocking."""
         points, counts = self.slots[slot]
         n_i, n_j = self._pair_counts(counts, i, j)
         return self.ctx.register_epipolar_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, radius, **opts)
@@ -330,8 +355,8 @@ class BatchExtractor:
 
     def register_pnp_guided(self, i, j, camera2, radius=None, slot=0, **opts):
         """register_pnp(i, j, camera2) with a second matching pass by projection: capi.Context.register_pnp_guided over
-        this extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on.
-        Blocking."""
+        this extractor's device records.  Returns its (first pass, guided pass).  Refused while cross_check is on;
+        with match_bits = 8 it runs with match8=True among the options (the second pass on bytes too).  Blocking."""
         points, counts = self.slots[slot]
         n_i, n_j = self._pair_counts(counts, i, j)
         return self.ctx.register_pnp_guided(points[i].data_ptr(), n_i, points[j].data_ptr(), n_j, camera2, radius, **opts)

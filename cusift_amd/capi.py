@@ -272,6 +272,12 @@ SIGNATURES = {
     "cusift_match8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cusift_match8_mutual": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     "cusift_match8_batch_mutual": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "cusift_match8_guided": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _f]),
+    "cusift_match8_projected": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, C.POINTER(Camera), _f]),
+    "cusift_match8_batch_guided": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _vp]),
+    "cusift_match8_batch_projected": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, C.POINTER(Camera), _f, _vp]),
+    "cusift_match8_guided_records": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _f]),
+    "cusift_match8_projected_records": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, C.POINTER(Camera), _f]),
     "cusift_register_rgbd_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _sz, C.POINTER(Camera), _vp, _i, _i, _f,
                                         _f, _i, _f, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "cusift_register_planar_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _f, _i, _f, C.c_uint64, _vp,
@@ -638,7 +644,7 @@ class Context:
             check(lib().cusift_ctx_create_borrowed(C.byref(self._h), device, C.c_void_p(int(stream))))
         self.device = device
         self.cross_check = False  # what set_cross_check last set: the guided chains refuse to run while it is on
-        self.match_bits = 32  # what set_match_bits last set: the guided chains refuse to run while it is 8
+        self.match_bits = 32  # what set_match_bits last set: at 8 the guided chains ask for match8=True
 
     @property
     def handle(self):
@@ -970,18 +976,24 @@ class Context:
 
     def _guided_chain(self, register, estimate, guided, thresh, d_sift1, n1, d_sift2, n2, radius, opts):
         """register -> the guided matcher under the refined model -> estimate over the rewritten records, same options.
-        guided(d_sift1, n1, d_sift2, n2, refined model, radius, distance) is match_guided under H or F, or
-        match_projected under [R | t]."""
+        guided(d_sift1, n1, d_sift2, n2, refined model, radius, distance, on_bytes) is match_guided under H or F, or
+        match_projected under [R | t] -- on_bytes: match8_guided_records / match8_projected_records, which quantise both
+        record sets into the context's tables and run the 8-bit guided matcher.  opts["match8"] (default False) chooses
+        the second pass on bytes; the first pass follows set_match_bits.  With the match bits at 8 the chain runs only
+        with match8=True: it never matches bytes first and floats second without being told to."""
+        opts = dict(opts)
+        on_bytes = bool(opts.pop("match8", False))
         if self.cross_check:
             raise CusiftError("guided registration: turn the cross-check off first (set_cross_check(False)) -- the "
                               "guided matcher has no column side")
-        if self.match_bits == 8:
-            raise CusiftError("guided registration: set the match bits back to 32 first (set_match_bits(32)) -- there "
-                              "is no 8-bit guided matcher")
+        if self.match_bits == 8 and not on_bytes:
+            raise CusiftError("guided registration: the match bits are 8 -- pass match8=True for a second pass on bytes "
+                              "too, or set them back to 32 first (set_match_bits(32))")
         first = register(d_sift1, n1, d_sift2, n2, **opts)
         distance = opts.get("distance", 1)
         rule, lo, hi = _rule_defaults(distance, opts.get("rule"), opts.get("lo"), opts.get("hi"))
-        guided(d_sift1, n1, d_sift2, n2, first[0], opts.get("thresh", thresh) if radius is None else radius, distance)
+        guided(d_sift1, n1, d_sift2, n2, first[0], opts.get("thresh", thresh) if radius is None else radius, distance,
+               on_bytes)
         again = {k: v for k, v in opts.items() if k != "distance"}
         again.update(rule=rule, lo=lo, hi=hi)
         return first, estimate(d_sift1, n1, n2, **again)
@@ -991,7 +1003,10 @@ class Context:
         homography it returned (radius None: that call's thresh), then estimate_homography over the rewritten records of
         d_sift1 with num_pts2 = n2 and the same options and seed.  Matches that the ratio test of the first pass threw
         away because a look-alike scored as well come back when the look-alike lies elsewhere.  Returns (first pass,
-        guided pass), two PlanarResults.  CusiftError while the cross-check is on.  Blocking, twice."""
+        guided pass), two PlanarResults.  match8=True: the second pass matches bytes (match8_guided_records) -- with
+        set_match_bits(8) both passes do, bit for bit register_planar + quantize_descriptors + match8_guided +
+        estimate_homography; at 8 bits the chain runs only with it.  CusiftError while the cross-check is on.  Blocking,
+        twice."""
         return self._guided_chain(self.register_planar, self.estimate_homography, self._guided_by("homography"), 5.0,
                                   d_sift1, n1, d_sift2, n2, radius, opts)
 
@@ -1003,8 +1018,11 @@ class Context:
                                   d_sift1, n1, d_sift2, n2, radius, opts)
 
     def _guided_by(self, model):
-        """match_guided under one kind of model, in _guided_chain's argument order"""
-        return lambda d1, n1, d2, n2, m, radius, distance: self.match_guided(d1, n1, d2, n2, model, m, radius, distance)
+        """match_guided -- on bytes: match8_guided_records -- under one kind of model, in _guided_chain's argument
+        order"""
+        def guided(d1, n1, d2, n2, m, radius, distance, on_bytes):
+            (self.match8_guided_records if on_bytes else self.match_guided)(d1, n1, d2, n2, model, m, radius, distance)
+        return guided
 
     @staticmethod
     def _pose(call):
@@ -1071,12 +1089,14 @@ class Context:
         """register_planar_guided for a pose from 3-D/2-D matches: register_pnp(camera2, **opts), match_projected under
         the refined [R | t] (radius None: that call's thresh, pixels from the projection of coords3D), estimate_pnp over
         the rewritten records with num_pts2 = n2 and the same options and seed.  Returns (first pass, guided pass), two
-        PnPResults.  CusiftError while the cross-check is on or the match bits are 8.  Blocking, twice."""
+        PnPResults.  match8=True: the second pass is match8_projected_records, on bytes; while the match bits are 8 the
+        chain runs only with it.  CusiftError while the cross-check is on.  Blocking, twice."""
+        def projected(d1, m1, d2, m2, rt, r, distance, on_bytes):
+            (self.match8_projected_records if on_bytes else self.match_projected)(d1, m1, d2, m2, rt, camera2, r, distance)
         return self._guided_chain(
             lambda d1, m1, d2, m2, **o: self.register_pnp(d1, m1, d2, m2, camera2, **o),
             lambda d1, m1, m2, **o: self.estimate_pnp(d1, m1, camera2, m2, **o),
-            lambda d1, m1, d2, m2, rt, r, distance: self.match_projected(d1, m1, d2, m2, rt, camera2, r, distance),
-            2.0, d_sift1, n1, d_sift2, n2, radius, opts)
+            projected, 2.0, d_sift1, n1, d_sift2, n2, radius, opts)
 
     def estimate_rigid(self, coord, indices=None, loops=None, thresh2=0.0025, kind="3d", seed=0, want_all=False):
         """cusift_estimate_rigid: RANSAC rigid transform x ~ R y + t from coord float32 [N, 6] (reference xyz, moving
@@ -1141,7 +1161,7 @@ class Context:
         """cusift_ctx_set_match_bits: 32 (default) or 8.  While 8, the calls set_cross_check affects quantise their
         records into scratch of the context and match the bytes on the int8 matrix pipe (match8 / match8_mutual and the
         batch forms) -- bit for bit the staged route quantize_descriptors + match8 + estimate_*.  Nothing else reads it;
-        the guided chains refuse to run while it is 8."""
+        while it is 8 the guided chains run with match8=True only (their second pass on bytes too)."""
         check(lib().cusift_ctx_set_match_bits(self.handle, check_match_bits(bits)))
         self.match_bits = int(bits)
 
@@ -1258,6 +1278,62 @@ class Context:
         pairs = pair_list(pairs)
         check(lib().cusift_match8_batch(self.handle, d_q, d_sums, d_counters, n_images, max_pts, pairs.ctypes.data,
                                         len(pairs), distance, d_rows))
+
+    def match8_guided(self, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, model, m, radius, distance=1):
+        """cusift_match8_guided: match8() where only the records of d_sift2 whose coords2D pass match_guided()'s test
+        against a row's coords2D count for it (`model`, m and radius as there; the coordinates come from the records, the
+        descriptors from the tables).  A row that nothing passes ends with match = -1 and the initial score.
+        Asynchronous; m is read before the call returns."""
+        model, m = (GUIDE_MODELS.get(model, model), None) if m is None else guide_models(model, m)
+        check(lib().cusift_match8_guided(self.handle, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance,
+                                         model, None if m is None else m.ctypes.data, radius))
+
+    def match8_projected(self, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, rt, camera2, radius, distance=1):
+        """cusift_match8_projected: match8() under match_projected()'s test -- a record of d_sift2 counts for a row only
+        within `radius` pixels of where rt and camera2 put the row's coords3D.  Asynchronous; rt and camera2 are read
+        before the call returns."""
+        rt = None if rt is None else pose_models(rt)
+        check(lib().cusift_match8_projected(self.handle, d_sift1, n1, d_q1, d_sums1, d_sift2, n2, d_q2, d_sums2, distance,
+                                            None if rt is None else rt.ctypes.data,
+                                            C.byref(camera2) if camera2 is not None else None, radius))
+
+    def match8_batch_guided(self, d_points, d_q, d_sums, d_counters, n_images, max_pts, pairs, model, m, radius, d_rows,
+                            distance=1):
+        """cusift_match8_batch_guided: match8_batch() with match8_guided()'s rule, pair p under m[p]; d_points are the
+        records the tables were quantised from (their coords2D are read, nothing of them is written).  Asynchronous; m is
+        read before the call returns."""
+        pairs = pair_list(pairs)
+        model, m = (GUIDE_MODELS.get(model, model), None) if m is None else guide_models(model, m, len(pairs))
+        check(lib().cusift_match8_batch_guided(self.handle, d_points, d_q, d_sums, d_counters, n_images, max_pts,
+                                               pairs.ctypes.data, len(pairs), distance, model,
+                                               None if m is None else m.ctypes.data, radius, d_rows))
+
+    def match8_batch_projected(self, d_points, d_q, d_sums, d_counters, n_images, max_pts, pairs, rts, camera2, radius,
+                               d_rows, distance=1):
+        """cusift_match8_batch_projected: match8_batch() with match8_projected()'s rule, pair p under rts[p] and the one
+        camera2; d_points are the records the tables were quantised from (coords2D and, of a pair's first frame, coords3D
+        are read).  Asynchronous; rts and camera2 are read before the call returns."""
+        pairs = pair_list(pairs)
+        rts = None if rts is None else pose_models(rts, len(pairs))
+        check(lib().cusift_match8_batch_projected(self.handle, d_points, d_q, d_sums, d_counters, n_images, max_pts,
+                                                  pairs.ctypes.data, len(pairs), distance,
+                                                  None if rts is None else rts.ctypes.data,
+                                                  C.byref(camera2) if camera2 is not None else None, radius, d_rows))
+
+    def match8_guided_records(self, d_sift1, n1, d_sift2, n2, model, m, radius, distance=1):
+        """cusift_match8_guided_records: quantize_descriptors() of both record sets into tables of the context's, then
+        match8_guided() on them -- match_guided()'s arguments, the 8-bit matcher's bytes.  Asynchronous."""
+        model, m = (GUIDE_MODELS.get(model, model), None) if m is None else guide_models(model, m)
+        check(lib().cusift_match8_guided_records(self.handle, d_sift1, n1, d_sift2, n2, distance, model,
+                                                 None if m is None else m.ctypes.data, radius))
+
+    def match8_projected_records(self, d_sift1, n1, d_sift2, n2, rt, camera2, radius, distance=1):
+        """cusift_match8_projected_records: quantize_descriptors() of both record sets into tables of the context's, then
+        match8_projected() on them -- match_projected()'s arguments, the 8-bit matcher's bytes.  Asynchronous."""
+        rt = None if rt is None else pose_models(rt)
+        check(lib().cusift_match8_projected_records(self.handle, d_sift1, n1, d_sift2, n2, distance,
+                                                    None if rt is None else rt.ctypes.data,
+                                                    C.byref(camera2) if camera2 is not None else None, radius))
 
     def register_rgbd_batch(self, d_points, d_counters, n_images, max_pts, d_depth, w, h, camera, pairs, pitch=None,
                             image_stride=None, distance=1, score_threshold=999.0, ambiguity_threshold=1.0, loops=1024,

@@ -7,6 +7,7 @@
 //                     calibrated pose, planar and epipolar registration on one chain, the absolute pose, the pair-list forms
 //   sift_select.hip   keep the K strongest keypoints per image: its three kernels, cusift_select_strongest
 //   sift_match8.hip   8-bit descriptors: the quantiser, the int8-MFMA matcher, their entry points (a unit of its own)
+//   sift_match8_guided.hip  the int8 matcher's kernels under a geometric guide, on sift_match8_block.h with sift_match8.hip
 //   sift_match_common.h  device code of both matchers (sift_match.hip, sift_match8.hip): write-out, pair-list frame,
 //                     fold of the partials, the "partial or final" sink
 //   sift_driver.hip   the octave driver: launch policy -> Plan (resolve_plan), cusift_extract_batch enqueues it; its
@@ -104,6 +105,22 @@ __global__ void match_projected_kernel(cusift_point *, int, const cusift_point *
 template <bool kL2>
 __global__ void match_batch_projected_kernel(const cusift_point *, const unsigned int *, int, const int *, int,
                                              MatchPartial *, int, cusift_match_row *, const ProjectModel *, float);
+struct Match8Partial;  // the int8 matcher's partial (sift_match8_block.h)
+struct M8GuideH;        // the same predicates inside the int8 matcher (sift_match8_guided.hip)
+struct M8GuideF;
+struct M8GuideP;
+template <bool kL2, class Guide, class Model>
+__global__ void match8_guided_kernel(cusift_point *, int, const unsigned char *, const int *, const cusift_point *, int,
+                                     const unsigned char *, const int *, int, Match8Partial *, int, Model, float);
+template <bool kL2>
+__global__ void match8_guided_merge_kernel(cusift_point *, int, const cusift_point *, int, const Match8Partial *, int, int);
+template <bool kL2, class Guide, class Model>
+__global__ void match8_batch_guided_kernel(const cusift_point *, const unsigned char *, const int *, const unsigned int *,
+                                           int, const int *, int, Match8Partial *, int, cusift_match_row *, const Model *,
+                                           float);
+template <bool kL2>
+__global__ void match8_batch_guided_merge_kernel(const unsigned int *, int, const int *, int, const Match8Partial *, int,
+                                                 int, cusift_match_row *);
 __global__ void sequence_select_kernel(const cusift_point *, const unsigned int *, int, const int *,
                                        const cusift_match_row *, float, float, int, int *, float *, int *,
                                        const cusift_match_row *);
@@ -434,6 +451,8 @@ struct MatcherShape {
 };
 constexpr MatcherShape kMatcher32{64, 32, 4, (int)sizeof(cusift_point), "MatchSiftData"};  // sift_match.hip
 constexpr MatcherShape kMatcher8{256, 64, 2, 128, "Match8"};                                // sift_match8.hip
+// the same under a guide: the columns' coords2D come through a buffer resource over the split's 588-byte records
+constexpr MatcherShape kMatcher8Guided{256, 64, 2, (int)sizeof(cusift_point), "Match8Guided"};
 
 // The column splits of a matcher over n_pairs pairs (a batch: sized from max_pts, the counts stay on the device): aim at
 // >= wgs_per_cu workgroups per CU over all pairs, keep >= 4 LDS tiles per split.  CUSIFT_POLICY_MATCH_SPLITS = k > 0: k
@@ -455,9 +474,25 @@ static inline int matcher_split_plan(const cusift_ctx *ctx, const MatcherShape &
   *cols_per_split_out = cols_per_split;
   return CUSIFT_OK;
 }
+// The geometry of a guided match (cusift_match_guided, cusift_match_batch_guided and the 8-bit forms), checked: which test,
+// the squared radius and the models as the caller's host array -- one of the pair call, one per pair of the pair-list call.
+// camera != NULL (cusift_match_projected, cusift_match_batch_projected and the 8-bit forms): the test is the projection of
+// coords3D, h_models holds [R | t], twelve doubles a pair, and `model` is not read.
+struct GuideCall {
+  int model;
+  float r2;
+  const double *h_models;
+  const PnPCam *camera = nullptr;
+};
+// sift_register.hip: every refusal the guided and the projected calls add to their unguided counterparts', the camera as
+// the kernels take it, and a pose beside it
+int check_guide(const char *who, int model, const double *h_models, float radius);
+int check_project(const char *who, const double *h_rts, const cusift_camera *camera2, float radius);
+PnPCam pnp_cam(const cusift_camera *c);
+ProjectModel project_model(const double *h_rt, const PnPCam &cam);
 // sift_match8.hip, for the registrations' matcher fronts (sift_register.hip)
 int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
-                        int distance, cusift_point *d_back);
+                        int distance, cusift_point *d_back, const GuideCall *guide = nullptr);
 int match8_batch_enqueue(cusift_ctx *ctx, const cusift_point *d_points, const unsigned int *d_counters, int n_images,
                          int max_pts, const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
                          cusift_match_row *d_rows_back, const int **d_pairs_out);

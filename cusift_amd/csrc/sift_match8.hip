@@ -1,8 +1,10 @@
 // sift_match8.hip -- 8-bit descriptors: the quantiser, the two sums of a byte descriptor, and the brute-force matcher on
 // the int8 matrix pipe (v_mfma_i32_16x16x64_i8), for a pair and for a pair list.  The definitions, expression by
 // expression, are in include/cusift_amd_extras.h (cusift_quantize_descriptors, cusift_desc8_sums, cusift_match8,
-// cusift_match8_batch, cusift_match8_mutual, cusift_match8_batch_mutual); this text is how they are computed.  At the end:
-// the registrations' matcher fronts while cusift_ctx_set_match_bits is 8.
+// cusift_match8_batch, cusift_match8_mutual, cusift_match8_batch_mutual); this text is how they are computed.  The block
+// body is sift_match8_block.h, shared with the guided kernels of sift_match8_guided.hip, whose launches and entry points
+// (cusift_match8_guided, cusift_match8_projected, their pair-list forms) are here too.  At the end: the registrations'
+// matcher fronts while cusift_ctx_set_match_bits is 8.
 //
 // Tables: q[n][128] unsigned bytes, dense and 16-byte aligned; sums[n][2] = (sum q, sum q^2) as int.
 //
@@ -34,310 +36,9 @@
 // C/D: col = lane & 15, row = 4 (lane >> 4) + reg.
 #include "sift_host.h"
 
-#include "sift_match_common.h"
+#include "sift_match8_block.h"
 
 namespace cusift {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kM8RowsPerWave = 64;                    // four 16-row A fragments
-constexpr int kM8RowsPerBlock = 4 * kM8RowsPerWave;   // 256
-constexpr int kM8TileCols = 64;                       // columns per LDS tile
-constexpr int kM8Stride = 144;                        // bytes per LDS column: 128 + the column's term + pad; 36 dwords,
-                                                      // = 4 mod 32 like the fp32 matcher's rows: ds_read_b128 without conflicts
-constexpr int kM8Masked = 1 << 30;                    // the term of a column past the split's end
-constexpr int kM8None = 1 << 29;                      // a key at or above this is no column
-constexpr int kM8Init = 0x7fffffff;
-constexpr float kM8FltMax = 999.0f;                   // cusift_match's initial values
-constexpr float kM8Scale = 1.0f / 262144.0f;          // 2^-18: (q / 512)^2
-
-// per-(column split, row) result: final keys (D, or -S), kM8Init where there is none
-struct Match8Partial {
-  int best, second, idx, pad;
-};
-
-__device__ __forceinline__ int med3i(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
-
-// (best, second, idx) of two disjoint column sets -> of their union: (key, column) pairs in order, second smallest key
-__device__ __forceinline__ void m8_merge(int &best, int &second, int &idx, int ob, int os, int oi) {
-  const bool take = ob < best || (ob == best && (unsigned)oi < (unsigned)idx);  // idx -1 (no column) loses to any column
-  second = min(max(best, ob), min(second, os));
-  best = min(best, ob);
-  idx = take ? oi : idx;
-}
-struct M8Merge {  // as fold_partials' merge step
-  __device__ __forceinline__ void operator()(Match8Partial &m, const Match8Partial &o) const {
-    m8_merge(m.best, m.second, m.idx, o.best, o.second, o.idx);
-  }
-};
-
-// what a row's term adds behind the scan
-template <bool kL2>
-__device__ __forceinline__ int m8_row_term(int sum, int sq) {
-  return kL2 ? sq - 256 * sum + (1 << 21) : (1 << 21) - 128 * sum;
-}
-template <bool kL2>
-__device__ __forceinline__ int m8_col_term(int sum, int sq) {
-  return kL2 ? sq - 256 * sum + (1 << 21) : -128 * sum;
-}
-
-// final keys -> the three values cusift_match's tail works on
-template <bool kL2>
-__device__ __forceinline__ void m8_floats(int best, int second, float &fb, float &fs) {
-  fb = kL2 ? (float)best * kM8Scale : (float)(-best) * kM8Scale;
-  fs = second >= kM8None ? (kL2 ? kM8FltMax : -1.0f) : (kL2 ? (float)second * kM8Scale : (float)(-second) * kM8Scale);
-}
-
-// cusift_match's tail on them (sift_match_common.h): the five fields of a record, or a row of a pair's row array
-template <bool kL2>
-__device__ __forceinline__ void m8_write_point(cusift_point *pt, const cusift_point *__restrict__ sift2, int n2, int best,
-                                               int second, int idx) {
-  float fb, fs;
-  m8_floats<kL2>(best, second, fb, fs);
-  write_match(pt, sift2, n2, fb, fs, idx, kL2);
-}
-template <bool kL2>
-__device__ __forceinline__ void m8_write_row(cusift_match_row *__restrict__ row, int best, int second, int idx) {
-  float fb, fs;
-  m8_floats<kL2>(best, second, fb, fs);
-  write_match_row(row, fb, fs, idx, kL2);
-}
-
-// The two sinks of the main kernels (partial_or, sift_match_common.h): the keys of record i of `dst` against the records
-// `other`, and of row i of a pair's row array.
-template <bool kL2>
-__device__ __forceinline__ auto m8_point_sink(Match8Partial *partials, size_t slab, cusift_point *dst,
-                                              const cusift_point *other, int n_other) {
-  return partial_or(partials, slab,
-                    [=](int i, int b, int s, int idx) { m8_write_point<kL2>(dst + i, other, n_other, b, s, idx); });
-}
-template <bool kL2>
-__device__ __forceinline__ auto m8_row_sink(Match8Partial *partials, size_t slab, cusift_match_row *rows) {
-  return partial_or(partials, slab, [=](int i, int b, int s, int idx) { m8_write_row<kL2>(rows + i, b, s, idx); });
-}
-
-// ---- the column side (cusift_match8_mutual, cusift_match8_batch_mutual) -------------------------------------------------
-// For every column the best and second best ROW, from the accumulators the row side already holds.  In the C/D layout lane
-// (r, g) has, per B fragment, the 16 scores of one column against rows 16 i + 4 g + j of its wave.  The column's order over
-// the rows does not depend on the column's own term, so the scan runs on
-//     key'' = R - 2 S'   (L2)          key'' = -128 sum q1 - S'   (dot product)
-// with the ROW's term (m8_col_term of the row's sums: the row is the "column" of the swapped call), and the column's term
-// (m8_row_term of its sums) is added once, behind the scan: the same integers as the row side, D or -S.  A row past n1
-// carries kM8ColMasked instead.  |key''| < 2^23 for a real row, so kM8ColBias - key'' lies in (2^24, 2^26) for a real row
-// and below 2^24 for a padding row, and a wave sees 64 rows: (bias - key'') << 6 | (63 - local row) is one unsigned word
-// whose DESCENDING order is that of (key, row) ascending.  Its maximum is the best key with the lowest row, the second
-// largest word carries the second smallest key of the multiset, and 0 is "nothing yet".  The 16 row terms are kept
-// negated, pre-shifted, with the row in their low bits; the accumulator enters shifted by 7 (2 S', L2) or 6, which
-// leaves the low 6 bits alone.  Per score: one shift-add, one max, one med3.  Then two cross-lane
-// steps fold the four g groups of a column, lanes g == 0 leave (best word, second word) in LDS -- [tile parity][wave][64]
-// -- and behind the NEXT tile's barrier 16 lanes of every wave fold the four waves of a column as (key, row) pairs with the
-// block's row numbers (m8_merge: the words' local rows do not order rows of different waves) and hand the final keys to
-// out.  A buffer is written again two tiles later, behind a barrier that every wave reaches only after its drain.
-constexpr int kM8ColBias = 1 << 25;
-constexpr int kM8ColMasked = (1 << 25) - (1 << 23);  // bias - masked - 2 S' stays in [2^22, 2^24)
-constexpr int kM8ColNone = 1 << 24;                  // key'' = bias - (word >> 6) above this is no row
-
-struct M8NoCols {
-  static constexpr bool kOn = false;
-};
-template <class ColOut>
-struct M8Cols {
-  static constexpr bool kOn = true;
-  uint2 *buf;  // [2][4][kM8TileCols]
-  ColOut out;  // out(column, best, second, row): final keys, kM8Init where there is no second
-};
-
-__device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) { return max(min(a, b), min(max(a, b), c)); }
-
-// the columns [c_prev, c_prev + 64) of the tile whose words lie in buffer `par`
-template <bool kL2, class Cols>
-__device__ __forceinline__ void m8_cols_drain(const Cols &cols, const int *__restrict__ sums2, int c_prev, int col_end,
-                                              int par, int lane, int wv) {
-  const int j = 16 * wv + lane, col = c_prev + j;
-  if (lane < 16 && col < col_end) {
-    int best = kM8Init, second = kM8Init, idx = -1;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const uint2 e = cols.buf[(par * 4 + w) * kM8TileCols + j];
-      m8_merge(best, second, idx, kM8ColBias - (int)(e.x >> 6), kM8ColBias - (int)(e.y >> 6),
-               (int)blockIdx.x * kM8RowsPerBlock + w * kM8RowsPerWave + 63 - (int)(e.x & 63u));
-    }
-    const int2 s = *reinterpret_cast<const int2 *>(sums2 + 2 * (size_t)col);
-    const int ct = m8_row_term<kL2>(s.x, s.y);
-    cols.out(col, best + ct, second > kM8ColNone ? kM8Init : second + ct, idx);
-  }
-}
-
-// One workgroup's 256 rows [blockIdx.x * 256 ..) of (q1, sums1, n1) against the columns [col_begin, col_end) of
-// (q2, sums2); col_begin < col_end and blockIdx.x * 256 < n1.  out(row, best, second, idx) receives every row < n1 once,
-// with final keys.  Cols = M8Cols: the column side as well, over this workgroup's rows.
-template <bool kL2, class Out, class Cols = M8NoCols>
-__device__ __forceinline__ void m8_block(const unsigned char *__restrict__ q1, const int *__restrict__ sums1, int n1,
-                                         const unsigned char *__restrict__ q2, const int *__restrict__ sums2,
-                                         int col_begin, int col_end, unsigned char *sB, Out out, Cols cols = Cols{}) {
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int p1_base = blockIdx.x * kM8RowsPerBlock + wv * kM8RowsPerWave;
-
-  // A fragments: lane (r, g) holds bytes 64 m + 16 g .. + 15 of row p1_base + 16 i + r (i = 0..3, m = 0..1), minus 128.
-  // A row past n1 is a copy of the last one; it is never written.
-  i32x4 a[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned char *row = q1 + (size_t)min(p1_base + 16 * i + r, n1 - 1) * 128 + 16 * g;
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const u4 v = *reinterpret_cast<const u4 *>(row + 64 * m);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[i][m][j] = (int)(v[j] ^ 0x80808080u);
-    }
-  }
-  // running top-2 of rows 16 i + 4 g + j over the columns this lane sees (r mod 16), on key'
-  int best[4][4], second[4][4], bidx[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      best[i][j] = second[i][j] = kM8Init;
-      bidx[i][j] = -1;
-    }
-  // column side: the terms of rows 16 i + 4 g + j, biased, shifted, the local row below them
-  unsigned cterm[4][4];
-  if constexpr (Cols::kOn) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int local = 16 * i + 4 * g + j;
-        int term = kM8ColMasked;
-        if (p1_base + local < n1) {
-          const int2 s = *reinterpret_cast<const int2 *>(sums1 + 2 * (size_t)(p1_base + local));
-          term = m8_col_term<kL2>(s.x, s.y);
-        }
-        cterm[i][j] = ((unsigned)(kM8ColBias - term) << 6) | (unsigned)(63 - local);
-      }
-  }
-
-  // staging: thread t moves two 16-byte chunks per tile; chunk c = t + 256 k -> column c >> 3, bytes 16 (c & 7).  Raw
-  // buffer loads from a descriptor based at the split's first column: a column past col_end reads as 0 and is masked by
-  // its term.  Threads 0..63 also fetch the sums of column c0 + t and turn them into the column's term.
-  const int n_cols = col_end - col_begin;
-  const __amdgpu_buffer_rsrc_t rsrc2 =
-      __builtin_amdgcn_make_buffer_rsrc((void *)(q2 + (size_t)col_begin * 128), 0, n_cols * 128, kBufFlags);
-  const int voff = (int)(threadIdx.x >> 3) * 128 + 16 * (int)(threadIdx.x & 7);
-  u4 stage[2];
-  int stage_term = kM8Masked;
-  auto fetch = [&](int c0) {
-    const int soff = __builtin_amdgcn_readfirstlane((c0 - col_begin) * 128);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) stage[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc2, voff, soff + 32 * k * 128, 0);
-    if (threadIdx.x < kM8TileCols) {
-      const int c = c0 + (int)threadIdx.x;
-      stage_term = kM8Masked;
-      if (c < col_end) {
-        const int2 s = *reinterpret_cast<const int2 *>(sums2 + 2 * (size_t)c);
-        stage_term = m8_col_term<kL2>(s.x, s.y);
-      }
-    }
-  };
-  fetch(col_begin);
-  int par = 0;
-  for (int c0 = col_begin; c0 < col_end; c0 += kM8TileCols, par ^= 1) {
-    // buffer `par` was last read two tiles ago, in front of the previous tile's barrier
-    unsigned char *buf = sB + par * (kM8TileCols * kM8Stride);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int c = threadIdx.x + 256 * k;
-      u4 v = stage[k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] ^= 0x80808080u;
-      *reinterpret_cast<u4 *>(buf + (c >> 3) * kM8Stride + 16 * (c & 7)) = v;
-    }
-    if (threadIdx.x < kM8TileCols) *reinterpret_cast<int *>(buf + threadIdx.x * kM8Stride + 128) = stage_term;
-    __syncthreads();
-    if (c0 + kM8TileCols < col_end) fetch(c0 + kM8TileCols);  // in flight while this tile is multiplied
-    if constexpr (Cols::kOn)
-      if (c0 > col_begin) m8_cols_drain<kL2>(cols, sums2, c0 - kM8TileCols, col_end, par ^ 1, lane, wv);
-
-    const unsigned char *bcol = buf + r * kM8Stride + 16 * g;
-#pragma unroll
-    for (int t = 0; t < kM8TileCols / 16; ++t) {
-      const i32x4 b0 = *reinterpret_cast<const i32x4 *>(bcol + 16 * t * kM8Stride);
-      const i32x4 b1 = *reinterpret_cast<const i32x4 *>(bcol + 16 * t * kM8Stride + 64);
-      const int term = *reinterpret_cast<const int *>(buf + (16 * t + r) * kM8Stride + 128);
-      const int p2 = c0 + 16 * t + r;
-      i32x4 acc[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc[i] = i32x4{0, 0, 0, 0};
-        acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i][0], b0, acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i][1], b1, acc[i], 0, 0, 0);
-      }
-      // acc[i][j] = S' of row 16 i + 4 g + j and column p2
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int v = kL2 ? term - 2 * acc[i][j] : term - acc[i][j];
-          const int old = best[i][j];
-          best[i][j] = min(old, v);
-          second[i][j] = med3i(old, second[i][j], v);
-          bidx[i][j] = v < old ? p2 : bidx[i][j];
-        }
-      if constexpr (Cols::kOn) {
-        unsigned cb = 0u, cs = 0u;  // cs <= cb
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const unsigned w = ((unsigned)acc[i][j] << (kL2 ? 7 : 6)) + cterm[i][j];
-            const unsigned old = cb;
-            cb = max(old, w);
-            cs = umed3(old, cs, w);  // the second largest of the three
-          }
-#pragma unroll
-        for (int d = 16; d <= 32; d <<= 1) {  // the four g groups of column p2
-          const unsigned ob = __shfl_xor(cb, d);
-          const unsigned os = __shfl_xor(cs, d);
-          cs = max(min(cb, ob), max(cs, os));
-          cb = max(cb, ob);
-        }
-        if (g == 0) cols.buf[(par * 4 + wv) * kM8TileCols + 16 * t + r] = uint2{cb, cs};
-      }
-    }
-  }
-  if constexpr (Cols::kOn) {  // the last tile's columns
-    __syncthreads();
-    m8_cols_drain<kL2>(cols, sums2, col_begin + (col_end - col_begin - 1) / kM8TileCols * kM8TileCols, col_end, par ^ 1, lane,
-                       wv);
-  }
-  // the tree over the 16 lanes of a row; lane r == 0 of group g ends with rows 16 i + 4 g + j
-#pragma unroll
-  for (int len = 8; len > 0; len >>= 1)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int ob = __shfl_down(best[i][j], len, 16);
-        const int os = __shfl_down(second[i][j], len, 16);
-        const int oi = __shfl_down(bidx[i][j], len, 16);
-        if (r < len) m8_merge(best[i][j], second[i][j], bidx[i][j], ob, os, oi);
-      }
-  if (r == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int p1 = p1_base + 16 * i + 4 * g + j;
-        if (p1 >= n1) continue;
-        const int2 s = *reinterpret_cast<const int2 *>(sums1 + 2 * (size_t)p1);
-        const int rt = m8_row_term<kL2>(s.x, s.y);
-        // a real column's key' is below 2^23 in magnitude; "none" stays none
-        out(p1, best[i][j] + rt, second[i][j] >= kM8None ? kM8Init : second[i][j] + rt, bidx[i][j]);
-      }
-  }
-}
 
 // One pair.  grid (row blocks, column splits).  partials == NULL (one split): the five fields are final; otherwise
 // partials[split][n1_pad] and match8_merge_kernel folds them.
@@ -598,13 +299,14 @@ static int check_tables8(const char *who, const unsigned char *d_q, const int *d
 
 // The matcher of one pair: one launch, plus the row-side merge when the columns are split.  d_back != NULL
 // (cusift_match8_mutual): image 2's records again, to receive the column side, merged when there are several row blocks.
-// Both counts >= 1, the arguments are checked.
+// guide != NULL (cusift_match8_guided, cusift_match8_projected, never with d_back): the guided kernel, its model a kernel
+// argument, and the none-aware merge.  Both counts >= 1, the arguments are checked.
 static int match8_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
                          const int *d_sums1, const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2,
-                         const int *d_sums2, int distance, cusift_point *d_back) {
+                         const int *d_sums2, int distance, cusift_point *d_back, const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(num_pts1, kM8RowsPerBlock);
   int splits, cols_per_split;
-  TRY(matcher_split_plan(ctx, kMatcher8, num_pts1, num_pts2, 1, &splits, &cols_per_split));
+  TRY(matcher_split_plan(ctx, guide ? kMatcher8Guided : kMatcher8, num_pts1, num_pts2, 1, &splits, &cols_per_split));
   const int n1_pad = row_blocks * kM8RowsPerBlock;
   Match8Partial *partials = nullptr, *col_partials = nullptr;
   if (splits > 1) {
@@ -621,11 +323,29 @@ static int match8_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, c
     hipLaunchKernelGGL(distance ? match8_mutual_kernel<true> : match8_mutual_kernel<false>, dim3(row_blocks, splits),
                        dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_q1, d_sums1, d_back, num_pts2, d_q2, d_sums2,
                        cols_per_split, partials, n1_pad, col_partials);
-  else
+  else if (guide && guide->camera) {
+    const auto kernel = distance ? match8_guided_kernel<true, M8GuideP, ProjectModel> : match8_guided_kernel<false, M8GuideP, ProjectModel>;
+    hipLaunchKernelGGL(kernel, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_q1, d_sums1,
+                       d_sift2, num_pts2, d_q2, d_sums2, cols_per_split, partials, n1_pad,
+                       project_model(guide->h_models, *guide->camera), guide->r2);
+  } else if (guide) {
+    GuideModel model;
+    memcpy(model.m, guide->h_models, sizeof(model.m));
+    const auto kernel =
+        guide->model == CUSIFT_GUIDE_EPIPOLAR
+            ? (distance ? match8_guided_kernel<true, M8GuideF, GuideModel> : match8_guided_kernel<false, M8GuideF, GuideModel>)
+            : (distance ? match8_guided_kernel<true, M8GuideH, GuideModel> : match8_guided_kernel<false, M8GuideH, GuideModel>);
+    hipLaunchKernelGGL(kernel, dim3(row_blocks, splits), dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_q1, d_sums1,
+                       d_sift2, num_pts2, d_q2, d_sums2, cols_per_split, partials, n1_pad, model, guide->r2);
+  } else
     hipLaunchKernelGGL(distance ? match8_kernel<true> : match8_kernel<false>, dim3(row_blocks, splits), dim3(256), 0,
                        ctx->stream, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, cols_per_split,
                        partials, n1_pad);
-  if (splits > 1)
+  if (splits > 1 && guide)
+    hipLaunchKernelGGL(distance ? match8_guided_merge_kernel<true> : match8_guided_merge_kernel<false>,
+                       dim3(idiv_up(num_pts1, 256)), dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2,
+                       (const Match8Partial *)partials, n1_pad, splits);
+  else if (splits > 1)
     hipLaunchKernelGGL(distance ? match8_merge_kernel<true> : match8_merge_kernel<false>, dim3(idiv_up(num_pts1, 256)),
                        dim3(256), 0, ctx->stream, d_sift1, num_pts1, d_sift2, num_pts2,
                        (const Match8Partial *)partials, n1_pad, splits);
@@ -633,7 +353,7 @@ static int match8_launch(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, c
     hipLaunchKernelGGL(distance ? match8_mutual_merge_kernel<true> : match8_mutual_merge_kernel<false>,
                        dim3(idiv_up(num_pts2, 256)), dim3(256), 0, ctx->stream, d_back, num_pts2,
                        (const cusift_point *)d_sift1, num_pts1, (const Match8Partial *)col_partials, row_blocks);
-  return check_launch(d_back ? "match8_mutual" : "match8");
+  return check_launch(d_back ? "match8_mutual" : guide ? (guide->camera ? "match8_projected" : "match8_guided") : "match8");
 }
 
 extern "C" int cusift_match8(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
@@ -662,20 +382,61 @@ extern "C" int cusift_match8_mutual(cusift_ctx *ctx, cusift_point *d_sift1, int 
   return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, d_sift2);
 }
 
+// cusift_match8 where only the columns that pass the geometric test against a row count for it: cusift_match8's refusals,
+// then cusift_match_guided's / cusift_match_projected's.
+static int check_pair8(const char *who, const cusift_point *d_sift1, const unsigned char *d_q1, const int *d_sums1,
+                       const cusift_point *d_sift2, const unsigned char *d_q2, const int *d_sums2, int distance) {
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "%s: missing data", who);
+  TRY(check_tables8(who, d_q1, d_sums1));
+  TRY(check_tables8(who, d_q2, d_sums2));
+  return check_distance(who, distance);
+}
+
+extern "C" int cusift_match8_guided(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
+                                    const int *d_sums1, const cusift_point *d_sift2, int num_pts2,
+                                    const unsigned char *d_q2, const int *d_sums2, int distance, int model,
+                                    const double h_model[9], float radius) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match8: nothing to match
+  TRY(check_pair8("Match8Guided", d_sift1, d_q1, d_sums1, d_sift2, d_q2, d_sums2, distance));
+  TRY(check_guide("Match8Guided", model, h_model, radius));
+  const GuideCall guide{model, radius * radius, h_model};
+  return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, nullptr, &guide);
+}
+
+extern "C" int cusift_match8_projected(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
+                                       const int *d_sums1, const cusift_point *d_sift2, int num_pts2,
+                                       const unsigned char *d_q2, const int *d_sums2, int distance, const double h_rt[12],
+                                       const cusift_camera *camera2, float radius) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match8: nothing to match
+  TRY(check_pair8("Match8Projected", d_sift1, d_q1, d_sums1, d_sift2, d_q2, d_sums2, distance));
+  TRY(check_project("Match8Projected", h_rt, camera2, radius));
+  const PnPCam cam = pnp_cam(camera2);
+  const GuideCall guide{0, radius * radius, h_rt, &cam};
+  return match8_launch(ctx, d_sift1, num_pts1, d_q1, d_sums1, d_sift2, num_pts2, d_q2, d_sums2, distance, nullptr, &guide);
+}
+
 // Uploads the pair list and enqueues the matcher of every pair: one launch, plus a merge when the columns are split and
 // -- with d_rows_back, the column side -- one more when max_pts spans several row blocks.  *d_pairs_out: the list on the
-// device.  n_pairs >= 1, max_pts >= 1, the arguments are checked.
+// device.  guide != NULL (cusift_match8_batch_guided, cusift_match8_batch_projected, never with d_rows_back): the guided
+// kernel over the frames' records d_points, its models -- GuideModel or ProjectModel [pair] -- uploaded behind the
+// partials, and the none-aware merge.  n_pairs >= 1, max_pts >= 1, the arguments are checked.
 int match8_batch_launch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_sums, const unsigned int *d_counters,
                         int max_pts, const int *h_pairs, int n_pairs, int distance, cusift_match_row *d_rows,
-                        cusift_match_row *d_rows_back, const int **d_pairs_out) {
+                        cusift_match_row *d_rows_back, const int **d_pairs_out, const cusift_point *d_points = nullptr,
+                        const GuideCall *guide = nullptr) {
   const int row_blocks = idiv_up(max_pts, kM8RowsPerBlock);
   int splits, cols_per_split;
-  TRY(matcher_split_plan(ctx, kMatcher8, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
+  TRY(matcher_split_plan(ctx, guide ? kMatcher8Guided : kMatcher8, max_pts, max_pts, n_pairs, &splits, &cols_per_split));
   const int n1_pad = row_blocks * kM8RowsPerBlock;
   const size_t list_b = align_up_sz(sizeof(int) * 2 * (size_t)n_pairs, 256);
   const size_t part_b = splits > 1 ? sizeof(Match8Partial) * (size_t)n_pairs * splits * n1_pad : 0;
   const size_t col_b = d_rows_back && row_blocks > 1 ? sizeof(Match8Partial) * (size_t)n_pairs * row_blocks * max_pts : 0;
-  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, list_b + part_b + col_b, "", false));
+  const size_t model_at = align_up_sz(list_b + part_b + col_b, 256);
+  const size_t model_b = guide ? (guide->camera ? sizeof(ProjectModel) : sizeof(GuideModel)) * (size_t)n_pairs : 0;
+  TRY(grow_scratch(ctx, ctx->pairs_scratch, ctx->pairs_scratch_bytes, guide ? model_at + model_b : list_b + part_b + col_b,
+                   "", false));
   int *d_pairs = (int *)ctx->pairs_scratch;
   Match8Partial *partials = splits > 1 ? (Match8Partial *)(ctx->pairs_scratch + list_b) : nullptr;
   Match8Partial *col_partials = col_b ? (Match8Partial *)(ctx->pairs_scratch + list_b + part_b) : nullptr;
@@ -685,10 +446,38 @@ int match8_batch_launch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_
     hipLaunchKernelGGL(distance ? match8_batch_mutual_kernel<true> : match8_batch_mutual_kernel<false>, grid, dim3(256), 0,
                        ctx->stream, d_q, d_sums, d_counters, max_pts, (const int *)d_pairs, cols_per_split, partials,
                        n1_pad, d_rows, col_partials, d_rows_back);
-  else
+  else if (guide && guide->camera) {
+    ProjectModel *d_models = (ProjectModel *)(ctx->pairs_scratch + model_at);
+    ctx->project_models.resize(n_pairs);  // stays allocated behind this call, whenever the upload reads it
+    for (int p = 0; p < n_pairs; ++p)
+      ctx->project_models[p] = project_model(guide->h_models + 12 * (size_t)p, *guide->camera);
+    HIP_TRY(hipMemcpyAsync(d_models, ctx->project_models.data(), model_b, hipMemcpyHostToDevice, ctx->stream));
+    const auto kernel =
+        distance ? match8_batch_guided_kernel<true, M8GuideP, ProjectModel> : match8_batch_guided_kernel<false, M8GuideP, ProjectModel>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, d_points, d_q, d_sums, d_counters, max_pts,
+                       (const int *)d_pairs, cols_per_split, partials, n1_pad, d_rows, (const ProjectModel *)d_models,
+                       guide->r2);
+  } else if (guide) {
+    // straight from the caller's array, as the pair list above: a copy from pageable memory is staged before
+    // hipMemcpyAsync returns, which is what "read before the call returns" rests on (cusift_match_batch_guided does the
+    // same).  The projected models are BUILT here, pose beside camera, so they need a home that outlives this frame.
+    GuideModel *d_models = (GuideModel *)(ctx->pairs_scratch + model_at);
+    HIP_TRY(hipMemcpyAsync(d_models, guide->h_models, model_b, hipMemcpyHostToDevice, ctx->stream));
+    const auto kernel =
+        guide->model == CUSIFT_GUIDE_EPIPOLAR
+            ? (distance ? match8_batch_guided_kernel<true, M8GuideF, GuideModel> : match8_batch_guided_kernel<false, M8GuideF, GuideModel>)
+            : (distance ? match8_batch_guided_kernel<true, M8GuideH, GuideModel> : match8_batch_guided_kernel<false, M8GuideH, GuideModel>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, d_points, d_q, d_sums, d_counters, max_pts,
+                       (const int *)d_pairs, cols_per_split, partials, n1_pad, d_rows, (const GuideModel *)d_models,
+                       guide->r2);
+  } else
     hipLaunchKernelGGL(distance ? match8_batch_kernel<true> : match8_batch_kernel<false>, grid, dim3(256), 0, ctx->stream,
                        d_q, d_sums, d_counters, max_pts, (const int *)d_pairs, cols_per_split, partials, n1_pad, d_rows);
-  if (splits > 1)
+  if (splits > 1 && guide)
+    hipLaunchKernelGGL(distance ? match8_batch_guided_merge_kernel<true> : match8_batch_guided_merge_kernel<false>,
+                       dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream, d_counters, max_pts,
+                       (const int *)d_pairs, cols_per_split, (const Match8Partial *)partials, n1_pad, splits, d_rows);
+  else if (splits > 1)
     hipLaunchKernelGGL(distance ? match8_batch_merge_kernel<true> : match8_batch_merge_kernel<false>,
                        dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream, d_counters, max_pts,
                        (const int *)d_pairs, cols_per_split, (const Match8Partial *)partials, n1_pad, splits, d_rows);
@@ -697,7 +486,9 @@ int match8_batch_launch(cusift_ctx *ctx, const unsigned char *d_q, const int *d_
                        dim3(idiv_up(max_pts, 256), n_pairs), dim3(256), 0, ctx->stream, d_counters, max_pts,
                        (const int *)d_pairs, (const Match8Partial *)col_partials, row_blocks, d_rows_back);
   if (d_pairs_out) *d_pairs_out = d_pairs;
-  return check_launch(d_rows_back ? "match8_batch_mutual" : "match8_batch");
+  return check_launch(d_rows_back ? "match8_batch_mutual"
+                      : guide     ? (guide->camera ? "match8_batch_projected" : "match8_batch_guided")
+                                  : "match8_batch");
 }
 
 // every refusal of the 8-bit pair-list calls; *nothing: a list or a capacity of zero
@@ -737,6 +528,39 @@ extern "C" int cusift_match8_batch_mutual(cusift_ctx *ctx, const unsigned char *
                              nullptr);
 }
 
+// cusift_match8_batch under one model per pair: the refusals of cusift_match_batch_guided / _projected -- a bad model or
+// radius is refused with an empty list too -- then cusift_match8_batch's
+extern "C" int cusift_match8_batch_guided(cusift_ctx *ctx, const cusift_point *d_points, const unsigned char *d_q,
+                                          const int *d_sums, const unsigned int *d_counters, int n_images, int max_pts,
+                                          const int *h_pairs, int n_pairs, int distance, int model,
+                                          const double *h_models, float radius, cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  bool nothing;
+  TRY(check_guide("Match8BatchGuided", model, h_models, radius));
+  TRY(check_batch8("Match8BatchGuided", d_q, d_sums, n_images, max_pts, h_pairs, n_pairs, distance, d_rows, &nothing));
+  if (nothing) return CUSIFT_OK;
+  if (!d_points) return fail(CUSIFT_ERR_INVALID, "Match8BatchGuided: missing data");
+  const GuideCall guide{model, radius * radius, h_models};
+  return match8_batch_launch(ctx, d_q, d_sums, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, nullptr, nullptr,
+                             d_points, &guide);
+}
+
+extern "C" int cusift_match8_batch_projected(cusift_ctx *ctx, const cusift_point *d_points, const unsigned char *d_q,
+                                             const int *d_sums, const unsigned int *d_counters, int n_images, int max_pts,
+                                             const int *h_pairs, int n_pairs, int distance, const double *h_rts,
+                                             const cusift_camera *camera2, float radius, cusift_match_row *d_rows) {
+  TRY(enter(ctx));
+  bool nothing;
+  TRY(check_project("Match8BatchProjected", h_rts, camera2, radius));
+  TRY(check_batch8("Match8BatchProjected", d_q, d_sums, n_images, max_pts, h_pairs, n_pairs, distance, d_rows, &nothing));
+  if (nothing) return CUSIFT_OK;
+  if (!d_points) return fail(CUSIFT_ERR_INVALID, "Match8BatchProjected: missing data");
+  const PnPCam cam = pnp_cam(camera2);
+  const GuideCall guide{0, radius * radius, h_rts, &cam};
+  return match8_batch_launch(ctx, d_q, d_sums, d_counters, max_pts, h_pairs, n_pairs, distance, d_rows, nullptr, nullptr,
+                             d_points, &guide);
+}
+
 // ---- the registrations' matcher front while cusift_ctx_set_match_bits is 8 (sift_register.hip) ---------------------------
 // The byte tables live in the context: q [n][128] on a 256-byte boundary, the sums behind them on another.
 static int tables8_scratch(cusift_ctx *ctx, size_t n, unsigned char **q, int **sums) {
@@ -747,10 +571,10 @@ static int tables8_scratch(cusift_ctx *ctx, size_t n, unsigned char **q, int **s
   return CUSIFT_OK;
 }
 
-// cusift_quantize_descriptors of both record sets, then cusift_match8 -- d_back != NULL: cusift_match8_mutual.  Counts
-// >= 1, the arguments are checked.
+// cusift_quantize_descriptors of both record sets, then cusift_match8 -- d_back != NULL: cusift_match8_mutual; guide !=
+// NULL: cusift_match8_guided or cusift_match8_projected.  Counts >= 1, the arguments are checked.
 int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2, int num_pts2,
-                        int distance, cusift_point *d_back) {
+                        int distance, cusift_point *d_back, const GuideCall *guide) {
   unsigned char *q;
   int *sums;
   const size_t n1_slots = align_up_sz((size_t)num_pts1, 32);  // keeps table 2 and its sums aligned
@@ -761,7 +585,35 @@ int match8_pair_enqueue(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, co
                      (const cusift_point *)d_sift1, (const unsigned int *)nullptr, num_pts1, q, sums);
   hipLaunchKernelGGL(quantize_kernel, dim3(idiv_up(num_pts2, 8), 1), dim3(256), 0, ctx->stream, d_sift2,
                      (const unsigned int *)nullptr, num_pts2, q2, sums2);
-  return match8_launch(ctx, d_sift1, num_pts1, q, sums, d_sift2, num_pts2, q2, sums2, distance, d_back);
+  return match8_launch(ctx, d_sift1, num_pts1, q, sums, d_sift2, num_pts2, q2, sums2, distance, d_back, guide);
+}
+
+// The second matching pass of a registration staged on bytes: a caller with records alone.
+// cusift_quantize_descriptors of both record sets into tables of the context's, then cusift_match8_guided /
+// cusift_match8_projected on them: the same bytes, the fp32 guided calls' refusals.
+extern "C" int cusift_match8_guided_records(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1,
+                                            const cusift_point *d_sift2, int num_pts2, int distance, int model,
+                                            const double h_model[9], float radius) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match_guided: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "Match8GuidedRecords: missing data");
+  TRY(check_distance("Match8GuidedRecords", distance));
+  TRY(check_guide("Match8GuidedRecords", model, h_model, radius));
+  const GuideCall guide{model, radius * radius, h_model};
+  return match8_pair_enqueue(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, nullptr, &guide);
+}
+
+extern "C" int cusift_match8_projected_records(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1,
+                                               const cusift_point *d_sift2, int num_pts2, int distance,
+                                               const double h_rt[12], const cusift_camera *camera2, float radius) {
+  TRY(enter(ctx));
+  if (num_pts1 <= 0 || num_pts2 <= 0) return CUSIFT_OK;  // as cusift_match_projected: nothing to match
+  if (!d_sift1 || !d_sift2) return fail(CUSIFT_ERR_INVALID, "Match8ProjectedRecords: missing data");
+  TRY(check_distance("Match8ProjectedRecords", distance));
+  TRY(check_project("Match8ProjectedRecords", h_rt, camera2, radius));
+  const PnPCam cam = pnp_cam(camera2);
+  const GuideCall guide{0, radius * radius, h_rt, &cam};
+  return match8_pair_enqueue(ctx, d_sift1, num_pts1, d_sift2, num_pts2, distance, nullptr, &guide);
 }
 
 // cusift_quantize_descriptors of the whole batch, then cusift_match8_batch -- d_rows_back != NULL: _batch_mutual.

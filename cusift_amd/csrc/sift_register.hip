@@ -45,24 +45,15 @@ static const double kIdentRtD[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
 // ------------------------------------------------------------------------------------------------
 // matcher
 // ------------------------------------------------------------------------------------------------
-// The geometry of a guided match (cusift_match_guided, cusift_match_batch_guided), checked: which test, the squared radius
-// and the models as the caller's host array -- one of the pair call, one per pair of the pair-list call.
-// camera != NULL (cusift_match_projected, cusift_match_batch_projected): the test is the projection of coords3D, h_models
-// holds [R | t], twelve doubles a pair, and `model` is not read.
-struct GuideCall {
-  int model;
-  float r2;
-  const double *h_models;
-  const PnPCam *camera = nullptr;
-};
-static ProjectModel project_model(const double *h_rt, const PnPCam &cam) {
+// GuideCall, the geometry of a guided match: sift_host.h (the 8-bit guided matchers share it and the four functions here)
+ProjectModel project_model(const double *h_rt, const PnPCam &cam) {
   ProjectModel pm;
   memcpy(pm.rt, h_rt, sizeof(pm.rt));
   pm.fx = cam.fx, pm.fy = cam.fy, pm.px = cam.px, pm.py = cam.py;
   return pm;
 }
 // every refusal the guided calls add to their unguided counterparts'
-static int check_guide(const char *who, int model, const double *h_models, float radius) {
+int check_guide(const char *who, int model, const double *h_models, float radius) {
   if (model != CUSIFT_GUIDE_HOMOGRAPHY && model != CUSIFT_GUIDE_EPIPOLAR)
     return fail(CUSIFT_ERR_INVALID, "%s: model must be 0 (homography) or 1 (epipolar), got %d", who, model);
   if (!h_models) return fail(CUSIFT_ERR_INVALID, "%s: NULL model", who);
@@ -912,7 +903,7 @@ static int pnp_check(const char *who, const cusift_point *d_sift, int num_pts, i
   TRY(precheck(who, d_sift, num_pts, rule, lo, hi, num_loops, thresh, refine_loops, refine_thresh, o));
   return check_pinhole(camera2, who);
 }
-static PnPCam pnp_cam(const cusift_camera *c) {
+PnPCam pnp_cam(const cusift_camera *c) {
   return PnPCam{(double)c->fx, (double)c->fy, (double)c->cx - (double)c->origin, (double)c->cy - (double)c->origin};
 }
 
@@ -1063,7 +1054,7 @@ extern "C" int cusift_match_batch_guided(cusift_ctx *ctx, const cusift_point *d_
 
 // Matching by projection (sift_match_project.hip): cusift_match / cusift_match_batch where a record of image 2 counts for
 // a row only within `radius` pixels of where the pose puts the row's coords3D.  Every refusal the two calls add:
-static int check_project(const char *who, const double *h_rts, const cusift_camera *camera2, float radius) {
+int check_project(const char *who, const double *h_rts, const cusift_camera *camera2, float radius) {
   if (!h_rts) return fail(CUSIFT_ERR_INVALID, "%s: NULL pose", who);
   if (!camera2) return fail(CUSIFT_ERR_INVALID, "%s: NULL camera", who);
   TRY(check_pinhole(camera2, who));

@@ -707,6 +707,76 @@ int cusift_match8_batch_mutual(cusift_ctx *ctx, const unsigned char *d_q, const 
                                const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
                                const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance, cusift_match_row *d_rows,
                                cusift_match_row *d_rows_back);
+/* 8-bit guided matching: cusift_match8 with one more rule -- the geometric predicate of cusift_match_guided (H or F) or of
+ * cusift_match_projected (a pose and coords3D), evaluated inside the int8 matcher's update.  The second matching pass of a
+ * registration, and a tracker's search against a map, for callers who keep bytes.
+ * THE TEST is cusift_match_guided's for `model` = CUSIFT_GUIDE_HOMOGRAPHY / CUSIFT_GUIDE_EPIPOLAR and
+ * cusift_match_projected's for the projected call: exactly the expressions pinned there -- fp64 per row, fp32 per pair,
+ * the same parenthesisation, the same conventions, -ffp-contract=off -- on x1 = coords2D (X1 = coords3D) of RECORD i of
+ * d_sift1 and x2 = coords2D of RECORD j of d_sift2.  The coordinates come from the records, the descriptors from the
+ * tables: row i is d_q1[i], column j is d_q2[j], as in cusift_match8.  A NaN anywhere is no pass.
+ * THE RESULT, over the set P(i) of the columns that pass against row i, with cusift_match8's exact integer keys (D for
+ * distance 1, -S for distance 0) and its scores:
+ *     match  = the LOWEST column of the passing set P(i) with the smallest key;   score = that column's score;
+ *     second = the score of the second smallest key of the multiset {key(i, j) : j in P(i)}, so a tied best among the
+ *              passing columns gives second == best;
+ *     EXACTLY ONE passing column: second = cusift_match's initial value, 999 for distance 1 and -1 for distance 0 (a
+ *              tiny ambiguity: the only compatible partner, as cusift_match_guided says);
+ *     NO COLUMN PASSES: match = -1, score = the initial value, the ambiguity that two initial values give (999 / (999 +
+ *              1e-6), or 2 / (2 + 1e-6)) and match_xpos / match_ypos of record 0 -- exactly as cusift_match_guided
+ *              documents;
+ *     ambiguity, match_xpos, match_ypos otherwise: cusift_match8's expressions on (score, second) and coords2D of
+ *              d_sift2[match].
+ * A column that fails changes nothing for that row, whatever its key and its index: a failing column with a smaller or
+ * an equal key than the winner, below or above it, is as if it were not there.  The same input gives the same bytes under
+ * every CUSIFT_POLICY_MATCH_SPLITS -- a row whose passing columns all lie in one split, or in none, included; there are
+ * no atomics.  With a radius that every pair passes (1e6 on finite coordinates under a mild model; +infinity, which is
+ * legal) the bytes are cusift_match8's.
+ * Writes the five fields cusift_match8 writes and nothing else; the records' coords2D and coords3D are read, never
+ * written.  A count <= 0 on either side: CUSIFT_OK, nothing enqueued, nothing written.  CUSIFT_ERR_INVALID (nothing
+ * enqueued, nothing written): every case of cusift_match8, and every case cusift_match_guided (an unknown model, a NULL
+ * h_model, radius not > 0, NaN included) or cusift_match_projected (a NULL h_rt or camera2, a camera that
+ * cusift_estimate_pnp refuses, radius not > 0) adds.  A model or a pose that is not finite is no error: it passes
+ * nothing, and every row gets the "no column passes" answer.  h_model / h_rt / camera2 are read before the call returns.
+ * Asynchronous on the context's stream; scratch as cusift_match8. */
+int cusift_match8_guided(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1, const int *d_sums1,
+                         const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2, const int *d_sums2,
+                         int distance, int model, const double h_model[9], float radius);
+int cusift_match8_projected(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const unsigned char *d_q1,
+                            const int *d_sums1, const cusift_point *d_sift2, int num_pts2, const unsigned char *d_q2,
+                            const int *d_sums2, int distance, const double h_rt[12], const struct cusift_camera *camera2,
+                            float radius);
+/* The same two over a pair list: cusift_match8_batch with cusift_match8_guided's / cusift_match8_projected's rule, pair p
+ * under h_models[9 p .. 9 p + 8] or h_rts[12 p .. 12 p + 11] -- one kind of model, one camera and one radius for the list.
+ * d_points[n_images][max_pts] are the records the tables were quantised from: the test reads coords2D (coords3D of the
+ * pair's first frame) there, the tables carry only bytes; the records are const and are never written.  d_rows[p *
+ * max_pts + i] = score, ambiguity and match exactly as the pair call writes them for pair p's records and tables; rows
+ * past frame 1's count are not written, a pair whose frame 2 is empty writes no row, (a, a) is legal.  The models are host
+ * memory, read before the call returns; the device copy lives in the context's scratch.
+ * CUSIFT_ERR_INVALID (nothing enqueued, nothing written): every case of cusift_match8_batch and of cusift_match_batch_guided
+ * / cusift_match_batch_projected -- the model, pose, camera and radius are checked for an empty list too -- and a NULL
+ * d_points with a list and a capacity that are not zero. */
+int cusift_match8_batch_guided(cusift_ctx *ctx, const cusift_point *d_points, const unsigned char *d_q, const int *d_sums,
+                               const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                               const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance, int model,
+                               const double *h_models /* [n_pairs][9] */, float radius, cusift_match_row *d_rows);
+int cusift_match8_batch_projected(cusift_ctx *ctx, const cusift_point *d_points, const unsigned char *d_q, const int *d_sums,
+                                  const unsigned int *d_counters /* or NULL */, int n_images, int max_pts,
+                                  const int *h_pairs /* [n_pairs][2] */, int n_pairs, int distance,
+                                  const double *h_rts /* [n_pairs][12] */, const struct cusift_camera *camera2, float radius,
+                                  cusift_match_row *d_rows);
+/* The pair calls for a caller with records alone (the second matching pass of a guided registration on bytes: a
+ * cusift_register_* call while cusift_ctx_set_match_bits is 8, one of these under its model, the cusift_estimate_* call --
+ * what the Python chains register_*_guided(match8=True) run):
+ * cusift_quantize_descriptors of both record sets into tables in the context's scratch,
+ * then cusift_match8_guided / cusift_match8_projected on them -- the same bytes as that staged route on tables of the
+ * caller's.  Refusals and empty counts: cusift_match_guided's / cusift_match_projected's.  Three launches (four with
+ * split columns), asynchronous. */
+int cusift_match8_guided_records(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                 int num_pts2, int distance, int model, const double h_model[9], float radius);
+int cusift_match8_projected_records(cusift_ctx *ctx, cusift_point *d_sift1, int num_pts1, const cusift_point *d_sift2,
+                                    int num_pts2, int distance, const double h_rt[12], const struct cusift_camera *camera2,
+                                    float radius);
 
 /* cusift_register_rgbd for every pair of a list, device-resident from the extractor's batch + depth images to one
  * [R | t] per pair: ONE cusift_lift_depth over all frames (frame k's depth image at d_depth + k * image_stride_elems),

@@ -21,25 +21,19 @@ typedef struct {
   float error;
 } SiftMatch;
 
-// Exhaustive search between all SIFT keypoints of two images (the caller owns the returned SiftMatch objects,
-// as in the reference).  Both SiftData need host AND device buffers, as in the reference.
-inline std::vector<SiftMatch *> MatchSiftData(SiftData &data1, SiftData &data2,
-                                              MatchSiftDistance distance = MatchSiftDistanceL2,
-                                              float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
-                                              MatchType type = MatchType2D) {
+namespace cusift_dropin {
+// What every MatchSiftData variant does behind its matcher: the five match fields of data1's records back to the host
+// (extras/matching.cu:311-315; without a host copy: a synchronisation and no matches), then MatchSiftData's
+// threshold filter.
+inline std::vector<SiftMatch *> read_back_matches(cusift_ctx *ctx, SiftData &data1, SiftData &data2, float scoreThreshold,
+                                                  float ambiguityThreshold, MatchType type) {
   std::vector<SiftMatch *> matches;
-  if (!data1.numPts || !data2.numPts) return matches;
-  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
-  cusift_ctx *ctx = cusift_dropin::ctx();
-  safeCall(cusift_match(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
-                        reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
-                        distance == MatchSiftDistanceL2 ? 1 : 0));
-  if (data1.h_data != nullptr)  // the 5 match fields of every record, extras/matching.cu:311-315
-    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
-                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
-  else
+  if (data1.h_data == nullptr) {
     safeCall(cusift_ctx_synchronize(ctx));
-  if (data1.h_data == nullptr) return matches;
+    return matches;
+  }
+  safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score, sizeof(SiftPoint),
+                               5 * sizeof(float), (size_t)data1.numPts));
   const float thresh2 = scoreThreshold * scoreThreshold;
   const float athresh2 = ambiguityThreshold * ambiguityThreshold;
   for (int i = 0; i < data1.numPts; i++) {
@@ -58,6 +52,23 @@ inline std::vector<SiftMatch *> MatchSiftData(SiftData &data1, SiftData &data2,
   }
   return matches;
 }
+}  // namespace cusift_dropin
+
+// Exhaustive search between all SIFT keypoints of two images (the caller owns the returned SiftMatch objects,
+// as in the reference).  Both SiftData need host AND device buffers, as in the reference.
+inline std::vector<SiftMatch *> MatchSiftData(SiftData &data1, SiftData &data2,
+                                              MatchSiftDistance distance = MatchSiftDistanceL2,
+                                              float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                              MatchType type = MatchType2D) {
+  std::vector<SiftMatch *> matches;
+  if (!data1.numPts || !data2.numPts) return matches;
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return matches;
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
+                        reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
+                        distance == MatchSiftDistanceL2 ? 1 : 0));
+  return cusift_dropin::read_back_matches(ctx, data1, data2, scoreThreshold, ambiguityThreshold, type);
+}
 
 // MatchSiftData under a model that is already known (not in the reference): cusift_match_guided() instead of
 // cusift_match() -- a record of data2 whose coords2D fail the test against a record of data1 cannot be its match.  model:
@@ -75,29 +86,7 @@ inline std::vector<SiftMatch *> MatchSiftDataGuided(SiftData &data1, SiftData &d
   safeCall(cusift_match_guided(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
                                reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
                                distance == MatchSiftDistanceL2 ? 1 : 0, model, M, radius));
-  if (data1.h_data != nullptr)  // the 5 match fields of every record, extras/matching.cu:311-315
-    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
-                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
-  else
-    safeCall(cusift_ctx_synchronize(ctx));
-  if (data1.h_data == nullptr) return matches;
-  const float thresh2 = scoreThreshold * scoreThreshold;
-  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
-  for (int i = 0; i < data1.numPts; i++) {
-    SiftPoint &p = data1.h_data[i];
-    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
-    if (p.match < 0 || p.match >= data2.numPts || data2.h_data == nullptr) continue;
-    if (type == MatchType2D || (p.coords3D[2] != 0 && data2.h_data[p.match].coords3D[2] != 0)) {
-      SiftMatch *m = new SiftMatch();
-      m->pt1 = &p;
-      m->pt2 = &data2.h_data[p.match];
-      m->score = p.score;
-      m->ambiguity = p.ambiguity;
-      m->error = 0.0f;
-      matches.push_back(m);
-    }
-  }
-  return matches;
+  return cusift_dropin::read_back_matches(ctx, data1, data2, scoreThreshold, ambiguityThreshold, type);
 }
 
 // MatchSiftData with the cross-check (not in the reference): one cusift_match_mutual() fills the match fields of BOTH
@@ -208,29 +197,26 @@ inline std::vector<SiftMatch *> MatchSiftData8(SiftData &data1, SiftDescriptors8
   safeCall(cusift_match8(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts, desc1.d_data, desc1.d_sums,
                          reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts, desc2.d_data, desc2.d_sums,
                          distance == MatchSiftDistanceL2 ? 1 : 0));
-  if (data1.h_data != nullptr)  // the 5 match fields of every record, as MatchSiftData
-    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
-                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
-  else
-    safeCall(cusift_ctx_synchronize(ctx));
-  if (data1.h_data == nullptr) return matches;
-  const float thresh2 = scoreThreshold * scoreThreshold;
-  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
-  for (int i = 0; i < data1.numPts; i++) {
-    SiftPoint &p = data1.h_data[i];
-    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
-    if (p.match < 0 || p.match >= data2.numPts || data2.h_data == nullptr) continue;
-    if (type == MatchType2D || (p.coords3D[2] != 0 && data2.h_data[p.match].coords3D[2] != 0)) {
-      SiftMatch *m = new SiftMatch();
-      m->pt1 = &p;
-      m->pt2 = &data2.h_data[p.match];
-      m->score = p.score;
-      m->ambiguity = p.ambiguity;
-      m->error = 0.0f;
-      matches.push_back(m);
-    }
-  }
-  return matches;
+  return cusift_dropin::read_back_matches(ctx, data1, data2, scoreThreshold, ambiguityThreshold, type);
+}
+
+// MatchSiftDataGuided on the byte descriptors (cusift_match8_guided): MatchSiftData8 where a record of data2 whose coords2D
+// fail the test of `model` under M against a record of data1 cannot be its match -- the same test, evaluated on the
+// records' coordinates inside the int8 matcher.  A record that nothing passes has match == -1 and is not returned.  The
+// same filter, the same return type.
+inline std::vector<SiftMatch *> MatchSiftData8Guided(SiftData &data1, SiftDescriptors8 &desc1, SiftData &data2,
+                                                     SiftDescriptors8 &desc2, int model, const double M[9], float radius,
+                                                     MatchSiftDistance distance = MatchSiftDistanceL2,
+                                                     float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                                     MatchType type = MatchType2D) {
+  if (!data1.numPts || !data2.numPts) return {};
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return {};
+  if (desc1.numPts != data1.numPts || desc2.numPts != data2.numPts) return {};  // not the descriptors of these sets
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match8_guided(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts, desc1.d_data,
+                                desc1.d_sums, reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
+                                desc2.d_data, desc2.d_sums, distance == MatchSiftDistanceL2 ? 1 : 0, model, M, radius));
+  return cusift_dropin::read_back_matches(ctx, data1, data2, scoreThreshold, ambiguityThreshold, type);
 }
 
 // MatchSiftData8 with the cross-check (cusift_match8_mutual: both directions from one pass over the integer scores): the

@@ -75,29 +75,27 @@ inline std::vector<SiftMatch *> MatchSiftDataProjected(SiftData &data1, SiftData
   safeCall(cusift_match_projected(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts,
                                   reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
                                   distance == MatchSiftDistanceL2 ? 1 : 0, Rt, camera2, radius));
-  if (data1.h_data != nullptr)  // the 5 match fields of every record, extras/matching.cu:311-315
-    safeCall(cusift_memcpy2d_d2h(ctx, &data1.h_data[0].score, sizeof(SiftPoint), &data1.d_data[0].score,
-                                 sizeof(SiftPoint), 5 * sizeof(float), (size_t)data1.numPts));
-  else
-    safeCall(cusift_ctx_synchronize(ctx));
-  if (data1.h_data == nullptr) return matches;
-  const float thresh2 = scoreThreshold * scoreThreshold;
-  const float athresh2 = ambiguityThreshold * ambiguityThreshold;
-  for (int i = 0; i < data1.numPts; i++) {
-    SiftPoint &p = data1.h_data[i];
-    if (!(p.score < thresh2 && p.ambiguity < athresh2)) continue;
-    if (p.match < 0 || p.match >= data2.numPts || data2.h_data == nullptr) continue;
-    if (type == MatchType2D || (p.coords3D[2] != 0 && data2.h_data[p.match].coords3D[2] != 0)) {
-      SiftMatch *m = new SiftMatch();
-      m->pt1 = &p;
-      m->pt2 = &data2.h_data[p.match];
-      m->score = p.score;
-      m->ambiguity = p.ambiguity;
-      m->error = 0.0f;
-      matches.push_back(m);
-    }
-  }
-  return matches;
+  return cusift_dropin::read_back_matches(ctx, data1, data2, scoreThreshold, ambiguityThreshold, type);
+}
+
+// MatchSiftDataProjected on the byte descriptors (cusift_match8_projected): MatchSiftData8 (matching.h) where a record of
+// data2 counts for a record of data1 only within `radius` pixels of where Rt and camera2 put that record's coords3D -- the
+// same test, evaluated on the records' coordinates inside the int8 matcher.  The same filter, the same return type.
+inline std::vector<SiftMatch *> MatchSiftData8Projected(SiftData &data1, SiftDescriptors8 &desc1, SiftData &data2,
+                                                        SiftDescriptors8 &desc2, const double Rt[12],
+                                                        const cusift_camera *camera2, float radius,
+                                                        MatchSiftDistance distance = MatchSiftDistanceL2,
+                                                        float scoreThreshold = 999.0, float ambiguityThreshold = 1.0,
+                                                        MatchType type = MatchType2D) {
+  if (!data1.numPts || !data2.numPts) return {};
+  if (data1.d_data == nullptr || data2.d_data == nullptr) return {};
+  if (desc1.numPts != data1.numPts || desc2.numPts != data2.numPts) return {};  // not the descriptors of these sets
+  cusift_ctx *ctx = cusift_dropin::ctx();
+  safeCall(cusift_match8_projected(ctx, reinterpret_cast<cusift_point *>(data1.d_data), data1.numPts, desc1.d_data,
+                                   desc1.d_sums, reinterpret_cast<const cusift_point *>(data2.d_data), data2.numPts,
+                                   desc2.d_data, desc2.d_sums, distance == MatchSiftDistanceL2 ? 1 : 0, Rt, camera2,
+                                   radius));
+  return cusift_dropin::read_back_matches(ctx, data1, data2, scoreThreshold, ambiguityThreshold, type);
 }
 
 // RegisterPnP for a whole sequence in one call (cusift_register_pnp_batch): pair k = (a, b) of `pairs` gives
